@@ -14,7 +14,16 @@ HBM, followed by the path's one exchange: an all-gather of the per-object class-
 contiguous per-rank shards (shard.shard_range; the reference loops over the objects serially, eval_classification.cpp:347-356),
 so the total work is fixed as N grows: STRONG scaling. value = objects classified by all ranks / max-over-ranks time.
 
-The JSON line also carries
+A plain run only sets up (the synthetic inputs are generated in worker processes before the GPU is touched), warms up, times
+--steps steps and prints the JSON line: metric, value, unit, ms_per_step (wall time of one timed step), dtype, the workload.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (float32 / float64): the gathered per-object
+records (object_id, predicted_class, class_score) and every model's maxima of this rank's objects ([model<m>_]maxima_<field>,
+what Recognizer.detect returns, launches concatenated; file suffix .rank<r> when N > 1). The inputs are a pure function of the
+arguments, so two builds can be compared output for output; above 64 MB in all, every array keeps a seeded sample of objects.
+
+--full adds everything else the benchmark measures and checks (per-kernel HIP-event timers in the timed region, one extra
+untimed pass for the roofline figures, the PCIe-inclusive leg, the CPU baseline, accuracy_last_step). The JSON line then also
+carries
   roofline      : the dominant kernel (k_knn_l2_ring16, the f16-MFMA candidate stage of the exact kNN, MFMA-bound): algorithmic
                   flop (2 * queries * codewords * 352) / launch time, measured with HIP events on the stream the kernel runs on
                   (ismhip timers), vs the dense F16/BF16 MFMA peak
@@ -31,6 +40,7 @@ The JSON line also carries
 import argparse
 import glob
 import json
+import multiprocessing
 import os
 import socket
 import subprocess
@@ -57,11 +67,14 @@ def parse_args(argv=None):
     ap.add_argument("--objects", type=int, default=0, help="objects of the test split classified per step by ALL ranks together (0 = the config's default; 908 for config 1)")
     ap.add_argument("--batch", type=int, default=1024, help="largest launch: a rank's shard is processed in chunks of at most this many objects (the 908-object split is one launch)")
     ap.add_argument("--train-per-class", type=int, default=0, help="training objects per class (0 = the config's default)")
-    ap.add_argument("--cpu-objects", type=int, default=24, help="objects of the bounded CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel timers, rooflines, "
+                    "the PCIe-inclusive leg, the CPU baseline, accuracy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--cpu-objects", type=int, default=24, help="objects of the bounded CPU-baseline sample (0 = skip; --full only)")
     ap.add_argument("--points", type=int, default=0)
     ap.add_argument("--keypoints", type=int, default=0)
     ap.add_argument("--classes", type=int, default=0)
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive (value_end_to_end) leg")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive (value_end_to_end) leg of --full")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="torch.distributed backend of the N > 1 run (nccl = RCCL; gloo only for --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="FUNCTIONAL run of the N > 1 path on one GPU: every rank uses cuda:0 (needs --backend gloo: "
                     "RCCL refuses two ranks on one device); exercises spawn -> shard -> per-rank training -> gather, measures nothing")
@@ -155,6 +168,63 @@ def latest_traffic_json(config=1):
     return None, None
 
 
+def _gen_object(job):
+    ds, i = job
+    return ds.get(i)
+
+
+class _Generated:
+    """stands in for a synthetic.Dataset inside Dataset.batch: get(i) returns the object generated already"""
+
+    def __init__(self, with_color, objs):
+        self.with_color, self.objs = with_color, objs
+
+    def get(self, i):
+        return self.objs[i]
+
+
+def generate_batches(synthetic, jobs, pool):
+    """[(dataset, ids), ...] -> [dataset.batch(ids), ...], the objects made by `pool` (forked workers; None = here). Every object
+    is a pure function of its seeds, so the arrays are those of the serial dataset.batch(ids)."""
+    keys = [(ds, i) for ds, ids in jobs for i in ids]
+    objs = pool.map(_gen_object, keys, chunksize=4) if pool is not None else [_gen_object(k) for k in keys]
+    out, n = [], 0
+    for ds, ids in jobs:
+        out.append(synthetic.Dataset.batch(_Generated(ds.with_color, dict(zip(ids, objs[n:n + len(ids)]))), ids))
+        n += len(ids)
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records, keep, n_objects, lo, rank, world):
+    """--dump-outputs: the last timed step's results as .npy files, floats as float32 and integers as float64 (exact). rank 0 writes
+    the gathered records (object_id, predicted_class, class_score); every rank writes its models' maxima (launches concatenated,
+    rows = objects lo, lo + 1, ...). Above DUMP_LIMIT_BYTES every array keeps the objects of a prefix of one seeded permutation."""
+    import torch
+    arrays = {}
+    if rank == 0:
+        oi, best, sc = records
+        arrays.update(object_id=oi, predicted_class=best, class_score=sc)
+    n_models = len(keep[0])
+    sfx = "" if world == 1 else f".rank{rank}"
+    for m in range(n_models):
+        pre = "maxima_" if n_models == 1 else f"model{m}_maxima_"
+        for k, v in keep[0][m].items():
+            if isinstance(v, torch.Tensor):
+                arrays[pre + k + sfx] = torch.cat([outs[m][k] for outs in keep])
+    arrays = {k: v.cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        ids = np.sort(np.random.default_rng(0).permutation(n_objects)[:int(n_objects * DUMP_LIMIT_BYTES / total)])
+        arrays = {k: a[ids] if k in ("object_id", "predicted_class", "class_score") else a[ids[(ids >= lo) & (ids < lo + len(a))] - lo]
+                  for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     args = parse_args()
     launched = "RANK" in os.environ and "MASTER_ADDR" in os.environ        # started by torch.distributed.run
@@ -167,9 +237,40 @@ def main():
         sys.stderr.write(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; start one rank per GPU\n")
         sys.exit(2)
 
+    import __graft_entry__ as ge
+    pkg = ge.load_package()
+    capi, pipeline, synthetic, shard = pkg.capi, pkg.pipeline, pkg.synthetic, pkg.shard
+    cdef = CONFIGS[args.config]
+    C = args.classes or cdef["classes"]
+    G = args.objects or cdef["objects"]
+    n_points = args.points or cdef["points"]
+    n_kp = args.keypoints or cdef["keypoints"]
+    tpc = args.train_per_class or cdef["train_per_class"]
+    ds_kw = dict(cdef.get("dataset", {}))
+    if n_kp:
+        ds_kw["n_keypoints"] = n_kp
+
+    # ---- host inputs: the training split (replicated per rank) and this rank's shard of the fixed test split, generated by forked
+    # workers (at most 16 CPUs in all, shared by the ranks) BEFORE this process touches the GPU
+    n_train = tpc * C
+    train = synthetic.Dataset(C, n_train, split=0, n_points=n_points, **ds_kw)
+    order = sorted(range(n_train), key=lambda i: (train.label(i), i))
+    test = synthetic.Dataset(C, G, split=1, n_points=n_points, **ds_kw)
+    lo, hi, pad, bounds = plan_shard(G, rank, world, args.batch)
+    assert (lo, hi) == shard.shard_range(G, rank, world)
+    test_ids = [list(range(bounds[j], bounds[j + 1])) for j in range(len(bounds) - 1) if bounds[j + 1] > bounds[j]]
+    workers = max(1, min(16, len(os.sched_getaffinity(0))) // world)
+    pool = multiprocessing.get_context("fork").Pool(workers) if workers > 1 else None
+    t0 = time.time()
+    train_h = generate_batches(synthetic, [(train, order[s:s + 32]) for s in range(0, n_train, 32)], pool)
+    t_train_gen = time.time() - t0
+    chunks_h = generate_batches(synthetic, [(test, ids) for ids in test_ids], pool)
+    if pool is not None:
+        pool.close()
+        pool.join()
+
     import torch
     import torch.distributed as dist
-    import __graft_entry__ as ge
 
     assert torch.cuda.is_available(), "bench.py needs an MI355X; the hot path has no CPU fallback"
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -190,26 +291,13 @@ def main():
             dist.init_process_group("gloo")
         assert dist.get_world_size() == world
 
-    pkg = ge.load_package()
-    capi, pipeline, synthetic, shard = pkg.capi, pkg.pipeline, pkg.synthetic, pkg.shard
     ctx = capi.Ctx(dev_index)             # on torch's current stream
-    cdef = CONFIGS[args.config]
-    C = args.classes or cdef["classes"]
-    G = args.objects or cdef["objects"]
-    n_points = args.points or cdef["points"]
-    n_kp = args.keypoints or cdef["keypoints"]
-    tpc = args.train_per_class or cdef["train_per_class"]
-    ds_kw = dict(cdef.get("dataset", {}))
-    if n_kp:
-        ds_kw["n_keypoints"] = n_kp
 
     # ---- models: codebooks trained the reference's way from the synthetic training split (replicated per rank)
     t0 = time.time()
-    n_train = tpc * C
-    train = synthetic.Dataset(C, n_train, split=0, n_points=n_points, **ds_kw)
-    order = sorted(range(n_train), key=lambda i: (train.label(i), i))
     recs, cbs, cfgs = [], [], []
-    tb = [pipeline.DeviceBatch(train.batch(order[s:s + 32]), dev) for s in range(0, n_train, 32)]
+    tb = [pipeline.DeviceBatch(b, dev) for b in train_h]
+    del train_h
     ctxs = []
     for mi, m in enumerate(cdef["models"]):
         cfg = pipeline.IsmConfig(k=1, n_classes=C, max_maxima=16, **m)
@@ -220,21 +308,11 @@ def main():
         recs.append(rec); cfgs.append(cfg)
     del tb
     n_words = [int(cb["words"].shape[0]) for cb in cbs]
-    t_train = time.time() - t0
+    t_train = t_train_gen + time.time() - t0
 
     # ---- inputs: this rank's shard of the fixed test split, resident in HBM before the clock starts
-    test = synthetic.Dataset(C, G, split=1, n_points=n_points, **ds_kw)
-    lo, hi, pad, bounds = plan_shard(G, rank, world, args.batch)
-    assert (lo, hi) == shard.shard_range(G, rank, world)
-    chunks_h, chunks, chunk_ids = [], [], []
-    for j in range(len(bounds) - 1):
-        ids = list(range(bounds[j], bounds[j + 1]))
-        if not ids:
-            continue
-        nb = test.batch(ids)
-        chunks_h.append(nb)
-        chunks.append(pipeline.DeviceBatch(nb, dev))
-        chunk_ids.append(torch.as_tensor(ids, device=dev))
+    chunks = [pipeline.DeviceBatch(nb, dev) for nb in chunks_h]
+    chunk_ids = [torch.as_tensor(ids, device=dev) for ids in test_ids]
     torch.cuda.synchronize()
 
     def classify(b):
@@ -252,17 +330,18 @@ def main():
         return shard.all_gather_records(rows, world), keep
 
     for i in range(args.warmup):
-        g, _ = step(chunks)
+        g, last = step(chunks)
     torch.cuda.synchronize()
-    for c_ in ctxs:
-        c_.timers_enable(True)
-        c_.timers_reset()
+    if args.full:
+        for c_ in ctxs:
+            c_.timers_enable(True)
+            c_.timers_reset()
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        g, _ = step(chunks)
+        g, last = step(chunks)
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -273,9 +352,49 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # ---- accuracy of the last gathered step (sanity, not part of the metric): every object of the split must be there once
-    oi, best, _ = shard.unpack_records(g)
+    # ---- the last gathered step: every object of the split must be there once
+    records = shard.unpack_records(g)
+    oi, best, _ = records
     assert oi.tolist() == list(range(G)), "the all-gather did not return every object of the split exactly once"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, records, last, G, lo, rank, world)
+    if args.full:
+        full = measure_full(args, locals())
+    if rank == 0:
+        line = {
+            "metric": "objects/sec classified (ModelNet10-like, SHOT-352)" if args.config == 1 else f"objects/sec classified (BASELINE configs[{args.config}])",
+            "value": round(G * args.steps / dt, 3), "unit": "objects/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "dtype_note": "results are the exact f32 values of the reference's functors; the squared-L2 kNN candidate filter runs on f16 MFMA",
+            "config": {"workload": cdef["name"], "objects_per_step_all_gpus": G, "objects_per_step_this_rank": hi - lo,
+                       "launches_per_step_per_gpu": len(chunks), "points_per_object": n_points, "keypoints_per_object": n_kp or "VoxelGrid leaf",
+                       "classes": C, "codebook_words": n_words if len(n_words) > 1 else n_words[0],
+                       "descriptor_dim": [c.dim for c in cfgs] if len(cfgs) > 1 else cfgs[0].dim,
+                       "parallelism": f"fixed {G}-object split sharded over {world} GPU(s) (contiguous blocks), codebook replicated, 1 RCCL all-gather/step",
+                       "collective_world_size": dist.get_world_size() if distributed else 1},
+        }
+        if args.full:
+            line.update(full)
+        line["train_seconds"] = round(t_train, 1)
+        if args.share_gpu:
+            line["functional_test_only"] = "all ranks share cuda:0 over gloo: the value is NOT a scaling measurement"
+        if args.emit_labels:
+            line["labels_last_step"] = [int(x) for x in best.tolist()]
+        print(json.dumps(line))
+    if distributed:
+        dist.destroy_process_group()
+
+
+def measure_full(args, st):
+    """--full: everything beyond the headline, from the state `st` (main's locals) the timed steps left. Returns the JSON line's
+    extra fields (rank 0) or None."""
+    import torch
+    import __graft_entry__ as ge
+    (ctx, ctxs, recs, cfgs, cbs, n_words, chunks, chunks_h, chunk_ids, test, classify, pipeline, best, oi, G, C, lo, hi, rank,
+     world, dev) = (st[k] for k in ("ctx", "ctxs", "recs", "cfgs", "cbs", "n_words", "chunks", "chunks_h", "chunk_ids", "test",
+                                   "classify", "pipeline", "best", "oi", "G", "C", "lo", "hi", "rank", "world", "dev"))
+    # ---- accuracy of the last gathered step (sanity, not part of the metric)
     labels = torch.as_tensor([test.label(int(k)) for k in oi.tolist()], device=best.device)
     correct, total = int((best == labels).sum().item()), int(len(oi))
 
@@ -455,32 +574,12 @@ def main():
                          f" + votes + mean-shift), {t_cpu:.1f} s, OpenMP over keypoints/queries as the reference; the reference's default "
                          "kNN is an approximate 4-tree FLANN forest, so this is the exact-match (FLANNExactMatch) CPU cost"}
 
-    n_objects = G * args.steps
-    if rank == 0:
-        cfg0 = cfgs[0]
-        line = {
-            "metric": "objects/sec classified (ModelNet10-like, SHOT-352)" if args.config == 1 else f"objects/sec classified (BASELINE configs[{args.config}])",
-            "value": round(n_objects / dt, 3), "unit": "objects/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "dtype_note": "results are the exact f32 values of the reference's functors; the squared-L2 kNN candidate filter runs on f16 MFMA",
-            "config": {"workload": cdef["name"], "objects_per_step_all_gpus": G, "objects_per_step_this_rank": hi - lo,
-                       "launches_per_step_per_gpu": len(chunks), "points_per_object": n_points, "keypoints_per_object": n_kp or "VoxelGrid leaf",
-                       "classes": C, "codebook_words": n_words if len(n_words) > 1 else n_words[0], "descriptor_dim": [c.dim for c in cfgs] if len(cfgs) > 1 else cfg0.dim,
-                       "parallelism": f"fixed {G}-object split sharded over {world} GPU(s) (contiguous blocks), codebook replicated, 1 RCCL all-gather/step",
-                       "collective_world_size": dist.get_world_size() if distributed else 1},
-            "roofline": rooflines.get("roofline"), "roofline_shot": rooflines.get("roofline_shot"),
+    if rank != 0:
+        return None
+    return {"roofline": rooflines.get("roofline"), "roofline_shot": rooflines.get("roofline_shot"),
             "value_end_to_end": e2e, "cpu_baseline": cpu,
             "kernel_ms_per_step": {k: round(v[0] / args.steps, 4) for k, v in tm.items() if v[1] > 0},
-            "knn_exact_fallback_last_launch": knn_fb, "accuracy_last_step": round(correct / max(1, total), 4), "train_seconds": round(t_train, 1),
-        }
-        if args.share_gpu:
-            line["functional_test_only"] = "all ranks share cuda:0 over gloo: the value is NOT a scaling measurement"
-        if args.emit_labels:
-            line["labels_last_step"] = [int(x) for x in best.tolist()]
-        print(json.dumps(line))
-    if distributed:
-        dist.destroy_process_group()
+            "knn_exact_fallback_last_launch": knn_fb, "accuracy_last_step": round(correct / max(1, total), 4)}
 
 
 if __name__ == "__main__":

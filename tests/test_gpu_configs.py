@@ -206,7 +206,7 @@ def test_bench_two_ranks_on_one_gpu_functional():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--objects", "64", "--steps", "1", "--warmup", "0", "--no-e2e", "--cpu-objects", "0", "--emit-labels", "--train-per-class", "2"]
+    common = ["--full", "--objects", "64", "--steps", "1", "--warmup", "0", "--no-e2e", "--cpu-objects", "0", "--emit-labels", "--train-per-class", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
 
     def run(extra):
@@ -226,3 +226,32 @@ def test_bench_two_ranks_on_one_gpu_functional():
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, cwd=root,
                        env=dict(env, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999"), capture_output=True, text=True, timeout=300)
     assert p.returncode == 2 and "WORLD_SIZE" in p.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, reports ms_per_step and none of the --full figures, and --dump-outputs
+    writes the last timed step's results: the gathered records (every object once, the labels the line reports) and the maxima."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--objects", "32",
+                        "--train-per-class", "2", "--emit-labels", "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "objects/s"
+    assert abs(line["value"] - 32 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"] + 1e-2
+    for k in ("roofline", "roofline_shot", "value_end_to_end", "cpu_baseline", "kernel_ms_per_step", "accuracy_last_step"):
+        assert k not in line, k
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert np.array_equal(got["object_id"], np.arange(32))
+    assert got["predicted_class"].tolist() == line["labels_last_step"]
+    assert got["class_score"].shape == (32, 10) and np.array_equal(got["maxima_class_score"], got["class_score"])
+    assert got["maxima_n"].shape == (32,) and got["maxima_cls"].shape == (32, 16)

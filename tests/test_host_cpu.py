@@ -130,6 +130,54 @@ def test_bench_strong_scaling_plan_covers_the_split_once():
     assert b.plan_shard(908, 0, 1, 512)[3] == [0, 454, 908] and b.plan_shard(908, 7, 8, 512)[:2] == (798, 908)
 
 
+def test_bench_parallel_generation_equals_the_serial_batches(pkg, monkeypatch):
+    """bench.py makes its inputs in forked worker processes: the batches must be bit for bit what Dataset.batch builds serially,
+    for plain and coloured partial-view datasets alike."""
+    import multiprocessing
+    b = _bench()
+    monkeypatch.setitem(sys.modules, "bench_mod", b)          # the workers' function is pickled by module name
+    syn = pkg.synthetic
+    plain = syn.Dataset(4, 9, split=1, n_points=1024, n_keypoints=64)
+    color = syn.Dataset(3, 5, split=0, n_points=1024, leaf=0.2, scale=0.15, with_color=True, partial_view=True)
+    jobs = [(plain, [0, 1, 2, 3]), (plain, [4, 5, 6, 7, 8]), (color, [3, 1, 4])]
+    with multiprocessing.get_context("fork").Pool(2) as pool:
+        for got in (b.generate_batches(syn, jobs, pool), b.generate_batches(syn, jobs, None)):
+            for g, (ds, ids) in zip(got, jobs):
+                want = ds.batch(ids)
+                assert g.keys() == want.keys()
+                for k in want:
+                    assert g[k].dtype == want[k].dtype and np.array_equal(g[k], want[k]), k
+
+
+def test_bench_dump_outputs_format_and_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 / float64 arrays only (integers exactly as float64), one file per output, and above the size
+    cap every array keeps the same seeded sample of objects."""
+    import torch
+    b = _bench()
+    n, c = 40, 5
+    rng = np.random.default_rng(1)
+    sc = torch.as_tensor(rng.random((n, c), dtype=np.float32))
+    records = (torch.arange(n), sc.argmax(1), sc)
+    keep = [[{"n": torch.full((20,), 3, dtype=torch.int32), "pos": torch.as_tensor(rng.random((20, 16, 3), dtype=np.float32)),
+              "cls": torch.as_tensor(rng.integers(-1, c, (20, 16)), dtype=torch.int32), "class_score": sc[s:s + 20], "_keep": (1, 2)}]
+            for s in (0, 20)]
+    b.dump_outputs(str(tmp_path / "all"), records, keep, n, 0, 0, 1)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["class_score", "maxima_class_score", "maxima_cls", "maxima_n", "maxima_pos", "object_id", "predicted_class"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["object_id"].dtype == np.float64 and np.array_equal(got["object_id"], np.arange(n))
+    assert got["maxima_pos"].shape == (n, 16, 3) and np.array_equal(got["maxima_class_score"], got["class_score"])
+    total = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", total // 4)
+    b.dump_outputs(str(tmp_path / "cut"), records, keep, n, 0, 0, 1)
+    cut = {f[:-4]: np.load(tmp_path / "cut" / f) for f in os.listdir(tmp_path / "cut")}
+    assert sum(a.nbytes for a in cut.values()) <= total // 4
+    ids = cut["object_id"].astype(np.int64)
+    assert 0 < len(ids) < n and np.array_equal(ids, np.unique(ids))
+    for k, a in cut.items():
+        assert np.array_equal(a, got[k][ids]), k
+
+
 def test_bench_refuses_more_ranks_than_gpus():
     """`bench.py --gpus N` without a launcher starts the N ranks itself -- or fails loudly when the box has fewer GPUs (here: none)."""
     import torch

@@ -11,7 +11,7 @@ set -e
 CFG=${1:-1}
 SFX=""; CARG=""
 if [ "$CFG" != "1" ]; then SFX="_cfg$CFG"; CARG="--config $CFG"; fi
-B="--cpu-objects 0 --no-e2e $CARG"
+B="--full --cpu-objects 0 --no-e2e $CARG"
 rm -rf gpurun_out/prof_final$SFX gpurun_out/pmc_fetch_final$SFX gpurun_out/pmc_write_final$SFX
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_final$SFX -o bench -- python3 bench.py $B --steps 3 --warmup 1 > gpurun_out/prof_final$SFX.log 2>&1
 echo "stats pass done"
