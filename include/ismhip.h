@@ -86,8 +86,11 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","knn","cast_votes","maxima". Returns accumulated
- * milliseconds and launch count since the last reset. */
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","knn","cast_votes","maxima"; ismhip_knn_threshold: "knn_threshold" and its
+ * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
+ * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
+ * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
+ * queries of the last such search whose candidate list exceeded the per-query cap and went to the exact scan. */
 int  ismhip_timers_enable(ismhip_ctx* ctx, int on);
 int  ismhip_timers_reset(ismhip_ctx* ctx);
 int  ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t* launches_out);
@@ -230,6 +233,14 @@ int  ismhip_knn_ratio(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, in
 int  ismhip_knn_rule(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q,
                      float ratio_threshold, int32_t* idx_out, float* dist_out);
 
+/* ActivationStrategyThreshold::activate (activation_strategy/activation_strategy_threshold.cpp:27-44): every codeword whose functor
+ * value is STRICTLY below threshold, in ascending row order, as a CSR: act_offsets_out[nq+1] (device), idx_out / dist_out (device,
+ * `capacity` entries; dist = the functor value, bit-equal to the FLANN functor). *n_act_h_out (host) = the total. The offsets and the
+ * total are always written; the lists only when the total fits capacity (0: count only; otherwise grow the buffers and call again).
+ * threshold <= 0 (or NaN) gives empty lists. A total of 2^32 or more is refused (ISMHIP_ERR_UNSUPPORTED). The call synchronises. */
+int  ismhip_knn_threshold(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, float threshold,
+                          int64_t capacity, uint32_t* act_offsets_out, int32_t* idx_out, float* dist_out, int64_t* n_act_h_out);
+
 /* ---- vote casting: Codebook::castVotes second loop + CodewordDistribution::castVotes/castVote
  *      (codebook.cpp:541-554, codeword_distribution.cpp:73-167), sink = Voting::vote (voting/voting.cpp:58-77).
  *      Vote slot of (feature f, activation j, stored vote v) = (f*k + j)*maxv + v with
@@ -245,6 +256,15 @@ int  ismhip_cast_votes(ismhip_ctx* ctx, const ismhip_codebook* cb, uint32_t weig
                        int32_t* vote_codeword_out,
                        float* vote_bbox_quat_out,/* [n_slots*4], may be NULL */
                        float* vote_bbox_size_out /* [n_slots*3], may be NULL */);
+
+/* The same for a variable number of activations per feature (ismhip_knn_threshold): activation a of feature f lies in
+ * [act_offsets[f], act_offsets[f+1]) (device, [nq+1]) of idx / dist (device, [n_act]). Vote slot of (activation a, stored vote v) =
+ * a*maxv + v (feature-major); all outputs are SoA of n_slots = n_act*maxv entries. */
+int  ismhip_cast_votes_csr(ismhip_ctx* ctx, const ismhip_codebook* cb, uint32_t weight_flags,
+                           int nq, const float* lrf9, const float* kpx, const float* kpy, const float* kpz,
+                           const uint32_t* act_offsets, int64_t n_act, const int32_t* idx, const float* dist,
+                           float* vote_pos_out, float* vote_weight_out, int32_t* vote_class_out, int32_t* vote_instance_out,
+                           int32_t* vote_codeword_out, float* vote_bbox_quat_out, float* vote_bbox_size_out);
 
 /* ---- maxima: Voting::findMaxima + VotingMeanShift::iFindMaxima + MaximaHandler
  *      (voting/voting.cpp:79-328,436-462; voting_mean_shift.cpp:39-177,201-481; maxima_handler.cpp:51-157) */
@@ -304,6 +324,19 @@ int  ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim, const fl
                            int k, int clean_up_single_vote, int n_classes,
                            int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
                            float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out);
+
+/* Codebook::activate with a variable number of activations per feature (ActivationStrategyThreshold, codebook.cpp:139-142): the
+ * activations are given as a CSR, act_offsets (device, [n+1]) into act_idx (device, [n_act], rows of `codewords`, ascending per
+ * feature), e.g. from ismhip_knn_threshold. No K = 1 clean-up. The sigma^2 word sample takes whole activation lists of a class's
+ * first features while it holds fewer than sqrt(#features) words (:159-160, so it may overshoot); a class whose sample is empty gets
+ * 0/0 = NaN, as the reference computes it. Outputs as ismhip_train_activate, sized n_act instead of n*k. */
+int  ismhip_train_activate_lists(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
+                                 const float* kpx, const float* kpy, const float* kpz,
+                                 const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h,
+                                 int n_codewords, const float* codewords /* device, may be NULL */,
+                                 const uint32_t* act_offsets, const int32_t* act_idx, int64_t n_act, int n_classes,
+                                 int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
+                                 float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out);
 
 /* ---- k-means codebook clustering: ClusteringKMeans::cluster (clustering/clustering_kmeans.h:53-131) =
  *      flann::hierarchicalClustering with branching == the cluster count (one level of Lloyd k-means: centre chooser, then

@@ -28,6 +28,7 @@ EXPORTS = [
     "ismhip_compact_features", "ismhip_compact_descriptor_rows", "ismhip_filter_normals", "ismhip_voxel_keypoints", "ismhip_gather_columns",
     "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims",
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
+    "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists",
 ]
 
 
@@ -407,6 +408,57 @@ def cast_votes(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, idx, dist, want_bbox=F
     return dict(pos=pos, weight=w, cls=cls, inst=inst, codeword=cw, bbox_quat=bq, bbox_size=bs)
 
 
+def knn_threshold(ctx, cb, metric, q, threshold, capacity=None):
+    """ActivationStrategyThreshold: every codeword with functor value < threshold, ascending row order, as a CSR ->
+    (act_offsets [nq+1] int64 host, idx [n_act] int32 device, dist [n_act] float32 device). capacity=None: count first, then fetch
+    the lists with a buffer of exactly the total; otherwise one call with that capacity (lists None when the total does not fit)."""
+    torch = _torch()
+    nq = q.shape[0]
+    off = torch.empty((nq + 1,), dtype=torch.int32, device=q.device)
+    n_act = C.c_int64(0)
+    cap = 0 if capacity is None else int(capacity)
+    idx = torch.empty((max(cap, 1),), dtype=torch.int32, device=q.device)
+    dist = torch.empty((max(cap, 1),), dtype=torch.float32, device=q.device)
+
+    def call():
+        ctx.check(lib().ismhip_knn_threshold(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_float(threshold), C.c_int64(cap),
+                                             _p(off), _p(idx), _p(dist), C.byref(n_act)), "ismhip_knn_threshold")
+    call()
+    total = n_act.value
+    if capacity is None and total > 0:
+        cap = total
+        idx = torch.empty((cap,), dtype=torch.int32, device=q.device)
+        dist = torch.empty((cap,), dtype=torch.float32, device=q.device)
+        call()
+    offsets = off.cpu().numpy().view(np.uint32).astype(np.int64)
+    if total > cap:
+        return offsets, None, None
+    return offsets, idx[:total], dist[:total]
+
+
+def cast_votes_csr(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, act_offsets, idx, dist, want_bbox=False):
+    """ismhip_cast_votes_csr: act_offsets [nq+1] (host array or device int32 tensor), idx / dist [n_act] device. Slot of (activation a,
+    stored vote v) = a * max_votes + v."""
+    torch = _torch()
+    dev = idx.device
+    if isinstance(act_offsets, np.ndarray):
+        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(dev)
+    nq = act_offsets.shape[0] - 1
+    n_act = idx.shape[0]
+    ns = n_act * max(cb.max_votes, 0)
+    pos = torch.empty((ns, 3), dtype=torch.float32, device=dev)
+    w = torch.empty((ns,), dtype=torch.float32, device=dev)
+    cls = torch.empty((ns,), dtype=torch.int32, device=dev)
+    inst = torch.empty((ns,), dtype=torch.int32, device=dev)
+    cw = torch.empty((ns,), dtype=torch.int32, device=dev)
+    bq = torch.empty((ns, 4), dtype=torch.float32, device=dev) if want_bbox else None
+    bs = torch.empty((ns, 3), dtype=torch.float32, device=dev) if want_bbox else None
+    ctx.check(lib().ismhip_cast_votes_csr(ctx._h, cb._h, C.c_uint32(weight_flags), C.c_int(nq), _p(lrf), _p(kpx), _p(kpy), _p(kpz), _p(act_offsets),
+                                          C.c_int64(n_act), _p(idx), _p(dist), _p(pos), _p(w), _p(cls), _p(inst), _p(cw), _p(bq), _p(bs)),
+              "ismhip_cast_votes_csr")
+    return dict(pos=pos, weight=w, cls=cls, inst=inst, codeword=cw, bbox_quat=bq, bbox_size=bs)
+
+
 def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, max_iter=1000, kernel=KERNEL_GAUSSIAN,
                 suppression=SUPPRESS_AVERAGE, min_votes_threshold=1, min_threshold=0.0, best_k=-1, max_maxima=16,
                 class_bandwidth=None, max_filter=0, average_rotation=False, single_object_max_type=SOM_MEANSHIFT,
@@ -490,6 +542,29 @@ def train_activate(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, f
     ctx.check(lib().ismhip_train_activate(ctx._h, C.c_int(metric), C.c_int(n), C.c_int(dim), _p(desc), _p(lrf), _p(kx), _p(ky), _p(kz), _p(fc), _p(fm),
                                           _p(ctr), C.c_int(ncw), _p(codewords), C.c_int(k), C.c_int(1 if clean_up else 0), C.c_int(C_), C.byref(nw), _p(word_src),
                                           _p(vo), _p(vf), _p(vxyz), _p(vw), _p(vcw), _p(sig)), "ismhip_train_activate")
+    m = nw.value; nv = int(vo[m])
+    return dict(word_src=word_src[:m].copy(), vote_offsets=vo[:m + 1].copy(), vote_feature=vf[:nv].copy(), vote_xyz=vxyz[:nv].copy(),
+                vote_weight=vw[:nv].copy(), vote_class_weight=vcw[:nv].copy(), class_sigma=sig)
+
+
+def train_activate_lists(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, act_offsets, act_idx, n_classes=None, codewords=None):
+    """Codebook::activate with a variable number of activations per feature (ActivationStrategyThreshold): act_offsets [n+1] (host
+    array or device int32 tensor), act_idx [n_act] device int32 rows of the codewords -> the dict of train_activate"""
+    torch = _torch()
+    n, dim = desc.shape
+    if isinstance(act_offsets, np.ndarray):
+        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(desc.device)
+    fc, fm = _u32(feat_class), _u32(feat_model)
+    ctr = np.ascontiguousarray(np.asarray(feat_center, dtype=np.float32))
+    C_ = int(n_classes if n_classes is not None else fc.max() + 1)
+    ncw = n if codewords is None else int(codewords.shape[0])
+    na = int(act_idx.shape[0])
+    nw = C.c_int32(0)
+    word_src = np.empty(ncw, np.uint32); vo = np.empty(ncw + 1, np.uint32); vf = np.empty(max(na, 1), np.uint32)
+    vxyz = np.empty((max(na, 1), 3), np.float32); vw = np.empty(max(na, 1), np.float32); vcw = np.empty(max(na, 1), np.float32); sig = np.empty(C_, np.float32)
+    ctx.check(lib().ismhip_train_activate_lists(ctx._h, C.c_int(metric), C.c_int(n), C.c_int(dim), _p(desc), _p(lrf), _p(kx), _p(ky), _p(kz), _p(fc), _p(fm),
+                                                _p(ctr), C.c_int(ncw), _p(codewords), _p(act_offsets), _p(act_idx), C.c_int64(na), C.c_int(C_), C.byref(nw),
+                                                _p(word_src), _p(vo), _p(vf), _p(vxyz), _p(vw), _p(vcw), _p(sig)), "ismhip_train_activate_lists")
     m = nw.value; nv = int(vo[m])
     return dict(word_src=word_src[:m].copy(), vote_offsets=vo[:m + 1].copy(), vote_feature=vf[:nv].copy(), vote_xyz=vxyz[:nv].copy(),
                 vote_weight=vw[:nv].copy(), vote_class_weight=vcw[:nv].copy(), class_sigma=sig)

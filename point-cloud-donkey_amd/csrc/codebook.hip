@@ -43,13 +43,24 @@ struct VoteArgs {
     const float* vote_bbox_quat; const float* vote_bbox_size; const float* class_sigma;
     int n_words, n_classes, maxv; uint32_t flags;
     int nq, k; const float* lrf; const float *kx, *ky, *kz; const int32_t* idx; const float* dist;
+    const uint32_t* act_off; int64_t n_act;   // CSR activations (k_cast_votes<true>): activation a belongs to feature f iff act_off[f] <= a < act_off[f+1]
     float* pos; float* w; int32_t* cls; int32_t* inst; int32_t* cw; float* bq; float* bs;
 };
 
+// one thread per activation t; CSR = false: k activations per feature (f = t / k), CSR = true: f by binary search in act_off
+template <bool CSR>
 __global__ __launch_bounds__(256) void k_cast_votes(VoteArgs a) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= a.nq * a.k) return;
-    const int f = t / a.k;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int f;
+    if constexpr (CSR) {
+        if (t >= a.n_act) return;
+        int lo = 0, hi = a.nq;                                               // largest f with act_off[f] <= t
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)a.act_off[mid] <= t) lo = mid; else hi = mid; }
+        f = lo;
+    } else {
+        if (t >= (int64_t)a.nq * a.k) return;
+        f = (int)(t / a.k);
+    }
     const size_t slot0 = (size_t)t * a.maxv;
     for (int v = 0; v < a.maxv; ++v) {
         const size_t s = slot0 + v;
@@ -266,12 +277,37 @@ int ismhip_cast_votes(ismhip_ctx* ctx, const ismhip_codebook* cb, uint32_t weigh
     a.vote_bbox_quat = cb->vote_bbox_quat; a.vote_bbox_size = cb->vote_bbox_size; a.class_sigma = cb->class_sigma;
     a.n_words = cb->n_words; a.n_classes = cb->n_classes; a.maxv = cb->max_votes; a.flags = weight_flags;
     a.nq = nq; a.k = k; a.lrf = lrf9; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.idx = idx; a.dist = dist;
+    a.act_off = nullptr; a.n_act = 0;
     a.pos = vote_pos_out; a.w = vote_weight_out; a.cls = vote_class_out; a.inst = vote_instance_out; a.cw = vote_codeword_out;
     a.bq = vote_bbox_quat_out; a.bs = vote_bbox_size_out;
     TimerScope ts(ctx, "cast_votes");
     const int n = nq * k;
-    hipLaunchKernelGGL(k_cast_votes, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_cast_votes<false>, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_cast_votes");
+    return ISMHIP_OK;
+}
+
+int ismhip_cast_votes_csr(ismhip_ctx* ctx, const ismhip_codebook* cb, uint32_t weight_flags,
+                          int nq, const float* lrf9, const float* kpx, const float* kpy, const float* kpz,
+                          const uint32_t* act_offsets, int64_t n_act, const int32_t* idx, const float* dist,
+                          float* vote_pos_out, float* vote_weight_out, int32_t* vote_class_out, int32_t* vote_instance_out,
+                          int32_t* vote_codeword_out, float* vote_bbox_quat_out, float* vote_bbox_size_out) {
+    if (!ctx || !cb || nq < 0 || n_act < 0 || !act_offsets || (n_act > 0 && (!lrf9 || !kpx || !kpy || !kpz || !idx || !dist || !vote_pos_out ||
+        !vote_weight_out || !vote_class_out || !vote_instance_out || !vote_codeword_out)))
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "cast_votes_csr: bad argument");
+    if (nq == 0 || n_act == 0 || cb->max_votes == 0) return ISMHIP_OK;
+    VoteArgs a;
+    a.word_weight = cb->word_weight; a.vote_off = cb->vote_off; a.vote_xyz = cb->vote_xyz; a.vote_weight = cb->vote_weight;
+    a.vote_class_weight = cb->vote_class_weight; a.vote_class = cb->vote_class; a.vote_instance = cb->vote_instance;
+    a.vote_bbox_quat = cb->vote_bbox_quat; a.vote_bbox_size = cb->vote_bbox_size; a.class_sigma = cb->class_sigma;
+    a.n_words = cb->n_words; a.n_classes = cb->n_classes; a.maxv = cb->max_votes; a.flags = weight_flags;
+    a.nq = nq; a.k = 0; a.lrf = lrf9; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.idx = idx; a.dist = dist;
+    a.act_off = act_offsets; a.n_act = n_act;
+    a.pos = vote_pos_out; a.w = vote_weight_out; a.cls = vote_class_out; a.inst = vote_instance_out; a.cw = vote_codeword_out;
+    a.bq = vote_bbox_quat_out; a.bs = vote_bbox_size_out;
+    TimerScope ts(ctx, "cast_votes");
+    hipLaunchKernelGGL(k_cast_votes<true>, dim3((unsigned)((n_act + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    ISM_CHECK_LAUNCH(ctx, "k_cast_votes<csr>");
     return ISMHIP_OK;
 }
 

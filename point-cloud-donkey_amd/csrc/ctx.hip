@@ -180,6 +180,8 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
     if (!ctx || !name) return ISMHIP_ERR_INVALID;
     resolve_timers(ctx);
     if (std::strcmp(name, "knn_pca_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_pca_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    if (std::strcmp(name, "knn_threshold_overflow_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_overflow; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    if (std::strcmp(name, "knn_threshold_mfma_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_mfma_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_stage2_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_queries; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_flagged_queries") == 0 || std::strcmp(name, "knn_flagged_items") == 0) {     // counters, not times
         if (ms_out) *ms_out = (double)ctx->knn_stats[name[12] == 'q' ? 0 : 1];

@@ -74,8 +74,9 @@ __global__ void k_tr_members(int na, const int32_t* __restrict__ act, const uint
     const int w = act[a];
     if (w >= 0) members[all_off[w] + rank[a]] = (uint32_t)a;
 }
-// one thread per activation: its stable position inside the word's distribution, the vote and the word list
-__global__ void k_tr_votes(int na, int k, const int32_t* __restrict__ act, const uint32_t* __restrict__ all_off, const uint32_t* __restrict__ members,
+// one thread per activation: its stable position inside the word's distribution, the vote and the word list. The activations of
+// feature f are act[act_off[f] .. act_off[f+1]).
+__global__ void k_tr_votes(int na, int n, const uint32_t* __restrict__ act_off, const int32_t* __restrict__ act, const uint32_t* __restrict__ all_off, const uint32_t* __restrict__ members,
                            const uint32_t* __restrict__ keep, const uint32_t* __restrict__ word_idx, const uint32_t* __restrict__ vote_off_w,
                            const float* __restrict__ lrf, const float* __restrict__ kx, const float* __restrict__ ky, const float* __restrict__ kz,
                            const float* __restrict__ center, uint32_t* __restrict__ word_src, uint32_t* __restrict__ vote_off,
@@ -89,7 +90,8 @@ __global__ void k_tr_votes(int na, int k, const int32_t* __restrict__ act, const
     for (uint32_t t = m0; t < m1; ++t) pos += members[t] < (uint32_t)a;
     const uint32_t e = word_idx[w], v = vote_off_w[w] + pos;
     if (pos == 0) { word_src[e] = (uint32_t)w; vote_off[e] = vote_off_w[w]; }
-    const int fi = a / k;
+    int fi = 0, hi = n;                                                   // largest f with act_off[f] <= a
+    while (hi - fi > 1) { const int mid = (fi + hi) >> 1; if (act_off[mid] <= (uint32_t)a) fi = mid; else hi = mid; }
     // vote = rotateInto(centre - keyPos, LRF): q * p * conj(q) (utils.cpp:154-165, 568-574)
     const Quat q = rot_quaternion(lrf + (size_t)fi * 9);
     const Quat p{0.f, center[fi * 3] - kx[fi], center[fi * 3 + 1] - ky[fi], center[fi * 3 + 2] - kz[fi]};
@@ -296,34 +298,18 @@ int ism_knn_only_codebook(ismhip_ctx* ctx, int n_words, int dim, const float* wo
     return rc;
 }
 
-extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
-                                     const float* kpx, const float* kpy, const float* kpz,
-                                     const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h,
-                                     int n_codewords, const float* codewords,
-                                     int k, int clean_up, int n_classes,
-                                     int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
-                                     float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
-    if (!ctx || n <= 0 || dim <= 0 || !desc || !lrf9 || !kpx || !kpy || !kpz || !feat_class_h || !feat_model_h || !feat_center_h || k <= 0 ||
-        n_classes <= 0 || !n_words_out || !word_src_out || !vote_offsets_out || !vote_feature_out || !vote_xyz_out || !vote_weight_out ||
-        !vote_class_weight_out || !class_sigma_out || (metric != ISMHIP_METRIC_L2SQ && metric != ISMHIP_METRIC_CHI2))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
-    if (dim > 1344) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: descriptor longer than 1344 not built");
-    for (int i = 0; i < n; ++i) {
-        if ((int)feat_class_h[i] >= n_classes) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: class id out of range");
-        if (i && feat_class_h[i] < feat_class_h[i - 1]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: features must be class-major (the reference iterates classes in ascending order)");
-    }
-    // the codewords: cluster centres (implicit_shape_model.cpp:445-475), or the features themselves (clustering_none.cpp:25-35)
-    if (!codewords) { codewords = desc; n_codewords = n; }
-    if (n_codewords <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: no codewords");
-    if (n_codewords < k) k = n_codewords;            // FLANN returns as many neighbours as there are rows: every feature activates every codeword
-    const size_t na = (size_t)n * k;
-    const int nw_in = n_codewords;
-    // ---- step 1a: every feature activates its k nearest codewords (exact, ties -> lowest row)
-    ismhip_codebook* cb = nullptr;
-    int rc = ism_knn_only_codebook(ctx, nw_in, dim, codewords, &cb, false);
-    if (rc != ISMHIP_OK) return rc;
-    // scratch: activation list + CSR work arrays, carved from one slot (two passes: size, then pointers)
-    unsigned long long* term3_key = nullptr; int32_t* act = nullptr; float* actd = nullptr;
+// Codebook::activate after the activation step: the activations of every feature as a CSR (act_off device [n+1], act_off_h its host
+// copy, act device [na]: rows of `codewords`, -1 = none). Everything of ismhip_train_activate after its kNN, for any number of
+// activations per feature.
+static int train_from_activations(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
+                                  const float* kpx, const float* kpy, const float* kpz,
+                                  const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h,
+                                  int nw_in, const float* codewords, const uint32_t* act_off, const uint32_t* act_off_h, const int32_t* act, size_t na,
+                                  int clean_up, int n_classes,
+                                  int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
+                                  float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
+    // scratch: CSR work arrays, carved from one slot (two passes: size, then pointers)
+    unsigned long long* term3_key = nullptr;
     uint32_t *rank = nullptr, *cnt = nullptr, *keep = nullptr, *kcnt = nullptr, *all_off = nullptr, *word_idx = nullptr, *vote_off_w = nullptr, *members = nullptr,
              *word_src = nullptr, *vote_off = nullptr, *vote_feature = nullptr, *vote_word = nullptr, *feat_class = nullptr, *num_features = nullptr,
              *words_per_class = nullptr, *overflow = nullptr;
@@ -334,7 +320,7 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
         size_t off = 0;
         auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 15) / 16 * 16; return p; };
         term3_key = (unsigned long long*)take((size_t)n_classes * 8);
-        act = (int32_t*)take(na * 4); actd = (float*)take(na * 4); rank = (uint32_t*)take(na * 4);
+        rank = (uint32_t*)take(na * 4);
         cnt = (uint32_t*)take(((size_t)nw_in + 1) * 4); keep = (uint32_t*)take(((size_t)nw_in + 1) * 4); kcnt = (uint32_t*)take(((size_t)nw_in + 1) * 4);
         all_off = (uint32_t*)take(((size_t)nw_in + 1) * 4); word_idx = (uint32_t*)take(((size_t)nw_in + 1) * 4); vote_off_w = (uint32_t*)take(((size_t)nw_in + 1) * 4);
         members = (uint32_t*)take(na * 4); word_src = (uint32_t*)take(((size_t)nw_in + 1) * 4); vote_off = (uint32_t*)take(((size_t)nw_in + 1) * 4);
@@ -345,13 +331,11 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
         if (pass == 0) {
             total = off;
             base = (char*)ism_scratch(ctx, SCR_TRAIN, total);
-            if (!base) { ismhip_codebook_destroy(ctx, cb); return ISMHIP_ERR_NOMEM; }
+            if (!base) return ISMHIP_ERR_NOMEM;
         }
     }
     words_per_class = num_features + n_classes; overflow = words_per_class + n_classes;
-    auto done = [&](int code) { ismhip_codebook_destroy(ctx, cb); return code; };
-    rc = ismhip_knn(ctx, cb, metric, n, desc, k, act, actd);
-    if (rc != ISMHIP_OK) return done(rc);
+    auto done = [&](int code) { return code; };
     hipStream_t st = ctx->stream;
 #define TR_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { ism_set_err(ctx, ISMHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); return done(ISMHIP_ERR_HIP); } } while (0)
     TR_HIP(hipMemcpyAsync(feat_class, feat_class_h, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -360,12 +344,12 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
     TR_HIP(hipMemsetAsync(num_features, 0, (size_t)n_classes * 8 + 32, st));      // num_features, words_per_class, overflow
     TR_HIP(hipMemsetAsync(term3_key, 0, (size_t)n_classes * 8, st));
     // ---- distributions: CSR in activation order, clean-up, votes
-    const unsigned ga = (unsigned)((na + 255) / 256), gn = (unsigned)((nw_in + 255) / 256);
+    const unsigned ga = (unsigned)std::max<size_t>(1, (na + 255) / 256), gn = (unsigned)((nw_in + 255) / 256);
     hipLaunchKernelGGL(k_tr_count, dim3(ga), dim3(256), 0, st, (int)na, act, cnt, rank);
     hipLaunchKernelGGL(k_tr_flags, dim3(gn), dim3(256), 0, st, nw_in, clean_up, cnt, keep, kcnt);
     hipLaunchKernelGGL(k_tr_scan, dim3(1), dim3(1024), 0, st, nw_in, cnt, all_off, keep, word_idx, kcnt, vote_off_w);
     hipLaunchKernelGGL(k_tr_members, dim3(ga), dim3(256), 0, st, (int)na, act, all_off, rank, members);
-    hipLaunchKernelGGL(k_tr_votes, dim3(ga), dim3(256), 0, st, (int)na, k, act, all_off, members, keep, word_idx, vote_off_w, lrf9, kpx, kpy, kpz, center,
+    hipLaunchKernelGGL(k_tr_votes, dim3(ga), dim3(256), 0, st, (int)na, n, act_off, act, all_off, members, keep, word_idx, vote_off_w, lrf9, kpx, kpy, kpz, center,
                        word_src, vote_off, vote_feature, vote_xyz);
     hipLaunchKernelGGL(k_tr_tail, dim3(1), dim3(1), 0, st, word_idx + nw_in, vote_off_w + nw_in, vote_off);
     // vote_off[n_words] = n_votes: the totals of the scans
@@ -375,7 +359,9 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
     // ---- class sigma^2: sample lists from the (host) class / model ids, distances and sequential sums on the device
     {
         std::vector<SigmaClass> sc((size_t)n_classes);
-        std::vector<uint32_t> sf; std::vector<uint32_t> swf;           // sample features; features whose activations form the word sample
+        std::vector<uint32_t> sf;                                       // sample features
+        std::vector<uint32_t> sw_src;                                   // per class with features: first activation of its word sample
+        size_t nsw = 0;                                                 // words in all classes' samples
         uint32_t d0 = 0;
         int i0 = 0;
         for (int c = 0; c < n_classes; ++c) {
@@ -384,10 +370,11 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
             const int nc = i1 - i0;
             if (nc > 0) {
                 const int max_elements = (int)std::sqrt((double)nc);
-                int words = 0, t = i0;
-                s.w0 = (uint32_t)swf.size() * (uint32_t)k;
-                while (t < i1 && words < max_elements) { swf.push_back((uint32_t)t); words += k; ++t; }   // :146-147 (checked before each feature's k words)
+                int64_t words = 0; int t = i0;
+                s.w0 = (uint32_t)nsw;
+                while (t < i1 && words < max_elements) { words += act_off_h[t + 1] - act_off_h[t]; ++t; }   // :146-147, :159-160 (checked before each feature's whole list)
                 s.nw = (uint32_t)words;
+                sw_src.push_back(act_off_h[i0]); nsw += (size_t)words;
                 int m = i0;
                 while (m < i1 && (int)(sf.size() - s.f0) < max_elements) {                              // :149-150 whole models
                     int e = m; while (e < i1 && feat_model_h[e] == feat_model_h[m]) ++e;
@@ -399,9 +386,8 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
             }
             sc[c] = s; i0 = i1;
         }
-        // word sample = the activations of the features in swf, flattened (every feature has k activations when n >= k)
-        const size_t nsw = swf.size() * (size_t)k;
-        char* sb = (char*)ism_scratch(ctx, SCR_TRAIN2, sc.size() * sizeof(SigmaClass) + (sf.size() + 1) * 4 + (nsw + 1) * 4 + ((size_t)d0 + 1) * 4 + (swf.size() + 1) * 4);
+        // word sample = the activations of the sampled features, flattened
+        char* sb = (char*)ism_scratch(ctx, SCR_TRAIN2, sc.size() * sizeof(SigmaClass) + (sf.size() + 1) * 4 + (nsw + 1) * 4 + ((size_t)d0 + 1) * 4);
         if (!sb) return done(ISMHIP_ERR_NOMEM);
         SigmaClass* d_sc = (SigmaClass*)sb; sb += sc.size() * sizeof(SigmaClass);
         uint32_t* d_sf = (uint32_t*)sb; sb += (sf.size() + 1) * 4;
@@ -409,13 +395,13 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
         float* d_dist = (float*)sb; sb += ((size_t)d0 + 1) * 4;
         TR_HIP(hipMemcpyAsync(d_sc, sc.data(), sc.size() * sizeof(SigmaClass), hipMemcpyHostToDevice, st));
         if (!sf.empty()) TR_HIP(hipMemcpyAsync(d_sf, sf.data(), sf.size() * 4, hipMemcpyHostToDevice, st));
-        // the sampled features of a class are its FIRST ones, so their activations are k-wide row ranges of act: copy device to device
+        // the sampled features of a class are its FIRST ones, so their activations are one range of act: copy device to device
         {
-            size_t o = 0;
+            size_t j = 0;
             for (int c = 0; c < n_classes; ++c) {
-                const uint32_t cnt_f = sc[c].nw / (uint32_t)k;
-                if (cnt_f) TR_HIP(hipMemcpyAsync(d_sw + o, act + (size_t)swf[sc[c].w0 / (uint32_t)k] * k, (size_t)cnt_f * k * 4, hipMemcpyDeviceToDevice, st));
-                o += (size_t)cnt_f * k;
+                if (sc[c].nf == 0) continue;
+                if (sc[c].nw) TR_HIP(hipMemcpyAsync(d_sw + sc[c].w0, act + sw_src[j], (size_t)sc[c].nw * 4, hipMemcpyDeviceToDevice, st));
+                ++j;
             }
         }
         if (d0) {
@@ -463,4 +449,88 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
     TR_HIP(hipMemcpy(class_sigma_out, sigma, (size_t)n_classes * 4, hipMemcpyDeviceToHost));
 #undef TR_HIP
     return done(ISMHIP_OK);
+}
+
+// argument checks shared by both entry points; codewords == NULL -> the features themselves (clustering_none.cpp:25-35)
+static int train_check(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9, const float* kpx, const float* kpy,
+                       const float* kpz, const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h, int n_classes,
+                       int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out, float* vote_xyz_out,
+                       float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
+    if (!ctx || n <= 0 || dim <= 0 || !desc || !lrf9 || !kpx || !kpy || !kpz || !feat_class_h || !feat_model_h || !feat_center_h ||
+        n_classes <= 0 || !n_words_out || !word_src_out || !vote_offsets_out || !vote_feature_out || !vote_xyz_out || !vote_weight_out ||
+        !vote_class_weight_out || !class_sigma_out || (metric != ISMHIP_METRIC_L2SQ && metric != ISMHIP_METRIC_CHI2))
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
+    if (dim > 1344) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: descriptor longer than 1344 not built");
+    for (int i = 0; i < n; ++i) {
+        if ((int)feat_class_h[i] >= n_classes) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: class id out of range");
+        if (i && feat_class_h[i] < feat_class_h[i - 1]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: features must be class-major (the reference iterates classes in ascending order)");
+    }
+    return ISMHIP_OK;
+}
+
+extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
+                                     const float* kpx, const float* kpy, const float* kpz,
+                                     const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h,
+                                     int n_codewords, const float* codewords,
+                                     int k, int clean_up, int n_classes,
+                                     int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
+                                     float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
+    int rc = train_check(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
+                         vote_offsets_out, vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (k <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
+    // the codewords: cluster centres (implicit_shape_model.cpp:445-475), or the features themselves (clustering_none.cpp:25-35)
+    if (!codewords) { codewords = desc; n_codewords = n; }
+    if (n_codewords <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: no codewords");
+    if (n_codewords < k) k = n_codewords;            // FLANN returns as many neighbours as there are rows: every feature activates every codeword
+    const size_t na = (size_t)n * k;
+    // ---- every feature activates its k nearest codewords (exact, ties -> lowest row): the regular CSR act_off[f] = f * k
+    ismhip_codebook* cb = nullptr;
+    rc = ism_knn_only_codebook(ctx, n_codewords, dim, codewords, &cb, false);
+    if (rc != ISMHIP_OK) return rc;
+    std::vector<uint32_t> act_off_h((size_t)n + 1);
+    for (int f = 0; f <= n; ++f) act_off_h[f] = (uint32_t)((size_t)f * k);
+    char* ab = (char*)ism_scratch(ctx, SCR_TRAIN_ACT, na * 8 + ((size_t)n + 1) * 4 + 16);
+    if (!ab) { ismhip_codebook_destroy(ctx, cb); return ISMHIP_ERR_NOMEM; }
+    int32_t* act = (int32_t*)ab; float* actd = (float*)(ab + na * 4); uint32_t* act_off = (uint32_t*)(ab + na * 8);
+    rc = ismhip_knn(ctx, cb, metric, n, desc, k, act, actd);
+    if (rc == ISMHIP_OK && hipMemcpyAsync(act_off, act_off_h.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = ism_set_err(ctx, ISMHIP_ERR_HIP, "train_activate: activation offsets copy");
+    if (rc == ISMHIP_OK)
+        rc = train_from_activations(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_codewords, codewords,
+                                    act_off, act_off_h.data(), act, na, clean_up, n_classes, n_words_out, word_src_out, vote_offsets_out, vote_feature_out,
+                                    vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
+    ismhip_codebook_destroy(ctx, cb);
+    return rc;
+}
+
+extern "C" int ismhip_train_activate_lists(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
+                                           const float* kpx, const float* kpy, const float* kpz,
+                                           const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h,
+                                           int n_codewords, const float* codewords,
+                                           const uint32_t* act_offsets, const int32_t* act_idx, int64_t n_act, int n_classes,
+                                           int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
+                                           float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
+    int rc = train_check(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
+                         vote_offsets_out, vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (!act_offsets || n_act < 0 || (n_act > 0 && !act_idx)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: bad argument");
+    if (n_act > 0x7fffffff) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate_lists: 2^31 or more activations not built");
+    if (!codewords) { codewords = desc; n_codewords = n; }
+    if (n_codewords <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: no codewords");
+    std::vector<uint32_t> act_off_h((size_t)n + 1);
+    ISM_HIP(ctx, hipMemcpyAsync(act_off_h.data(), act_offsets, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (act_off_h[0] != 0 || (int64_t)act_off_h[n] != n_act) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: offsets do not match n_act");
+    for (int f = 0; f < n; ++f)
+        if (act_off_h[f + 1] < act_off_h[f]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: offsets not monotone");
+    {   // every activation must name a codeword row (the kernels index per-word arrays with it)
+        std::vector<int32_t> a_h((size_t)n_act);
+        if (n_act) ISM_HIP(ctx, hipMemcpy(a_h.data(), act_idx, (size_t)n_act * 4, hipMemcpyDeviceToHost));
+        for (int32_t w : a_h) if (w < 0 || w >= n_codewords) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: activation outside the codewords");
+    }
+    // no K = 1 clean-up: codebook.cpp:201-224 applies to KNN with k = 1 and INN only
+    return train_from_activations(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_codewords, codewords,
+                                  act_offsets, act_off_h.data(), act_idx, (size_t)n_act, 0, n_classes, n_words_out, word_src_out, vote_offsets_out,
+                                  vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
 }

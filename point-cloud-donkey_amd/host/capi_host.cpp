@@ -102,6 +102,29 @@ int ism3d_codebook_get_all(void* m, int* n_words_out, int* dim_out, int* n_class
     cp(class_sigma, d.class_sigma);
     return (int)d.vote_class.size();
 }
+// diagnostics (tests): features of the last train() (which = 0) or detectBatch() (which = 1). Any array may be NULL. Returns the number
+// of features; *dim_out and *n_obj_out (detection: objects of the batch, off_out [n_obj+1]) the shape. cls / model / center [n*3]: the
+// training features' class, model and bounding-box centre (which = 0 only).
+int ism3d_last_features(void* m, int which, int* dim_out, int* n_obj_out, uint32_t* off_out, float* desc, float* lrf9, float* kxyz,
+                        uint32_t* cls, uint32_t* model, float* center) {
+    GUARD(
+        const auto d = ((ImplicitShapeModel*)m)->lastFeatures(which);
+        if (dim_out) *dim_out = d.dim;
+        if (n_obj_out) *n_obj_out = (int)d.off.size() - 1;
+        auto cp = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+        cp(off_out, d.off); cp(desc, d.desc); cp(lrf9, d.lrf); cp(cls, d.cls); cp(model, d.model); cp(center, d.center);
+        if (kxyz) for (uint32_t i = 0; i < d.n; ++i) { kxyz[3 * i] = d.kx[i]; kxyz[3 * i + 1] = d.ky[i]; kxyz[3 * i + 2] = d.kz[i]; }
+        return (int)d.n;)
+}
+// diagnostics (tests): the vote space of the last detectBatch(): slot_off [n_obj+1], pos [n*3], weight, cls, inst [n]. Any array may be
+// NULL. Returns the number of vote slots.
+int ism3d_last_votes(void* m, uint32_t* slot_off, float* pos, float* weight, int32_t* cls, int32_t* inst) {
+    GUARD(
+        const auto d = ((ImplicitShapeModel*)m)->lastVotes();
+        auto cp = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+        cp(slot_off, d.slot_off); cp(pos, d.pos); cp(weight, d.weight); cp(cls, d.cls); cp(inst, d.inst);
+        return (int)d.weight.size();)
+}
 // label maps and the per-class size hints (Voting::forwardBoxesAndRadii) that travel with the model
 int ism3d_set_labels(void* m, int n_classes, const char* const* class_labels, int n_inst, const char* const* inst_labels, const unsigned* inst_to_class) {
     GUARD(((ImplicitShapeModel*)m)->setLabels(std::vector<std::string>(class_labels, class_labels + n_classes), std::vector<std::string>(inst_labels, inst_labels + n_inst),

@@ -66,6 +66,7 @@ public:
     bool has_color = false;
     // vote space of the current batch (Voting::m_votes)
     DevBuf v_pos, v_w, v_cls, v_inst, v_cw, v_bs, v_bq, idx, dist;
+    DevBuf act_off;                       // [n+1] activation ranges of the list path (ActivationStrategyThreshold)
     DevBuf obj_cen, obj_rad;              // per-object cloud centroid / farthest point (single-object max types)
     std::vector<uint32_t> slot_off;
     size_t n_slots = 0;
@@ -435,6 +436,26 @@ int ActivationStrategyKnnRule::activateKNN(DeviceSession& s, const ismhip_codebo
     return 1;
 }
 
+ActivationStrategyThreshold::ActivationStrategyThreshold() { addParameter(m_threshold, "Threshold", 1.0f); }   // activation_strategy_threshold.cpp:20
+int ActivationStrategyThreshold::activateKNN(DeviceSession&, const ismhip_codebook*, const DeviceFeatures&, int, int32_t*, float*, const float*) const {
+    throw RuntimeException("Threshold activation has no fixed number of activations per feature: use the list path");
+}
+
+// ActivationStrategyThreshold over n descriptors (device, n x dim): act_off [n+1], idx / dist grown to the total. Returns the total.
+static int64_t thresholdLists(DeviceSession& s, const ismhip_codebook* codewords, int metric, uint32_t n, const float* desc, float threshold) {
+    s.act_off.reserve(((size_t)n + 1) * 4);
+    int64_t total = 0;
+    const int64_t cap = (int64_t)(std::min(s.idx.bytes, s.dist.bytes) / 4);
+    s.check(ismhip_knn_threshold(s.ctx, codewords, metric, (int)n, desc, threshold, cap, s.act_off.as<uint32_t>(), s.idx.as<int32_t>(), s.dist.as<float>(), &total),
+            "ismhip_knn_threshold");
+    if (total > cap) {                                           // the lists did not fit: grow and search again
+        s.idx.reserve((size_t)total * 4); s.dist.reserve((size_t)total * 4);
+        s.check(ismhip_knn_threshold(s.ctx, codewords, metric, (int)n, desc, threshold, total, s.act_off.as<uint32_t>(), s.idx.as<int32_t>(),
+                                     s.dist.as<float>(), &total), "ismhip_knn_threshold");
+    }
+    return total;
+}
+
 // FLANN functors on the host, used by the training statistics only (utils/distance.cpp:33-52)
 // Utils::getRotQuaternion + matrix2Quat (utils.cpp:136-151, 342-380): rows of the matrix are the frame axes; out = (w, x, y, z)
 static void hostRotQuaternion(const float* l, float* out) {
@@ -479,6 +500,7 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
     const int D = f.dim;
     if (n == 0) throw RuntimeException("no training features");
     const ActivationStrategy* knn = m_activationStrategy.get();
+    const auto* thr = dynamic_cast<const ActivationStrategyThreshold*>(knn);
     const bool is_knn = m_activationStrategy->getType() == "KNN";
     const int k = is_knn ? knn->getK() : 1;                      // KNNRule trains with plain 1-NN (activation_strategy_knn_rule.h:70-74)
     if (k > 16) throw RuntimeException("KNN activation with K > 16 is not built");
@@ -495,12 +517,33 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
     for (uint32_t i = 0; i < n; ++i) for (int d = 0; d < 3; ++d) centers[(size_t)i * 3 + d] = feat_center[i][d];
     const bool clean_up = is_knn && k == 1;                     // codebook.cpp:201-224
     int32_t n_words = 0;
-    std::vector<uint32_t> word_src(n_cw), vote_off((size_t)n_cw + 1), vote_feature((size_t)n * k);
-    std::vector<float> vote_xyz((size_t)n * k * 3), vote_weight((size_t)n * k), vote_cw((size_t)n * k), sigma((size_t)std::max(1, n_classes));
-    s.check(ismhip_train_activate(s.ctx, metric, (int)n, D, f.desc.as<float>(), f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(),
-                                  feat_class.data(), feat_model.data(), centers.data(), (int)n_cw, clustered ? clustering.getClusterCentersDevice() : nullptr,
-                                  k, clean_up ? 1 : 0, std::max(1, n_classes), &n_words, word_src.data(),
-                                  vote_off.data(), vote_feature.data(), vote_xyz.data(), vote_weight.data(), vote_cw.data(), sigma.data()), "ismhip_train_activate");
+    size_t n_act = (size_t)n * k;
+    if (thr) {                                                   // Threshold (codebook.cpp:139-142): every codeword below the threshold
+        std::vector<uint32_t> one((size_t)n_cw + 1), zc(n_cw, 0u);
+        std::iota(one.begin(), one.end(), 0u);
+        std::vector<float> zxyz((size_t)n_cw * 3, 0.f), sig1(1, 1.f);
+        ismhip_codebook* cwb = nullptr;                          // search structure of the codewords only (one dummy vote per word)
+        s.check(ismhip_codebook_create(s.ctx, (int)n_cw, D, words.data(), nullptr, one.data(), zxyz.data(), nullptr, nullptr, zc.data(), zc.data(),
+                                       nullptr, nullptr, 1, sig1.data(), &cwb), "ismhip_codebook_create");
+        try { n_act = (size_t)thresholdLists(s, cwb, metric, n, f.desc.as<float>(), thr->getThreshold()); }
+        catch (...) { ismhip_codebook_destroy(s.ctx, cwb); throw; }
+        ismhip_codebook_destroy(s.ctx, cwb);
+    }
+    std::vector<uint32_t> word_src(n_cw), vote_off((size_t)n_cw + 1), vote_feature(std::max<size_t>(n_act, 1));
+    std::vector<float> vote_xyz(std::max<size_t>(n_act, 1) * 3), vote_weight(std::max<size_t>(n_act, 1)), vote_cw(std::max<size_t>(n_act, 1)),
+                       sigma((size_t)std::max(1, n_classes));
+    if (thr) {
+        s.check(ismhip_train_activate_lists(s.ctx, metric, (int)n, D, f.desc.as<float>(), f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(),
+                                            feat_class.data(), feat_model.data(), centers.data(), (int)n_cw, clustered ? clustering.getClusterCentersDevice() : nullptr,
+                                            s.act_off.as<uint32_t>(), s.idx.as<int32_t>(), (int64_t)n_act, std::max(1, n_classes), &n_words, word_src.data(),
+                                            vote_off.data(), vote_feature.data(), vote_xyz.data(), vote_weight.data(), vote_cw.data(), sigma.data()),
+                "ismhip_train_activate_lists");
+    } else {
+        s.check(ismhip_train_activate(s.ctx, metric, (int)n, D, f.desc.as<float>(), f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(),
+                                      feat_class.data(), feat_model.data(), centers.data(), (int)n_cw, clustered ? clustering.getClusterCentersDevice() : nullptr,
+                                      k, clean_up ? 1 : 0, std::max(1, n_classes), &n_words, word_src.data(),
+                                      vote_off.data(), vote_feature.data(), vote_xyz.data(), vote_weight.data(), vote_cw.data(), sigma.data()), "ismhip_train_activate");
+    }
     std::vector<uint32_t> kept(word_src.begin(), word_src.begin() + n_words);
     std::vector<uint32_t> sel(kept.size());
     std::iota(sel.begin(), sel.end(), 0u);
@@ -556,13 +599,29 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
         s.check(ismhip_gather_columns(s.ctx, (int)n, f.dim, f.desc.as<float>(), (int)m_partial_cols.size(), m_partial_cols.data(), partial.as<float>()), "ismhip_gather_columns");
         qdesc = partial.as<float>();
     }
+    const uint32_t flags = (m_useClassWeight ? ISMHIP_W_CLASS : 0u) | (m_useVoteWeight ? ISMHIP_W_VOTE : 0u) |
+                           (m_useMatchingWeight ? ISMHIP_W_MATCHING : 0u) | (m_useCodewordWeight ? ISMHIP_W_CODEWORD : 0u);
+    if (const auto* thr = dynamic_cast<const ActivationStrategyThreshold*>(knn)) {
+        // list path (codebook.cpp:505-508): every activated codeword casts all its votes; slot of (activation a, vote v) = a*maxv + v
+        const int64_t na = thresholdLists(s, m_dev, metric, n, qdesc ? qdesc : f.desc.as<float>(), thr->getThreshold());
+        const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
+        const size_t ns = (size_t)na * maxv;
+        s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
+        s.check(ismhip_cast_votes_csr(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), s.act_off.as<uint32_t>(),
+                                      na, s.idx.as<int32_t>(), s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(),
+                                      s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(), s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes_csr");
+        std::vector<uint32_t> act_off;
+        s.d2h(act_off, s.act_off, (size_t)n + 1);
+        s.n_slots = ns;
+        for (int o = 0; o <= s.n_obj; ++o) s.slot_off[o] = act_off[f.off[o]] * (uint32_t)maxv;
+        s.n_classes = (int)m_data.class_sigma.size();
+        return;
+    }
     const int k = knn->activateKNN(s, m_dev, f, metric, s.idx.as<int32_t>(), s.dist.as<float>(), qdesc);
     if (qdesc) s.check(ismhip_sync(s.ctx), "ismhip_sync");     // the partial descriptors are released when this function returns
     const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
     const size_t ns = (size_t)n * k * maxv;
     s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
-    const uint32_t flags = (m_useClassWeight ? ISMHIP_W_CLASS : 0u) | (m_useVoteWeight ? ISMHIP_W_VOTE : 0u) |
-                           (m_useMatchingWeight ? ISMHIP_W_MATCHING : 0u) | (m_useCodewordWeight ? ISMHIP_W_CODEWORD : 0u);
     s.check(ismhip_cast_votes(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),
                               s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(),
                               s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes");
@@ -900,7 +959,8 @@ template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type)
 template <> ActivationStrategy* Factory<ActivationStrategy>::createByType(const std::string& type) {
     if (type == ActivationStrategyKNN::getTypeStatic()) return new ActivationStrategyKNN();
     if (type == ActivationStrategyKnnRule::getTypeStatic()) return new ActivationStrategyKnnRule();
-    throw RuntimeException("activation strategy \"" + type + "\" is not built (built: KNN, KNNRule)");
+    if (type == ActivationStrategyThreshold::getTypeStatic()) return new ActivationStrategyThreshold();
+    throw RuntimeException("activation strategy \"" + type + "\" is not built (built: KNN, KNNRule, Threshold)");
 }
 template <> Voting* Factory<Voting>::createByType(const std::string& type) {
     if (type == VotingMeanShift::getTypeStatic()) return new VotingMeanShift();
@@ -1308,6 +1368,9 @@ void ImplicitShapeModel::train() {                // :252-500
     if (!m_clustering) m_clustering.reset(new ClusteringNone());
     (*m_clustering)(s, *all, met);
     m_codebook->activate(s, *all, fclass, finst, fmodel, fcenter, fbox, met, m_n_classes, *m_clustering);
+    m_last_train = all; m_last_fclass = fclass; m_last_fmodel = fmodel;
+    m_last_fcenter.clear();
+    for (const auto& c : fcenter) m_last_fcenter.insert(m_last_fcenter.end(), c.begin(), c.end());
     LOG_INFO("training done");
 }
 
@@ -1328,6 +1391,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     m_voting->clear();
     m_codebook->castVotes(s, *f, metric(), *m_voting);
     s.sync();
+    m_last_detect = f;
     auto t1 = std::chrono::steady_clock::now();
     m_processing_times["voting"] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     LOG_INFO("finding maxima");
@@ -1338,6 +1402,28 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     m_processing_times["normals"] += 0; m_processing_times["flann"] += 0;
     for (size_t i = 0; i < res.size(); ++i) out[map[i]] = res[i];
     return out;
+}
+
+ImplicitShapeModel::FeatureDump ImplicitShapeModel::lastFeatures(int which) const {
+    FeatureDump d;
+    const std::shared_ptr<DeviceFeatures>& f = which == 0 ? m_last_train : m_last_detect;
+    if (!f || !m_session) return d;
+    const DeviceSession& s = *m_session;
+    d.dim = f->dim; d.n = f->n; d.off = f->off;
+    s.d2h(d.desc, f->desc, (size_t)f->n * f->dim); s.d2h(d.lrf, f->lrf, (size_t)f->n * 9);
+    s.d2h(d.kx, f->kx, f->n); s.d2h(d.ky, f->ky, f->n); s.d2h(d.kz, f->kz, f->n);
+    if (which == 0) { d.cls = m_last_fclass; d.model = m_last_fmodel; d.center = m_last_fcenter; }
+    return d;
+}
+
+ImplicitShapeModel::VoteDump ImplicitShapeModel::lastVotes() const {
+    VoteDump d;
+    if (!m_session) return d;
+    const DeviceSession& s = *m_session;
+    d.slot_off = s.slot_off;
+    s.d2h(d.pos, s.v_pos, s.n_slots * 3); s.d2h(d.weight, s.v_w, s.n_slots);
+    s.d2h(d.cls, s.v_cls, s.n_slots); s.d2h(d.inst, s.v_inst, s.n_slots);
+    return d;
 }
 
 std::tuple<std::vector<VotingMaximum>, std::map<std::string, double>> ImplicitShapeModel::detect(const PointCloud& pointCloud, bool hasNormals) {

@@ -251,6 +251,22 @@ private:
     int m_k;
 };
 
+// activation_strategy/activation_strategy_threshold.cpp:18-44: every codeword whose functor value is STRICTLY below Threshold, in
+// codebook row order -- any number per feature, zero included. Codebook::activate / castVotes take the list path for it
+// (ismhip_knn_threshold -> ismhip_train_activate_lists / ismhip_cast_votes_csr); UseDistanceRatio is inherited and never read.
+class ActivationStrategyThreshold : public ActivationStrategy {
+public:
+    ActivationStrategyThreshold();
+    static std::string getTypeStatic() { return "Threshold"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getK() const override { return 1; }             // no fixed fan-out (the K > 16 checks do not apply)
+    float getThreshold() const { return m_threshold; }
+    // the fixed-column interface does not fit a variable fan-out: throws (the codebook calls the list path instead)
+    int activateKNN(DeviceSession& s, const ismhip_codebook* codewords, const DeviceFeatures& f, int metric, int32_t* idx_out, float* dist_out, const float* desc = nullptr) const override;
+private:
+    float m_threshold;
+};
+
 // ---- Clustering (clustering/clustering.h:31-99) ----------------------------------------------------------------------------
 // operator() clusters the descriptors of all training features; getClusterCenters / getClusterIndices as in the reference, with
 // the centres left on the device (they are the rows of the activation codebook). "None": one cluster per feature, no centre matrix.
@@ -458,6 +474,13 @@ public:
     std::vector<std::vector<VotingMaximum>> detectBatch(const std::vector<const PointCloud*>& clouds);
 
     const Codebook* getCodebook() const { return m_codebook.get(); }
+    // diagnostics (tests): the features of the last train() (which = 0) or detectBatch() (which = 1) and the vote space of the last
+    // detectBatch(), copied to the host
+    struct FeatureDump { int dim = 0; uint32_t n = 0; std::vector<uint32_t> off; std::vector<float> desc, lrf, kx, ky, kz;
+                         std::vector<unsigned> cls, model; std::vector<float> center; };
+    struct VoteDump { std::vector<uint32_t> slot_off; std::vector<float> pos, weight; std::vector<int32_t> cls, inst; };
+    FeatureDump lastFeatures(int which) const;
+    VoteDump lastVotes() const;
     const Voting* getVoting() const { return m_voting.get(); }
     void setSignalsState(bool) {}
     void setLogging(bool l) { m_logging = l; }
@@ -513,6 +536,8 @@ private:
     bool m_logging = true;
     int m_device = 0;
     std::unique_ptr<DeviceSession> m_session;
+    std::shared_ptr<DeviceFeatures> m_last_train, m_last_detect;            // for lastFeatures()
+    std::vector<unsigned> m_last_fclass, m_last_fmodel; std::vector<float> m_last_fcenter;
 };
 
 // list files of eval_tool (eval_tool/eval_helpers.h:100-177)
