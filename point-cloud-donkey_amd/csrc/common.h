@@ -78,7 +78,7 @@ struct ismhip_codebook {
     unsigned short* words_bf16_hi = nullptr;   // [n_words_pad * dim_pad] RN_bf16(word)            (one allocation holds hi then lo)
     unsigned short* words_bf16_lo = nullptr;   // [n_words_pad * dim_pad] RN_bf16(word - hi)
     unsigned short* words_f16 = nullptr;       // [n_words_pad * dim_pad] RN_f16(word * f16_scale)  (same allocation)
-    unsigned short* words_f16t = nullptr;      // the f16 image in k_knn_l2_ring's streaming layout (k_to_f16_tiled), own allocation
+    unsigned short* words_f16t = nullptr;      // the f16 image in k_knn_l2_ring16's streaming layout (k_to_f16_tiled), own allocation
     int ld16 = 0;                    // row stride (halves) of the 16-bit images: dim rounded up to 64, zero padded
     float f16_scale = 1.f;           // power of two: largest |element| * f16_scale in [2^13, 2^14)
     bool words_nonneg = false;       // no negative (or NaN) element: k_knn_chi2 may drop the functor's "sum > 0" test (see there)
@@ -131,17 +131,11 @@ struct ismhip_ctx {
     std::set<const void*> attr_done;  // kernels whose MaxDynamicSharedMemorySize attribute has been raised on THIS ctx's device
     uint32_t knn_stage2_queries = 0;  // last two-stage ismhip_knn: queries the T = 2 stage could not prove (searched again with T = 4)
     bool knn_two_stage = true;   // env ISMHIP_KNN_TWOSTAGE=0: single-stage T = 4 search (A/B runs)
-    bool knn_small_tile = false; // env ISMHIP_KNN_TILE128=1: keep the bf16x3 kernel on its 128x128 tile (A/B runs)
     bool knn_join = true;        // env ISMHIP_KNN_JOIN=0: every workgroup of the ring kernel sweeps its split from the first tile (A/B runs); default: joined streams
     bool knn_qpanel2 = true;     // env ISMHIP_KNN_QPANEL2=0: stage 1 on <= 160 rotated coordinates WITHOUT the 256-query panel resident in LDS (A/B runs; default on: 27.5 -> 25.4 ms per bench launch)
-    bool knn_qpanel = false;     // env ISMHIP_KNN_QPANEL=1: the ring kernel on 256 x 128 tiles with the query panel resident in LDS (A/B runs)
-    bool knn_half = false;       // env ISMHIP_KNN_HALF=1: the ring kernel on 128 x 256 tiles, two workgroups per CU (A/B runs)
-    bool knn_ring32 = false;     // env ISMHIP_KNN_RING32=1: the ring kernel on the 32x32x16 MFMA shape instead of 16x16x32 (A/B runs)
+    bool knn_half = false;       // env ISMHIP_KNN_HALF=1: the ring kernel on 128 x 256 tiles, two workgroups per CU (A/B runs; stage-2 chunks of 4096-32767 queries take them anyway)
     int knn_splits = 0;          // env ISMHIP_KNN_SPLITS: force the number of codebook splits of the squared-L2 candidate kernels (A/B runs)
     int knn_t = 0;               // env ISMHIP_KNN_T = 2 | 3: candidates kept per slot (default 4 on the 16-bit paths); fewer = cheaper epilogue, more unproven slots
-    int knn_dbg = 0;             // env ISMHIP_KNN_DBG: timing experiments on k_knn_l2_ring (1 no epilogue, 2 no MFMA, 3 no DMA); results invalid
-    bool knn_no_ring = false;    // env ISMHIP_KNN_NORING=1: f16 candidates by the register-staged kernel instead of the LDS-DMA ring (A/B runs)
-    bool knn_kb32 = false;       // env ISMHIP_KNN_KB32=1: f16 candidates with 32-deep LDS slices instead of 64 (A/B runs)
     bool xcd_map = true;         // env ISMHIP_XCD_MAP=0: per-object kernels on the plain object-major block order instead of the XCD-local map (A/B runs)
     float grid_xfrac = 0.f;      // env ISMHIP_GRID_XFRAC: x cells this many times finer than y/z cells (default ISM_GRID_XFRAC; A/B runs)
     int shot_var = 0;            // env ISMHIP_SHOT_VAR=2: k_shot on the contiguous candidate sweep instead of 16 interleaved segments (A/B runs; same histogram)

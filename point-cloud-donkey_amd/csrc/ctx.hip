@@ -67,15 +67,10 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_SHOT_VAR"); ctx->shot_var = e ? atoi(e) : 0; }
     { const char* e = getenv("ISMHIP_KNN_TWOSTAGE"); ctx->knn_two_stage = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_JOIN"); ctx->knn_join = !(e && e[0] == '0'); }
-    { const char* e = getenv("ISMHIP_KNN_QPANEL"); ctx->knn_qpanel = e && e[0] == '1'; }
     { const char* e = getenv("ISMHIP_KNN_QPANEL2"); ctx->knn_qpanel2 = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_HALF"); ctx->knn_half = e && e[0] == '1'; }
-    { const char* e = getenv("ISMHIP_KNN_RING32"); ctx->knn_ring32 = e && e[0] == '1'; }
     { const char* e = getenv("ISMHIP_KNN_SPLITS"); ctx->knn_splits = e ? atoi(e) : 0; }
     { const char* e = getenv("ISMHIP_KNN_T"); ctx->knn_t = e ? atoi(e) : 0; }
-    { const char* e = getenv("ISMHIP_KNN_DBG"); ctx->knn_dbg = e ? atoi(e) : 0; }
-    { const char* e = getenv("ISMHIP_KNN_NORING"); ctx->knn_no_ring = e && e[0] == '1'; }
-    { const char* e = getenv("ISMHIP_KNN_KB32"); ctx->knn_kb32 = e && e[0] == '1'; }
     { const char* e = getenv("ISMHIP_KNN_HELL_EMIT"); ctx->knn_hell_emit = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_HELLINGER"); ctx->knn_hellinger = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_T1"); if (e) ctx->knn_t1 = atoi(e); }
@@ -85,7 +80,6 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_PREPASS"); ctx->knn_prepass = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_PCA_M"); ctx->knn_pca_m = e ? atoi(e) : -1; }
     { const char* e = getenv("ISMHIP_KNN_PCA_M2"); ctx->knn_pca_m2 = e ? atoi(e) : -1; }
-    { const char* e = getenv("ISMHIP_KNN_TILE128"); ctx->knn_small_tile = e && e[0] == '1'; }
     if (!own) { ctx->stream = (hipStream_t)stream; ctx->own_stream = false; }
     else {
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return ISMHIP_ERR_HIP; }

@@ -9,7 +9,7 @@
 //     ONE query per accumulator tile: the running top-T per query lives in registers with no cross-lane traffic and the Nq x Nc
 //     matrix is never materialised. Every kernel keeps, per lane slot, the T best candidates AND the value of the best candidate
 //     it dropped (the slot's bound).
-//       k_knn_l2_ring    f16 MFMA, 256x256 tile, LDS-DMA ring          default for launches >= 4096 queries x 4096 codewords
+//       k_knn_l2_ring16  f16 MFMA, 256x256 tile, LDS-DMA ring          default for launches >= 4096 queries x 4096 codewords
 //       k_knn_l2_mfma16  f16 (or bf16x3) MFMA, register-staged tiles   smaller launches; ISMHIP_KNN_MODE=bf16x3 for A/B runs
 //       k_knn_l2_mfma    f32 MFMA (exact fma chain)                    ISMHIP_KNN_MODE=f32: the independent route used by the tests
 //       k_knn_chi2       VALU 64x64 tile, v_rcp_f32                    chi-square is not a contraction
@@ -313,7 +313,7 @@ __global__ void k_to_f16(const float* __restrict__ src, int n, int dim, int ld, 
     dst[i] = __builtin_bit_cast(u16, hx);
 }
 
-// The same conversion into the layout k_knn_l2_ring / k_knn_l2_ring16 stream: [256-row tile][32-k slice][row][4 x 16-byte
+// The same conversion into the layout k_knn_l2_ring16 streams: [256-row tile][32-k slice][row][4 x 16-byte
 // segments], i.e. every (tile, slice) is one contiguous 16 KB block that already is the LDS image (segment p of row r holds
 // logical segment p ^ F[(r>>2)&3], F = {0,2,3,1}). A DMA instruction then copies 1 KB of consecutive, fully used 128-byte lines; with a row-major image each
 // 32-k slice touches only half of every line and the other half is fetched again one slice later.
@@ -356,6 +356,8 @@ __global__ void k_to_f16_tiled(const float* __restrict__ src, int n, int dim, in
 // EMIT = 1: no candidate lists; every row whose score is <= emit_tau[query] is appended to emit_list[query * emit_cap ...] (count in
 // emit_cnt[query], which may exceed emit_cap: the caller checks). Used by the chi-square search for the queries whose Hellinger
 // proof failed: with tau derived from the best chi-square value already found, the emitted rows are ALL rows that can still beat it.
+// dynamic LDS of k_knn_l2_mfma16 (bytes): two slices of the BM codeword and BN query rows (two images each for bf16x3) + |c|^2 of a tile
+constexpr size_t knn_mfma16_lds(int BM, int BN, int KB, int NTERM) { return (size_t)2 * (BM + BN) * KB * sizeof(u16) * (NTERM == 3 ? 2 : 1) + BM * sizeof(float); }
 template <int T, int WR, int WC, int MI, int NI, int NTERM, int KB, int EMIT = 0>
 __global__ __launch_bounds__(WR * WC * 64, 2) void k_knn_l2_mfma16(const u16* __restrict__ wh, const u16* __restrict__ wl,
                                                           const float* __restrict__ word_norm, int n_tiles_m, int ld, int k_steps,
@@ -555,235 +557,54 @@ __global__ void k_scale_norms(const float* __restrict__ norm, int n, const float
 // one being multiplied, in a ring of four 32 KB stages; the prefetch stream runs across codeword tiles, so it also covers the
 // top-T epilogue. One barrier per slice: "my DMAs for slice g have landed" (s_waitcnt vmcnt) + s_barrier makes slice g visible
 // to all waves and proves that everybody is done reading the stage that the next DMA overwrites.
-//   tile 256 codewords x 256 queries, 8 waves (2 x 4), wave = 128 x 64 = 4 x 2 MFMA tiles of 32x32x16 f16
-//   stage: rows 0..255 = codeword slice, 256..511 = query slice, 64 B per row (32 k), 16-B segments XOR-swizzled by (row>>2)&3;
-//          a DMA instruction fills 1 KB = 16 rows in LDS order, so the swizzle is applied to the SOURCE address of each lane
+//   tile 256 codewords x 256 queries, 8 waves (2 x 4), wave = 128 codeword rows x 64 queries = 8 x 4 MFMA tiles of 16x16x32 f16
+//   stage: rows 0..255 = codeword slice, 256..511 = query slice, 64 B per row (32 k), 16-B segments XOR-swizzled by F[(row>>2)&3];
+//          a DMA instruction fills 1 KB = 16 rows in LDS order, so the swizzle is applied to the SOURCE address of each lane (the
+//          images are stored already swizzled, see k_to_f16_tiled)
 //   |c|^2 of a tile arrives the same way (one 1 KB DMA by wave 0) in a ring of four tiles
-#define RG_BM 256
-#define RG_BN 256
-#define RG_KB 32
-#define RG_STAGES 4
-#define RG_STAGE_HALVES ((RG_BM + RG_BN) * RG_KB)
-__device__ __forceinline__ void lds_dma16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void lds_dma16_nt(const void* g, void* l) {      // non-temporal: see MI355X_MICROARCH 'nt-weights'
-    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 16, 0, 2);
-}
-template <int T, int DBG = 0>
-__global__ __launch_bounds__(512, 2) void k_knn_l2_ring(const u16* __restrict__ wh, const float* __restrict__ word_norm, int n_tiles_m, int ld, int k_steps,
-                                                        const u16* __restrict__ qh, int nq, const float* __restrict__ out_scale,
-                                                        int tiles_per_split, int n_splits,
-                                                        float* __restrict__ cand_val, int* __restrict__ cand_idx, int cand_stride,
-                                                        float* __restrict__ cand_bound, int bound_stride) {
-    constexpr int WR = 2, WC = 4, MI = 4, NI = 2, KB = RG_KB, BM = RG_BM, BN = RG_BN;
-    extern __shared__ __attribute__((aligned(16))) unsigned char knn_smem[];
-    u16* ring = (u16*)knn_smem;                                        // [RG_STAGES][512 rows][32 halves]
-    float* sCn = (float*)(ring + RG_STAGES * RG_STAGE_HALVES);        // [4][BM]
-    float* sThr = sCn + 4 * BM;                                        // [8 waves][NI][64]: thresholds published to the partner wave
-    const float oscale = out_scale[0];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform values must live in SGPRs (DMA bases, ring pointers)
-    const int wr = wv / WC, wc = wv % WC;
-    const int r = lane & 31, h = lane >> 5;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int split = jx % n_splits, qtile = (jx / n_splits) * 8 + xcd;
-    if (qtile * BN >= nq) return;
-    const int mt0 = split * tiles_per_split;
-    const int n_t = min(n_tiles_m, mt0 + tiles_per_split) - mt0;
-    if (n_t <= 0) return;
-    const int nk = (k_steps + 1) / 2;                                  // 32-deep slices
-    const int G = n_t * nk;                                            // slices in this workgroup's stream
-
-    // DMA role of this wave: waves 0-3 bring codeword rows, 4-7 query rows; 4 instructions x 16 rows per slice. The address of a
-    // lane is a wave-uniform 64-bit base (tile, slice, instruction: scalar arithmetic) plus a per-lane byte offset that never changes.
-    // (the 16-bit images are stored tile by tile, slice by slice, already swizzled: see k_to_f16_tiled -- a slice of a tile is a
-    // linear 16 KB copy; ld is unused here)
-    const bool dma_a = wv < 4;
-    const unsigned lane_off = (unsigned)(lane * 16);                   // bytes
-    const char* dbase = (dma_a ? (const char*)(wh + (size_t)mt0 * nk * (BM * KB)) : (const char*)(qh + (size_t)qtile * nk * (BN * KB)))
-                        + (wv & 3) * (64 * KB * 2);
-    const int ddst = (dma_a ? 0 : BM * KB) + (wv & 3) * 64 * KB;       // halves, wave-uniform
-    const size_t tile_stride = dma_a ? (size_t)nk * (BM * KB * 2) : 0; // bytes
-    int pt = 0, pkc = 0, pg = 0;                                       // prefetch cursor (tile, slice, stream index), clamped at the end
-    auto issue = [&]() {
-        u16* st = ring + (pg & (RG_STAGES - 1)) * RG_STAGE_HALVES + ddst;
-        if (wv == 0 && pkc == 0) lds_dma16(word_norm + (size_t)(mt0 + pt) * BM + lane * 4, sCn + (pt & 3) * BM);
-        const char* sp = ((DBG & 512) ? (dma_a ? (const char*)wh : (const char*)qh) + (wv & 3) * (64 * KB * 2) : dbase + pt * tile_stride) + (size_t)pkc * (BM * KB * 2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if ((DBG & 64) && dma_a) lds_dma16_nt(sp + j * (16 * KB * 2) + lane_off, st + j * 16 * KB);
-            else if ((DBG & 128) && !dma_a) lds_dma16_nt(sp + j * (16 * KB * 2) + lane_off, st + j * 16 * KB);
-            else lds_dma16(sp + j * (16 * KB * 2) + lane_off, st + j * 16 * KB);
-        }
-        ++pg;
-        if (pt * nk + pkc + 1 < G) { if (++pkc == nk) { pkc = 0; ++pt; } }   // past the end: re-load the last slice into a free stage
-    };
-    issue(); issue(); issue(); issue();
-
-    const int fragA = (wr * (MI * 32) + r) * KB, fragB = BM * KB + (wc * (NI * 32) + r) * KB;
-    const int fsw = (0x78 >> (2 * ((r >> 2) & 3))) & 3;                 // F[(row >> 2) & 3], see k_to_f16_tiled
-    const int so0 = ((0 + h) ^ fsw) << 3, so1 = ((2 + h) ^ fsw) << 3;    // k-step 0 / 1 segment of this lane
-    TopT<T + 1> top[NI];
-#pragma unroll
-    for (int n = 0; n < NI; ++n) top[n].init();
-    // The accumulators start at |c|^2 / out_scale instead of 0 (out_scale = -2/(s_q s_c) < 0, a power of two up to the factor -2,
-    // so the division is exact; word_norm here is that pre-scaled row, see k_scale_norms): after the last slice
-    // acc = (|c|^2 - 2 c.q) / out_scale, and ranking the scores ascending is ranking acc DESCENDING. The epilogue is then one
-    // compare per value against the lane's current threshold; TopT keeps -acc.
-    float thr[NI];
-#pragma unroll
-    for (int n = 0; n < NI; ++n) thr[n] = -__builtin_inff();
-    f32x16 acc[MI][NI];
-    // A query column is scanned by four lane slots of this workgroup (two accumulator halves h x two wave rows wr). A value that
-    // is not better than the (T+1)-th best of ANY of them can be dropped by all of them: thresholds only rise, every dropped value
-    // is <= the threshold its lane used at the time <= that lane's final threshold, which is what the slot reports as its bound.
-    // Sharing cuts the insertions ~4x. Partner half: one cross-lane read per tile; partner wave: a 4-byte slot in LDS (a stale
-    // value is only a lower, i.e. more conservative, threshold).
-    const int pw = (1 - wr) * WC + wc;
-#pragma unroll
-    for (int n = 0; n < NI; ++n) sThr[(wv * NI + n) * 64 + lane] = -__builtin_inff();
-
-    // Software pipeline. Step g multiplies slice g: its k-step-1 fragments (set Y) are read at the top of the step, behind the
-    // k-step-0 MFMAs (set X, read during step g-1); slice g+1's k-step-0 fragments are read behind the k-step-1 MFMAs, so no MFMA
-    // waits on an LDS round trip. ONE barrier per step, in the middle: before it every wave has waited for its own DMAs of slice
-    // g+1 (slices g+2, g+3 = 8 instructions stay in flight) and for its own LDS reads (lgkmcnt(0): slice g's stage is no longer
-    // read by anybody), after it slice g+1 is visible to all and slice g+4 is sent into slice g's stage: three slices (96 KB)
-    // of look-ahead in a ring of four stages.
-    f16x8 xa[MI], xb[NI], ya[MI], yb[NI];
-    asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");     // slice 0 (and the first |c|^2 row) landed
-    {
-#pragma unroll
-        for (int n = 0; n < NI; ++n) xb[n] = *(const f16x8*)(ring + fragB + n * 32 * KB + so0);
-#pragma unroll
-        for (int m = 0; m < MI; ++m) xa[m] = *(const f16x8*)(ring + fragA + m * 32 * KB + so0);
-    }
-    int t = 0, kc = 0;
-    for (int g = 0; g < G; ++g) {
-        const u16* st = ring + (g & (RG_STAGES - 1)) * RG_STAGE_HALVES;
-        const u16* sn = ring + ((g + 1) & (RG_STAGES - 1)) * RG_STAGE_HALVES;
-        if (!(DBG & 16) || g == 0) {
-#pragma unroll
-        for (int n = 0; n < NI; ++n) yb[n] = *(const f16x8*)(st + fragB + n * 32 * KB + so1);
-#pragma unroll
-        for (int m = 0; m < MI; ++m) ya[m] = *(const f16x8*)(st + fragA + m * 32 * KB + so1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-        if (kc == 0) {
-            // first slice of tile t: the accumulators START from the tile's row of |c|^2 / out_scale (pre-scaled per launch by
-            // k_scale_norms, landed by DMA with this slice), passed as the C operand -- no re-arming moves in the epilogue
-            const float* cnp = sCn + (t & 3) * BM + wr * (MI * 32) + 4 * h;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                f32x16 c0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f32x4 v = *(const f32x4*)(cnp + mi * 32 + 8 * j);     // rows 8j + 4h + 0..3 = elements 4j..4j+3
-                    c0[4 * j] = v[0]; c0[4 * j + 1] = v[1]; c0[4 * j + 2] = v[2]; c0[4 * j + 3] = v[3];
-                }
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[mi], xb[ni], c0, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-                if (!(DBG & 2)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xa[mi], xb[ni], acc[mi][ni], 0, 0, 0);
-                else acc[mi][ni][0] += (float)xa[mi][0] * (float)xb[ni][0];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(DBG & 32)) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (!(DBG & 4) || g < 4) issue();                               // slice g+4 -> the stage of slice g
-        if (!(DBG & 16)) {
-#pragma unroll
-        for (int n = 0; n < NI; ++n) xb[n] = *(const f16x8*)(sn + fragB + n * 32 * KB + so0);
-#pragma unroll
-        for (int m = 0; m < MI; ++m) xa[m] = *(const f16x8*)(sn + fragA + m * 32 * KB + so0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-                if (!(DBG & 2)) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ya[mi], yb[ni], acc[mi][ni], 0, 0, 0);
-                else acc[mi][ni][0] += (float)ya[mi][0] * (float)yb[ni][0];
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (++kc == nk) {
-            // epilogue of tile t. A lane inserts ~ (T+1)/n of the n values it has seen, so after the first tiles a 64-lane vector of
-            // values rarely holds an insertion: each vector is tested at wave level and the insertion code runs only for those.
-                        const int row0 = (mt0 + t) * BM + wr * (MI * 32) + 4 * h;
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-#pragma unroll
-                    for (int ni = 0; ni < NI; ++ni) {
-                        const float a = acc[mi][ni][e];
-                        if (DBG & 1) { if (e == 0) top[ni].v[0] += a; }
-                        else if (__builtin_expect(__any(a > thr[ni]), 0)) {
-                            if (DBG & 256) { top[ni].i[0] += 1; }
-                            else {
-                            if (a > thr[ni]) top[ni].push(-a, row0 + mi * 32 + (e & 3) + 8 * (e >> 2));
-                            thr[ni] = fmaxf(thr[ni], -top[ni].v[T]);
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-                float sh = fmaxf(thr[ni], __shfl_xor(thr[ni], 32, 64));
-                sThr[(wv * NI + ni) * 64 + lane] = sh;
-                thr[ni] = fmaxf(sh, sThr[(pw * NI + ni) * 64 + lane]);
-            }
-            kc = 0; ++t;
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the clamped re-loads past the end: LDS must be quiet before exit
-    // candidates: slot = split*(2*WR*T) + (wr*2 + h)*T + t; bound slot = split*(2*WR) + wr*2 + h
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-        const int qi = qtile * BN + wc * (NI * 32) + ni * 32 + r;
-        if (qi < nq) {
-#pragma unroll
-            for (int tt = 0; tt < T; ++tt) {                            // v = -acc, score = out_scale * acc (+inf stays +inf: out_scale < 0)
-                const size_t o = (size_t)qi * cand_stride + split * (2 * WR * T) + (wr * 2 + h) * T + tt;
-                cand_val[o] = -oscale * top[ni].v[tt]; cand_idx[o] = top[ni].i[tt];
-            }
-            cand_bound[(size_t)qi * bound_stride + split * (2 * WR) + (wr * 2 + h)] = oscale * thr[ni];   // the lane's final threshold
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same ring on v_mfma_f32_16x16x32_f16
-// ---------------------------------------------------------------------------------------------
-// A bare MFMA loop (tools/mfma_shape_bench.hip: operands in registers, two waves per SIMD, random f16) sustains 1.96 PFLOP/s
-// with the 16x16x32 shape against 1.63 with 32x32x16 on this chip: same cycles per FLOP, but the chip holds a higher clock on the
-// small shape (MI355X_MICROARCH 'DVFS give-back' item 7). Geometry, ring, DMA and synchronisation are those of k_knn_l2_ring;
-// what changes is the fragment and accumulator layout:
+// MFMA shape: a bare MFMA loop (tools/mfma_shape_bench.hip: operands in registers, two waves per SIMD, random f16) sustains
+// 1.96 PFLOP/s with the 16x16x32 shape against 1.63 with 32x32x16 on this chip: same cycles per FLOP, but the chip holds a higher
+// clock on the small shape (MI355X_MICROARCH 'DVFS give-back' item 7). Fragment and accumulator layout:
 //   A / B fragment of a 16-row tile: lane l reads row (l & 15), 16-byte segment (l >> 4) of the 64-byte slice row: ONE ds_read_b128
 //     per 16 x 32 tile (8 for the wave's 128 codeword rows + 4 for its 64 queries per slice); conflict-free with segments XOR-swizzled
 //     by F[(row >> 2) & 3], F = {0,2,3,1} (worked out against ds_read_b128's lane groups {0-3,12-15,20-27}, ...)
 //   C tile: lane l holds rows 4 (l >> 4) + j, j = 0..3, of column (l & 15): a lane now serves FOUR query columns (one per n-tile)
 //     with four codeword rows per tile each, so a query column is scanned by 8 lane slots per workgroup (4 row groups x 2 wave
 //     rows) and the kernel leaves 8 slots per codebook split (the host limits it to two splits: 64 candidates per query)
-#ifdef ISM_KNN_DBG_VARIANTS
-// DBG & 256: [0] wave-tiles, [1] with a hit, [2] flagged columns, [3] flagged groups, [4] flagged scores, [5] inserting lanes;
-// [8 + t] flagged scores of tile index t (t < 248) summed over waves
-__device__ unsigned long long g_knn_dbg[256];
-#endif
+// The accumulators start at |c|^2 / out_scale instead of 0 (out_scale = -2/(s_q s_c) < 0, a power of two up to the factor -2,
+// so the division is exact; word_norm here is that pre-scaled row, see k_scale_norms): after the last slice
+// acc = (|c|^2 - 2 c.q) / out_scale, and ranking the scores ascending is ranking acc DESCENDING. The epilogue is then one
+// compare per value against the lane's current threshold; TopT keeps -acc.
+// Shared thresholds: a value that is not better than the (T+1)-th best of ANY lane slot of its query column can be dropped by all
+// of them: thresholds only rise, every dropped value is <= the threshold its lane used at the time <= that lane's final
+// threshold, which is what the slot reports as its bound. Sharing cuts the insertions ~4x. Slots of the same wave: register
+// swaps once per tile; partner wave: a 4-byte slot in LDS (a stale value is only a lower, i.e. more conservative, threshold).
+#define RG_BN 256
+#define RG_KB 32
+__device__ __forceinline__ void lds_dma16(const void* g, void* l) {
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 16, 0, 0);
+}
+// LDS layout of k_knn_l2_ring16<T, WR, QP, PRE> in bytes: the ring of STAGES stages at 0, |c|^2 of four tiles at cn (a DMA always
+// delivers 256 floats), the thresholds published to the partner wave at thr (WR = 2: [8 waves][4 n-tiles][64]) and, QP = 2, the
+// query panel [ring_nk slices][256 queries][32 halves] at panel. The kernel takes its pointers from it, the host its launch size.
+template <int WR, int QP>
+struct Ring16Lds {
+    static constexpr int STAGES = WR == 2 ? 4 : 3, STAGE_HALVES = (QP ? WR * 128 : WR * 128 + RG_BN) * RG_KB;
+    static constexpr size_t cn = (size_t)STAGES * STAGE_HALVES * sizeof(u16);
+    static constexpr size_t thr = cn + 4 * 256 * sizeof(float);
+    static constexpr size_t panel = thr + (WR == 2 ? 8 * 4 * 64 * sizeof(float) : 0);
+    static constexpr size_t total(int ring_nk) { return panel + (QP ? (size_t)ring_nk * 256 * RG_KB * sizeof(u16) : 0); }
+};
 // WR = 2: the 256 x 256 tile, 8 waves (2 x 4), one workgroup per CU, four ring stages (three slices in flight).
-// WR = 1 (ISMHIP_KNN_HALF=1): a 128 x 256 tile, 4 waves, 76 KB of LDS: TWO independent workgroups per CU, three stages (two in
-// flight). The eight waves of the big workgroup meet at a barrier every slice, so their DMA issue and their epilogues coincide
-// and the matrix pipes idle meanwhile; two small workgroups drift apart and fill each other's gaps, at 1.5x the DMA per flop.
-// QP = 1 (ISMHIP_KNN_QPANEL=1, WR = 2, descriptors of at most 352 elements): a 256 x 128 tile whose QUERY panel (128 queries x all
-// slices, 88 KB) is loaded into LDS once per workgroup; only the codeword tiles stream through the ring. The 256 x 256 kernel
-// re-reads its 180 KB query tile for every codeword tile, and that is what falls out of the XCD L2s.
+// WR = 1 (stage-2 chunks of 4 096 - 32 767 queries, ISMHIP_KNN_HALF=1): a 128 x 256 tile, 4 waves, 76 KB of LDS: TWO independent
+// workgroups per CU, three stages (two in flight). The eight waves of the big workgroup meet at a barrier every slice, so their DMA
+// issue and their epilogues coincide and the matrix pipes idle meanwhile; two small workgroups drift apart and fill each other's
+// gaps, at 1.5x the DMA per flop.
+// QP = 2 (round 3; stage 1 on <= 160 rotated coordinates): the 256 x 256 tile WITH its whole query panel (256 queries x <= 5 slices,
+// <= 80 KB) resident in LDS: the ring then streams codeword slices only (16 KB per step instead of 32 KB, half the DMA
+// instructions). QP = 0 re-reads its 180 KB query tile for every codeword tile, and that is what falls out of the XCD L2s
+// (DESIGN §5); the panel did not fit next to a four-stage ring at 11 slices, and a 256 x 128 tile pays for it with half the
+// queries per tile.
 // PRE = 1 (WR = 2, QP = 0): the SAMPLING PRE-PASS. The workgroup sweeps every tile_step-th codeword tile (one split) and keeps, per
 // query column, only the best score it meets; thr_out[query] = that score (lowered by a few ulps). The main launch (PRE = 0) then
 // STARTS every lane slot of the query from thr_init[query] instead of -inf. Why this is sound for ANY start value: thresholds only
@@ -793,29 +614,26 @@ __device__ unsigned long long g_knn_dbg[256];
 // and refines itself independently (measured: 28 inserting lanes per wave and tile, 27 % of the kernel at 4 slices per tile); the
 // best of a 1/16 sample is about the 16th best score of the query overall, so with it as the start only a few dozen scores per
 // QUERY (not per list) ever reach the insertion code.
-template <int T, int WR = 2, int DBG = 0, int QP = 0, int PRE = 0>
+template <int T, int WR = 2, int QP = 0, int PRE = 0>
 __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __restrict__ wh, const float* __restrict__ word_norm, int n_tiles_m, int ld, int k_steps,
                                                           const u16* __restrict__ qh, int nq, const float* __restrict__ out_scale,
                                                           int tiles_per_split, int n_splits,
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int cand_stride,
                                                           float* __restrict__ cand_bound, int bound_stride, unsigned int* __restrict__ stream_clock,
                                                           const float* __restrict__ thr_init, float* __restrict__ thr_out, int tile_step, float thr_relax) {
-    constexpr int WC = 4, MT = 8, NT = QP == 1 ? 2 : 4, KB = RG_KB, BM = WR * 128, BN = QP == 1 ? 128 : RG_BN;
-    constexpr int PROWS = QP == 2 ? 256 : 128;                           // query rows of the resident panel
-    // QP = 2 (round 3; stage 1 on <= 160 rotated coordinates): the 256 x 256 tile WITH its whole query panel (256 queries x <= 5 slices,
-    // <= 80 KB) resident in LDS: the ring then streams codeword slices only (16 KB per step instead of 32 KB, half the DMA
-    // instructions); the panel did not fit next to a four-stage ring at 11 slices, and QP = 1 pays for it with half the queries per tile
-    constexpr int STAGES = WR == 2 ? 4 : 3, STAGE_HALVES = (QP ? BM : BM + BN) * KB, CNS = 256;
+    using L = Ring16Lds<WR, QP>;
+    constexpr int WC = 4, MT = 8, NT = 4, KB = RG_KB, BM = WR * 128, BN = RG_BN;
+    constexpr int STAGES = L::STAGES, STAGE_HALVES = L::STAGE_HALVES, CNS = 256;
     extern __shared__ __attribute__((aligned(16))) unsigned char knn_smem[];
     u16* ring = (u16*)knn_smem;                                        // [STAGES][BM + BN rows][32 halves] (QP: codeword rows only)
-    float* sCn = (float*)(ring + STAGES * STAGE_HALVES);              // [4][CNS]: |c|^2 of four tiles (a DMA always delivers 256 floats)
-    float* sThr = sCn + 4 * CNS;                                       // [8 waves][NT][64] (WR = 2 only)
-    u16* panel = (u16*)(sThr + 8 * NT * 64);                           // QP: [slices][PROWS queries][32 halves]
+    float* sCn = (float*)(knn_smem + L::cn);                           // [4][CNS]: |c|^2 of four tiles
+    float* sThr = (float*)(knn_smem + L::thr);                         // [8 waves][NT][64] (WR = 2 only)
+    u16* panel = (u16*)(knn_smem + L::panel);                          // QP: [slices][256 queries][32 halves]
     const float oscale = out_scale[0];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform values must live in SGPRs (DMA bases, ring pointers)
     const int wr = wv / WC, wc = wv % WC;
     const int fr = lane & 15, fq = lane >> 4;
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
@@ -846,23 +664,21 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
 
     // DMA shares per slice (pieces of 16 rows x 64 B = 1 KB per wave instruction). WR = 2: waves 0-3 bring 64 codeword rows each,
     // waves 4-7 64 query rows each; WR = 1: every wave brings 32 codeword rows and 64 query rows. Both images are stored in
-    // 256-row tiles [tile][slice][row][64 B]; a 128-row codeword tile is one half of such a block.
+    // 256-row tiles [tile][slice][row][64 B]; a 128-row codeword tile is one half of such a block. The address of a lane is a
+    // wave-uniform 64-bit base (tile, slice, instruction: scalar arithmetic) plus a per-lane byte offset that never changes.
     constexpr int NA = QP ? 2 : (WR == 2 ? 4 : 2), NB = 4;
     const bool dma_a = QP || WR == 1 || wv < 4, dma_b = !QP && (WR == 1 || wv >= 4);
     const unsigned lane_off = (unsigned)(lane * 16);
     const int row_a = QP ? wv * 32 : (WR == 2 ? (wv & 3) * 64 : wv * 32), row_b = (wv & 3) * 64;
-    const char* qbase = QP == 2 ? (const char*)(qh + (size_t)qtile * nk * (256 * KB)) + (wv * 32) * (KB * 2)
-                      : QP ? (const char*)(qh + (size_t)(qtile >> 1) * nk * (256 * KB)) + ((qtile & 1) * 128 + wv * 16) * (KB * 2)
+    const char* qbase = QP ? (const char*)(qh + (size_t)qtile * nk * (256 * KB)) + (wv * 32) * (KB * 2)
                            : (const char*)(qh + (size_t)qtile * nk * (BN * KB)) + row_b * (KB * 2);
-    if (QP == 2) {       // the query panel: wave w brings rows 32 w .. 32 w + 31 of every slice (two 16-row pieces)
+    if (QP) {            // the query panel: wave w brings rows 32 w .. 32 w + 31 of every slice (two 16-row pieces)
         for (int s_ = 0; s_ < nk; ++s_) {
             lds_dma16(qbase + (size_t)s_ * (256 * KB * 2) + lane_off, panel + (s_ * 256 + wv * 32) * KB);
             lds_dma16(qbase + (size_t)s_ * (256 * KB * 2) + 16 * KB * 2 + lane_off, panel + (s_ * 256 + wv * 32 + 16) * KB);
         }
-    } else if (QP) {     // the query panel: wave w brings rows 16 w .. 16 w + 15 of every slice
-        for (int s_ = 0; s_ < nk; ++s_) lds_dma16(qbase + (size_t)s_ * (256 * KB * 2) + lane_off, panel + (s_ * 128 + wv * 16) * KB);
     }
-    int pt = 0, pkc = 0, ps = 0;
+    int pt = 0, pkc = 0, ps = 0;                                       // prefetch cursor (tile, slice, stage), clamped at the end
     auto issue = [&]() {
         u16* st = ring + ps * STAGE_HALVES;
         const int tt = tile_of(pt);
@@ -870,21 +686,15 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
         if (dma_a) {
             const char* sp = (const char*)wh + ((size_t)(WR == 2 ? tt : (tt >> 1)) * nk + pkc) * (256 * KB * 2) + ((WR == 2 ? 0 : (tt & 1) * 128) + row_a) * (KB * 2);
 #pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                if (DBG & 128) lds_dma16_nt(sp + j * (16 * KB * 2) + lane_off, st + (row_a + j * 16) * KB);   // timing / traffic experiments
-                else lds_dma16(sp + j * (16 * KB * 2) + lane_off, st + (row_a + j * 16) * KB);
-            }
+            for (int j = 0; j < NA; ++j) lds_dma16(sp + j * (16 * KB * 2) + lane_off, st + (row_a + j * 16) * KB);
         }
         if (dma_b) {
             const char* sp = qbase + (size_t)pkc * (BN * KB * 2);
 #pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                if (DBG & 1024) lds_dma16_nt(sp + j * (16 * KB * 2) + lane_off, st + BM * KB + (row_b + j * 16) * KB);
-                else lds_dma16(sp + j * (16 * KB * 2) + lane_off, st + BM * KB + (row_b + j * 16) * KB);
-            }
+            for (int j = 0; j < NB; ++j) lds_dma16(sp + j * (16 * KB * 2) + lane_off, st + BM * KB + (row_b + j * 16) * KB);
         }
         if (++ps == STAGES) ps = 0;
-        if (pt * nk + pkc + 1 < G) { if (++pkc == nk) { pkc = 0; ++pt; } }
+        if (pt * nk + pkc + 1 < G) { if (++pkc == nk) { pkc = 0; ++pt; } }   // past the end: re-load the last slice into a free stage
     };
 #pragma unroll
     for (int i = 0; i < STAGES; ++i) issue();
@@ -900,17 +710,18 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
         if (!PRE && thr_init) { const int qi_ = qtile * BN + wc * (NT * 16) + n * 16 + fr; if (qi_ < nq) thr[n] = thr_init[qi_]; }
     }
     f32x4 acc[MT][NT];
-#ifdef ISM_KNN_DBG_VARIANTS
-    unsigned dbg_c[6] = {0, 0, 0, 0, 0, 0};
-#endif
     const int pw = (1 - wr) * WC + wc;
     if (WR == 2) {
 #pragma unroll
         for (int n = 0; n < NT; ++n) sThr[(wv * NT + n) * 64 + lane] = -__builtin_inff();
     }
 
-    // pipeline as in k_knn_l2_ring, with the fragments split by codeword rows instead of k-steps: X = tiles 0-3 (read during the
-    // previous step), Y = tiles 4-7 and the four query fragments (read at the top of the step)
+    // Software pipeline. Step g multiplies slice g, its fragments split by codeword rows: the query fragments are read at the top of
+    // the step, set Y (m-tiles 4-7) behind the MFMAs of set X (m-tiles 0-3, read during step g-1), and slice g+1's set X behind the
+    // MFMAs of set Y, so no MFMA waits on an LDS round trip. ONE barrier per step, in the middle: before it every wave has waited
+    // for its own DMAs of slice g+1 (WR = 2, QP = 0: slices g+2, g+3 = 8 instructions stay in flight) and for its own LDS reads
+    // (lgkmcnt(0): slice g's stage is no longer read by anybody), after it slice g+1 is visible to all and slice g+STAGES is sent
+    // into slice g's stage: STAGES - 1 slices of look-ahead.
     f16x8 xa[4], ya[4], bq[NT];
     if (QP) asm volatile("s_waitcnt vmcnt(6)\n\ts_barrier" ::: "memory");        // panel + slice 0 landed (2 pieces per wave and slice)
     else asm volatile("s_waitcnt vmcnt(12)\n\ts_barrier" ::: "memory");
@@ -922,10 +733,8 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
         const u16* st = ring + gs * STAGE_HALVES;
         const u16* sn = ring + gn * STAGE_HALVES;
         gs = gn;
-        if (!(DBG & 16) || g == 0) {
 #pragma unroll
-        for (int n = 0; n < NT; ++n) bq[n] = *(const f16x8*)((QP ? panel + kc * (PROWS * KB) : st) + fragB + n * 16 * KB);
-        }
+        for (int n = 0; n < NT; ++n) bq[n] = *(const f16x8*)((QP ? panel + kc * (256 * KB) : st) + fragB + n * 16 * KB);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         // first slice of a tile: the accumulators START from the tile's pre-scaled |c|^2 row (rows 16 mt + 4 fq + j), passed as
@@ -936,30 +745,28 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
             if (kc == 0) {
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
-                    const f32x4 c0 = (DBG & 2048) ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(cnp + (mb + mt) * 16);
+                    const f32x4 c0 = *(const f32x4*)(cnp + (mb + mt) * 16);
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) { if (!(DBG & 2)) acc[mb + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bq[nt], c0, 0, 0, 0); else acc[mb + mt][nt] = c0; }
-                    if (!(DBG & 16) || g == 0) nxt[mt] = *(const f16x8*)(nsrc + mt * 16 * KB);
+                    for (int nt = 0; nt < NT; ++nt) acc[mb + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bq[nt], c0, 0, 0, 0);
+                    nxt[mt] = *(const f16x8*)(nsrc + mt * 16 * KB);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) if (!(DBG & 2)) acc[mb + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bq[nt], acc[mb + mt][nt], 0, 0, 0);
-                    if (!(DBG & 16) || g == 0) nxt[mt] = *(const f16x8*)(nsrc + mt * 16 * KB);
+                    for (int nt = 0; nt < NT; ++nt) acc[mb + mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt], bq[nt], acc[mb + mt][nt], 0, 0, 0);
+                    nxt[mt] = *(const f16x8*)(nsrc + mt * 16 * KB);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         };
         mma4(0, xa, ya, st + fragA + 4 * 16 * KB);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(DBG & 32)) {
-            if (QP) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else if (WR == 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        if (!(DBG & 4) || g < 4) issue();
+        if (QP) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        else if (WR == 2) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        issue();                                                       // slice g + STAGES -> the stage of slice g
         __builtin_amdgcn_sched_barrier(0);
         mma4(4, ya, xa, sn + fragA);
         __builtin_amdgcn_s_setprio(0);
@@ -979,13 +786,9 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
                     }
                     thr[nt] = m;
                 }
-            } else if (DBG & 1) {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) top[nt].v[0] += acc[mt][nt][0];
             } else {
-                // Epilogue. A scalar branch right behind the vector compare it depends on stalls ~19 cycles, and 128 of those pairs
+                // Epilogue. A lane inserts ~ (T+1)/n of the n values it has seen, so after the first tiles a column rarely holds an
+                // insertion. A scalar branch right behind the vector compare it depends on stalls ~19 cycles, and 128 of those pairs
                 // per tile were a good part of the kernel. So: the largest of a column's 32 scores by 16 v_max3_f32, ONE compare
                 // per column into its own SGPR pair, one branch per tile (measured: the test itself is free, 13.0 ms with and
                 // without it); only a column that does hold a score above its threshold is walked.
@@ -1008,17 +811,10 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
                 unsigned long long any_hit = 0ull;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) any_hit |= hit[nt];
-#ifdef ISM_KNN_DBG_VARIANTS
-                if (DBG & 256) { ++dbg_c[0]; if (any_hit != 0ull) ++dbg_c[1]; }
-#endif
-                if (DBG & 64) { if (any_hit != 0ull) top[0].i[0] += 1; }
-                else if (__builtin_expect(any_hit != 0ull, 0)) {
+                if (__builtin_expect(any_hit != 0ull, 0)) {
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         if (hit[nt] == 0ull) continue;
-#ifdef ISM_KNN_DBG_VARIANTS
-                        if (DBG & 256) ++dbg_c[2];
-#endif
                         // Every step ends in a workgroup barrier, so a tile's epilogue costs what it costs the SLOWEST of the eight
                         // waves: keep the walk of a flagged column short. The largest of each 4-row group (two instructions per
                         // group), eight compares into eight SGPR pairs, eight scalar tests; only a group that holds a score above
@@ -1038,9 +834,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
                             if (gk[mt] == 0ull) continue;
-#ifdef ISM_KNN_DBG_VARIANTS
-                            if (DBG & 256) ++dbg_c[3];
-#endif
                             unsigned long long mk[4];
 #pragma unroll
                             for (int j = 0; j < 4; ++j) mk[j] = __ballot(acc[mt][nt][j] > thr[nt]);
@@ -1048,9 +841,6 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
 #pragma unroll
                             for (int j = 0; j < 4; ++j) {
                                 if (mk[j] == 0ull) continue;
-#ifdef ISM_KNN_DBG_VARIANTS
-                                if (DBG & 256) { ++dbg_c[4]; dbg_c[5] += __popcll(mk[j]); if (lane == 0 && t < 248) atomicAdd(&g_knn_dbg[8 + t], 1ull); }
-#endif
                                 const float a = acc[mt][nt][j];
                                 top[nt].push_flat(a > thr[nt] ? -a : __builtin_inff(), row0 + mt * 16 + j);
                                 asm("v_max_f32_e64 %0, %1, -%2" : "=v"(thr[nt]) : "v"(thr[nt]), "v"(top[nt].v[T]));
@@ -1061,10 +851,9 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
             }
             // thresholds shared by the 8 lane slots of a query column: the four row groups of this wave (lanes fr, fr+16, fr+32,
             // fr+48) by two register swaps (v_permlane32_swap / v_permlane16_swap: no LDS round trip), then the partner wave row
-            // through LDS (see k_knn_l2_ring)
+            // through LDS (see the header)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                if (DBG & 64) asm volatile("" : "+v"(thr[nt]));
                 const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr[nt]), __float_as_uint(thr[nt]), false, false);
                 float sh;
                 asm("v_max_f32 %0, %1, %2" : "=v"(sh) : "v"(__uint_as_float(h[0])), "v"(__uint_as_float(h[1])));
@@ -1079,10 +868,7 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
             kc = 0; ++t;
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ISM_KNN_DBG_VARIANTS
-    if ((DBG & 256) && lane == 0) for (int c = 0; c < 6; ++c) atomicAdd(&g_knn_dbg[c], (unsigned long long)dbg_c[c]);
-#endif
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the clamped re-loads past the end: LDS must be quiet before exit
     if (PRE) {
         // thr[] is the best over this wave's four row groups and (through sThr, one tile late) the partner wave row; one more exchange
         // behind a barrier makes it the best of the whole sample: the nearest SAMPLED row in the stage-1 coordinates. The start value
@@ -1333,7 +1119,7 @@ struct VerifyParams {
     float dabs_c;     // f16 candidates: worst-case absolute error of one codebook element (2^-14 / scale), else 0
     const float* dabs_q;   // f16 candidates: the same for the query batch (device scalar), else nullptr
     float sqrt_dim;   // sqrt(dim_pad)
-    float cn_acc;     // k_knn_l2_ring adds |c|^2 through the accumulator: extra 1.01 (K+1) 2^-23 |c|max^2 on the score, else 0
+    float cn_acc;     // k_knn_l2_ring16 adds |c|^2 through the accumulator: extra 1.01 (K+1) 2^-23 |c|max^2 on the score, else 0
 };
 // absolute part of the candidate kernel's dot-product error: sum |dq_i c_i| + |q_i dc_i| + |dq_i dc_i| with |dq_i| <= dq, |dc_i| <= dc
 __device__ __forceinline__ float knn_abs_err(const VerifyParams& vp, float qn2) {
@@ -1890,18 +1676,155 @@ __global__ void k_rule(int nq, float thr, const int32_t* __restrict__ idx3, cons
 }
 
 // stage1 != nullptr: FIRST stage of the two-stage search -- candidates + exact re-rank + proof only; the unproven queries are
-// left in the queue (*stage1 = {flag_count, qrec}) for the caller instead of going to the exact scan. tname: timer of the
-// candidate kernel.
+// left in the queue (*stage1 = {flag_count, qrec}) for the caller instead of going to the exact scan.
 struct KnnStage1 { uint32_t* flag_count; uint32_t* qrec; };
+// what the caller of run_knn asks for beyond the search itself
+struct KnnRequest {
+    KnnStage1* stage1 = nullptr;
+    const char* tname = nullptr;       // timer of the candidate kernel
+    bool many_splits = false;          // few queries: as many codebook splits as fill the chip, folded into one slot (k_knn_merge_splits)
+    int use_pca = 0;                   // 1: stage-1 image, 2: stage-2 image (pca.hip)
+    const float* hell_q = nullptr;     // chi-square only: sqrt(q) rows of dim_pad floats -> Hellinger candidates (k_knn_rerank_hell)
+    bool half = false;                 // the 128 x 256 ring tile (k_knn_l2_ring16<T, 1>), as with ISMHIP_KNN_HALF=1
+};
+
+// error model of the candidate scores for the proofs (k_knn_rerank, k_knn_rerank_hell, k_hell_tau, k_thr_tau). mode as in KnnPlan;
+// f16: qsc = the query batch's scalars (k_to_f16), cn_acc = the caller charges |c|^2 carried through the accumulator
+VerifyParams knn_verify_params(const ismhip_codebook* xb, int dim_pad, int mode, const uint32_t* qsc, bool cn_acc) {
+    VerifyParams vp;
+    vp.ku = 1.01f * (float)dim_pad * KNN_U;
+    // relative part of the candidate kernel's dot error (see the kernels): representation + accumulation (<= 2^-23 per add, any order)
+    vp.dot_rel = mode == 0 ? (2.002f * 4.8828125e-04f + 1.01f * (float)dim_pad * 1.1920929e-07f)
+               : mode == 1 ? (3.1f * 1.52587890625e-05f + 1.01f * 3.f * (float)dim_pad * 1.1920929e-07f) : vp.ku;
+    vp.cmax2 = xb->max_norm2;
+    vp.dabs_c = mode == 0 ? 6.103515625e-05f / xb->f16_scale : 0.f;
+    vp.dabs_q = mode == 0 ? (const float*)(qsc + 2) : nullptr;
+    vp.sqrt_dim = sqrtf((float)dim_pad);
+    vp.cn_acc = mode == 0 && cn_acc ? 1.01f * (float)(dim_pad + 1) * 1.1920929e-07f : 0.f;
+    return vp;
+}
+
+// the dynamic-LDS cap of a kernel is raised once per ctx (per device), to the largest size any launch of that kernel uses
+int knn_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes) {
+    if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); ctx->attr_done.insert(kern); }
+    return ISMHIP_OK;
+}
+
+// How run_knn runs one search. knn_plan decides it from the request, the ctx switches and the codebook, without side effects.
+enum KnnCand { KNN_CAND_F32, KNN_CAND_CHI2, KNN_CAND_MFMA16, KNN_CAND_RING16 };
+struct KnnPlan {
+    bool hell;                  // Hellinger candidates: squared L2 on the sqrt images of the shadow codebook
+    int mode;                   // squared-L2 candidates: 0 f16, 1 bf16x3, 2 exact f32; -1 chi-square
+    KnnCand cand;
+    const void* kern;           // KNN_CAND_MFMA16 / KNN_CAND_RING16: the kernel instance (nullptr: not built)
+    int BM, BN, threads;        // codeword rows and queries per tile, threads per workgroup
+    bool big_tile, half, qpanel2, pca, merged, prepass, join;
+    int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
+    int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
+    int fb_tiles_per_split, fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout (k_knn_fallback's wr_rows)
+    size_t lds, lds_cap;        // dynamic LDS of this launch, and the largest any launch of the kernel uses
+};
+
+template <int T>
+KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, int k, const KnnRequest& rq) {
+    KnnPlan p{};
+    // hell_q != nullptr (chi-square only): candidates come from the squared-L2 kernels run on the SQUARE-ROOT images (Hellinger lower
+    // bound, see k_knn_rerank_hell): xb = the shadow codebook that owns those images
+    p.hell = rq.hell_q != nullptr && metric == ISMHIP_METRIC_CHI2 && cb->chi_shadow;
+    const ismhip_codebook* xb = p.hell ? cb->chi_shadow : cb;
+    const bool l2 = p.hell || metric == ISMHIP_METRIC_L2SQ;
+    // candidate kernel for squared L2: f16 (default), bf16x3 (ISMHIP_KNN_MODE=bf16x3) or the exact-f32 MFMA contraction
+    // (ISMHIP_KNN_MODE=f32); the last two are kept for A/B runs and as the reference points of the error model tests
+    // short descriptors (FPFH-33: values up to 100, |q||c| ~ 1e4): the f16 error bound is of the order of the neighbour distances, most
+    // proofs fail and the exact scan takes over (measured: 135 ms of scan per 524288 queries). The exact-f32 MFMA contraction costs
+    // 2 Nq Nc D flop at ~125 TFLOP/s, which for D <= 64 is cheaper than the 16-bit kernels' fixed overheads -- and it proves everything.
+    const PcaImage& PI = rq.use_pca == 2 ? cb->pca2 : cb->pca;
+    const bool short_dim = cb->dim <= 64 && ctx->knn_mode == 0 && !(rq.use_pca && PI.m > 0);     // (stage 1 of a short-descriptor codebook with an f16 stage-1 image: pca.hip)
+    p.mode = !l2 ? -1 : (p.hell ? 0 : (short_dim ? 2 : (ctx->knn_mode == 0 && cb->words_f16 ? 0 : (ctx->knn_mode <= 1 && cb->words_bf16_hi ? 1 : 2))));
+    const bool use_lp = p.mode == 0 || p.mode == 1;
+    p.big_tile = use_lp && nq >= 4096 && cb->n_words_pad >= 4096;       // 256x256 tile, 8 waves
+    // (the ring kernel prefetches four slices ahead and keeps the |c|^2 rows of four tiles: a tile must have at least two slices)
+    const bool ring = p.big_tile && p.mode == 0 && xb->words_f16t && (cb->dim + 15) / 16 > 2;
+    p.half = ring && (rq.half || ctx->knn_half);                       // 128 x 256 tile, two workgroups per CU (k_knn_l2_ring16<T, 1>)
+    // 256 x 256 tile with the whole query panel resident (k_knn_l2_ring16<T, 2, 2>): stage 1 on a rotated image of <= 160 coordinates
+    p.qpanel2 = ring && !p.half && ctx->knn_qpanel2 && rq.use_pca && PI.m > 0 && PI.m <= 160;
+    // stage 1 of the two-stage search on the rotated, truncated image (pca.hip): same kernel, pca_m / 32 slices instead of dim / 32
+    p.pca = rq.use_pca && ring && PI.m > 0;
+    p.ring_nk = p.pca ? PI.m / 32 : ((cb->dim + 15) / 16 + 1) / 2;     // 32-k slices per row in the tiled images
+    p.merged = rq.many_splits && l2 && use_lp && !p.big_tile;
+    p.join = ring && ctx->knn_join;
+    p.BM = !l2 ? CHI_B : (p.half ? 128 : (p.big_tile ? 256 : KNN_BM));
+    p.BN = !l2 ? CHI_B : (p.big_tile ? 256 : KNN_BN);
+    p.slots = ring && !p.half ? 8 : 4;                                 // 16x16x32 MFMA shape: 8 lane slots per query and split
+    p.n_qt = (nq + p.BN - 1) / p.BN;
+    const int n_mt = cb->n_words_pad / p.BM;
+    if (l2) {
+        const int max_s = (p.hell ? 64 * KNN_HELL_CPL : 64) / (p.slots * T);
+        // at least three codebook splits (two when the candidate slots allow no more): with one, the 32 workgroups of an XCD hold 32
+        // different query tiles (6 MB of f16 queries re-read per codeword tile) and fall out of its 4 MB L2; two splits halve that
+        // working set (measured 21.0 -> 19.9 ms at 262144 queries), three cost the same time as two and fetch a fifth less from
+        // beyond the L2 (joined streams, DESIGN §5); four are 1.5 % slower
+        // (stage 1 on the rotated image: two -- with 4-6 slices per tile the epilogue is a larger share of the kernel, and every split
+        // is another eight candidate lists per query to fill: 29.8 -> 28.1 ms per bench launch)
+        p.n_splits = std::max(1, std::min(std::min(max_s, n_mt), std::max(p.pca ? 2 : 3, (1024 + p.n_qt - 1) / p.n_qt)));
+        // ... as long as a workgroup still has a few dozen tiles to amortise its prologue over (10 k-word codebook, 40 tiles: 1 / 2 / 3
+        // splits = 3.81 / 4.18 / 4.51 ms) and the launch fills the chip without them
+        if (p.big_tile && p.n_qt >= 512) p.n_splits = std::min(p.n_splits, std::max(1, n_mt / 32));
+        // Hellinger candidates for chi-square: as many splits as the candidate slots allow (up to eight, at least four tiles each) --
+        // the bound of a proof has to lie beyond EVERY row whose Hellinger distance is below the best chi-square value, and
+        // those are dozens to hundreds (CSHOT-1344, 10 k words, measured: median 28, 90th percentile 131, 99th 352)
+        if (p.hell) p.n_splits = std::max(1, std::min(std::min(max_s, 8), n_mt / 4));
+        if (ctx->knn_splits > 0) p.n_splits = std::max(1, std::min(std::min(max_s, n_mt), ctx->knn_splits));
+        // few queries (stage 2 of the two-stage search): cut the codebook into as many splits as it takes to fill the chip; the
+        // candidates of all splits are then folded into one slot of KNN_MERGE_KEEP by k_knn_merge_splits
+        if (p.merged) p.n_splits = std::max(1, std::min(n_mt, (1024 + 8 * ((p.n_qt + 7) / 8) - 1) / (8 * ((p.n_qt + 7) / 8))));
+        p.cand_per_split = p.slots * T;
+    } else {
+        const int max_s = 64 / T;
+        p.n_splits = std::max(1, std::min(std::min(max_s, n_mt), (2048 + p.n_qt - 1) / p.n_qt));
+        if (k > T) p.n_splits = std::max(p.n_splits, std::min(std::min(max_s, n_mt), (2 * k + T - 1) / T));    // at least 2k candidates to re-rank
+        p.cand_per_split = T;
+    }
+    p.tiles_per_split = (n_mt + p.n_splits - 1) / p.n_splits;
+    p.n_splits = (n_mt + p.tiles_per_split - 1) / p.tiles_per_split;
+    p.n_cand = p.n_splits * p.cand_per_split;
+    p.n_bound = l2 ? p.n_splits * p.slots : p.n_splits;
+    // sampling pre-pass (stage 1 of the two-stage search on the 256 x 256 kernel, codebooks of >= 128 tiles): the best score
+    // every query meets in every 16th codeword tile becomes the start threshold of all its lane slots (see the kernel)
+    // (not for an untruncated stage-1 image: with nothing left out there is no scale to relax the start value by, and the
+    // unrelaxed best of the sample is the nearest neighbour itself too often)
+    p.prepass = rq.stage1 && ring && !p.half && ctx->knn_prepass && n_mt >= 128 && !(p.pca && PI.resid2 <= 0.f);
+    p.fb_tiles_per_split = p.merged ? n_mt : p.tiles_per_split;
+    p.fb_layout = p.merged ? -2 : (p.half ? -3 : (ring ? -1 : (p.big_tile ? 128 : 64)));
+    p.threads = 256;
+    if (!l2) p.cand = KNN_CAND_CHI2;
+    else if (!use_lp) p.cand = KNN_CAND_F32;
+    else if (ring) {
+        p.cand = KNN_CAND_RING16;
+        p.threads = p.half ? 256 : 512;
+        if (p.half) { p.kern = (const void*)k_knn_l2_ring16<T, 1>; p.lds = p.lds_cap = Ring16Lds<1, 0>::total(0); }
+        else if (p.qpanel2) { p.kern = (const void*)k_knn_l2_ring16<T, 2, 2>; p.lds = Ring16Lds<2, 2>::total(p.ring_nk); p.lds_cap = Ring16Lds<2, 2>::total(160 / 32); }
+        else { p.kern = (const void*)k_knn_l2_ring16<T, 2>; p.lds = p.lds_cap = Ring16Lds<2, 0>::total(0); }
+    } else {
+        // bf16x3 on either tile (the two bf16x3 images only fit LDS with 32-deep slices), f16 on the 128x128 tile (f16 launches big
+        // enough for the 256x256 tile take the ring)
+        p.cand = KNN_CAND_MFMA16;
+        p.threads = p.big_tile ? 512 : 256;
+        if (p.mode == 1) p.kern = p.big_tile ? (const void*)k_knn_l2_mfma16<T, 2, 4, 4, 2, 3, 32> : (const void*)k_knn_l2_mfma16<T, 2, 2, 2, 2, 3, 32>;
+        else if (!p.big_tile) p.kern = (const void*)k_knn_l2_mfma16<T, 2, 2, 2, 2, 1, 64>;
+        p.lds = p.lds_cap = knn_mfma16_lds(p.BM, p.BN, p.mode == 1 ? 32 : 64, p.mode == 1 ? 3 : 1);
+    }
+    return p;
+}
+
 template <int T>
 int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k,
-            int32_t* idx_out, float* dist_out, KnnStage1* stage1 = nullptr, const char* tname = nullptr, bool many_splits = false, int use_pca = 0 /* 1: stage-1 image, 2: stage-2 image */, const float* hell_q = nullptr) {
-    // hell_q != nullptr (chi-square only): candidates come from the squared-L2 kernels run on the SQUARE-ROOT images (Hellinger lower
-    // bound, see k_knn_rerank_lb): xb = the shadow codebook that owns those images, hell_q = sqrt(q) rows of dim_pad floats
-    const bool hell = hell_q != nullptr && metric == ISMHIP_METRIC_CHI2 && cb->chi_shadow;
-    const ismhip_codebook* xb = hell ? cb->chi_shadow : cb;
-    const int cmetric = hell ? ISMHIP_METRIC_L2SQ : metric;
+            int32_t* idx_out, float* dist_out, const KnnRequest& rq = KnnRequest()) {
     if (cb->dim_pad / 16 > KNN_FB_MAXJ) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: descriptor longer than 1344 not built");
+    const KnnPlan p = knn_plan<T>(ctx, cb, metric, nq, k, rq);
+    if (p.cand == KNN_CAND_MFMA16 && !p.kern) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: f16 256x256 tile without the ring not built");
+    const ismhip_codebook* xb = p.hell ? cb->chi_shadow : cb;
+    const PcaImage& PI = rq.use_pca == 2 ? cb->pca2 : cb->pca;
     const float* qq = q; int ldq = cb->dim;
     if (cb->dim_pad != cb->dim) {
         float* qpad = (float*)ism_scratch(ctx, SCR_QPAD, (size_t)nq * cb->dim_pad * sizeof(float));
@@ -1911,71 +1834,9 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
         ISM_CHECK_LAUNCH(ctx, "k_pad_rows");
         qq = qpad; ldq = cb->dim_pad;
     }
-    int n_splits, cand_per_split, n_cand, tiles_per_split;
-    // candidate kernel for squared L2: f16 (default), bf16x3 (ISMHIP_KNN_MODE=bf16x3) or the exact-f32 MFMA contraction
-    // (ISMHIP_KNN_MODE=f32); the last two are kept for A/B runs and as the reference points of the error model tests
-    // short descriptors (FPFH-33: values up to 100, |q||c| ~ 1e4): the f16 error bound is of the order of the neighbour distances, most
-    // proofs fail and the exact scan takes over (measured: 135 ms of scan per 524288 queries). The exact-f32 MFMA contraction costs
-    // 2 Nq Nc D flop at ~125 TFLOP/s, which for D <= 64 is cheaper than the 16-bit kernels' fixed overheads -- and it proves everything.
-    const PcaImage& PI = use_pca == 2 ? cb->pca2 : cb->pca;
-    const bool short_dim = cb->dim <= 64 && ctx->knn_mode == 0 && !(use_pca && PI.m > 0);     // (stage 1 of a short-descriptor codebook with an f16 stage-1 image: pca.hip)
-    const int mode = cmetric != ISMHIP_METRIC_L2SQ ? -1 : (hell ? 0 : (short_dim ? 2 : (ctx->knn_mode == 0 && cb->words_f16 ? 0 : (ctx->knn_mode <= 1 && cb->words_bf16_hi ? 1 : 2))));
-    const bool use_lp = mode == 0 || mode == 1;
-    const bool big_tile = use_lp && nq >= 4096 && cb->n_words_pad >= 4096 && !ctx->knn_small_tile;      // 256x256 tile, 8 waves
-    const int BM0 = cmetric == ISMHIP_METRIC_L2SQ ? (big_tile ? 256 : KNN_BM) : CHI_B;
-    int BNq = cmetric == ISMHIP_METRIC_L2SQ ? (big_tile ? 256 : KNN_BN) : CHI_B;
-    const int wr_rows = big_tile ? 128 : 64;
-    // (the ring kernels prefetch four slices ahead and keep the |c|^2 rows of four tiles: a tile must have at least two slices)
-    const bool use_ring = big_tile && mode == 0 && !ctx->knn_no_ring && xb->words_f16t && (cb->dim + 15) / 16 > 2;
-    const bool ring16 = use_ring && !ctx->knn_ring32;                  // 16x16x32 MFMA shape: 8 lane slots per query and split instead of 4
-    const bool half = ring16 && ctx->knn_half;                         // 128 x 256 tile, two workgroups per CU (k_knn_l2_ring16<T, 1>)
-    const bool qpanel = ring16 && !half && ctx->knn_qpanel && ((cb->dim + 15) / 16 + 1) / 2 <= 11;   // 256 x 128 tile, query panel resident in LDS
-    if (qpanel) BNq = 128;
-    // 256 x 256 tile with the whole query panel resident (k_knn_l2_ring16<T, 2, 0, 2>): stage 1 on a rotated image of <= 160 coordinates
-    const bool qpanel2 = ring16 && !half && !qpanel && ctx->knn_qpanel2 && use_pca && PI.m > 0 && PI.m <= 160;
-    const int BM = half ? 128 : BM0;
-    const int slots = ring16 && !half ? 8 : 4;
-    // stage 1 of the two-stage search on the rotated, truncated image (pca.hip): same kernel, pca_m / 32 slices instead of dim / 32
-    const bool pca = use_pca && use_ring && PI.m > 0;
-    const int ring_nk = pca ? PI.m / 32 : ((cb->dim + 15) / 16 + 1) / 2;   // 32-k slices per row in the tiled images
-    const bool merged = many_splits && cmetric == ISMHIP_METRIC_L2SQ && use_lp && !big_tile;
-    if (cmetric == ISMHIP_METRIC_L2SQ) {
-        const int n_qt = (nq + BNq - 1) / BNq, n_mt = cb->n_words_pad / BM;
-        const int max_s = (hell ? 64 * KNN_HELL_CPL : 64) / (slots * T);
-        // at least three codebook splits (two when the candidate slots allow no more): with one, the 32 workgroups of an XCD hold 32
-        // different query tiles (6 MB of f16 queries re-read per codeword tile) and fall out of its 4 MB L2; two splits halve that
-        // working set (measured 21.0 -> 19.9 ms at 262144 queries), three cost the same time as two and fetch a fifth less from
-        // beyond the L2 (joined streams, DESIGN §5); four are 1.5 % slower
-        // (stage 1 on the rotated image: two -- with 4-6 slices per tile the epilogue is a larger share of the kernel, and every split
-        // is another eight candidate lists per query to fill: 29.8 -> 28.1 ms per bench launch)
-        n_splits = std::max(1, std::min(std::min(max_s, n_mt), std::max(pca ? 2 : 3, (1024 + n_qt - 1) / n_qt)));
-        // ... as long as a workgroup still has a few dozen tiles to amortise its prologue over (10 k-word codebook, 40 tiles: 1 / 2 / 3
-        // splits = 3.81 / 4.18 / 4.51 ms) and the launch fills the chip without them
-        if (big_tile && n_qt >= 512) n_splits = std::min(n_splits, std::max(1, n_mt / 32));
-        // Hellinger candidates for chi-square: as many splits as the candidate slots allow (up to eight, at least four tiles each) --
-        // the bound of a proof has to lie beyond EVERY row whose Hellinger distance is below the best chi-square value, and
-        // those are dozens to hundreds (CSHOT-1344, 10 k words, measured: median 28, 90th percentile 131, 99th 352)
-        if (hell) n_splits = std::max(1, std::min(std::min(max_s, 8), n_mt / 4));
-        if (ctx->knn_splits > 0) n_splits = std::max(1, std::min(std::min(max_s, n_mt), ctx->knn_splits));
-        // few queries (stage 2 of the two-stage search): cut the codebook into as many splits as it takes to fill the chip; the
-        // candidates of all splits are then folded into one slot of KNN_MERGE_KEEP by k_knn_merge_splits
-        if (merged) n_splits = std::max(1, std::min(n_mt, (1024 + 8 * ((n_qt + 7) / 8) - 1) / (8 * ((n_qt + 7) / 8))));
-        tiles_per_split = (n_mt + n_splits - 1) / n_splits;
-        n_splits = (n_mt + tiles_per_split - 1) / tiles_per_split;
-        cand_per_split = slots * T;
-    } else {
-        const int n_qt = (nq + CHI_B - 1) / CHI_B, n_mt = cb->n_words_pad / CHI_B;
-        const int max_s = 64 / T;
-        n_splits = std::max(1, std::min(std::min(max_s, n_mt), (2048 + n_qt - 1) / n_qt));
-        if (k > T) n_splits = std::max(n_splits, std::min(std::min(max_s, n_mt), (2 * k + T - 1) / T));    // at least 2k candidates to re-rank
-        tiles_per_split = (n_mt + n_splits - 1) / n_splits;
-        n_splits = (n_mt + tiles_per_split - 1) / tiles_per_split;
-        cand_per_split = T;
-    }
-    n_cand = n_splits * cand_per_split;
-    int n_bound = cmetric == ISMHIP_METRIC_L2SQ ? n_splits * slots : n_splits;
-    float* cand_val = (float*)ism_scratch(ctx, SCR_KNN_CAND_VAL, (size_t)nq * (n_cand + n_bound + (merged ? KNN_MERGE_KEEP + 1 : 0)) * sizeof(float));
-    int* cand_idx = (int*)ism_scratch(ctx, SCR_KNN_CAND_IDX, (size_t)nq * (n_cand + (merged ? KNN_MERGE_KEEP : 0)) * sizeof(int));
+    int n_cand = p.n_cand, n_bound = p.n_bound;
+    float* cand_val = (float*)ism_scratch(ctx, SCR_KNN_CAND_VAL, (size_t)nq * (n_cand + n_bound + (p.merged ? KNN_MERGE_KEEP + 1 : 0)) * sizeof(float));
+    int* cand_idx = (int*)ism_scratch(ctx, SCR_KNN_CAND_IDX, (size_t)nq * (n_cand + (p.merged ? KNN_MERGE_KEEP : 0)) * sizeof(int));
     // queue of unproven work: 16 counters | query records [nq*3] | items [nq*n_bound*2] | item results [nq*n_bound*4] u64
     const size_t q_items = (size_t)nq * n_bound;
     uint32_t* flags = (uint32_t*)ism_scratch(ctx, SCR_KNN_FLAGS, (16 + 3 * (size_t)nq + 2 * q_items) * sizeof(uint32_t) + 8 + (q_items + KNN_FB_UNITS) * (k > 4 ? KNN_MAX_K : 4) * sizeof(unsigned long long));
@@ -1985,23 +1846,24 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
     unsigned long long* item_out = (unsigned long long*)(((uintptr_t)(items + 2 * q_items) + 7) & ~(uintptr_t)7);
     ISM_HIP(ctx, hipMemsetAsync(flag_count, 0, 64, ctx->stream));
     uint32_t* qsc = flag_count + 4;      // f16 mode: [0] absmax bits of the query batch, [1] -2/(s_q s_c), [2] 2^-14/s_q
+    const bool ring = p.cand == KNN_CAND_RING16;
     u16 *q_hi = nullptr, *q_lo = nullptr;
-    if (use_lp) {
-        const int nq_pad = use_ring ? (nq + 255) / 256 * 256 : (nq + BNq - 1) / BNq * BNq;
-        const size_t tot = use_ring ? (size_t)(nq_pad / 256) * ring_nk * 8192 : (size_t)nq_pad * cb->ld16;
+    if (p.mode == 0 || p.mode == 1) {
+        const int nq_pad = ring ? (nq + 255) / 256 * 256 : (nq + p.BN - 1) / p.BN * p.BN;
+        const size_t tot = ring ? (size_t)(nq_pad / 256) * p.ring_nk * 8192 : (size_t)nq_pad * cb->ld16;
         q_hi = (u16*)ism_scratch(ctx, SCR_KNN_QSPLIT, tot * 2 * sizeof(u16));
         if (!q_hi) return ISMHIP_ERR_NOMEM;
         q_lo = q_hi + tot;
-        if (pca) {
+        if (p.pca) {
             TimerScope tr(ctx, "knn_rotate");
             const int rc = ism_pca_rotate_queries(ctx, cb, &PI, qq, nq, ldq, q_hi);
             if (rc != ISMHIP_OK) return rc;
             ++ctx->knn_pca_launches;
-        } else if (mode == 0) {
-            const float* cq = hell ? hell_q : qq; const int cldq = hell ? cb->dim_pad : ldq;     // Hellinger: the images are made from sqrt(q)
+        } else if (p.mode == 0) {
+            const float* cq = p.hell ? rq.hell_q : qq; const int cldq = p.hell ? cb->dim_pad : ldq;     // Hellinger: the images are made from sqrt(q)
             hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, qsc);
             ISM_CHECK_LAUNCH(ctx, "k_absmax");
-            if (use_ring) hipLaunchKernelGGL(k_to_f16_tiled, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad / 256, ring_nk, qsc, xb->f16_scale, q_hi);
+            if (ring) hipLaunchKernelGGL(k_to_f16_tiled, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad / 256, p.ring_nk, qsc, xb->f16_scale, q_hi);
             else hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad, cb->ld16, qsc, xb->f16_scale, q_hi);
             ISM_CHECK_LAUNCH(ctx, "k_to_f16");
         } else {
@@ -2010,150 +1872,93 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
         }
     }
     {
-        TimerScope ts(ctx, tname ? tname : (metric == ISMHIP_METRIC_L2SQ ? "knn_l2_mfma" : "knn_chi2"));      // chi-square: whichever kernel makes its candidates
-        if (use_lp) {
-            const int n_qt = (nq + BNq - 1) / BNq;
-            const dim3 grid(8 * ((n_qt + 7) / 8) * n_splits);
-            const u16* wh = mode == 0 ? xb->words_f16 : xb->words_bf16_hi;
-            const u16* wl = mode == 0 ? nullptr : xb->words_bf16_lo;
-            const int nterm = mode == 0 ? 1 : 3;
-            const int kb = (nterm == 1 && !ctx->knn_kb32) ? 64 : 32;       // the two bf16x3 images only fit LDS with 32-deep slices
-            const size_t lds = (size_t)2 * (BM + BNq) * kb * sizeof(u16) * (nterm == 3 ? 2 : 1) + BM * sizeof(float);
-            const void* kern;
-            int ai;
-            if (big_tile) {
-                if (nterm == 3) { kern = (const void*)k_knn_l2_mfma16<T, 2, 4, 4, 2, 3, 32>; ai = 0; }
-                else if (kb == 64) { kern = (const void*)k_knn_l2_mfma16<T, 2, 4, 4, 2, 1, 64>; ai = 1; }
-                else { kern = (const void*)k_knn_l2_mfma16<T, 2, 4, 4, 2, 1, 32>; ai = 2; }
-            } else {
-                if (nterm == 3) { kern = (const void*)k_knn_l2_mfma16<T, 2, 2, 2, 2, 3, 32>; ai = 3; }
-                else if (kb == 64) { kern = (const void*)k_knn_l2_mfma16<T, 2, 2, 2, 2, 1, 64>; ai = 4; }
-                else { kern = (const void*)k_knn_l2_mfma16<T, 2, 2, 2, 2, 1, 32>; ai = 5; }
+        TimerScope ts(ctx, rq.tname ? rq.tname : (metric == ISMHIP_METRIC_L2SQ ? "knn_l2_mfma" : "knn_chi2"));      // chi-square: whichever kernel makes its candidates
+        const dim3 grid(8 * ((p.n_qt + 7) / 8) * p.n_splits);
+        int n_tiles_m = cb->n_words_pad / p.BM, ld16 = cb->ld16, k_steps = p.pca ? PI.m / 16 : (cb->dim + 15) / 16, nq_ = nq, tps = p.tiles_per_split, nsp = p.n_splits, ncand = n_cand, nb = n_bound;
+        const u16* qh_ = q_hi;
+        const float* osc = (const float*)(qsc + 1);
+        if (ring) {
+            const int rc = knn_lds_cap(ctx, p.kern, p.lds_cap);
+            if (rc != ISMHIP_OK) return rc;
+            const u16* wh = xb->words_f16t;
+            const float* word_norm;
+            if (p.pca) { wh = PI.f16t; osc = PI.osc; word_norm = PI.cn_scaled; }      // scales fixed per codebook: the C operand is precomputed
+            else {
+                float* cn_scaled = (float*)ism_scratch(ctx, SCR_QNORM2, ((size_t)cb->n_words_pad + 256) * sizeof(float));   // the |c|^2 DMA of a 128-row tile reads 256 floats
+                if (!cn_scaled) return ISMHIP_ERR_NOMEM;
+                hipLaunchKernelGGL(k_scale_norms, dim3((cb->n_words_pad + 255) / 256), dim3(256), 0, ctx->stream, xb->word_norm, cb->n_words_pad, osc, cn_scaled);
+                ISM_CHECK_LAUNCH(ctx, "k_scale_norms");
+                word_norm = cn_scaled;
             }
-            if (use_ring) {
-                wh = xb->words_f16t;
-                const void* rk = ring16 ? (qpanel2 ? (const void*)k_knn_l2_ring16<T, 2, 0, 2> : qpanel ? (const void*)k_knn_l2_ring16<T, 2, 0, 1> : half ? (const void*)k_knn_l2_ring16<T, 1, 0> : (const void*)k_knn_l2_ring16<T, 2, 0>) : (const void*)k_knn_l2_ring<T, 0>;
-#ifdef ISM_KNN_DBG_VARIANTS
-                if (ring16) switch (ctx->knn_dbg) {       // 1 no epilogue, 2 no MFMA, 4 no DMA, 16 no fragment reads, 32 no barrier, 64 pre-test only, 256 counters
-                    case 1: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 1> : (const void*)k_knn_l2_ring16<T, 2, 1>; break;  case 2: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 2> : (const void*)k_knn_l2_ring16<T, 2, 2>; break;
-                    case 5: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 5> : (const void*)k_knn_l2_ring16<T, 2, 5>; break;  case 21: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 21> : (const void*)k_knn_l2_ring16<T, 2, 21>; break;
-                    case 53: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 53> : (const void*)k_knn_l2_ring16<T, 2, 53>; break; case 64: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 64> : (const void*)k_knn_l2_ring16<T, 2, 64>; break;
-                    case 256: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 256> : (const void*)k_knn_l2_ring16<T, 2, 256>; break;
-                    case 2048: rk = (const void*)k_knn_l2_ring16<T, 2, 2048>; break; case 2049: rk = (const void*)k_knn_l2_ring16<T, 2, 2049>; break; case 2069: rk = (const void*)k_knn_l2_ring16<T, 2, 2069>; break;
-                    case 128: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 128> : (const void*)k_knn_l2_ring16<T, 2, 128>; break; case 1024: rk = half ? (const void*)k_knn_l2_ring16<T, 1, 1024> : (const void*)k_knn_l2_ring16<T, 2, 1024>; break;
-                    default: break;
-                } else
-                switch (ctx->knn_dbg) {
-                    case 1: rk = (const void*)k_knn_l2_ring<T, 1>; break;  case 3: rk = (const void*)k_knn_l2_ring<T, 3>; break;
-                    case 5: rk = (const void*)k_knn_l2_ring<T, 5>; break;  case 7: rk = (const void*)k_knn_l2_ring<T, 7>; break;
-                    case 9: rk = (const void*)k_knn_l2_ring<T, 9>; break;  case 13: rk = (const void*)k_knn_l2_ring<T, 13>; break;
-                    case 15: rk = (const void*)k_knn_l2_ring<T, 15>; break; case 11: rk = (const void*)k_knn_l2_ring<T, 11>; break;
-                    case 21: rk = (const void*)k_knn_l2_ring<T, 21>; break; case 513: rk = (const void*)k_knn_l2_ring<T, 513>; break; case 256: rk = (const void*)k_knn_l2_ring<T, 256>; break; case 64: rk = (const void*)k_knn_l2_ring<T, 64>; break; case 128: rk = (const void*)k_knn_l2_ring<T, 128>; break; case 192: rk = (const void*)k_knn_l2_ring<T, 192>; break; case 53: rk = (const void*)k_knn_l2_ring<T, 53>; break; case 37: rk = (const void*)k_knn_l2_ring<T, 37>; break;
-                    default: break;
-                }
-#endif
-                const size_t rlds = qpanel2 ? (size_t)4 * 256 * RG_KB * sizeof(u16) + 4 * 256 * sizeof(float) + 8 * 4 * 64 * sizeof(float) + (size_t)ring_nk * 256 * RG_KB * sizeof(u16)
-                                  : qpanel ? (size_t)4 * 256 * RG_KB * sizeof(u16) + 4 * 256 * sizeof(float) + 8 * 2 * 64 * sizeof(float) + (size_t)ring_nk * 128 * RG_KB * sizeof(u16)
-                                  : half ? (size_t)3 * (128 + 256) * RG_KB * sizeof(u16) + 4 * 256 * sizeof(float)
-                                         : (size_t)RG_STAGES * RG_STAGE_HALVES * sizeof(u16) + 4 * RG_BM * sizeof(float) + 8 * 4 * 64 * sizeof(float);
-                if (ctx->knn_dbg || !ctx->attr_done.count(rk)) {          // per device, so remembered per ctx
-                    ISM_HIP(ctx, hipFuncSetAttribute(rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-                    ctx->attr_done.insert(rk);
-                }
-                const float* osc = (const float*)(qsc + 1);
-                const float* word_norm;
-                if (pca) { wh = PI.f16t; osc = PI.osc; word_norm = PI.cn_scaled; }      // scales fixed per codebook: the C operand is precomputed
-                else {
-                    float* cn_scaled = (float*)ism_scratch(ctx, SCR_QNORM2, ((size_t)cb->n_words_pad + 256) * sizeof(float));   // the |c|^2 DMA of a 128-row tile reads 256 floats
-                    if (!cn_scaled) return ISMHIP_ERR_NOMEM;
-                    hipLaunchKernelGGL(k_scale_norms, dim3((cb->n_words_pad + 255) / 256), dim3(256), 0, ctx->stream, xb->word_norm, cb->n_words_pad, osc, cn_scaled);
-                    ISM_CHECK_LAUNCH(ctx, "k_scale_norms");
-                    word_norm = cn_scaled;
-                }
-                int n_tiles_m = cb->n_words_pad / BM, ld16 = cb->ld16, k_steps = pca ? PI.m / 16 : (cb->dim + 15) / 16, nq_ = nq, tps = tiles_per_split, nsp = n_splits, ncand = n_cand, nb = n_bound;
-                const u16* qh_ = q_hi;
-                unsigned int* clock = nullptr;                                   // joined codeword streams (k_knn_l2_ring16), one clock per (XCD, split)
-                if (ring16 && ctx->knn_join) {
-                    clock = (unsigned int*)ism_scratch(ctx, SCR_KNN_CLOCK, 8 * 64 * sizeof(unsigned int));
-                    if (!clock) return ISMHIP_ERR_NOMEM;
-                    ISM_HIP(ctx, hipMemsetAsync(clock, 0, 8 * 64 * sizeof(unsigned int), ctx->stream));
-                }
-                // sampling pre-pass (stage 1 of the two-stage search on the 256 x 256 kernel, codebooks of >= 128 tiles): the best score
-                // every query meets in every 16th codeword tile becomes the start threshold of all its lane slots (see the kernel)
-                const float* thr_init = nullptr; float* thr_out = nullptr; int tile_step = 1;
-                // (not for an untruncated stage-1 image: with nothing left out there is no scale to relax the start value by, and the
-                // unrelaxed best of the sample is the nearest neighbour itself too often)
-                if (stage1 && ring16 && !half && !qpanel && ctx->knn_prepass && n_tiles_m >= 128 && ctx->knn_dbg == 0 && !(pca && PI.resid2 <= 0.f)) {
-                    float* thr0 = (float*)ism_scratch(ctx, SCR_KNN_THR0, (size_t)((nq + 255) / 256 * 256) * sizeof(float));
-                    if (!thr0) return ISMHIP_ERR_NOMEM;
-                    const void* pk = (const void*)k_knn_l2_ring16<T, 2, 0, 0, 1>;
-                    if (!ctx->attr_done.count(pk)) { ISM_HIP(ctx, hipFuncSetAttribute(pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); ctx->attr_done.insert(pk); }
-                    int one = 1, all = n_tiles_m, step = ctx->knn_pre_step; unsigned int* noclk = nullptr; const float* noinit = nullptr;
-                    // relaxation: gamma x the second moment the truncation leaves out (codeword + query side, taken as equal), in
-                    // accumulator units (score / out_scale); the original image truncates nothing
-                    float relax = 0.f;
-                    if (pca) relax = -ctx->knn_pre_gamma * 2.0f * PI.resid2 * (PI.sq * PI.sc * 0.5f);
-                    void* pargs[] = {&wh, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &nq_, &osc, &all, &one, &cand_val, &cand_idx, &ncand, &cand_bound, &nb, &noclk, &noinit, &thr0, &step, &relax};
-                    ISM_HIP(ctx, hipLaunchKernel(pk, dim3(8 * ((n_qt + 7) / 8)), dim3(512), pargs, rlds, ctx->stream));
-                    ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16<pre>");
-                    thr_init = thr0;
-                }
-                float no_relax = 0.f;
-                void* rargs[] = {&wh, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &nq_, &osc, &tps, &nsp, &cand_val, &cand_idx, &ncand, &cand_bound, &nb, &clock, &thr_init, &thr_out, &tile_step, &no_relax};
-                ISM_HIP(ctx, hipLaunchKernel(rk, grid, dim3(half ? 256 : 512), rargs, rlds, ctx->stream));
-                ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring");
-            } else {
-            (void)ai;
-            if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ctx->attr_done.insert(kern); }
-            const float* word_norm = xb->word_norm; const float* osc = (const float*)(qsc + 1);
-            int n_tiles_m = cb->n_words_pad / BM, ld16 = cb->ld16, k_steps = (cb->dim + 15) / 16, nq_ = nq, tps = tiles_per_split, nsp = n_splits, ncand = n_cand, nb = n_bound;
-            const u16* qh_ = q_hi; const u16* ql_ = q_lo;
+            unsigned int* clock = nullptr;                                   // joined codeword streams, one clock per (XCD, split)
+            if (p.join) {
+                clock = (unsigned int*)ism_scratch(ctx, SCR_KNN_CLOCK, 8 * 64 * sizeof(unsigned int));
+                if (!clock) return ISMHIP_ERR_NOMEM;
+                ISM_HIP(ctx, hipMemsetAsync(clock, 0, 8 * 64 * sizeof(unsigned int), ctx->stream));
+            }
+            const float* thr_init = nullptr; float* thr_out = nullptr; int tile_step = 1;
+            if (p.prepass) {
+                float* thr0 = (float*)ism_scratch(ctx, SCR_KNN_THR0, (size_t)((nq + 255) / 256 * 256) * sizeof(float));
+                if (!thr0) return ISMHIP_ERR_NOMEM;
+                const void* pk = (const void*)k_knn_l2_ring16<T, 2, 0, 1>;
+                const size_t plds = Ring16Lds<2, 0>::total(0);
+                const int rc2 = knn_lds_cap(ctx, pk, plds);
+                if (rc2 != ISMHIP_OK) return rc2;
+                int one = 1, all = n_tiles_m, step = ctx->knn_pre_step; unsigned int* noclk = nullptr; const float* noinit = nullptr;
+                // relaxation: gamma x the second moment the truncation leaves out (codeword + query side, taken as equal), in
+                // accumulator units (score / out_scale); the original image truncates nothing
+                float relax = 0.f;
+                if (p.pca) relax = -ctx->knn_pre_gamma * 2.0f * PI.resid2 * (PI.sq * PI.sc * 0.5f);
+                void* pargs[] = {&wh, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &nq_, &osc, &all, &one, &cand_val, &cand_idx, &ncand, &cand_bound, &nb, &noclk, &noinit, &thr0, &step, &relax};
+                ISM_HIP(ctx, hipLaunchKernel(pk, dim3(8 * ((p.n_qt + 7) / 8)), dim3(512), pargs, plds, ctx->stream));
+                ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16<pre>");
+                thr_init = thr0;
+            }
+            float no_relax = 0.f;
+            void* rargs[] = {&wh, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &nq_, &osc, &tps, &nsp, &cand_val, &cand_idx, &ncand, &cand_bound, &nb, &clock, &thr_init, &thr_out, &tile_step, &no_relax};
+            ISM_HIP(ctx, hipLaunchKernel(p.kern, grid, dim3(p.threads), rargs, p.lds, ctx->stream));
+            ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16");
+        } else if (p.cand == KNN_CAND_MFMA16) {
+            const int rc = knn_lds_cap(ctx, p.kern, p.lds_cap);
+            if (rc != ISMHIP_OK) return rc;
+            const u16* wh = p.mode == 0 ? xb->words_f16 : xb->words_bf16_hi;
+            const u16* wl = p.mode == 0 ? nullptr : xb->words_bf16_lo;
+            const float* word_norm = xb->word_norm;
+            const u16* ql_ = q_lo;
             const float* no_tau = nullptr; uint32_t* no_u = nullptr; int no_cap = 0;
             void* args[] = {&wh, &wl, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &ql_, &nq_, &osc, &tps, &nsp, &cand_val, &cand_idx, &ncand, &cand_bound, &nb, &no_tau, &no_u, &no_u, &no_cap};
-            ISM_HIP(ctx, hipLaunchKernel(kern, grid, dim3(big_tile ? 512 : 256), args, lds, ctx->stream));
+            ISM_HIP(ctx, hipLaunchKernel(p.kern, grid, dim3(p.threads), args, p.lds, ctx->stream));
             ISM_CHECK_LAUNCH(ctx, "k_knn_l2_mfma16");
-            }
-        } else if (cmetric == ISMHIP_METRIC_L2SQ) {
-            const int n_qt = (nq + KNN_BN - 1) / KNN_BN;
-            hipLaunchKernelGGL(k_knn_l2_mfma<T>, dim3(8 * ((n_qt + 7) / 8) * n_splits), dim3(256), 0, ctx->stream, cb->words, cb->word_norm,
-                               cb->n_words_pad / KNN_BM, cb->dim_pad, qq, nq, ldq, tiles_per_split, n_splits, cand_val, cand_idx, n_cand,
+        } else if (p.cand == KNN_CAND_F32) {
+            hipLaunchKernelGGL(k_knn_l2_mfma<T>, grid, dim3(256), 0, ctx->stream, cb->words, cb->word_norm,
+                               cb->n_words_pad / KNN_BM, cb->dim_pad, qq, nq, ldq, p.tiles_per_split, p.n_splits, cand_val, cand_idx, n_cand,
                                cand_bound, n_bound, std::min(16, cb->dim - (cb->dim_pad / KNN_BK - 1) * KNN_BK));
             ISM_CHECK_LAUNCH(ctx, "k_knn_l2_mfma");
         } else {
-            const int n_qt = (nq + CHI_B - 1) / CHI_B;
             uint32_t* q_negative = flag_count + 12;                 // zeroed with the counters above
             if (cb->words_nonneg) {
                 hipLaunchKernelGGL(k_any_negative, dim3(512), dim3(256), 0, ctx->stream, qq, nq, cb->dim, ldq, q_negative);
                 ISM_CHECK_LAUNCH(ctx, "k_any_negative");
             }
-            hipLaunchKernelGGL(k_knn_chi2<T>, dim3(n_qt, n_splits), dim3(256), 0, ctx->stream, cb->words, cb->n_words_pad, cb->dim_pad,
-                               qq, nq, ldq, cb->words_nonneg ? 1 : 0, q_negative, tiles_per_split, cand_val, cand_idx, n_cand, cand_bound, n_bound);
+            hipLaunchKernelGGL(k_knn_chi2<T>, dim3(p.n_qt, p.n_splits), dim3(256), 0, ctx->stream, cb->words, cb->n_words_pad, cb->dim_pad,
+                               qq, nq, ldq, cb->words_nonneg ? 1 : 0, q_negative, p.tiles_per_split, cand_val, cand_idx, n_cand, cand_bound, n_bound);
             ISM_CHECK_LAUNCH(ctx, "k_knn_chi2");
         }
     }
-    if (merged) {
+    if (p.merged) {
         float* m_val = cand_bound + (size_t)nq * n_bound; float* m_bound = m_val + (size_t)nq * KNN_MERGE_KEEP;
         int* m_idx = cand_idx + (size_t)nq * n_cand;
         hipLaunchKernelGGL(k_knn_merge_splits, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, nq, cand_val, cand_idx, n_cand, cand_bound, n_bound, m_val, m_idx, m_bound);
         ISM_CHECK_LAUNCH(ctx, "k_knn_merge_splits");
         cand_val = m_val; cand_idx = m_idx; cand_bound = m_bound; n_cand = KNN_MERGE_KEEP; n_bound = 1;
     }
-    VerifyParams vp;
-    vp.ku = 1.01f * (float)cb->dim_pad * KNN_U;
-    // relative part of the candidate kernel's dot error (see the kernels): representation + accumulation (<= 2^-23 per add, any order)
-    vp.dot_rel = mode == 0 ? (2.002f * 4.8828125e-04f + 1.01f * (float)cb->dim_pad * 1.1920929e-07f)
-               : mode == 1 ? (3.1f * 1.52587890625e-05f + 1.01f * 3.f * (float)cb->dim_pad * 1.1920929e-07f) : vp.ku;
-    vp.cmax2 = xb->max_norm2;
-    vp.dabs_c = mode == 0 ? 6.103515625e-05f / xb->f16_scale : 0.f;
-    vp.dabs_q = mode == 0 ? (const float*)(qsc + 2) : nullptr;
-    vp.sqrt_dim = sqrtf((float)cb->dim_pad);
-    vp.cn_acc = mode == 0 ? 1.01f * (float)(cb->dim_pad + 1) * 1.1920929e-07f : 0.f;
+    const VerifyParams vp = knn_verify_params(xb, cb->dim_pad, p.mode, qsc, true);
     {
     TimerScope trr(ctx, "knn_rerank");
-    if (pca) {
+    if (p.pca) {
         PcaVerify pv;
         const float acc_rel = 1.01f * (float)PI.m * 1.1920929e-07f;            // accumulation only: products of f16 values are exact in fp32
-        pv.qimg = q_hi; pv.nk = ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
+        pv.qimg = q_hi; pv.nk = p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
         pv.inv_sig2 = PI.inv_sig2; pv.d_rel = PI.d_rel; pv.dq_abs = PI.dq_abs;
         pv.dc = (PI.d_rel * sqrtf(cb->max_norm2) + PI.dc_abs) * 1.00001f;
         pv.cmax2 = PI.cmax2;
@@ -2164,22 +1969,22 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
         pv.ku = vp.ku;
         hipLaunchKernelGGL(k_knn_rerank_pca, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
                            qq, nq, ldq, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, pv, k, idx_out, dist_out, flag_count, qrec, items);
-    } else if (hell) {
+    } else if (p.hell) {
         hipLaunchKernelGGL(k_knn_rerank_hell, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                           qq, nq, ldq, hell_q, xb->shadow_perm, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, vp, k, idx_out, dist_out, flag_count, qrec, items);
+                           qq, nq, ldq, rq.hell_q, xb->shadow_perm, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, vp, k, idx_out, dist_out, flag_count, qrec, items);
     } else
     hipLaunchKernelGGL(k_knn_rerank, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
                        qq, nq, ldq, metric, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, vp, k, idx_out, dist_out, flag_count, qrec, items);
     ISM_CHECK_LAUNCH(ctx, "k_knn_rerank");
     }
-    if (stage1) { stage1->flag_count = flag_count; stage1->qrec = qrec; return ISMHIP_OK; }
+    if (rq.stage1) { rq.stage1->flag_count = flag_count; rq.stage1->qrec = qrec; return ISMHIP_OK; }
     {
         TimerScope ts(ctx, "knn_fallback");
-        const int fb_tps = merged ? cb->n_words_pad / BM : tiles_per_split, fb_lay = merged ? -2 : (half ? -3 : (ring16 ? -1 : wr_rows));
+        const int n_tiles = cb->n_words_pad / p.BM;
         if (k <= 4) hipLaunchKernelGGL(k_knn_fallback<4>, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, qq, ldq, metric, k,
-                                       fb_tps, cb->n_words_pad / BM, BM, fb_lay, flag_count, items, idx_out, dist_out, item_out, q_items);
+                                       p.fb_tiles_per_split, n_tiles, p.BM, p.fb_layout, flag_count, items, idx_out, dist_out, item_out, q_items);
         else hipLaunchKernelGGL(k_knn_fallback<KNN_MAX_K>, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, qq, ldq, metric, k,
-                                fb_tps, cb->n_words_pad / BM, BM, fb_lay, flag_count, items, idx_out, dist_out, item_out, q_items);
+                                p.fb_tiles_per_split, n_tiles, p.BM, p.fb_layout, flag_count, items, idx_out, dist_out, item_out, q_items);
         ISM_CHECK_LAUNCH(ctx, "k_knn_fallback");
         if (k <= 4) hipLaunchKernelGGL(k_knn_fallback_merge<4>, dim3(256), dim3(256), 0, ctx->stream, k, flag_count, qrec, item_out, q_items, idx_out, dist_out);
         else hipLaunchKernelGGL(k_knn_fallback_merge<KNN_MAX_K>, dim3(256), dim3(256), 0, ctx->stream, k, flag_count, qrec, item_out, q_items, idx_out, dist_out);
@@ -2214,8 +2019,9 @@ __global__ void k_knn_scatter_results(const uint32_t* __restrict__ list2, int n2
 
 int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out) {
     KnnStage1 s1{nullptr, nullptr};
-    int rc = ctx->knn_t1 == 1 && k == 1 ? run_knn<1>(ctx, cb, ISMHIP_METRIC_L2SQ, nq, q, k, idx_out, dist_out, &s1, nullptr, false, true)
-                                        : run_knn<2>(ctx, cb, ISMHIP_METRIC_L2SQ, nq, q, k, idx_out, dist_out, &s1, nullptr, false, true);
+    KnnRequest r1; r1.stage1 = &s1; r1.use_pca = 1;
+    int rc = ctx->knn_t1 == 1 && k == 1 ? run_knn<1>(ctx, cb, ISMHIP_METRIC_L2SQ, nq, q, k, idx_out, dist_out, r1)
+                                        : run_knn<2>(ctx, cb, ISMHIP_METRIC_L2SQ, nq, q, k, idx_out, dist_out, r1);
     if (rc != ISMHIP_OK) return rc;
     uint32_t n2u = 0;
     ISM_HIP(ctx, hipMemcpyAsync(&n2u, s1.flag_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2240,12 +2046,11 @@ int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const 
         // of four would allow four splits, but 1 % of these queries then fail their proof in a whole split and the exact scan costs
         // more than was won (measured: 9.18 vs 9.39 ms per step of 114 objects, 17.6 vs 15.0 of 227). The 128-query tile variant
         // (k_knn_l2_ring16<T, 1>: four lane slots per split, so four splits at T = 4) doubles the workgroups twice over instead.
-        const bool was_half = ctx->knn_half;
+        KnnRequest r2; r2.tname = "knn_stage2"; r2.many_splits = n < 4096;
         // (on the stage-2 image, if the codebook has one: 8 slices per tile instead of 11 on the bench data)
-        const int lvl2 = cb->pca2.m > 0 && !(n < 4096) ? 2 : 0;
-        if (n >= 4096 && n < 32768 && !ctx->knn_stage2_t4) ctx->knn_half = true;
-        rc = run_knn<4>(ctx, cb, ISMHIP_METRIC_L2SQ, n, q2 + (size_t)o * cb->dim, k, idx2 + (size_t)o * k, dist2 + (size_t)o * k, nullptr, "knn_stage2", n < 4096, lvl2);
-        ctx->knn_half = was_half;
+        r2.use_pca = cb->pca2.m > 0 && !(n < 4096) ? 2 : 0;
+        r2.half = n >= 4096 && n < 32768 && !ctx->knn_stage2_t4;
+        rc = run_knn<4>(ctx, cb, ISMHIP_METRIC_L2SQ, n, q2 + (size_t)o * cb->dim, k, idx2 + (size_t)o * k, dist2 + (size_t)o * k, r2);
         if (rc != ISMHIP_OK) return rc;
         o += n;
     }
@@ -2342,6 +2147,38 @@ __global__ __launch_bounds__(256) void k_hell_eval(int n2, const uint32_t* __res
     if (lane == 0 && best != ~0ull) { idx_out[qi] = (int)(best & 0xffffffffull); dist_out[qi] = __uint_as_float((unsigned)(best >> 32)); }
 }
 
+// The f16 EMIT sweep of the chi-square stage 2 (k_hell_tau) and the radius search (k_thr_tau): the f16 image qimg of n query rows qv
+// (row stride ldv, n_pad = n rounded up to 128; sc = the batch's f16 scalars, zeroed by the caller), the error model vp of its scores
+// (cn_acc: see knn_verify_params), tau[] by the caller's launch_tau(vp), then k_knn_l2_mfma16<EMIT> appends every row with
+// score <= tau[q] to rows[q * cap ...] (count in emit_cnt[q]).
+template <class LaunchTau>
+int knn_f16_emit_sweep(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_codebook* xb, const float* qv, int n, int ldv, int n_pad,
+                       uint32_t* sc, u16* qimg, bool cn_acc, VerifyParams& vp, LaunchTau launch_tau, const float* tau,
+                       uint32_t* emit_cnt, uint32_t* rows, int cap) {
+    hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, qv, n, cb->dim, ldv, sc);
+    ISM_CHECK_LAUNCH(ctx, "k_absmax");
+    const size_t tot = (size_t)n_pad * cb->ld16;
+    hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, qv, n, cb->dim, ldv, n_pad, cb->ld16, sc, xb->f16_scale, qimg);
+    ISM_CHECK_LAUNCH(ctx, "k_to_f16");
+    vp = knn_verify_params(xb, cb->dim_pad, 0, sc, cn_acc);
+    int rc = launch_tau(vp);
+    if (rc != ISMHIP_OK) return rc;
+    const void* kern = (const void*)k_knn_l2_mfma16<4, 2, 2, 2, 2, 1, 64, 1>;
+    const size_t lds = knn_mfma16_lds(128, 128, 64, 1);
+    rc = knn_lds_cap(ctx, kern, lds);
+    if (rc != ISMHIP_OK) return rc;
+    const int n_qt = n_pad / 128, n_mt = cb->n_words_pad / 128;
+    int nsp = std::max(1, std::min(n_mt / 2, (2048 + 8 * ((n_qt + 7) / 8) - 1) / (8 * ((n_qt + 7) / 8))));
+    int tps = (n_mt + nsp - 1) / nsp; nsp = (n_mt + tps - 1) / tps;
+    const u16* wh = xb->words_f16; const u16* wl = nullptr; const float* word_norm = xb->word_norm; const float* osc = (const float*)(sc + 1);
+    int n_tiles_m = n_mt, ld16 = cb->ld16, k_steps = (cb->dim + 15) / 16, nq_ = n, ncand = cb->n_words, nb = 0, cap_ = cap;
+    const u16* qh_ = qimg; const u16* ql_ = nullptr; float* nf = nullptr; int* ni = nullptr;
+    void* args[] = {&wh, &wl, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &ql_, &nq_, &osc, &tps, &nsp, &nf, &ni, &ncand, &nf, &nb, &tau, &emit_cnt, &rows, &cap_};
+    ISM_HIP(ctx, hipLaunchKernel(kern, dim3(8 * ((n_qt + 7) / 8) * nsp), dim3(256), args, lds, ctx->stream));
+    ISM_CHECK_LAUNCH(ctx, "k_knn_l2_mfma16<emit>");
+    return ISMHIP_OK;
+}
+
 // chi-square, two stages: Hellinger candidates on the matrix cores + exact chi-square re-rank and proof (k_knn_rerank_hell); the
 // queries that stage cannot prove are gathered and go through the VALU chi-square kernel (k_knn_chi2) with its own proof and
 // exact scan. One 8-byte read-back (negative flag of the batch; later the number of unproven queries) synchronises the call.
@@ -2360,7 +2197,8 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
     if (neg) return ISMHIP_OK;                                          // not histogram data: the caller takes the VALU kernel
     taken = true;
     KnnStage1 s1{nullptr, nullptr};
-    int rc = run_knn<4>(ctx, cb, ISMHIP_METRIC_CHI2, nq, q, k, idx_out, dist_out, &s1, nullptr, false, false, sq);
+    KnnRequest rh; rh.stage1 = &s1; rh.hell_q = sq;
+    int rc = run_knn<4>(ctx, cb, ISMHIP_METRIC_CHI2, nq, q, k, idx_out, dist_out, rh);
     if (rc != ISMHIP_OK) return rc;
     uint32_t n2u = 0;
     ISM_HIP(ctx, hipMemcpyAsync(&n2u, s1.flag_count, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -2392,32 +2230,13 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
         ISM_HIP(ctx, hipMemsetAsync(cnt, 0, b_cnt, ctx->stream));
         hipLaunchKernelGGL(k_knn_gather_flagged, dim3(n2), dim3(256), 0, ctx->stream, s1.qrec, n2, (const float*)sq, dp, sq2, list2);
         ISM_CHECK_LAUNCH(ctx, "k_knn_gather_flagged");
-        hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, (const float*)sq2, n2, cb->dim, dp, sc);
-        ISM_CHECK_LAUNCH(ctx, "k_absmax");
-        const size_t tot = (size_t)n2p * cb->ld16;
-        hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)sq2, n2, cb->dim, dp, n2p, cb->ld16, sc, xb->f16_scale, qimg);
-        ISM_CHECK_LAUNCH(ctx, "k_to_f16");
         VerifyParams vp;
-        vp.ku = 1.01f * (float)dp * KNN_U;
-        vp.dot_rel = 2.002f * 4.8828125e-04f + 1.01f * (float)dp * 1.1920929e-07f;
-        vp.cmax2 = xb->max_norm2; vp.dabs_c = 6.103515625e-05f / xb->f16_scale; vp.dabs_q = (const float*)(sc + 2);
-        vp.sqrt_dim = sqrtf((float)dp); vp.cn_acc = 0.f;
-        hipLaunchKernelGGL(k_hell_tau, dim3((n2 + 3) / 4), dim3(256), 0, ctx->stream, n2, (const uint32_t*)list2, (const float*)sq2, cb->dim, dp, (const float*)dist_out, vp, tau);
-        ISM_CHECK_LAUNCH(ctx, "k_hell_tau");
-        {
-            const void* kern = (const void*)k_knn_l2_mfma16<4, 2, 2, 2, 2, 1, 64, 1>;
-            const size_t lds = (size_t)2 * (128 + 128) * 64 * sizeof(u16) + 128 * sizeof(float);
-            if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ctx->attr_done.insert(kern); }
-            const int n_qt = n2p / 128, n_mt = cb->n_words_pad / 128;
-            int nsp = std::max(1, std::min(n_mt / 2, (2048 + 8 * ((n_qt + 7) / 8) - 1) / (8 * ((n_qt + 7) / 8))));
-            int tps = (n_mt + nsp - 1) / nsp; nsp = (n_mt + tps - 1) / tps;
-            const u16* wh = xb->words_f16; const u16* wl = nullptr; const float* word_norm = xb->word_norm; const float* osc = (const float*)(sc + 1);
-            int n_tiles_m = n_mt, ld16 = cb->ld16, k_steps = (cb->dim + 15) / 16, nq_ = n2, ncand = cb->n_words, nb = 0, cap_ = cap;
-            const u16* qh_ = qimg; const u16* ql_ = nullptr; float* nf = nullptr; int* ni = nullptr; const float* tau_ = tau;
-            void* args[] = {&wh, &wl, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &ql_, &nq_, &osc, &tps, &nsp, &nf, &ni, &ncand, &nf, &nb, &tau_, &cnt, &rows, &cap_};
-            ISM_HIP(ctx, hipLaunchKernel(kern, dim3(8 * ((n_qt + 7) / 8) * nsp), dim3(256), args, lds, ctx->stream));
-            ISM_CHECK_LAUNCH(ctx, "k_knn_l2_mfma16<emit>");
-        }
+        rc = knn_f16_emit_sweep(ctx, cb, xb, sq2, n2, dp, n2p, sc, qimg, false, vp, [&](const VerifyParams& v) {
+            hipLaunchKernelGGL(k_hell_tau, dim3((n2 + 3) / 4), dim3(256), 0, ctx->stream, n2, (const uint32_t*)list2, (const float*)sq2, cb->dim, dp, (const float*)dist_out, v, tau);
+            ISM_CHECK_LAUNCH(ctx, "k_hell_tau");
+            return ISMHIP_OK;
+        }, tau, cnt, rows, cap);
+        if (rc != ISMHIP_OK) return rc;
         hipLaunchKernelGGL(k_hell_eval, dim3(n2), dim3(256), 0, ctx->stream, n2, (const uint32_t*)list2, (const uint32_t*)cnt, (const uint32_t*)rows, cap,
                            (const uint32_t*)xb->shadow_perm, q, cb->dim, (const float*)cb->words, dp, vp.ku, idx_out, dist_out, sc + 8);
         ISM_CHECK_LAUNCH(ctx, "k_hell_eval");
@@ -2430,8 +2249,9 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
     }
     {
         TimerScope t2(ctx, "knn_stage2");
-        rc = k > 2 ? run_knn<4>(ctx, cb, ISMHIP_METRIC_CHI2, n2, q2, k, idx2, dist2, nullptr, "knn_chi2_valu")
-                   : run_knn<2>(ctx, cb, ISMHIP_METRIC_CHI2, n2, q2, k, idx2, dist2, nullptr, "knn_chi2_valu");
+        KnnRequest rv; rv.tname = "knn_chi2_valu";
+        rc = k > 2 ? run_knn<4>(ctx, cb, ISMHIP_METRIC_CHI2, n2, q2, k, idx2, dist2, rv)
+                   : run_knn<2>(ctx, cb, ISMHIP_METRIC_CHI2, n2, q2, k, idx2, dist2, rv);
         if (rc != ISMHIP_OK) return rc;
     }
     hipLaunchKernelGGL(k_knn_scatter_results, dim3((n2 * k + 255) / 256), dim3(256), 0, ctx->stream, list2, n2, k, idx2, dist2, idx_out, dist_out);
@@ -2616,29 +2436,12 @@ int run_thr_mfma(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq,
         TimerScope t1(ctx, "knn_threshold_sweep");
         ISM_HIP(ctx, hipMemsetAsync(sc, 0, 64, ctx->stream));
         ISM_HIP(ctx, hipMemsetAsync(emit_cnt, 0, (size_t)nqp * 4, ctx->stream));
-        hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, qv, nq, cb->dim, ldv, sc);
-        ISM_CHECK_LAUNCH(ctx, "k_absmax");
-        const size_t tot = (size_t)nqp * cb->ld16;
-        hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, qv, nq, cb->dim, ldv, nqp, cb->ld16, sc, xb->f16_scale, qimg);
-        ISM_CHECK_LAUNCH(ctx, "k_to_f16");
-        vp.ku = 1.01f * (float)dp * KNN_U;
-        vp.dot_rel = 2.002f * 4.8828125e-04f + 1.01f * (float)dp * 1.1920929e-07f;
-        vp.cmax2 = xb->max_norm2; vp.dabs_c = 6.103515625e-05f / xb->f16_scale; vp.dabs_q = (const float*)(sc + 2);
-        vp.sqrt_dim = sqrtf((float)dp); vp.cn_acc = 1.01f * (float)(dp + 1) * 1.1920929e-07f;
-        hipLaunchKernelGGL(k_thr_tau, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, nq, qv, ldv, cb->dim, thr, vp, tau);
-        ISM_CHECK_LAUNCH(ctx, "k_thr_tau");
-        const void* kern = (const void*)k_knn_l2_mfma16<4, 2, 2, 2, 2, 1, 64, 1>;
-        const size_t lds = (size_t)2 * (128 + 128) * 64 * sizeof(u16) + 128 * sizeof(float);
-        if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ctx->attr_done.insert(kern); }
-        const int n_qt = nqp / 128, n_mt = cb->n_words_pad / 128;
-        int nsp = std::max(1, std::min(n_mt / 2, (2048 + 8 * ((n_qt + 7) / 8) - 1) / (8 * ((n_qt + 7) / 8))));
-        int tps = (n_mt + nsp - 1) / nsp; nsp = (n_mt + tps - 1) / tps;
-        const u16* wh = xb->words_f16; const u16* wl = nullptr; const float* word_norm = xb->word_norm; const float* osc = (const float*)(sc + 1);
-        int n_tiles_m = n_mt, ld16 = cb->ld16, k_steps = (cb->dim + 15) / 16, nq_ = nq, ncand = cb->n_words, nb = 0, cap_ = THR_EMIT_CAP;
-        const u16* qh_ = qimg; const u16* ql_ = nullptr; float* nf = nullptr; int* ni = nullptr; const float* tau_ = tau;
-        void* args[] = {&wh, &wl, &word_norm, &n_tiles_m, &ld16, &k_steps, &qh_, &ql_, &nq_, &osc, &tps, &nsp, &nf, &ni, &ncand, &nf, &nb, &tau_, &emit_cnt, &rows, &cap_};
-        ISM_HIP(ctx, hipLaunchKernel(kern, dim3(8 * ((n_qt + 7) / 8) * nsp), dim3(256), args, lds, ctx->stream));
-        ISM_CHECK_LAUNCH(ctx, "k_knn_l2_mfma16<emit>");
+        const int rc = knn_f16_emit_sweep(ctx, cb, xb, qv, nq, ldv, nqp, sc, qimg, true, vp, [&](const VerifyParams& v) {
+            hipLaunchKernelGGL(k_thr_tau, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, nq, qv, ldv, cb->dim, thr, v, tau);
+            ISM_CHECK_LAUNCH(ctx, "k_thr_tau");
+            return ISMHIP_OK;
+        }, tau, emit_cnt, rows, THR_EMIT_CAP);
+        if (rc != ISMHIP_OK) return rc;
     }
     {
         TimerScope t2(ctx, "knn_threshold_eval");
@@ -2688,13 +2491,6 @@ int ism_codebook_split_bf16(ismhip_ctx* ctx, ismhip_codebook* cb, uint32_t absma
     return ISMHIP_OK;
 }
 
-#ifdef ISM_KNN_DBG_VARIANTS
-extern "C" int ismhip_debug_knn_counters(unsigned long long* out256, int reset) {
-    if (out256 && hipMemcpyFromSymbol(out256, HIP_SYMBOL(g_knn_dbg), 2048) != hipSuccess) return -1;
-    if (reset) { static unsigned long long z[256]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_dbg), z, 2048) != hipSuccess) return -1; }
-    return 0;
-}
-#endif
 extern "C" {
 
 int ismhip_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k,
@@ -2713,7 +2509,7 @@ int ismhip_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, c
     const bool wide = k > 2 || (metric == ISMHIP_METRIC_L2SQ && cb->words_bf16_hi && ctx->knn_mode <= 1 && !(cb->dim <= 64 && ctx->knn_mode == 0));
     // default for big squared-L2 launches with k <= 2 (every shipped configuration): the two-stage search (see run_knn_two_stage)
     if (metric == ISMHIP_METRIC_L2SQ && k <= 2 && ctx->knn_t == 0 && ctx->knn_mode == 0 && ctx->knn_two_stage && cb->words_f16t && nq >= 4096 &&
-        cb->n_words_pad >= 4096 && !ctx->knn_small_tile && !ctx->knn_no_ring && (cb->dim > 64 || cb->pca.m > 0))
+        cb->n_words_pad >= 4096 && (cb->dim > 64 || cb->pca.m > 0))
         return run_knn_two_stage(ctx, cb, nq, q, k, idx_out, dist_out);
     // chi-square on histogram data: Hellinger candidates on the matrix cores (run_knn_chi2_hellinger); a batch with a negative element
     // keeps the VALU kernel
