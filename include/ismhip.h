@@ -223,6 +223,16 @@ int  ismhip_codebook_stage2_dims(const ismhip_codebook* cb, float* energy_out);
  *      functor value (utils/distance.cpp:33-52), recomputed by direct summation for the winners. */
 int  ismhip_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q,
                 int k, int32_t* idx_out, float* dist_out);
+#define ISMHIP_KNN_LARGE_K_MAX 1024
+/* ActivationStrategyKNN::activateKNN for any K (FLANNExactMatch semantics): the contract of ismhip_knn for
+ * 1 <= k <= ISMHIP_KNN_LARGE_K_MAX. idx_out / dist_out device [nq*k]. Synchronises. k <= 16 is ismhip_knn itself. Larger k: squared-L2
+ * launches that ismhip_knn_threshold would run on the matrix cores take a certified threshold search there first;
+ * chi-square launches only with the environment variable ISMHIP_KNN_LARGE_K_FAST=1 at context creation; every query not certified
+ * (all of them with ISMHIP_KNN_LARGE_K_EXACT=1) goes to an exact scan. Counters (ismhip_timer_get, valid without timers): "knn_large_k_certified_queries",
+ * "knn_large_k_retry_queries", "knn_large_k_exact_queries" of the last call; timers "knn_large_k" and its parts
+ * "knn_large_k_seed", "knn_large_k_sweep", "knn_large_k_eval", "knn_large_k_exact". */
+int  ismhip_knn_large_k(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q,
+                        int k, int32_t* idx_out, float* dist_out);
 /* distance-ratio test of activateKNN (:74-85), k must be 1: needs the 2-NN; idx -> -1 when d1/d2 > threshold */
 int  ismhip_knn_ratio(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q,
                       float ratio_threshold, int32_t* idx_out, float* dist_out);
@@ -315,7 +325,8 @@ int  ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets
  *      features in the order the reference iterates them); feat_*_h are host arrays ([n], centre [n*3] = the model's bounding-box
  *      centre). Outputs are HOST arrays with m = number of codewords: word_src_out[m] (row of `codewords` behind every kept
  *      codeword, ascending = codeword order), vote_offsets_out[m+1] (CSR), vote_feature_out / vote_weight_out /
- *      vote_class_weight_out [n*k], vote_xyz_out[n*k*3], class_sigma_out[n_classes]. The call synchronises. k <= 16;
+ *      vote_class_weight_out [n*k], vote_xyz_out[n*k*3], class_sigma_out[n_classes]. The call synchronises.
+ *      k <= ISMHIP_KNN_LARGE_K_MAX (k > 16 activates through ismhip_knn_large_k);
  *      a codeword with more than 32768 votes is refused (ISMHIP_ERR_UNSUPPORTED). */
 int  ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9,
                            const float* kpx, const float* kpy, const float* kpz,

@@ -28,7 +28,7 @@ EXPORTS = [
     "ismhip_compact_features", "ismhip_compact_descriptor_rows", "ismhip_filter_normals", "ismhip_voxel_keypoints", "ismhip_gather_columns",
     "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims",
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
-    "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists",
+    "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
 ]
 
 
@@ -368,6 +368,16 @@ def knn(ctx, cb, metric, q, k=1):
     idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ctx.check(lib().ismhip_knn(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn")
+    return idx, dist
+
+
+def knn_large_k(ctx, cb, metric, q, k):
+    """ismhip_knn_large_k: the contract of knn for any 1 <= k <= 1024 (k <= 16 is knn itself); synchronises"""
+    torch = _torch()
+    nq = q.shape[0]
+    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ctx.check(lib().ismhip_knn_large_k(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn_large_k")
     return idx, dist
 
 

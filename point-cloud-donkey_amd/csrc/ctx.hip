@@ -79,6 +79,9 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_PRE_GAMMA"); if (e) ctx->knn_pre_gamma = (float)atof(e); }
     { const char* e = getenv("ISMHIP_KNN_PREPASS"); ctx->knn_prepass = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_PCA_M"); ctx->knn_pca_m = e ? atoi(e) : -1; }
+    { const char* e = getenv("ISMHIP_KNN_LARGE_K_FAST"); ctx->knn_lk_fast = e && e[0] == '1'; }
+    { const char* e = getenv("ISMHIP_KNN_LARGE_K_EXACT"); ctx->knn_lk_exact = e && e[0] == '1'; }
+    { const char* e = getenv("ISMHIP_KNN_LARGE_K_SEED_SCALE"); if (e) ctx->knn_lk_seed_scale = (float)atof(e); }
     { const char* e = getenv("ISMHIP_KNN_PCA_M2"); ctx->knn_pca_m2 = e ? atoi(e) : -1; }
     if (!own) { ctx->stream = (hipStream_t)stream; ctx->own_stream = false; }
     else {
@@ -176,6 +179,11 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
     if (std::strcmp(name, "knn_pca_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_pca_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_overflow_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_overflow; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_mfma_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_mfma_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    {
+        static const char* const lk[3] = {"knn_large_k_certified_queries", "knn_large_k_retry_queries", "knn_large_k_exact_queries"};
+        for (int i = 0; i < 3; ++i)
+            if (std::strcmp(name, lk[i]) == 0) { if (ms_out) *ms_out = (double)ctx->knn_lk_stats[i]; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    }
     if (std::strcmp(name, "knn_stage2_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_queries; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_flagged_queries") == 0 || std::strcmp(name, "knn_flagged_items") == 0) {     // counters, not times
         if (ms_out) *ms_out = (double)ctx->knn_stats[name[12] == 'q' ? 0 : 1];

@@ -479,11 +479,13 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
                          vote_offsets_out, vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
     if (rc != ISMHIP_OK) return rc;
     if (k <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
+    if (k > ISMHIP_KNN_LARGE_K_MAX) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: k > 1024 not built");
     // the codewords: cluster centres (implicit_shape_model.cpp:445-475), or the features themselves (clustering_none.cpp:25-35)
     if (!codewords) { codewords = desc; n_codewords = n; }
     if (n_codewords <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: no codewords");
     if (n_codewords < k) k = n_codewords;            // FLANN returns as many neighbours as there are rows: every feature activates every codeword
     const size_t na = (size_t)n * k;
+    if (na > 0x7fffffff) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: 2^31 or more activations not built");   // (int)na below, as in train_activate_lists
     // ---- every feature activates its k nearest codewords (exact, ties -> lowest row): the regular CSR act_off[f] = f * k
     ismhip_codebook* cb = nullptr;
     rc = ism_knn_only_codebook(ctx, n_codewords, dim, codewords, &cb, false);
@@ -493,7 +495,7 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
     char* ab = (char*)ism_scratch(ctx, SCR_TRAIN_ACT, na * 8 + ((size_t)n + 1) * 4 + 16);
     if (!ab) { ismhip_codebook_destroy(ctx, cb); return ISMHIP_ERR_NOMEM; }
     int32_t* act = (int32_t*)ab; float* actd = (float*)(ab + na * 4); uint32_t* act_off = (uint32_t*)(ab + na * 8);
-    rc = ismhip_knn(ctx, cb, metric, n, desc, k, act, actd);
+    rc = ismhip_knn_large_k(ctx, cb, metric, n, desc, k, act, actd);      // k <= 16: ismhip_knn
     if (rc == ISMHIP_OK && hipMemcpyAsync(act_off, act_off_h.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = ism_set_err(ctx, ISMHIP_ERR_HIP, "train_activate: activation offsets copy");
     if (rc == ISMHIP_OK)

@@ -416,11 +416,13 @@ void Codebook::upload(DeviceSession& s) const {
 
 int ActivationStrategyKNN::activateKNN(DeviceSession& s, const ismhip_codebook* codewords, const DeviceFeatures& f, int metric,
                                        int32_t* idx_out, float* dist_out, const float* desc) const {     // activation_strategy_knn.h:41-126
-    if (m_k > 16) throw RuntimeException("KNN activation with K > 16 is not built");
+    if (m_k > ISMHIP_KNN_LARGE_K_MAX) throw RuntimeException("KNN activation with K > 1024 (ISMHIP_KNN_LARGE_K_MAX) is not built");
     if (f.n == 0) return m_k;
     if (!desc) desc = f.desc.as<float>();                        // desc: the (possibly partial, codebook.cpp:416-475) descriptors to match
-    if (m_use_distance_ratio && m_is_detection && m_k == 1)
+    if (m_use_distance_ratio && m_is_detection && m_k == 1)     // the reference applies the ratio only for K == 1
         s.check(ismhip_knn_ratio(s.ctx, codewords, metric, (int)f.n, desc, m_distance_ratio_threshold, idx_out, dist_out), "ismhip_knn_ratio");
+    else if (m_k > 16)
+        s.check(ismhip_knn_large_k(s.ctx, codewords, metric, (int)f.n, desc, m_k, idx_out, dist_out), "ismhip_knn_large_k");
     else
         s.check(ismhip_knn(s.ctx, codewords, metric, (int)f.n, desc, m_k, idx_out, dist_out), "ismhip_knn");
     return m_k;
@@ -503,7 +505,7 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
     const auto* thr = dynamic_cast<const ActivationStrategyThreshold*>(knn);
     const bool is_knn = m_activationStrategy->getType() == "KNN";
     const int k = is_knn ? knn->getK() : 1;                      // KNNRule trains with plain 1-NN (activation_strategy_knn_rule.h:70-74)
-    if (k > 16) throw RuntimeException("KNN activation with K > 16 is not built");
+    if (k > ISMHIP_KNN_LARGE_K_MAX) throw RuntimeException("KNN activation with K > 1024 (ISMHIP_KNN_LARGE_K_MAX) is not built");
     // the whole of Codebook::activate runs on the device (ismhip_train_activate): self-kNN, class sigma^2, K = 1 clean-up,
     // vote CSR, computeWeights and the statistical class weights. Features must be class-major, as train() collects them.
     const bool clustered = clustering.hasCenters();
@@ -587,10 +589,12 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
     upload(s);
     m_activationStrategy->setIsDetection();
     const ActivationStrategy* knn = m_activationStrategy.get();
-    if (knn->getK() > 16) throw RuntimeException("KNN activation with K > 16 is not built");
+    if (knn->getK() > ISMHIP_KNN_LARGE_K_MAX) throw RuntimeException("KNN activation with K > 1024 (ISMHIP_KNN_LARGE_K_MAX) is not built");
     const uint32_t n = f.n;
     if (n == 0) return;
-    s.idx.reserve((size_t)n * 4 * 4); s.dist.reserve((size_t)n * 4 * 4);
+    const size_t kmax = (size_t)std::max(knn->getK(), 1);          // activations per feature of the K-nearest strategies
+    const size_t kres = std::max<size_t>(kmax, 4);                // (at least the 4 per feature this buffer always had: Threshold grows from it)
+    s.idx.reserve((size_t)n * kres * 4); s.dist.reserve((size_t)n * kres * 4);
     const float* qdesc = nullptr;
     DevBuf partial;
     if (!m_partial_cols.empty()) {                              // reduce every feature the way the codewords were reduced (codebook.cpp:416-475)
@@ -617,9 +621,15 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
         s.n_classes = (int)m_data.class_sigma.size();
         return;
     }
+    const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
+    // refuse what would not fit rather than truncate: ismhip_cast_votes counts activations in an int, vote slots are addressed with
+    // 32 bits (slot_off, ismhip_find_maxima)
+    if ((uint64_t)n * kmax > 0x7fffffffull)
+        throw RuntimeException("castVotes: features x K reaches 2^31 activations, not built");
+    if ((uint64_t)n * kmax * (uint64_t)std::max(maxv, 1) >= (1ull << 32))
+        throw RuntimeException("castVotes: features x K x votes per codeword reaches 2^32 vote slots, not built");
     const int k = knn->activateKNN(s, m_dev, f, metric, s.idx.as<int32_t>(), s.dist.as<float>(), qdesc);
     if (qdesc) s.check(ismhip_sync(s.ctx), "ismhip_sync");     // the partial descriptors are released when this function returns
-    const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
     const size_t ns = (size_t)n * k * maxv;
     s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
     s.check(ismhip_cast_votes(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),

@@ -259,7 +259,7 @@ public:
     ActivationStrategyThreshold();
     static std::string getTypeStatic() { return "Threshold"; }
     std::string getType() const override { return getTypeStatic(); }
-    int getK() const override { return 1; }             // no fixed fan-out (the K > 16 checks do not apply)
+    int getK() const override { return 1; }             // no fixed fan-out (the K cap checks do not apply)
     float getThreshold() const { return m_threshold; }
     // the fixed-column interface does not fit a variable fan-out: throws (the codebook calls the list path instead)
     int activateKNN(DeviceSession& s, const ismhip_codebook* codewords, const DeviceFeatures& f, int metric, int32_t* idx_out, float* dist_out, const float* desc = nullptr) const override;

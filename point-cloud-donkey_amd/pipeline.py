@@ -265,7 +265,7 @@ class Recognizer:
         elif c.use_distance_ratio and c.k == 1:
             idx, dist = capi.knn_ratio(ctx, cb, c.metric, q, c.distance_ratio_threshold)
         else:
-            idx, dist = capi.knn(ctx, cb, c.metric, q, c.k)
+            idx, dist = (capi.knn_large_k if c.k > 16 else capi.knn)(ctx, cb, c.metric, q, c.k)
         votes = capi.cast_votes(ctx, cb, c.weight_flags, f["lrf"], f["kx"], f["ky"], f["kz"], idx, dist, want_bbox=c.average_rotation)
         slot_off = f["off"].astype(np.uint64) * (c.k * cb.max_votes)
         max_filter = capi.MAXFILTER_NONE if c.single_object_mode else {"Simple": capi.MAXFILTER_SIMPLE, "Merge": capi.MAXFILTER_MERGE}.get(c.max_filter, capi.MAXFILTER_NONE)
