@@ -86,7 +86,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","knn","cast_votes","maxima"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -120,6 +120,34 @@ int  ismhip_estimate_normals_pca(ismhip_ctx* ctx, ismhip_cloud* cloud, float rad
  * pt_offsets_h_out[n_obj+1] (host) receives the new ranges. The call synchronises. */
 typedef struct ismhip_point_arrays { float *x, *y, *z, *nx, *ny, *nz; uint32_t* rgba; } ismhip_point_arrays;
 int  ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in,
+                           const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out);
+/* ---- point-cloud pre-filters: the first steps of ImplicitShapeModel::computeFeatures (implicit_shape_model.cpp:739-758, :810-821).
+ *      PCL is external; the arithmetic is this library's definition, restated from PCL 1.10. Masks are device
+ *      uint8_t[n_pts] in the ORIGINAL point order of the cloud, 1 = keep. A point that is not finite in x, y and z is never a
+ *      neighbour and is always dropped. Every squared distance is the unfused float (dx*dx + dy*dy) + dz*dz. Results do not depend
+ *      on the cell_size the cloud was created with. The filters are chained by the caller: mask -> ismhip_compact_points -> a new
+ *      ismhip_cloud over the surviving points -> next filter. */
+#define ISMHIP_SOR_MAX_MEAN_K 64
+/* pcl::StatisticalOutlierRemoval (:739-748; MeanK, StddevMul :95-98): per finite point the mean_k + 1 smallest squared distances to the
+ * finite points of its object (itself included, duplicates count), the smallest dropped, mean_dist = (float)(sum of sqrt((double)d2)
+ * in ascending order / mean_k); per object in double mean, var = (sum d^2 - (sum d)^2 / n) / (n - 1), threshold = mean +
+ * stddev_mul * sqrt(var), summed in a fixed order; keep iff !(mean_dist > threshold). An object with fewer than mean_k + 1 finite points
+ * keeps all of them (threshold +inf, mean_dist NaN). mean_k < 1: ISMHIP_ERR_INVALID; mean_k > ISMHIP_SOR_MAX_MEAN_K is REFUSED with
+ * ISMHIP_ERR_UNSUPPORTED (there is no slower path). mean_dist_out: device [n_pts] or NULL (NaN for the non-finite points);
+ * threshold_h_out: host [n_obj] or NULL. Timer "filter_sor". The call synchronises. */
+int  ismhip_filter_statistical(ismhip_ctx* ctx, const ismhip_cloud* cloud, int mean_k, float stddev_mul, uint8_t* keep_out,
+                               float* mean_dist_out, double* threshold_h_out);
+/* pcl::RadiusOutlierRemoval, radius-search branch (:749-758; the reference's clouds are is_dense = false :519,:612,:744): count =
+ * finite points of the object with d2 < (float)((double)radius * radius), STRICTLY, the point itself included; keep iff
+ * count > min_neighbors. count_out: device [n_pts] or NULL; when given it holds the full counts (0 for non-finite points), when NULL a
+ * query stops counting once it is kept. Timer "filter_ror". Asynchronous. */
+int  ismhip_filter_radius(ismhip_ctx* ctx, const ismhip_cloud* cloud, float radius, int min_neighbors, uint8_t* keep_out, uint32_t* count_out);
+/* pcl::PassThrough on z with limits (0, CutoffDistanceZAxis) (:810-821): keep iff the point is finite and !(z < z_min || z > z_max). */
+int  ismhip_filter_passthrough_z(ismhip_ctx* ctx, uint32_t n_pts, const float* x, const float* y, const float* z, float z_min, float z_max,
+                                 uint8_t* keep_out);
+/* Stable compaction of the point arrays by a keep mask (device uint8_t[n_pts], 1 = keep): as ismhip_filter_normals, with the mask in
+ * place of the NaN-normal test. Normals and colours travel with their points. Timer "filter_compact". The call synchronises. */
+int  ismhip_compact_points(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in, const uint8_t* keep,
                            const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out);
 /* per-object centroid (features_shot.cpp:45-51) -> centroid_out[n_obj*3] */
 int  ismhip_cloud_centroids(ismhip_ctx* ctx, const ismhip_cloud* cloud, float* centroid_out);

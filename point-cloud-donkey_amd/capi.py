@@ -29,6 +29,7 @@ EXPORTS = [
     "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims",
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
+    "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
 ]
 
 
@@ -303,6 +304,55 @@ def filter_normals(ctx, pt_offsets, x, y, z, nx, ny, nz, rgba=None):
     a_out = _PointArrays(*[t.data_ptr() for t in outs], *([None] if rgba is None else []))
     new = np.zeros(n_obj + 1, dtype=np.uint32)
     ctx.check(lib().ismhip_filter_normals(ctx._h, C.c_int(n_obj), _p(po), C.byref(a_in), C.byref(a_out), _p(new)), "ismhip_filter_normals")
+    m = int(new[-1])
+    outs = [t[:m] for t in outs]
+    return (new, *outs, *([None] if rgba is None else []))
+
+
+def filter_statistical(ctx, cloud, mean_k=20, stddev_mul=2.0, want_mean_dist=True):
+    """pcl::StatisticalOutlierRemoval on the device: returns (keep uint8[n_pts], mean_dist float32[n_pts] or None, thresholds float64[n_obj])"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    keep = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    md = torch.empty((n,), dtype=torch.float32, device=dev) if want_mean_dist else None
+    thr = np.zeros(cloud.n_obj, dtype=np.float64)
+    ctx.check(lib().ismhip_filter_statistical(ctx._h, cloud._h, C.c_int(mean_k), C.c_float(stddev_mul), _p(keep), _p(md), _p(thr)),
+              "ismhip_filter_statistical")
+    return keep, md, thr
+
+
+def filter_radius(ctx, cloud, radius, min_neighbors, want_counts=False):
+    """pcl::RadiusOutlierRemoval on the device: returns (keep uint8[n_pts], counts int32[n_pts] or None)"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    keep = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_filter_radius(ctx._h, cloud._h, C.c_float(radius), C.c_int(min_neighbors), _p(keep), _p(cnt)), "ismhip_filter_radius")
+    return keep, cnt
+
+
+def filter_passthrough_z(ctx, x, y, z, z_min, z_max):
+    """pcl::PassThrough on z: keep uint8[n_pts], 1 where the point is finite and z_min <= z <= z_max"""
+    torch = _torch()
+    keep = torch.zeros((x.numel(),), dtype=torch.uint8, device=x.device)
+    ctx.check(lib().ismhip_filter_passthrough_z(ctx._h, C.c_uint32(x.numel()), _p(x), _p(y), _p(z), C.c_float(z_min), C.c_float(z_max), _p(keep)),
+              "ismhip_filter_passthrough_z")
+    return keep
+
+
+def compact_points(ctx, pt_offsets, keep, x, y, z, nx, ny, nz, rgba=None):
+    """the points with keep == 1, order kept: returns (new_offsets numpy, x, y, z, nx, ny, nz, rgba or None)"""
+    torch = _torch()
+    po = _u32(pt_offsets)
+    n_obj = len(po) - 1
+    ins = [x, y, z, nx, ny, nz] + ([rgba] if rgba is not None else [])
+    outs = [torch.empty_like(t) for t in ins]
+    a_in = _PointArrays(*[t.data_ptr() for t in ins], *([None] if rgba is None else []))
+    a_out = _PointArrays(*[t.data_ptr() for t in outs], *([None] if rgba is None else []))
+    new = np.zeros(n_obj + 1, dtype=np.uint32)
+    ctx.check(lib().ismhip_compact_points(ctx._h, C.c_int(n_obj), _p(po), C.byref(a_in), _p(keep), C.byref(a_out), _p(new)), "ismhip_compact_points")
     m = int(new[-1])
     outs = [t[:m] for t in outs]
     return (new, *outs, *([None] if rgba is None else []))

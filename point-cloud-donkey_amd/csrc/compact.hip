@@ -161,6 +161,10 @@ __global__ void k_keep_normals(uint32_t n, const float* __restrict__ nx, const f
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) keep[i] = (isnan(nx[i]) || isnan(ny[i]) || isnan(nz[i])) ? 0u : 1u;
 }
+__global__ void k_keep_mask(uint32_t n, const uint8_t* __restrict__ mask, uint32_t* __restrict__ keep) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keep[i] = mask[i] ? 1u : 0u;
+}
 __global__ __launch_bounds__(256) void k_gather_points(const uint32_t* __restrict__ off, const uint32_t* __restrict__ new_off, const uint32_t* __restrict__ keep,
                                                        const uint32_t* __restrict__ pos, ismhip_point_arrays in, ismhip_point_arrays out) {
     const int o = blockIdx.y;
@@ -173,17 +177,18 @@ __global__ __launch_bounds__(256) void k_gather_points(const uint32_t* __restric
 }
 }  // namespace
 
-extern "C" int ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in,
-                                     const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out) {
+// mask == nullptr: the NaN-normal flag of filterNormals; otherwise the caller's keep mask (1 = keep)
+static int compact_points(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in, const uint8_t* mask,
+                          const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out, const std::string& who) {
     if (!ctx || n_obj <= 0 || !pt_offsets_h || !in || !out || !pt_offsets_h_out || !in->x || !in->y || !in->z || !in->nx || !in->ny || !in->nz ||
         !out->x || !out->y || !out->z || !out->nx || !out->ny || !out->nz || (in->rgba && !out->rgba))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "filter_normals: bad argument");
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": bad argument");
     if (in->x == out->x || in->y == out->y || in->z == out->z || in->nx == out->nx || in->ny == out->ny || in->nz == out->nz || (in->rgba && in->rgba == out->rgba))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "filter_normals: the output arrays must not alias the inputs");
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": the output arrays must not alias the inputs");
     const uint32_t n = pt_offsets_h[n_obj];
     uint32_t maxn = 0;
     for (int o = 0; o < n_obj; ++o) {
-        if (pt_offsets_h[o + 1] < pt_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "filter_normals: offsets not monotone");
+        if (pt_offsets_h[o + 1] < pt_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": offsets not monotone");
         maxn = std::max(maxn, pt_offsets_h[o + 1] - pt_offsets_h[o]);
     }
     pt_offsets_h_out[0] = 0;
@@ -193,7 +198,8 @@ extern "C" int ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t*
     uint32_t* pos = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_POS, (size_t)n * 4);
     uint32_t* cnt = (uint32_t*)ism_scratch(ctx, SCR_OBJ_COUNT, (size_t)(2 * n_obj + 2) * 4);
     if (!po || !keep || !pos || !cnt) return ISMHIP_ERR_NOMEM;
-    hipLaunchKernelGGL(k_keep_normals, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, in->nx, in->ny, in->nz, keep);
+    if (mask) hipLaunchKernelGGL(k_keep_mask, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, mask, keep);
+    else hipLaunchKernelGGL(k_keep_normals, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, in->nx, in->ny, in->nz, keep);
     ISM_CHECK_LAUNCH(ctx, "k_keep_normals");
     hipLaunchKernelGGL(k_scan_obj, dim3(n_obj), dim3(256), 0, ctx->stream, po, keep, pos, cnt);
     ISM_CHECK_LAUNCH(ctx, "k_scan_obj");
@@ -207,6 +213,20 @@ extern "C" int ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t*
     ISM_CHECK_LAUNCH(ctx, "k_gather_points");
     ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host copy of the offsets is pageable memory read by the H2D above
     return ISMHIP_OK;
+}
+
+extern "C" int ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in,
+                                     const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out) {
+    return compact_points(ctx, n_obj, pt_offsets_h, in, nullptr, out, pt_offsets_h_out, "filter_normals");
+}
+
+// the pre-filters' compaction (prefilter.hip): the same flag / per-object scan / gather, driven by a keep mask in point order
+extern "C" int ismhip_compact_points(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in, const uint8_t* keep,
+                                     const ismhip_point_arrays* out, uint32_t* pt_offsets_h_out) {
+    if (!keep) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "compact_points: keep is NULL");
+    if (!ctx) return ISMHIP_ERR_INVALID;
+    TimerScope ts(ctx, "filter_compact");
+    return compact_points(ctx, n_obj, pt_offsets_h, in, keep, out, pt_offsets_h_out, "compact_points");
 }
 
 // ---- partial descriptors: Codebook::castVotes with UsePartialShot (codebook/codebook.cpp:416-475) keeps the histograms of a subset

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <numeric>
 #include <random>
@@ -1069,7 +1070,7 @@ void ClusteringKMeansHartigan::process(DeviceSession& s, const DeviceFeatures& f
 // ---------------------------------------------------------------------------------------------------------------
 // ImplicitShapeModel (implicit_shape_model.cpp)
 // ---------------------------------------------------------------------------------------------------------------
-ImplicitShapeModel::ImplicitShapeModel() {        // :91-168 (hot-path subset + the filter switches, which must stay off)
+ImplicitShapeModel::ImplicitShapeModel() {        // :91-168 (hot-path subset + the pre-filters; smoothing and voxel filtering must stay off)
     addParameter(m_distanceType, "DistanceType", std::string("Euclidean"));
     addParameter(m_normal_radius, "NormalRadius", 0.05f);
     addParameter(m_consistent_normals_method, "ConsistentNormalsMethod", 2);
@@ -1080,9 +1081,14 @@ ImplicitShapeModel::ImplicitShapeModel() {        // :91-168 (hot-path subset + 
     addParameter(m_instance_labels_primary, "InstanceLabelsPrimary", true);
     addParameter(m_single_object_mode_legacy, "SingleObjectMode", false);
     addParameter(m_use_smoothing, "UseSmoothing", false);
-    addParameter(m_use_sor, "UseStatisticalOutlierRemoval", false);
+    addParameter(m_use_sor, "UseStatisticalOutlierRemoval", false);     // :95-103
+    addParameter(m_sor_mean_k, "OutlierRemovalMeanK", 20);
+    addParameter(m_sor_stddev_mul, "OutlierRemovalStddevMul", 2.0f);
     addParameter(m_use_ror, "UseRadiusOutlierRemoval", false);
+    addParameter(m_ror_min_neighbors, "OutlierRemovalMinNeighbors", 10);
+    addParameter(m_ror_radius, "OutlierRemovalRadius", 0.005f);
     addParameter(m_use_voxel_filtering, "UseVoxelFiltering", false);
+    addParameter(m_cutoff_distance_z, "CutoffDistanceZAxis", 0.0f);
     m_codebook.reset(new Codebook());
     m_keypoints_detector.reset(new KeypointsVoxelGrid());
     m_feature_descriptor.reset(new FeaturesSHOT());
@@ -1122,7 +1128,10 @@ bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
     if (const Json* gf = c.find("GlobalFeatures")) m_global_features_cfg = *gf;
     const Json* rt = fw->find("Type");
     if (!rt || rt->str != "Uniform") throw RuntimeException("feature ranking type \"" + (rt ? rt->str : std::string()) + "\" is out of scope (built: Uniform)");
-    if (m_use_smoothing || m_use_sor || m_use_ror || m_use_voxel_filtering) throw RuntimeException("point cloud pre-filters (smoothing / outlier removal / voxel filtering) are not built");
+    if (m_use_smoothing || m_use_voxel_filtering) throw RuntimeException("point cloud pre-filters smoothing (UseSmoothing) and voxel filtering (UseVoxelFiltering) are not built");
+    if (m_use_sor && (m_sor_mean_k < 1 || m_sor_mean_k > ISMHIP_SOR_MAX_MEAN_K))
+        throw RuntimeException("OutlierRemovalMeanK " + std::to_string(m_sor_mean_k) + " is not built (built: 1 .. " + std::to_string(ISMHIP_SOR_MAX_MEAN_K) + ")");
+    if (m_use_ror && !(m_ror_radius > 0.f)) throw BadParamExceptionType<float>("invalid outlier removal radius", m_ror_radius);
     return m_codebook && m_keypoints_detector && m_feature_descriptor && m_voting && m_clustering;
 }
 
@@ -1191,6 +1200,98 @@ static bool firstNormalValid(const PointCloud& c) {   // :615-625 — decided fr
     if (c.nx.size() != c.size() || c.empty()) return false;
     if ((c.nx[0] == 0 && c.ny[0] == 0 && c.nz[0] == 0) || std::isnan(c.nx[0])) return false;
     return true;
+}
+
+// The head of computeFeatures (:739-758, :810-821): statistical outlier removal, radius outlier removal on its output, z pass-through
+// on that. The whole batch goes up once, every filter writes a keep mask in HBM and ismhip_compact_points closes the gaps (normals
+// and colours travel along); the surviving points then come back to the host, where the existing routes (device normals, mixed
+// batches, host keypoint detectors) take them as if they had been the input.
+std::vector<const PointCloud*> ImplicitShapeModel::preFilterClouds(const std::vector<const PointCloud*>& clouds, std::vector<std::unique_ptr<PointCloud>>& store) {
+    const bool cut = m_cutoff_distance_z > 0.f;
+    if (!(m_use_sor || m_use_ror || cut) || clouds.empty()) return clouds;
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceSession& s = session();
+    const int n_obj = (int)clouds.size();
+    bool with_color = false;
+    for (const PointCloud* c : clouds) with_color |= !c->empty() && c->rgba.size() == c->size();
+    std::vector<float> h[6]; std::vector<uint32_t> hc, off(1, 0);
+    for (const PointCloud* c : clouds) {
+        const bool nrm = c->nx.size() == c->size() && c->ny.size() == c->size() && c->nz.size() == c->size();
+        h[0].insert(h[0].end(), c->x.begin(), c->x.end()); h[1].insert(h[1].end(), c->y.begin(), c->y.end()); h[2].insert(h[2].end(), c->z.begin(), c->z.end());
+        if (nrm) { h[3].insert(h[3].end(), c->nx.begin(), c->nx.end()); h[4].insert(h[4].end(), c->ny.begin(), c->ny.end()); h[5].insert(h[5].end(), c->nz.begin(), c->nz.end()); }
+        else for (int a = 3; a < 6; ++a) h[a].insert(h[a].end(), c->size(), 0.f);
+        if (with_color) { if (c->rgba.size() == c->size()) hc.insert(hc.end(), c->rgba.begin(), c->rgba.end()); else hc.insert(hc.end(), c->size(), 0u); }
+        off.push_back((uint32_t)h[0].size());
+    }
+    if (s.cloud) { ismhip_cloud_destroy(s.ctx, s.cloud); s.cloud = nullptr; }
+    DevBuf* cur[7] = {&s.x, &s.y, &s.z, &s.nx, &s.ny, &s.nz, &s.rgba};
+    DevBuf* alt[7] = {&s.fx, &s.fy, &s.fz, &s.fnx, &s.fny, &s.fnz, &s.frgba};
+    for (int a = 0; a < 6; ++a) DeviceSession::h2d(*cur[a], h[a]);
+    if (with_color) DeviceSession::h2d(s.rgba, hc);
+    const size_t n_in = std::max<size_t>(off.back(), 1);
+    for (int a = 0; a < 7; ++a) if (a < 6 || with_color) alt[a]->reserve(n_in * 4);
+    DevBuf keep; keep.reserve(n_in);
+    auto arrays = [&](DevBuf* const b[7]) {
+        return ismhip_point_arrays{b[0]->as<float>(), b[1]->as<float>(), b[2]->as<float>(), b[3]->as<float>(), b[4]->as<float>(), b[5]->as<float>(),
+                                   with_color ? b[6]->as<uint32_t>() : nullptr};
+    };
+    auto with_cloud = [&](float cell, const std::function<void(ismhip_cloud*)>& fn) {
+        ismhip_cloud* c = nullptr;
+        s.check(ismhip_cloud_create(s.ctx, n_obj, off.data(), s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>(),
+                                    nullptr, cell, &c), "ismhip_cloud_create");
+        try { fn(c); } catch (...) { ismhip_cloud_destroy(s.ctx, c); throw; }
+        ismhip_cloud_destroy(s.ctx, c);
+    };
+    auto compact = [&]() {
+        if (off.back() == 0) return;
+        const ismhip_point_arrays in = arrays(cur), out = arrays(alt);
+        std::vector<uint32_t> new_off(off.size());
+        s.check(ismhip_compact_points(s.ctx, n_obj, off.data(), &in, keep.as<uint8_t>(), &out, new_off.data()), "ismhip_compact_points");
+        for (int a = 0; a < 7; ++a) if (a < 6 || with_color) cur[a]->swap(*alt[a]);
+        off = new_off;
+    };
+    // the search grids: SOR on the descriptor stage's cell (its result does not depend on it), ROR on cells of one radius
+    const float cell = std::min(m_feature_descriptor->getRadius(), m_feature_descriptor->getType() == "FPFH" ? m_feature_descriptor->getRadius()
+                                                                                                           : m_feature_descriptor->getReferenceFrameRadius()) * 0.4f;
+    if (m_use_sor && off.back() > 0) {
+        LOG_INFO("performing statistical outlier removal");
+        with_cloud(cell, [&](ismhip_cloud* c) {
+            s.check(ismhip_filter_statistical(s.ctx, c, m_sor_mean_k, m_sor_stddev_mul, keep.as<uint8_t>(), nullptr, nullptr), "ismhip_filter_statistical");
+        });
+        compact();
+    }
+    if (m_use_ror && off.back() > 0) {
+        LOG_INFO("performing radius outlier removal");
+        with_cloud(m_ror_radius, [&](ismhip_cloud* c) {
+            s.check(ismhip_filter_radius(s.ctx, c, m_ror_radius, m_ror_min_neighbors, keep.as<uint8_t>(), nullptr), "ismhip_filter_radius");
+        });
+        compact();
+    }
+    if (cut && off.back() > 0) {
+        LOG_INFO("performing pass through filtering");
+        s.check(ismhip_filter_passthrough_z(s.ctx, off.back(), s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), 0.f, m_cutoff_distance_z, keep.as<uint8_t>()),
+                "ismhip_filter_passthrough_z");
+        compact();
+    }
+    const size_t n_out = off.back();
+    for (int a = 0; a < 6; ++a) s.d2h(h[a], *cur[a], n_out);
+    if (with_color) s.d2h(hc, s.rgba, n_out);
+    std::vector<const PointCloud*> out;
+    for (int o = 0; o < n_obj; ++o) {
+        const PointCloud& src = *clouds[o];
+        std::unique_ptr<PointCloud> c(new PointCloud());
+        const size_t b = off[o], e = off[o + 1];
+        c->x.assign(h[0].begin() + b, h[0].begin() + e); c->y.assign(h[1].begin() + b, h[1].begin() + e); c->z.assign(h[2].begin() + b, h[2].begin() + e);
+        if (src.nx.size() == src.size() && src.ny.size() == src.size() && src.nz.size() == src.size()) {
+            c->nx.assign(h[3].begin() + b, h[3].begin() + e); c->ny.assign(h[4].begin() + b, h[4].begin() + e); c->nz.assign(h[5].begin() + b, h[5].begin() + e);
+        }
+        if (with_color && src.rgba.size() == src.size()) c->rgba.assign(hc.begin() + b, hc.begin() + e);
+        out.push_back(c.get());
+        store.push_back(std::move(c));
+    }
+    // an entry of its own next to the reference's seven keys, present only when a filter is enabled
+    m_processing_times["filters"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return out;
 }
 
 std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::vector<const PointCloud*>& clouds_in, bool) {   // :733-927
@@ -1338,7 +1439,16 @@ void ImplicitShapeModel::train() {                // :252-500
     const int D = m_feature_descriptor->getDescriptorLength();
     for (size_t b = 0; b < clouds.size(); b += chunk) {
         std::vector<const PointCloud*> part(clouds.begin() + b, clouds.begin() + std::min(clouds.size(), b + chunk));
-        auto f = computeFeatures(part, true);
+        // pre-filters first (:739-821); the bounding box and the radius below are taken from the unfiltered cloud, as the reference does
+        // (:296-336 run before computeFeatures). An object a filter empties contributes no features.
+        std::vector<std::unique_ptr<PointCloud>> filtered_store;
+        const std::vector<const PointCloud*> filtered = preFilterClouds(part, filtered_store);
+        std::vector<const PointCloud*> live; std::vector<int> live_of(part.size(), -1);
+        for (size_t o = 0; o < part.size(); ++o) {
+            if (filtered[o]->empty()) { LOG_WARN("training cloud is empty after the pre-filters"); continue; }
+            live_of[o] = (int)live.size(); live.push_back(filtered[o]);
+        }
+        auto f = live.empty() ? std::make_shared<DeviceFeatures>() : computeFeatures(live, true);
         std::vector<float> t;
         s.d2h(t, f->desc, (size_t)f->n * D); hdesc.insert(hdesc.end(), t.begin(), t.end());
         s.d2h(t, f->lrf, (size_t)f->n * 9); hlrf.insert(hlrf.end(), t.begin(), t.end());
@@ -1365,7 +1475,8 @@ void ImplicitShapeModel::train() {                // :252-500
                 radius = std::max(radius, std::sqrt(dx * dx + dy * dy + dz * dz));
             }
             box_sizes[obj_class[b + o]].push_back(bsize); object_radii[obj_class[b + o]].push_back(radius);
-            const uint32_t cnt = f->off[o + 1] - f->off[o];
+            if (live_of[o] < 0) continue;
+            const uint32_t cnt = f->off[live_of[o] + 1] - f->off[live_of[o]];
             fclass.insert(fclass.end(), cnt, obj_class[b + o]); finst.insert(finst.end(), cnt, obj_inst[b + o]);
             fmodel.insert(fmodel.end(), cnt, (unsigned)(b + o)); fcenter.insert(fcenter.end(), cnt, center); fbox.insert(fbox.end(), cnt, bsize);
         }
@@ -1384,7 +1495,7 @@ void ImplicitShapeModel::train() {                // :252-500
     LOG_INFO("training done");
 }
 
-std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const std::vector<const PointCloud*>& clouds) {   // detect() :583-712 over a batch
+std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const std::vector<const PointCloud*>& clouds_in) {   // detect() :583-712 over a batch
     g_log_info = m_logging;
     if (m_single_object_mode_legacy)
         throw RuntimeException("The parameter for \"single object mode\" must be set inside the \"Voting\" section of the config file. You are using the \"Parameters\" section.");
@@ -1392,6 +1503,9 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     DeviceSession& s = session();
     std::vector<const PointCloud*> nonempty;
     std::vector<int> map;
+    // pre-filters first (:739-821): an object they empty is an empty input cloud from here on
+    std::vector<std::unique_ptr<PointCloud>> filtered_store;
+    const std::vector<const PointCloud*> clouds = preFilterClouds(clouds_in, filtered_store);
     for (size_t i = 0; i < clouds.size(); ++i) { if (clouds[i]->empty()) LOG_WARN("point cloud is empty"); else { map.push_back((int)i); nonempty.push_back(clouds[i]); } }
     std::vector<std::vector<VotingMaximum>> out(clouds.size());
     if (nonempty.empty()) return out;

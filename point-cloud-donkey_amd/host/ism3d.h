@@ -516,11 +516,16 @@ private:
     DeviceSession& session();
     int metric() const;
     std::shared_ptr<DeviceFeatures> computeFeatures(const std::vector<const PointCloud*>& clouds, bool is_training);
+    // the enabled pre-filters (SOR, ROR, z cut-off) on a batch, in that order; returns `clouds` itself when none is enabled, else
+    // pointers to the filtered copies it puts into `store`
+    std::vector<const PointCloud*> preFilterClouds(const std::vector<const PointCloud*>& clouds, std::vector<std::unique_ptr<PointCloud>>& store);
 
     std::string m_distanceType, m_bounding_box_type;
     float m_normal_radius; int m_consistent_normals_method, m_num_threads, m_num_kd_trees;
     bool m_flann_exact_match, m_instance_labels_primary, m_single_object_mode_legacy;
     bool m_use_smoothing, m_use_sor, m_use_ror, m_use_voxel_filtering;
+    int m_sor_mean_k, m_ror_min_neighbors;
+    float m_sor_stddev_mul, m_ror_radius, m_cutoff_distance_z;
     std::unique_ptr<Codebook> m_codebook;
     std::unique_ptr<Keypoints> m_keypoints_detector;
     std::unique_ptr<Features> m_feature_descriptor;
