@@ -42,12 +42,19 @@ struct ismhip_cloud {
     float4* sp4 = nullptr;                // (x, y, z, bits of the object-local original index)
     float4* sn4 = nullptr;                // (nx, ny, nz, 0)
     float4* slab4 = nullptr;              // normalised CIELab (L, a, b, 0), only with rgba
+    // scratch of the five-kernel grid build, allocated when a batch first takes it (grid.hip)
     uint32_t* cell_of_pt = nullptr;       // scratch: cell id per original point
     uint32_t* rank_of_pt = nullptr;       // scratch: arrival rank inside the cell
     uint32_t* members = nullptr;          // scratch: object-local original indices grouped by cell in arrival order
     GridMeta* meta = nullptr;             // [n_obj]
     uint32_t* cell_start = nullptr;       // [n_obj * ISM_GRID_STRIDE]
     float requested_cell = 0.f;
+    // keypoints in cell order (grid.hip: ism_kp_order): object-local keypoint indices of the last keypoint set described on this cloud,
+    // sorted by cell id, so that the waves of a workgroup sweep overlapping balls. Scheduling only: any permutation gives the same results.
+    uint32_t* kp_perm = nullptr;          // [kp_perm_off.back()]
+    size_t kp_perm_cap = 0;
+    const float* kp_perm_key = nullptr;   // the kpx pointer the order was built from (nullptr: none)
+    std::vector<uint32_t> kp_perm_off;    // and its offsets
     // capacities of the owned allocations (clouds are recycled through ismhip_ctx::cloud_pool)
     size_t cap_pts = 0; int cap_obj = 0; bool cap_color = false;
 };
@@ -137,6 +144,8 @@ struct ismhip_ctx {
     int knn_splits = 0;          // env ISMHIP_KNN_SPLITS: force the number of codebook splits of the squared-L2 candidate kernels (A/B runs)
     int knn_t = 0;               // env ISMHIP_KNN_T = 2 | 3: candidates kept per slot (default 4 on the 16-bit paths); fewer = cheaper epilogue, more unproven slots
     bool xcd_map = true;         // env ISMHIP_XCD_MAP=0: per-object kernels on the plain object-major block order instead of the XCD-local map (A/B runs)
+    bool grid_fused = true;      // env ISMHIP_GRID_FUSED=0: ismhip_cloud_create on the five-kernel grid build instead of one workgroup per object (A/B runs, tests; same bytes)
+    bool kp_order = true;        // env ISMHIP_KP_ORDER=0: LRF and SHOT take the keypoints in the caller's order instead of cell order (A/B runs; same results)
     float grid_xfrac = 0.f;      // env ISMHIP_GRID_XFRAC: x cells this many times finer than y/z cells (default ISM_GRID_XFRAC; A/B runs)
     int shot_var = 0;            // env ISMHIP_SHOT_VAR=2: k_shot on the contiguous candidate sweep instead of 16 interleaved segments (A/B runs; same histogram)
     bool knn_hell_emit = true;   // env ISMHIP_KNN_HELL_EMIT=0: queries the Hellinger proof leaves open go to the VALU kernel instead of the list-and-evaluate stage (A/B runs)
@@ -292,6 +301,10 @@ __device__ __forceinline__ bool xcd_object_block(int nbx, int n_obj, int& o, int
     o = (slot / nbx) * 8 + (blockIdx.x & 7);
     bx = slot % nbx;
     return o < n_obj;
+}
+// keypoint of wave `slot` of object o: through the cell-order permutation when there is one (ism_kp_order), else the slot itself
+__device__ __forceinline__ uint32_t ordered_keypoint(const uint32_t* __restrict__ perm, uint32_t kp_begin, uint32_t slot) {
+    return kp_begin + (perm ? perm[kp_begin + slot] : slot);
 }
 static inline unsigned xcd_object_grid(unsigned nbx, int n_obj) { return n_obj < 8 ? nbx * (unsigned)n_obj : 8u * nbx * (unsigned)((n_obj + 7) / 8); }
 

@@ -63,6 +63,8 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     ctx->device = device;
     { const char* e = getenv("ISMHIP_KNN_MODE"); ctx->knn_mode = !e ? 0 : (!strcmp(e, "bf16x3") ? 1 : (!strcmp(e, "f32") ? 2 : 0)); }
     { const char* e = getenv("ISMHIP_XCD_MAP"); ctx->xcd_map = !(e && e[0] == '0'); }
+    { const char* e = getenv("ISMHIP_GRID_FUSED"); ctx->grid_fused = !(e && e[0] == '0'); }
+    { const char* e = getenv("ISMHIP_KP_ORDER"); ctx->kp_order = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_GRID_XFRAC"); ctx->grid_xfrac = e ? (float)atof(e) : 0.f; }
     { const char* e = getenv("ISMHIP_SHOT_VAR"); ctx->shot_var = e ? atoi(e) : 0; }
     { const char* e = getenv("ISMHIP_KNN_TWOSTAGE"); ctx->knn_two_stage = !(e && e[0] == '0'); }

@@ -5,17 +5,23 @@
 //
 // Roofline: HBM-bound gather, algorithmic bytes = sum_k M'_k * 12 + K * 48.
 // Four small kernels instead of one fat one (the fused version needed 245 VGPRs -> 2 waves/SIMD and sat 51 % of its
-// wave cycles in s_waitcnt):
+// wave cycles in s_waitcnt). Measured since and NOT kept: two candidate blocks in flight in ball_for_each<1>
+// (78 / 72 VGPRs, one wave per SIMD fewer: lrf 5.9 -> 7.3 ms), sign votes decided in FP32 with an FP64 fallback, the wave-uniform
+// keypoint values in scalar registers (58 / 56 VGPRs, 8 waves per SIMD: lrf 5.4 -> 5.5 ms -- the sweeps wait for memory, not for the ALUs):
 //   k_lrf_cov  : wave per keypoint, streams the clipped candidate runs (coalesced SoA loads of the cell-sorted cloud),
 //                FP64 weighted covariance per lane + wave reduction -> 8 doubles per keypoint
 //   k_lrf_eig  : thread per keypoint, cyclic Jacobi 3x3 (eigen3.h) -> x / z axis candidates
 //   k_lrf_sign : wave per keypoint, re-streams the runs, counts the sign votes, writes the frame or queues a tie
+//   (k_lrf_cov and k_lrf_sign take an object's keypoints in cell order when grid.hip's ism_kp_order has built one: the four waves
+//    of a workgroup then sweep overlapping balls; every keypoint's row is written at its own index, so the order changes no result)
 //   k_lrf_tie  : work-queue kernel for sign ties (~3 % of keypoints): the 5 median neighbours BY DISTANCE decide
 //                (shot_na_lrf.hpp:139-151); rank selection by bitwise bisection over 64-bit (d^2, index) keys
 #include "common.h"
 #include "eigen3.h"
 
 uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
+const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
+                             const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
 
 namespace {
 
@@ -32,6 +38,7 @@ struct CloudView {
     const float4* sp4;        // cell-sorted (x, y, z, original index bits)
     const float *x, *y, *z;   // original order (tie kernel)
     int n_obj, nbx;           // XCD-local block map (common.h)
+    const uint32_t* kp_perm;  // keypoints in cell order (k_lrf_cov / k_lrf_sign; nullptr: as they come)
 };
 
 __device__ __forceinline__ void write_lrf(float* out, const double v1[3], const double v3[3]) {
@@ -58,8 +65,9 @@ __global__ __launch_bounds__(256) void k_lrf_cov(CloudView cv, const uint32_t* _
                                                  float radius, float r2, double* __restrict__ cov_out) {
     int o, bx;
     if (!xcd_object_block(cv.nbx, cv.n_obj, o, bx)) return;
-    const uint32_t k = kp_off[o] + bx * 4 + (threadIdx.x >> 6);
-    if (k >= kp_off[o + 1]) return;
+    const uint32_t slot = bx * 4 + (threadIdx.x >> 6);
+    if (kp_off[o] + slot >= kp_off[o + 1]) return;
+    const uint32_t k = ordered_keypoint(cv.kp_perm, kp_off[o], slot);
     const int lane = lane_id();
     const float cx = kx[k], cy = ky[k], cz = kz[k];
     const GridMeta m = cv.meta[o];
@@ -129,8 +137,9 @@ __global__ __launch_bounds__(256, 4) void k_lrf_sign(CloudView cv, const uint32_
                                                   float* __restrict__ lrf_out, uint32_t* __restrict__ tie_count, TieRec* __restrict__ tie_rec) {
     int o, bx;
     if (!xcd_object_block(cv.nbx, cv.n_obj, o, bx)) return;
-    const uint32_t k = kp_off[o] + bx * 4 + (threadIdx.x >> 6);
-    if (k >= kp_off[o + 1]) return;
+    const uint32_t slot = bx * 4 + (threadIdx.x >> 6);
+    if (kp_off[o] + slot >= kp_off[o + 1]) return;
+    const uint32_t k = ordered_keypoint(cv.kp_perm, kp_off[o], slot);
     const double* a = axes + (size_t)k * 6;
     if (isnan(a[0]) || cov[(size_t)k * 8 + 7] < 5.0) return;             // frame already written as NaN
     const int lane = lane_id();
@@ -321,6 +330,7 @@ extern "C" int ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const
                  ctx->xcd_map ? n_obj : 0, (int)((maxk + 3) / 4)};
     const float r2 = (float)((double)radius * (double)radius);   // PCL: static_cast<float>(radius*radius) with double radius
     TimerScope ts(ctx, "lrf");
+    cv.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, ko, kpx, kpy, kpz, maxk);
     ISM_HIP(ctx, hipMemsetAsync(tie_count, 0, 4, ctx->stream));
     const dim3 grid(ctx->xcd_map ? xcd_object_grid((maxk + 3) / 4, n_obj) : ((maxk + 3) / 4) * (unsigned)n_obj);
     hipLaunchKernelGGL(k_lrf_cov, grid, dim3(256), 0, ctx->stream, cv, ko, kpx, kpy, kpz, radius, r2, cov);

@@ -15,6 +15,8 @@
 #include "common.h"
 
 uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
+const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
+                             const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
 
 namespace {
 
@@ -31,6 +33,7 @@ struct ShotArgs {
     const float *lut_srgb, *lut_sxyz;
     float* desc; uint32_t* count;
     int n_obj, nbx;
+    const uint32_t* kp_perm;   // keypoints in cell order (nullptr: as they come)
 };
 
 // The per-wave LDS histogram is kept in 64-bit FIXED POINT (2^-28 units) and updated with ds_add_u64.
@@ -221,8 +224,8 @@ __global__ __launch_bounds__(256, COLOR ? 2 : 6) void k_shot(ShotArgs a) {
     if (!xcd_object_block(a.nbx, a.n_obj, o, bx)) return;
     const int wv = threadIdx.x >> 6;
     const int lane = lane_id();
-    const uint32_t k = a.kp_off[o] + bx * 4 + wv;
-    if (k >= a.kp_off[o + 1]) return;          // wave-uniform; no block-level barrier below
+    if (a.kp_off[o] + bx * 4 + wv >= a.kp_off[o + 1]) return;          // wave-uniform; no block-level barrier below
+    const uint32_t k = ordered_keypoint(a.kp_perm, a.kp_off[o], (uint32_t)(bx * 4 + wv));
     shot_bin_t* hist = sm.hist[wv];
     float* out = a.desc + (size_t)k * D;
     const float cx = a.kx[k], cy = a.ky[k], cz = a.kz[k];
@@ -320,6 +323,7 @@ int launch_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_o
     a.desc = desc_out; a.count = count_out;
     a.n_obj = ctx->xcd_map ? n_obj : 0; a.nbx = (int)((maxk + 3) / 4);
     TimerScope ts(ctx, name);
+    a.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, ko, kpx, kpy, kpz, maxk);
     const dim3 grid(ctx->xcd_map ? xcd_object_grid((unsigned)a.nbx, n_obj) : (unsigned)a.nbx * (unsigned)n_obj);
     if (ctx->shot_var & 2) hipLaunchKernelGGL((k_shot<COLOR, 2>), grid, dim3(256), 0, ctx->stream, a);      // contiguous sweep (A/B runs)
     else hipLaunchKernelGGL((k_shot<COLOR, 0>), grid, dim3(256), 0, ctx->stream, a);
