@@ -1,0 +1,169 @@
+// knn_internal.h — what more than one unit of the codeword search needs (the map of the units is at the top of knn.hip): the
+// types and device helpers in an anonymous namespace (they appear in kernel signatures, so every unit has its own), then the host
+// functions through which the units call each other. Each of those is defined in the unit that holds the kernels it launches.
+#pragma once
+#include "common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+#define KNN_BM 128       // codeword rows per tile
+#define KNN_BN 128       // queries per tile
+#define CHI_B 64         // both, in k_knn_chi2
+#define KNN_MAX_K 16
+#define KNN_FB_MAXJ 84          // dim_pad <= 1344 -> at most 84 elements per lane of a 16-lane row group
+
+template <int T>
+struct TopT {
+    float v[T]; int i[T];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int t = 0; t < T; ++t) { v[t] = __builtin_inff(); i[t] = -1; }
+    }
+    // the same insertion without a branch (k_knn_l2_ring16's epilogue: a wave enters it when ANY lane has a score to insert, and
+    // nested exec-mask branches cost more than thirteen predicated instructions); x = +inf leaves the list as it is
+    __device__ __forceinline__ void push_flat(float x, int idx) {
+        bool c[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) c[t] = x < v[t];
+#pragma unroll
+        for (int t = T - 1; t > 0; --t) {
+            v[t] = c[t - 1] ? v[t - 1] : (c[t] ? x : v[t]);
+            i[t] = c[t - 1] ? i[t - 1] : (c[t] ? idx : i[t]);
+        }
+        v[0] = c[0] ? x : v[0];
+        i[0] = c[0] ? idx : i[0];
+    }
+    // insert keeping ascending order; strict < keeps the earlier (lower row) on ties
+    __device__ __forceinline__ void push(float x, int idx) {
+        if (!(x < v[T - 1])) return;
+        v[T - 1] = x; i[T - 1] = idx;
+#pragma unroll
+        for (int t = T - 1; t > 0; --t) {
+            if (v[t] < v[t - 1]) {
+                float tv = v[t]; v[t] = v[t - 1]; v[t - 1] = tv;
+                int ti = i[t]; i[t] = i[t - 1]; i[t - 1] = ti;
+            }
+        }
+    }
+};
+
+// dynamic LDS of k_knn_l2_mfma16 (bytes): two slices of the BM codeword and BN query rows (two images each for bf16x3) + |c|^2 of a tile
+constexpr size_t knn_mfma16_lds(int BM, int BN, int KB, int NTERM) { return (size_t)2 * (BM + BN) * KB * sizeof(u16) * (NTERM == 3 ? 2 : 1) + BM * sizeof(float); }
+#define RG_BN 256
+#define RG_KB 32
+// LDS layout of k_knn_l2_ring16<T, WR, QP, PRE> in bytes: the ring of STAGES stages at 0, |c|^2 of four tiles at cn (a DMA always
+// delivers 256 floats), the thresholds published to the partner wave at thr (WR = 2: [8 waves][4 n-tiles][64]) and, QP = 2, the
+// query panel [ring_nk slices][256 queries][32 halves] at panel. The kernel takes its pointers from it, the host its launch size.
+template <int WR, int QP>
+struct Ring16Lds {
+    static constexpr int STAGES = WR == 2 ? 4 : 3, STAGE_HALVES = (QP ? WR * 128 : WR * 128 + RG_BN) * RG_KB;
+    static constexpr size_t cn = (size_t)STAGES * STAGE_HALVES * sizeof(u16);
+    static constexpr size_t thr = cn + 4 * 256 * sizeof(float);
+    static constexpr size_t panel = thr + (WR == 2 ? 8 * 4 * 64 * sizeof(float) : 0);
+    static constexpr size_t total(int ring_nk) { return panel + (QP ? (size_t)ring_nk * 256 * RG_KB * sizeof(u16) : 0); }
+};
+
+struct VerifyParams {
+    float ku;         // 1.01 * K * u : relative error bound of a K-term fp32 functor sum (u = 2^-24)
+    float dot_rel;    // bound on |approx(q.c) - q.c| / (|q||c|) of the candidate kernel (f32 fma chain: ku; bf16x3: see k_knn_l2_mfma16)
+    float cmax2;      // max |c|^2 over the codebook (L2 only)
+    float dabs_c;     // f16 candidates: worst-case absolute error of one codebook element (2^-14 / scale), else 0
+    const float* dabs_q;   // f16 candidates: the same for the query batch (device scalar), else nullptr
+    float sqrt_dim;   // sqrt(dim_pad)
+    float cn_acc;     // k_knn_l2_ring16 adds |c|^2 through the accumulator: extra 1.01 (K+1) 2^-23 |c|max^2 on the score, else 0
+};
+// absolute part of the candidate kernel's dot-product error: sum |dq_i c_i| + |q_i dc_i| + |dq_i dc_i| with |dq_i| <= dq, |dc_i| <= dc
+__device__ __forceinline__ float knn_abs_err(const VerifyParams& vp, float qn2) {
+    if (!vp.dabs_q) return 0.f;
+    const float dq = vp.dabs_q[0], dc = vp.dabs_c;
+    return 1.01f * (vp.sqrt_dim * (dq * sqrtf(vp.cmax2) + dc * sqrtf(qn2)) + vp.sqrt_dim * vp.sqrt_dim * dq * dc);
+}
+#define KNN_U 5.9604645e-08f
+// eps_s of the lower-bound proofs (k_knn_rerank_hell, k_hell_tau, thr_tau_of): the error bound of a candidate score for a query
+// with |q|^2 = qn2 (k_knn_rerank's proof comment derives it), rounded up
+__device__ __forceinline__ float knn_eps_s(const VerifyParams& vp, float qn2) {
+    return (17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2) * 1.00001f;
+}
+
+// error model of the candidate scores for the proofs (k_knn_rerank, k_knn_rerank_hell, k_hell_tau, k_thr_tau). mode as in KnnPlan;
+// f16: qsc = the query batch's scalars (k_to_f16), cn_acc = the caller charges |c|^2 carried through the accumulator
+VerifyParams knn_verify_params(const ismhip_codebook* xb, int dim_pad, int mode, const uint32_t* qsc, bool cn_acc) {
+    VerifyParams vp;
+    vp.ku = 1.01f * (float)dim_pad * KNN_U;
+    // relative part of the candidate kernel's dot error (see the kernels): representation + accumulation (<= 2^-23 per add, any order)
+    vp.dot_rel = mode == 0 ? (2.002f * 4.8828125e-04f + 1.01f * (float)dim_pad * 1.1920929e-07f)
+               : mode == 1 ? (3.1f * 1.52587890625e-05f + 1.01f * 3.f * (float)dim_pad * 1.1920929e-07f) : vp.ku;
+    vp.cmax2 = xb->max_norm2;
+    vp.dabs_c = mode == 0 ? 6.103515625e-05f / xb->f16_scale : 0.f;
+    vp.dabs_q = mode == 0 ? (const float*)(qsc + 2) : nullptr;
+    vp.sqrt_dim = sqrtf((float)dim_pad);
+    vp.cn_acc = mode == 0 && cn_acc ? 1.01f * (float)(dim_pad + 1) * 1.1920929e-07f : 0.f;
+    return vp;
+}
+
+// tau_q such that functor(q, c) < thr  =>  score(c) <= tau_q. A row with score s has D >= |q|^2 (1 - 16u) + s - eps_s and functor
+// value >= D (1 - ku) (k_knn_rerank, k_hell_tau with dk := thr); the extra (dim/64 + 8) u |q|^2 covers the rounding of this wave's
+// own |q|^2 sum. A non-finite tau (inf / NaN in the batch) lists every row: the cap then sends the query to the exact scan.
+__device__ __forceinline__ float thr_tau_of(float thr, float qn2, int dim, const VerifyParams& vp) {
+    const float eps_s = knn_eps_s(vp, qn2);
+    float t = thr * (1.f + 2.f * vp.ku) - qn2 * (1.f - 16.f * KNN_U) + eps_s + 8.f * KNN_U * (qn2 + vp.cmax2 + thr)
+            + (float)(dim / 64 + 8) * KNN_U * qn2;
+    if (!(fabsf(t) < __builtin_inff())) t = __builtin_inff();
+    return t;
+}
+
+// the conditions under which the searches run on the matrix cores (shared by ismhip_knn and ismhip_knn_threshold): a launch big
+// enough to fill the chip, whole 16-byte chunks per descriptor, no A/B override of the candidate kernel
+bool knn_matrix_gate(const ismhip_ctx* ctx, const ismhip_codebook* cb, int nq) {
+    return ctx->knn_mode == 0 && ctx->knn_t == 0 && nq >= 256 && cb->n_words >= 1024 && cb->dim % 4 == 0;
+}
+
+}  // namespace
+
+// ---- knn.hip ------------------------------------------------------------------------------------------------------------------------
+// the dynamic-LDS cap of a kernel is raised once per ctx (per device), to the largest size any launch of that kernel uses
+int knn_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes);
+// sq[nq x dim_pad] = sqrt of the query rows (zero padded; 4 more bytes behind them hold the flag); negative = some element is
+// negative or NaN, read back: the call synchronises the stream
+int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, float* sq, bool& negative);
+// An f16 EMIT sweep (chi-square stage 2, radius search, large K) is three steps on the stream: knn_f16_emit_image makes the f16
+// image qimg of the n query rows qv (row stride ldv, n_pad = n rounded up to 128; sc = the batch's f16 scalars, zeroed by the caller),
+// the caller launches its tau kernel with knn_verify_params(xb, dim_pad, 0, sc, cn_acc), knn_mfma16_emit lists the rows.
+int knn_f16_emit_image(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_codebook* xb, const float* qv, int n, int ldv, int n_pad,
+                       uint32_t* sc, u16* qimg);
+
+// ---- the 16-bit candidate kernels: knn_ring16.hip, knn_mfma16.hip ---------------------------------------------------------------------
+// what k_knn_l2_ring16 and k_knn_l2_mfma16 both take, under the names of their parameter lists (the ring has no wl / ql)
+struct KnnCandArgs {
+    const u16 *wh, *wl; const float* word_norm; int n_tiles_m, ld, k_steps;
+    const u16 *qh, *ql; int nq; const float* out_scale; int tiles_per_split, n_splits;
+    float* cand_val; int* cand_idx; int cand_stride; float* cand_bound; int bound_stride;
+};
+// the instance for T candidates per slot (1 .. 4, else nullptr): WR x 128 codeword rows per tile, QP = 2 with the resident query
+// panel, PRE = 1 the sampling pre-pass
+const void* knn_ring16_kernel(int T, int WR, int QP, int PRE = 0);
+// one candidate launch of kern = knn_ring16_kernel(T, ...); thr0 != nullptr: the sampling pre-pass over every pre_step-th tile first,
+// which leaves the start thresholds of the main launch in thr0[nq rounded up to 256], relaxed by pre_relax
+int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, int threads, size_t lds, KnnCandArgs a,
+                      unsigned int* stream_clock, float* thr0, int pre_step, float pre_relax);
+// the candidate instances: bf16x3 on the 256 x 256 or the 128 x 128 tile, f16 on the 128 x 128 tile (nullptr: not built)
+const void* knn_mfma16_kernel(int T, int mode, bool big_tile);
+int knn_mfma16_launch(ismhip_ctx* ctx, const void* kern, unsigned grid, int threads, size_t lds, KnnCandArgs a,
+                      const float* emit_tau, uint32_t* emit_cnt, uint32_t* emit_list, int emit_cap);
+// k_knn_l2_mfma16<EMIT> over the f16 image qimg (knn_f16_emit_image): every row with score <= tau[q] is appended to
+// rows[q * cap ...] (count in emit_cnt[q])
+int knn_mfma16_emit(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_codebook* xb, int n, int n_pad, const uint32_t* sc, const u16* qimg,
+                    const float* tau, uint32_t* emit_cnt, uint32_t* rows, int cap);
+
+// ---- knn_cand.hip: the f32 MFMA and the chi-square candidate kernels, T = 1 .. 4 -------------------------------------------------------
+int knn_l2_f32_launch(ismhip_ctx* ctx, int T, unsigned grid, const ismhip_codebook* cb, const float* q, int nq, int ldq, int tiles_per_split, int n_splits,
+                      float* cand_val, int* cand_idx, int n_cand, float* cand_bound, int n_bound);
+// (with k_any_negative over the batch into q_negative, zeroed by the caller, when the codebook has no negative element)
+int knn_chi2_launch(ismhip_ctx* ctx, int T, int n_qt, const ismhip_codebook* cb, const float* q, int nq, int ldq, uint32_t* q_negative, int tiles_per_split, int n_splits,
+                    float* cand_val, int* cand_idx, int n_cand, float* cand_bound, int n_bound);

@@ -12,7 +12,7 @@
 //   R        the fp32 matrix that is uploaded; sigma_max(R)^2 <= 1 + |R R^T - I|_F, computed in fp64 from those fp32 values
 //   x^       := f16 image of fl(R x) divided by its scale (an exactly representable fp32 vector). The candidate kernel's score is
 //            |c^|^2 - 2 c^.q^ up to ACCUMULATION error only (products of f16 values are exact in fp32), so
-//            |q^ - c^|^2 >= |q^|^2 + score - eps_acc                                        (eps_acc: VerifyParams of knn.hip)
+//            |q^ - c^|^2 >= |q^|^2 + score - eps_acc                                        (eps_acc: VerifyParams of knn_internal.h)
 //   |x^ - R x|_2 <= d_rel |x|_2 + d_abs: fp32 rotation (any summation order, 2^-23 per add) + round-to-nearest f16 + flush-to-zero floor
 //   => |q - c| >= (|q^ - c^| - delta(q) - delta(c)) / sigma_max(R)
 // The query image uses a scale FIXED per codebook (queries are assumed to be at most twice as long as the longest codeword; three
