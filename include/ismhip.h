@@ -236,6 +236,9 @@ int  ismhip_codebook_create(ismhip_ctx* ctx, int n_words, int dim, const float* 
 /* Codeword::getClassId per word (codebook/codeword.h:73-75; only meaningful for one-feature codewords). Default when not set:
  * the class of the word's first stored vote. Needed by ismhip_knn_rule only. */
 int  ismhip_codebook_set_word_class(ismhip_ctx* ctx, ismhip_codebook* cb, const uint32_t* word_class_h);
+/* Codeword::getFeaturePosition per word (codebook/codeword.h; the keypoint the codeword was trained at, Vote::keypoint_training of
+ * every vote it casts, voting.cpp:71). word_keypoint_h: host [n_words*3]. Needed by ismhip_vote_keypoints(_csr) only. */
+int  ismhip_codebook_set_word_keypoint(ismhip_ctx* ctx, ismhip_codebook* cb, const float* word_keypoint_h);
 int  ismhip_codebook_destroy(ismhip_ctx* ctx, ismhip_codebook* cb);
 int  ismhip_codebook_max_votes_per_word(const ismhip_codebook* cb);
 /* Diagnostic: leading rotated coordinates of the codebook's stage-1 search image (0 = none: the squared-L2 candidate stage runs on
@@ -304,6 +307,42 @@ int  ismhip_cast_votes_csr(ismhip_ctx* ctx, const ismhip_codebook* cb, uint32_t 
                            float* vote_pos_out, float* vote_weight_out, int32_t* vote_class_out, int32_t* vote_instance_out,
                            int32_t* vote_codeword_out, float* vote_bbox_quat_out, float* vote_bbox_size_out);
 
+/* The keypoint pair every vote carries (Voting::vote, voting/voting.cpp:58-77: Vote::keypoint = the query keypoint, Vote::keypoint_training
+ * = the activated codeword's getFeaturePosition()), in the slot layout of ismhip_cast_votes / ismhip_cast_votes_csr with the same
+ * (nq, k, idx) / (act_offsets, n_act, idx). vote_kp_out / vote_kp_train_out: device [n_slots*3]; a slot beyond the codeword's stored
+ * votes gets zeros (the weight tests of castVote are not repeated: such a slot has class -1 and is never read). The codebook must
+ * hold its training keypoints (ismhip_codebook_set_word_keypoint). Input of the RANSAC vote filter. */
+int  ismhip_vote_keypoints(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* kpx, const float* kpy, const float* kpz,
+                           int k, const int32_t* idx, float* vote_kp_out, float* vote_kp_train_out);
+int  ismhip_vote_keypoints_csr(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* kpx, const float* kpy, const float* kpz,
+                               const uint32_t* act_offsets, int64_t n_act, const int32_t* idx, float* vote_kp_out, float* vote_kp_train_out);
+
+/* ---- RANSAC vote filter: Voting::filterVotesWithRansac (voting/voting.cpp:110-127, 356-433) over
+ *      pcl::registration::CorrespondenceRejectorSampleConsensus. PCL is EXTERNAL: the draws (a counter-based hash instead of PCL's
+ *      mt19937(12345)), the three-point model in double and the scoring in double are this library's own definitions (DESIGN.md §4.6,
+ *      restated in tests/ransac_ref.py; parity with the reference unpinned). PCL's SEQUENTIAL loop is the contract: hypotheses are
+ *      evaluated in chunks, the stopping point is found by a scan in index order, ties keep the lowest index.
+ *      Cluster c = votes [cluster_offsets_h[c], cluster_offsets_h[c+1]) of src_xyz (training keypoints) / tgt_xyz (scene keypoints)
+ *      (device [n*3]); threshold_h[n_clusters] (host): inlier distance of every cluster, <= 0 drops it. A cluster is dropped
+ *      (kept_out 0, no inliers) with fewer than 3 votes, without a good sample, with fewer than 3 inliers, or when the best motion
+ *      is the identity to 1e-4 (Eigen isIdentity: the reference drops an object seen in its training pose). Outputs (device):
+ *      inlier_out[n] 0/1, kept_out / n_inliers_out / best_hypothesis_out / iterations_out [n_clusters] (the last two may be NULL;
+ *      iterations = the sequential stopping point), transform_out [n_clusters*16] row-major 4x4 or NULL (identity when dropped).
+ *      RansacRefineModel is not built. Synchronises. Counters (ismhip_timer_get, valid without timers, since the last
+ *      ismhip_timers_reset): "ransac_clusters", "ransac_clusters_kept", "ransac_hypotheses_needed" (sum of the stopping points),
+ *      "ransac_hypotheses_evaluated" (what the chunks ran); timer "ransac_filter". */
+int  ismhip_ransac_filter(ismhip_ctx* ctx, int n_clusters, const uint32_t* cluster_offsets_h, const float* src_xyz, const float* tgt_xyz,
+                          const float* threshold_h, int max_iterations, unsigned long long seed,
+                          uint8_t* inlier_out, int32_t* kept_out, int32_t* n_inliers_out, int32_t* best_hypothesis_out, int32_t* iterations_out,
+                          float* transform_out);
+/* Diagnostic: exactly hypothesis hypothesis_h[c] of cluster c, whatever its count: valid_out[c] = it had a good sample, inlier_out
+ * its inlier mask, n_inliers_out its count, d2_out (device double [n]) the squared residual of every vote, transform_out (device
+ * double [n_clusters*12], R row-major then t, or NULL). No identity test, no counters. The parity tests measure the library's d^2
+ * against the restatement's with it. Synchronises. */
+int  ismhip_ransac_hypothesis(ismhip_ctx* ctx, int n_clusters, const uint32_t* cluster_offsets_h, const float* src_xyz, const float* tgt_xyz,
+                              const float* threshold_h, unsigned long long seed, const int32_t* hypothesis_h,
+                              uint8_t* inlier_out, int32_t* valid_out, int32_t* n_inliers_out, double* d2_out, double* transform_out);
+
 /* ---- maxima: Voting::findMaxima + VotingMeanShift::iFindMaxima + MaximaHandler
  *      (voting/voting.cpp:79-328,436-462; voting_mean_shift.cpp:39-177,201-481; maxima_handler.cpp:51-157) */
 typedef struct ismhip_maxima_params {
@@ -342,6 +381,32 @@ int  ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets
                         int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                         float* max_bbox_size_out /* may be NULL */, int32_t* max_n_votes_out,
                         float* class_score_out);
+
+/* Voting.RansacVoteFiltering (voting.cpp:110-127): every maximum's votes pass the RANSAC vote filter between the mode search and
+ * the per-maximum sums (voting.cpp:131-236), which then see the inliers only; MinVotesThreshold is tested before and after; a
+ * dropped cluster gives no maximum. The in-place reweighting of ALL votes around a maximum (voting_mean_shift.cpp:161-176) stays
+ * before the filter. The cluster's list is its votes in ascending slot order. The instance tally uses the inlier votes' own
+ * instance ids (the reference indexes the unfiltered list). */
+typedef struct ismhip_ransac_params {
+    const float* vote_keypoint;             /* device [n_slots*3]: vote_kp_out of ismhip_vote_keypoints(_csr) (the RANSAC target) */
+    const float* vote_keypoint_training;    /* device [n_slots*3]: vote_kp_train_out (the RANSAC source) */
+    float inlier_threshold;                 /* Voting.RansacInlierThreshold, already scaled when the type is not "Fixed" */
+    const float* class_inlier_threshold_h;  /* [n_classes] per-class threshold (RansacInlierThresholdType "ObjectRadius" /
+                                               "BoundingBoxMedian": the factor times m_dimensions_map[class]); NULL -> inlier_threshold */
+    int   max_iterations;                   /* corr_rejector.setMaximumIterations: 10000 in the reference */
+    unsigned long long seed;                /* of the draws; the same stream for every cluster, as in PCL */
+} ismhip_ransac_params;
+/* The arguments of ismhip_find_maxima, then the filter's. max_transform_out: device [n_obj*max_maxima*16] or NULL: the 4x4 (row-major,
+ * float) of every returned maximum's best hypothesis (the reference discards it); a maximum merged by MaxFilterType "Merge" carries
+ * the motion of the maximum whose place it takes. Timer "maxima"; the counters of ismhip_ransac_filter. */
+int  ismhip_find_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                               const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                               const int32_t* vote_instance, const float* vote_bbox_size /* may be NULL */,
+                               const ismhip_maxima_params* params,
+                               int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                               int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                               float* max_bbox_size_out /* may be NULL */, int32_t* max_n_votes_out,
+                               float* class_score_out, const ismhip_ransac_params* ransac, float* max_transform_out);
 
 /* ---- training: Codebook::activate (codebook/codebook.cpp:64-368): exact kNN activation of every training feature in the
  *      codebook, class sigma^2 (:94-193), K = 1 clean-up (:201-224), vote = rotateInto(centre - keypoint, LRF)
@@ -422,6 +487,18 @@ int  ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offs
                            int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                            float* max_bbox_size_out /* may be NULL */, int32_t* max_n_votes_out,
                            float* class_score_out);
+
+/* ismhip_hough3d_maxima with Voting.RansacVoteFiltering: as ismhip_find_maxima_ransac. The voters of a maximum's bin are the cluster;
+ * the maximum's position stays the weighted centre of ALL voters (filterVotesWithRansac leaves a cluster's position alone), every
+ * other per-maximum sum is taken over the inliers. Timer "hough3d". */
+int  ismhip_hough3d_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                                  const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                                  const int32_t* vote_instance, const float* vote_bbox_size /* may be NULL */,
+                                  const ismhip_hough_params* params,
+                                  int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                                  int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                                  float* max_bbox_size_out /* may be NULL */, int32_t* max_n_votes_out,
+                                  float* class_score_out, const ismhip_ransac_params* ransac, float* max_transform_out);
 
 #ifdef __cplusplus
 }

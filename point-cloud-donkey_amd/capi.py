@@ -30,7 +30,11 @@ EXPORTS = [
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
+    "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
+    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac",
 ]
+RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
+RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
 
 
 class MaximaParams(C.Structure):
@@ -47,6 +51,11 @@ class HoughParams(C.Structure):
                 ("class_bin_h", C.c_void_p), ("use_interpolation", C.c_int), ("rel_threshold", C.c_float),
                 ("min_votes_threshold", C.c_int), ("min_threshold", C.c_float), ("best_k", C.c_int), ("max_maxima", C.c_int), ("max_filter", C.c_int),
                 ("vote_bbox_quat", C.c_void_p), ("max_bbox_quat_out", C.c_void_p)]
+
+
+class RansacParams(C.Structure):
+    _fields_ = [("vote_keypoint", C.c_void_p), ("vote_keypoint_training", C.c_void_p), ("inlier_threshold", C.c_float),
+                ("class_inlier_threshold_h", C.c_void_p), ("max_iterations", C.c_int), ("seed", C.c_ulonglong)]
 
 
 class IsmHipError(RuntimeError):
@@ -192,6 +201,12 @@ class Codebook:
 
     def set_word_class(self, word_class):
         self.ctx.check(lib().ismhip_codebook_set_word_class(self.ctx._h, self._h, _p(_u32(word_class))), "ismhip_codebook_set_word_class")
+
+    def set_word_keypoint(self, word_keypoint):
+        """[n_words, 3] training keypoint of every codeword (Codeword::getFeaturePosition): the RANSAC vote filter's source points"""
+        kp = np.ascontiguousarray(np.asarray(word_keypoint, dtype=np.float32))
+        assert kp.shape == (self.n_words, 3)
+        self.ctx.check(lib().ismhip_codebook_set_word_keypoint(self.ctx._h, self._h, _p(kp)), "ismhip_codebook_set_word_keypoint")
 
     def close(self):
         if self._h:
@@ -519,12 +534,92 @@ def cast_votes_csr(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, act_offsets, idx, 
     return dict(pos=pos, weight=w, cls=cls, inst=inst, codeword=cw, bbox_quat=bq, bbox_size=bs)
 
 
+def vote_keypoints(ctx, cb, kpx, kpy, kpz, idx):
+    """ismhip_vote_keypoints: (keypoint, keypoint_training) [n_slots, 3] of every vote slot of cast_votes(idx [nq, k])"""
+    torch = _torch()
+    nq, k = idx.shape
+    ns = nq * k * max(cb.max_votes, 0)
+    kp = torch.zeros((ns, 3), dtype=torch.float32, device=idx.device)
+    kpt = torch.zeros((ns, 3), dtype=torch.float32, device=idx.device)
+    ctx.check(lib().ismhip_vote_keypoints(ctx._h, cb._h, C.c_int(nq), _p(kpx), _p(kpy), _p(kpz), C.c_int(k), _p(idx), _p(kp), _p(kpt)), "ismhip_vote_keypoints")
+    return kp, kpt
+
+
+def vote_keypoints_csr(ctx, cb, kpx, kpy, kpz, act_offsets, idx):
+    """ismhip_vote_keypoints_csr: the same in the slot layout of cast_votes_csr"""
+    torch = _torch()
+    dev = idx.device
+    if isinstance(act_offsets, np.ndarray):
+        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(dev)
+    nq = act_offsets.shape[0] - 1
+    n_act = idx.shape[0]
+    ns = n_act * max(cb.max_votes, 0)
+    kp = torch.zeros((ns, 3), dtype=torch.float32, device=dev)
+    kpt = torch.zeros((ns, 3), dtype=torch.float32, device=dev)
+    ctx.check(lib().ismhip_vote_keypoints_csr(ctx._h, cb._h, C.c_int(nq), _p(kpx), _p(kpy), _p(kpz), _p(act_offsets), C.c_int64(n_act), _p(idx), _p(kp), _p(kpt)),
+              "ismhip_vote_keypoints_csr")
+    return kp, kpt
+
+
+def ransac_filter(ctx, cluster_offsets, src_xyz, tgt_xyz, threshold, max_iterations=RANSAC_MAX_ITERATIONS, seed=RANSAC_SEED, want_transform=True):
+    """ismhip_ransac_filter over a CSR of clusters: src_xyz / tgt_xyz device [n, 3] (training / scene keypoints), threshold a scalar or
+    one value per cluster -> dict(inlier [n] uint8, kept, n_inliers, best_hypothesis, iterations [n_clusters] int32, transform
+    [n_clusters, 4, 4]) of device tensors"""
+    torch = _torch()
+    off = _u32(cluster_offsets)
+    nc = len(off) - 1
+    n = int(off[-1])
+    dev = src_xyz.device
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (nc,)))
+    out = dict(inlier=torch.zeros((n,), dtype=torch.uint8, device=dev), kept=torch.zeros((nc,), dtype=torch.int32, device=dev),
+               n_inliers=torch.zeros((nc,), dtype=torch.int32, device=dev), best_hypothesis=torch.zeros((nc,), dtype=torch.int32, device=dev),
+               iterations=torch.zeros((nc,), dtype=torch.int32, device=dev),
+               transform=torch.zeros((nc, 4, 4), dtype=torch.float32, device=dev) if want_transform else None)
+    ctx.check(lib().ismhip_ransac_filter(ctx._h, C.c_int(nc), _p(off), _p(src_xyz), _p(tgt_xyz), _p(thr), C.c_int(max_iterations), C.c_ulonglong(seed),
+                                         _p(out["inlier"]), _p(out["kept"]), _p(out["n_inliers"]), _p(out["best_hypothesis"]), _p(out["iterations"]),
+                                         _p(out["transform"])), "ismhip_ransac_filter")
+    return out
+
+
+def ransac_hypothesis(ctx, cluster_offsets, src_xyz, tgt_xyz, threshold, hypothesis, seed=RANSAC_SEED):
+    """ismhip_ransac_hypothesis (diagnostic): hypothesis[c] of every cluster -> dict(inlier, valid, n_inliers, d2 [n] float64,
+    transform [n_clusters, 12] float64 = R row-major, then t)"""
+    torch = _torch()
+    off = _u32(cluster_offsets)
+    nc = len(off) - 1
+    n = int(off[-1])
+    dev = src_xyz.device
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (nc,)))
+    hyp = np.ascontiguousarray(np.broadcast_to(np.asarray(hypothesis, dtype=np.int32), (nc,)))
+    out = dict(inlier=torch.zeros((n,), dtype=torch.uint8, device=dev), valid=torch.zeros((nc,), dtype=torch.int32, device=dev),
+               n_inliers=torch.zeros((nc,), dtype=torch.int32, device=dev), d2=torch.zeros((n,), dtype=torch.float64, device=dev),
+               transform=torch.zeros((nc, 12), dtype=torch.float64, device=dev))
+    ctx.check(lib().ismhip_ransac_hypothesis(ctx._h, C.c_int(nc), _p(off), _p(src_xyz), _p(tgt_xyz), _p(thr), C.c_ulonglong(seed), _p(hyp),
+                                             _p(out["inlier"]), _p(out["valid"]), _p(out["n_inliers"]), _p(out["d2"]), _p(out["transform"])),
+              "ismhip_ransac_hypothesis")
+    return out
+
+
+def _ransac_params(ransac, n_classes):
+    """ransac: dict(vote_keypoint, vote_keypoint_training [n_slots, 3] device; inlier_threshold; optional class_inlier_threshold [n_classes],
+    max_iterations, seed) -> (RansacParams, objects to keep alive)"""
+    cthr = ransac.get("class_inlier_threshold")
+    if cthr is not None:
+        cthr = np.ascontiguousarray(np.asarray(cthr, dtype=np.float32))
+        assert cthr.shape == (n_classes,)
+    R = RansacParams(_p(ransac["vote_keypoint"]).value, _p(ransac["vote_keypoint_training"]).value, float(ransac.get("inlier_threshold", 0.1)),
+                     cthr.ctypes.data if cthr is not None else None, int(ransac.get("max_iterations", RANSAC_MAX_ITERATIONS)),
+                     int(ransac.get("seed", RANSAC_SEED)))
+    return R, cthr
+
+
 def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, max_iter=1000, kernel=KERNEL_GAUSSIAN,
                 suppression=SUPPRESS_AVERAGE, min_votes_threshold=1, min_threshold=0.0, best_k=-1, max_maxima=16,
                 class_bandwidth=None, max_filter=0, average_rotation=False, single_object_max_type=SOM_MEANSHIFT,
-                object_centroid=None, object_radius=None):
+                object_centroid=None, object_radius=None, ransac=None):
     """average_rotation: votes["bbox_quat"] in, out["bbox_quat"] per maximum; single_object_max_type != SOM_MEANSHIFT needs
-    object_centroid [n_obj,3] (and object_radius [n_obj] for SOM_MODEL_RADIUS) as device tensors"""
+    object_centroid [n_obj,3] (and object_radius [n_obj] for SOM_MODEL_RADIUS) as device tensors; ransac (see _ransac_params):
+    Voting.RansacVoteFiltering through ismhip_find_maxima_ransac, out["transform"] [n_obj, max_maxima, 4, 4]"""
     torch = _torch()
     so = _u32(slot_offsets)
     n_obj = len(so) - 1
@@ -546,10 +641,16 @@ def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, 
         n_votes=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
         class_score=torch.empty((n_obj, n_classes), dtype=torch.float32, device=dev),
     )
-    ctx.check(lib().ismhip_find_maxima(ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
-                                       _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
-                                       _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
-                                       _p(out["n_votes"]), _p(out["class_score"])), "ismhip_find_maxima")
+    args = (ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
+            _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
+            _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
+            _p(out["n_votes"]), _p(out["class_score"]))
+    if ransac is None:
+        ctx.check(lib().ismhip_find_maxima(*args), "ismhip_find_maxima")
+    else:
+        R, _keep = _ransac_params(ransac, n_classes)
+        out["transform"] = torch.zeros((n_obj, max_maxima, 4, 4), dtype=torch.float32, device=dev)
+        ctx.check(lib().ismhip_find_maxima_ransac(*args, C.byref(R), _p(out["transform"])), "ismhip_find_maxima_ransac")
     if bq_out is not None:
         out["bbox_quat"] = bq_out
     return out
@@ -557,8 +658,8 @@ def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, 
 
 def hough3d_maxima(ctx, slot_offsets, votes, n_classes, bin_size, min_coord=(-5, -5, -5), max_coord=(5, 5, 5), use_interpolation=True,
                    rel_threshold=0.8, min_votes_threshold=1, min_threshold=0.0, best_k=-1, max_maxima=16, class_bin=None, max_filter=0,
-                   average_rotation=False):
-    """VotingHough3D on the device: same outputs as find_maxima"""
+                   average_rotation=False, ransac=None):
+    """VotingHough3D on the device: same outputs as find_maxima (ransac: as there, through ismhip_hough3d_maxima_ransac)"""
     torch = _torch()
     so = _u32(slot_offsets)
     n_obj = len(so) - 1
@@ -579,10 +680,16 @@ def hough3d_maxima(ctx, slot_offsets, votes, n_classes, bin_size, min_coord=(-5,
         n_votes=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
         class_score=torch.empty((n_obj, n_classes), dtype=torch.float32, device=dev),
     )
-    ctx.check(lib().ismhip_hough3d_maxima(ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
-                                          _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
-                                          _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
-                                          _p(out["n_votes"]), _p(out["class_score"])), "ismhip_hough3d_maxima")
+    args = (ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
+            _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
+            _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
+            _p(out["n_votes"]), _p(out["class_score"]))
+    if ransac is None:
+        ctx.check(lib().ismhip_hough3d_maxima(*args), "ismhip_hough3d_maxima")
+    else:
+        R, _keep = _ransac_params(ransac, n_classes)
+        out["transform"] = torch.zeros((n_obj, max_maxima, 4, 4), dtype=torch.float32, device=dev)
+        ctx.check(lib().ismhip_hough3d_maxima_ransac(*args, C.byref(R), _p(out["transform"])), "ismhip_hough3d_maxima_ransac")
     if bq_out is not None:
         out["bbox_quat"] = bq_out
     return out

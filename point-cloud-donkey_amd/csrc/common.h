@@ -101,6 +101,7 @@ struct ismhip_codebook {
     float* vote_bbox_size = nullptr; // [n_votes*3]
     float* class_sigma = nullptr;    // [n_classes]
     uint32_t* word_class = nullptr;  // [n_words] Codeword::getClassId
+    float* word_keypoint = nullptr;  // [n_words*3] Codeword::getFeaturePosition (ismhip_codebook_set_word_keypoint; the RANSAC vote filter's training keypoints)
     // chi-square candidates on the matrix cores (Hellinger lower bound, k_knn_rerank_hell): a shadow codebook that owns the 16-bit
     // images, norms and scales of sqrt(words); its fp32 words are not kept. Only for codebooks without negative / NaN elements.
     ismhip_codebook* chi_shadow = nullptr;
@@ -134,6 +135,7 @@ struct ismhip_ctx {
     // destroyed clouds keep their device allocations here for the next ismhip_cloud_create (no hipMalloc/hipFree per batch)
     std::vector<ismhip_cloud*> cloud_pool;
     uint32_t* truncated_d = nullptr;  // device counter: maxima dropped by the per-class / per-object caps of find_maxima / hough3d_maxima (ismhip_sync reports and clears it)
+    unsigned long long* ransac_counters_d = nullptr;   // device counters of the RANSAC vote filter: clusters, clusters kept, hypotheses needed, hypotheses evaluated (since the last ismhip_timers_reset)
     uint32_t knn_stats[2] = {0, 0};   // last ismhip_knn: {queries, (query,slot) items} sent to the exact fallback (valid with timers on, after a sync)
     std::set<const void*> attr_done;  // kernels whose MaxDynamicSharedMemorySize attribute has been raised on THIS ctx's device
     uint32_t knn_stage2_queries = 0;  // last two-stage ismhip_knn: queries the T = 2 stage could not prove (searched again with T = 4)
@@ -171,7 +173,7 @@ struct ismhip_ctx {
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC
 };
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);

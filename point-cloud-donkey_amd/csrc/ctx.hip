@@ -123,6 +123,7 @@ int ismhip_ctx_destroy(ismhip_ctx* ctx) {
     if (ctx->lut_srgb) (void)hipFree(ctx->lut_srgb);
     if (ctx->lut_sxyz) (void)hipFree(ctx->lut_sxyz);
     if (ctx->truncated_d) (void)hipFree(ctx->truncated_d);
+    if (ctx->ransac_counters_d) (void)hipFree(ctx->ransac_counters_d);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return ISMHIP_OK;
@@ -172,6 +173,7 @@ int ismhip_timers_reset(ismhip_ctx* ctx) {
     if (!ctx) return ISMHIP_ERR_INVALID;
     resolve_timers(ctx);
     for (auto& kv : ctx->timers) { kv.second.ms = 0; kv.second.launches = 0; }
+    if (ctx->ransac_counters_d) { ISM_HIP(ctx, hipMemsetAsync(ctx->ransac_counters_d, 0, 4 * sizeof(unsigned long long), ctx->stream)); ISM_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
     return ISMHIP_OK;
 }
 
@@ -185,6 +187,18 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
         static const char* const lk[3] = {"knn_large_k_certified_queries", "knn_large_k_retry_queries", "knn_large_k_exact_queries"};
         for (int i = 0; i < 3; ++i)
             if (std::strcmp(name, lk[i]) == 0) { if (ms_out) *ms_out = (double)ctx->knn_lk_stats[i]; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    }
+    {   // RANSAC vote filter (ransac.hip, maxima.hip): device counters, read on the ctx stream
+        static const char* const rs[4] = {"ransac_clusters", "ransac_clusters_kept", "ransac_hypotheses_needed", "ransac_hypotheses_evaluated"};
+        for (int i = 0; i < 4; ++i)
+            if (std::strcmp(name, rs[i]) == 0) {
+                unsigned long long v[4] = {0, 0, 0, 0};
+                if (ctx->ransac_counters_d) {
+                    ISM_HIP(ctx, hipMemcpyAsync(v, ctx->ransac_counters_d, sizeof(v), hipMemcpyDeviceToHost, ctx->stream));
+                    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                }
+                if (ms_out) *ms_out = (double)v[i]; if (launches_out) *launches_out = 1; return ISMHIP_OK;
+            }
     }
     if (std::strcmp(name, "knn_stage2_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_queries; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_flagged_queries") == 0 || std::strcmp(name, "knn_flagged_items") == 0) {     // counters, not times

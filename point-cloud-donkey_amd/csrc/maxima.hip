@@ -9,8 +9,11 @@
 // seed at a time with its 64 lanes striding the votes, and the order-dependent greedy passes (average, suppress)
 // run on one lane exactly as the reference's loops do. Votes of a class are taken in slot order.
 // Round 3: single-object max types (one density estimate at the cloud centroid), MaxFilterType "Merge", AverageRotation (quaternion
-// scatter matrix -> dominant eigenvector). Not built (as in the oracle): RANSAC vote filter, global features.
+// scatter matrix -> dominant eigenvector). Not built (as in the oracle): global features.
+// RANSAC vote filter (Voting.RansacVoteFiltering, voting.cpp:110-127, 356-433): k_find_maxima_ransac / k_hough3d_ransac run ransac.h's
+// filter on every maximum's member list between the member search and the per-maximum sums; the plain kernels do not contain it.
 #include "common.h"
+#include "ransac.h"
 #include <cstring>
 
 namespace {
@@ -31,7 +34,17 @@ struct MaxArgs {
     uint32_t* truncated;                 // ctx counter: maxima dropped by a cap (MX_MAXM_C per class, MX_MAXM per object); ismhip_sync reports it
     const float* vbq; float* mbq;        // Voting.AverageRotation: bbox quaternions of the votes (w,x,y,z) in, of the maxima out (both or neither)
     int som_type; const float* obj_centroid; const float* obj_radius;   // single-object max types (voting_mean_shift.cpp:124-157)
+    float* mtf; const float* rec_tf;     // RANSAC entries: 4x4 of the maxima out, (R, t) records per (object, class, maximum) in (both or neither)
 };
+// what the RANSAC variants need on top: the votes' keypoint pairs by global slot, thresholds, the draws, transform records, counters
+struct RansacKArgs {
+    const float* kp; const float* kpt; const float* class_thr; float thr; int max_iter; unsigned long long seed;
+    float* rec_tf; unsigned long long* counters;
+};
+__device__ __forceinline__ void rs_count(unsigned long long* counters, const RansacResult& rr) {
+    atomicAdd(&counters[0], 1ull); atomicAdd(&counters[1], (unsigned long long)rr.kept);
+    atomicAdd(&counters[2], (unsigned long long)rr.iterations); atomicAdd(&counters[3], (unsigned long long)rr.evaluated);
+}
 #define MX_LDS_SLOTS 2048  // vote slots per object that fit the LDS-resident kernels
 #define MX_WORK_STRIDE 72  // bytes of workspace per vote slot (65 used by k_find_maxima, 37 by k_hough3d)
 __device__ __forceinline__ int pow2_cap(uint32_t n) { int c = 64; while ((uint32_t)c < n) c <<= 1; return c; }
@@ -137,8 +150,11 @@ __device__ __forceinline__ int block_sum_i(int v, int* s_red) {
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
-template <bool GM>      // GM: the vote arrays live in the global workspace (objects with more than MX_LDS_SLOTS slots)
-__global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) {
+// GM: the vote arrays live in the global workspace (objects with more than MX_LDS_SLOTS slots); RS: with the RANSAC vote filter
+template <bool GM, bool RS>
+__device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacKArgs* rk) {
+    RansacLds* Lp = nullptr;
+    if constexpr (RS) { __shared__ RansacLds s_rs; Lp = &s_rs; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // power of two >= max votes of one object (LDS) / >= the votes of this (object, class) (workspace)
     const int cap = GM ? pow2_cap(a.class_count[(size_t)blockIdx.x * a.n_classes + blockIdx.y]) : a.cap;
@@ -362,13 +378,43 @@ __global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) {
                 if (in) {
                     const float w = ms_kernel(a.kernel, d2 / hh) * vw[i];
                     vw[i] = w;
-                    cnt++; sw += w;
+                    cnt++;
+                    if constexpr (!RS) {
+                    sw += w;
                     if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
                     if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
+                    }
                 }
             }
             cnt = block_sum_i(cnt, s_redi);
             if (cnt < a.min_votes || cnt == 0) continue;      // uniform across the block
+            if constexpr (RS) {
+                // filterVotesWithRansac (voting.cpp:356-433) on the members in slot order; every member keeps its reweighted weight
+                // (voting_mean_shift.cpp:161-176 ran before), member[] becomes the inlier mask and the sums below see inliers only
+                int* clist = (int*)keys;                                 // keys / ctr are free once the final positions sit in ctr2
+                unsigned char* inl = (unsigned char*)(clist + cap);
+                const int nm = rs_compact(n, member, clist, *Lp);
+                const float* kp = rk->kp; const float* kpt = rk->kpt;
+                auto fetch = [&](int j, float* sp, float* tp) {
+                    const size_t g = (size_t)vslot[clist[j]] * 3;
+                    sp[0] = kpt[g]; sp[1] = kpt[g + 1]; sp[2] = kpt[g + 2]; tp[0] = kp[g]; tp[1] = kp[g + 1]; tp[2] = kp[g + 2];
+                };
+                const RansacResult rr = ransac_cluster(nm, fetch, rk->class_thr ? rk->class_thr[c] : rk->thr, rk->max_iter, rk->seed, -1, inl, *Lp);
+                if (tid == 0) rs_count(rk->counters, rr);
+                if (!rr.kept) continue;                                  // uniform across the block
+                for (int j = tid; j < nm; j += 256) member[clist[j]] = inl[j];
+                __syncthreads();
+                cnt = 0;
+                for (int i = tid; i < n; i += 256) {
+                    if (!member[i]) continue;
+                    const float w = vw[i];
+                    cnt++; sw += w;
+                    if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
+                    if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
+                }
+                cnt = block_sum_i(cnt, s_redi);
+                if (cnt < a.min_votes || cnt == 0) continue;  // MinVotesThreshold again, on the filtered list (voting.cpp:131-136)
+            }
             sw = block_sum_f(sw, s_redf);
             b0 = block_sum_f(b0, s_redf); b1 = block_sum_f(b1, s_redf); b2 = block_sum_f(b2, s_redf);
             if (a.vbq) {
@@ -426,6 +472,7 @@ __global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) {
                     r[6] = b0 / sw; r[7] = b1 / sw; r[8] = b2 / sw; r[9] = __int_as_float(cnt);
                     r[10] = 1.f; r[11] = 0.f; r[12] = 0.f; r[13] = 0.f;
                     if (a.vbq) quat_from_scatter(qs, r + 10);          // voting.cpp:210-215
+                    if constexpr (RS) if (rk->rec_tf) { float* tf = rk->rec_tf + (((size_t)o * C + c) * MX_MAXM_C + m) * 12; for (int e = 0; e < 12; ++e) tf[e] = (float)Lp->M[e]; }
                     s_nmax = m + 1;
                 } else atomicAdd(a.truncated, 1u);
             }
@@ -435,6 +482,10 @@ __global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) {
     }
     if (tid == 0) a.rec_count[(size_t)o * C + c] = s_nmax;
 }
+template <bool GM>
+__global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) { find_maxima_body<GM, false>(a, nullptr); }
+template <bool GM>
+__global__ __launch_bounds__(256) void k_find_maxima_ransac(MaxArgs a, RansacKArgs rk) { find_maxima_body<GM, true>(a, &rk); }
 
 // Voting::findMaxima tail (voting.cpp:272, 298-323, 441-462): gather the maxima of all classes (class order, then the order
 // in which iFindMaxima produced them), stable sort by weight, normalise, MinThreshold, BestK, class scores.
@@ -583,6 +634,12 @@ __global__ __launch_bounds__(64) void k_finalize_maxima(MaxArgs a) {
         a.miw[t] = ok ? s_iw[m] : 0.f; a.mnv[t] = ok ? __float_as_int(r[9]) : 0;
         if (a.mbs) { a.mbs[t * 3] = ok ? r[6] : 0.f; a.mbs[t * 3 + 1] = ok ? r[7] : 0.f; a.mbs[t * 3 + 2] = ok ? r[8] : 0.f; }
         if (a.mbq) { a.mbq[t * 4] = ok ? r[10] : 1.f; a.mbq[t * 4 + 1] = ok ? r[11] : 0.f; a.mbq[t * 4 + 2] = ok ? r[12] : 0.f; a.mbq[t * 4 + 3] = ok ? r[13] : 0.f; }
+        if (a.mtf) {                                                 // RANSAC entries: the 4x4 of the maximum's best hypothesis
+            const float* tf = a.rec_tf + ((size_t)o * C * MX_MAXM_C + (ok ? s_src[m] : 0)) * 12;
+            float* mo = a.mtf + t * 16;
+            for (int rr = 0; rr < 3; ++rr) { for (int cc = 0; cc < 3; ++cc) mo[rr * 4 + cc] = ok ? tf[rr * 3 + cc] : (rr == cc ? 1.f : 0.f); mo[rr * 4 + 3] = ok ? tf[9 + rr] : 0.f; }
+            mo[12] = 0.f; mo[13] = 0.f; mo[14] = 0.f; mo[15] = 1.f;
+        }
     }
 }
 
@@ -624,8 +681,10 @@ __device__ __forceinline__ HgBin hg_bin(const HoughArgs& a, double bin, const in
     return b;
 }
 
-template <bool GM>
-__global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) {
+template <bool GM, bool RS>
+__device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKArgs* rk) {
+    RansacLds* Lp = nullptr;
+    if constexpr (RS) { __shared__ RansacLds s_rs; Lp = &s_rs; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int cap = GM ? pow2_cap(a.class_count[(size_t)blockIdx.x * a.n_classes + blockIdx.y]) : a.cap;
     unsigned char* arrays = smem;
@@ -787,14 +846,44 @@ __global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) {
             if (in) {
                 const float w = vw[i];
                 vcnt++; sw += w; px += vx[i] * w; py += vy[i] * w; pz += vz[i] * w;
+                if constexpr (!RS) {
                 if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
                 if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
+                }
             }
         }
         vcnt = block_sum_i(vcnt, s_redi);
         if (vcnt < a.min_votes || vcnt == 0) continue;        // uniform across the block
         sw = block_sum_f(sw, s_redf);
         px = block_sum_f(px, s_redf); py = block_sum_f(py, s_redf); pz = block_sum_f(pz, s_redf);
+        float sw_pos = sw;                                    // the maximum's position: the weighted centre of ALL voters (voting_hough_3d.cpp:70-93)
+        if constexpr (RS) {
+            // filterVotesWithRansac (voting.cpp:356-433) on the voters in slot order: the position stays, every other sum sees inliers only
+            int* clist = (int*)hval;                                     // the instance tally's arrays are free until the tally below
+            unsigned char* inl = (unsigned char*)(clist + cap);
+            const int nv = rs_compact(n, member, clist, *Lp);
+            const float* kp = rk->kp; const float* kpt = rk->kpt;
+            auto fetch = [&](int j, float* sp, float* tp) {
+                const size_t g = (size_t)vslot[clist[j]] * 3;
+                sp[0] = kpt[g]; sp[1] = kpt[g + 1]; sp[2] = kpt[g + 2]; tp[0] = kp[g]; tp[1] = kp[g + 1]; tp[2] = kp[g + 2];
+            };
+            const RansacResult rr = ransac_cluster(nv, fetch, rk->class_thr ? rk->class_thr[c] : rk->thr, rk->max_iter, rk->seed, -1, inl, *Lp);
+            if (tid == 0) rs_count(rk->counters, rr);
+            if (!rr.kept) continue;                                      // uniform across the block
+            for (int j = tid; j < nv; j += 256) member[clist[j]] = inl[j];
+            __syncthreads();
+            vcnt = 0; sw = 0.f;
+            for (int i = tid; i < n; i += 256) {
+                if (!member[i]) continue;
+                const float w = vw[i];
+                vcnt++; sw += w;
+                if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
+                if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
+            }
+            vcnt = block_sum_i(vcnt, s_redi);
+            if (vcnt < a.min_votes || vcnt == 0) continue;    // MinVotesThreshold again, on the filtered list (voting.cpp:131-136)
+            sw = block_sum_f(sw, s_redf);
+        }
         b0 = block_sum_f(b0, s_redf); b1 = block_sum_f(b1, s_redf); b2 = block_sum_f(b2, s_redf);
         if (a.vbq) {
 #pragma unroll
@@ -840,11 +929,12 @@ __global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) {
             const int m = s_nmax;
             if (m < MX_MAXM_C) {
                 float* r = rec + (size_t)m * MX_REC;
-                r[0] = px / sw; r[1] = py / sw; r[2] = pz / sw; r[3] = sw;
+                r[0] = px / sw_pos; r[1] = py / sw_pos; r[2] = pz / sw_pos; r[3] = sw;
                 r[4] = __int_as_float(bestS > 0.f ? bestI : -1); r[5] = bestS > 0.f ? bestS : 0.f;
                 r[6] = b0 / sw; r[7] = b1 / sw; r[8] = b2 / sw; r[9] = __int_as_float(vcnt);
                 r[10] = 1.f; r[11] = 0.f; r[12] = 0.f; r[13] = 0.f;
                 if (a.vbq) quat_from_scatter(qs, r + 10);
+                if constexpr (RS) if (rk->rec_tf) { float* tf = rk->rec_tf + (((size_t)o * C + c) * MX_MAXM_C + m) * 12; for (int e = 0; e < 12; ++e) tf[e] = (float)Lp->M[e]; }
                 s_nmax = m + 1;
             } else atomicAdd(a.truncated, 1u);
         }
@@ -852,6 +942,10 @@ __global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) {
     }
     if (tid == 0) a.rec_count[(size_t)o * C + c] = s_nmax;
 }
+template <bool GM>
+__global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) { hough3d_body<GM, false>(a, nullptr); }
+template <bool GM>
+__global__ __launch_bounds__(256) void k_hough3d_ransac(HoughArgs a, RansacKArgs rk) { hough3d_body<GM, true>(a, &rk); }
 
 }  // namespace
 
@@ -876,13 +970,34 @@ static int big_object_workspace(ismhip_ctx* ctx, int n_obj, int n_classes, const
     return ISMHIP_OK;
 }
 
-extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+unsigned long long* ism_ransac_counters(ismhip_ctx* ctx);
+
+// the filter's side of a RANSAC launch: per-class thresholds and the transform records in one scratch slot
+static int ransac_kernel_args(ismhip_ctx* ctx, const char* what, const ismhip_ransac_params* R, int n_classes, size_t n_oc, bool want_tf, RansacKArgs* rk) {
+    if (!R || !R->vote_keypoint || !R->vote_keypoint_training || R->max_iterations < 0)
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(what) + ": ransac parameters (vote_keypoint, vote_keypoint_training, max_iterations)");
+    const size_t thr_bytes = ((size_t)n_classes * 4 + 255) / 256 * 256;
+    unsigned char* scr = (unsigned char*)ism_scratch(ctx, SCR_RANSAC, thr_bytes + (want_tf ? n_oc * MX_MAXM_C * 12 * sizeof(float) : 0));
+    if (!scr) return ISMHIP_ERR_NOMEM;
+    rk->kp = R->vote_keypoint; rk->kpt = R->vote_keypoint_training; rk->thr = R->inlier_threshold; rk->class_thr = nullptr;
+    if (R->class_inlier_threshold_h) {
+        ISM_HIP(ctx, hipMemcpyAsync(scr, R->class_inlier_threshold_h, (size_t)n_classes * 4, hipMemcpyHostToDevice, ctx->stream));
+        rk->class_thr = (const float*)scr;
+    }
+    rk->max_iter = std::min(R->max_iterations, 1 << 30); rk->seed = R->seed;
+    rk->rec_tf = want_tf ? (float*)(scr + thr_bytes) : nullptr;
+    rk->counters = ism_ransac_counters(ctx);
+    return rk->counters ? ISMHIP_OK : ISMHIP_ERR_NOMEM;
+}
+
+static int find_maxima_impl(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                                   const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
                                   const int32_t* vote_instance, const float* vote_bbox_size,
                                   const ismhip_maxima_params* P,
                                   int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
                                   int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
-                                  float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
+                                  float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
+                                  bool ransac, const ismhip_ransac_params* R, float* max_transform_out) {
     if (!ctx || n_obj <= 0 || !slot_offsets_h || !vote_pos || !vote_weight || !vote_class || !vote_instance || !P ||
         !n_maxima_out || !max_pos_out || !max_weight_out || !max_class_out || !max_instance_out || !max_instance_weight_out ||
         !max_n_votes_out || !class_score_out || P->n_classes <= 0 || P->max_maxima <= 0 || !(P->bandwidth > 0.f || P->class_bandwidth_h))
@@ -921,9 +1036,10 @@ extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* sl
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: single-object max types need object_centroid (and object_radius for MODEL_RADIUS)");
     a.n_max = n_maxima_out; a.mpos = max_pos_out; a.mw = max_weight_out; a.mcls = max_class_out; a.minst = max_instance_out;
     a.miw = max_instance_weight_out; a.mbs = max_bbox_size_out; a.mnv = max_n_votes_out; a.class_score = class_score_out;
-    if (!ctx->attr_done.count((const void*)k_find_maxima<false>)) {      // the attribute is per device: remembered per ctx, not per process
-        ISM_HIP(ctx, hipFuncSetAttribute((const void*)k_find_maxima<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        ctx->attr_done.insert((const void*)k_find_maxima<false>);
+    const void* lds_kernel = ransac ? (const void*)k_find_maxima_ransac<false> : (const void*)k_find_maxima<false>;
+    if (!ctx->attr_done.count(lds_kernel)) {      // the attribute is per device: remembered per ctx, not per process
+        ISM_HIP(ctx, hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        ctx->attr_done.insert(lds_kernel);
     }
     a.truncated = ctx->truncated_d;
     a.work = nullptr; a.work_off = nullptr; a.class_count = nullptr;
@@ -932,8 +1048,19 @@ extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* sl
     a.rec = (float*)ism_scratch(ctx, SCR_MAX_REC, n_oc * MX_MAXM_C * MX_REC * sizeof(float) + n_oc * sizeof(int32_t));
     if (!a.rec) return ISMHIP_ERR_NOMEM;
     a.rec_count = (int32_t*)(a.rec + n_oc * MX_MAXM_C * MX_REC);
+    a.mtf = nullptr; a.rec_tf = nullptr;
+    RansacKArgs rk{};
+    if (ransac) {
+        int rc = ransac_kernel_args(ctx, "find_maxima_ransac", R, P->n_classes, n_oc, max_transform_out != nullptr, &rk);
+        if (rc != ISMHIP_OK) return rc;
+        a.mtf = max_transform_out; a.rec_tf = rk.rec_tf;
+    }
     TimerScope ts(ctx, "maxima");
-    if (big) hipLaunchKernelGGL(k_find_maxima<true>, dim3(n_obj, P->n_classes), dim3(256), 0, ctx->stream, a);
+    if (ransac) {
+        if (big) hipLaunchKernelGGL(k_find_maxima_ransac<true>, dim3(n_obj, P->n_classes), dim3(256), 0, ctx->stream, a, rk);
+        else hipLaunchKernelGGL(k_find_maxima_ransac<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, a, rk);
+    }
+    else if (big) hipLaunchKernelGGL(k_find_maxima<true>, dim3(n_obj, P->n_classes), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k_find_maxima<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_find_maxima");
     hipLaunchKernelGGL(k_finalize_maxima, dim3(n_obj), dim3(64), 0, ctx->stream, a);
@@ -941,14 +1068,39 @@ extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* sl
     return ISMHIP_OK;
 }
 
+extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                                  const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                                  const int32_t* vote_instance, const float* vote_bbox_size,
+                                  const ismhip_maxima_params* P,
+                                  int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                                  int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                                  float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
+    return find_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
+                            max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                            false, nullptr, nullptr);
+}
+extern "C" int ismhip_find_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                                         const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                                         const int32_t* vote_instance, const float* vote_bbox_size,
+                                         const ismhip_maxima_params* P,
+                                         int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                                         int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                                         float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
+                                         const ismhip_ransac_params* R, float* max_transform_out) {
+    if (!R) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima_ransac: ransac parameters missing");
+    return find_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
+                            max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                            true, R, max_transform_out);
+}
 
-extern "C" int ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+static int hough3d_maxima_impl(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                                      const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
                                      const int32_t* vote_instance, const float* vote_bbox_size,
                                      const ismhip_hough_params* P,
                                      int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
                                      int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
-                                     float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
+                                     float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
+                                     bool ransac, const ismhip_ransac_params* R, float* max_transform_out) {
     if (!ctx || n_obj <= 0 || !slot_offsets_h || !vote_pos || !vote_weight || !vote_class || !vote_instance || !P ||
         !n_maxima_out || !max_pos_out || !max_weight_out || !max_class_out || !max_instance_out || !max_instance_weight_out ||
         !max_n_votes_out || !class_score_out || P->n_classes <= 0 || P->max_maxima <= 0 || !(P->bin_size > 0.f || P->class_bin_h))
@@ -998,19 +1150,55 @@ extern "C" int ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t*
     a.n_max = n_maxima_out; a.mpos = max_pos_out; a.mw = max_weight_out; a.mcls = max_class_out; a.minst = max_instance_out;
     a.miw = max_instance_weight_out; a.mbs = max_bbox_size_out; a.mnv = max_n_votes_out; a.class_score = class_score_out;
     a.rec = h.rec; a.rec_count = h.rec_count;
-    const void* hk = big ? (const void*)k_hough3d<true> : (const void*)k_hough3d<false>;
+    const void* hk = ransac ? (big ? (const void*)k_hough3d_ransac<true> : (const void*)k_hough3d_ransac<false>)
+                            : (big ? (const void*)k_hough3d<true> : (const void*)k_hough3d<false>);
     if (!ctx->attr_done.count(hk)) {
         ISM_HIP(ctx, hipFuncSetAttribute(hk, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
         ctx->attr_done.insert(hk);
     }
     h.work = nullptr; h.work_off = nullptr; h.class_count = nullptr; h.truncated = ctx->truncated_d; a.truncated = ctx->truncated_d;
     if (big) { int rc = big_object_workspace(ctx, n_obj, P->n_classes, slot_offsets_h, so, vote_class, &h.work, &h.work_off, &h.class_count); if (rc != ISMHIP_OK) return rc; }
+    RansacKArgs rk{};
+    if (ransac) {
+        int rc = ransac_kernel_args(ctx, "hough3d_maxima_ransac", R, P->n_classes, n_oc, max_transform_out != nullptr, &rk);
+        if (rc != ISMHIP_OK) return rc;
+        a.mtf = max_transform_out; a.rec_tf = rk.rec_tf;
+    }
     TimerScope ts(ctx, "hough3d");
     ISM_HIP(ctx, hipMemsetAsync(h.overflow, 0, 4, ctx->stream));
-    if (big) hipLaunchKernelGGL(k_hough3d<true>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h);
+    if (ransac) {
+        if (big) hipLaunchKernelGGL(k_hough3d_ransac<true>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h, rk);
+        else hipLaunchKernelGGL(k_hough3d_ransac<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h, rk);
+    }
+    else if (big) hipLaunchKernelGGL(k_hough3d<true>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h);
     else hipLaunchKernelGGL(k_hough3d<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h);
     ISM_CHECK_LAUNCH(ctx, "k_hough3d");
     hipLaunchKernelGGL(k_finalize_maxima, dim3(n_obj), dim3(64), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_finalize_maxima");
     return ISMHIP_OK;
+}
+
+extern "C" int ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                                     const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                                     const int32_t* vote_instance, const float* vote_bbox_size,
+                                     const ismhip_hough_params* P,
+                                     int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                                     int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                                     float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
+    return hough3d_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
+                               max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                               false, nullptr, nullptr);
+}
+extern "C" int ismhip_hough3d_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
+                                            const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
+                                            const int32_t* vote_instance, const float* vote_bbox_size,
+                                            const ismhip_hough_params* P,
+                                            int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
+                                            int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
+                                            float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
+                                            const ismhip_ransac_params* R, float* max_transform_out) {
+    if (!R) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima_ransac: ransac parameters missing");
+    return hough3d_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
+                               max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                               true, R, max_transform_out);
 }

@@ -125,6 +125,8 @@ int ism3d_last_votes(void* m, uint32_t* slot_off, float* pos, float* weight, int
         cp(slot_off, d.slot_off); cp(pos, d.pos); cp(weight, d.weight); cp(cls, d.cls); cp(inst, d.inst);
         return (int)d.weight.size();)
 }
+// diagnostics (tests): a timer (ms) or counter of the model's device context by its ismhip_timer_get name, e.g. "ransac_clusters"
+int ism3d_device_timer(void* m, const char* name, double* out) { GUARD(*out = ((ImplicitShapeModel*)m)->deviceTimer(name); return 0;) }
 // label maps and the per-class size hints (Voting::forwardBoxesAndRadii) that travel with the model
 int ism3d_set_labels(void* m, int n_classes, const char* const* class_labels, int n_inst, const char* const* inst_labels, const unsigned* inst_to_class) {
     GUARD(((ImplicitShapeModel*)m)->setLabels(std::vector<std::string>(class_labels, class_labels + n_classes), std::vector<std::string>(inst_labels, inst_labels + n_inst),

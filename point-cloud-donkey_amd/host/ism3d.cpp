@@ -67,6 +67,7 @@ public:
     bool has_color = false;
     // vote space of the current batch (Voting::m_votes)
     DevBuf v_pos, v_w, v_cls, v_inst, v_cw, v_bs, v_bq, idx, dist;
+    DevBuf v_kp, v_kpt;                   // Vote::keypoint / keypoint_training of every slot (only with Voting.RansacVoteFiltering)
     DevBuf act_off;                       // [n+1] activation ranges of the list path (ActivationStrategyThreshold)
     DevBuf obj_cen, obj_rad;              // per-object cloud centroid / farthest point (single-object max types)
     std::vector<uint32_t> slot_off;
@@ -412,6 +413,8 @@ void Codebook::upload(DeviceSession& s) const {
                                    d.vote_bbox_quat.empty() ? nullptr : d.vote_bbox_quat.data(), d.vote_bbox_size.empty() ? nullptr : d.vote_bbox_size.data(),
                                    (int)d.class_sigma.size(), d.class_sigma.data(), &m_dev), "ismhip_codebook_create");
     if ((int)d.word_class.size() == d.numWords()) s.check(ismhip_codebook_set_word_class(s.ctx, m_dev, d.word_class.data()), "ismhip_codebook_set_word_class");
+    if (d.word_keypoint.size() == (size_t)d.numWords() * 3)       // Codeword::getFeaturePosition: Vote::keypoint_training (voting.cpp:71)
+        s.check(ismhip_codebook_set_word_keypoint(s.ctx, m_dev, d.word_keypoint.data()), "ismhip_codebook_set_word_keypoint");
     m_dirty = false;
 }
 
@@ -584,9 +587,12 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
 }
 
 void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, Voting& voting) const {   // codebook.cpp:403-555
-    (void)voting;
     s.n_slots = 0; s.slot_off.assign(s.n_obj + 1, 0);
     if (isEmpty()) return;
+    // Voting::vote keeps the keypoint pair of every vote (voting.cpp:58-77); only the RANSAC vote filter reads it
+    const bool want_kp = voting.m_vote_filtering_with_ransac;
+    if (want_kp && m_data.word_keypoint.size() != (size_t)m_data.numWords() * 3)
+        throw RuntimeException("RansacVoteFiltering needs the codewords' training keypoints, which this codebook does not hold");
     upload(s);
     m_activationStrategy->setIsDetection();
     const ActivationStrategy* knn = m_activationStrategy.get();
@@ -615,6 +621,11 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
         s.check(ismhip_cast_votes_csr(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), s.act_off.as<uint32_t>(),
                                       na, s.idx.as<int32_t>(), s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(),
                                       s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(), s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes_csr");
+        if (want_kp) {
+            s.v_kp.reserve(ns * 12); s.v_kpt.reserve(ns * 12);
+            s.check(ismhip_vote_keypoints_csr(s.ctx, m_dev, (int)n, f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), s.act_off.as<uint32_t>(), na,
+                                              s.idx.as<int32_t>(), s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints_csr");
+        }
         std::vector<uint32_t> act_off;
         s.d2h(act_off, s.act_off, (size_t)n + 1);
         s.n_slots = ns;
@@ -636,6 +647,11 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
     s.check(ismhip_cast_votes(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),
                               s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(),
                               s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes");
+    if (want_kp) {
+        s.v_kp.reserve(ns * 12); s.v_kpt.reserve(ns * 12);
+        s.check(ismhip_vote_keypoints(s.ctx, m_dev, (int)n, f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),
+                                      s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints");
+    }
     s.n_slots = ns;
     for (int o = 0; o <= s.n_obj; ++o) s.slot_off[o] = f.off[o] * (uint32_t)(k * maxv);
     s.n_classes = (int)m_data.class_sigma.size();
@@ -823,7 +839,7 @@ bool Voting::load(BoostBinaryIArchive& ia) {
 // ---------------------------------------------------------------------------------------------------------------
 // Voting (voting/voting.cpp, voting_mean_shift.cpp)
 // ---------------------------------------------------------------------------------------------------------------
-Voting::Voting() {                                // voting.cpp:28-50 (hot-path subset; the global-feature / RANSAC keys are accepted and must stay off)
+Voting::Voting() {                                // voting.cpp:28-50 (hot-path subset; the global-feature keys are accepted and must stay off)
     addParameter(m_minThreshold, "MinThreshold", 0.0f);
     addParameter(m_minVotesThreshold, "MinVotesThreshold", 1);
     addParameter(m_bestK, "BestK", -1);
@@ -834,12 +850,33 @@ Voting::Voting() {                                // voting.cpp:28-50 (hot-path 
     addParameter(m_max_type_param, "SingleObjectMaxType", std::string("Default"));
     addParameter(m_single_object_mode, "SingleObjectMode", false);
     addParameter(m_use_global_features, "UseGlobalFeatures", false);
-    addParameter(m_vote_filtering_with_ransac, "RansacVoteFiltering", false);
+    addParameter(m_vote_filtering_with_ransac, "RansacVoteFiltering", false);      // voting.cpp:47-50
+    addParameter(m_refine_model, "RansacRefineModel", false);
+    addParameter(m_inlier_threshold, "RansacInlierThreshold", 0.1f);
+    addParameter(m_inlier_threshold_type, "RansacInlierThresholdType", std::string("Fixed"));
+}
+// Voting::findMaxima (voting.cpp:112-122): the threshold of every class; "ObjectRadius" / "BoundingBoxMedian" scale it by the class's
+// entry of m_dimensions_map, anything else is "Fixed". Resolved per class like BinOrBandwidthType (searchDistPerClass).
+std::vector<float> Voting::ransacThresholdPerClass(int n_classes) const {
+    const bool first = m_inlier_threshold_type == "ObjectRadius", second = m_inlier_threshold_type == "BoundingBoxMedian";
+    if (!first && !second) return {};
+    std::vector<float> out((size_t)n_classes, m_inlier_threshold);
+    for (int c = 0; c < n_classes; ++c) {
+        auto it = m_dimensions_map.find((unsigned)c);
+        if (it == m_dimensions_map.end()) continue;            // a class that was never trained casts no votes either
+        out[c] = m_inlier_threshold * (first ? it->second.first : it->second.second);
+    }
+    return out;
+}
+void Voting::fillRansacParams(DeviceSession& s, const std::vector<float>& class_thr, ismhip_ransac_params& R) const {
+    R.vote_keypoint = s.v_kp.as<float>(); R.vote_keypoint_training = s.v_kpt.as<float>();
+    R.inlier_threshold = m_inlier_threshold; R.class_inlier_threshold_h = class_thr.empty() ? nullptr : class_thr.data();
+    R.max_iterations = 10000;                                  // corr_rejector.setMaximumIterations(10000) (voting.cpp:398)
+    R.seed = 12345ull;                                         // PCL seeds every cluster's generator with 12345; the draws are this library's
 }
 void Voting::clear() {}
 std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s) {
     if (m_use_global_features) throw RuntimeException("UseGlobalFeatures is out of scope of the MI355X path (SURVEY §2 row 10)");
-    if (m_vote_filtering_with_ransac) throw RuntimeException("RansacVoteFiltering is not built on the MI355X path");
     if (m_max_filter_type != "None" && m_max_filter_type != "Simple" && m_max_filter_type != "Merge")
         LOG_ERROR("Invalid maxima filter type specified: " << m_max_filter_type << "! No filtering is performed!");            // maxima_handler.cpp:292-295
     if (m_max_type_param != "None" && m_max_type_param != "Default" && m_max_type_param != "BandwidthVotes" && m_max_type_param != "VotingSpaceVotes" &&
@@ -891,6 +928,14 @@ void VotingMeanShift::iFindMaxima(DeviceSession& s, std::vector<std::vector<Voti
     MaximaBuffers B; B.M = M; B.reserve(s.n_obj, C);
     if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }              // voting.cpp:210-215
     P.single_object_max_type = singleObjectMaxType(); P.object_centroid = s.obj_cen.as<float>(); P.object_radius = s.obj_rad.as<float>();
+    if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127: the filter runs inside the maxima search
+        const std::vector<float> class_thr = ransacThresholdPerClass(C);
+        ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
+        s.check(ismhip_find_maxima_ransac(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
+                                          s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
+                                          B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), &R, nullptr), "ismhip_find_maxima_ransac");
+        s.sync();                                               // class_thr is read by the launch
+    } else
     s.check(ismhip_find_maxima(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
                                s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
                                B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>()), "ismhip_find_maxima");
@@ -947,6 +992,14 @@ void VotingHough3D::iFindMaxima(DeviceSession& s, std::vector<std::vector<Voting
     P.max_filter = maxFilter();
     MaximaBuffers B; B.M = M; P.max_maxima = B.M; B.reserve(s.n_obj, C);
     if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }
+    if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127
+        const std::vector<float> class_thr = ransacThresholdPerClass(C);
+        ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
+        s.check(ismhip_hough3d_maxima_ransac(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
+                                             s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
+                                             B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), &R, nullptr), "ismhip_hough3d_maxima_ransac");
+        s.sync();                                               // class_thr is read by the launch
+    } else
     s.check(ismhip_hough3d_maxima(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
                                   s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
                                   B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>()), "ismhip_hough3d_maxima");
@@ -1124,6 +1177,8 @@ bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
     m_keypoints_detector.reset(Factory<Keypoints>::create(*kp));
     m_feature_descriptor.reset(Factory<Features>::create(*ft));
     m_voting.reset(Factory<Voting>::create(*vo));
+    if (m_voting && m_voting->refineModelRequested())
+        throw RuntimeException("Voting.RansacRefineModel is not built (PCL's sac.refineModel is not restated); RansacVoteFiltering runs without it");
     m_clustering.reset(Factory<Clustering>::create(*cl)); m_feature_ranking_cfg = *fw;
     if (const Json* gf = c.find("GlobalFeatures")) m_global_features_cfg = *gf;
     const Json* rt = fw->find("Type");
@@ -1526,6 +1581,13 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     m_processing_times["normals"] += 0; m_processing_times["flann"] += 0;
     for (size_t i = 0; i < res.size(); ++i) out[map[i]] = res[i];
     return out;
+}
+
+double ImplicitShapeModel::deviceTimer(const std::string& name) const {
+    if (!m_session) return 0.0;
+    double v = 0.0; int64_t launches = 0;
+    m_session->check(ismhip_timer_get(m_session->ctx, name.c_str(), &v, &launches), "ismhip_timer_get");
+    return v;
 }
 
 ImplicitShapeModel::FeatureDump ImplicitShapeModel::lastFeatures(int which) const {

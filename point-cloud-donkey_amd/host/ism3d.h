@@ -397,6 +397,7 @@ public:
     std::vector<std::vector<VotingMaximum>> findMaxima(DeviceSession& s);
     void clear();
     bool isSingleObjectMode() const { return m_single_object_mode; }
+    bool refineModelRequested() const { return m_refine_model; }   // RansacRefineModel: refused when the config is read
     // Voting::forwardBoxesAndRadii (voting.cpp:496-551): per class (mean object radius, mean median box edge) and their variances
     void forwardBoxesAndRadii(const std::map<unsigned, std::vector<std::array<float, 3>>>& box_sizes, const std::map<unsigned, std::vector<float>>& object_radii);
     const std::map<unsigned, std::pair<float, float>>& getDimensionsMap() const { return m_dimensions_map; }
@@ -415,9 +416,13 @@ protected:
     static bool collectMaxima(DeviceSession& s, MaximaBuffers& b, std::vector<std::vector<VotingMaximum>>& out, bool with_quat);
     int singleObjectMaxType() const;                             // ISMHIP_SOM_* from SingleObjectMode / SingleObjectMaxType
     int maxFilter() const;                                       // ISMHIP_MAXFILTER_* from MaxFilterType
+    // RANSAC vote filter (voting.cpp:110-127): per-class inlier thresholds (empty = the configured one for all) and the device call's parameters
+    std::vector<float> ransacThresholdPerClass(int n_classes) const;
+    void fillRansacParams(DeviceSession& s, const std::vector<float>& class_thr, ismhip_ransac_params& R) const;
     float m_minThreshold; int m_minVotesThreshold; int m_bestK; bool m_averageRotation;
     std::string m_radiusType; float m_radiusFactor; std::string m_max_filter_type, m_max_type_param;
     bool m_single_object_mode; bool m_use_global_features; bool m_vote_filtering_with_ransac;
+    bool m_refine_model; float m_inlier_threshold; std::string m_inlier_threshold_type;      // RansacRefineModel, RansacInlierThreshold(Type)
 };
 class VotingHough3D : public Voting {             // voting/voting_hough_3d.{h,cpp}
 public:
@@ -481,6 +486,8 @@ public:
     struct VoteDump { std::vector<uint32_t> slot_off; std::vector<float> pos, weight; std::vector<int32_t> cls, inst; };
     FeatureDump lastFeatures(int which) const;
     VoteDump lastVotes() const;
+    // diagnostics (tests): a timer or counter of the device library's context (ismhip_timer_get); 0 before the first device call
+    double deviceTimer(const std::string& name) const;
     const Voting* getVoting() const { return m_voting.get(); }
     void setSignalsState(bool) {}
     void setLogging(bool l) { m_logging = l; }

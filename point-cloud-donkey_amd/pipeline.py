@@ -39,6 +39,11 @@ class IsmConfig:
     best_k: int = -1
     max_maxima: int = 16
     average_rotation: bool = False   # Voting.AverageRotation (voting.cpp:210-215): out["bbox_quat"]
+    ransac_vote_filtering: bool = False        # Voting.RansacVoteFiltering (voting.cpp:110-127, 356-433): out["transform"]
+    ransac_refine_model: bool = False          # Voting.RansacRefineModel: not built, must stay False
+    ransac_inlier_threshold: float = 0.1       # Voting.RansacInlierThreshold
+    ransac_inlier_threshold_type: str = "Fixed"   # Voting.RansacInlierThresholdType: "Fixed" | "ObjectRadius" | "BoundingBoxMedian" (x class_dimensions)
+    class_dimensions: dict = None    # {class id: (mean object radius, mean median box edge)}: Voting::m_dimensions_map, for the per-class threshold types
     max_filter: str = "None"         # Voting.MaxFilterType: "None" | "Simple" | "Merge" (ignored in single-object mode, voting.cpp:262-268)
     single_object_mode: bool = False # Voting.SingleObjectMode
     single_object_max_type: str = "Default"   # Voting.SingleObjectMaxType: "Default" | "BandwidthVotes" | "ModelRadiusVotes" | "VotingSpaceVotes"
@@ -232,7 +237,7 @@ class Recognizer:
         self.cb_host = dict(words=words_h[keep_words], vote_offsets=vote_off.astype(np.uint32), vote_xyz=vote_xyz,
                             vote_class=cls[src], vote_instance=inst[src], class_sigma=act["class_sigma"],
                             vote_class_weight=vote_cw.astype(np.float32), vote_weight=vote_w.astype(np.float32), word_weight=np.ones(m, np.float32),
-                            word_class=cls[keep_words])
+                            word_class=cls[keep_words], word_keypoint=kp.cpu().numpy()[keep_words])   # Codeword(.., keypoint of feature i)
         self.load_codebook(self.cb_host)
         return self.cb_host
 
@@ -254,6 +259,19 @@ class Recognizer:
                                       vote_bbox_quat=cb.get("vote_bbox_quat"), vote_bbox_size=cb.get("vote_bbox_size"))
         if cb.get("word_class") is not None:
             self.codebook.set_word_class(cb["word_class"])       # Codeword::getClassId = class of the feature the word was made from
+        if cb.get("word_keypoint") is not None:
+            self.codebook.set_word_keypoint(cb["word_keypoint"]) # Codeword::getFeaturePosition: Vote::keypoint_training (RansacVoteFiltering)
+
+    def ransac_thresholds(self):
+        """Voting::findMaxima (voting.cpp:112-122): RansacInlierThreshold, times the class's mean object radius / mean median box edge for
+        the types "ObjectRadius" / "BoundingBoxMedian" -> [n_classes] or None ("Fixed" and anything else)"""
+        c = self.cfg
+        which = {"ObjectRadius": 0, "BoundingBoxMedian": 1}.get(c.ransac_inlier_threshold_type)
+        if which is None:
+            return None
+        dims = c.class_dimensions or {}
+        return np.asarray([np.float32(c.ransac_inlier_threshold) * np.float32(dims[k][which]) if k in dims else np.float32(c.ransac_inlier_threshold)
+                           for k in range(c.n_classes)], np.float32)
 
     # -- ImplicitShapeModel::detect() over a batch --------------------------------------------------------------
     def detect(self, b: DeviceBatch, keep_intermediates=False):
@@ -268,11 +286,20 @@ class Recognizer:
             idx, dist = (capi.knn_large_k if c.k > 16 else capi.knn)(ctx, cb, c.metric, q, c.k)
         votes = capi.cast_votes(ctx, cb, c.weight_flags, f["lrf"], f["kx"], f["ky"], f["kz"], idx, dist, want_bbox=c.average_rotation)
         slot_off = f["off"].astype(np.uint64) * (c.k * cb.max_votes)
+        ransac = None
+        if c.ransac_vote_filtering:
+            if c.ransac_refine_model:
+                raise capi.IsmHipError("RansacRefineModel is not built (sac.refineModel of PCL is not restated, DESIGN.md §7)")
+            if self.cb_host.get("word_keypoint") is None:
+                raise capi.IsmHipError("RansacVoteFiltering needs a codebook with training keypoints (word_keypoint)")
+            vkp, vkpt = capi.vote_keypoints(ctx, cb, f["kx"], f["ky"], f["kz"], idx)
+            ransac = dict(vote_keypoint=vkp, vote_keypoint_training=vkpt, inlier_threshold=c.ransac_inlier_threshold,
+                          class_inlier_threshold=self.ransac_thresholds())
         max_filter = capi.MAXFILTER_NONE if c.single_object_mode else {"Simple": capi.MAXFILTER_SIMPLE, "Merge": capi.MAXFILTER_MERGE}.get(c.max_filter, capi.MAXFILTER_NONE)
         if c.voting == "Hough3D":
             mx = capi.hough3d_maxima(ctx, slot_off.astype(np.uint32), votes, c.n_classes, c.hough_bin_size, c.hough_min_coord, c.hough_max_coord,
                                      c.hough_use_interpolation, c.hough_rel_threshold, c.min_votes_threshold, c.min_threshold, c.best_k, c.max_maxima,
-                                     max_filter=max_filter, average_rotation=c.average_rotation)
+                                     max_filter=max_filter, average_rotation=c.average_rotation, ransac=ransac)
         else:
             som = capi.SOM_MEANSHIFT if not c.single_object_mode else {"BandwidthVotes": capi.SOM_BANDWIDTH, "ModelRadiusVotes": capi.SOM_MODEL_RADIUS,
                                                                       "VotingSpaceVotes": capi.SOM_COMPLETE_VOTING_SPACE}.get(c.single_object_max_type, capi.SOM_MEANSHIFT)
@@ -284,9 +311,10 @@ class Recognizer:
                                   capi.KERNEL_GAUSSIAN if c.kernel == "Gaussian" else capi.KERNEL_UNIFORM,
                                   {"Average": capi.SUPPRESS_AVERAGE, "Suppress": capi.SUPPRESS_SUPPRESS}.get(c.maxima_suppression, capi.SUPPRESS_NONE),
                                   c.min_votes_threshold, c.min_threshold, c.best_k, c.max_maxima, max_filter=max_filter,
-                                  average_rotation=c.average_rotation, single_object_max_type=som, object_centroid=cen, object_radius=rad)
+                                  average_rotation=c.average_rotation, single_object_max_type=som, object_centroid=cen, object_radius=rad,
+                                  ransac=ransac)
         if keep_intermediates:
             mx.update(features=f, idx=idx, dist=dist, votes=votes, slot_off=slot_off.astype(np.uint32))
         else:
-            mx["_keep"] = (f, idx, dist, votes)   # outputs are produced asynchronously: keep inputs alive until the caller syncs
+            mx["_keep"] = (f, idx, dist, votes, ransac)   # outputs are produced asynchronously: keep inputs alive until the caller syncs
         return mx
