@@ -613,6 +613,41 @@ def _ransac_params(ransac, n_classes):
     return R, cthr
 
 
+def _maxima_outputs(n_obj, max_maxima, n_classes, dev):
+    """the output tensors of find_maxima / hough3d_maxima"""
+    torch = _torch()
+    return dict(
+        n=torch.empty((n_obj,), dtype=torch.int32, device=dev),
+        pos=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
+        weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
+        cls=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
+        inst=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
+        inst_weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
+        bbox_size=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
+        n_votes=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
+        class_score=torch.empty((n_obj, n_classes), dtype=torch.float32, device=dev),
+    )
+
+
+def _maxima_call(ctx, symbol, so, votes, P, out, bq_out, ransac):
+    """calls `symbol` (with ransac: symbol + "_ransac", which also fills out["transform"]) on the arguments both voting back ends
+    share; P is the back end's params struct, bq_out the AverageRotation output or None"""
+    n_obj, max_maxima = out["weight"].shape
+    args = (ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
+            _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
+            _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
+            _p(out["n_votes"]), _p(out["class_score"]))
+    if ransac is not None:
+        symbol += "_ransac"
+        R, _keep = _ransac_params(ransac, out["class_score"].shape[1])
+        out["transform"] = _torch().zeros((n_obj, max_maxima, 4, 4), dtype=out["weight"].dtype, device=out["weight"].device)
+        args += (C.byref(R), _p(out["transform"]))
+    ctx.check(getattr(lib(), symbol)(*args), symbol)
+    if bq_out is not None:
+        out["bbox_quat"] = bq_out
+    return out
+
+
 def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, max_iter=1000, kernel=KERNEL_GAUSSIAN,
                 suppression=SUPPRESS_AVERAGE, min_votes_threshold=1, min_threshold=0.0, best_k=-1, max_maxima=16,
                 class_bandwidth=None, max_filter=0, average_rotation=False, single_object_max_type=SOM_MEANSHIFT,
@@ -630,30 +665,7 @@ def find_maxima(ctx, slot_offsets, votes, n_classes, bandwidth, threshold=1e-3, 
                      min_votes_threshold, min_threshold, best_k, max_maxima, max_filter,
                      _p(votes["bbox_quat"]).value if average_rotation else None, _p(bq_out).value, single_object_max_type,
                      _p(object_centroid).value, _p(object_radius).value)
-    out = dict(
-        n=torch.empty((n_obj,), dtype=torch.int32, device=dev),
-        pos=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
-        weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
-        cls=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        inst=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        inst_weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
-        bbox_size=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
-        n_votes=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        class_score=torch.empty((n_obj, n_classes), dtype=torch.float32, device=dev),
-    )
-    args = (ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
-            _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
-            _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
-            _p(out["n_votes"]), _p(out["class_score"]))
-    if ransac is None:
-        ctx.check(lib().ismhip_find_maxima(*args), "ismhip_find_maxima")
-    else:
-        R, _keep = _ransac_params(ransac, n_classes)
-        out["transform"] = torch.zeros((n_obj, max_maxima, 4, 4), dtype=torch.float32, device=dev)
-        ctx.check(lib().ismhip_find_maxima_ransac(*args, C.byref(R), _p(out["transform"])), "ismhip_find_maxima_ransac")
-    if bq_out is not None:
-        out["bbox_quat"] = bq_out
-    return out
+    return _maxima_call(ctx, "ismhip_find_maxima", so, votes, P, _maxima_outputs(n_obj, max_maxima, n_classes, dev), bq_out, ransac)
 
 
 def hough3d_maxima(ctx, slot_offsets, votes, n_classes, bin_size, min_coord=(-5, -5, -5), max_coord=(5, 5, 5), use_interpolation=True,
@@ -669,30 +681,7 @@ def hough3d_maxima(ctx, slot_offsets, votes, n_classes, bin_size, min_coord=(-5,
     P = HoughParams(n_classes, (C.c_float * 3)(*min_coord), (C.c_float * 3)(*max_coord), bin_size, cb.ctypes.data if cb is not None else None,
                     1 if use_interpolation else 0, rel_threshold, min_votes_threshold, min_threshold, best_k, max_maxima, max_filter,
                     _p(votes["bbox_quat"]).value if average_rotation else None, _p(bq_out).value)
-    out = dict(
-        n=torch.empty((n_obj,), dtype=torch.int32, device=dev),
-        pos=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
-        weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
-        cls=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        inst=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        inst_weight=torch.empty((n_obj, max_maxima), dtype=torch.float32, device=dev),
-        bbox_size=torch.empty((n_obj, max_maxima, 3), dtype=torch.float32, device=dev),
-        n_votes=torch.empty((n_obj, max_maxima), dtype=torch.int32, device=dev),
-        class_score=torch.empty((n_obj, n_classes), dtype=torch.float32, device=dev),
-    )
-    args = (ctx._h, C.c_int(n_obj), _p(so), _p(votes["pos"]), _p(votes["weight"]), _p(votes["cls"]),
-            _p(votes["inst"]), _p(votes.get("bbox_size")), C.byref(P), _p(out["n"]), _p(out["pos"]),
-            _p(out["weight"]), _p(out["cls"]), _p(out["inst"]), _p(out["inst_weight"]), _p(out["bbox_size"]),
-            _p(out["n_votes"]), _p(out["class_score"]))
-    if ransac is None:
-        ctx.check(lib().ismhip_hough3d_maxima(*args), "ismhip_hough3d_maxima")
-    else:
-        R, _keep = _ransac_params(ransac, n_classes)
-        out["transform"] = torch.zeros((n_obj, max_maxima, 4, 4), dtype=torch.float32, device=dev)
-        ctx.check(lib().ismhip_hough3d_maxima_ransac(*args, C.byref(R), _p(out["transform"])), "ismhip_hough3d_maxima_ransac")
-    if bq_out is not None:
-        out["bbox_quat"] = bq_out
-    return out
+    return _maxima_call(ctx, "ismhip_hough3d_maxima", so, votes, P, _maxima_outputs(n_obj, max_maxima, n_classes, dev), bq_out, ransac)
 
 
 def train_activate(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, k=1, clean_up=True, n_classes=None, codewords=None):

@@ -178,6 +178,8 @@ enum ScratchSlot {
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);
 void* ism_scratch(ismhip_ctx* ctx, int slot, size_t bytes);   // nullptr on failure (error recorded)
+// raises a kernel's MaxDynamicSharedMemorySize to `bytes` once per ctx (attr_done): pass the largest size any launch of that kernel uses
+int  ism_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes);
 
 #define ISM_HIP(ctx, call)                                                                          \
     do {                                                                                            \

@@ -11,6 +11,13 @@ int ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+int ism_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes) {
+    if (ctx->attr_done.count(kern)) return ISMHIP_OK;      // the attribute is per device: remembered per ctx, not per process
+    ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    ctx->attr_done.insert(kern);
+    return ISMHIP_OK;
+}
+
 void* ism_scratch(ismhip_ctx* ctx, int slot, size_t bytes) {
     if (bytes == 0) bytes = 16;
     auto& s = ctx->scratch[slot];

@@ -908,7 +908,7 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
         a.cand_val = cand_val; a.cand_idx = cand_idx; a.cand_stride = n_cand; a.cand_bound = cand_bound; a.bound_stride = n_bound;
         int rc = ISMHIP_OK;
         if (ring) {
-            rc = knn_lds_cap(ctx, p.kern, p.lds_cap);
+            rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
             if (rc != ISMHIP_OK) return rc;
             a.wh = xb->words_f16t;
             if (p.pca) { a.wh = PI.f16t; a.out_scale = PI.osc; a.word_norm = PI.cn_scaled; }      // scales fixed per codebook: the C operand is precomputed
@@ -936,7 +936,7 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
             }
             rc = knn_ring16_launch(ctx, T, p.kern, grid, p.threads, p.lds, a, clock, thr0, ctx->knn_pre_step, relax);
         } else if (p.cand == KNN_CAND_MFMA16) {
-            rc = knn_lds_cap(ctx, p.kern, p.lds_cap);
+            rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
             if (rc != ISMHIP_OK) return rc;
             a.wh = p.mode == 0 ? xb->words_f16 : xb->words_bf16_hi;
             a.wl = p.mode == 0 ? nullptr : xb->words_bf16_lo;
@@ -1229,12 +1229,6 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
 }
 
 }  // namespace
-
-// the dynamic-LDS cap of a kernel is raised once per ctx (per device), to the largest size any launch of that kernel uses
-int knn_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes) {
-    if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); ctx->attr_done.insert(kern); }
-    return ISMHIP_OK;
-}
 
 int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, float* sq, bool& negative) {
     uint32_t* flag = (uint32_t*)(sq + (size_t)nq * cb->dim_pad);

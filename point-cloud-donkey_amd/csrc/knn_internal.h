@@ -127,8 +127,6 @@ bool knn_matrix_gate(const ismhip_ctx* ctx, const ismhip_codebook* cb, int nq) {
 }  // namespace
 
 // ---- knn.hip ------------------------------------------------------------------------------------------------------------------------
-// the dynamic-LDS cap of a kernel is raised once per ctx (per device), to the largest size any launch of that kernel uses
-int knn_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes);
 // sq[nq x dim_pad] = sqrt of the query rows (zero padded; 4 more bytes behind them hold the flag); negative = some element is
 // negative or NaN, read back: the call synchronises the stream
 int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, float* sq, bool& negative);

@@ -255,7 +255,7 @@ int knn_mfma16_emit(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_cod
                     const float* tau, uint32_t* emit_cnt, uint32_t* rows, int cap) {
     const void* kern = (const void*)k_knn_l2_mfma16<4, 2, 2, 2, 2, 1, 64, 1>;
     const size_t lds = knn_mfma16_lds(128, 128, 64, 1);
-    const int rc = knn_lds_cap(ctx, kern, lds);
+    const int rc = ism_lds_cap(ctx, kern, lds);
     if (rc != ISMHIP_OK) return rc;
     const int n_qt = n_pad / 128, n_mt = cb->n_words_pad / 128;
     int nsp = std::max(1, std::min(n_mt / 2, (2048 + 8 * ((n_qt + 7) / 8) - 1) / (8 * ((n_qt + 7) / 8))));

@@ -373,7 +373,7 @@ int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, i
     if (thr0) {
         const void* pk = knn_ring16_kernel(T, 2, 0, 1);
         const size_t plds = Ring16Lds<2, 0>::total(0);
-        const int rc2 = knn_lds_cap(ctx, pk, plds);
+        const int rc2 = ism_lds_cap(ctx, pk, plds);
         if (rc2 != ISMHIP_OK) return rc2;
         int one = 1, all = a.n_tiles_m; unsigned int* noclk = nullptr; const float* noinit = nullptr;
         void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax};

@@ -14,7 +14,6 @@
 // filter on every maximum's member list between the member search and the per-maximum sums; the plain kernels do not contain it.
 #include "common.h"
 #include "ransac.h"
-#include <cstring>
 
 namespace {
 
@@ -150,19 +149,179 @@ __device__ __forceinline__ int block_sum_i(int v, int* s_red) {
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The per-(object, class) steps that both voting back ends take, written once. Args = MaxArgs or HoughArgs. The helpers declare
+// no __shared__ storage of their own: their LDS scratch (4 entries per array, one per wave) comes from the calling body.
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// The votes of one class, `cap` entries per array: in dynamic LDS, or (GM: objects with more than MX_LDS_SLOTS slots) in the
+// (object, class)'s region of the global workspace. `rest`: what follows the six arrays, for the back end's own.
+struct ClassVotes { float* x; float* y; float* z; float* w; int* inst; int* slot; unsigned char* rest; int cap; };
+template <bool GM, class Args>
+__device__ __forceinline__ ClassVotes class_votes_layout(const Args& a, unsigned char* smem) {
+    ClassVotes V;
+    // power of two >= max votes of one object (LDS) / >= the votes of this (object, class) (workspace)
+    V.cap = GM ? pow2_cap(a.class_count[(size_t)blockIdx.x * a.n_classes + blockIdx.y]) : a.cap;
+    unsigned char* arrays = smem;
+    if constexpr (GM) arrays = a.work + (size_t)a.work_off[(size_t)blockIdx.x * a.n_classes + blockIdx.y] * MX_WORK_STRIDE;
+    V.x = (float*)arrays;               V.y = V.x + V.cap; V.z = V.y + V.cap; V.w = V.z + V.cap;
+    V.inst = (int*)(V.w + V.cap);       V.slot = V.inst + V.cap;
+    V.rest = (unsigned char*)(V.slot + V.cap);
+    return V;
+}
+
+// Ordered compaction of the votes of class blockIdx.y among the slots of object blockIdx.x: slot order is kept (the reference visits
+// the votes of a class in the order they were cast). [s0, s1): the object's slots, read by the caller before its first store so
+// that they stay scalar loads. s_n: zeroed by the caller before a barrier. Returns the number of votes held.
+template <class Args>
+__device__ __forceinline__ int compact_class_votes(const Args& a, const ClassVotes& V, uint32_t s0, uint32_t s1, int& s_n, int* s_wcnt) {
+    const int c = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (uint32_t base = s0; base < s1; base += 256) {
+        const uint32_t s = base + tid;
+        const bool f = s < s1 && a.vcls[s] == c;
+        const unsigned long long mask = __ballot(f);
+        if (lane == 0) s_wcnt[wv] = __popcll(mask);
+        __syncthreads();
+        int off = s_n;
+        for (int k = 0; k < wv; ++k) off += s_wcnt[k];
+        if (f) {
+            const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
+            if (pos < V.cap) {
+                V.x[pos] = a.vpos[(size_t)s * 3]; V.y[pos] = a.vpos[(size_t)s * 3 + 1]; V.z[pos] = a.vpos[(size_t)s * 3 + 2];
+                V.w[pos] = a.vw[s]; V.inst[pos] = a.vinst[s]; V.slot[pos] = (int)s;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) s_n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        __syncthreads();
+    }
+    return min(s_n, V.cap);
+}
+
+// One member's share of the weighted box size and of the quaternion scatter matrix (voting.cpp:167-215); slot = its global vote slot
+struct BoxSums { float b0 = 0.f, b1 = 0.f, b2 = 0.f; float qs[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; };
+template <class Args>
+__device__ __forceinline__ void member_box_sums(const Args& a, int slot, float w, BoxSums& B) {
+    if (a.vbs) { const size_t s = (size_t)slot * 3; B.b0 += w * a.vbs[s]; B.b1 += w * a.vbs[s + 1]; B.b2 += w * a.vbs[s + 2]; }
+    if (a.vbq) quat_scatter_add(B.qs, w, a.vbq + (size_t)slot * 4);
+}
+__device__ __forceinline__ void block_sum_box(BoxSums& B, bool with_quat, float* s_redf) {
+    B.b0 = block_sum_f(B.b0, s_redf); B.b1 = block_sum_f(B.b1, s_redf); B.b2 = block_sum_f(B.b2, s_redf);
+    if (with_quat) {
+#pragma unroll
+        for (int e = 0; e < 10; ++e) B.qs[e] = block_sum_f(B.qs[e], s_redf);
+    }
+    __syncthreads();
+}
+
+// filterVotesWithRansac (voting.cpp:356-433) on the members of one maximum, in slot order. Every member keeps the weight it has in
+// V.w; member[] becomes the inlier mask, and cnt (block-wide), sw and B (per thread, to be block-summed) are taken again over the
+// inliers alone. B comes in zeroed. Returns false when the maximum goes: no hypothesis kept, or fewer inliers than MinVotesThreshold
+// (checked again on the filtered list, voting.cpp:131-136); uniform across the block.
+// clist: free storage for V.cap ints and V.cap bytes.
+template <class Args>
+__device__ __forceinline__ bool ransac_filter_members(const Args& a, const RansacKArgs& rk, const ClassVotes& V, int n, unsigned char* member, int* clist,
+                                                      RansacLds& L, int* s_redi, int& cnt, float& sw, BoxSums& B) {
+    const int tid = threadIdx.x;
+    unsigned char* inl = (unsigned char*)(clist + V.cap);
+    const int nm = rs_compact(n, member, clist, L);
+    const float* kp = rk.kp; const float* kpt = rk.kpt;
+    auto fetch = [&](int j, float* sp, float* tp) {
+        const size_t g = (size_t)V.slot[clist[j]] * 3;
+        sp[0] = kpt[g]; sp[1] = kpt[g + 1]; sp[2] = kpt[g + 2]; tp[0] = kp[g]; tp[1] = kp[g + 1]; tp[2] = kp[g + 2];
+    };
+    const RansacResult rr = ransac_cluster(nm, fetch, rk.class_thr ? rk.class_thr[blockIdx.y] : rk.thr, rk.max_iter, rk.seed, -1, inl, L);
+    if (tid == 0) rs_count(rk.counters, rr);
+    if (!rr.kept) return false;
+    for (int j = tid; j < nm; j += 256) member[clist[j]] = inl[j];
+    __syncthreads();
+    cnt = 0; sw = 0.f;
+    for (int i = tid; i < n; i += 256) {
+        if (!member[i]) continue;
+        const float w = V.w[i];
+        cnt++; sw += w;
+        member_box_sums(a, V.slot[i], w, B);
+    }
+    cnt = block_sum_i(cnt, s_redi);
+    return !(cnt < a.min_votes || cnt == 0);
+}
+
+// Instance id with the largest summed weight among the members; ties -> smallest id; weights <= 0 never win (voting.cpp:139-165).
+// Per-instance sums in a hash table of V.cap entries (open addressing, keys = instance ids, values = 2^-32 fixed point updated with
+// ds_add_u64: O(n), order independent) instead of the O(n^2) pairwise tally. Leaves the best of every wave in s_bS / s_bi, behind a
+// barrier; best_of_waves gives the winner to the one thread that writes the record.
+struct InstanceBest { unsigned long long sum; int id; };       // sum: 2^-32 fixed point
+__device__ __forceinline__ void instance_tally(const ClassVotes& V, int n, const unsigned char* member, int* hkey, unsigned long long* hval,
+                                               unsigned long long (&s_bS)[4], int (&s_bi)[4]) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int cap = V.cap;
+    const int HEMPTY = (int)0x80000000;
+    for (int i = tid; i < cap; i += 256) { hkey[i] = HEMPTY; hval[i] = 0ull; }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        if (!member[i]) continue;
+        const int id = V.inst[i];
+        const float wv_ = V.w[i];
+        const unsigned long long fx = wv_ > 0.f ? (unsigned long long)((double)wv_ * 4294967296.0) : 0ull;
+        unsigned slot = ((unsigned)id * 2654435761u) & (unsigned)(cap - 1);
+        for (int probe = 0; probe < cap; ++probe) {
+            const int old = atomicCAS(&hkey[slot], HEMPTY, id);
+            if (old == HEMPTY || old == id) { atomicAdd(&hval[slot], fx); break; }
+            slot = (slot + 1) & (unsigned)(cap - 1);
+        }
+    }
+    __syncthreads();
+    unsigned long long bS = 0ull; int bI = 0x7fffffff;
+    for (int i = tid; i < cap; i += 256) {
+        const int id = hkey[i];
+        if (id == HEMPTY) continue;
+        const unsigned long long S = hval[i];
+        if (S > bS || (S == bS && S > 0ull && (unsigned)id < (unsigned)bI)) { bS = S; bI = id; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long oS = __shfl_xor(bS, off, 64); const int oI = __shfl_xor(bI, off, 64);
+        if (oS > bS || (oS == bS && oS > 0ull && (unsigned)oI < (unsigned)bI)) { bS = oS; bI = oI; }
+    }
+    if (lane == 0) { s_bS[wv] = bS; s_bi[wv] = bI; }
+    __syncthreads();
+}
+__device__ __forceinline__ InstanceBest best_of_waves(const unsigned long long (&s_bS)[4], const int (&s_bi)[4]) {
+    unsigned long long fS = s_bS[0]; int bestI = s_bi[0];
+    for (int k = 1; k < 4; ++k)
+        if (s_bS[k] > fS || (s_bS[k] == fS && fS > 0ull && (unsigned)s_bi[k] < (unsigned)bestI)) { fS = s_bS[k]; bestI = s_bi[k]; }
+    return {fS, bestI};
+}
+
+// One thread writes the class's next record (layout: MX_REC) and, in the RANSAC kernels that were asked for it, the motion of the
+// best hypothesis (L->M) beside it; a maximum beyond MX_MAXM_C is dropped and counted. (px, py, pz): the back end's position;
+// B: block-summed; qs: its scatter matrix with Voting.AverageRotation, else NULL.
+__device__ __forceinline__ void write_maximum_record(float* rec, float* rec_tf, const RansacLds* L, int& s_nmax, uint32_t* truncated, float px, float py, float pz,
+                                                     float sw, int cnt, const InstanceBest& best, const BoxSums& B, const float* qs) {
+    const float bestS = (float)((double)best.sum * 2.3283064365386963e-10);
+    const int m = s_nmax;
+    if (m < MX_MAXM_C) {
+        float* r = rec + (size_t)m * MX_REC;
+        r[0] = px; r[1] = py; r[2] = pz; r[3] = sw;
+        r[4] = __int_as_float(bestS > 0.f ? best.id : -1); r[5] = bestS > 0.f ? bestS : 0.f;
+        r[6] = B.b0 / sw; r[7] = B.b1 / sw; r[8] = B.b2 / sw; r[9] = __int_as_float(cnt);
+        r[10] = 1.f; r[11] = 0.f; r[12] = 0.f; r[13] = 0.f;
+        if (qs) quat_from_scatter(qs, r + 10);                     // voting.cpp:210-215
+        if (rec_tf) { float* tf = rec_tf + (size_t)m * 12; for (int e = 0; e < 12; ++e) tf[e] = (float)L->M[e]; }
+        s_nmax = m + 1;
+    } else atomicAdd(truncated, 1u);
+}
+
 // GM: the vote arrays live in the global workspace (objects with more than MX_LDS_SLOTS slots); RS: with the RANSAC vote filter
 template <bool GM, bool RS>
 __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacKArgs* rk) {
     RansacLds* Lp = nullptr;
     if constexpr (RS) { __shared__ RansacLds s_rs; Lp = &s_rs; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // power of two >= max votes of one object (LDS) / >= the votes of this (object, class) (workspace)
-    const int cap = GM ? pow2_cap(a.class_count[(size_t)blockIdx.x * a.n_classes + blockIdx.y]) : a.cap;
-    unsigned char* arrays = smem;
-    if constexpr (GM) arrays = a.work + (size_t)a.work_off[(size_t)blockIdx.x * a.n_classes + blockIdx.y] * MX_WORK_STRIDE;
-    float* vx = (float*)arrays;             float* vy = vx + cap; float* vz = vy + cap; float* vw = vz + cap;
-    int* vinst = (int*)(vw + cap);          int* vslot = vinst + cap;
-    unsigned long long* keys = (unsigned long long*)(vslot + cap);
+    const ClassVotes V = class_votes_layout<GM>(a, smem);
+    const int cap = V.cap;
+    unsigned long long* keys = (unsigned long long*)V.rest;
     float4* ctr = (float4*)(keys + cap);    float4* ctr2 = ctr + cap;
     unsigned char* member = (unsigned char*)(ctr2 + cap);
     __shared__ int s_nmax, s_n, s_ns, s_nc, s_np;
@@ -170,43 +329,27 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
     __shared__ float s_redf[4];
     __shared__ int s_redi[4];
     __shared__ int s_bi[4];
+    __shared__ unsigned long long s_bS[4];
 
     const int o = blockIdx.x;
     const int c = blockIdx.y;                                    // the reference visits the classes of m_votes one by one (voting.cpp:95)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t s0 = a.slot_off[o], s1 = a.slot_off[o + 1];
-    const int C = a.n_classes;
-    float* rec = a.rec + ((size_t)o * C + c) * MX_MAXM_C * MX_REC;
-    if (tid == 0) { s_nmax = 0; a.rec_count[(size_t)o * C + c] = 0; }
+    const size_t oc = (size_t)o * a.n_classes + c;
+    float* rec = a.rec + oc * MX_MAXM_C * MX_REC;
+    float* rec_tf = nullptr;                                     // RANSAC entries: (R, t) records of this class, when asked for
+    if constexpr (RS) if (rk->rec_tf) rec_tf = rk->rec_tf + oc * MX_MAXM_C * 12;
+    if (tid == 0) { s_nmax = 0; a.rec_count[oc] = 0; }
     __syncthreads();
     {
         float h = a.class_bw ? a.class_bw[c] : a.bandwidth;                // voting_mean_shift.cpp:48-49
         float h2 = (float)((double)h * (double)h);
         float hh = h * h;
-        // ---- ordered compaction of the class's votes into LDS
         if (tid == 0) s_n = 0;
         __syncthreads();
-        for (uint32_t base = s0; base < s1; base += 256) {
-            const uint32_t s = base + tid;
-            const bool f = s < s1 && a.vcls[s] == c;
-            const unsigned long long mask = __ballot(f);
-            if (lane == 0) s_wcnt[wv] = __popcll(mask);
-            __syncthreads();
-            int off = s_n;
-            for (int k = 0; k < wv; ++k) off += s_wcnt[k];
-            if (f) {
-                const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
-                if (pos < cap) {
-                    vx[pos] = a.vpos[(size_t)s * 3]; vy[pos] = a.vpos[(size_t)s * 3 + 1]; vz[pos] = a.vpos[(size_t)s * 3 + 2];
-                    vw[pos] = a.vw[s]; vinst[pos] = a.vinst[s]; vslot[pos] = (int)s;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) s_n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-            __syncthreads();
-        }
-        const int n = min(s_n, cap);
+        const int n = compact_class_votes(a, V, s0, s1, s_n, s_wcnt);
         if (n == 0) return;                                       // class absent from m_votes (uniform across the block)
+        const float* vx = V.x; const float* vy = V.y; const float* vz = V.z; float* vw = V.w;
         if (a.som_type != ISMHIP_SOM_MEANSHIFT) {
             // Single-object mode with SingleObjectMaxType BANDWIDTH / MODEL_RADIUS / COMPLETE_VOTING_SPACE (voting_mean_shift.cpp:124-157):
             // no mean shift; ONE maximum per class at the centroid of the object's cloud, density and reweighting with the bandwidth
@@ -369,8 +512,8 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
         // ---- per maximum: density + in-place reweighting (:289-328) and the Voting::findMaxima block (voting.cpp:131-236)
         for (int pi = 0; pi < np; ++pi) {
             const float4 p = ctr2[pi];
-            int cnt = 0; float sw = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-            float qs[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int cnt = 0; float sw = 0.f;
+            BoxSums B;
             for (int i = tid; i < n; i += 256) {
                 const float d2 = sqdist3(vx[i], vy[i], vz[i], p.x, p.y, p.z);
                 const bool in = d2 < h2;
@@ -379,108 +522,23 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
                     const float w = ms_kernel(a.kernel, d2 / hh) * vw[i];
                     vw[i] = w;
                     cnt++;
-                    if constexpr (!RS) {
-                    sw += w;
-                    if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
-                    if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
-                    }
+                    if constexpr (!RS) { sw += w; member_box_sums(a, V.slot[i], w, B); }
                 }
             }
             cnt = block_sum_i(cnt, s_redi);
             if (cnt < a.min_votes || cnt == 0) continue;      // uniform across the block
-            if constexpr (RS) {
-                // filterVotesWithRansac (voting.cpp:356-433) on the members in slot order; every member keeps its reweighted weight
-                // (voting_mean_shift.cpp:161-176 ran before), member[] becomes the inlier mask and the sums below see inliers only
-                int* clist = (int*)keys;                                 // keys / ctr are free once the final positions sit in ctr2
-                unsigned char* inl = (unsigned char*)(clist + cap);
-                const int nm = rs_compact(n, member, clist, *Lp);
-                const float* kp = rk->kp; const float* kpt = rk->kpt;
-                auto fetch = [&](int j, float* sp, float* tp) {
-                    const size_t g = (size_t)vslot[clist[j]] * 3;
-                    sp[0] = kpt[g]; sp[1] = kpt[g + 1]; sp[2] = kpt[g + 2]; tp[0] = kp[g]; tp[1] = kp[g + 1]; tp[2] = kp[g + 2];
-                };
-                const RansacResult rr = ransac_cluster(nm, fetch, rk->class_thr ? rk->class_thr[c] : rk->thr, rk->max_iter, rk->seed, -1, inl, *Lp);
-                if (tid == 0) rs_count(rk->counters, rr);
-                if (!rr.kept) continue;                                  // uniform across the block
-                for (int j = tid; j < nm; j += 256) member[clist[j]] = inl[j];
-                __syncthreads();
-                cnt = 0;
-                for (int i = tid; i < n; i += 256) {
-                    if (!member[i]) continue;
-                    const float w = vw[i];
-                    cnt++; sw += w;
-                    if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
-                    if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
-                }
-                cnt = block_sum_i(cnt, s_redi);
-                if (cnt < a.min_votes || cnt == 0) continue;  // MinVotesThreshold again, on the filtered list (voting.cpp:131-136)
-            }
+            // RANSAC: every member keeps its reweighted weight (voting_mean_shift.cpp:161-176 ran before), the sums see inliers only.
+            // keys / ctr are free once the final positions sit in ctr2
+            if constexpr (RS) if (!ransac_filter_members(a, *rk, V, n, member, (int*)keys, *Lp, s_redi, cnt, sw, B)) continue;
             sw = block_sum_f(sw, s_redf);
-            b0 = block_sum_f(b0, s_redf); b1 = block_sum_f(b1, s_redf); b2 = block_sum_f(b2, s_redf);
-            if (a.vbq) {
-#pragma unroll
-                for (int e = 0; e < 10; ++e) qs[e] = block_sum_f(qs[e], s_redf);
-            }
-            __syncthreads();
-            // instance id with the largest summed weight; ties -> smallest id; weights <= 0 never win (voting.cpp:139-165).
-            // Per-instance sums in an LDS hash table (open addressing, keys = instance ids, values = 2^-32 fixed point updated with
-            // ds_add_u64: O(n), order independent) instead of the O(n^2) pairwise tally.
-            int* hkey = (int*)ctr;                                   // ctr / keys are free once the final positions sit in ctr2
-            unsigned long long* hval = keys;
-            const int HEMPTY = (int)0x80000000;
-            for (int i = tid; i < cap; i += 256) { hkey[i] = HEMPTY; hval[i] = 0ull; }
-            __syncthreads();
-            for (int i = tid; i < n; i += 256) {
-                if (!member[i]) continue;
-                const int id = vinst[i];
-                const float wv_ = vw[i];
-                const unsigned long long fx = wv_ > 0.f ? (unsigned long long)((double)wv_ * 4294967296.0) : 0ull;
-                unsigned slot = ((unsigned)id * 2654435761u) & (unsigned)(cap - 1);
-                for (int probe = 0; probe < cap; ++probe) {
-                    const int old = atomicCAS(&hkey[slot], HEMPTY, id);
-                    if (old == HEMPTY || old == id) { atomicAdd(&hval[slot], fx); break; }
-                    slot = (slot + 1) & (unsigned)(cap - 1);
-                }
-            }
-            __syncthreads();
-            unsigned long long bS = 0ull; int bI = 0x7fffffff;
-            for (int i = tid; i < cap; i += 256) {
-                const int id = hkey[i];
-                if (id == HEMPTY) continue;
-                const unsigned long long S = hval[i];
-                if (S > bS || (S == bS && S > 0ull && (unsigned)id < (unsigned)bI)) { bS = S; bI = id; }
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long oS = __shfl_xor(bS, off, 64); const int oI = __shfl_xor(bI, off, 64);
-                if (oS > bS || (oS == bS && oS > 0ull && (unsigned)oI < (unsigned)bI)) { bS = oS; bI = oI; }
-            }
-            float bestS = (float)((double)bS * 2.3283064365386963e-10); int bestI = bI;
-            __shared__ unsigned long long s_bS[4];
-            if (lane == 0) { s_bS[wv] = bS; s_bi[wv] = bI; }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned long long fS = s_bS[0]; bestI = s_bi[0];
-                for (int k = 1; k < 4; ++k)
-                    if (s_bS[k] > fS || (s_bS[k] == fS && fS > 0ull && (unsigned)s_bi[k] < (unsigned)bestI)) { fS = s_bS[k]; bestI = s_bi[k]; }
-                bestS = (float)((double)fS * 2.3283064365386963e-10);
-                const int m = s_nmax;
-                if (m < MX_MAXM_C) {
-                    float* r = rec + (size_t)m * MX_REC;
-                    r[0] = p.x; r[1] = p.y; r[2] = p.z; r[3] = sw;
-                    r[4] = __int_as_float(bestS > 0.f ? bestI : -1); r[5] = bestS > 0.f ? bestS : 0.f;
-                    r[6] = b0 / sw; r[7] = b1 / sw; r[8] = b2 / sw; r[9] = __int_as_float(cnt);
-                    r[10] = 1.f; r[11] = 0.f; r[12] = 0.f; r[13] = 0.f;
-                    if (a.vbq) quat_from_scatter(qs, r + 10);          // voting.cpp:210-215
-                    if constexpr (RS) if (rk->rec_tf) { float* tf = rk->rec_tf + (((size_t)o * C + c) * MX_MAXM_C + m) * 12; for (int e = 0; e < 12; ++e) tf[e] = (float)Lp->M[e]; }
-                    s_nmax = m + 1;
-                } else atomicAdd(a.truncated, 1u);
-            }
+            block_sum_box(B, a.vbq != nullptr, s_redf);
+            instance_tally(V, n, member, (int*)ctr, keys, s_bS, s_bi);
+            if (tid == 0) write_maximum_record(rec, rec_tf, Lp, s_nmax, a.truncated, p.x, p.y, p.z, sw, cnt, best_of_waves(s_bS, s_bi), B, a.vbq ? B.qs : nullptr);
             __syncthreads();
         }
         __syncthreads();
     }
-    if (tid == 0) a.rec_count[(size_t)o * C + c] = s_nmax;
+    if (tid == 0) a.rec_count[oc] = s_nmax;
 }
 template <bool GM>
 __global__ __launch_bounds__(256) void k_find_maxima(MaxArgs a) { find_maxima_body<GM, false>(a, nullptr); }
@@ -659,7 +717,7 @@ struct HoughArgs {
     const float* vbq;                    // Voting.AverageRotation: bbox quaternions of the votes, or NULL
     const uint32_t* slot_off; const float* vpos; const float* vw; const int32_t* vcls; const int32_t* vinst; const float* vbs;
     int n_classes; const float* class_bin; float bin; float minc[3], maxc[3]; int use_int; float rel; int min_votes, cap, tile_edge;
-    float* rec; int32_t* rec_count; int32_t* overflow;
+    float* rec; int32_t* rec_count;
     unsigned char* work; const uint32_t* work_off; const uint32_t* class_count;
     uint32_t* truncated;
 };
@@ -686,12 +744,9 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     RansacLds* Lp = nullptr;
     if constexpr (RS) { __shared__ RansacLds s_rs; Lp = &s_rs; }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int cap = GM ? pow2_cap(a.class_count[(size_t)blockIdx.x * a.n_classes + blockIdx.y]) : a.cap;
-    unsigned char* arrays = smem;
-    if constexpr (GM) arrays = a.work + (size_t)a.work_off[(size_t)blockIdx.x * a.n_classes + blockIdx.y] * MX_WORK_STRIDE;
-    float* vx = (float*)arrays;             float* vy = vx + cap; float* vz = vy + cap; float* vw = vz + cap;
-    int* vinst = (int*)(vw + cap);          int* vslot = vinst + cap;
-    unsigned long long* hval = (unsigned long long*)(vslot + cap);      // instance tally (values)
+    const ClassVotes V = class_votes_layout<GM>(a, smem);
+    const int cap = V.cap;
+    unsigned long long* hval = (unsigned long long*)V.rest;             // instance tally (values)
     int* hkey = (int*)(hval + cap);                                       // instance tally (keys)
     unsigned char* member = (unsigned char*)(hkey + cap);
     unsigned long long* tile = GM ? (unsigned long long*)smem : (unsigned long long*)(member + cap);     // tile_edge^3 bins, always in LDS
@@ -703,35 +758,18 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     __shared__ unsigned long long s_bS[4], s_hmax;
     __shared__ long long s_mbin[MX_MAXM_C];
     const int o = blockIdx.x, c = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t s0 = a.slot_off[o], s1 = a.slot_off[o + 1];
-    const int C = a.n_classes;
-    float* rec = a.rec + ((size_t)o * C + c) * MX_MAXM_C * MX_REC;
-    if (tid == 0) { s_nmax = 0; s_n = 0; s_nm = 0; s_hmax = 0ull; a.rec_count[(size_t)o * C + c] = 0;
+    const size_t oc = (size_t)o * a.n_classes + c;
+    float* rec = a.rec + oc * MX_MAXM_C * MX_REC;
+    float* rec_tf = nullptr;                                     // RANSAC entries: (R, t) records of this class, when asked for
+    if constexpr (RS) if (rk->rec_tf) rec_tf = rk->rec_tf + oc * MX_MAXM_C * 12;
+    if (tid == 0) { s_nmax = 0; s_n = 0; s_nm = 0; s_hmax = 0ull; a.rec_count[oc] = 0;
                     for (int d = 0; d < 3; ++d) { s_lo[d] = 0x7fffffff; s_hi[d] = -1; } }
     __syncthreads();
-    // ---- ordered compaction of the class's votes into LDS (as k_find_maxima)
-    for (uint32_t base = s0; base < s1; base += 256) {
-        const uint32_t s = base + tid;
-        const bool f = s < s1 && a.vcls[s] == c;
-        const unsigned long long mask = __ballot(f);
-        if (lane == 0) s_wcnt[wv] = __popcll(mask);
-        __syncthreads();
-        int off = s_n;
-        for (int k = 0; k < wv; ++k) off += s_wcnt[k];
-        if (f) {
-            const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < cap) {
-                vx[pos] = a.vpos[(size_t)s * 3]; vy[pos] = a.vpos[(size_t)s * 3 + 1]; vz[pos] = a.vpos[(size_t)s * 3 + 2];
-                vw[pos] = a.vw[s]; vinst[pos] = a.vinst[s]; vslot[pos] = (int)s;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) s_n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        __syncthreads();
-    }
-    const int n = min(s_n, cap);
+    const int n = compact_class_votes(a, V, s0, s1, s_n, s_wcnt);
     if (n == 0) return;                                       // class absent from m_votes (uniform across the block)
+    const float* vx = V.x; const float* vy = V.y; const float* vz = V.z; const float* vw = V.w;
     const double bin = (double)(a.class_bin ? a.class_bin[c] : a.bin);
     int cnt[3];
     for (int d = 0; d < 3; ++d) {
@@ -751,9 +789,8 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     const int lo[3] = {s_lo[0], s_lo[1], s_lo[2]}, hi[3] = {s_hi[0], s_hi[1], s_hi[2]};
     const int nt[3] = {(hi[0] - lo[0]) / EI + 1, (hi[1] - lo[1]) / EI + 1, (hi[2] - lo[2]) / EI + 1};
     const int n_tiles = nt[0] * nt[1] * nt[2];
-    const int passes = a.rel > 0.f || true ? 2 : 1;          // pass 0: max(H); pass 1: maxima
     unsigned long long thr_fix = 0ull;
-    for (int pass = 0; pass < passes; ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {                   // pass 0: max(H) for the relative threshold; pass 1: maxima
         for (int t = 0; t < n_tiles; ++t) {
             // tile t covers interior bins [t0, t0 + EI) per axis, stored at local (b - t0 + 1)
             const int t0[3] = {lo[0] + (t % nt[0]) * EI, lo[1] + ((t / nt[0]) % nt[1]) * EI, lo[2] + (t / (nt[0] * nt[1])) * EI};
@@ -816,7 +853,7 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
         }
     }
     int nm = s_nm;
-    if (nm > MX_MAXM_C) { if (tid == 0) { atomicAdd(a.overflow, 1); atomicAdd(a.truncated, 1u); } nm = MX_MAXM_C; }
+    if (nm > MX_MAXM_C) { if (tid == 0) atomicAdd(a.truncated, 1u); nm = MX_MAXM_C; }
     if (tid == 0)                                               // ascending bin index = the order findMaxima reports them in
         for (int i = 1; i < nm; ++i) { const long long v = s_mbin[i]; int j = i - 1; while (j >= 0 && s_mbin[j] > v) { s_mbin[j + 1] = s_mbin[j]; --j; } s_mbin[j + 1] = v; }
     __syncthreads();
@@ -824,8 +861,8 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     for (int pi = 0; pi < nm; ++pi) {
         const long long mb = s_mbin[pi];
         const int mbx = (int)(mb % cnt[0]), mby = (int)((mb / cnt[0]) % cnt[1]), mbz = (int)(mb / ((long long)cnt[0] * cnt[1]));
-        int vcnt = 0; float sw = 0.f, px = 0.f, py = 0.f, pz = 0.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-        float qs[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int vcnt = 0; float sw = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+        BoxSums B;
         for (int i = tid; i < n; i += 256) {
             const HgBin b = hg_bin(a, bin, cnt, vx[i], vy[i], vz[i]);
             bool in = b.in;
@@ -846,101 +883,25 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
             if (in) {
                 const float w = vw[i];
                 vcnt++; sw += w; px += vx[i] * w; py += vy[i] * w; pz += vz[i] * w;
-                if constexpr (!RS) {
-                if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
-                if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
-                }
+                if constexpr (!RS) member_box_sums(a, V.slot[i], w, B);
             }
         }
         vcnt = block_sum_i(vcnt, s_redi);
         if (vcnt < a.min_votes || vcnt == 0) continue;        // uniform across the block
         sw = block_sum_f(sw, s_redf);
         px = block_sum_f(px, s_redf); py = block_sum_f(py, s_redf); pz = block_sum_f(pz, s_redf);
-        float sw_pos = sw;                                    // the maximum's position: the weighted centre of ALL voters (voting_hough_3d.cpp:70-93)
+        const float sw_pos = sw;                              // the maximum's position: the weighted centre of ALL voters (voting_hough_3d.cpp:70-93)
         if constexpr (RS) {
-            // filterVotesWithRansac (voting.cpp:356-433) on the voters in slot order: the position stays, every other sum sees inliers only
-            int* clist = (int*)hval;                                     // the instance tally's arrays are free until the tally below
-            unsigned char* inl = (unsigned char*)(clist + cap);
-            const int nv = rs_compact(n, member, clist, *Lp);
-            const float* kp = rk->kp; const float* kpt = rk->kpt;
-            auto fetch = [&](int j, float* sp, float* tp) {
-                const size_t g = (size_t)vslot[clist[j]] * 3;
-                sp[0] = kpt[g]; sp[1] = kpt[g + 1]; sp[2] = kpt[g + 2]; tp[0] = kp[g]; tp[1] = kp[g + 1]; tp[2] = kp[g + 2];
-            };
-            const RansacResult rr = ransac_cluster(nv, fetch, rk->class_thr ? rk->class_thr[c] : rk->thr, rk->max_iter, rk->seed, -1, inl, *Lp);
-            if (tid == 0) rs_count(rk->counters, rr);
-            if (!rr.kept) continue;                                      // uniform across the block
-            for (int j = tid; j < nv; j += 256) member[clist[j]] = inl[j];
-            __syncthreads();
-            vcnt = 0; sw = 0.f;
-            for (int i = tid; i < n; i += 256) {
-                if (!member[i]) continue;
-                const float w = vw[i];
-                vcnt++; sw += w;
-                if (a.vbs) { const size_t s = (size_t)vslot[i] * 3; b0 += w * a.vbs[s]; b1 += w * a.vbs[s + 1]; b2 += w * a.vbs[s + 2]; }
-                if (a.vbq) quat_scatter_add(qs, w, a.vbq + (size_t)vslot[i] * 4);
-            }
-            vcnt = block_sum_i(vcnt, s_redi);
-            if (vcnt < a.min_votes || vcnt == 0) continue;    // MinVotesThreshold again, on the filtered list (voting.cpp:131-136)
+            // RANSAC on the voters: the position stays, every other sum sees inliers only. The instance tally's arrays are free until the tally
+            if (!ransac_filter_members(a, *rk, V, n, member, (int*)hval, *Lp, s_redi, vcnt, sw, B)) continue;
             sw = block_sum_f(sw, s_redf);
         }
-        b0 = block_sum_f(b0, s_redf); b1 = block_sum_f(b1, s_redf); b2 = block_sum_f(b2, s_redf);
-        if (a.vbq) {
-#pragma unroll
-            for (int e = 0; e < 10; ++e) qs[e] = block_sum_f(qs[e], s_redf);
-        }
-        __syncthreads();
-        // instance tally: as k_find_maxima (LDS hash, 2^-32 fixed point, ties -> smallest id, weights <= 0 never win)
-        const int HEMPTY = (int)0x80000000;
-        for (int i = tid; i < cap; i += 256) { hkey[i] = HEMPTY; hval[i] = 0ull; }
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            if (!member[i]) continue;
-            const int id = vinst[i];
-            const float wv_ = vw[i];
-            const unsigned long long fx = wv_ > 0.f ? (unsigned long long)((double)wv_ * 4294967296.0) : 0ull;
-            unsigned slot = ((unsigned)id * 2654435761u) & (unsigned)(cap - 1);
-            for (int probe = 0; probe < cap; ++probe) {
-                const int old = atomicCAS(&hkey[slot], HEMPTY, id);
-                if (old == HEMPTY || old == id) { atomicAdd(&hval[slot], fx); break; }
-                slot = (slot + 1) & (unsigned)(cap - 1);
-            }
-        }
-        __syncthreads();
-        unsigned long long bS = 0ull; int bI = 0x7fffffff;
-        for (int i = tid; i < cap; i += 256) {
-            const int id = hkey[i];
-            if (id == HEMPTY) continue;
-            const unsigned long long S = hval[i];
-            if (S > bS || (S == bS && S > 0ull && (unsigned)id < (unsigned)bI)) { bS = S; bI = id; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long oS = __shfl_xor(bS, off, 64); const int oI = __shfl_xor(bI, off, 64);
-            if (oS > bS || (oS == bS && oS > 0ull && (unsigned)oI < (unsigned)bI)) { bS = oS; bI = oI; }
-        }
-        if (lane == 0) { s_bS[wv] = bS; s_bi[wv] = bI; }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long fS = s_bS[0]; int bestI = s_bi[0];
-            for (int k = 1; k < 4; ++k)
-                if (s_bS[k] > fS || (s_bS[k] == fS && fS > 0ull && (unsigned)s_bi[k] < (unsigned)bestI)) { fS = s_bS[k]; bestI = s_bi[k]; }
-            const float bestS = (float)((double)fS * 2.3283064365386963e-10);
-            const int m = s_nmax;
-            if (m < MX_MAXM_C) {
-                float* r = rec + (size_t)m * MX_REC;
-                r[0] = px / sw_pos; r[1] = py / sw_pos; r[2] = pz / sw_pos; r[3] = sw;
-                r[4] = __int_as_float(bestS > 0.f ? bestI : -1); r[5] = bestS > 0.f ? bestS : 0.f;
-                r[6] = b0 / sw; r[7] = b1 / sw; r[8] = b2 / sw; r[9] = __int_as_float(vcnt);
-                r[10] = 1.f; r[11] = 0.f; r[12] = 0.f; r[13] = 0.f;
-                if (a.vbq) quat_from_scatter(qs, r + 10);
-                if constexpr (RS) if (rk->rec_tf) { float* tf = rk->rec_tf + (((size_t)o * C + c) * MX_MAXM_C + m) * 12; for (int e = 0; e < 12; ++e) tf[e] = (float)Lp->M[e]; }
-                s_nmax = m + 1;
-            } else atomicAdd(a.truncated, 1u);
-        }
+        block_sum_box(B, a.vbq != nullptr, s_redf);
+        instance_tally(V, n, member, hkey, hval, s_bS, s_bi);
+        if (tid == 0) write_maximum_record(rec, rec_tf, Lp, s_nmax, a.truncated, px / sw_pos, py / sw_pos, pz / sw_pos, sw, vcnt, best_of_waves(s_bS, s_bi), B, a.vbq ? B.qs : nullptr);
         __syncthreads();
     }
-    if (tid == 0) a.rec_count[(size_t)o * C + c] = s_nmax;
+    if (tid == 0) a.rec_count[oc] = s_nmax;
 }
 template <bool GM>
 __global__ __launch_bounds__(256) void k_hough3d(HoughArgs a) { hough3d_body<GM, false>(a, nullptr); }
@@ -990,82 +951,133 @@ static int ransac_kernel_args(ismhip_ctx* ctx, const char* what, const ismhip_ra
     return rk->counters ? ISMHIP_OK : ISMHIP_ERR_NOMEM;
 }
 
-static int find_maxima_impl(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
-                                  const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
-                                  const int32_t* vote_instance, const float* vote_bbox_size,
-                                  const ismhip_maxima_params* P,
-                                  int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
-                                  int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
-                                  float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
-                                  bool ransac, const ismhip_ransac_params* R, float* max_transform_out) {
-    if (!ctx || n_obj <= 0 || !slot_offsets_h || !vote_pos || !vote_weight || !vote_class || !vote_instance || !P ||
-        !n_maxima_out || !max_pos_out || !max_weight_out || !max_class_out || !max_instance_out || !max_instance_weight_out ||
-        !max_n_votes_out || !class_score_out || P->n_classes <= 0 || P->max_maxima <= 0 || !(P->bandwidth > 0.f || P->class_bandwidth_h))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: bad argument");
-    if (P->n_classes > MX_MAXC) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "find_maxima: more than 256 classes not built");
-    if (P->kernel != ISMHIP_KERNEL_GAUSSIAN && P->kernel != ISMHIP_KERNEL_UNIFORM) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: kernel");
+// What the four entries have in common: the votes by slot (device), the nine outputs and, for the RANSAC entries, the filter's side.
+// name: the prefix of the entry's error messages (the RANSAC entries report under name + "_ransac" where the filter is concerned).
+struct MaximaCall {
+    const char* name; int n_obj; const uint32_t* slot_offsets_h;
+    const float* vote_pos; const float* vote_weight; const int32_t* vote_class; const int32_t* vote_instance; const float* vote_bbox_size;
+    int32_t* n_maxima; float* max_pos; float* max_weight; int32_t* max_class; int32_t* max_instance; float* max_instance_weight;
+    float* max_bbox_size; int32_t* max_n_votes; float* class_score;
+    bool ransac; const ismhip_ransac_params* R; float* max_transform;
+};
+// what maxima_setup hands to the back end: the shared fields of MaxArgs filled in, the RANSAC kernel arguments, the uploaded per-class array
+struct MaximaPlan { MaxArgs a; RansacKArgs rk; float* class_val; bool big; };
+
+// The part of a call that does not depend on the back end: validation, the offsets with cap and big, the per-class float array
+// (bandwidths / bin edges), the record scratch, the output, filter and quaternion fields of MaxArgs, the big-object workspace and the
+// RANSAC arguments. Params: ismhip_maxima_params or ismhip_hough_params; size_given: a scalar size > 0 or a per-class array.
+template <class Params>
+static int maxima_setup(ismhip_ctx* ctx, const MaximaCall& io, const Params* P, bool size_given, const float* class_val_h, MaximaPlan* pl) {
+    const std::string name = io.name;
+    if (io.ransac && !io.R) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + "_ransac: ransac parameters missing");
+    if (!ctx || io.n_obj <= 0 || !io.slot_offsets_h || !io.vote_pos || !io.vote_weight || !io.vote_class || !io.vote_instance || !P ||
+        !io.n_maxima || !io.max_pos || !io.max_weight || !io.max_class || !io.max_instance || !io.max_instance_weight ||
+        !io.max_n_votes || !io.class_score || P->n_classes <= 0 || P->max_maxima <= 0 || !size_given)
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": bad argument");
+    if (P->n_classes > MX_MAXC) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, name + ": more than 256 classes not built");
     uint32_t max_slots = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (slot_offsets_h[o + 1] < slot_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: offsets not monotone");
-        max_slots = std::max(max_slots, slot_offsets_h[o + 1] - slot_offsets_h[o]);
+    for (int o = 0; o < io.n_obj; ++o) {
+        if (io.slot_offsets_h[o + 1] < io.slot_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": offsets not monotone");
+        max_slots = std::max(max_slots, io.slot_offsets_h[o + 1] - io.slot_offsets_h[o]);
     }
-    int cap = 64; while ((uint32_t)cap < max_slots) cap <<= 1;
-    const bool big = cap > MX_LDS_SLOTS;
-    const size_t dyn = big ? 0 : (size_t)cap * (4 * 4 + 2 * 4 + 8 + 16 + 16 + 1);
-    uint32_t* so = ism_upload_offsets(ctx, SCR_SLOT_OFF, slot_offsets_h, n_obj + 1);
-    if (!so) return ISMHIP_ERR_HIP;
-    float* bw = nullptr;
-    if (P->class_bandwidth_h) {
-        bw = (float*)ism_scratch(ctx, SCR_CLASS_BW, (size_t)P->n_classes * 4);
-        if (!bw) return ISMHIP_ERR_NOMEM;
-        ISM_HIP(ctx, hipMemcpyAsync(bw, P->class_bandwidth_h, (size_t)P->n_classes * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    MaxArgs a;
-    a.slot_off = so; a.vpos = vote_pos; a.vw = vote_weight; a.vcls = vote_class; a.vinst = vote_instance; a.vbs = vote_bbox_size;
-    a.n_classes = P->n_classes; a.class_bw = bw; a.bandwidth = P->bandwidth; a.threshold = P->threshold; a.max_iter = P->max_iter;
-    a.kernel = P->kernel; a.suppression = P->suppression; a.min_votes = P->min_votes_threshold; a.min_threshold = P->min_threshold;
-    a.best_k = P->best_k; a.max_maxima = P->max_maxima; a.cap = cap;
     if (P->max_filter != ISMHIP_MAXFILTER_NONE && P->max_filter != ISMHIP_MAXFILTER_SIMPLE && P->max_filter != ISMHIP_MAXFILTER_MERGE)
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: MaxFilterType");
-    a.max_filter = P->max_filter; a.filter_radius = P->bandwidth;      // MaximaHandler::m_radius = the configured bandwidth (voting_mean_shift.cpp:46)
-    if ((P->vote_bbox_quat == nullptr) != (P->max_bbox_quat_out == nullptr)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: vote_bbox_quat and max_bbox_quat_out go together");
-    a.vbq = P->vote_bbox_quat; a.mbq = P->max_bbox_quat_out;
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": MaxFilterType");
+    if ((P->vote_bbox_quat == nullptr) != (P->max_bbox_quat_out == nullptr)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": vote_bbox_quat and max_bbox_quat_out go together");
+    MaxArgs& a = pl->a;
+    a = MaxArgs{};
+    a.cap = 64; while ((uint32_t)a.cap < max_slots) a.cap <<= 1;
+    pl->big = a.cap > MX_LDS_SLOTS;
+    uint32_t* so = ism_upload_offsets(ctx, SCR_SLOT_OFF, io.slot_offsets_h, io.n_obj + 1);
+    if (!so) return ISMHIP_ERR_HIP;
+    pl->class_val = nullptr;
+    if (class_val_h) {
+        pl->class_val = (float*)ism_scratch(ctx, SCR_CLASS_BW, (size_t)P->n_classes * 4);
+        if (!pl->class_val) return ISMHIP_ERR_NOMEM;
+        ISM_HIP(ctx, hipMemcpyAsync(pl->class_val, class_val_h, (size_t)P->n_classes * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    a.slot_off = so; a.vpos = io.vote_pos; a.vw = io.vote_weight; a.vcls = io.vote_class; a.vinst = io.vote_instance; a.vbs = io.vote_bbox_size;
+    a.n_classes = P->n_classes; a.min_votes = P->min_votes_threshold; a.min_threshold = P->min_threshold; a.best_k = P->best_k; a.max_maxima = P->max_maxima;
+    a.max_filter = P->max_filter; a.vbq = P->vote_bbox_quat; a.mbq = P->max_bbox_quat_out;
+    a.n_max = io.n_maxima; a.mpos = io.max_pos; a.mw = io.max_weight; a.mcls = io.max_class; a.minst = io.max_instance;
+    a.miw = io.max_instance_weight; a.mbs = io.max_bbox_size; a.mnv = io.max_n_votes; a.class_score = io.class_score;
+    a.truncated = ctx->truncated_d;
+    const size_t n_oc = (size_t)io.n_obj * P->n_classes;
+    a.rec = (float*)ism_scratch(ctx, SCR_MAX_REC, n_oc * MX_MAXM_C * MX_REC * sizeof(float) + n_oc * sizeof(int32_t));
+    if (!a.rec) return ISMHIP_ERR_NOMEM;
+    a.rec_count = (int32_t*)(a.rec + n_oc * MX_MAXM_C * MX_REC);
+    if (pl->big) { int rc = big_object_workspace(ctx, io.n_obj, P->n_classes, io.slot_offsets_h, so, io.vote_class, &a.work, &a.work_off, &a.class_count); if (rc != ISMHIP_OK) return rc; }
+    pl->rk = RansacKArgs{};
+    if (io.ransac) {
+        int rc = ransac_kernel_args(ctx, (name + "_ransac").c_str(), io.R, P->n_classes, n_oc, io.max_transform != nullptr, &pl->rk);
+        if (rc != ISMHIP_OK) return rc;
+        a.mtf = io.max_transform; a.rec_tf = pl->rk.rec_tf;
+    }
+    return ISMHIP_OK;
+}
+
+// The back end's kernel, then the shared tail. kern[ransac][big]: its four instantiations, the plain ones taking (args), the RANSAC
+// ones (args, RansacKArgs). lds_cap: the most dynamic LDS any launch of them asks for.
+template <class Args>
+static int maxima_launch(ismhip_ctx* ctx, const MaximaCall& io, MaximaPlan& pl, const char* timer, const char* kernel_name, const void* const (&kern)[2][2],
+                         Args& args, size_t lds_cap, size_t dyn) {
+    const void* k = kern[io.ransac][pl.big];
+    int rc = ism_lds_cap(ctx, k, lds_cap);
+    if (rc != ISMHIP_OK) return rc;
+    TimerScope ts(ctx, timer);
+    void* kargs[] = {&args, &pl.rk};
+    (void)hipLaunchKernel(k, dim3(io.n_obj, pl.a.n_classes), dim3(256), kargs, dyn, ctx->stream);
+    ISM_CHECK_LAUNCH(ctx, kernel_name);
+    hipLaunchKernelGGL(k_finalize_maxima, dim3(io.n_obj), dim3(64), 0, ctx->stream, pl.a);
+    ISM_CHECK_LAUNCH(ctx, "k_finalize_maxima");
+    return ISMHIP_OK;
+}
+
+static int find_maxima_impl(ismhip_ctx* ctx, const MaximaCall& io, const ismhip_maxima_params* P) {
+    MaximaPlan pl;
+    int rc = maxima_setup(ctx, io, P, P && (P->bandwidth > 0.f || P->class_bandwidth_h), P ? P->class_bandwidth_h : nullptr, &pl);
+    if (rc != ISMHIP_OK) return rc;
+    if (P->kernel != ISMHIP_KERNEL_GAUSSIAN && P->kernel != ISMHIP_KERNEL_UNIFORM) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: kernel");
+    MaxArgs& a = pl.a;
+    a.class_bw = pl.class_val; a.bandwidth = P->bandwidth; a.threshold = P->threshold; a.max_iter = P->max_iter;
+    a.kernel = P->kernel; a.suppression = P->suppression;
+    a.filter_radius = P->bandwidth;                                    // MaximaHandler::m_radius = the configured bandwidth (voting_mean_shift.cpp:46)
     a.som_type = P->single_object_max_type; a.obj_centroid = P->object_centroid; a.obj_radius = P->object_radius;
     if (a.som_type < ISMHIP_SOM_MEANSHIFT || a.som_type > ISMHIP_SOM_COMPLETE_VOTING_SPACE) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: single_object_max_type");
     if (a.som_type != ISMHIP_SOM_MEANSHIFT && (!a.obj_centroid || (a.som_type == ISMHIP_SOM_MODEL_RADIUS && !a.obj_radius)))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima: single-object max types need object_centroid (and object_radius for MODEL_RADIUS)");
-    a.n_max = n_maxima_out; a.mpos = max_pos_out; a.mw = max_weight_out; a.mcls = max_class_out; a.minst = max_instance_out;
-    a.miw = max_instance_weight_out; a.mbs = max_bbox_size_out; a.mnv = max_n_votes_out; a.class_score = class_score_out;
-    const void* lds_kernel = ransac ? (const void*)k_find_maxima_ransac<false> : (const void*)k_find_maxima<false>;
-    if (!ctx->attr_done.count(lds_kernel)) {      // the attribute is per device: remembered per ctx, not per process
-        ISM_HIP(ctx, hipFuncSetAttribute(lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-        ctx->attr_done.insert(lds_kernel);
-    }
-    a.truncated = ctx->truncated_d;
-    a.work = nullptr; a.work_off = nullptr; a.class_count = nullptr;
-    if (big) { int rc = big_object_workspace(ctx, n_obj, P->n_classes, slot_offsets_h, so, vote_class, &a.work, &a.work_off, &a.class_count); if (rc != ISMHIP_OK) return rc; }
-    const size_t n_oc = (size_t)n_obj * P->n_classes;
-    a.rec = (float*)ism_scratch(ctx, SCR_MAX_REC, n_oc * MX_MAXM_C * MX_REC * sizeof(float) + n_oc * sizeof(int32_t));
-    if (!a.rec) return ISMHIP_ERR_NOMEM;
-    a.rec_count = (int32_t*)(a.rec + n_oc * MX_MAXM_C * MX_REC);
-    a.mtf = nullptr; a.rec_tf = nullptr;
-    RansacKArgs rk{};
-    if (ransac) {
-        int rc = ransac_kernel_args(ctx, "find_maxima_ransac", R, P->n_classes, n_oc, max_transform_out != nullptr, &rk);
-        if (rc != ISMHIP_OK) return rc;
-        a.mtf = max_transform_out; a.rec_tf = rk.rec_tf;
-    }
-    TimerScope ts(ctx, "maxima");
-    if (ransac) {
-        if (big) hipLaunchKernelGGL(k_find_maxima_ransac<true>, dim3(n_obj, P->n_classes), dim3(256), 0, ctx->stream, a, rk);
-        else hipLaunchKernelGGL(k_find_maxima_ransac<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, a, rk);
-    }
-    else if (big) hipLaunchKernelGGL(k_find_maxima<true>, dim3(n_obj, P->n_classes), dim3(256), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(k_find_maxima<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, a);
-    ISM_CHECK_LAUNCH(ctx, "k_find_maxima");
-    hipLaunchKernelGGL(k_finalize_maxima, dim3(n_obj), dim3(64), 0, ctx->stream, a);
-    ISM_CHECK_LAUNCH(ctx, "k_finalize_maxima");
-    return ISMHIP_OK;
+    // LDS: 65 B per vote slot; big objects keep the arrays in the workspace and ask for none
+    const size_t dyn = pl.big ? 0 : (size_t)a.cap * (4 * 4 + 2 * 4 + 8 + 16 + 16 + 1);
+    static const void* const kern[2][2] = {{(const void*)k_find_maxima<false>, (const void*)k_find_maxima<true>},
+                                           {(const void*)k_find_maxima_ransac<false>, (const void*)k_find_maxima_ransac<true>}};
+    return maxima_launch(ctx, io, pl, "maxima", "k_find_maxima", kern, a, 140 * 1024, dyn);
+}
+
+static int hough3d_maxima_impl(ismhip_ctx* ctx, const MaximaCall& io, const ismhip_hough_params* P) {
+    MaximaPlan pl;
+    int rc = maxima_setup(ctx, io, P, P && (P->bin_size > 0.f || P->class_bin_h), P ? P->class_bin_h : nullptr, &pl);
+    if (rc != ISMHIP_OK) return rc;
+    for (int d = 0; d < 3; ++d) if (!(P->max_coord[d] > P->min_coord[d])) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: MaxCoord must exceed MinCoord");
+    if (P->class_bin_h) for (int c = 0; c < P->n_classes; ++c) if (!(P->class_bin_h[c] > 0.f)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: bin size");
+    if (P->max_filter == ISMHIP_MAXFILTER_MERGE && P->class_bin_h) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "hough3d_maxima: MaxFilterType Merge with per-class bin sizes not built");
+    MaxArgs& a = pl.a;
+    a.filter_radius = P->bin_size / 2;                                 // MaximaHandler::setRadius(BinSize[0] / 2) (voting_hough_3d.cpp:45)
+    a.bandwidth = P->bin_size / 2;                                     // getSearchDistForClass of the Merge filter (class_bw stays NULL)
+    // LDS: 37 B per vote slot; the rest of ~150 KB holds the accumulator tile (edge 16 .. 24 bins including the halo)
+    const size_t vote_bytes = pl.big ? 0 : (size_t)a.cap * (4 * 4 + 2 * 4 + 8 + 4 + 1);
+    int edge = 24;
+    while (edge > 8 && ((vote_bytes + 15) / 16 * 16 + (size_t)edge * edge * edge * 8) > 150 * 1024) --edge;
+    const size_t dyn = (vote_bytes + 15) / 16 * 16 + (size_t)edge * edge * edge * 8 + 16;
+    HoughArgs h;
+    h.vbq = a.vbq;
+    h.slot_off = a.slot_off; h.vpos = a.vpos; h.vw = a.vw; h.vcls = a.vcls; h.vinst = a.vinst; h.vbs = a.vbs;
+    h.n_classes = a.n_classes; h.class_bin = pl.class_val; h.bin = P->bin_size;
+    for (int d = 0; d < 3; ++d) { h.minc[d] = P->min_coord[d]; h.maxc[d] = P->max_coord[d]; }
+    h.use_int = P->use_interpolation ? 1 : 0; h.rel = P->rel_threshold; h.min_votes = a.min_votes; h.cap = a.cap; h.tile_edge = edge;
+    h.rec = a.rec; h.rec_count = a.rec_count;
+    h.work = a.work; h.work_off = a.work_off; h.class_count = a.class_count; h.truncated = a.truncated;
+    static const void* const kern[2][2] = {{(const void*)k_hough3d<false>, (const void*)k_hough3d<true>},
+                                           {(const void*)k_hough3d_ransac<false>, (const void*)k_hough3d_ransac<true>}};
+    return maxima_launch(ctx, io, pl, "hough3d", "k_hough3d", kern, h, 152 * 1024, dyn);
 }
 
 extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
@@ -1075,9 +1087,9 @@ extern "C" int ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* sl
                                   int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
                                   int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                                   float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
-    return find_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
-                            max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
-                            false, nullptr, nullptr);
+    return find_maxima_impl(ctx, {"find_maxima", n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, n_maxima_out, max_pos_out,
+                                  max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                                  false, nullptr, nullptr}, P);
 }
 extern "C" int ismhip_find_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                                          const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
@@ -1087,97 +1099,10 @@ extern "C" int ismhip_find_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint3
                                          int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                                          float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
                                          const ismhip_ransac_params* R, float* max_transform_out) {
-    if (!R) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "find_maxima_ransac: ransac parameters missing");
-    return find_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
-                            max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
-                            true, R, max_transform_out);
+    return find_maxima_impl(ctx, {"find_maxima", n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, n_maxima_out, max_pos_out,
+                                  max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                                  true, R, max_transform_out}, P);
 }
-
-static int hough3d_maxima_impl(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
-                                     const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
-                                     const int32_t* vote_instance, const float* vote_bbox_size,
-                                     const ismhip_hough_params* P,
-                                     int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
-                                     int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
-                                     float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
-                                     bool ransac, const ismhip_ransac_params* R, float* max_transform_out) {
-    if (!ctx || n_obj <= 0 || !slot_offsets_h || !vote_pos || !vote_weight || !vote_class || !vote_instance || !P ||
-        !n_maxima_out || !max_pos_out || !max_weight_out || !max_class_out || !max_instance_out || !max_instance_weight_out ||
-        !max_n_votes_out || !class_score_out || P->n_classes <= 0 || P->max_maxima <= 0 || !(P->bin_size > 0.f || P->class_bin_h))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: bad argument");
-    if (P->n_classes > MX_MAXC) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "hough3d_maxima: more than 256 classes not built");
-    for (int d = 0; d < 3; ++d) if (!(P->max_coord[d] > P->min_coord[d])) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: MaxCoord must exceed MinCoord");
-    if (P->class_bin_h) for (int c = 0; c < P->n_classes; ++c) if (!(P->class_bin_h[c] > 0.f)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: bin size");
-    uint32_t max_slots = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (slot_offsets_h[o + 1] < slot_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: offsets not monotone");
-        max_slots = std::max(max_slots, slot_offsets_h[o + 1] - slot_offsets_h[o]);
-    }
-    int cap = 64; while ((uint32_t)cap < max_slots) cap <<= 1;
-    const bool big = cap > MX_LDS_SLOTS;
-    // LDS: 37 B per vote slot; the rest of ~150 KB holds the accumulator tile (edge 16 .. 24 bins including the halo)
-    const size_t vote_bytes = big ? 0 : (size_t)cap * (4 * 4 + 2 * 4 + 8 + 4 + 1);
-    int edge = 24;
-    while (edge > 8 && ((vote_bytes + 15) / 16 * 16 + (size_t)edge * edge * edge * 8) > 150 * 1024) --edge;
-    const size_t dyn = (vote_bytes + 15) / 16 * 16 + (size_t)edge * edge * edge * 8 + 16;
-    uint32_t* so = ism_upload_offsets(ctx, SCR_SLOT_OFF, slot_offsets_h, n_obj + 1);
-    if (!so) return ISMHIP_ERR_HIP;
-    float* cbin = nullptr;
-    if (P->class_bin_h) {
-        cbin = (float*)ism_scratch(ctx, SCR_CLASS_BW, (size_t)P->n_classes * 4);
-        if (!cbin) return ISMHIP_ERR_NOMEM;
-        ISM_HIP(ctx, hipMemcpyAsync(cbin, P->class_bin_h, (size_t)P->n_classes * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    const size_t n_oc = (size_t)n_obj * P->n_classes;
-    float* rec = (float*)ism_scratch(ctx, SCR_MAX_REC, n_oc * MX_MAXM_C * MX_REC * sizeof(float) + (n_oc + 1) * sizeof(int32_t));
-    if (!rec) return ISMHIP_ERR_NOMEM;
-    HoughArgs h;
-    h.slot_off = so; h.vpos = vote_pos; h.vw = vote_weight; h.vcls = vote_class; h.vinst = vote_instance; h.vbs = vote_bbox_size;
-    h.n_classes = P->n_classes; h.class_bin = cbin; h.bin = P->bin_size;
-    for (int d = 0; d < 3; ++d) { h.minc[d] = P->min_coord[d]; h.maxc[d] = P->max_coord[d]; }
-    h.use_int = P->use_interpolation ? 1 : 0; h.rel = P->rel_threshold; h.min_votes = P->min_votes_threshold; h.cap = cap; h.tile_edge = edge;
-    h.rec = rec; h.rec_count = (int32_t*)(rec + n_oc * MX_MAXM_C * MX_REC); h.overflow = h.rec_count + n_oc;
-    MaxArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.n_classes = P->n_classes; a.min_threshold = P->min_threshold; a.best_k = P->best_k; a.max_maxima = P->max_maxima;
-    if (P->max_filter != ISMHIP_MAXFILTER_NONE && P->max_filter != ISMHIP_MAXFILTER_SIMPLE && P->max_filter != ISMHIP_MAXFILTER_MERGE)
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: MaxFilterType");
-    if (P->max_filter == ISMHIP_MAXFILTER_MERGE && P->class_bin_h) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "hough3d_maxima: MaxFilterType Merge with per-class bin sizes not built");
-    a.max_filter = P->max_filter; a.filter_radius = P->bin_size / 2;   // MaximaHandler::setRadius(BinSize[0] / 2) (voting_hough_3d.cpp:45)
-    a.bandwidth = P->bin_size / 2;                                     // getSearchDistForClass of the Merge filter (class_bw stays NULL)
-    if ((P->vote_bbox_quat == nullptr) != (P->max_bbox_quat_out == nullptr)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima: vote_bbox_quat and max_bbox_quat_out go together");
-    h.vbq = P->vote_bbox_quat; a.mbq = P->max_bbox_quat_out;
-    a.n_max = n_maxima_out; a.mpos = max_pos_out; a.mw = max_weight_out; a.mcls = max_class_out; a.minst = max_instance_out;
-    a.miw = max_instance_weight_out; a.mbs = max_bbox_size_out; a.mnv = max_n_votes_out; a.class_score = class_score_out;
-    a.rec = h.rec; a.rec_count = h.rec_count;
-    const void* hk = ransac ? (big ? (const void*)k_hough3d_ransac<true> : (const void*)k_hough3d_ransac<false>)
-                            : (big ? (const void*)k_hough3d<true> : (const void*)k_hough3d<false>);
-    if (!ctx->attr_done.count(hk)) {
-        ISM_HIP(ctx, hipFuncSetAttribute(hk, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
-        ctx->attr_done.insert(hk);
-    }
-    h.work = nullptr; h.work_off = nullptr; h.class_count = nullptr; h.truncated = ctx->truncated_d; a.truncated = ctx->truncated_d;
-    if (big) { int rc = big_object_workspace(ctx, n_obj, P->n_classes, slot_offsets_h, so, vote_class, &h.work, &h.work_off, &h.class_count); if (rc != ISMHIP_OK) return rc; }
-    RansacKArgs rk{};
-    if (ransac) {
-        int rc = ransac_kernel_args(ctx, "hough3d_maxima_ransac", R, P->n_classes, n_oc, max_transform_out != nullptr, &rk);
-        if (rc != ISMHIP_OK) return rc;
-        a.mtf = max_transform_out; a.rec_tf = rk.rec_tf;
-    }
-    TimerScope ts(ctx, "hough3d");
-    ISM_HIP(ctx, hipMemsetAsync(h.overflow, 0, 4, ctx->stream));
-    if (ransac) {
-        if (big) hipLaunchKernelGGL(k_hough3d_ransac<true>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h, rk);
-        else hipLaunchKernelGGL(k_hough3d_ransac<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h, rk);
-    }
-    else if (big) hipLaunchKernelGGL(k_hough3d<true>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h);
-    else hipLaunchKernelGGL(k_hough3d<false>, dim3(n_obj, P->n_classes), dim3(256), dyn, ctx->stream, h);
-    ISM_CHECK_LAUNCH(ctx, "k_hough3d");
-    hipLaunchKernelGGL(k_finalize_maxima, dim3(n_obj), dim3(64), 0, ctx->stream, a);
-    ISM_CHECK_LAUNCH(ctx, "k_finalize_maxima");
-    return ISMHIP_OK;
-}
-
 extern "C" int ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                                      const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
                                      const int32_t* vote_instance, const float* vote_bbox_size,
@@ -1185,9 +1110,9 @@ extern "C" int ismhip_hough3d_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t*
                                      int32_t* n_maxima_out, float* max_pos_out, float* max_weight_out,
                                      int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                                      float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out) {
-    return hough3d_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
-                               max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
-                               false, nullptr, nullptr);
+    return hough3d_maxima_impl(ctx, {"hough3d_maxima", n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, n_maxima_out, max_pos_out,
+                                     max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                                     false, nullptr, nullptr}, P);
 }
 extern "C" int ismhip_hough3d_maxima_ransac(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                                             const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
@@ -1197,8 +1122,7 @@ extern "C" int ismhip_hough3d_maxima_ransac(ismhip_ctx* ctx, int n_obj, const ui
                                             int32_t* max_class_out, int32_t* max_instance_out, float* max_instance_weight_out,
                                             float* max_bbox_size_out, int32_t* max_n_votes_out, float* class_score_out,
                                             const ismhip_ransac_params* R, float* max_transform_out) {
-    if (!R) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "hough3d_maxima_ransac: ransac parameters missing");
-    return hough3d_maxima_impl(ctx, n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, P, n_maxima_out, max_pos_out,
-                               max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
-                               true, R, max_transform_out);
+    return hough3d_maxima_impl(ctx, {"hough3d_maxima", n_obj, slot_offsets_h, vote_pos, vote_weight, vote_class, vote_instance, vote_bbox_size, n_maxima_out, max_pos_out,
+                                     max_weight_out, max_class_out, max_instance_out, max_instance_weight_out, max_bbox_size_out, max_n_votes_out, class_score_out,
+                                     true, R, max_transform_out}, P);
 }

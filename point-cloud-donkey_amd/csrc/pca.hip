@@ -198,7 +198,7 @@ int launch_rotate(ismhip_ctx* ctx, const float* x, int n, int ldx, int kdim, con
     const void* kern = nct <= 4 ? (const void*)k_rotate_f16t<4> : nct <= 6 ? (const void*)k_rotate_f16t<6> : (const void*)k_rotate_f16t<8>;
     const int nt = nct <= 4 ? 4 : nct <= 6 ? 6 : 8;
     const size_t lds = (size_t)(128 + nt * 32) * ROT_LD * sizeof(float);
-    if (!ctx->attr_done.count(kern)) { ISM_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ctx->attr_done.insert(kern); }
+    { const int rc = ism_lds_cap(ctx, kern, lds); if (rc != ISMHIP_OK) return rc; }
     const unsigned blocks = (unsigned)((((size_t)n + 255) / 256 * 256) / 128);
     void* args[] = {&x, &n, &ldx, &kdim, &rmat, &m, &scale, &dst};
     ISM_HIP(ctx, hipLaunchKernel(kern, dim3(blocks), dim3(256), args, lds, ctx->stream));

@@ -416,10 +416,8 @@ static int train_from_activations(ismhip_ctx* ctx, int metric, int n, int dim, c
                        vote_weight, overflow);
     {   // codewords with 2049 .. 32768 votes: clustered codebooks, but also a hub word or many duplicate descriptors with Clustering
         // "None" and k > 1 / KNNRule (every tie goes to the lowest row) -- the kernel skips every smaller word by itself
-        if (!ctx->attr_done.count((const void*)k_tr_weights_big)) {
-            TR_HIP(hipFuncSetAttribute((const void*)k_tr_weights_big, hipFuncAttributeMaxDynamicSharedMemorySize, TR_MAXM_BIG * 4));
-            ctx->attr_done.insert((const void*)k_tr_weights_big);
-        }
+        const int rc = ism_lds_cap(ctx, (const void*)k_tr_weights_big, TR_MAXM_BIG * 4);
+        if (rc != ISMHIP_OK) return done(rc);
         hipLaunchKernelGGL(k_tr_weights_big, dim3(1024), dim3(256), TR_MAXM_BIG * 4, st, n_votes_p, vote_word, vote_off, vote_feature, vote_xyz, lrf9, kpx, kpy, kpz, center,
                            vote_weight);
     }

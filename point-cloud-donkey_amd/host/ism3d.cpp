@@ -928,17 +928,18 @@ void VotingMeanShift::iFindMaxima(DeviceSession& s, std::vector<std::vector<Voti
     MaximaBuffers B; B.M = M; B.reserve(s.n_obj, C);
     if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }              // voting.cpp:210-215
     P.single_object_max_type = singleObjectMaxType(); P.object_centroid = s.obj_cen.as<float>(); P.object_radius = s.obj_rad.as<float>();
+    auto call = [&](auto entry, auto... filter_args) {          // the plain entry, or the RANSAC one with its two arguments more
+        return entry(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
+                     s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
+                     B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), filter_args...);
+    };
     if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127: the filter runs inside the maxima search
         const std::vector<float> class_thr = ransacThresholdPerClass(C);
         ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
-        s.check(ismhip_find_maxima_ransac(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                                          s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                                          B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), &R, nullptr), "ismhip_find_maxima_ransac");
+        s.check(call(ismhip_find_maxima_ransac, &R, (float*)nullptr), "ismhip_find_maxima_ransac");
         s.sync();                                               // class_thr is read by the launch
     } else
-    s.check(ismhip_find_maxima(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                               s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                               B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>()), "ismhip_find_maxima");
+    s.check(call(ismhip_find_maxima), "ismhip_find_maxima");
     if (collectMaxima(s, B, out, m_averageRotation) || M == 1024) break;
     }
 }
@@ -992,17 +993,18 @@ void VotingHough3D::iFindMaxima(DeviceSession& s, std::vector<std::vector<Voting
     P.max_filter = maxFilter();
     MaximaBuffers B; B.M = M; P.max_maxima = B.M; B.reserve(s.n_obj, C);
     if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }
+    auto call = [&](auto entry, auto... filter_args) {          // the plain entry, or the RANSAC one with its two arguments more
+        return entry(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
+                     s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
+                     B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), filter_args...);
+    };
     if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127
         const std::vector<float> class_thr = ransacThresholdPerClass(C);
         ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
-        s.check(ismhip_hough3d_maxima_ransac(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                                             s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                                             B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), &R, nullptr), "ismhip_hough3d_maxima_ransac");
+        s.check(call(ismhip_hough3d_maxima_ransac, &R, (float*)nullptr), "ismhip_hough3d_maxima_ransac");
         s.sync();                                               // class_thr is read by the launch
     } else
-    s.check(ismhip_hough3d_maxima(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                                  s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                                  B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>()), "ismhip_hough3d_maxima");
+    s.check(call(ismhip_hough3d_maxima), "ismhip_hough3d_maxima");
     if (collectMaxima(s, B, out, m_averageRotation) || M == 1024) break;
     }
 }
