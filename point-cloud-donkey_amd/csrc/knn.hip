@@ -16,12 +16,16 @@
 //       knn_cand.hip     k_knn_l2_mfma    f32 MFMA (exact fma chain)                   ISMHIP_KNN_MODE=f32: the independent route used by the tests
 //                        k_knn_chi2       VALU 64x64 tile, v_rcp_f32                   chi-square is not a contraction
 //  2. this file: the query / codebook images the candidate kernels read (k_split_bf16, k_absmax, k_to_f16, k_to_f16_tiled,
-//     k_scale_norms, k_pad_rows, k_sqrt_rows), knn_plan / run_knn, and k_knn_rerank (_pca, _hell) — one wave per query: candidates
-//     that can still matter are recomputed with the FLANN functor's own summation order (bit-identical to the CPU functor), the k
-//     smallest (distance, row) pairs are selected (ties: lowest row), and the result is PROVEN slot by slot from the slot bounds and a
-//     rigorous bound of the candidate kernel's error; a (query, slot) pair that cannot be proven is queued for
+//     k_scale_norms, k_pad_rows, k_sqrt_rows; the f16 scale rule and the tiled layout are defined in knn_internal.h), knn_plan /
+//     run_knn, and k_knn_rerank (_pca, _hell) — one wave per query: candidates that can still matter are recomputed with the FLANN
+//     functor's own summation order (bit-identical to the CPU functor), the k smallest (distance, row) pairs are selected (ties:
+//     lowest row), and the result is PROVEN slot by slot from the slot bounds and a rigorous bound of the candidate kernel's error;
+//     a (query, slot) pair that cannot be proven is queued for
 //  3. k_knn_fallback / k_knn_fallback_merge — exact scan of the queued slots' rows. Rare for descriptor data, the rule for
 //     adversarial inputs (un-normalised magnitudes, hundreds of near-duplicates): it keeps the answer exact in every case.
+//  The three re-rank kernels differ in how they pick the candidates to evaluate and in their proof; what they share is written once
+//  (knn_load_cand, knn_select_write, knn_queue_unproven here; wave_norm2, knn_eps_s_raw in knn_internal.h). run_knn is the phases in
+//  that order on one stream: knn_carve_scratch, knn_query_images, knn_launch_candidates, knn_rerank_prove, knn_exact_scan.
 //  Also here: the two-stage and the Hellinger (chi-square) drivers, ismhip_knn, _ratio, _rule.
 //       knn_threshold.hip  ismhip_knn_threshold  radius search: EMIT sweep + k_thr_* 
 //       knn_large_k.hip    ismhip_knn_large_k    any K up to 1024: seeded EMIT sweep + certificate, exact top-K scan
@@ -50,10 +54,8 @@ __global__ void k_split_bf16(const float* __restrict__ src, int n, int dim, int 
 }
 
 
-// ---- f16 image (NTERM = 1). x -> RN_f16(x * s), s a power of two that puts the largest |element| into [2^13, 2^14) (clamped to
-// 2^+-40), so neither overflow nor the fp16 subnormal range matters: element error <= 2^-11 |x| + 2^-14 / s, where the second
-// term assumes the worst (subnormal results flushed to zero). absmax is kept as float bits (non-negative floats order like uints;
-// NaN/inf sort last and select s = 1, the affected scores become NaN/inf and those queries take the exact path).
+// ---- f16 image (NTERM = 1; scale rule and layout: knn_internal.h). absmax is kept as float bits (non-negative floats order like
+// uints; NaN/inf sort last and select s = 1, the affected scores become NaN/inf and those queries take the exact path).
 __global__ void k_absmax(const float* __restrict__ src, int n, int dim, int ld, uint32_t* __restrict__ out_bits) {
     uint32_t m = 0u;
     const size_t tot = (size_t)n * dim;
@@ -84,53 +86,40 @@ __global__ void k_absmax(const float* __restrict__ src, int n, int dim, int ld, 
         if (m) atomicMax(out_bits, m);
     }
 }
-__host__ __device__ inline float f16_scale_for(uint32_t absmax_bits) {
-    const int e = (int)(absmax_bits >> 23);          // biased exponent; 0 = zero/subnormal, 255 = inf/NaN
-    if (e == 0 || e == 255) return 1.0f;
-    int k = 13 - (e - 127);                          // absmax * 2^k in [2^13, 2^14)
-    k = k > 40 ? 40 : (k < -40 ? -40 : k);
-    union { uint32_t u; float f; } v; v.u = (uint32_t)(127 + k) << 23;
-    return v.f;
-}
-// sc[0] = absmax bits (in), sc[1] = -2 / (s * other_scale) (out), sc[2] = 2^-14 / s (out: worst-case absolute element error)
-__global__ void k_to_f16(const float* __restrict__ src, int n, int dim, int ld, int n_pad, int dim_pad,
-                         uint32_t* __restrict__ sc, float other_scale, u16* __restrict__ dst) {
+// sc[0] = absmax bits (in), sc[1] = -2 / (s * other_scale) (out), sc[2] = 2^-14 / s (out: worst-case absolute element error);
+// returns s. Thread 0 of the grid writes the two.
+__device__ __forceinline__ float f16_image_scalars(uint32_t* __restrict__ sc, float other_scale, size_t i) {
     const float s = f16_scale_for(sc[0]);
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) {
         ((float*)sc)[1] = -2.0f / (s * other_scale);
-        ((float*)sc)[2] = (sc[0] >> 23) == 255u ? __builtin_inff() : 6.103515625e-05f / s;     // inf/NaN in the batch: nothing is provable
+        ((float*)sc)[2] = (sc[0] >> 23) == 255u ? __builtin_inff() : F16_FLUSH / s;     // inf/NaN in the batch: nothing is provable
     }
-    if (i >= (size_t)n_pad * dim_pad) return;
-    const int row = (int)(i / dim_pad), col = (int)(i % dim_pad);
-    float x = 0.f;
-    if (row < n && col < dim) x = src[(size_t)row * ld + col];
-    const _Float16 hx = (_Float16)(x * s);            // v_cvt_f16_f32, round to nearest even
-    dst[i] = __builtin_bit_cast(u16, hx);
+    return s;
 }
-
-// The same conversion into the layout k_knn_l2_ring16 streams: [256-row tile][32-k slice][row][4 x 16-byte
-// segments], i.e. every (tile, slice) is one contiguous 16 KB block that already is the LDS image (segment p of row r holds
-// logical segment p ^ F[(r>>2)&3], F = {0,2,3,1}). A DMA instruction then copies 1 KB of consecutive, fully used 128-byte lines; with a row-major image each
-// 32-k slice touches only half of every line and the other half is fetched again one slice later.
-__global__ void k_to_f16_tiled(const float* __restrict__ src, int n, int dim, int ld, int n_tiles, int nk,
-                               uint32_t* __restrict__ sc, float other_scale, u16* __restrict__ dst) {
-    const float s = f16_scale_for(sc[0]);
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        ((float*)sc)[1] = -2.0f / (s * other_scale);
-        ((float*)sc)[2] = (sc[0] >> 23) == 255u ? __builtin_inff() : 6.103515625e-05f / s;
-    }
-    if (i >= (size_t)n_tiles * nk * 8192) return;
-    const int e = (int)(i & 7), p = (int)((i >> 3) & 3), r = (int)((i >> 5) & 255);
-    const size_t blk = i >> 13;
-    const int kc = (int)(blk % nk); const size_t tile = blk / nk;
-    const int col = kc * 32 + ((p ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3)) << 3) + e;      // F = {0,2,3,1}[(r>>2)&3]: conflict-free for both MFMA shapes
-    const size_t row = tile * 256 + r;
+// element (row, col) of the image: zero beyond n rows / dim columns
+__device__ __forceinline__ u16 f16_image_element(const float* __restrict__ src, int n, int dim, int ld, size_t row, int col, float s) {
     float x = 0.f;
     if (row < (size_t)n && col < dim) x = src[row * ld + col];
-    const _Float16 hx = (_Float16)(x * s);
-    dst[i] = __builtin_bit_cast(u16, hx);
+    const _Float16 hx = (_Float16)(x * s);            // v_cvt_f16_f32, round to nearest even
+    return __builtin_bit_cast(u16, hx);
+}
+__global__ void k_to_f16(const float* __restrict__ src, int n, int dim, int ld, int n_pad, int dim_pad,
+                         uint32_t* __restrict__ sc, float other_scale, u16* __restrict__ dst) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float s = f16_image_scalars(sc, other_scale, i);
+    if (i >= (size_t)n_pad * dim_pad) return;
+    dst[i] = f16_image_element(src, n, dim, ld, i / dim_pad, (int)(i % dim_pad), s);
+}
+// The same conversion into the tiled layout k_knn_l2_ring16 streams (knn_internal.h): thread i writes half i of the image
+__global__ void k_to_f16_tiled(const float* __restrict__ src, int n, int dim, int ld, int n_tiles, int nk,
+                               uint32_t* __restrict__ sc, float other_scale, u16* __restrict__ dst) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float s = f16_image_scalars(sc, other_scale, i);
+    if (i >= f16t_halves(n_tiles, nk)) return;
+    const int e = (int)(i & 7), p = (int)((i >> 3) & 3), r = (int)((i / F16T_KB) % F16T_ROWS);
+    const size_t blk = i / F16T_BLOCK;
+    const int col = (int)(blk % nk) * F16T_KB + ((p ^ f16t_swizzle(r)) << 3) + e;          // the swizzle is its own inverse
+    dst[i] = f16_image_element(src, n, dim, ld, blk / nk * F16T_ROWS + r, col, s);
 }
 
 // |c|^2 / out_scale for every codebook row (out_scale is known on the device only: it holds the batch's query scale)
@@ -187,6 +176,67 @@ __global__ __launch_bounds__(256) void k_knn_merge_splits(int nq, const float* _
 
 #include "functor.h"
 
+// The 16-word counter block at the head of the queue scratch (flag_count of the kernels), zeroed before every search:
+enum KnnCounter {
+    KNN_CNT_QUERIES = 0, KNN_CNT_ITEMS = 1,   // the queue: unproven queries, their (query, slot) work items (ctx->knn_stats reads both)
+    KNN_CNT_QSC = 4,                          // f16 mode, three words: absmax bits of the query batch, -2 / (s_q s_c), 2^-14 / s_q (k_to_f16)
+    KNN_CNT_NEGATIVE = 12,                    // chi-square: some query element is negative (k_any_negative)
+    KNN_CNT_WORDS = 16
+};
+// Slot -> rows layout of the exact scan, chosen by knn_plan and decoded by k_knn_fallback (its wr_rows). The two positive values ARE
+// the rows per wave-row block of the 32x32 MFMA tile (MI * 32): 64 on the 128-row tile, 128 on the 256-row tile.
+enum KnnFbLayout { KNN_FB_TILE128 = 64, KNN_FB_TILE256 = 128, KNN_FB_RING = -1, KNN_FB_ALL = -2, KNN_FB_RING_HALF = -3 };
+
+// ---- steps the three re-rank kernels share (one wave per query, one candidate / bound slot per lane) ------------------------------
+// candidate j of query qi: its row and approximate score, or -1 and +inf (j beyond the list, empty entry, row out of range)
+__device__ __forceinline__ int knn_load_cand(const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int qi, int cand_stride,
+                                             int j, int n_cand, int n_words, float& av) {
+    int id = -1; av = __builtin_inff();
+    if (j < n_cand) { id = cand_idx[(size_t)qi * cand_stride + j]; av = cand_val[(size_t)qi * cand_stride + j]; }
+    if (!(id >= 0 && id < n_words)) { id = -1; av = __builtin_inff(); }
+    return id;
+}
+// The k smallest of the wave's keys (CPL per lane; ~0 = none; distances are >= 0 or NaN: positive float bit patterns order like
+// unsigned integers, ties go to the lowest row) become the query's result, -1 / NaN where the keys ran short (k_knn_fallback_merge
+// ends the same way on its private lists). Returns whether there were k; dk = the k-th distance.
+template <int CPL>
+__device__ __forceinline__ bool knn_select_write(unsigned long long* key, int qi, int k, int lane, int32_t* __restrict__ idx_out, float* __restrict__ dist_out, float& dk) {
+    bool have_k = true;
+    dk = 0.f;
+    for (int j = 0; j < k; ++j) {
+        unsigned long long lm = key[0];
+#pragma unroll
+        for (int c = 1; c < CPL; ++c) lm = key[c] < lm ? key[c] : lm;
+        const unsigned long long mn = wave_min_u64(lm);
+        if (lane == 0) {
+            if (mn == ~0ull) { idx_out[(size_t)qi * k + j] = -1; dist_out[(size_t)qi * k + j] = __builtin_nanf(""); }
+            else { idx_out[(size_t)qi * k + j] = (int)(mn & 0xffffffffull); dist_out[(size_t)qi * k + j] = __uint_as_float((unsigned)(mn >> 32)); }
+        }
+        if (mn == ~0ull) have_k = false; else dk = __uint_as_float((unsigned)(mn >> 32));
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) if (key[c] == mn) key[c] = ~0ull;       // rows are unique among candidates, so exactly one retires
+    }
+    return have_k;
+}
+// queue: one record per unproven query {query, first item, #items} and one work item {query, slot} per failing slot
+__device__ __forceinline__ void knn_queue_unproven(bool viol, int qi, int lane, uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
+    const unsigned long long vmask = __ballot(viol);
+    if (vmask != 0ull) {
+        const int nv = __popcll(vmask);
+        uint32_t ibase = 0;
+        if (lane == 0) {
+            const uint32_t qs = atomicAdd(&flag_count[KNN_CNT_QUERIES], 1u);
+            ibase = atomicAdd(&flag_count[KNN_CNT_ITEMS], (uint32_t)nv);
+            qrec[3 * (size_t)qs] = (uint32_t)qi; qrec[3 * (size_t)qs + 1] = ibase; qrec[3 * (size_t)qs + 2] = (uint32_t)nv;
+        }
+        ibase = __shfl(ibase, 0, 64);
+        if (viol) {
+            const uint32_t it = ibase + __popcll(vmask & ((1ull << lane) - 1ull));
+            items[2 * (size_t)it] = (uint32_t)qi; items[2 * (size_t)it + 1] = (uint32_t)lane;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ words, int dim, int dim_pad, int n_words,
                                                     const float* __restrict__ q, int nq, int ldq, int metric,
                                                     const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
@@ -197,15 +247,11 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
     if (qi >= nq) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
-    // |q|^2 by a wave sum (needed by the error bounds below)
-    float qn2 = 0.f;
-    for (int i = lane; i < dim; i += 64) { const float v = qp[i]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
+    const float qn2 = wave_norm2(qp, dim, lane);          // needed by the error bounds below
     // n_cand <= 64 by construction (host): one candidate per lane. Only candidates whose approximate score is within twice the
     // error bound of the k-th best approximate score can be among the exact k best; the others skip the functor.
-    int id = -1; float av = __builtin_inff();
-    if (lane < n_cand) { id = cand_idx[(size_t)qi * cand_stride + lane]; av = cand_val[(size_t)qi * cand_stride + lane]; }
-    if (!(id >= 0 && id < n_words)) { id = -1; av = __builtin_inff(); }
+    float av;
+    const int id = knn_load_cand(cand_idx, cand_val, qi, cand_stride, lane, n_cand, n_words, av);
     float kth = av;
     {
         float cur = av;                       // k-th smallest approximate score (k <= 4) by k rounds of wave-min
@@ -218,33 +264,24 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
     }
     float slack;
     if (metric == ISMHIP_METRIC_CHI2) slack = 4.f * (((float)dim_pad + 8.f) * KNN_U + vp.ku) * fabsf(kth);
-    else slack = 2.f * (17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2) + 4.f * vp.ku * (qn2 + fabsf(kth) + vp.cmax2);
+    else slack = 2.f * knn_eps_s_raw(vp, qn2) + 4.f * vp.ku * (qn2 + fabsf(kth) + vp.cmax2);
     unsigned long long key = ~0ull;
     {
-        __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+        __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
         float* sT = s_terms[threadIdx.x >> 6];
         unsigned long long need = __ballot(id >= 0 && !(av > kth + slack));     // NaN scores are never skipped
         while (need) {
             const int src = __ffsll((long long)need) - 1; need &= need - 1;
             const int cid = __shfl(id, src, 64);
             const float d = wave_functor(metric, qp, words + (size_t)cid * dim_pad, dim, lane, sT);
-            // distances are >= 0 (or NaN); positive float bit patterns order like unsigned integers
             if (lane == src) key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id;
         }
     }
     // every bound slot (L2: split x 4 lane slots, chi2: split) holds the smallest approximate score that slot dropped
     float bnd = __builtin_inff();
     if (lane < n_bound) bnd = cand_bound[(size_t)qi * n_bound + lane];
-    float dk = 0.f; bool have_k = true;
-    for (int j = 0; j < k; ++j) {
-        const unsigned long long mn = wave_min_u64(key);
-        if (lane == 0) {
-            if (mn == ~0ull) { idx_out[(size_t)qi * k + j] = -1; dist_out[(size_t)qi * k + j] = __builtin_nanf(""); }
-            else { idx_out[(size_t)qi * k + j] = (int)(mn & 0xffffffffull); dist_out[(size_t)qi * k + j] = __uint_as_float((unsigned)(mn >> 32)); }
-        }
-        if (mn == ~0ull) have_k = false; else dk = __uint_as_float((unsigned)(mn >> 32));
-        if (key == mn) key = ~0ull;     // rows are unique among candidates, so exactly one lane retires
-    }
+    float dk;
+    const bool have_k = knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk);
     // Proof of exactness, slot by slot. A codeword dropped by slot b has approximate score >= bnd_b, so
     //   L2  : true distance D >= |q|^2 (1 - 16u) + bnd_b - eps_s,  eps_s = 17u |c|max^2 + (2 dot_rel + 2u) |q||c|max
     //         (|c|^2 by a short tree sum: 16u; K-term fma chain: 1.01 K u on sum|q_i c_i| <= |q||c|; final subtraction: u)
@@ -254,35 +291,19 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
     // A slot whose bound is still +inf dropped nothing -- unless scores overflowed (+inf / NaN scores are never kept): that needs
     // an inf or NaN in |q|^2, |c|max^2 or their product (or in the f16 scales), all of which make the error bound below non-finite.
     bool viol = false;
-    const float eps_chk = metric == ISMHIP_METRIC_CHI2 ? qn2 + vp.cmax2
-                        : 17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2 + qn2;
+    const float eps_chk = metric == ISMHIP_METRIC_CHI2 ? qn2 + vp.cmax2 : knn_eps_s_raw(vp, qn2) + qn2;
     if (lane < n_bound && (bnd != __builtin_inff() || !(eps_chk < __builtin_inff()))) {
         if (!have_k) viol = true;
         else if (metric == ISMHIP_METRIC_CHI2) {
             const float lo = bnd * (1.f - ((float)dim_pad + 8.f) * KNN_U) * (1.f - vp.ku);
             viol = !(dk < lo);
         } else {
-            const float eps_s = 17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2;
+            const float eps_s = knn_eps_s_raw(vp, qn2);
             const float rhs = qn2 * (1.f - 16.f * KNN_U) + bnd - eps_s;
             viol = !(dk < rhs - vp.ku * fabsf(rhs) - 1e-37f);
         }
     }
-    // queue: one record per unproven query {query, first item, #items} and one work item {query, slot} per failing slot
-    const unsigned long long vmask = __ballot(viol);
-    if (vmask != 0ull) {
-        const int nv = __popcll(vmask);
-        uint32_t ibase = 0;
-        if (lane == 0) {
-            const uint32_t qs = atomicAdd(&flag_count[0], 1u);
-            ibase = atomicAdd(&flag_count[1], (uint32_t)nv);
-            qrec[3 * (size_t)qs] = (uint32_t)qi; qrec[3 * (size_t)qs + 1] = ibase; qrec[3 * (size_t)qs + 2] = (uint32_t)nv;
-        }
-        ibase = __shfl(ibase, 0, 64);
-        if (viol) {
-            const uint32_t it = ibase + __popcll(vmask & ((1ull << lane) - 1ull));
-            items[2 * (size_t)it] = (uint32_t)qi; items[2 * (size_t)it + 1] = (uint32_t)lane;
-        }
-    }
+    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
 }
 
 // ---- re-rank + proof for a stage 1 that ran on the ROTATED, TRUNCATED image (pca.hip) --------------------------------------------
@@ -301,24 +322,6 @@ struct PcaVerify {
     float eps_c2, dot2, cmax2;        // eps_acc = eps_c2 + dot2 |q^||c^|max;  cmax2 = max |c^|^2
     float ku;
 };
-__device__ __forceinline__ void knn_queue_unproven(bool viol, int qi, int lane, uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
-    // queue: one record per unproven query {query, first item, #items} and one work item {query, slot} per failing slot
-    const unsigned long long vmask = __ballot(viol);
-    if (vmask != 0ull) {
-        const int nv = __popcll(vmask);
-        uint32_t ibase = 0;
-        if (lane == 0) {
-            const uint32_t qs = atomicAdd(&flag_count[0], 1u);
-            ibase = atomicAdd(&flag_count[1], (uint32_t)nv);
-            qrec[3 * (size_t)qs] = (uint32_t)qi; qrec[3 * (size_t)qs + 1] = ibase; qrec[3 * (size_t)qs + 2] = (uint32_t)nv;
-        }
-        ibase = __shfl(ibase, 0, 64);
-        if (viol) {
-            const uint32_t it = ibase + __popcll(vmask & ((1ull << lane) - 1ull));
-            items[2 * (size_t)it] = (uint32_t)qi; items[2 * (size_t)it + 1] = (uint32_t)lane;
-        }
-    }
-}
 __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict__ words, int dim, int dim_pad, int n_words,
                                                         const float* __restrict__ q, int nq, int ldq,
                                                         const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
@@ -329,18 +332,13 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     if (qi >= nq) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
-    float qn2 = 0.f;
-    for (int i = lane; i < dim; i += 64) { const float v = qp[i]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
-    float qn2h = 0.f;                                                  // |q^|^2 from the image itself (any element order)
-    {
-        const size_t tile = (size_t)(qi >> 8); const int r = qi & 255;
-        for (int i = lane; i < pv.nk * 32; i += 64) {
-            const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[((tile * pv.nk + (i >> 5)) * 256 + r) * 32 + (i & 31)]);
-            qn2h += v * v;
-        }
-        qn2h = wave_sum_f(qn2h) * pv.inv_sq2;
+    const float qn2 = wave_norm2(qp, dim, lane);
+    float qn2h = 0.f;                                                  // |q^|^2 from the image itself (the halves as stored: any element order)
+    for (int i = lane; i < pv.nk * F16T_KB; i += 64) {
+        const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[f16t_stored(qi, pv.nk, i)]);
+        qn2h += v * v;
     }
+    qn2h = wave_sum_f(qn2h) * pv.inv_sq2;
     const float dlt = pv.d_rel * (sqrtf(qn2) * 1.00001f) + pv.dq_abs + pv.dc;
     const float eps_s = (pv.eps_c2 + pv.dot2 * sqrtf(qn2h * pv.cmax2)) * 1.00001f;
     auto lb_of = [&](float s) -> float {
@@ -351,14 +349,13 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
         if (!(t > 0.f)) return 0.f;
         return t * t * pv.inv_sig2 * (1.f - 8.f * KNN_U);
     };
-    int id = -1; float av = __builtin_inff();
-    if (lane < n_cand) { id = cand_idx[(size_t)qi * cand_stride + lane]; av = cand_val[(size_t)qi * cand_stride + lane]; }
-    if (!(id >= 0 && id < n_words)) { id = -1; av = __builtin_inff(); }
+    float av;
+    const int id = knn_load_cand(cand_idx, cand_val, qi, cand_stride, lane, n_cand, n_words, av);
     const float lb = id >= 0 ? lb_of(av) : __builtin_inff();
     bool done = id < 0;
     unsigned long long key = ~0ull;
     {
-        __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+        __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
         float* sT = s_terms[threadIdx.x >> 6];
         float kth = __builtin_inff(); int n_eval = 0;
         for (;;) {
@@ -380,16 +377,8 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     }
     float bnd = __builtin_inff();
     if (lane < n_bound) bnd = cand_bound[(size_t)qi * n_bound + lane];
-    float dk = 0.f; bool have_k = true;
-    for (int j = 0; j < k; ++j) {
-        const unsigned long long mn = wave_min_u64(key);
-        if (lane == 0) {
-            if (mn == ~0ull) { idx_out[(size_t)qi * k + j] = -1; dist_out[(size_t)qi * k + j] = __builtin_nanf(""); }
-            else { idx_out[(size_t)qi * k + j] = (int)(mn & 0xffffffffull); dist_out[(size_t)qi * k + j] = __uint_as_float((unsigned)(mn >> 32)); }
-        }
-        if (mn == ~0ull) have_k = false; else dk = __uint_as_float((unsigned)(mn >> 32));
-        if (key == mn) key = ~0ull;
-    }
+    float dk;
+    const bool have_k = knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk);
     // a slot whose bound is still +inf dropped nothing -- unless scores overflowed, which needs a non-finite |q^|^2 or bound term
     bool viol = false;
     if (lane < n_bound && (bnd != __builtin_inff() || !(eps_s + qn2h + dlt < __builtin_inff()))) {
@@ -439,9 +428,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
     if (qi >= nq) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
-    float qn2 = 0.f;                                                   // |sqrt q|^2
-    for (int i = lane; i < dim; i += 64) { const float v = sq[(size_t)qi * dim_pad + i]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
+    const float qn2 = wave_norm2(sq + (size_t)qi * dim_pad, dim, lane);   // |sqrt q|^2
     const float eps_s = knn_eps_s(vp, qn2);
     auto lb_of = [&](float s) -> float {
         float L = qn2 * (1.f - 16.f * KNN_U) + s - eps_s;
@@ -453,12 +440,10 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
     int id[KNN_HELL_CPL]; float lb[KNN_HELL_CPL], fd[KNN_HELL_CPL]; unsigned long long key[KNN_HELL_CPL];
 #pragma unroll
     for (int c = 0; c < KNN_HELL_CPL; ++c) {
-        const int j = lane + 64 * c;
+        float av;
+        const int x = knn_load_cand(cand_idx, cand_val, qi, cand_stride, lane + 64 * c, n_cand, n_words, av);
         id[c] = -1; lb[c] = __builtin_inff(); fd[c] = __builtin_inff(); key[c] = ~0ull;
-        if (j < n_cand) {
-            const int x = cand_idx[(size_t)qi * cand_stride + j];
-            if (x >= 0 && x < n_words) { id[c] = (int)perm[x]; lb[c] = lb_of(cand_val[(size_t)qi * cand_stride + j]); }
-        }
+        if (x >= 0) { id[c] = (int)perm[x]; lb[c] = lb_of(av); }
     }
     // Phase 1: a FAST chi-square (lanes sum their elements, wave tree sum) for the candidates in ascending LB order. The functor's own
     // value f (one sequential chain of dim additions, ~5 us per row at 1344 elements) differs from it by at most 3 ku f, so with
@@ -514,7 +499,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
     }
     // Phase 2: the functor's sequential chain for the contenders
     {
-        __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+        __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
         float* sT = s_terms[threadIdx.x >> 6];
         const float win = kth_fast * (1.f + 3.f * mg);
         for (;;) {
@@ -534,20 +519,8 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
     }
     float bnd = __builtin_inff();
     if (lane < n_bound) bnd = cand_bound[(size_t)qi * n_bound + lane];
-    float dk = 0.f; bool have_k = true;
-    for (int j = 0; j < k; ++j) {
-        unsigned long long lm = key[0];
-#pragma unroll
-        for (int c = 1; c < KNN_HELL_CPL; ++c) lm = key[c] < lm ? key[c] : lm;
-        const unsigned long long mn = wave_min_u64(lm);
-        if (lane == 0) {
-            if (mn == ~0ull) { idx_out[(size_t)qi * k + j] = -1; dist_out[(size_t)qi * k + j] = __builtin_nanf(""); }
-            else { idx_out[(size_t)qi * k + j] = (int)(mn & 0xffffffffull); dist_out[(size_t)qi * k + j] = __uint_as_float((unsigned)(mn >> 32)); }
-        }
-        if (mn == ~0ull) have_k = false; else dk = __uint_as_float((unsigned)(mn >> 32));
-#pragma unroll
-        for (int c = 0; c < KNN_HELL_CPL; ++c) if (key[c] == mn) key[c] = ~0ull;       // rows are unique among candidates
-    }
+    float dk;
+    const bool have_k = knn_select_write<KNN_HELL_CPL>(key, qi, k, lane, idx_out, dist_out, dk);
     bool viol = false;
     if (lane < n_bound && (bnd != __builtin_inff() || !(eps_s + qn2 < __builtin_inff()))) {
         if (!have_k) viol = true;
@@ -575,14 +548,14 @@ __global__ __launch_bounds__(256) void k_knn_fallback(const float* __restrict__ 
                                                       const uint32_t* __restrict__ flag_count, const uint32_t* __restrict__ items,
                                                       const int32_t* __restrict__ idx_in, const float* __restrict__ dist_in,
                                                       unsigned long long* __restrict__ item_out, size_t part_base) {
-    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+    __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
     const int lane = threadIdx.x & 63;
     const int g = lane >> 4, l16 = lane & 15;
-    const uint32_t n_items = flag_count[1];
+    const uint32_t n_items = flag_count[KNN_CNT_ITEMS];
     const bool l2 = metric != ISMHIP_METRIC_CHI2;
-    const bool lay_all = l2 && wr_rows == -2;                     // merged splits (k_knn_merge_splits): the one slot owns every row
-    const bool lay16 = l2 && wr_rows == -1;                       // k_knn_l2_ring16: slot b = split*8 + wr*4 + fq owns rows wr*128 + 16 m + 4 fq + j
-    const bool lay16h = l2 && wr_rows == -3;                      // k_knn_l2_ring16<T, 1>: 128-row tiles, slot b = split*4 + fq owns rows 16 m + 4 fq + j
+    const bool lay_all = l2 && wr_rows == KNN_FB_ALL;                     // merged splits (k_knn_merge_splits): the one slot owns every row
+    const bool lay16 = l2 && wr_rows == KNN_FB_RING;                       // k_knn_l2_ring16: slot b = split*8 + wr*4 + fq owns rows wr*128 + 16 m + 4 fq + j
+    const bool lay16h = l2 && wr_rows == KNN_FB_RING_HALF;                      // k_knn_l2_ring16<T, 1>: 128-row tiles, slot b = split*4 + fq owns rows 16 m + 4 fq + j
     const int rows_per_tile = lay_all ? tile_rows : ((lay16 || lay16h) ? 32 : (l2 ? wr_rows / 2 : tile_rows));   // else a lane slot sees half of its wave-row block (bit 2 of the row == h)
     const int nj = dim_pad / 16;
     const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
@@ -650,8 +623,8 @@ __global__ __launch_bounds__(256) void k_knn_fallback(const float* __restrict__ 
 template <int KM>
 __global__ __launch_bounds__(256) void k_knn_fallback_merge(int k, const uint32_t* __restrict__ flag_count, const uint32_t* __restrict__ qrec,
                                      const unsigned long long* __restrict__ item_out, size_t part_base, int32_t* __restrict__ idx_out, float* __restrict__ dist_out) {
-    const uint32_t n_q = flag_count[0];
-    const uint32_t P = knn_fb_parts(flag_count[1]);
+    const uint32_t n_q = flag_count[KNN_CNT_QUERIES];
+    const uint32_t P = knn_fb_parts(flag_count[KNN_CNT_ITEMS]);
     const unsigned long long* outp = P > 1 ? item_out + KM * part_base : item_out;
     const int lane = threadIdx.x & 63;
     for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_q; t += gridDim.x * 4) {
@@ -752,7 +725,7 @@ struct KnnPlan {
     bool big_tile, half, qpanel2, pca, merged, prepass, join;
     int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
     int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
-    int fb_tiles_per_split, fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout (k_knn_fallback's wr_rows)
+    int fb_tiles_per_split; KnnFbLayout fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout
     size_t lds, lds_cap;        // dynamic LDS of this launch, and the largest any launch of the kernel uses
 };
 
@@ -826,7 +799,7 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     // unrelaxed best of the sample is the nearest neighbour itself too often)
     p.prepass = rq.stage1 && ring && !p.half && ctx->knn_prepass && n_mt >= 128 && !(p.pca && PI.resid2 <= 0.f);
     p.fb_tiles_per_split = p.merged ? n_mt : p.tiles_per_split;
-    p.fb_layout = p.merged ? -2 : (p.half ? -3 : (ring ? -1 : (p.big_tile ? 128 : 64)));
+    p.fb_layout = p.merged ? KNN_FB_ALL : (p.half ? KNN_FB_RING_HALF : (ring ? KNN_FB_RING : (p.big_tile ? KNN_FB_TILE256 : KNN_FB_TILE128)));
     p.threads = 256;
     if (!l2) p.cand = KNN_CAND_CHI2;
     else if (!use_lp) p.cand = KNN_CAND_F32;
@@ -845,69 +818,77 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     return p;
 }
 
-int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k, int T,
-            int32_t* idx_out, float* dist_out, const KnnRequest& rq = KnnRequest()) {
-    if (cb->dim_pad / 16 > KNN_FB_MAXJ) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: descriptor longer than 1344 not built");
-    const KnnPlan p = knn_plan(ctx, cb, metric, nq, k, T, rq);
-    if (p.cand == KNN_CAND_MFMA16 && !p.kern) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: f16 256x256 tile without the ring not built");
-    const ismhip_codebook* xb = p.hell ? cb->chi_shadow : cb;
-    const PcaImage& PI = rq.use_pca == 2 ? cb->pca2 : cb->pca;
-    const float* qq = q; int ldq = cb->dim;
-    if (cb->dim_pad != cb->dim) {
-        float* qpad = (float*)ism_scratch(ctx, SCR_QPAD, (size_t)nq * cb->dim_pad * sizeof(float));
-        if (!qpad) return ISMHIP_ERR_NOMEM;
-        const size_t tot = (size_t)nq * cb->dim_pad;
-        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, q, nq, cb->dim, qpad, cb->dim_pad);
-        ISM_CHECK_LAUNCH(ctx, "k_pad_rows");
-        qq = qpad; ldq = cb->dim_pad;
-    }
-    int n_cand = p.n_cand, n_bound = p.n_bound;
-    float* cand_val = (float*)ism_scratch(ctx, SCR_KNN_CAND_VAL, (size_t)nq * (n_cand + n_bound + (p.merged ? KNN_MERGE_KEEP + 1 : 0)) * sizeof(float));
-    int* cand_idx = (int*)ism_scratch(ctx, SCR_KNN_CAND_IDX, (size_t)nq * (n_cand + (p.merged ? KNN_MERGE_KEEP : 0)) * sizeof(int));
-    // queue of unproven work: 16 counters | query records [nq*3] | items [nq*n_bound*2] | item results [nq*n_bound*4] u64
-    const size_t q_items = (size_t)nq * n_bound;
-    uint32_t* flags = (uint32_t*)ism_scratch(ctx, SCR_KNN_FLAGS, (16 + 3 * (size_t)nq + 2 * q_items) * sizeof(uint32_t) + 8 + (q_items + KNN_FB_UNITS) * (k > 4 ? KNN_MAX_K : 4) * sizeof(unsigned long long));
-    if (!cand_val || !cand_idx || !flags) return ISMHIP_ERR_NOMEM;
-    float* cand_bound = cand_val + (size_t)nq * n_cand;
-    uint32_t* flag_count = flags; uint32_t* qrec = flags + 16; uint32_t* items = qrec + 3 * (size_t)nq;
-    unsigned long long* item_out = (unsigned long long*)(((uintptr_t)(items + 2 * q_items) + 7) & ~(uintptr_t)7);
-    ISM_HIP(ctx, hipMemsetAsync(flag_count, 0, 64, ctx->stream));
-    uint32_t* qsc = flag_count + 4;      // f16 mode: [0] absmax bits of the query batch, [1] -2/(s_q s_c), [2] 2^-14/s_q
+// The carve-up of a search's scratch, filled by knn_carve_scratch.
+struct KnnScratch {
+    float *cand_val, *cand_bound; int* cand_idx; int n_cand, n_bound;      // candidate lists and slot bounds (after a merge: the folded slot)
+    uint32_t *flag_count, *qrec, *items; unsigned long long* item_out; size_t q_items;    // counter block and queue of unproven work
+    uint32_t* qsc;                       // the counter block's f16 scalars
+};
+// One search in flight: what the phases of run_knn hand to each other.
+struct KnnRun : KnnScratch {
+    ismhip_ctx* ctx; const ismhip_codebook *cb, *xb; const PcaImage* PI; const KnnRequest* rq; KnnPlan p;
+    int metric, nq, k, T;
+    const float* qq; int ldq;            // the query rows as the kernels read them (padded to dim_pad when dim is not)
+    u16 *q_hi, *q_lo;                    // 16-bit query images (knn_query_images; nullptr: the candidate kernel reads the rows themselves)
+};
+
+// queue of unproven work: counters | query records [nq*3] | items [nq*n_bound*2] | item results [nq*n_bound*4] u64
+int knn_carve_scratch(KnnRun& r) {
+    const KnnPlan& p = r.p; const size_t nq = (size_t)r.nq;
+    r.n_cand = p.n_cand; r.n_bound = p.n_bound; r.q_items = nq * p.n_bound;
+    r.cand_val = (float*)ism_scratch(r.ctx, SCR_KNN_CAND_VAL, nq * (p.n_cand + p.n_bound + (p.merged ? KNN_MERGE_KEEP + 1 : 0)) * sizeof(float));
+    r.cand_idx = (int*)ism_scratch(r.ctx, SCR_KNN_CAND_IDX, nq * (p.n_cand + (p.merged ? KNN_MERGE_KEEP : 0)) * sizeof(int));
+    r.flag_count = (uint32_t*)ism_scratch(r.ctx, SCR_KNN_FLAGS, (KNN_CNT_WORDS + 3 * nq + 2 * r.q_items) * sizeof(uint32_t) + 8 + (r.q_items + KNN_FB_UNITS) * (r.k > 4 ? KNN_MAX_K : 4) * sizeof(unsigned long long));
+    if (!r.cand_val || !r.cand_idx || !r.flag_count) return ISMHIP_ERR_NOMEM;
+    r.cand_bound = r.cand_val + nq * p.n_cand;
+    r.qrec = r.flag_count + KNN_CNT_WORDS; r.items = r.qrec + 3 * nq; r.qsc = r.flag_count + KNN_CNT_QSC;
+    r.item_out = (unsigned long long*)(((uintptr_t)(r.items + 2 * r.q_items) + 7) & ~(uintptr_t)7);
+    ISM_HIP(r.ctx, hipMemsetAsync(r.flag_count, 0, KNN_CNT_WORDS * sizeof(uint32_t), r.ctx->stream));
+    return ISMHIP_OK;
+}
+
+// the 16-bit images of the query batch (none for the f32 and chi-square candidates)
+int knn_query_images(KnnRun& r) {
+    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p; const int nq = r.nq;
+    if (p.mode != 0 && p.mode != 1) return ISMHIP_OK;
     const bool ring = p.cand == KNN_CAND_RING16;
-    u16 *q_hi = nullptr, *q_lo = nullptr;
-    if (p.mode == 0 || p.mode == 1) {
-        const int nq_pad = ring ? (nq + 255) / 256 * 256 : (nq + p.BN - 1) / p.BN * p.BN;
-        const size_t tot = ring ? (size_t)(nq_pad / 256) * p.ring_nk * 8192 : (size_t)nq_pad * cb->ld16;
-        q_hi = (u16*)ism_scratch(ctx, SCR_KNN_QSPLIT, tot * 2 * sizeof(u16));
-        if (!q_hi) return ISMHIP_ERR_NOMEM;
-        q_lo = q_hi + tot;
-        if (p.pca) {
-            TimerScope tr(ctx, "knn_rotate");
-            const int rc = ism_pca_rotate_queries(ctx, cb, &PI, qq, nq, ldq, q_hi);
-            if (rc != ISMHIP_OK) return rc;
-            ++ctx->knn_pca_launches;
-        } else if (p.mode == 0) {
-            const float* cq = p.hell ? rq.hell_q : qq; const int cldq = p.hell ? cb->dim_pad : ldq;     // Hellinger: the images are made from sqrt(q)
-            hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, qsc);
-            ISM_CHECK_LAUNCH(ctx, "k_absmax");
-            if (ring) hipLaunchKernelGGL(k_to_f16_tiled, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad / 256, p.ring_nk, qsc, xb->f16_scale, q_hi);
-            else hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad, cb->ld16, qsc, xb->f16_scale, q_hi);
-            ISM_CHECK_LAUNCH(ctx, "k_to_f16");
-        } else {
-            hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, qq, nq, cb->dim, ldq, nq_pad, cb->ld16, q_hi, q_lo);
-            ISM_CHECK_LAUNCH(ctx, "k_split_bf16");
-        }
+    const int nq_pad = ring ? (nq + F16T_ROWS - 1) / F16T_ROWS * F16T_ROWS : (nq + p.BN - 1) / p.BN * p.BN;
+    const size_t tot = ring ? f16t_halves(nq_pad / F16T_ROWS, p.ring_nk) : (size_t)nq_pad * cb->ld16;
+    r.q_hi = (u16*)ism_scratch(ctx, SCR_KNN_QSPLIT, tot * 2 * sizeof(u16));
+    if (!r.q_hi) return ISMHIP_ERR_NOMEM;
+    r.q_lo = r.q_hi + tot;
+    if (p.pca) {
+        TimerScope tr(ctx, "knn_rotate");
+        const int rc = ism_pca_rotate_queries(ctx, cb, r.PI, r.qq, nq, r.ldq, r.q_hi);
+        if (rc != ISMHIP_OK) return rc;
+        ++ctx->knn_pca_launches;
+    } else if (p.mode == 0) {
+        const float* cq = p.hell ? r.rq->hell_q : r.qq; const int cldq = p.hell ? cb->dim_pad : r.ldq;     // Hellinger: the images are made from sqrt(q)
+        hipLaunchKernelGGL(k_absmax, dim3(512), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, r.qsc);
+        ISM_CHECK_LAUNCH(ctx, "k_absmax");
+        if (ring) hipLaunchKernelGGL(k_to_f16_tiled, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad / F16T_ROWS, p.ring_nk, r.qsc, r.xb->f16_scale, r.q_hi);
+        else hipLaunchKernelGGL(k_to_f16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, cq, nq, cb->dim, cldq, nq_pad, cb->ld16, r.qsc, r.xb->f16_scale, r.q_hi);
+        ISM_CHECK_LAUNCH(ctx, "k_to_f16");
+    } else {
+        hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, r.qq, nq, cb->dim, r.ldq, nq_pad, cb->ld16, r.q_hi, r.q_lo);
+        ISM_CHECK_LAUNCH(ctx, "k_split_bf16");
     }
+    return ISMHIP_OK;
+}
+
+// the candidate kernel of the plan; many splits are then folded into one slot, which becomes the run's candidate list
+int knn_launch_candidates(KnnRun& r) {
+    ismhip_ctx* ctx = r.ctx; const ismhip_codebook *cb = r.cb, *xb = r.xb; const KnnPlan& p = r.p; const PcaImage& PI = *r.PI; const int nq = r.nq;
     {
-        TimerScope ts(ctx, rq.tname ? rq.tname : (metric == ISMHIP_METRIC_L2SQ ? "knn_l2_mfma" : "knn_chi2"));      // chi-square: whichever kernel makes its candidates
+        TimerScope ts(ctx, r.rq->tname ? r.rq->tname : (r.metric == ISMHIP_METRIC_L2SQ ? "knn_l2_mfma" : "knn_chi2"));      // chi-square: whichever kernel makes its candidates
         const unsigned grid = 8 * ((p.n_qt + 7) / 8) * p.n_splits;
         KnnCandArgs a{};                                                     // the 16-bit kernels; f32 and chi-square read the codebook itself
         a.n_tiles_m = cb->n_words_pad / p.BM; a.ld = cb->ld16; a.k_steps = p.pca ? PI.m / 16 : (cb->dim + 15) / 16;
-        a.qh = q_hi; a.ql = q_lo; a.nq = nq; a.out_scale = (const float*)(qsc + 1);
+        a.qh = r.q_hi; a.ql = r.q_lo; a.nq = nq; a.out_scale = (const float*)(r.qsc + 1);
         a.tiles_per_split = p.tiles_per_split; a.n_splits = p.n_splits;
-        a.cand_val = cand_val; a.cand_idx = cand_idx; a.cand_stride = n_cand; a.cand_bound = cand_bound; a.bound_stride = n_bound;
+        a.cand_val = r.cand_val; a.cand_idx = r.cand_idx; a.cand_stride = r.n_cand; a.cand_bound = r.cand_bound; a.bound_stride = r.n_bound;
         int rc = ISMHIP_OK;
-        if (ring) {
+        if (p.cand == KNN_CAND_RING16) {
             rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
             if (rc != ISMHIP_OK) return rc;
             a.wh = xb->words_f16t;
@@ -934,7 +915,7 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
                 // accumulator units (score / out_scale); the original image truncates nothing
                 if (p.pca) relax = -ctx->knn_pre_gamma * 2.0f * PI.resid2 * (PI.sq * PI.sc * 0.5f);
             }
-            rc = knn_ring16_launch(ctx, T, p.kern, grid, p.threads, p.lds, a, clock, thr0, ctx->knn_pre_step, relax);
+            rc = knn_ring16_launch(ctx, r.T, p.kern, grid, p.threads, p.lds, a, clock, thr0, ctx->knn_pre_step, relax);
         } else if (p.cand == KNN_CAND_MFMA16) {
             rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
             if (rc != ISMHIP_OK) return rc;
@@ -943,58 +924,94 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
             a.word_norm = xb->word_norm;
             rc = knn_mfma16_launch(ctx, p.kern, grid, p.threads, p.lds, a, nullptr, nullptr, nullptr, 0);
         } else if (p.cand == KNN_CAND_F32) {
-            rc = knn_l2_f32_launch(ctx, T, grid, cb, qq, nq, ldq, p.tiles_per_split, p.n_splits, cand_val, cand_idx, n_cand, cand_bound, n_bound);
+            rc = knn_l2_f32_launch(ctx, r.T, grid, cb, r.qq, nq, r.ldq, p.tiles_per_split, p.n_splits, r.cand_val, r.cand_idx, r.n_cand, r.cand_bound, r.n_bound);
         } else {
-            uint32_t* q_negative = flag_count + 12;                 // zeroed with the counters above
-            rc = knn_chi2_launch(ctx, T, p.n_qt, cb, qq, nq, ldq, q_negative, p.tiles_per_split, p.n_splits, cand_val, cand_idx, n_cand, cand_bound, n_bound);
+            rc = knn_chi2_launch(ctx, r.T, p.n_qt, cb, r.qq, nq, r.ldq, r.flag_count + KNN_CNT_NEGATIVE, p.tiles_per_split, p.n_splits, r.cand_val, r.cand_idx, r.n_cand, r.cand_bound, r.n_bound);
         }
         if (rc != ISMHIP_OK) return rc;
     }
     if (p.merged) {
-        float* m_val = cand_bound + (size_t)nq * n_bound; float* m_bound = m_val + (size_t)nq * KNN_MERGE_KEEP;
-        int* m_idx = cand_idx + (size_t)nq * n_cand;
-        hipLaunchKernelGGL(k_knn_merge_splits, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, nq, cand_val, cand_idx, n_cand, cand_bound, n_bound, m_val, m_idx, m_bound);
+        float* m_val = r.cand_bound + (size_t)nq * r.n_bound; float* m_bound = m_val + (size_t)nq * KNN_MERGE_KEEP;
+        int* m_idx = r.cand_idx + (size_t)nq * r.n_cand;
+        hipLaunchKernelGGL(k_knn_merge_splits, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, nq, r.cand_val, r.cand_idx, r.n_cand, r.cand_bound, r.n_bound, m_val, m_idx, m_bound);
         ISM_CHECK_LAUNCH(ctx, "k_knn_merge_splits");
-        cand_val = m_val; cand_idx = m_idx; cand_bound = m_bound; n_cand = KNN_MERGE_KEEP; n_bound = 1;
+        r.cand_val = m_val; r.cand_idx = m_idx; r.cand_bound = m_bound; r.n_cand = KNN_MERGE_KEEP; r.n_bound = 1;
     }
-    const VerifyParams vp = knn_verify_params(xb, cb->dim_pad, p.mode, qsc, true);
-    {
+    return ISMHIP_OK;
+}
+
+// exact functor values of the candidates that matter, the k best, and the proof; what it cannot prove is queued
+int knn_rerank_prove(KnnRun& r, int32_t* idx_out, float* dist_out) {
+    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p; const PcaImage& PI = *r.PI;
+    const VerifyParams vp = knn_verify_params(r.xb, cb->dim_pad, p.mode, r.qsc, true);
+    const dim3 grid((r.nq + 3) / 4), block(256);
     TimerScope trr(ctx, "knn_rerank");
     if (p.pca) {
         PcaVerify pv;
         const float acc_rel = 1.01f * (float)PI.m * 1.1920929e-07f;            // accumulation only: products of f16 values are exact in fp32
-        pv.qimg = q_hi; pv.nk = p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
+        pv.qimg = r.q_hi; pv.nk = p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
         pv.inv_sig2 = PI.inv_sig2; pv.d_rel = PI.d_rel; pv.dq_abs = PI.dq_abs;
         pv.dc = (PI.d_rel * sqrtf(cb->max_norm2) + PI.dc_abs) * 1.00001f;
         pv.cmax2 = PI.cmax2;
         // subnormal f16 operands may be flushed to zero by the matrix cores: |dq_i| <= 2^-14 / sq, |dc_i| <= 2^-14 / sc per element
-        const float fq = 6.103515625e-05f / PI.sq, fc = 6.103515625e-05f / PI.sc, sm = sqrtf((float)PI.m);
+        const float fq = F16_FLUSH / PI.sq, fc = F16_FLUSH / PI.sc, sm = sqrtf((float)PI.m);
         pv.eps_c2 = (17.f * KNN_U + 1.01f * (float)(PI.m + 1) * 1.1920929e-07f) * PI.cmax2 + 2.02f * (sm * fq * sqrtf(PI.cmax2) + sm * sm * fq * fc);
         pv.dot2 = 2.f * acc_rel + 2.f * KNN_U + 2.02f * sm * fc / sqrtf(PI.cmax2);
         pv.ku = vp.ku;
-        hipLaunchKernelGGL(k_knn_rerank_pca, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                           qq, nq, ldq, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, pv, k, idx_out, dist_out, flag_count, qrec, items);
+        hipLaunchKernelGGL(k_knn_rerank_pca, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
+                           r.qq, r.nq, r.ldq, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, pv, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
     } else if (p.hell) {
-        hipLaunchKernelGGL(k_knn_rerank_hell, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                           qq, nq, ldq, rq.hell_q, xb->shadow_perm, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, vp, k, idx_out, dist_out, flag_count, qrec, items);
+        hipLaunchKernelGGL(k_knn_rerank_hell, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
+                           r.qq, r.nq, r.ldq, r.rq->hell_q, r.xb->shadow_perm, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
     } else
-    hipLaunchKernelGGL(k_knn_rerank, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                       qq, nq, ldq, metric, cand_idx, cand_val, n_cand, n_cand, cand_bound, n_bound, vp, k, idx_out, dist_out, flag_count, qrec, items);
+    hipLaunchKernelGGL(k_knn_rerank, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
+                       r.qq, r.nq, r.ldq, r.metric, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
     ISM_CHECK_LAUNCH(ctx, "k_knn_rerank");
+    return ISMHIP_OK;
+}
+
+// exact scan of the queued slots' rows, folded into the results of the unproven queries
+int knn_exact_scan(KnnRun& r, int32_t* idx_out, float* dist_out) {
+    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p; const int k = r.k;
+    TimerScope ts(ctx, "knn_fallback");
+    const int n_tiles = cb->n_words_pad / p.BM;
+    const auto scan = k <= 4 ? k_knn_fallback<4> : k_knn_fallback<KNN_MAX_K>;      // capacity of the per-item result lists
+    const auto merge = k <= 4 ? k_knn_fallback_merge<4> : k_knn_fallback_merge<KNN_MAX_K>;
+    hipLaunchKernelGGL(scan, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, r.qq, r.ldq, r.metric, k,
+                       p.fb_tiles_per_split, n_tiles, p.BM, (int)p.fb_layout, r.flag_count, r.items, idx_out, dist_out, r.item_out, r.q_items);
+    ISM_CHECK_LAUNCH(ctx, "k_knn_fallback");
+    hipLaunchKernelGGL(merge, dim3(256), dim3(256), 0, ctx->stream, k, r.flag_count, r.qrec, r.item_out, r.q_items, idx_out, dist_out);
+    ISM_CHECK_LAUNCH(ctx, "k_knn_fallback_merge");
+    return ISMHIP_OK;
+}
+
+int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k, int T,
+            int32_t* idx_out, float* dist_out, const KnnRequest& rq = KnnRequest()) {
+    if (cb->dim_pad / 16 > KNN_FB_MAXJ) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: descriptor longer than 1344 not built");
+    KnnRun r{};
+    r.ctx = ctx; r.cb = cb; r.rq = &rq; r.metric = metric; r.nq = nq; r.k = k; r.T = T;
+    r.p = knn_plan(ctx, cb, metric, nq, k, T, rq);
+    if (r.p.cand == KNN_CAND_MFMA16 && !r.p.kern) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: f16 256x256 tile without the ring not built");
+    r.xb = r.p.hell ? cb->chi_shadow : cb;
+    r.PI = rq.use_pca == 2 ? &cb->pca2 : &cb->pca;
+    r.qq = q; r.ldq = cb->dim;
+    if (cb->dim_pad != cb->dim) {
+        float* qpad = (float*)ism_scratch(ctx, SCR_QPAD, (size_t)nq * cb->dim_pad * sizeof(float));
+        if (!qpad) return ISMHIP_ERR_NOMEM;
+        const size_t tot = (size_t)nq * cb->dim_pad;
+        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, q, nq, cb->dim, qpad, cb->dim_pad);
+        ISM_CHECK_LAUNCH(ctx, "k_pad_rows");
+        r.qq = qpad; r.ldq = cb->dim_pad;
     }
-    if (rq.stage1) { rq.stage1->flag_count = flag_count; rq.stage1->qrec = qrec; return ISMHIP_OK; }
-    {
-        TimerScope ts(ctx, "knn_fallback");
-        const int n_tiles = cb->n_words_pad / p.BM;
-        const auto scan = k <= 4 ? k_knn_fallback<4> : k_knn_fallback<KNN_MAX_K>;      // capacity of the per-item result lists
-        const auto merge = k <= 4 ? k_knn_fallback_merge<4> : k_knn_fallback_merge<KNN_MAX_K>;
-        hipLaunchKernelGGL(scan, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, qq, ldq, metric, k,
-                           p.fb_tiles_per_split, n_tiles, p.BM, p.fb_layout, flag_count, items, idx_out, dist_out, item_out, q_items);
-        ISM_CHECK_LAUNCH(ctx, "k_knn_fallback");
-        hipLaunchKernelGGL(merge, dim3(256), dim3(256), 0, ctx->stream, k, flag_count, qrec, item_out, q_items, idx_out, dist_out);
-        ISM_CHECK_LAUNCH(ctx, "k_knn_fallback_merge");
-    }
-    if (ctx->timers_on) ISM_HIP(ctx, hipMemcpyAsync(ctx->knn_stats, flag_count, 8, hipMemcpyDeviceToHost, ctx->stream));   // read back after a sync
+    int rc = knn_carve_scratch(r);
+    if (rc == ISMHIP_OK) rc = knn_query_images(r);
+    if (rc == ISMHIP_OK) rc = knn_launch_candidates(r);
+    if (rc == ISMHIP_OK) rc = knn_rerank_prove(r, idx_out, dist_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (rq.stage1) { rq.stage1->flag_count = r.flag_count; rq.stage1->qrec = r.qrec; return ISMHIP_OK; }
+    rc = knn_exact_scan(r, idx_out, dist_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (ctx->timers_on) ISM_HIP(ctx, hipMemcpyAsync(ctx->knn_stats, r.flag_count, 8, hipMemcpyDeviceToHost, ctx->stream));   // read back after a sync
     return ISMHIP_OK;
 }
 
@@ -1104,9 +1121,7 @@ __global__ __launch_bounds__(256) void k_hell_tau(int n2, const uint32_t* __rest
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n2) return;
     const int lane = lane_id();
-    float qn2 = 0.f;
-    for (int c = lane; c < dim; c += 64) { const float v = sq2[(size_t)i * dim_pad + c]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
+    const float qn2 = wave_norm2(sq2 + (size_t)i * dim_pad, dim, lane);
     if (lane == 0) {
         const float dk = dist_out[list2[i]];                             // k = 1: the best exact value of stage 1 (NaN: no candidate at all)
         const float eps_s = knn_eps_s(vp, qn2);
@@ -1122,7 +1137,7 @@ __global__ __launch_bounds__(256) void k_hell_eval(int n2, const uint32_t* __res
                                                    const uint32_t* __restrict__ perm, const float* __restrict__ q, int dim, const float* __restrict__ words, int dim_pad, float ku,
                                                    int32_t* __restrict__ idx_out, float* __restrict__ dist_out, uint32_t* __restrict__ overflow) {
     __shared__ float s_fast[HELL_EMIT_CAP];
-    __shared__ __attribute__((aligned(16))) float s_terms[1344];
+    __shared__ __attribute__((aligned(16))) float s_terms[KNN_TERMS];
     const int i = blockIdx.x;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     const uint32_t qi = list2[i];
@@ -1270,8 +1285,8 @@ int ism_codebook_split_bf16(ismhip_ctx* ctx, ismhip_codebook* cb, uint32_t absma
                        cb->n_words_pad, cb->ld16, sc, 1.0f, cb->words_f16);
     ISM_CHECK_LAUNCH(ctx, "k_to_f16");
     {
-        const int nk = ((cb->dim + 15) / 16 + 1) / 2, n_tiles = cb->n_words_pad / 256;
-        const size_t tt = (size_t)n_tiles * nk * 8192;
+        const int nk = ((cb->dim + 15) / 16 + 1) / 2, n_tiles = cb->n_words_pad / F16T_ROWS;
+        const size_t tt = f16t_halves(n_tiles, nk);
         if (hipMalloc((void**)&cb->words_f16t, tt * sizeof(u16)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook tiled f16 image");
         hipLaunchKernelGGL(k_to_f16_tiled, dim3((unsigned)((tt + 255) / 256)), dim3(256), 0, ctx->stream, cb->words, cb->n_words_pad, cb->dim_pad, cb->dim_pad,
                            n_tiles, nk, sc, 1.0f, cb->words_f16t);

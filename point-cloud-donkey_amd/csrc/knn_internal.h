@@ -1,6 +1,8 @@
-// knn_internal.h — what more than one unit of the codeword search needs (the map of the units is at the top of knn.hip): the
-// types and device helpers in an anonymous namespace (they appear in kernel signatures, so every unit has its own), then the host
-// functions through which the units call each other. Each of those is defined in the unit that holds the kernels it launches.
+// knn_internal.h — what more than one unit of the codeword search needs (the map of the units is at the top of knn.hip; pca.hip
+// includes it for the f16 images): the types and device helpers in an anonymous namespace (they appear in kernel signatures, so
+// every unit has its own) -- candidate lists, THE definition of the scaled f16 images and their tiled layout, the error model of
+// the proofs, the steps the re-rank kernels share -- then the host functions through which the units call each other. Each of
+// those is defined in the unit that holds the kernels it launches.
 #pragma once
 #include "common.h"
 
@@ -17,6 +19,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define CHI_B 64         // both, in k_knn_chi2
 #define KNN_MAX_K 16
 #define KNN_FB_MAXJ 84          // dim_pad <= 1344 -> at most 84 elements per lane of a 16-lane row group
+#define KNN_TERMS (16 * KNN_FB_MAXJ)   // floats of LDS a wave hands to wave_functor: one term per element of the longest row
 
 template <int T>
 struct TopT {
@@ -69,6 +72,34 @@ struct Ring16Lds {
     static constexpr size_t total(int ring_nk) { return panel + (QP ? (size_t)ring_nk * 256 * RG_KB * sizeof(u16) : 0); }
 };
 
+// ---- the scaled f16 images --------------------------------------------------------------------------------------------------------
+// x -> RN_f16(x * s), s a power of two that puts the largest |element| into [2^13, 2^14) (clamped to 2^+-40), so neither overflow
+// nor the fp16 subnormal range matters: element error <= 2^-11 |x| + F16_FLUSH / s, where the second term assumes the worst
+// (subnormal results flushed to zero). bits = the float bits of that largest |element| or of a bound on it (sign bit clear);
+// zero / subnormal and inf / NaN select s = 1.
+#define F16_FLUSH 6.103515625e-05f        // 2^-14, the smallest normal f16
+__host__ __device__ inline float f16_scale_for(uint32_t bits) {
+    const int e = (int)(bits >> 23);                 // biased exponent; 0 = zero/subnormal, 255 = inf/NaN
+    if (e == 0 || e == 255) return 1.0f;
+    int k = 13 - (e - 127);                          // value * 2^k in [2^13, 2^14)
+    k = k > 40 ? 40 : (k < -40 ? -40 : k);
+    return __builtin_bit_cast(float, (uint32_t)(127 + k) << 23);
+}
+// The layout k_knn_l2_ring16 streams: [F16T_ROWS-row tile][F16T_KB-k slice][row][4 x 16-byte segments], i.e. every (tile, slice) is
+// one contiguous 16 KB block that already is the LDS image: segment p of row r holds logical segment p ^ f16t_swizzle(r), which
+// makes the fragment reads of both MFMA shapes conflict-free. A DMA instruction then copies 1 KB of consecutive, fully used
+// 128-byte lines; with a row-major image each slice touches only half of every line and the other half is fetched again one
+// slice later. Rows are padded to whole tiles; nk = slices per row.
+#define F16T_ROWS 256
+#define F16T_KB 32
+#define F16T_BLOCK (F16T_ROWS * F16T_KB)             // halves per (tile, slice) block
+__host__ __device__ inline size_t f16t_halves(size_t n_tiles, int nk) { return n_tiles * nk * F16T_BLOCK; }
+__device__ __forceinline__ int f16t_swizzle(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }      // F[(r >> 2) & 3], F = {0,2,3,1}
+// index of (row r of tile `tile`, logical column kc * F16T_KB + 8 seg + e): f16t_row(tile, r, nk, kc) + ((seg ^ f16t_swizzle(r)) << 3) + e
+__device__ __forceinline__ size_t f16t_row(size_t tile, int r, int nk, int kc) { return ((tile * nk + kc) * F16T_ROWS + r) * F16T_KB; }
+// half h (0 .. nk * F16T_KB - 1, in the order they are stored) of image row `row`: for sums that do not care about the order
+__device__ __forceinline__ size_t f16t_stored(unsigned row, int nk, unsigned h) { return f16t_row(row / F16T_ROWS, row % F16T_ROWS, nk, h / F16T_KB) + h % F16T_KB; }
+
 struct VerifyParams {
     float ku;         // 1.01 * K * u : relative error bound of a K-term fp32 functor sum (u = 2^-24)
     float dot_rel;    // bound on |approx(q.c) - q.c| / (|q||c|) of the candidate kernel (f32 fma chain: ku; bf16x3: see k_knn_l2_mfma16)
@@ -85,10 +116,18 @@ __device__ __forceinline__ float knn_abs_err(const VerifyParams& vp, float qn2) 
     return 1.01f * (vp.sqrt_dim * (dq * sqrtf(vp.cmax2) + dc * sqrtf(qn2)) + vp.sqrt_dim * vp.sqrt_dim * dq * dc);
 }
 #define KNN_U 5.9604645e-08f
-// eps_s of the lower-bound proofs (k_knn_rerank_hell, k_hell_tau, thr_tau_of): the error bound of a candidate score for a query
-// with |q|^2 = qn2 (k_knn_rerank's proof comment derives it), rounded up
-__device__ __forceinline__ float knn_eps_s(const VerifyParams& vp, float qn2) {
-    return (17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2) * 1.00001f;
+// eps_s: the error bound of a candidate score for a query with |q|^2 = qn2 (k_knn_rerank's proof comment derives it). _raw is the
+// expression as evaluated (k_knn_rerank, whose slack and proof margins absorb its rounding); the lower-bound proofs
+// (k_knn_rerank_hell, k_hell_tau, thr_tau_of) take it rounded up
+__device__ __forceinline__ float knn_eps_s_raw(const VerifyParams& vp, float qn2) {
+    return 17.f * KNN_U * vp.cmax2 + (2.f * vp.dot_rel + 2.f * KNN_U) * sqrtf(qn2 * vp.cmax2) + 2.f * knn_abs_err(vp, qn2) + vp.cn_acc * vp.cmax2;
+}
+__device__ __forceinline__ float knn_eps_s(const VerifyParams& vp, float qn2) { return knn_eps_s_raw(vp, qn2) * 1.00001f; }
+// |x|^2 of a row of dim floats by a wave: lane l adds the elements l, l + 64, ..., then a tree sum
+__device__ __forceinline__ float wave_norm2(const float* __restrict__ x, int dim, int lane) {
+    float s = 0.f;
+    for (int i = lane; i < dim; i += 64) { const float v = x[i]; s += v * v; }
+    return wave_sum_f(s);
 }
 
 // error model of the candidate scores for the proofs (k_knn_rerank, k_knn_rerank_hell, k_hell_tau, k_thr_tau). mode as in KnnPlan;
@@ -100,7 +139,7 @@ VerifyParams knn_verify_params(const ismhip_codebook* xb, int dim_pad, int mode,
     vp.dot_rel = mode == 0 ? (2.002f * 4.8828125e-04f + 1.01f * (float)dim_pad * 1.1920929e-07f)
                : mode == 1 ? (3.1f * 1.52587890625e-05f + 1.01f * 3.f * (float)dim_pad * 1.1920929e-07f) : vp.ku;
     vp.cmax2 = xb->max_norm2;
-    vp.dabs_c = mode == 0 ? 6.103515625e-05f / xb->f16_scale : 0.f;
+    vp.dabs_c = mode == 0 ? F16_FLUSH / xb->f16_scale : 0.f;
     vp.dabs_q = mode == 0 ? (const float*)(qsc + 2) : nullptr;
     vp.sqrt_dim = sqrtf((float)dim_pad);
     vp.cn_acc = mode == 0 && cn_acc ? 1.01f * (float)(dim_pad + 1) * 1.1920929e-07f : 0.f;

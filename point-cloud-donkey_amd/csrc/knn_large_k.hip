@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void k_knn_topk_exact(const float* __restrict_
                                                         int32_t* __restrict__ idx_out, float* __restrict__ dist_out) {
     __shared__ unsigned long long s_key[2 * KM];
     __shared__ __attribute__((aligned(16))) float s_q[1344];
-    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+    __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
     __shared__ uint32_t s_nb;
     __shared__ float s_thr;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, g = lane >> 4, l16 = lane & 15;
@@ -148,9 +148,7 @@ __global__ __launch_bounds__(256) void k_lk_tau(int n, const float* __restrict__
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const int lane = lane_id();
-    float qn2 = 0.f;
-    for (int c = lane; c < dim; c += 64) { const float v = qv[(size_t)i * ldv + c]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
+    const float qn2 = wave_norm2(qv + (size_t)i * ldv, dim, lane);
     if (lane == 0) {
         const float tv = tq[qmap ? (int)qmap[i] : q0 + i] * f;
         tau[i] = (tv > 0.f && tv < __builtin_inff()) ? thr_tau_of(nextafterf(tv, __builtin_inff()), qn2, dim, vp) : -__builtin_inff();
@@ -175,7 +173,7 @@ __global__ __launch_bounds__(256) void k_lk_eval(const uint32_t* __restrict__ qm
                                                  int32_t* __restrict__ idx_out, float* __restrict__ dist_out, uint32_t* __restrict__ retry, uint32_t* __restrict__ exact) {
     __shared__ unsigned long long s_key[CAP];
     __shared__ __attribute__((aligned(16))) float s_q[1344];
-    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+    __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
     __shared__ uint32_t s_c;
     const int li = blockIdx.x, t = threadIdx.x, lane = lane_id(), wv = t >> 6;
     const int qi = qmap ? (int)qmap[li] : q0 + li;

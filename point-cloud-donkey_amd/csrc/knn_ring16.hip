@@ -142,8 +142,8 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
 #pragma unroll
     for (int i = 0; i < STAGES; ++i) issue();
 
-    // fragment address of this lane inside a 16-row tile: row fr, physical segment fq ^ F[(fr >> 2) & 3]
-    const int fso = (fr * KB) + ((fq ^ ((0x78 >> (2 * ((fr >> 2) & 3))) & 3)) << 3);
+    // fragment address of this lane inside a 16-row tile: row fr, physical segment fq ^ f16t_swizzle(fr)
+    const int fso = (fr * KB) + ((fq ^ f16t_swizzle(fr)) << 3);
     const int fragA = wr * (MT * 16) * KB + fso, fragB = (QP ? 0 : BM * KB) + wc * (NT * 16) * KB + fso;
     TopT<T + 1> top[NT];
     float thr[NT];

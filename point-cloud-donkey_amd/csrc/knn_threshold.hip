@@ -20,9 +20,7 @@ __global__ __launch_bounds__(256) void k_thr_tau(int nq, const float* __restrict
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= nq) return;
     const int lane = lane_id();
-    float qn2 = 0.f;
-    for (int c = lane; c < dim; c += 64) { const float v = qv[(size_t)i * ldq + c]; qn2 += v * v; }
-    qn2 = wave_sum_f(qn2);
+    const float qn2 = wave_norm2(qv + (size_t)i * ldq, dim, lane);
     if (lane == 0) tau[i] = thr_tau_of(thr_q ? thr_q[i] : thr, qn2, dim, vp);
 }
 
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(256) void k_thr_eval(int nq, const uint32_t* __rest
     __shared__ uint32_t s_row[THR_EMIT_CAP];
     __shared__ float s_d[THR_EMIT_CAP];
     __shared__ __attribute__((aligned(16))) float s_q[1344];
-    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+    __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
     __shared__ uint32_t s_w[4];
     const int qi = blockIdx.x;
     const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;

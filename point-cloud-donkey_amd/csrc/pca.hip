@@ -18,17 +18,12 @@
 // The query image uses a scale FIXED per codebook (queries are assumed to be at most twice as long as the longest codeword; three
 // more bits of f16 headroom above that; a query beyond it overflows to inf, fails its proof and is searched by stage 2 in the
 // original coordinates): no pass over the query batch to find its largest element.
-#include "common.h"
+#include "knn_internal.h"
 #include <cmath>
-#include <cstring>
 #include <algorithm>
 #include <numeric>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 
 // ---- second-moment matrix S = W^T W, in row chunks (partial sums are added on the host in a fixed order) ----------------------
 #define SM_ROWS 64
@@ -66,8 +61,7 @@ __global__ __launch_bounds__(256) void k_second_moment(const float* __restrict__
 // (column lane & 31), the rotated coordinates 8 j + 4 h + 0..3 of every 32-wide output tile -- four consecutive halves of the
 // image row, one 8-byte store. 128 descriptors per workgroup (4 waves x 32), all m outputs per wave (m / 32 accumulator tiles),
 // K walked in 32-wide chunks staged through LDS (rows padded to 36 floats: conflict-free 16-byte fragment reads).
-// Image layout (k_to_f16_tiled of knn.hip): [256-row tile][32-k slice][row][4 x 16 B], segment p of row r holds logical segment
-// p ^ F[(r >> 2) & 3], F = {0,2,3,1}.
+// Image layout: the tiled f16 image of knn_internal.h, nct slices per row.
 #define ROT_LD 36
 template <int NT>
 __global__ __launch_bounds__(256, 2) void k_rotate_f16t(const float* __restrict__ x, int n, int ldx, int kdim,
@@ -116,15 +110,15 @@ __global__ __launch_bounds__(256, 2) void k_rotate_f16t(const float* __restrict_
     }
     // C layout of the 32x32 tile: column = lane & 31 (descriptor), row = (e & 3) + 8 (e >> 2) + 4 h (rotated coordinate)
     const size_t row = row0 + wv * 32 + r32;
-    const size_t n_img = ((size_t)n + 255) / 256 * 256;
+    const size_t n_img = ((size_t)n + F16T_ROWS - 1) / F16T_ROWS * F16T_ROWS;
     if (row >= n_img) return;
     const bool live = row < (size_t)n;
-    const size_t tile = row >> 8; const int r = (int)(row & 255);
-    const int fsw = (0x78 >> (2 * ((r >> 2) & 3))) & 3;
+    const size_t tile = row / F16T_ROWS; const int r = (int)(row % F16T_ROWS);
+    const int fsw = f16t_swizzle(r);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         if (t >= nct) continue;
-        u16* base = dst + ((tile * nct + t) * 256 + r) * 32 + 4 * h;
+        u16* base = dst + f16t_row(tile, r, nct, t) + 4 * h;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             union { _Float16 hf[4]; uint2 u; } pk;
@@ -142,11 +136,9 @@ __global__ __launch_bounds__(256) void k_f16t_norms(const u16* __restrict__ img,
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n_rows_pad) return;
     const int lane = lane_id();
-    const size_t tile = (size_t)(row >> 8); const int r = row & 255;
     float s = 0.f;
-    for (int i = lane; i < nk * 32; i += 64) {
-        const int kc = i >> 5, j = i & 31;
-        const float v = (float)__builtin_bit_cast(_Float16, img[((tile * nk + kc) * 256 + r) * 32 + j]);
+    for (int i = lane; i < nk * F16T_KB; i += 64) {                 // the halves as stored: the order does not matter to the sum
+        const float v = (float)__builtin_bit_cast(_Float16, img[f16t_stored(row, nk, i)]);
         s += v * v;
     }
     s = wave_sum_f(s);
@@ -180,17 +172,6 @@ void jacobi_eig(int n, std::vector<double>& A, std::vector<double>& V, std::vect
     }
     w.resize(n);
     for (int i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
-}
-
-float f16_scale_of_bound(float bound) {          // power of two s with bound * s in [2^13, 2^14) (clamped to 2^+-40), as knn.hip's f16_scale_for
-    uint32_t b; memcpy(&b, &bound, 4);
-    const int e = (int)((b >> 23) & 255u);
-    if (e == 0 || e == 255) return 1.0f;
-    int k = 13 - (e - 127);
-    k = k > 40 ? 40 : (k < -40 ? -40 : k);
-    const uint32_t u = (uint32_t)(127 + k) << 23;
-    float f; memcpy(&f, &u, 4);
-    return f;
 }
 
 int launch_rotate(ismhip_ctx* ctx, const float* x, int n, int ldx, int kdim, const float* rmat, int m, float scale, u16* dst) {
@@ -227,19 +208,19 @@ static int build_image(ismhip_ctx* ctx, ismhip_codebook* cb, PcaImage& P, const 
     const double sig2 = 1.0 + std::sqrt(e2), sig = std::sqrt(sig2), fro = std::sqrt(fro2);
     if (!(sig2 < 1.01)) return ISMHIP_OK;                                              // a basis this far from orthonormal is a bug, not a bound
     const double cmax = std::sqrt((double)cb->max_norm2);
-    P.sc = f16_scale_of_bound((float)(1.001 * sig * cmax));
-    P.sq = f16_scale_of_bound((float)(2.002 * sig * cmax));
+    P.sc = f16_scale_for(__builtin_bit_cast(uint32_t, (float)(1.001 * sig * cmax)));      // (positive bounds: the sign bit is clear)
+    P.sq = f16_scale_for(__builtin_bit_cast(uint32_t, (float)(2.002 * sig * cmax)));
     const double gamma = 1.01 * dp * 1.1920929e-07;                                    // fp32 rotation: K adds of relative error <= 2^-23, any order
     P.d_rel = (float)(1.001 * (gamma * fro + 4.8828125e-04 * (sig + gamma * fro)));
-    P.dq_abs = (float)(1.001 * std::sqrt((double)m) * 6.103515625e-05 / P.sq);
-    P.dc_abs = (float)(1.001 * std::sqrt((double)m) * 6.103515625e-05 / P.sc);
+    P.dq_abs = (float)(1.001 * std::sqrt((double)m) * (double)F16_FLUSH / P.sq);
+    P.dc_abs = (float)(1.001 * std::sqrt((double)m) * (double)F16_FLUSH / P.sc);
     P.inv_sig2 = (float)((1.0 / sig2) * (1.0 - 1e-6));
     P.energy = (float)energy;
     P.resid2 = (float)((1.0 - energy) * trace / (double)cb->n_words);
-    const int nk = m / 32, n_tiles = cb->n_words_pad / 256;
+    const int nk = m / F16T_KB, n_tiles = cb->n_words_pad / F16T_ROWS;
     if (hipMalloc((void**)&P.R, R.size() * sizeof(float)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotation matrix");
     ISM_HIP(ctx, hipMemcpy(P.R, R.data(), R.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (hipMalloc((void**)&P.f16t, (size_t)n_tiles * nk * 8192 * sizeof(u16)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotated f16 image");
+    if (hipMalloc((void**)&P.f16t, f16t_halves(n_tiles, nk) * sizeof(u16)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotated f16 image");
     if (hipMalloc((void**)&P.cn_scaled, ((size_t)cb->n_words_pad + 256) * sizeof(float) + 16) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotated norms");
     P.osc = P.cn_scaled + cb->n_words_pad + 256;
     P.m = m;
