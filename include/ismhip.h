@@ -372,7 +372,12 @@ typedef struct ismhip_maxima_params {
 /* slot_offsets_h[n_obj+1]: vote-slot range of each object. Outputs per object o, maximum m (sorted by
  * weight, descending): index o*max_maxima + m. n_maxima_out[n_obj]. class_score_out[n_obj*n_classes] =
  * best normalised weight per class (0 when the class has no maximum) — the record the multi-GPU
- * all-gather exchanges. */
+ * all-gather exchanges.
+ * vote_instance: any int32 except INT32_MIN (0x80000000), which marks an empty entry of the per-maximum instance table. A vote
+ * carrying it adds its weight to an entry whose key stays empty; another id that claims that entry later inherits the weight, so
+ * such a vote can inflate a different instance's sum and change the winner. Negative ids are fine; among equal sums the lowest id
+ * AS AN UNSIGNED NUMBER wins (the reference's std::map<unsigned, float>). The same holds for ismhip_hough3d_maxima and the _ransac
+ * entries. */
 int  ismhip_find_maxima(ismhip_ctx* ctx, int n_obj, const uint32_t* slot_offsets_h,
                         const float* vote_pos, const float* vote_weight, const int32_t* vote_class,
                         const int32_t* vote_instance, const float* vote_bbox_size /* may be NULL */,

@@ -256,7 +256,7 @@ __device__ __forceinline__ void instance_tally(const ClassVotes& V, int n, const
                                                unsigned long long (&s_bS)[4], int (&s_bi)[4]) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int cap = V.cap;
-    const int HEMPTY = (int)0x80000000;
+    const int HEMPTY = (int)0x80000000;                             // the empty marker, hence no usable id: its weight would land on a slot that stays free for another id to inherit (ismhip.h)
     for (int i = tid; i < cap; i += 256) { hkey[i] = HEMPTY; hval[i] = 0ull; }
     __syncthreads();
     for (int i = tid; i < n; i += 256) {

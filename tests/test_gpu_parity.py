@@ -9,6 +9,7 @@ import pytest
 
 from conftest import make_cloud
 import kat_checks
+from maxima_scenes import colliding_classes_scene, stacked_classes_scene, vote_scene as _vote_scene, with_quats as _with_quats
 
 pytestmark = pytest.mark.gpu
 KAT = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "kat.json")))
@@ -851,47 +852,11 @@ def test_cast_votes_matches_oracle(pkg, gpu, ora, flags):
         np.testing.assert_allclose(got[key].cpu().numpy(), want[key], atol=1e-5, rtol=1e-5, err_msg=key)
 
 
-def _vote_scene(rng, n_obj, n_classes, with_empty=True, big=()):
-    pos, w, cls, inst, bs, off = [], [], [], [], [], [0]
-    for o in range(n_obj):
-        if with_empty and o == 1:
-            off.append(off[-1]); continue
-        n_blobs = rng.integers(1, 4) + (3 if o in big else 0)
-        for b in range(n_blobs):
-            c = rng.integers(0, n_classes)
-            m = rng.integers(5, 120) * (12 if o in big else 1)
-            centre = rng.uniform(-2, 2, 3)
-            pos.append(centre + 0.15 * rng.normal(size=(m, 3))); w.append(rng.uniform(0.2, 1.0, m))
-            cls.append(np.full(m, c)); inst.append(rng.integers(0, 4, m)); bs.append(rng.uniform(0.5, 1.5, (m, 3)))
-        m = rng.integers(0, 40)                                   # clutter + slots without a vote
-        pos.append(rng.uniform(-3, 3, (m, 3))); w.append(rng.uniform(0.2, 1.0, m)); cls.append(rng.integers(-1, n_classes, m))
-        inst.append(rng.integers(0, 4, m)); bs.append(rng.uniform(0.5, 1.5, (m, 3)))
-        off.append(off[-1] + sum(len(x) for x in pos) - off[-1])
-    v = dict(pos=np.concatenate(pos).astype(np.float32), weight=np.concatenate(w).astype(np.float32), cls=np.concatenate(cls).astype(np.int32),
-             inst=np.concatenate(inst).astype(np.int32), bbox_size=np.concatenate(bs).astype(np.float32))
-    # shuffle inside every object so that classes interleave like real vote slots
-    for o in range(n_obj):
-        s, e = off[o], off[o + 1]
-        p = s + rng.permutation(e - s)
-        for key in v:
-            v[key][s:e] = v[key][p]
-    return np.asarray(off, np.uint32), v
-
-
 def test_find_maxima_filter_and_class_bandwidths_match_oracle(pkg, gpu, ora):
     """MaxFilterType "Simple" (greedy NMS over all classes inside the bandwidth, maxima_handler.cpp:227-268) and per-class
     bandwidths (BinOrBandwidthType ObjectRadius / BoundingBoxMedian -> MaximaHandler::getSearchDistForClass, :509-521)"""
     ctx, dev = gpu
-    rng = np.random.default_rng(77)
-    off, v = _vote_scene(rng, 12, 5)
-    # make different classes collide: copy every object's votes once more under another class, slightly shifted
-    v2 = {k: np.concatenate([a, a]) for k, a in v.items()}
-    n = len(v["weight"])
-    v2["cls"][n:] = np.where(v["cls"] >= 0, (v["cls"] + 1) % 5, -1); v2["pos"][n:] += 0.05; v2["weight"][n:] *= 0.7
-    off2 = np.concatenate([off, off[1:] + off[-1]]).astype(np.uint32)          # the copies form 12 further objects ...
-    order = np.concatenate([np.r_[off[o]:off[o + 1], n + off[o]:n + off[o + 1]] for o in range(12)])   # ... interleave them per object instead
-    v3 = {k: a[order] for k, a in v2.items()}
-    off3 = (2 * off.astype(np.int64)).astype(np.uint32)
+    off3, v3 = colliding_classes_scene()
     tv = {k2: T(a, dev) for k2, a in v3.items()}
     for kw in (dict(max_filter=1), dict(class_bandwidth=[0.3, 0.5, 0.8, 0.4, 0.6]), dict(max_filter=1, class_bandwidth=[0.3, 0.5, 0.8, 0.4, 0.6])):
         kw = dict(n_classes=5, bandwidth=0.5, max_maxima=12, min_votes_threshold=2, **kw)
@@ -925,16 +890,6 @@ def test_find_maxima_matches_oracle(pkg, gpu, ora, suppression, kernel):
     np.testing.assert_allclose(got["bbox_size"].cpu().numpy(), want["bbox_size"], atol=1e-3)
     np.testing.assert_allclose(got["class_score"].cpu().numpy(), want["class_score"], atol=TOL)
     assert want["n"][1] == 0 and want["n"].max() >= 2
-
-
-def _with_quats(rng, v):
-    """bbox quaternions per vote slot: a few base rotations per blob-ish neighbourhood + jitter, unit length"""
-    n = len(v["weight"])
-    base = rng.normal(size=(6, 4)); base /= np.linalg.norm(base, axis=1, keepdims=True)
-    q = base[rng.integers(0, 6, n)] + 0.05 * rng.normal(size=(n, 4))
-    q *= np.where(rng.random(n) < 0.5, -1.0, 1.0)[:, None]           # q and -q are the same rotation: the scatter matrix does not care
-    v = dict(v); v["bbox_quat"] = (q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32)
-    return v
 
 
 def _same_rotation(a, b, atol):
@@ -1034,20 +989,7 @@ def test_max_filter_merge_matches_oracle(pkg, gpu, ora):
     merged per class (running weighted means, instance tallies, quaternion average) and replaced by the heaviest merged maximum.
     Scenes with blobs of DIFFERENT classes on top of each other and same-class blobs just outside the intra-class suppression."""
     ctx, dev = gpu
-    rng = np.random.default_rng(83)
-    pos, w, cls, inst, bs, off = [], [], [], [], [], [0]
-    for o in range(12):
-        for b in range(rng.integers(2, 4)):
-            centre = rng.uniform(-1.5, 1.5, 3)
-            for c in rng.choice(5, size=rng.integers(1, 4), replace=False):      # several classes vote for (almost) the same place
-                m = rng.integers(8, 60)
-                pos.append(centre + rng.uniform(-0.2, 0.2, 3) + 0.08 * rng.normal(size=(m, 3))); w.append(rng.uniform(0.2, 1.0, m))
-                cls.append(np.full(m, c)); inst.append(rng.integers(0, 3, m)); bs.append(rng.uniform(0.5, 1.5, (m, 3)))
-        off.append(sum(len(x) for x in pos))
-    v = dict(pos=np.concatenate(pos).astype(np.float32), weight=np.concatenate(w).astype(np.float32), cls=np.concatenate(cls).astype(np.int32),
-             inst=np.concatenate(inst).astype(np.int32), bbox_size=np.concatenate(bs).astype(np.float32))
-    v = _with_quats(rng, v)
-    off = np.asarray(off, np.uint32)
+    off, v = stacked_classes_scene()
     tv = {k2: T(a, dev) for k2, a in v.items()}
     cbw = np.asarray([0.5, 0.6, 0.4, 0.5, 0.7], np.float32)
     for class_bandwidth in (None, cbw):
