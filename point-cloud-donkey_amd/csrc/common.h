@@ -139,6 +139,8 @@ struct ismhip_ctx {
     uint32_t knn_stats[2] = {0, 0};   // last ismhip_knn: {queries, (query,slot) items} sent to the exact fallback (valid with timers on, after a sync)
     std::set<const void*> attr_done;  // kernels whose MaxDynamicSharedMemorySize attribute has been raised on THIS ctx's device
     uint32_t knn_stage2_queries = 0;  // last two-stage ismhip_knn: queries the T = 2 stage could not prove (searched again with T = 4)
+    uint32_t knn_seed_launches = 0;   // candidate launches that started from k_knn_seed_thr's thresholds (tests)
+    bool knn_stage2_seed = true;      // env ISMHIP_KNN_STAGE2_SEED=0: stage 2 starts its candidate lists cold, with T = 4 (A/B runs, tests; same results)
     bool knn_two_stage = true;   // env ISMHIP_KNN_TWOSTAGE=0: single-stage T = 4 search (A/B runs)
     bool knn_join = true;        // env ISMHIP_KNN_JOIN=0: every workgroup of the ring kernel sweeps its split from the first tile (A/B runs); default: joined streams
     bool knn_qpanel2 = true;     // env ISMHIP_KNN_QPANEL2=0: stage 1 on <= 160 rotated coordinates WITHOUT the 256-query panel resident in LDS (A/B runs; default on: 27.5 -> 25.4 ms per bench launch)

@@ -84,6 +84,7 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_HELLINGER"); ctx->knn_hellinger = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_T1"); if (e) ctx->knn_t1 = atoi(e); }
     { const char* e = getenv("ISMHIP_KNN_STAGE2_T4"); if (e) ctx->knn_stage2_t4 = atoi(e) != 0; }
+    { const char* e = getenv("ISMHIP_KNN_STAGE2_SEED"); ctx->knn_stage2_seed = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_PRE_STEP"); if (e && atoi(e) > 0) ctx->knn_pre_step = atoi(e); }
     { const char* e = getenv("ISMHIP_KNN_PRE_GAMMA"); if (e) ctx->knn_pre_gamma = (float)atof(e); }
     { const char* e = getenv("ISMHIP_KNN_PREPASS"); ctx->knn_prepass = !(e && e[0] == '0'); }
@@ -187,6 +188,7 @@ int ismhip_timers_reset(ismhip_ctx* ctx) {
 int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t* launches_out) {
     if (!ctx || !name) return ISMHIP_ERR_INVALID;
     resolve_timers(ctx);
+    if (std::strcmp(name, "knn_seed_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_seed_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_pca_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_pca_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_overflow_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_overflow; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_mfma_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_mfma_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }

@@ -26,7 +26,9 @@
 //  The three re-rank kernels differ in how they pick the candidates to evaluate and in their proof; what they share is written once
 //  (knn_load_cand, knn_select_write, knn_queue_unproven here; wave_norm2, knn_eps_s_raw in knn_internal.h). run_knn is the phases in
 //  that order on one stream: knn_carve_scratch, knn_query_images, knn_launch_candidates, knn_rerank_prove, knn_exact_scan.
-//  Also here: the two-stage and the Hellinger (chi-square) drivers, ismhip_knn, _ratio, _rule.
+//  Also here: the two-stage and the Hellinger (chi-square) drivers, ismhip_knn, _ratio, _rule. Stage 2 of the two-stage search is
+//  SEEDED: k_knn_seed_thr turns the k-th exact value stage 1 found for a query into the start threshold of all its lane slots (the
+//  slot proofs it inverts are written once, in knn_internal.h: knn_l2_slot_proven, pca_lb_of / pca_slot_proven).
 //       knn_threshold.hip  ismhip_knn_threshold  radius search: EMIT sweep + k_thr_* 
 //       knn_large_k.hip    ismhip_knn_large_k    any K up to 1024: seeded EMIT sweep + certificate, exact top-K scan
 #include "knn_internal.h"
@@ -297,11 +299,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
         else if (metric == ISMHIP_METRIC_CHI2) {
             const float lo = bnd * (1.f - ((float)dim_pad + 8.f) * KNN_U) * (1.f - vp.ku);
             viol = !(dk < lo);
-        } else {
-            const float eps_s = knn_eps_s_raw(vp, qn2);
-            const float rhs = qn2 * (1.f - 16.f * KNN_U) + bnd - eps_s;
-            viol = !(dk < rhs - vp.ku * fabsf(rhs) - 1e-37f);
-        }
+        } else viol = !knn_l2_slot_proven(dk, bnd, qn2, vp);
     }
     knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
 }
@@ -322,6 +320,20 @@ struct PcaVerify {
     float eps_c2, dot2, cmax2;        // eps_acc = eps_c2 + dot2 |q^||c^|max;  cmax2 = max |c^|^2
     float ku;
 };
+// what LB(s) takes of query qi (row qp, |q|^2 = qn2 by wave_norm2), by the whole wave
+__device__ __forceinline__ PcaLb pca_lb_query(const PcaVerify& pv, int qi, float qn2, int lane) {
+    float qn2h = 0.f;                                                  // |q^|^2 from the image itself (the halves as stored: any element order)
+    for (int i = lane; i < pv.nk * F16T_KB; i += 64) {
+        const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[f16t_stored(qi, pv.nk, i)]);
+        qn2h += v * v;
+    }
+    PcaLb b;
+    b.qn2h = wave_sum_f(qn2h) * pv.inv_sq2;
+    b.dlt = pv.d_rel * (sqrtf(qn2) * 1.00001f) + pv.dq_abs + pv.dc;
+    b.eps_s = (pv.eps_c2 + pv.dot2 * sqrtf(b.qn2h * pv.cmax2)) * 1.00001f;
+    b.inv_sig2 = pv.inv_sig2;
+    return b;
+}
 __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict__ words, int dim, int dim_pad, int n_words,
                                                         const float* __restrict__ q, int nq, int ldq,
                                                         const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
@@ -332,26 +344,10 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     if (qi >= nq) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
-    const float qn2 = wave_norm2(qp, dim, lane);
-    float qn2h = 0.f;                                                  // |q^|^2 from the image itself (the halves as stored: any element order)
-    for (int i = lane; i < pv.nk * F16T_KB; i += 64) {
-        const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[f16t_stored(qi, pv.nk, i)]);
-        qn2h += v * v;
-    }
-    qn2h = wave_sum_f(qn2h) * pv.inv_sq2;
-    const float dlt = pv.d_rel * (sqrtf(qn2) * 1.00001f) + pv.dq_abs + pv.dc;
-    const float eps_s = (pv.eps_c2 + pv.dot2 * sqrtf(qn2h * pv.cmax2)) * 1.00001f;
-    auto lb_of = [&](float s) -> float {
-        float L = qn2h * (1.f - 16.f * KNN_U) + s - eps_s;
-        L -= 4.f * KNN_U * (qn2h + fabsf(s));                          // rounding of the two additions above
-        if (!(L > 0.f)) return 0.f;                                    // also NaN
-        const float t = sqrtf(L) * (1.f - 4.f * KNN_U) - dlt;
-        if (!(t > 0.f)) return 0.f;
-        return t * t * pv.inv_sig2 * (1.f - 8.f * KNN_U);
-    };
+    const PcaLb lbq = pca_lb_query(pv, qi, wave_norm2(qp, dim, lane), lane);
     float av;
     const int id = knn_load_cand(cand_idx, cand_val, qi, cand_stride, lane, n_cand, n_words, av);
-    const float lb = id >= 0 ? lb_of(av) : __builtin_inff();
+    const float lb = id >= 0 ? pca_lb_of(lbq, av) : __builtin_inff();
     bool done = id < 0;
     unsigned long long key = ~0ull;
     {
@@ -381,11 +377,54 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     const bool have_k = knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk);
     // a slot whose bound is still +inf dropped nothing -- unless scores overflowed, which needs a non-finite |q^|^2 or bound term
     bool viol = false;
-    if (lane < n_bound && (bnd != __builtin_inff() || !(eps_s + qn2h + dlt < __builtin_inff()))) {
+    if (lane < n_bound && (bnd != __builtin_inff() || !(lbq.eps_s + lbq.qn2h + lbq.dlt < __builtin_inff()))) {
         if (!have_k) viol = true;
-        else viol = !(dk < lb_of(bnd) * (1.f - pv.ku) - 1e-37f);
+        else viol = !pca_slot_proven(dk, bnd, lbq, pv.ku);
     }
     knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
+}
+
+// ---- start thresholds of a SEEDED search (stage 2 of the two-stage search) -------------------------------------------------------
+// Stage 1 has left every stage-2 query an exact functor value U for its k-th best row (seed_dk; NaN: fewer than k rows). Only a row
+// that beats or ties U can change the answer, and the proof of this search will ask of every slot bound b exactly
+// "U' < LB(b)" with U' <= U the k-th value found here (knn_l2_slot_proven / pca_slot_proven). So every lane slot of the query may
+// start from the loosest threshold whose bound already passes that test with dk := U: the rows of stage 1's answer lie below it and
+// are kept, nearly everything else never reaches the insertion code, and a slot that does not overflow is proven by construction.
+// A closed-form inverse of the bound gives a first guess in score units; it is then moved outwards in steps of about an ulp of the
+// bound's largest term until the test itself, evaluated on the value the candidate kernel will report (out_scale * threshold), holds.
+// Soundness does not depend on any of this (k_knn_l2_ring16: any start value is sound); a seed that cannot be made to hold -- U not
+// finite, an image row that overflowed -- is -inf, the cold start. One wave per query, as in the re-rank kernels: the proof's |q|^2
+// sums are the same bits.
+__global__ __launch_bounds__(256) void k_knn_seed_thr(const float* __restrict__ q, int nq, int ldq, int dim, const float* __restrict__ seed_dk,
+                                                      bool pca, PcaVerify pv, VerifyParams vp, const float* __restrict__ out_scale, float* __restrict__ thr) {
+    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qi >= nq) return;
+    const int lane = lane_id();
+    const float qn2 = wave_norm2(q + (size_t)qi * ldq, dim, lane);
+    PcaLb lbq{};
+    if (pca) lbq = pca_lb_query(pv, qi, qn2, lane);
+    if (lane != 0) return;
+    const float U = seed_dk[qi], osc = out_scale[0];
+    float t0 = -__builtin_inff();
+    if (U >= 0.f && U < __builtin_inff()) {
+        float s, step;
+        if (pca) {
+            // LB(s) (1 - ku) > U  <=  t^2 > U / (inv_sig2 (1 - 8u) (1 - ku)),  sqrt(L) (1 - 4u) - dlt = t,  s = L + eps_s - |q^|^2 (1 - 16u)
+            const float t = sqrtf((U + 1e-37f) / (lbq.inv_sig2 * (1.f - 8.f * KNN_U) * (1.f - pv.ku))) * (1.f + 4.f * KNN_U);
+            const float rl = (t + lbq.dlt) / (1.f - 4.f * KNN_U);
+            s = rl * rl * (1.f + 8.f * KNN_U) + lbq.eps_s - lbq.qn2h * (1.f - 16.f * KNN_U);
+            step = 4.f * KNN_U * (lbq.qn2h + fabsf(s) + lbq.eps_s);
+        } else {
+            s = thr_tau_of(U, qn2, dim, vp);
+            step = 4.f * KNN_U * (qn2 + fabsf(s) + vp.cmax2);
+        }
+        s += step;
+        for (int it = 0; it < 24 && s < __builtin_inff(); ++it, s += step, step *= 2.f) {
+            const float a = s / osc;                                   // accumulator units; the kernel reports osc * a as the slot's bound
+            if (pca ? pca_slot_proven(U, osc * a, lbq, pv.ku) : knn_l2_slot_proven(U, osc * a, qn2, vp)) { t0 = a; break; }
+        }
+    }
+    thr[qi] = t0;
 }
 
 // fast chi-square of one row by a whole wave: every lane owns the 16-byte chunks lane, lane + 64, ... of the (zero padded) rows, all
@@ -712,6 +751,8 @@ struct KnnRequest {
     int use_pca = 0;                   // 1: stage-1 image, 2: stage-2 image (pca.hip)
     const float* hell_q = nullptr;     // chi-square only: sqrt(q) rows of dim_pad floats -> Hellinger candidates (k_knn_rerank_hell)
     bool half = false;                 // the 128 x 256 ring tile (k_knn_l2_ring16<T, 1>), as with ISMHIP_KNN_HALF=1
+    const float* seed_dk = nullptr;    // per query, an exact functor value its k-th best row is known not to exceed (NaN: none): the ring
+                                       // kernel starts from the thresholds k_knn_seed_thr derives from it
 };
 
 // How run_knn runs one search. knn_plan decides it from the request, the ctx switches and the codebook, without side effects.
@@ -722,7 +763,7 @@ struct KnnPlan {
     KnnCand cand;
     const void* kern;           // KNN_CAND_MFMA16 / KNN_CAND_RING16: the kernel instance (nullptr: not built)
     int BM, BN, threads;        // codeword rows and queries per tile, threads per workgroup
-    bool big_tile, half, qpanel2, pca, merged, prepass, join;
+    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join;
     int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
     int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
     int fb_tiles_per_split; KnnFbLayout fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout
@@ -798,6 +839,7 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     // (not for an untruncated stage-1 image: with nothing left out there is no scale to relax the start value by, and the
     // unrelaxed best of the sample is the nearest neighbour itself too often)
     p.prepass = rq.stage1 && ring && !p.half && ctx->knn_prepass && n_mt >= 128 && !(p.pca && PI.resid2 <= 0.f);
+    p.seeded = rq.seed_dk && ring && !p.prepass;
     p.fb_tiles_per_split = p.merged ? n_mt : p.tiles_per_split;
     p.fb_layout = p.merged ? KNN_FB_ALL : (p.half ? KNN_FB_RING_HALF : (ring ? KNN_FB_RING : (p.big_tile ? KNN_FB_TILE256 : KNN_FB_TILE128)));
     p.threads = 256;
@@ -876,6 +918,23 @@ int knn_query_images(KnnRun& r) {
     return ISMHIP_OK;
 }
 
+// the constants of the lower-bound proof on the run's rotated image (k_knn_rerank_pca, k_knn_seed_thr)
+PcaVerify knn_pca_verify(const KnnRun& r, const VerifyParams& vp) {
+    const PcaImage& PI = *r.PI;
+    PcaVerify pv;
+    const float acc_rel = 1.01f * (float)PI.m * 1.1920929e-07f;            // accumulation only: products of f16 values are exact in fp32
+    pv.qimg = r.q_hi; pv.nk = r.p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
+    pv.inv_sig2 = PI.inv_sig2; pv.d_rel = PI.d_rel; pv.dq_abs = PI.dq_abs;
+    pv.dc = (PI.d_rel * sqrtf(r.cb->max_norm2) + PI.dc_abs) * 1.00001f;
+    pv.cmax2 = PI.cmax2;
+    // subnormal f16 operands may be flushed to zero by the matrix cores: |dq_i| <= 2^-14 / sq, |dc_i| <= 2^-14 / sc per element
+    const float fq = F16_FLUSH / PI.sq, fc = F16_FLUSH / PI.sc, sm = sqrtf((float)PI.m);
+    pv.eps_c2 = (17.f * KNN_U + 1.01f * (float)(PI.m + 1) * 1.1920929e-07f) * PI.cmax2 + 2.02f * (sm * fq * sqrtf(PI.cmax2) + sm * sm * fq * fc);
+    pv.dot2 = 2.f * acc_rel + 2.f * KNN_U + 2.02f * sm * fc / sqrtf(PI.cmax2);
+    pv.ku = vp.ku;
+    return pv;
+}
+
 // the candidate kernel of the plan; many splits are then folded into one slot, which becomes the run's candidate list
 int knn_launch_candidates(KnnRun& r) {
     ismhip_ctx* ctx = r.ctx; const ismhip_codebook *cb = r.cb, *xb = r.xb; const KnnPlan& p = r.p; const PcaImage& PI = *r.PI; const int nq = r.nq;
@@ -908,14 +967,21 @@ int knn_launch_candidates(KnnRun& r) {
             }
             float* thr0 = nullptr;                                           // the pre-pass leaves the start thresholds here
             float relax = 0.f;
-            if (p.prepass) {
+            if (p.prepass || p.seeded) {
                 thr0 = (float*)ism_scratch(ctx, SCR_KNN_THR0, (size_t)((nq + 255) / 256 * 256) * sizeof(float));
                 if (!thr0) return ISMHIP_ERR_NOMEM;
                 // relaxation: gamma x the second moment the truncation leaves out (codeword + query side, taken as equal), in
                 // accumulator units (score / out_scale); the original image truncates nothing
                 if (p.pca) relax = -ctx->knn_pre_gamma * 2.0f * PI.resid2 * (PI.sq * PI.sc * 0.5f);
             }
-            rc = knn_ring16_launch(ctx, r.T, p.kern, grid, p.threads, p.lds, a, clock, thr0, ctx->knn_pre_step, relax);
+            if (p.seeded) {                                                  // needs the query image and, on the original image, its scalars
+                const VerifyParams vp = knn_verify_params(xb, cb->dim_pad, p.mode, r.qsc, true);
+                hipLaunchKernelGGL(k_knn_seed_thr, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, r.qq, nq, r.ldq, cb->dim, r.rq->seed_dk,
+                                   p.pca, p.pca ? knn_pca_verify(r, vp) : PcaVerify{}, vp, a.out_scale, thr0);
+                ISM_CHECK_LAUNCH(ctx, "k_knn_seed_thr");
+                ++ctx->knn_seed_launches;
+            }
+            rc = knn_ring16_launch(ctx, r.T, p.kern, grid, p.threads, p.lds, a, clock, thr0, p.prepass ? ctx->knn_pre_step : 0, relax);
         } else if (p.cand == KNN_CAND_MFMA16) {
             rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
             if (rc != ISMHIP_OK) return rc;
@@ -942,22 +1008,12 @@ int knn_launch_candidates(KnnRun& r) {
 
 // exact functor values of the candidates that matter, the k best, and the proof; what it cannot prove is queued
 int knn_rerank_prove(KnnRun& r, int32_t* idx_out, float* dist_out) {
-    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p; const PcaImage& PI = *r.PI;
+    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p;
     const VerifyParams vp = knn_verify_params(r.xb, cb->dim_pad, p.mode, r.qsc, true);
     const dim3 grid((r.nq + 3) / 4), block(256);
     TimerScope trr(ctx, "knn_rerank");
     if (p.pca) {
-        PcaVerify pv;
-        const float acc_rel = 1.01f * (float)PI.m * 1.1920929e-07f;            // accumulation only: products of f16 values are exact in fp32
-        pv.qimg = r.q_hi; pv.nk = p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
-        pv.inv_sig2 = PI.inv_sig2; pv.d_rel = PI.d_rel; pv.dq_abs = PI.dq_abs;
-        pv.dc = (PI.d_rel * sqrtf(cb->max_norm2) + PI.dc_abs) * 1.00001f;
-        pv.cmax2 = PI.cmax2;
-        // subnormal f16 operands may be flushed to zero by the matrix cores: |dq_i| <= 2^-14 / sq, |dc_i| <= 2^-14 / sc per element
-        const float fq = F16_FLUSH / PI.sq, fc = F16_FLUSH / PI.sc, sm = sqrtf((float)PI.m);
-        pv.eps_c2 = (17.f * KNN_U + 1.01f * (float)(PI.m + 1) * 1.1920929e-07f) * PI.cmax2 + 2.02f * (sm * fq * sqrtf(PI.cmax2) + sm * sm * fq * fc);
-        pv.dot2 = 2.f * acc_rel + 2.f * KNN_U + 2.02f * sm * fc / sqrtf(PI.cmax2);
-        pv.ku = vp.ku;
+        const PcaVerify pv = knn_pca_verify(r, vp);
         hipLaunchKernelGGL(k_knn_rerank_pca, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
                            r.qq, r.nq, r.ldq, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, pv, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
     } else if (p.hell) {
@@ -1008,7 +1064,7 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
     if (rc == ISMHIP_OK) rc = knn_launch_candidates(r);
     if (rc == ISMHIP_OK) rc = knn_rerank_prove(r, idx_out, dist_out);
     if (rc != ISMHIP_OK) return rc;
-    if (rq.stage1) { rq.stage1->flag_count = r.flag_count; rq.stage1->qrec = r.qrec; return ISMHIP_OK; }
+    if (rq.stage1) { *rq.stage1 = KnnStage1{r.flag_count, r.qrec}; return ISMHIP_OK; }
     rc = knn_exact_scan(r, idx_out, dist_out);
     if (rc != ISMHIP_OK) return rc;
     if (ctx->timers_on) ISM_HIP(ctx, hipMemcpyAsync(ctx->knn_stats, r.flag_count, 8, hipMemcpyDeviceToHost, ctx->stream));   // read back after a sync
@@ -1022,12 +1078,17 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
 // So: stage 1 runs T = 2 over all queries; the few queries its proof rejects are gathered and searched again with T = 4 (a
 // launch ~1000x smaller), and only what THAT proof rejects goes to the exact scan. Every answer is still the exact functor
 // minimum, proven or scanned.
+// (dk2 != nullptr: also the k-th exact value stage 1 found for the query, NaN when it found fewer than k rows)
 __global__ __launch_bounds__(256) void k_knn_gather_flagged(const uint32_t* __restrict__ qrec, int n2, const float* __restrict__ q, int dim,
-                                                            float* __restrict__ q2, uint32_t* __restrict__ list2) {
+                                                            float* __restrict__ q2, uint32_t* __restrict__ list2,
+                                                            const int32_t* __restrict__ idx1, const float* __restrict__ dist1, int k, float* __restrict__ dk2) {
     const int i = blockIdx.x;
     if (i >= n2) return;
     const uint32_t qi = qrec[3 * (size_t)i];
-    if (threadIdx.x == 0) list2[i] = qi;
+    if (threadIdx.x == 0) {
+        list2[i] = qi;
+        if (dk2) dk2[i] = idx1[(size_t)qi * k + (k - 1)] >= 0 ? dist1[(size_t)qi * k + (k - 1)] : __builtin_nanf("");
+    }
     for (int c = threadIdx.x; c < dim; c += blockDim.x) q2[(size_t)i * dim + c] = q[(size_t)qi * dim + c];
 }
 __global__ void k_knn_scatter_results(const uint32_t* __restrict__ list2, int n2, int k, const int32_t* __restrict__ idx2, const float* __restrict__ dist2,
@@ -1040,9 +1101,11 @@ __global__ void k_knn_scatter_results(const uint32_t* __restrict__ list2, int n2
 
 // The queries a first stage left unproven (s1), gathered for a second search: n2 of them (read back: the one host round trip of the
 // call; n2 == 0: nothing left to do), their rows in q2, their ids in list2, and room for the second stage's results idx2 / dist2,
-// which knn_scatter_stage2 writes to the queries' places in the caller's arrays.
-struct KnnStage2 { int n2; float* q2; uint32_t* list2; int32_t* idx2; float* dist2; };
-int knn_gather_stage2(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const float* q, int k, KnnStage2& g) {
+// which knn_scatter_stage2 writes to the queries' places in the caller's arrays. dk2 = the k-th exact values of stage 1's results
+// idx1 / dist1 (the seeds of a seeded second search; nullptr: none wanted).
+struct KnnStage2 { int n2; float* q2; uint32_t* list2; int32_t* idx2; float* dist2; float* dk2; };
+int knn_gather_stage2(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const float* q, int k, KnnStage2& g,
+                      const int32_t* idx1, const float* dist1) {
     uint32_t n2u = 0;
     ISM_HIP(ctx, hipMemcpyAsync(&n2u, s1.flag_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1050,11 +1113,12 @@ int knn_gather_stage2(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage
     const int n2 = g.n2 = (int)n2u;
     if (n2 == 0) { ctx->knn_stats[0] = ctx->knn_stats[1] = 0; return ISMHIP_OK; }
     g.q2 = (float*)ism_scratch(ctx, SCR_KNN_Q2, (size_t)n2 * cb->dim * sizeof(float));
-    g.list2 = (uint32_t*)ism_scratch(ctx, SCR_KNN_LIST2, (size_t)n2 * (sizeof(uint32_t) + (size_t)k * (sizeof(int32_t) + sizeof(float))));
+    g.list2 = (uint32_t*)ism_scratch(ctx, SCR_KNN_LIST2, (size_t)n2 * (sizeof(uint32_t) + (size_t)k * (sizeof(int32_t) + sizeof(float)) + (idx1 ? sizeof(float) : 0)));
     if (!g.q2 || !g.list2) return ISMHIP_ERR_NOMEM;
     g.idx2 = (int32_t*)(g.list2 + n2);
     g.dist2 = (float*)(g.idx2 + (size_t)n2 * k);
-    hipLaunchKernelGGL(k_knn_gather_flagged, dim3(n2), dim3(256), 0, ctx->stream, s1.qrec, n2, q, cb->dim, g.q2, g.list2);
+    g.dk2 = idx1 ? g.dist2 + (size_t)n2 * k : nullptr;
+    hipLaunchKernelGGL(k_knn_gather_flagged, dim3(n2), dim3(256), 0, ctx->stream, s1.qrec, n2, q, cb->dim, g.q2, g.list2, idx1, dist1, k, g.dk2);
     ISM_CHECK_LAUNCH(ctx, "k_knn_gather_flagged");
     return ISMHIP_OK;
 }
@@ -1065,28 +1129,33 @@ int knn_scatter_stage2(ismhip_ctx* ctx, const KnnStage2& g, int k, int32_t* idx_
 }
 
 int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out) {
-    KnnStage1 s1{nullptr, nullptr};
+    KnnStage1 s1{};
     KnnRequest r1; r1.stage1 = &s1; r1.use_pca = 1;
     int rc = run_knn(ctx, cb, ISMHIP_METRIC_L2SQ, nq, q, k, ctx->knn_t1 == 1 && k == 1 ? 1 : 2, idx_out, dist_out, r1);
     if (rc != ISMHIP_OK) return rc;
     KnnStage2 g;
-    rc = knn_gather_stage2(ctx, cb, s1, q, k, g);
+    const bool seed = ctx->knn_stage2_seed;
+    rc = knn_gather_stage2(ctx, cb, s1, q, k, g, seed ? idx_out : nullptr, seed ? dist_out : nullptr);
     if (rc != ISMHIP_OK || g.n2 == 0) return rc;
     const int n2 = g.n2;
+    // Stage 2 is SEEDED (k_knn_seed_thr): every lane slot starts from the threshold that stage 1's k-th exact value allows, so a slot
+    // that does not overflow is proven by construction and few scores ever reach the insertion code. Four candidates per slot and two
+    // splits, as in the cold start (ISMHIP_KNN_STAGE2_SEED=0): two candidates leave room for twice the codebook splits and make the sweep
+    // itself no slower, but 0.9 % of the bench's stage-2 queries have three or more rows below their seed in ONE slot, overflow it and
+    // go to the exact scan (605 instead of 11 queries per launch: + 4.7 ms; on a 114-object shard 97 instead of 6: + 0.07 ms). DESIGN.md §5.
     // Stage 2 runs 256-query tiles x 2 codebook splits on 256 CUs: 65 536 queries are two full rounds of workgroups, 66 000 are three
-    // (measured 4.5 vs 6.7 ms). So a large stage 2 is cut into a multiple of 32 768 queries and a remainder, which (below 4096
-    // queries) takes the merged-splits kernel that fills the chip with splits instead of query tiles.
+    // (measured from a cold start: 4.5 vs 6.7 ms). So a large stage 2 is cut into a multiple of 32 768 queries and a remainder, which
+    // (below 4096 queries) takes the merged-splits kernel that fills the chip with splits instead of query tiles.
     for (int o = 0; o < n2;) {
         const int left = n2 - o, n = left >= 32768 ? left / 32768 * 32768 : left;
-        // a chunk below one full round (a shard of the split on N GPUs: 8 300 stage-2 queries per rank at N = 8) is 33 query tiles x 2
-        // codebook splits = 66 workgroups on 256 CUs (2.17 ms for 8 300 queries, 2.24 for 16 600). Two candidates per lane slot instead
-        // of four would allow four splits, but 1 % of these queries then fail their proof in a whole split and the exact scan costs
-        // more than was won (measured: 9.18 vs 9.39 ms per step of 114 objects, 17.6 vs 15.0 of 227). The 128-query tile variant
-        // (k_knn_l2_ring16<T, 1>: four lane slots per split, so four splits at T = 4) doubles the workgroups twice over instead.
+        // a chunk below one full round (a shard of the split on N GPUs: 8 300 stage-2 queries per rank at N = 8) would be 33 query tiles
+        // x 2 codebook splits = 66 workgroups on 256 CUs. The 128-query tile variant (k_knn_l2_ring16<T, 1>: four lane slots per split,
+        // so four splits) doubles the workgroups twice over instead.
         KnnRequest r2; r2.tname = "knn_stage2"; r2.many_splits = n < 4096;
         // (on the stage-2 image, if the codebook has one: 8 slices per tile instead of 11 on the bench data)
         r2.use_pca = cb->pca2.m > 0 && !(n < 4096) ? 2 : 0;
         r2.half = n >= 4096 && n < 32768 && !ctx->knn_stage2_t4;
+        r2.seed_dk = g.dk2 ? g.dk2 + o : nullptr;
         rc = run_knn(ctx, cb, ISMHIP_METRIC_L2SQ, n, g.q2 + (size_t)o * cb->dim, k, 4, g.idx2 + (size_t)o * k, g.dist2 + (size_t)o * k, r2);
         if (rc != ISMHIP_OK) return rc;
         o += n;
@@ -1191,12 +1260,12 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
     int rc = knn_sqrt_queries(ctx, cb, nq, q, sq, neg);
     if (rc != ISMHIP_OK || neg) return rc;                              // not histogram data: the caller takes the VALU kernel
     taken = true;
-    KnnStage1 s1{nullptr, nullptr};
+    KnnStage1 s1{};
     KnnRequest rh; rh.stage1 = &s1; rh.hell_q = sq;
     rc = run_knn(ctx, cb, ISMHIP_METRIC_CHI2, nq, q, k, 4, idx_out, dist_out, rh);
     if (rc != ISMHIP_OK) return rc;
     KnnStage2 g;
-    rc = knn_gather_stage2(ctx, cb, s1, q, k, g);
+    rc = knn_gather_stage2(ctx, cb, s1, q, k, g, nullptr, nullptr);
     if (rc != ISMHIP_OK || g.n2 == 0) return rc;
     const int n2 = g.n2;
     uint32_t* list2 = g.list2;
@@ -1215,7 +1284,8 @@ int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, c
         uint32_t* sc = cnt + n2p;                                       // [0..2] f16 scalars of the gathered batch, [8] overflow counter
         uint32_t* rows = (uint32_t*)(buf + b_sq2 + b_tau + b_cnt); u16* qimg = (u16*)(buf + b_sq2 + b_tau + b_cnt + b_rows);
         ISM_HIP(ctx, hipMemsetAsync(cnt, 0, b_cnt, ctx->stream));
-        hipLaunchKernelGGL(k_knn_gather_flagged, dim3(n2), dim3(256), 0, ctx->stream, s1.qrec, n2, (const float*)sq, dp, sq2, list2);
+        hipLaunchKernelGGL(k_knn_gather_flagged, dim3(n2), dim3(256), 0, ctx->stream, s1.qrec, n2, (const float*)sq, dp, sq2, list2,
+                           (const int32_t*)nullptr, (const float*)nullptr, k, (float*)nullptr);
         ISM_CHECK_LAUNCH(ctx, "k_knn_gather_flagged");
         rc = knn_f16_emit_image(ctx, cb, xb, sq2, n2, dp, n2p, sc, qimg);
         if (rc != ISMHIP_OK) return rc;

@@ -157,6 +157,27 @@ __device__ __forceinline__ float thr_tau_of(float thr, float qn2, int dim, const
     return t;
 }
 
+// ---- the slot proofs of the squared-L2 re-rank kernels, shared with the kernel that seeds stage 2 (k_knn_seed_thr) ------------------
+// k_knn_rerank (scores approximate the functor value; the derivation is at its proof): a slot whose dropped scores are all >= bnd
+// cannot hold a row that beats or ties the k-th exact value dk
+__device__ __forceinline__ bool knn_l2_slot_proven(float dk, float bnd, float qn2, const VerifyParams& vp) {
+    const float eps_s = knn_eps_s_raw(vp, qn2);
+    const float rhs = qn2 * (1.f - 16.f * KNN_U) + bnd - eps_s;
+    return dk < rhs - vp.ku * fabsf(rhs) - 1e-37f;
+}
+// k_knn_rerank_pca (scores on a rotated, truncated image are lower-bound pieces; derivation at that kernel): what LB(s) needs of one
+// query -- |q^|^2 of its image row, the accumulation error eps_s of its scores, dlt = delta_q + delta_c -- and of the image
+struct PcaLb { float qn2h, eps_s, dlt, inv_sig2; };
+__device__ __forceinline__ float pca_lb_of(const PcaLb& b, float s) {
+    float L = b.qn2h * (1.f - 16.f * KNN_U) + s - b.eps_s;
+    L -= 4.f * KNN_U * (b.qn2h + fabsf(s));                            // rounding of the two additions above
+    if (!(L > 0.f)) return 0.f;                                        // also NaN
+    const float t = sqrtf(L) * (1.f - 4.f * KNN_U) - b.dlt;
+    if (!(t > 0.f)) return 0.f;
+    return t * t * b.inv_sig2 * (1.f - 8.f * KNN_U);
+}
+__device__ __forceinline__ bool pca_slot_proven(float dk, float bnd, const PcaLb& b, float ku) { return dk < pca_lb_of(b, bnd) * (1.f - ku) - 1e-37f; }
+
 // the conditions under which the searches run on the matrix cores (shared by ismhip_knn and ismhip_knn_threshold): a launch big
 // enough to fill the chip, whole 16-byte chunks per descriptor, no A/B override of the candidate kernel
 bool knn_matrix_gate(const ismhip_ctx* ctx, const ismhip_codebook* cb, int nq) {
@@ -185,8 +206,9 @@ struct KnnCandArgs {
 // the instance for T candidates per slot (1 .. 4, else nullptr): WR x 128 codeword rows per tile, QP = 2 with the resident query
 // panel, PRE = 1 the sampling pre-pass
 const void* knn_ring16_kernel(int T, int WR, int QP, int PRE = 0);
-// one candidate launch of kern = knn_ring16_kernel(T, ...); thr0 != nullptr: the sampling pre-pass over every pre_step-th tile first,
-// which leaves the start thresholds of the main launch in thr0[nq rounded up to 256], relaxed by pre_relax
+// one candidate launch of kern = knn_ring16_kernel(T, ...). thr0 != nullptr: every lane slot of query i starts from the threshold
+// thr0[i] (accumulator units) instead of -inf. pre_step > 0: the sampling pre-pass over every pre_step-th tile runs first and leaves
+// those thresholds in thr0[nq rounded up to 256], relaxed by pre_relax; pre_step == 0: the caller has written thr0[nq]
 int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, int threads, size_t lds, KnnCandArgs a,
                       unsigned int* stream_clock, float* thr0, int pre_step, float pre_relax);
 // the candidate instances: bf16x3 on the 256 x 256 or the 128 x 128 tile, f16 on the 128 x 128 tile (nullptr: not built)

@@ -333,6 +333,18 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
         }
         return;
     }
+    // The bound a slot reports is its final threshold. In the loop the two wave rows read each other's thresholds without waiting
+    // (header), so what a wave holds now depends on how the two ran. One exchange behind a barrier makes it the largest threshold
+    // of the column's eight slots -- max(start value, the best (T+1)-th best of any slot: a score above that value is inserted whatever
+    // the order) -- i.e. the same bounds, and the same proofs, for every run of the same search.
+    if (WR == 2) {
+        __syncthreads();
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) sThr[(wv * NT + nt) * 64 + lane] = thr[nt];
+        __syncthreads();
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) thr[nt] = fmaxf(thr[nt], sThr[(pw * NT + nt) * 64 + lane]);
+    }
     // candidates: slot = split*(WR*4*T) + (wr*4 + fq)*T + t; bound slot = split*WR*4 + wr*4 + fq
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -370,7 +382,7 @@ const void* knn_ring16_kernel(int T, int WR, int QP, int PRE) {
 int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, int threads, size_t lds, KnnCandArgs a,
                       unsigned int* stream_clock, float* thr0, int pre_step, float pre_relax) {
     const float* thr_init = nullptr; float* thr_out = nullptr; int tile_step = 1;
-    if (thr0) {
+    if (thr0 && pre_step > 0) {
         const void* pk = knn_ring16_kernel(T, 2, 0, 1);
         const size_t plds = Ring16Lds<2, 0>::total(0);
         const int rc2 = ism_lds_cap(ctx, pk, plds);
@@ -379,8 +391,8 @@ int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, i
         void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax};
         ISM_HIP(ctx, hipLaunchKernel(pk, dim3(grid / a.n_splits), dim3(512), pargs, plds, ctx->stream));      // one split: a workgroup per query tile
         ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16<pre>");
-        thr_init = thr0;
     }
+    thr_init = thr0;
     float no_relax = 0.f;
     void* rargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &stream_clock, &thr_init, &thr_out, &tile_step, &no_relax};
     ISM_HIP(ctx, hipLaunchKernel(kern, dim3(grid), dim3(threads), rargs, lds, ctx->stream));
