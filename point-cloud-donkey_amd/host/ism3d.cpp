@@ -49,6 +49,28 @@ struct DevBuf {
     template <typename T> const T* as() const { return reinterpret_cast<const T*>(p); }
 };
 
+// the seven point arrays of a batch. The rgba buffer is reserved, passed and swapped only when the batch has colour.
+struct PointArrays {
+    DevBuf x, y, z, nx, ny, nz, rgba;
+    std::array<DevBuf*, 6> floats() { return {{&x, &y, &z, &nx, &ny, &nz}}; }
+    ismhip_point_arrays view(bool with_color) {
+        return ismhip_point_arrays{x.as<float>(), y.as<float>(), z.as<float>(), nx.as<float>(), ny.as<float>(), nz.as<float>(),
+                                   with_color ? rgba.as<uint32_t>() : nullptr};
+    }
+    void reserve(size_t n_points, bool with_color) {
+        for (DevBuf* b : floats()) b->reserve(std::max<size_t>(n_points, 1) * 4);
+        if (with_color) rgba.reserve(std::max<size_t>(n_points, 1) * 4);
+    }
+    void swap(PointArrays& o, bool with_color) {
+        for (int a = 0; a < 6; ++a) floats()[a]->swap(*o.floats()[a]);
+        if (with_color) rgba.swap(o.rgba);
+    }
+};
+
+// owning handles of a temporary search surface / codebook (the deleter holds the context)
+typedef std::unique_ptr<ismhip_cloud, std::function<void(ismhip_cloud*)>> TempCloud;
+typedef std::unique_ptr<ismhip_codebook, std::function<void(ismhip_codebook*)>> TempCodebook;
+
 struct DeviceFeatures {
     std::vector<uint32_t> off{0};     // per-object ranges of the kept features
     int dim = 0;
@@ -61,8 +83,8 @@ public:
     ismhip_ctx* ctx = nullptr;
     int n_obj = 0;
     std::vector<uint32_t> pt_off, kp_off;
-    DevBuf x, y, z, nx, ny, nz, rgba, kx, ky, kz, krgba;
-    DevBuf fx, fy, fz, fnx, fny, fnz, frgba;      // second set of point arrays: target of ismhip_filter_normals, swapped in afterwards
+    PointArrays pts, spare;               // the batch's points; spare: target of a compaction (compactPoints), swapped in afterwards
+    DevBuf kx, ky, kz, krgba;
     ismhip_cloud* cloud = nullptr;
     bool has_color = false;
     // vote space of the current batch (Voting::m_votes)
@@ -82,13 +104,14 @@ public:
         if (rc != ISMHIP_OK) throw RuntimeException("ismhip_ctx_create failed");
     }
     ~DeviceSession() {
-        if (cloud) ismhip_cloud_destroy(ctx, cloud);
+        dropCloud();
         if (ctx) ismhip_ctx_destroy(ctx);
     }
     void check(int rc, const char* what) const {
         if (rc != ISMHIP_OK) throw RuntimeException(std::string(what) + " failed (" + std::to_string(rc) + "): " + ismhip_last_error(ctx));
     }
     void sync() const { check(ismhip_sync(ctx), "ismhip_sync"); }
+    void dropCloud() { if (cloud) { ismhip_cloud_destroy(ctx, cloud); cloud = nullptr; } }
     template <typename T> static void h2d(DevBuf& b, const std::vector<T>& v) {
         b.reserve(std::max<size_t>(v.size(), 1) * sizeof(T));
         if (!v.empty() && hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) throw RuntimeException("hipMemcpy H2D failed");
@@ -98,60 +121,73 @@ public:
         v.resize(n);
         if (n && hipMemcpy(v.data(), b.p, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) throw RuntimeException("hipMemcpy D2H failed");
     }
-    // concatenates the objects into SoA arrays, uploads them and builds the search surface
-    // kps == nullptr: voxel-grid keypoints are computed on the device (ismhip_voxel_keypoints) with leaf `device_leaf`
-    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps_p, float cell, bool with_color, float device_leaf = 0.f) {
-        static const std::vector<KeypointSet> no_kps;
-        const bool dev_kp = kps_p == nullptr;
+    // the colours of a cloud or keypoint set in a coloured batch: 0 when it has none
+    static void appendColors(std::vector<uint32_t>& dst, const std::vector<uint32_t>& rgba, size_t n) {
+        if (rgba.size() == n) dst.insert(dst.end(), rgba.begin(), rgba.end());
+        else dst.insert(dst.end(), n, 0u);
+    }
+    // concatenates the objects into SoA arrays and uploads them as the session's batch (pts, pt_off, n_obj, has_color); the search
+    // surface of the previous batch goes first. pad_normals: a cloud without normals gets zeros, otherwise they are taken as they are.
+    void uploadPoints(const std::vector<const PointCloud*>& clouds, bool with_color, bool pad_normals) {
         n_obj = (int)clouds.size();
-        const std::vector<KeypointSet>& kps = dev_kp ? no_kps : *kps_p;
-        static const KeypointSet empty_set;
-        pt_off.assign(1, 0); kp_off.assign(1, 0);
-        std::vector<float> hx, hy, hz, hnx, hny, hnz, hkx, hky, hkz;
-        std::vector<uint32_t> hrgba, hkrgba;
-        for (int o = 0; o < n_obj; ++o) {
-            const PointCloud& c = *clouds[o];
-            hx.insert(hx.end(), c.x.begin(), c.x.end()); hy.insert(hy.end(), c.y.begin(), c.y.end()); hz.insert(hz.end(), c.z.begin(), c.z.end());
-            hnx.insert(hnx.end(), c.nx.begin(), c.nx.end()); hny.insert(hny.end(), c.ny.begin(), c.ny.end()); hnz.insert(hnz.end(), c.nz.begin(), c.nz.end());
-            if (with_color) {
-                if (c.rgba.size() == c.size()) hrgba.insert(hrgba.end(), c.rgba.begin(), c.rgba.end());
-                else hrgba.insert(hrgba.end(), c.size(), 0u);
+        pt_off.assign(1, 0);
+        std::vector<float> h[6]; std::vector<uint32_t> hrgba;
+        for (const PointCloud* c : clouds) {
+            const std::vector<float>* src[6] = {&c->x, &c->y, &c->z, &c->nx, &c->ny, &c->nz};
+            const bool pad = pad_normals && !(c->nx.size() == c->size() && c->ny.size() == c->size() && c->nz.size() == c->size());
+            for (int a = 0; a < 6; ++a) {
+                if (a >= 3 && pad) h[a].insert(h[a].end(), c->size(), 0.f);
+                else h[a].insert(h[a].end(), src[a]->begin(), src[a]->end());
             }
-            pt_off.push_back((uint32_t)hx.size());
-            const KeypointSet& k = dev_kp ? empty_set : kps[o];
-            hkx.insert(hkx.end(), k.x.begin(), k.x.end()); hky.insert(hky.end(), k.y.begin(), k.y.end()); hkz.insert(hkz.end(), k.z.begin(), k.z.end());
-            if (with_color) {
-                if (k.rgba.size() == k.size()) hkrgba.insert(hkrgba.end(), k.rgba.begin(), k.rgba.end());
-                else hkrgba.insert(hkrgba.end(), k.size(), 0u);
-            }
-            kp_off.push_back((uint32_t)hkx.size());
+            if (with_color) appendColors(hrgba, c->rgba, c->size());
+            pt_off.push_back((uint32_t)h[0].size());
         }
-        if (cloud) { ismhip_cloud_destroy(ctx, cloud); cloud = nullptr; }
-        h2d(x, hx); h2d(y, hy); h2d(z, hz); h2d(nx, hnx); h2d(ny, hny); h2d(nz, hnz);
+        dropCloud();
+        for (int a = 0; a < 6; ++a) h2d(*pts.floats()[a], h[a]);
         has_color = with_color;
-        if (with_color) h2d(rgba, hrgba);
-        if (!dev_kp) {
+        if (with_color) h2d(pts.rgba, hrgba);
+    }
+    // uploads the batch and builds the search surface
+    // kps == nullptr: voxel-grid keypoints are computed on the device (ismhip_voxel_keypoints) with leaf `device_leaf`
+    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps, float cell, bool with_color, float device_leaf = 0.f) {
+        uploadPoints(clouds, with_color, false);
+        if (kps) {
+            kp_off.assign(1, 0);
+            std::vector<float> hkx, hky, hkz; std::vector<uint32_t> hkrgba;
+            for (const KeypointSet& k : *kps) {
+                hkx.insert(hkx.end(), k.x.begin(), k.x.end()); hky.insert(hky.end(), k.y.begin(), k.y.end()); hkz.insert(hkz.end(), k.z.begin(), k.z.end());
+                if (with_color) appendColors(hkrgba, k.rgba, k.size());
+                kp_off.push_back((uint32_t)hkx.size());
+            }
             h2d(kx, hkx); h2d(ky, hky); h2d(kz, hkz);
             if (with_color) h2d(krgba, hkrgba);
         }
-        finishBatch(dev_kp, cell, device_leaf);
+        finishBatch(kps == nullptr, cell, device_leaf);
     }
-    // the point arrays of the batch are in HBM (x..rgba, pt_off): keypoints (device voxel grid when dev_kp) and the search surface
+    // the point arrays of the batch are in HBM (pts, pt_off): keypoints (device voxel grid when dev_kp) and the search surface
     void finishBatch(bool dev_kp, float cell, float device_leaf) {
-        const bool with_color = has_color;
-        if (cloud) { ismhip_cloud_destroy(ctx, cloud); cloud = nullptr; }
+        const ismhip_point_arrays p = pts.view(has_color);
+        dropCloud();
         if (dev_kp) {
             // KeypointsVoxelGrid::iComputeKeypoints on the device: centroids stay in HBM, only the per-object counts come back
             const size_t n_pts = pt_off.back();
             kx.reserve(std::max<size_t>(n_pts, 1) * 4); ky.reserve(std::max<size_t>(n_pts, 1) * 4); kz.reserve(std::max<size_t>(n_pts, 1) * 4);
-            if (with_color) krgba.reserve(std::max<size_t>(n_pts, 1) * 4);
+            if (has_color) krgba.reserve(std::max<size_t>(n_pts, 1) * 4);
             kp_off.assign((size_t)n_obj + 1, 0);
-            check(ismhip_voxel_keypoints(ctx, n_obj, pt_off.data(), x.as<float>(), y.as<float>(), z.as<float>(), with_color ? rgba.as<uint32_t>() : nullptr,
-                                         device_leaf, (uint32_t)n_pts, kx.as<float>(), ky.as<float>(), kz.as<float>(),
-                                         with_color ? krgba.as<uint32_t>() : nullptr, kp_off.data()), "ismhip_voxel_keypoints");
+            check(ismhip_voxel_keypoints(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.rgba, device_leaf, (uint32_t)n_pts, kx.as<float>(), ky.as<float>(),
+                                         kz.as<float>(), has_color ? krgba.as<uint32_t>() : nullptr, kp_off.data()), "ismhip_voxel_keypoints");
         }
-        check(ismhip_cloud_create(ctx, n_obj, pt_off.data(), x.as<float>(), y.as<float>(), z.as<float>(), nx.as<float>(), ny.as<float>(),
-                                  nz.as<float>(), with_color ? rgba.as<uint32_t>() : nullptr, cell, &cloud), "ismhip_cloud_create");
+        check(ismhip_cloud_create(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.nx, p.ny, p.nz, p.rgba, cell, &cloud), "ismhip_cloud_create");
+    }
+    // one compaction of the batch's points: reserves the spare arrays, runs `call` (which writes them and the new offsets), makes them
+    // the current ones and replaces pt_off
+    void compactPoints(const char* what, const std::function<int(const ismhip_point_arrays* in, const ismhip_point_arrays* out, uint32_t* new_off)>& call) {
+        spare.reserve(pt_off.back(), has_color);
+        const ismhip_point_arrays in = pts.view(has_color), out = spare.view(has_color);
+        std::vector<uint32_t> new_off(pt_off.size());
+        check(call(&in, &out, new_off.data()), what);
+        pts.swap(spare, has_color);
+        pt_off = new_off;
     }
 };
 
@@ -462,6 +498,17 @@ static int64_t thresholdLists(DeviceSession& s, const ismhip_codebook* codewords
     return total;
 }
 
+// search structure over n_cw codewords only (one dummy vote per word): what the Threshold branch of Codebook::activate searches
+static TempCodebook searchOnlyCodebook(DeviceSession& s, uint32_t n_cw, int D, const float* words) {
+    std::vector<uint32_t> one((size_t)n_cw + 1), zc(n_cw, 0u);
+    std::iota(one.begin(), one.end(), 0u);
+    std::vector<float> zxyz((size_t)n_cw * 3, 0.f), sig1(1, 1.f);
+    ismhip_codebook* cwb = nullptr;
+    s.check(ismhip_codebook_create(s.ctx, (int)n_cw, D, words, nullptr, one.data(), zxyz.data(), nullptr, nullptr, zc.data(), zc.data(),
+                                   nullptr, nullptr, 1, sig1.data(), &cwb), "ismhip_codebook_create");
+    return TempCodebook(cwb, [&s](ismhip_codebook* cb) { ismhip_codebook_destroy(s.ctx, cb); });
+}
+
 // FLANN functors on the host, used by the training statistics only (utils/distance.cpp:33-52)
 // Utils::getRotQuaternion + matrix2Quat (utils.cpp:136-151, 342-380): rows of the matrix are the frame axes; out = (w, x, y, z)
 static void hostRotQuaternion(const float* l, float* out) {
@@ -525,15 +572,8 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
     int32_t n_words = 0;
     size_t n_act = (size_t)n * k;
     if (thr) {                                                   // Threshold (codebook.cpp:139-142): every codeword below the threshold
-        std::vector<uint32_t> one((size_t)n_cw + 1), zc(n_cw, 0u);
-        std::iota(one.begin(), one.end(), 0u);
-        std::vector<float> zxyz((size_t)n_cw * 3, 0.f), sig1(1, 1.f);
-        ismhip_codebook* cwb = nullptr;                          // search structure of the codewords only (one dummy vote per word)
-        s.check(ismhip_codebook_create(s.ctx, (int)n_cw, D, words.data(), nullptr, one.data(), zxyz.data(), nullptr, nullptr, zc.data(), zc.data(),
-                                       nullptr, nullptr, 1, sig1.data(), &cwb), "ismhip_codebook_create");
-        try { n_act = (size_t)thresholdLists(s, cwb, metric, n, f.desc.as<float>(), thr->getThreshold()); }
-        catch (...) { ismhip_codebook_destroy(s.ctx, cwb); throw; }
-        ismhip_codebook_destroy(s.ctx, cwb);
+        const TempCodebook cwb = searchOnlyCodebook(s, n_cw, D, words.data());
+        n_act = (size_t)thresholdLists(s, cwb.get(), metric, n, f.desc.as<float>(), thr->getThreshold());
     }
     std::vector<uint32_t> word_src(n_cw), vote_off((size_t)n_cw + 1), vote_feature(std::max<size_t>(n_act, 1));
     std::vector<float> vote_xyz(std::max<size_t>(n_act, 1) * 3), vote_weight(std::max<size_t>(n_act, 1)), vote_cw(std::max<size_t>(n_act, 1)),
@@ -612,48 +652,44 @@ void Codebook::castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, 
     }
     const uint32_t flags = (m_useClassWeight ? ISMHIP_W_CLASS : 0u) | (m_useVoteWeight ? ISMHIP_W_VOTE : 0u) |
                            (m_useMatchingWeight ? ISMHIP_W_MATCHING : 0u) | (m_useCodewordWeight ? ISMHIP_W_CODEWORD : 0u);
-    if (const auto* thr = dynamic_cast<const ActivationStrategyThreshold*>(knn)) {
-        // list path (codebook.cpp:505-508): every activated codeword casts all its votes; slot of (activation a, vote v) = a*maxv + v
-        const int64_t na = thresholdLists(s, m_dev, metric, n, qdesc ? qdesc : f.desc.as<float>(), thr->getThreshold());
-        const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
-        const size_t ns = (size_t)na * maxv;
-        s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
-        s.check(ismhip_cast_votes_csr(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), s.act_off.as<uint32_t>(),
-                                      na, s.idx.as<int32_t>(), s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(),
-                                      s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(), s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes_csr");
-        if (want_kp) {
-            s.v_kp.reserve(ns * 12); s.v_kpt.reserve(ns * 12);
-            s.check(ismhip_vote_keypoints_csr(s.ctx, m_dev, (int)n, f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), s.act_off.as<uint32_t>(), na,
-                                              s.idx.as<int32_t>(), s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints_csr");
-        }
-        std::vector<uint32_t> act_off;
-        s.d2h(act_off, s.act_off, (size_t)n + 1);
-        s.n_slots = ns;
-        for (int o = 0; o <= s.n_obj; ++o) s.slot_off[o] = act_off[f.off[o]] * (uint32_t)maxv;
-        s.n_classes = (int)m_data.class_sigma.size();
-        return;
-    }
+    const auto* thr = dynamic_cast<const ActivationStrategyThreshold*>(knn);
     const int maxv = ismhip_codebook_max_votes_per_word(m_dev);
-    // refuse what would not fit rather than truncate: ismhip_cast_votes counts activations in an int, vote slots are addressed with
-    // 32 bits (slot_off, ismhip_find_maxima)
-    if ((uint64_t)n * kmax > 0x7fffffffull)
-        throw RuntimeException("castVotes: features x K reaches 2^31 activations, not built");
-    if ((uint64_t)n * kmax * (uint64_t)std::max(maxv, 1) >= (1ull << 32))
-        throw RuntimeException("castVotes: features x K x votes per codeword reaches 2^32 vote slots, not built");
-    const int k = knn->activateKNN(s, m_dev, f, metric, s.idx.as<int32_t>(), s.dist.as<float>(), qdesc);
-    if (qdesc) s.check(ismhip_sync(s.ctx), "ismhip_sync");     // the partial descriptors are released when this function returns
-    const size_t ns = (size_t)n * k * maxv;
-    s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
-    s.check(ismhip_cast_votes(s.ctx, m_dev, flags, (int)n, f.lrf.as<float>(), f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),
-                              s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(),
-                              s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes");
-    if (want_kp) {
-        s.v_kp.reserve(ns * 12); s.v_kpt.reserve(ns * 12);
-        s.check(ismhip_vote_keypoints(s.ctx, m_dev, (int)n, f.kx.as<float>(), f.ky.as<float>(), f.kz.as<float>(), k, s.idx.as<int32_t>(),
-                                      s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints");
+    int64_t na = 0;                                               // activations of the batch
+    int k = 0;                                                    // per feature (K-nearest strategies)
+    if (thr) {
+        // list path (codebook.cpp:505-508): every activated codeword casts all its votes; slot of (activation a, vote v) = a*maxv + v
+        na = thresholdLists(s, m_dev, metric, n, qdesc ? qdesc : f.desc.as<float>(), thr->getThreshold());
+    } else {
+        // refuse what would not fit rather than truncate: ismhip_cast_votes counts activations in an int, vote slots are addressed with
+        // 32 bits (slot_off, ismhip_find_maxima)
+        if ((uint64_t)n * kmax > 0x7fffffffull)
+            throw RuntimeException("castVotes: features x K reaches 2^31 activations, not built");
+        if ((uint64_t)n * kmax * (uint64_t)std::max(maxv, 1) >= (1ull << 32))
+            throw RuntimeException("castVotes: features x K x votes per codeword reaches 2^32 vote slots, not built");
+        k = knn->activateKNN(s, m_dev, f, metric, s.idx.as<int32_t>(), s.dist.as<float>(), qdesc);
+        if (qdesc) s.check(ismhip_sync(s.ctx), "ismhip_sync");     // the partial descriptors are released when this function returns
+        na = (int64_t)n * k;
     }
+    const size_t ns = (size_t)na * maxv;
+    s.v_pos.reserve(ns * 12); s.v_w.reserve(ns * 4); s.v_cls.reserve(ns * 4); s.v_inst.reserve(ns * 4); s.v_cw.reserve(ns * 4); s.v_bs.reserve(ns * 12); s.v_bq.reserve(ns * 16);
+    if (want_kp) { s.v_kp.reserve(ns * 12); s.v_kpt.reserve(ns * 12); }
+    const float *lrf = f.lrf.as<float>(), *kx = f.kx.as<float>(), *ky = f.ky.as<float>(), *kz = f.kz.as<float>();
+    const uint32_t* act_off = s.act_off.as<uint32_t>();
+    const int32_t* idx = s.idx.as<int32_t>();
+    if (thr) {
+        s.check(ismhip_cast_votes_csr(s.ctx, m_dev, flags, (int)n, lrf, kx, ky, kz, act_off, na, idx, s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(),
+                                      s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(), s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes_csr");
+        if (want_kp) s.check(ismhip_vote_keypoints_csr(s.ctx, m_dev, (int)n, kx, ky, kz, act_off, na, idx, s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints_csr");
+    } else {
+        s.check(ismhip_cast_votes(s.ctx, m_dev, flags, (int)n, lrf, kx, ky, kz, k, idx, s.dist.as<float>(), s.v_pos.as<float>(), s.v_w.as<float>(),
+                                  s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(), s.v_cw.as<int32_t>(), s.v_bq.as<float>(), s.v_bs.as<float>()), "ismhip_cast_votes");
+        if (want_kp) s.check(ismhip_vote_keypoints(s.ctx, m_dev, (int)n, kx, ky, kz, k, idx, s.v_kp.as<float>(), s.v_kpt.as<float>()), "ismhip_vote_keypoints");
+    }
+    // an object's first slot: its first activation (list path: from the activation ranges; K-nearest: k per feature) times maxv
+    std::vector<uint32_t> first_act;
+    if (thr) s.d2h(first_act, s.act_off, (size_t)n + 1);
     s.n_slots = ns;
-    for (int o = 0; o <= s.n_obj; ++o) s.slot_off[o] = f.off[o] * (uint32_t)(k * maxv);
+    for (int o = 0; o <= s.n_obj; ++o) s.slot_off[o] = (thr ? first_act[f.off[o]] : f.off[o] * (uint32_t)k) * (uint32_t)maxv;
     s.n_classes = (int)m_data.class_sigma.size();
 }
 
@@ -908,6 +944,33 @@ int Voting::maxFilter() const {                                // voting.cpp:262
 // the host asks for 32 and, when some object fills them all, again for 1024 = the kernels' own per-object limit, beyond which
 // ismhip_sync reports the truncation.
 struct Voting::MaximaBuffers { DevBuf n_max, pos, w, cls, inst, iw, bs, bq, nv, score; int M = 32; void reserve(int n_obj, int C); };
+// The maxima search of both back ends: P carries the back end's own fields, the fields the two parameter structs share are filled
+// here; `entry` / `ransac_entry` are its plain entry point and the one with the RANSAC vote filter (two arguments more).
+template <typename Params, typename Entry, typename RansacEntry>
+void Voting::searchMaxima(DeviceSession& s, Params P, Entry entry, RansacEntry ransac_entry, const char* what, std::vector<std::vector<VotingMaximum>>& out) const {
+    P.n_classes = std::max(1, s.n_classes);
+    P.min_votes_threshold = m_minVotesThreshold; P.min_threshold = m_minThreshold; P.best_k = m_bestK;
+    P.max_filter = maxFilter();
+    for (int M : {32, 1024}) {
+        MaximaBuffers B; B.M = M; B.reserve(s.n_obj, P.n_classes);
+        P.max_maxima = M;
+        if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }              // voting.cpp:210-215
+        auto call = [&](auto fn, auto... filter_args) {
+            return fn(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
+                      s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
+                      B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), filter_args...);
+        };
+        if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127: the filter runs inside the maxima search
+            const std::vector<float> class_thr = ransacThresholdPerClass(P.n_classes);
+            ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
+            s.check(call(ransac_entry, &R, (float*)nullptr), (std::string(what) + "_ransac").c_str());
+            s.sync();                                               // class_thr is read by the launch
+        } else {
+            s.check(call(entry), what);
+        }
+        if (collectMaxima(s, B, out, m_averageRotation)) break;     // (with 1024 slots it takes what there is)
+    }
+}
 VotingMeanShift::VotingMeanShift() {              // voting_mean_shift.cpp:20-27
     addParameter(m_bandwidth, "Bandwidth", 0.2f);
     addParameter(m_threshold, "Threshold", 1e-3f);
@@ -916,32 +979,13 @@ VotingMeanShift::VotingMeanShift() {              // voting_mean_shift.cpp:20-27
     addParameter(m_maxima_suppression_type, "MaximaSuppression", std::string("Average"));
 }
 void VotingMeanShift::iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) {
-    const int C = std::max(1, s.n_classes);
-    for (int M : {32, 1024}) {
     ismhip_maxima_params P{};
-    const std::vector<float> class_bw = searchDistPerClass(m_bandwidth, C);      // voting_mean_shift.cpp:46-49
-    P.n_classes = C; P.class_bandwidth_h = class_bw.empty() ? nullptr : class_bw.data(); P.bandwidth = m_bandwidth; P.threshold = m_threshold; P.max_iter = m_maxIter;
+    const std::vector<float> class_bw = searchDistPerClass(m_bandwidth, std::max(1, s.n_classes));      // voting_mean_shift.cpp:46-49
+    P.class_bandwidth_h = class_bw.empty() ? nullptr : class_bw.data(); P.bandwidth = m_bandwidth; P.threshold = m_threshold; P.max_iter = m_maxIter;
     P.kernel = m_kernel == "Uniform" ? ISMHIP_KERNEL_UNIFORM : ISMHIP_KERNEL_GAUSSIAN;
     P.suppression = m_maxima_suppression_type == "Average" ? ISMHIP_SUPPRESS_AVERAGE : (m_maxima_suppression_type == "Suppress" ? ISMHIP_SUPPRESS_SUPPRESS : ISMHIP_SUPPRESS_NONE);
-    P.min_votes_threshold = m_minVotesThreshold; P.min_threshold = m_minThreshold; P.best_k = m_bestK; P.max_maxima = M;
-    P.max_filter = maxFilter();
-    MaximaBuffers B; B.M = M; B.reserve(s.n_obj, C);
-    if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }              // voting.cpp:210-215
     P.single_object_max_type = singleObjectMaxType(); P.object_centroid = s.obj_cen.as<float>(); P.object_radius = s.obj_rad.as<float>();
-    auto call = [&](auto entry, auto... filter_args) {          // the plain entry, or the RANSAC one with its two arguments more
-        return entry(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                     s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                     B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), filter_args...);
-    };
-    if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127: the filter runs inside the maxima search
-        const std::vector<float> class_thr = ransacThresholdPerClass(C);
-        ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
-        s.check(call(ismhip_find_maxima_ransac, &R, (float*)nullptr), "ismhip_find_maxima_ransac");
-        s.sync();                                               // class_thr is read by the launch
-    } else
-    s.check(call(ismhip_find_maxima), "ismhip_find_maxima");
-    if (collectMaxima(s, B, out, m_averageRotation) || M == 1024) break;
-    }
+    searchMaxima(s, P, ismhip_find_maxima, ismhip_find_maxima_ransac, "ismhip_find_maxima", out);
 }
 void Voting::MaximaBuffers::reserve(int n_obj, int C) {
     const size_t t = (size_t)n_obj * M;
@@ -978,35 +1022,15 @@ VotingHough3D::VotingHough3D() {                  // voting_hough_3d.cpp:15-26
 }
 void VotingHough3D::iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) {
     if (m_single_object_mode) LOG_WARN("SingleObjectMode is not supported with Hough3D - switch to MeanShift to use it!");   // :42-43
-    const int C = std::max(1, s.n_classes);
-    for (int M : {32, 1024}) {
     ismhip_hough_params P{};
-    P.n_classes = C;
     for (int d = 0; d < 3; ++d) { P.min_coord[d] = (float)m_minCoord[d]; P.max_coord[d] = (float)m_maxCoord[d]; }
     // :45-47: MaximaHandler::setRadius(BinSize[0] / 2); the bins become cubes of edge 2 * getSearchDistForClass (= BinSize[0] with "Config")
     P.bin_size = 2.0f * (float)(m_binSize[0] / 2);
-    std::vector<float> class_bin = searchDistPerClass((float)(m_binSize[0] / 2), C);
+    std::vector<float> class_bin = searchDistPerClass((float)(m_binSize[0] / 2), std::max(1, s.n_classes));
     for (float& b : class_bin) b *= 2.0f;
     P.class_bin_h = class_bin.empty() ? nullptr : class_bin.data();
     P.use_interpolation = m_useInterpolation ? 1 : 0; P.rel_threshold = m_relThreshold;
-    P.min_votes_threshold = m_minVotesThreshold; P.min_threshold = m_minThreshold; P.best_k = m_bestK;
-    P.max_filter = maxFilter();
-    MaximaBuffers B; B.M = M; P.max_maxima = B.M; B.reserve(s.n_obj, C);
-    if (m_averageRotation) { P.vote_bbox_quat = s.v_bq.as<float>(); P.max_bbox_quat_out = B.bq.as<float>(); }
-    auto call = [&](auto entry, auto... filter_args) {          // the plain entry, or the RANSAC one with its two arguments more
-        return entry(s.ctx, s.n_obj, s.slot_off.data(), s.v_pos.as<float>(), s.v_w.as<float>(), s.v_cls.as<int32_t>(), s.v_inst.as<int32_t>(),
-                     s.v_bs.as<float>(), &P, B.n_max.as<int32_t>(), B.pos.as<float>(), B.w.as<float>(), B.cls.as<int32_t>(), B.inst.as<int32_t>(),
-                     B.iw.as<float>(), B.bs.as<float>(), B.nv.as<int32_t>(), B.score.as<float>(), filter_args...);
-    };
-    if (m_vote_filtering_with_ransac) {                         // voting.cpp:110-127
-        const std::vector<float> class_thr = ransacThresholdPerClass(C);
-        ismhip_ransac_params R{}; fillRansacParams(s, class_thr, R);
-        s.check(call(ismhip_hough3d_maxima_ransac, &R, (float*)nullptr), "ismhip_hough3d_maxima_ransac");
-        s.sync();                                               // class_thr is read by the launch
-    } else
-    s.check(call(ismhip_hough3d_maxima), "ismhip_hough3d_maxima");
-    if (collectMaxima(s, B, out, m_averageRotation) || M == 1024) break;
-    }
+    searchMaxima(s, P, ismhip_hough3d_maxima, ismhip_hough3d_maxima_ransac, "ismhip_hough3d_maxima", out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1259,6 +1283,29 @@ static bool firstNormalValid(const PointCloud& c) {   // :615-625 — decided fr
     return true;
 }
 
+// adds the milliseconds since the previous lap (or since its construction) to an entry of the processing times
+struct LapTimer {
+    std::map<std::string, double>& times;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void lap(const char* key) {
+        const auto now = std::chrono::steady_clock::now();
+        times[key] += std::chrono::duration<double, std::milli>(now - last).count();
+        last = now;
+    }
+};
+
+// cell size of the descriptor stage's search surface (the pre-filter test relies on SOR searching the same grid)
+static float descriptorSearchCell(const Features& f) {
+    return std::min(f.getRadius(), f.getType() == "FPFH" ? f.getRadius() : f.getReferenceFrameRadius()) * 0.4f;
+}
+
+// a copy of the cloud whose normals are all zero: "has no normals" to firstNormalValid, and the shape the normal estimation fills
+static PointCloud withZeroedNormals(const PointCloud& src) {
+    PointCloud c = src;
+    c.nx.assign(c.size(), 0.f); c.ny.assign(c.size(), 0.f); c.nz.assign(c.size(), 0.f);
+    return c;
+}
+
 // The head of computeFeatures (:739-758, :810-821): statistical outlier removal, radius outlier removal on its output, z pass-through
 // on that. The whole batch goes up once, every filter writes a keep mask in HBM and ismhip_compact_points closes the gaps (normals
 // and colours travel along); the surviving points then come back to the host, where the existing routes (device normals, mixed
@@ -1266,78 +1313,54 @@ static bool firstNormalValid(const PointCloud& c) {   // :615-625 — decided fr
 std::vector<const PointCloud*> ImplicitShapeModel::preFilterClouds(const std::vector<const PointCloud*>& clouds, std::vector<std::unique_ptr<PointCloud>>& store) {
     const bool cut = m_cutoff_distance_z > 0.f;
     if (!(m_use_sor || m_use_ror || cut) || clouds.empty()) return clouds;
-    const auto t0 = std::chrono::steady_clock::now();
+    LapTimer timer{m_processing_times};
     DeviceSession& s = session();
-    const int n_obj = (int)clouds.size();
     bool with_color = false;
     for (const PointCloud* c : clouds) with_color |= !c->empty() && c->rgba.size() == c->size();
-    std::vector<float> h[6]; std::vector<uint32_t> hc, off(1, 0);
-    for (const PointCloud* c : clouds) {
-        const bool nrm = c->nx.size() == c->size() && c->ny.size() == c->size() && c->nz.size() == c->size();
-        h[0].insert(h[0].end(), c->x.begin(), c->x.end()); h[1].insert(h[1].end(), c->y.begin(), c->y.end()); h[2].insert(h[2].end(), c->z.begin(), c->z.end());
-        if (nrm) { h[3].insert(h[3].end(), c->nx.begin(), c->nx.end()); h[4].insert(h[4].end(), c->ny.begin(), c->ny.end()); h[5].insert(h[5].end(), c->nz.begin(), c->nz.end()); }
-        else for (int a = 3; a < 6; ++a) h[a].insert(h[a].end(), c->size(), 0.f);
-        if (with_color) { if (c->rgba.size() == c->size()) hc.insert(hc.end(), c->rgba.begin(), c->rgba.end()); else hc.insert(hc.end(), c->size(), 0u); }
-        off.push_back((uint32_t)h[0].size());
-    }
-    if (s.cloud) { ismhip_cloud_destroy(s.ctx, s.cloud); s.cloud = nullptr; }
-    DevBuf* cur[7] = {&s.x, &s.y, &s.z, &s.nx, &s.ny, &s.nz, &s.rgba};
-    DevBuf* alt[7] = {&s.fx, &s.fy, &s.fz, &s.fnx, &s.fny, &s.fnz, &s.frgba};
-    for (int a = 0; a < 6; ++a) DeviceSession::h2d(*cur[a], h[a]);
-    if (with_color) DeviceSession::h2d(s.rgba, hc);
-    const size_t n_in = std::max<size_t>(off.back(), 1);
-    for (int a = 0; a < 7; ++a) if (a < 6 || with_color) alt[a]->reserve(n_in * 4);
-    DevBuf keep; keep.reserve(n_in);
-    auto arrays = [&](DevBuf* const b[7]) {
-        return ismhip_point_arrays{b[0]->as<float>(), b[1]->as<float>(), b[2]->as<float>(), b[3]->as<float>(), b[4]->as<float>(), b[5]->as<float>(),
-                                   with_color ? b[6]->as<uint32_t>() : nullptr};
-    };
-    auto with_cloud = [&](float cell, const std::function<void(ismhip_cloud*)>& fn) {
+    s.uploadPoints(clouds, with_color, true);
+    DevBuf keep; keep.reserve(std::max<size_t>(s.pt_off.back(), 1));
+    auto surface = [&](float cell) {                            // a temporary search surface over the points as they are now
+        const ismhip_point_arrays p = s.pts.view(false);
         ismhip_cloud* c = nullptr;
-        s.check(ismhip_cloud_create(s.ctx, n_obj, off.data(), s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>(),
-                                    nullptr, cell, &c), "ismhip_cloud_create");
-        try { fn(c); } catch (...) { ismhip_cloud_destroy(s.ctx, c); throw; }
-        ismhip_cloud_destroy(s.ctx, c);
+        s.check(ismhip_cloud_create(s.ctx, s.n_obj, s.pt_off.data(), p.x, p.y, p.z, p.nx, p.ny, p.nz, nullptr, cell, &c), "ismhip_cloud_create");
+        return TempCloud(c, [&s](ismhip_cloud* p) { ismhip_cloud_destroy(s.ctx, p); });
     };
     auto compact = [&]() {
-        if (off.back() == 0) return;
-        const ismhip_point_arrays in = arrays(cur), out = arrays(alt);
-        std::vector<uint32_t> new_off(off.size());
-        s.check(ismhip_compact_points(s.ctx, n_obj, off.data(), &in, keep.as<uint8_t>(), &out, new_off.data()), "ismhip_compact_points");
-        for (int a = 0; a < 7; ++a) if (a < 6 || with_color) cur[a]->swap(*alt[a]);
-        off = new_off;
+        s.compactPoints("ismhip_compact_points", [&](const ismhip_point_arrays* in, const ismhip_point_arrays* out, uint32_t* new_off) {
+            return ismhip_compact_points(s.ctx, s.n_obj, s.pt_off.data(), in, keep.as<uint8_t>(), out, new_off);
+        });
     };
     // the search grids: SOR on the descriptor stage's cell (its result does not depend on it), ROR on cells of one radius
-    const float cell = std::min(m_feature_descriptor->getRadius(), m_feature_descriptor->getType() == "FPFH" ? m_feature_descriptor->getRadius()
-                                                                                                           : m_feature_descriptor->getReferenceFrameRadius()) * 0.4f;
-    if (m_use_sor && off.back() > 0) {
+    if (m_use_sor && s.pt_off.back() > 0) {
         LOG_INFO("performing statistical outlier removal");
-        with_cloud(cell, [&](ismhip_cloud* c) {
-            s.check(ismhip_filter_statistical(s.ctx, c, m_sor_mean_k, m_sor_stddev_mul, keep.as<uint8_t>(), nullptr, nullptr), "ismhip_filter_statistical");
-        });
+        {
+            const TempCloud c = surface(descriptorSearchCell(*m_feature_descriptor));
+            s.check(ismhip_filter_statistical(s.ctx, c.get(), m_sor_mean_k, m_sor_stddev_mul, keep.as<uint8_t>(), nullptr, nullptr), "ismhip_filter_statistical");
+        }
         compact();
     }
-    if (m_use_ror && off.back() > 0) {
+    if (m_use_ror && s.pt_off.back() > 0) {
         LOG_INFO("performing radius outlier removal");
-        with_cloud(m_ror_radius, [&](ismhip_cloud* c) {
-            s.check(ismhip_filter_radius(s.ctx, c, m_ror_radius, m_ror_min_neighbors, keep.as<uint8_t>(), nullptr), "ismhip_filter_radius");
-        });
+        {
+            const TempCloud c = surface(m_ror_radius);
+            s.check(ismhip_filter_radius(s.ctx, c.get(), m_ror_radius, m_ror_min_neighbors, keep.as<uint8_t>(), nullptr), "ismhip_filter_radius");
+        }
         compact();
     }
-    if (cut && off.back() > 0) {
+    if (cut && s.pt_off.back() > 0) {
         LOG_INFO("performing pass through filtering");
-        s.check(ismhip_filter_passthrough_z(s.ctx, off.back(), s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), 0.f, m_cutoff_distance_z, keep.as<uint8_t>()),
-                "ismhip_filter_passthrough_z");
+        s.check(ismhip_filter_passthrough_z(s.ctx, s.pt_off.back(), s.pts.x.as<float>(), s.pts.y.as<float>(), s.pts.z.as<float>(), 0.f, m_cutoff_distance_z,
+                                            keep.as<uint8_t>()), "ismhip_filter_passthrough_z");
         compact();
     }
-    const size_t n_out = off.back();
-    for (int a = 0; a < 6; ++a) s.d2h(h[a], *cur[a], n_out);
-    if (with_color) s.d2h(hc, s.rgba, n_out);
+    std::vector<float> h[6]; std::vector<uint32_t> hc;
+    for (int a = 0; a < 6; ++a) s.d2h(h[a], *s.pts.floats()[a], s.pt_off.back());
+    if (with_color) s.d2h(hc, s.pts.rgba, s.pt_off.back());
     std::vector<const PointCloud*> out;
-    for (int o = 0; o < n_obj; ++o) {
+    for (size_t o = 0; o < clouds.size(); ++o) {
         const PointCloud& src = *clouds[o];
         std::unique_ptr<PointCloud> c(new PointCloud());
-        const size_t b = off[o], e = off[o + 1];
+        const size_t b = s.pt_off[o], e = s.pt_off[o + 1];
         c->x.assign(h[0].begin() + b, h[0].begin() + e); c->y.assign(h[1].begin() + b, h[1].begin() + e); c->z.assign(h[2].begin() + b, h[2].begin() + e);
         if (src.nx.size() == src.size() && src.ny.size() == src.size() && src.nz.size() == src.size()) {
             c->nx.assign(h[3].begin() + b, h[3].begin() + e); c->ny.assign(h[4].begin() + b, h[4].begin() + e); c->nz.assign(h[5].begin() + b, h[5].begin() + e);
@@ -1346,132 +1369,120 @@ std::vector<const PointCloud*> ImplicitShapeModel::preFilterClouds(const std::ve
         out.push_back(c.get());
         store.push_back(std::move(c));
     }
-    // an entry of its own next to the reference's seven keys, present only when a filter is enabled
-    m_processing_times["filters"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timer.lap("filters");       // an entry of its own next to the reference's seven keys, present only when a filter is enabled
     return out;
 }
 
 std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::vector<const PointCloud*>& clouds_in, bool) {   // :733-927
     DeviceSession& s = session();
-    auto t0 = std::chrono::steady_clock::now();
+    LapTimer timer{m_processing_times};
     // clouds that come without normals get them on the device (computeNormals :940-1032, ConsistentNormalsMethod 2), then lose the
     // points whose normal is NaN (filterNormals :1034-1075); the features are computed on those completed copies
     std::vector<const PointCloud*> clouds = clouds_in;
     std::vector<std::unique_ptr<PointCloud>> completed;
-    const float cell = std::min(m_feature_descriptor->getRadius(), m_feature_descriptor->getType() == "FPFH" ? m_feature_descriptor->getRadius()
-                                                                                                           : m_feature_descriptor->getReferenceFrameRadius()) * 0.4f;
+    const float cell = descriptorSearchCell(*m_feature_descriptor);
     // VoxelGrid keypoints are taken on the device with the batch (ismhip_voxel_keypoints); any other detector, or
     // ISM3D_HOST_KEYPOINTS=1, runs the host implementation per object and uploads its result
     const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(m_keypoints_detector.get());
     const char* host_kp = getenv("ISM3D_HOST_KEYPOINTS");
     const bool dev_kp = vg && !(host_kp && host_kp[0] == '1');
-    auto estimate = [&]() {
-        if (m_consistent_normals_method == 2)
-            s.check(ismhip_estimate_normals(s.ctx, s.cloud, m_normal_radius, s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>()), "ismhip_estimate_normals");
-        else                                                // :969-1003
-            s.check(ismhip_estimate_normals_pca(s.ctx, s.cloud, m_normal_radius, m_consistent_normals_method, s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>()),
-                    "ismhip_estimate_normals_pca");
+    auto describe = [&]() {
+        auto f = (*m_feature_descriptor)(s);
+        s.sync();
+        timer.lap("features");
+        return f;
     };
-    {
-        std::vector<size_t> need;
-        for (size_t i = 0; i < clouds.size(); ++i) if (!firstNormalValid(*clouds[i])) need.push_back(i);
-        for (size_t i : need)
-            if (clouds[i]->organized) {       // computeNormals :948-966 (pcl::IntegralImageNormalEstimation, AVERAGE_3D_GRADIENT) is not built
-                LOG_WARN("organized input cloud without normals: the reference estimates them from the depth image (IntegralImageNormalEstimation); "
-                         "here ConsistentNormalsMethod " << m_consistent_normals_method << " is used as for unorganized clouds -- the normals differ");
-                break;
-            }
-        if (!need.empty() && (m_consistent_normals_method < 0 || m_consistent_normals_method > 2))
+    std::vector<size_t> need;
+    for (size_t i = 0; i < clouds.size(); ++i) if (!firstNormalValid(*clouds[i])) need.push_back(i);
+    for (size_t i : need)
+        if (clouds[i]->organized) {       // computeNormals :948-966 (pcl::IntegralImageNormalEstimation, AVERAGE_3D_GRADIENT) is not built
+            LOG_WARN("organized input cloud without normals: the reference estimates them from the depth image (IntegralImageNormalEstimation); "
+                     "here ConsistentNormalsMethod " << m_consistent_normals_method << " is used as for unorganized clouds -- the normals differ");
+            break;
+        }
+    if (!need.empty()) {
+        if (m_consistent_normals_method < 0 || m_consistent_normals_method > 2)
             throw RuntimeException("input cloud has no normals and ConsistentNormalsMethod " + std::to_string(m_consistent_normals_method) +
                                    " is not built (built: 0 = PCA towards the origin, 1 = PCA away from the centroid, 2 = SHOT reference frames)");
+        // Every cloud of the batch needs normals and the keypoints are taken on the device: the points are uploaded once (with
+        // their colours), the normals are estimated, the NaN ones leave (ismhip_filter_normals) and the search surface of the
+        // descriptor stage is built over the compacted arrays -- nothing returns to the host in between.
+        // Mixed batches and host-side keypoint detectors (or ISM3D_HOST_NORMAL_FILTER=1): the estimated normals come back, the filter
+        // runs here and the completed copies are uploaded with the rest.
         const char* host_nf = getenv("ISM3D_HOST_NORMAL_FILTER");
-        if (need.size() == clouds.size() && dev_kp && !(host_nf && host_nf[0] == '1')) {
-            // every cloud of the batch needs normals and the keypoints are taken on the device: the points are uploaded once (with
-            // their colours), the normals are estimated, the NaN ones leave (ismhip_filter_normals) and the search surface of the
-            // descriptor stage is built over the compacted arrays -- nothing returns to the host in between
-            std::vector<std::unique_ptr<PointCloud>> tmp;
-            std::vector<const PointCloud*> part;
-            for (const PointCloud* src : clouds) {
-                tmp.emplace_back(new PointCloud(*src));
-                PointCloud& c = *tmp.back();
-                c.nx.assign(c.size(), 0.f); c.ny.assign(c.size(), 0.f); c.nz.assign(c.size(), 0.f);
-                part.push_back(&c);
-            }
-            const std::vector<KeypointSet> none(part.size());
-            const bool with_color = m_feature_descriptor->needsColor();
-            s.uploadBatch(part, &none, m_normal_radius * 0.5f, with_color);
-            estimate();
-            const size_t n_all = std::max<size_t>(s.pt_off.back(), 1);
-            DevBuf* dst[7] = {&s.fx, &s.fy, &s.fz, &s.fnx, &s.fny, &s.fnz, &s.frgba};
-            for (int a = 0; a < 7; ++a) if (a < 6 || with_color) dst[a]->reserve(n_all * 4);
-            const ismhip_point_arrays in = {s.x.as<float>(), s.y.as<float>(), s.z.as<float>(), s.nx.as<float>(), s.ny.as<float>(), s.nz.as<float>(),
-                                            with_color ? s.rgba.as<uint32_t>() : nullptr};
-            const ismhip_point_arrays out = {s.fx.as<float>(), s.fy.as<float>(), s.fz.as<float>(), s.fnx.as<float>(), s.fny.as<float>(), s.fnz.as<float>(),
-                                             with_color ? s.frgba.as<uint32_t>() : nullptr};
-            std::vector<uint32_t> new_off(s.pt_off.size());
-            s.check(ismhip_filter_normals(s.ctx, s.n_obj, s.pt_off.data(), &in, &out, new_off.data()), "ismhip_filter_normals");
-            s.x.swap(s.fx); s.y.swap(s.fy); s.z.swap(s.fz); s.nx.swap(s.fnx); s.ny.swap(s.fny); s.nz.swap(s.fnz);
-            if (with_color) s.rgba.swap(s.frgba);
-            s.pt_off = new_off;
-            auto t1 = std::chrono::steady_clock::now();
-            m_processing_times["normals"] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        const bool on_device = need.size() == clouds.size() && dev_kp && !(host_nf && host_nf[0] == '1');
+        std::vector<PointCloud> tmp;
+        tmp.reserve(need.size());
+        std::vector<const PointCloud*> part;
+        for (size_t i : need) { tmp.push_back(withZeroedNormals(*clouds[i])); part.push_back(&tmp.back()); }
+        const std::vector<KeypointSet> none(part.size());
+        s.uploadBatch(part, &none, m_normal_radius * 0.5f, on_device && m_feature_descriptor->needsColor());
+        if (m_consistent_normals_method == 2)
+            s.check(ismhip_estimate_normals(s.ctx, s.cloud, m_normal_radius, s.pts.nx.as<float>(), s.pts.ny.as<float>(), s.pts.nz.as<float>()), "ismhip_estimate_normals");
+        else                                                // :969-1003
+            s.check(ismhip_estimate_normals_pca(s.ctx, s.cloud, m_normal_radius, m_consistent_normals_method, s.pts.nx.as<float>(), s.pts.ny.as<float>(),
+                                                s.pts.nz.as<float>()), "ismhip_estimate_normals_pca");
+        if (on_device) {
+            s.compactPoints("ismhip_filter_normals", [&](const ismhip_point_arrays* in, const ismhip_point_arrays* out, uint32_t* new_off) {
+                return ismhip_filter_normals(s.ctx, s.n_obj, s.pt_off.data(), in, out, new_off);
+            });
+            timer.lap("normals");
             s.finishBatch(true, cell, vg->getLeafSize());
-            auto t2 = std::chrono::steady_clock::now();
-            m_processing_times["keypoints"] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-            auto f = (*m_feature_descriptor)(s);
-            s.sync();
-            m_processing_times["features"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
-            return f;
+            timer.lap("keypoints");
+            return describe();
         }
-        if (!need.empty()) {
-            // mixed batches and host-side keypoint detectors: the estimated normals come back, the filter runs here and the completed
-            // copies are uploaded with the rest
-            std::vector<std::unique_ptr<PointCloud>> tmp;
-            std::vector<const PointCloud*> part;
-            for (size_t i : need) {
-                tmp.emplace_back(new PointCloud(*clouds[i]));
-                PointCloud& c = *tmp.back();
-                c.nx.assign(c.size(), 0.f); c.ny.assign(c.size(), 0.f); c.nz.assign(c.size(), 0.f);
-                part.push_back(&c);
+        std::vector<float> hnx, hny, hnz;
+        const size_t n_all = s.pt_off.back();
+        s.d2h(hnx, s.pts.nx, n_all); s.d2h(hny, s.pts.ny, n_all); s.d2h(hnz, s.pts.nz, n_all);
+        for (size_t k = 0; k < need.size(); ++k) {
+            const PointCloud& src = tmp[k];
+            std::unique_ptr<PointCloud> out(new PointCloud());
+            const size_t b = s.pt_off[k];
+            const bool col = src.rgba.size() == src.size();
+            for (size_t i = 0; i < src.size(); ++i) {
+                const float a = hnx[b + i], bb = hny[b + i], cc = hnz[b + i];
+                if (std::isnan(a) || std::isnan(bb) || std::isnan(cc)) continue;
+                out->x.push_back(src.x[i]); out->y.push_back(src.y[i]); out->z.push_back(src.z[i]);
+                out->nx.push_back(a); out->ny.push_back(bb); out->nz.push_back(cc);
+                if (col) out->rgba.push_back(src.rgba[i]);
             }
-            const std::vector<KeypointSet> none(part.size());
-            s.uploadBatch(part, &none, m_normal_radius * 0.5f, false);
-            estimate();
-            std::vector<float> hnx, hny, hnz;
-            const size_t n_all = s.pt_off.back();
-            s.d2h(hnx, s.nx, n_all); s.d2h(hny, s.ny, n_all); s.d2h(hnz, s.nz, n_all);
-            for (size_t k = 0; k < need.size(); ++k) {
-                const PointCloud& src = *tmp[k];
-                std::unique_ptr<PointCloud> out(new PointCloud());
-                const size_t b = s.pt_off[k];
-                const bool col = src.rgba.size() == src.size();
-                for (size_t i = 0; i < src.size(); ++i) {
-                    const float a = hnx[b + i], bb = hny[b + i], cc = hnz[b + i];
-                    if (std::isnan(a) || std::isnan(bb) || std::isnan(cc)) continue;
-                    out->x.push_back(src.x[i]); out->y.push_back(src.y[i]); out->z.push_back(src.z[i]);
-                    out->nx.push_back(a); out->ny.push_back(bb); out->nz.push_back(cc);
-                    if (col) out->rgba.push_back(src.rgba[i]);
-                }
-                clouds[need[k]] = out.get();
-                completed.push_back(std::move(out));
-            }
+            clouds[need[k]] = out.get();
+            completed.push_back(std::move(out));
         }
     }
-    auto t1 = t0;
     if (dev_kp) {
         s.uploadBatch(clouds, nullptr, cell, m_feature_descriptor->needsColor(), vg->getLeafSize());
-        t1 = std::chrono::steady_clock::now();
+        timer.lap("keypoints");
     } else {
         std::vector<KeypointSet> kps;
         for (const PointCloud* c : clouds) kps.push_back((*m_keypoints_detector)(*c));
-        t1 = std::chrono::steady_clock::now();
+        timer.lap("keypoints");
         s.uploadBatch(clouds, &kps, cell, m_feature_descriptor->needsColor());
     }
-    m_processing_times["keypoints"] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    auto f = (*m_feature_descriptor)(s);
-    s.sync();
-    m_processing_times["features"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    return f;
+    return describe();
+}
+
+// Utils::computeAABB (utils.cpp:222-233): size = max - min, position = min + size / 2
+static void cloudAABB(const PointCloud& c, std::array<float, 3>& center, std::array<float, 3>& size) {
+    float mn[3] = {c.x[0], c.y[0], c.z[0]}, mx[3] = {c.x[0], c.y[0], c.z[0]};
+    for (size_t i = 0; i < c.size(); ++i) {
+        mn[0] = std::min(mn[0], c.x[i]); mx[0] = std::max(mx[0], c.x[i]); mn[1] = std::min(mn[1], c.y[i]); mx[1] = std::max(mx[1], c.y[i]);
+        mn[2] = std::min(mn[2], c.z[i]); mx[2] = std::max(mx[2], c.z[i]);
+    }
+    size = {mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]};
+    center = {mn[0] + size[0] / 2, mn[1] + size[1] / 2, mn[2] + size[2] / 2};
+}
+// Utils::computeCloudRadius (utils.cpp:302-321): largest distance to the centroid (pcl::compute3DCentroid into a Vector4f)
+static float cloudRadius(const PointCloud& c) {
+    float cs[3] = {0, 0, 0};
+    for (size_t i = 0; i < c.size(); ++i) { cs[0] += c.x[i]; cs[1] += c.y[i]; cs[2] += c.z[i]; }
+    for (int d = 0; d < 3; ++d) cs[d] /= (float)c.size();
+    float radius = 0.f;
+    for (size_t i = 0; i < c.size(); ++i) {
+        const float dx = c.x[i] - cs[0], dy = c.y[i] - cs[1], dz = c.z[i] - cs[2];
+        radius = std::max(radius, std::sqrt(dx * dx + dy * dy + dz * dz));
+    }
+    return radius;
 }
 
 void ImplicitShapeModel::train() {                // :252-500
@@ -1506,32 +1517,13 @@ void ImplicitShapeModel::train() {                // :252-500
             live_of[o] = (int)live.size(); live.push_back(filtered[o]);
         }
         auto f = live.empty() ? std::make_shared<DeviceFeatures>() : computeFeatures(live, true);
-        std::vector<float> t;
-        s.d2h(t, f->desc, (size_t)f->n * D); hdesc.insert(hdesc.end(), t.begin(), t.end());
-        s.d2h(t, f->lrf, (size_t)f->n * 9); hlrf.insert(hlrf.end(), t.begin(), t.end());
-        s.d2h(t, f->kx, f->n); hkx.insert(hkx.end(), t.begin(), t.end());
-        s.d2h(t, f->ky, f->n); hky.insert(hky.end(), t.begin(), t.end());
-        s.d2h(t, f->kz, f->n); hkz.insert(hkz.end(), t.begin(), t.end());
+        auto append = [&](std::vector<float>& dst, const DevBuf& src, size_t n) { std::vector<float> t; s.d2h(t, src, n); dst.insert(dst.end(), t.begin(), t.end()); };
+        append(hdesc, f->desc, (size_t)f->n * D); append(hlrf, f->lrf, (size_t)f->n * 9);
+        append(hkx, f->kx, f->n); append(hky, f->ky, f->n); append(hkz, f->kz, f->n);
         for (size_t o = 0; o < part.size(); ++o) {
-            const PointCloud& c = *part[o];
-            float mn[3] = {c.x[0], c.y[0], c.z[0]}, mx[3] = {c.x[0], c.y[0], c.z[0]};
-            for (size_t i = 0; i < c.size(); ++i) {
-                mn[0] = std::min(mn[0], c.x[i]); mx[0] = std::max(mx[0], c.x[i]); mn[1] = std::min(mn[1], c.y[i]); mx[1] = std::max(mx[1], c.y[i]);
-                mn[2] = std::min(mn[2], c.z[i]); mx[2] = std::max(mx[2], c.z[i]);
-            }
-            // Utils::computeAABB (utils.cpp:222-233): size = max - min, position = min + size / 2
-            const std::array<float, 3> bsize = {mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]};
-            const std::array<float, 3> center = {mn[0] + bsize[0] / 2, mn[1] + bsize[1] / 2, mn[2] + bsize[2] / 2};
-            // Utils::computeCloudRadius (utils.cpp:302-321): largest distance to the centroid (pcl::compute3DCentroid into a Vector4f)
-            float cs[3] = {0, 0, 0};
-            for (size_t i = 0; i < c.size(); ++i) { cs[0] += c.x[i]; cs[1] += c.y[i]; cs[2] += c.z[i]; }
-            for (int d = 0; d < 3; ++d) cs[d] /= (float)c.size();
-            float radius = 0.f;
-            for (size_t i = 0; i < c.size(); ++i) {
-                const float dx = c.x[i] - cs[0], dy = c.y[i] - cs[1], dz = c.z[i] - cs[2];
-                radius = std::max(radius, std::sqrt(dx * dx + dy * dy + dz * dz));
-            }
-            box_sizes[obj_class[b + o]].push_back(bsize); object_radii[obj_class[b + o]].push_back(radius);
+            std::array<float, 3> center, bsize;
+            cloudAABB(*part[o], center, bsize);
+            box_sizes[obj_class[b + o]].push_back(bsize); object_radii[obj_class[b + o]].push_back(cloudRadius(*part[o]));
             if (live_of[o] < 0) continue;
             const uint32_t cnt = f->off[live_of[o] + 1] - f->off[live_of[o]];
             fclass.insert(fclass.end(), cnt, obj_class[b + o]); finst.insert(finst.end(), cnt, obj_inst[b + o]);
@@ -1556,7 +1548,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     g_log_info = m_logging;
     if (m_single_object_mode_legacy)
         throw RuntimeException("The parameter for \"single object mode\" must be set inside the \"Voting\" section of the config file. You are using the \"Parameters\" section.");
-    auto t_all = std::chrono::steady_clock::now();
+    LapTimer complete{m_processing_times};
     DeviceSession& s = session();
     std::vector<const PointCloud*> nonempty;
     std::vector<int> map;
@@ -1567,19 +1559,17 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     std::vector<std::vector<VotingMaximum>> out(clouds.size());
     if (nonempty.empty()) return out;
     auto f = computeFeatures(nonempty, false);
-    auto t0 = std::chrono::steady_clock::now();
+    LapTimer stage{m_processing_times};
     LOG_INFO("activating codewords and casting votes");
     m_voting->clear();
     m_codebook->castVotes(s, *f, metric(), *m_voting);
     s.sync();
     m_last_detect = f;
-    auto t1 = std::chrono::steady_clock::now();
-    m_processing_times["voting"] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    stage.lap("voting");
     LOG_INFO("finding maxima");
     auto res = m_voting->findMaxima(s);
-    auto t2 = std::chrono::steady_clock::now();
-    m_processing_times["maxima"] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-    m_processing_times["complete"] += std::chrono::duration<double, std::milli>(t2 - t_all).count();
+    stage.lap("maxima");
+    complete.lap("complete");
     m_processing_times["normals"] += 0; m_processing_times["flann"] += 0;
     for (size_t i = 0; i < res.size(); ++i) out[map[i]] = res[i];
     return out;
@@ -1620,7 +1610,7 @@ std::tuple<std::vector<VotingMaximum>, std::map<std::string, double>> ImplicitSh
     // estimated again; hasNormals == true is still checked against the FIRST point (:615-625) inside computeFeatures (firstNormalValid)
     PointCloud stripped;
     const PointCloud* in = &pointCloud;
-    if (!hasNormals) { stripped = pointCloud; stripped.nx.assign(stripped.size(), 0.f); stripped.ny.assign(stripped.size(), 0.f); stripped.nz.assign(stripped.size(), 0.f); in = &stripped; }
+    if (!hasNormals) { stripped = withZeroedNormals(pointCloud); in = &stripped; }
     auto r = detectBatch({in});
     LOG_INFO("detected " << r[0].size() << " maxima");
     return std::make_tuple(r[0], m_processing_times);

@@ -414,6 +414,9 @@ protected:
     // device outputs of ismhip_find_maxima / ismhip_hough3d_maxima -> VotingMaximum lists
     struct MaximaBuffers;                                        // defined in ism3d.cpp (device buffers)
     static bool collectMaxima(DeviceSession& s, MaximaBuffers& b, std::vector<std::vector<VotingMaximum>>& out, bool with_quat);
+    // the search both back ends share: P (ismhip_maxima_params / ismhip_hough_params) with the back end's own fields, its two entry points
+    template <typename Params, typename Entry, typename RansacEntry>
+    void searchMaxima(DeviceSession& s, Params P, Entry entry, RansacEntry ransac_entry, const char* what, std::vector<std::vector<VotingMaximum>>& out) const;
     int singleObjectMaxType() const;                             // ISMHIP_SOM_* from SingleObjectMode / SingleObjectMaxType
     int maxFilter() const;                                       // ISMHIP_MAXFILTER_* from MaxFilterType
     // RANSAC vote filter (voting.cpp:110-127): per-class inlier thresholds (empty = the configured one for all) and the device call's parameters
