@@ -307,21 +307,27 @@ class _PointArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x", "y", "z", "nx", "ny", "nz", "rgba")]
 
 
-def filter_normals(ctx, pt_offsets, x, y, z, nx, ny, nz, rgba=None):
-    """ImplicitShapeModel::filterNormals on the device: returns (new_offsets numpy, x, y, z, nx, ny, nz, rgba or None) without the
-    points whose normal holds a NaN (order kept)"""
+def _compact_point_arrays(ctx, symbol, pt_offsets, arrays, rgba, *mask):
+    """ismhip_filter_normals / ismhip_compact_points (which takes its keep mask between the two array sets) on x, y, z, nx, ny, nz and
+    rgba or None: returns (new_offsets numpy, x, y, z, nx, ny, nz, rgba or None)"""
     torch = _torch()
     po = _u32(pt_offsets)
     n_obj = len(po) - 1
-    ins = [x, y, z, nx, ny, nz] + ([rgba] if rgba is not None else [])
+    ins = list(arrays) + ([rgba] if rgba is not None else [])
     outs = [torch.empty_like(t) for t in ins]
     a_in = _PointArrays(*[t.data_ptr() for t in ins], *([None] if rgba is None else []))
     a_out = _PointArrays(*[t.data_ptr() for t in outs], *([None] if rgba is None else []))
     new = np.zeros(n_obj + 1, dtype=np.uint32)
-    ctx.check(lib().ismhip_filter_normals(ctx._h, C.c_int(n_obj), _p(po), C.byref(a_in), C.byref(a_out), _p(new)), "ismhip_filter_normals")
+    ctx.check(getattr(lib(), symbol)(ctx._h, C.c_int(n_obj), _p(po), C.byref(a_in), *[_p(m) for m in mask], C.byref(a_out), _p(new)), symbol)
     m = int(new[-1])
     outs = [t[:m] for t in outs]
     return (new, *outs, *([None] if rgba is None else []))
+
+
+def filter_normals(ctx, pt_offsets, x, y, z, nx, ny, nz, rgba=None):
+    """ImplicitShapeModel::filterNormals on the device: returns (new_offsets numpy, x, y, z, nx, ny, nz, rgba or None) without the
+    points whose normal holds a NaN (order kept)"""
+    return _compact_point_arrays(ctx, "ismhip_filter_normals", pt_offsets, (x, y, z, nx, ny, nz), rgba)
 
 
 def filter_statistical(ctx, cloud, mean_k=20, stddev_mul=2.0, want_mean_dist=True):
@@ -359,18 +365,7 @@ def filter_passthrough_z(ctx, x, y, z, z_min, z_max):
 
 def compact_points(ctx, pt_offsets, keep, x, y, z, nx, ny, nz, rgba=None):
     """the points with keep == 1, order kept: returns (new_offsets numpy, x, y, z, nx, ny, nz, rgba or None)"""
-    torch = _torch()
-    po = _u32(pt_offsets)
-    n_obj = len(po) - 1
-    ins = [x, y, z, nx, ny, nz] + ([rgba] if rgba is not None else [])
-    outs = [torch.empty_like(t) for t in ins]
-    a_in = _PointArrays(*[t.data_ptr() for t in ins], *([None] if rgba is None else []))
-    a_out = _PointArrays(*[t.data_ptr() for t in outs], *([None] if rgba is None else []))
-    new = np.zeros(n_obj + 1, dtype=np.uint32)
-    ctx.check(lib().ismhip_compact_points(ctx._h, C.c_int(n_obj), _p(po), C.byref(a_in), _p(keep), C.byref(a_out), _p(new)), "ismhip_compact_points")
-    m = int(new[-1])
-    outs = [t[:m] for t in outs]
-    return (new, *outs, *([None] if rgba is None else []))
+    return _compact_point_arrays(ctx, "ismhip_compact_points", pt_offsets, (x, y, z, nx, ny, nz), rgba, keep)
 
 
 def voxel_keypoints(ctx, pt_offsets, x, y, z, leaf, rgba=None):
@@ -388,9 +383,8 @@ def voxel_keypoints(ctx, pt_offsets, x, y, z, leaf, rgba=None):
     return ko, kx[:m], ky[:m], kz[:m], (kc[:m] if kc is not None else None)
 
 
-def compact_descriptor_rows(ctx, kp_offsets, desc, lrf, kpx, kpy, kpz):
-    """compact_features for descriptor matrices of this library (rows are NaN as a whole): when nothing is dropped the INPUT tensors are
-    returned, no copy is made"""
+def _compact_feature_rows(ctx, symbol, report_all_kept, kp_offsets, desc, lrf, kpx, kpy, kpz):
+    """ismhip_compact_features / ismhip_compact_descriptor_rows (which reports "nothing dropped": the inputs are then returned)"""
     torch = _torch()
     ko = _u32(kp_offsets)
     n_obj = len(ko) - 1
@@ -401,86 +395,89 @@ def compact_descriptor_rows(ctx, kp_offsets, desc, lrf, kpx, kpy, kpz):
     src = torch.empty((n,), dtype=torch.int32, device=desc.device)
     keep = np.zeros(n_obj + 1, dtype=np.uint32)
     all_kept = C.c_int(0)
-    ctx.check(lib().ismhip_compact_descriptor_rows(ctx._h, C.c_int(n_obj), _p(ko), C.c_int(dim), _p(desc), _p(lrf), _p(kpx), _p(kpy), _p(kpz),
-                                                   _p(d_o), _p(l_o), _p(x_o), _p(y_o), _p(z_o), _p(src), _p(keep), C.byref(all_kept)),
-              "ismhip_compact_descriptor_rows")
+    ctx.check(getattr(lib(), symbol)(ctx._h, C.c_int(n_obj), _p(ko), C.c_int(dim), _p(desc), _p(lrf), _p(kpx), _p(kpy), _p(kpz),
+                                     _p(d_o), _p(l_o), _p(x_o), _p(y_o), _p(z_o), _p(src), _p(keep), *([C.byref(all_kept)] if report_all_kept else [])),
+              symbol)
     if all_kept.value:
         return keep, desc, lrf, kpx, kpy, kpz, src
     m = int(keep[-1])
     return keep, d_o[:m], (l_o[:m] if l_o is not None else None), x_o[:m], y_o[:m], z_o[:m], src[:m]
 
 
+def compact_descriptor_rows(ctx, kp_offsets, desc, lrf, kpx, kpy, kpz):
+    """compact_features for descriptor matrices of this library (rows are NaN as a whole): when nothing is dropped the INPUT tensors are
+    returned, no copy is made"""
+    return _compact_feature_rows(ctx, "ismhip_compact_descriptor_rows", True, kp_offsets, desc, lrf, kpx, kpy, kpz)
+
+
 def compact_features(ctx, kp_offsets, desc, lrf, kpx, kpy, kpz):
     """returns (keep_offsets, desc, lrf, kpx, kpy, kpz, src_index) with NaN rows removed (order preserved)"""
+    return _compact_feature_rows(ctx, "ismhip_compact_features", False, kp_offsets, desc, lrf, kpx, kpy, kpz)
+
+
+def _knn_outputs(q, k):
+    """(nq, idx [nq, k] int32, dist [nq, k] float32) for the queries q"""
     torch = _torch()
-    ko = _u32(kp_offsets)
-    n_obj = len(ko) - 1
-    n, dim = desc.shape
-    d_o = torch.empty_like(desc)
-    l_o = torch.empty_like(lrf) if lrf is not None else None
-    x_o, y_o, z_o = torch.empty_like(kpx), torch.empty_like(kpy), torch.empty_like(kpz)
-    src = torch.empty((n,), dtype=torch.int32, device=desc.device)
-    keep = np.zeros(n_obj + 1, dtype=np.uint32)
-    ctx.check(lib().ismhip_compact_features(ctx._h, C.c_int(n_obj), _p(ko), C.c_int(dim), _p(desc), _p(lrf), _p(kpx), _p(kpy), _p(kpz),
-                                            _p(d_o), _p(l_o), _p(x_o), _p(y_o), _p(z_o), _p(src), _p(keep)), "ismhip_compact_features")
-    m = int(keep[-1])
-    return keep, d_o[:m], (l_o[:m] if l_o is not None else None), x_o[:m], y_o[:m], z_o[:m], src[:m]
+    nq = q.shape[0]
+    return nq, torch.empty((nq, k), dtype=torch.int32, device=q.device), torch.empty((nq, k), dtype=torch.float32, device=q.device)
 
 
 def knn(ctx, cb, metric, q, k=1):
-    torch = _torch()
-    nq = q.shape[0]
-    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    nq, idx, dist = _knn_outputs(q, k)
     ctx.check(lib().ismhip_knn(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn")
     return idx, dist
 
 
 def knn_large_k(ctx, cb, metric, q, k):
     """ismhip_knn_large_k: the contract of knn for any 1 <= k <= 1024 (k <= 16 is knn itself); synchronises"""
-    torch = _torch()
-    nq = q.shape[0]
-    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
-    dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    nq, idx, dist = _knn_outputs(q, k)
     ctx.check(lib().ismhip_knn_large_k(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn_large_k")
     return idx, dist
 
 
 def knn_ratio(ctx, cb, metric, q, ratio_threshold):
-    torch = _torch()
-    nq = q.shape[0]
-    idx = torch.empty((nq, 1), dtype=torch.int32, device=q.device)
-    dist = torch.empty((nq, 1), dtype=torch.float32, device=q.device)
+    nq, idx, dist = _knn_outputs(q, 1)
     ctx.check(lib().ismhip_knn_ratio(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_float(ratio_threshold), _p(idx), _p(dist)),
               "ismhip_knn_ratio")
     return idx, dist
 
 
 def knn_rule(ctx, cb, metric, q, ratio_threshold):
-    torch = _torch()
-    nq = q.shape[0]
-    idx = torch.empty((nq, 1), dtype=torch.int32, device=q.device)
-    dist = torch.empty((nq, 1), dtype=torch.float32, device=q.device)
+    nq, idx, dist = _knn_outputs(q, 1)
     ctx.check(lib().ismhip_knn_rule(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_float(ratio_threshold), _p(idx), _p(dist)),
               "ismhip_knn_rule")
     return idx, dist
 
 
-def cast_votes(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, idx, dist, want_bbox=False):
+def _act_offsets(act_offsets, dev):
+    """activation offsets as the device int32 tensor the C ABI takes: a host array is converted and uploaded"""
+    if isinstance(act_offsets, np.ndarray):
+        return _torch().from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(dev)
+    return act_offsets
+
+
+def _vote_outputs(ns, dev, want_bbox):
+    """the output tensors of cast_votes / cast_votes_csr for ns vote slots, in the order of the C arguments"""
     torch = _torch()
+    return dict(pos=torch.empty((ns, 3), dtype=torch.float32, device=dev), weight=torch.empty((ns,), dtype=torch.float32, device=dev),
+                cls=torch.empty((ns,), dtype=torch.int32, device=dev), inst=torch.empty((ns,), dtype=torch.int32, device=dev),
+                codeword=torch.empty((ns,), dtype=torch.int32, device=dev),
+                bbox_quat=torch.empty((ns, 4), dtype=torch.float32, device=dev) if want_bbox else None,
+                bbox_size=torch.empty((ns, 3), dtype=torch.float32, device=dev) if want_bbox else None)
+
+
+def _vote_keypoint_outputs(ns, dev):
+    """(keypoint, keypoint_training) [ns, 3] of vote_keypoints / vote_keypoints_csr; zero where a slot holds no vote"""
+    torch = _torch()
+    return torch.zeros((ns, 3), dtype=torch.float32, device=dev), torch.zeros((ns, 3), dtype=torch.float32, device=dev)
+
+
+def cast_votes(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, idx, dist, want_bbox=False):
     nq, k = idx.shape
-    ns = nq * k * max(cb.max_votes, 0)
-    dev = idx.device
-    pos = torch.empty((ns, 3), dtype=torch.float32, device=dev)
-    w = torch.empty((ns,), dtype=torch.float32, device=dev)
-    cls = torch.empty((ns,), dtype=torch.int32, device=dev)
-    inst = torch.empty((ns,), dtype=torch.int32, device=dev)
-    cw = torch.empty((ns,), dtype=torch.int32, device=dev)
-    bq = torch.empty((ns, 4), dtype=torch.float32, device=dev) if want_bbox else None
-    bs = torch.empty((ns, 3), dtype=torch.float32, device=dev) if want_bbox else None
+    out = _vote_outputs(nq * k * max(cb.max_votes, 0), idx.device, want_bbox)
     ctx.check(lib().ismhip_cast_votes(ctx._h, cb._h, C.c_uint32(weight_flags), C.c_int(nq), _p(lrf), _p(kpx), _p(kpy), _p(kpz), C.c_int(k),
-                                      _p(idx), _p(dist), _p(pos), _p(w), _p(cls), _p(inst), _p(cw), _p(bq), _p(bs)), "ismhip_cast_votes")
-    return dict(pos=pos, weight=w, cls=cls, inst=inst, codeword=cw, bbox_quat=bq, bbox_size=bs)
+                                      _p(idx), _p(dist), *[_p(t) for t in out.values()]), "ismhip_cast_votes")
+    return out
 
 
 def knn_threshold(ctx, cb, metric, q, threshold, capacity=None):
@@ -514,48 +511,29 @@ def knn_threshold(ctx, cb, metric, q, threshold, capacity=None):
 def cast_votes_csr(ctx, cb, weight_flags, lrf, kpx, kpy, kpz, act_offsets, idx, dist, want_bbox=False):
     """ismhip_cast_votes_csr: act_offsets [nq+1] (host array or device int32 tensor), idx / dist [n_act] device. Slot of (activation a,
     stored vote v) = a * max_votes + v."""
-    torch = _torch()
-    dev = idx.device
-    if isinstance(act_offsets, np.ndarray):
-        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(dev)
+    act_offsets = _act_offsets(act_offsets, idx.device)
     nq = act_offsets.shape[0] - 1
     n_act = idx.shape[0]
-    ns = n_act * max(cb.max_votes, 0)
-    pos = torch.empty((ns, 3), dtype=torch.float32, device=dev)
-    w = torch.empty((ns,), dtype=torch.float32, device=dev)
-    cls = torch.empty((ns,), dtype=torch.int32, device=dev)
-    inst = torch.empty((ns,), dtype=torch.int32, device=dev)
-    cw = torch.empty((ns,), dtype=torch.int32, device=dev)
-    bq = torch.empty((ns, 4), dtype=torch.float32, device=dev) if want_bbox else None
-    bs = torch.empty((ns, 3), dtype=torch.float32, device=dev) if want_bbox else None
+    out = _vote_outputs(n_act * max(cb.max_votes, 0), idx.device, want_bbox)
     ctx.check(lib().ismhip_cast_votes_csr(ctx._h, cb._h, C.c_uint32(weight_flags), C.c_int(nq), _p(lrf), _p(kpx), _p(kpy), _p(kpz), _p(act_offsets),
-                                          C.c_int64(n_act), _p(idx), _p(dist), _p(pos), _p(w), _p(cls), _p(inst), _p(cw), _p(bq), _p(bs)),
-              "ismhip_cast_votes_csr")
-    return dict(pos=pos, weight=w, cls=cls, inst=inst, codeword=cw, bbox_quat=bq, bbox_size=bs)
+                                          C.c_int64(n_act), _p(idx), _p(dist), *[_p(t) for t in out.values()]), "ismhip_cast_votes_csr")
+    return out
 
 
 def vote_keypoints(ctx, cb, kpx, kpy, kpz, idx):
     """ismhip_vote_keypoints: (keypoint, keypoint_training) [n_slots, 3] of every vote slot of cast_votes(idx [nq, k])"""
-    torch = _torch()
     nq, k = idx.shape
-    ns = nq * k * max(cb.max_votes, 0)
-    kp = torch.zeros((ns, 3), dtype=torch.float32, device=idx.device)
-    kpt = torch.zeros((ns, 3), dtype=torch.float32, device=idx.device)
+    kp, kpt = _vote_keypoint_outputs(nq * k * max(cb.max_votes, 0), idx.device)
     ctx.check(lib().ismhip_vote_keypoints(ctx._h, cb._h, C.c_int(nq), _p(kpx), _p(kpy), _p(kpz), C.c_int(k), _p(idx), _p(kp), _p(kpt)), "ismhip_vote_keypoints")
     return kp, kpt
 
 
 def vote_keypoints_csr(ctx, cb, kpx, kpy, kpz, act_offsets, idx):
     """ismhip_vote_keypoints_csr: the same in the slot layout of cast_votes_csr"""
-    torch = _torch()
-    dev = idx.device
-    if isinstance(act_offsets, np.ndarray):
-        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(dev)
+    act_offsets = _act_offsets(act_offsets, idx.device)
     nq = act_offsets.shape[0] - 1
     n_act = idx.shape[0]
-    ns = n_act * max(cb.max_votes, 0)
-    kp = torch.zeros((ns, 3), dtype=torch.float32, device=dev)
-    kpt = torch.zeros((ns, 3), dtype=torch.float32, device=dev)
+    kp, kpt = _vote_keypoint_outputs(n_act * max(cb.max_votes, 0), idx.device)
     ctx.check(lib().ismhip_vote_keypoints_csr(ctx._h, cb._h, C.c_int(nq), _p(kpx), _p(kpy), _p(kpz), _p(act_offsets), C.c_int64(n_act), _p(idx), _p(kp), _p(kpt)),
               "ismhip_vote_keypoints_csr")
     return kp, kpt
@@ -684,46 +662,39 @@ def hough3d_maxima(ctx, slot_offsets, votes, n_classes, bin_size, min_coord=(-5,
     return _maxima_call(ctx, "ismhip_hough3d_maxima", so, votes, P, _maxima_outputs(n_obj, max_maxima, n_classes, dev), bq_out, ransac)
 
 
-def train_activate(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, k=1, clean_up=True, n_classes=None, codewords=None):
-    """Codebook::activate on the device (features class-major; codewords = device matrix of cluster centres, None = the features
-    themselves) -> dict of host arrays (word_src, vote_offsets, vote_feature, vote_xyz, vote_weight, vote_class_weight, class_sigma)"""
+def _train_activate(ctx, symbol, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, n_classes, codewords, vote_cap, activation):
+    """the two training entries: host output buffers for at most vote_cap votes, the call (`activation` = the arguments between the
+    codewords and n_classes, where the two differ) and the dict of host arrays trimmed to the words and votes that were written"""
     n, dim = desc.shape
     fc, fm = _u32(feat_class), _u32(feat_model)
     ctr = np.ascontiguousarray(np.asarray(feat_center, dtype=np.float32))
     C_ = int(n_classes if n_classes is not None else fc.max() + 1)
     ncw = n if codewords is None else int(codewords.shape[0])
     nw = C.c_int32(0)
-    word_src = np.empty(ncw, np.uint32); vo = np.empty(ncw + 1, np.uint32); vf = np.empty(n * k, np.uint32)
-    vxyz = np.empty((n * k, 3), np.float32); vw = np.empty(n * k, np.float32); vcw = np.empty(n * k, np.float32); sig = np.empty(C_, np.float32)
-    ctx.check(lib().ismhip_train_activate(ctx._h, C.c_int(metric), C.c_int(n), C.c_int(dim), _p(desc), _p(lrf), _p(kx), _p(ky), _p(kz), _p(fc), _p(fm),
-                                          _p(ctr), C.c_int(ncw), _p(codewords), C.c_int(k), C.c_int(1 if clean_up else 0), C.c_int(C_), C.byref(nw), _p(word_src),
-                                          _p(vo), _p(vf), _p(vxyz), _p(vw), _p(vcw), _p(sig)), "ismhip_train_activate")
+    word_src = np.empty(ncw, np.uint32); vo = np.empty(ncw + 1, np.uint32); vf = np.empty(vote_cap, np.uint32)
+    vxyz = np.empty((vote_cap, 3), np.float32); vw = np.empty(vote_cap, np.float32); vcw = np.empty(vote_cap, np.float32); sig = np.empty(C_, np.float32)
+    ctx.check(getattr(lib(), symbol)(ctx._h, C.c_int(metric), C.c_int(n), C.c_int(dim), _p(desc), _p(lrf), _p(kx), _p(ky), _p(kz), _p(fc), _p(fm),
+                                     _p(ctr), C.c_int(ncw), _p(codewords), *activation, C.c_int(C_), C.byref(nw), _p(word_src),
+                                     _p(vo), _p(vf), _p(vxyz), _p(vw), _p(vcw), _p(sig)), symbol)
     m = nw.value; nv = int(vo[m])
     return dict(word_src=word_src[:m].copy(), vote_offsets=vo[:m + 1].copy(), vote_feature=vf[:nv].copy(), vote_xyz=vxyz[:nv].copy(),
                 vote_weight=vw[:nv].copy(), vote_class_weight=vcw[:nv].copy(), class_sigma=sig)
+
+
+def train_activate(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, k=1, clean_up=True, n_classes=None, codewords=None):
+    """Codebook::activate on the device (features class-major; codewords = device matrix of cluster centres, None = the features
+    themselves) -> dict of host arrays (word_src, vote_offsets, vote_feature, vote_xyz, vote_weight, vote_class_weight, class_sigma)"""
+    return _train_activate(ctx, "ismhip_train_activate", metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, n_classes, codewords,
+                           desc.shape[0] * k, (C.c_int(k), C.c_int(1 if clean_up else 0)))
 
 
 def train_activate_lists(ctx, metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, act_offsets, act_idx, n_classes=None, codewords=None):
     """Codebook::activate with a variable number of activations per feature (ActivationStrategyThreshold): act_offsets [n+1] (host
     array or device int32 tensor), act_idx [n_act] device int32 rows of the codewords -> the dict of train_activate"""
-    torch = _torch()
-    n, dim = desc.shape
-    if isinstance(act_offsets, np.ndarray):
-        act_offsets = torch.from_numpy(np.ascontiguousarray(act_offsets.astype(np.uint32)).view(np.int32)).to(desc.device)
-    fc, fm = _u32(feat_class), _u32(feat_model)
-    ctr = np.ascontiguousarray(np.asarray(feat_center, dtype=np.float32))
-    C_ = int(n_classes if n_classes is not None else fc.max() + 1)
-    ncw = n if codewords is None else int(codewords.shape[0])
+    act_offsets = _act_offsets(act_offsets, desc.device)
     na = int(act_idx.shape[0])
-    nw = C.c_int32(0)
-    word_src = np.empty(ncw, np.uint32); vo = np.empty(ncw + 1, np.uint32); vf = np.empty(max(na, 1), np.uint32)
-    vxyz = np.empty((max(na, 1), 3), np.float32); vw = np.empty(max(na, 1), np.float32); vcw = np.empty(max(na, 1), np.float32); sig = np.empty(C_, np.float32)
-    ctx.check(lib().ismhip_train_activate_lists(ctx._h, C.c_int(metric), C.c_int(n), C.c_int(dim), _p(desc), _p(lrf), _p(kx), _p(ky), _p(kz), _p(fc), _p(fm),
-                                                _p(ctr), C.c_int(ncw), _p(codewords), _p(act_offsets), _p(act_idx), C.c_int64(na), C.c_int(C_), C.byref(nw),
-                                                _p(word_src), _p(vo), _p(vf), _p(vxyz), _p(vw), _p(vcw), _p(sig)), "ismhip_train_activate_lists")
-    m = nw.value; nv = int(vo[m])
-    return dict(word_src=word_src[:m].copy(), vote_offsets=vo[:m + 1].copy(), vote_feature=vf[:nv].copy(), vote_xyz=vxyz[:nv].copy(),
-                vote_weight=vw[:nv].copy(), vote_class_weight=vcw[:nv].copy(), class_sigma=sig)
+    return _train_activate(ctx, "ismhip_train_activate_lists", metric, desc, lrf, kx, ky, kz, feat_class, feat_model, feat_center, n_classes, codewords,
+                           max(na, 1), (_p(act_offsets), _p(act_idx), C.c_int64(na)))
 
 
 CENTERS_INIT = {"FLANN_CENTERS_RANDOM": 0, "FLANN_CENTERS_GONZALES": 1, "FLANN_CENTERS_KMEANSPP": 2}

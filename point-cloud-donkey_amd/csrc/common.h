@@ -183,6 +183,22 @@ void* ism_scratch(ismhip_ctx* ctx, int slot, size_t bytes);   // nullptr on fail
 // raises a kernel's MaxDynamicSharedMemorySize to `bytes` once per ctx (attr_done): pass the largest size any launch of that kernel uses
 int  ism_lds_cap(ismhip_ctx* ctx, const void* kern, size_t bytes);
 
+// ---- ragged batches (grid.hip): run r of an offsets array off[0 .. n] is [off[r], off[r + 1]) ---------------------------------
+// uploads a small host offsets array into a scratch slot; returns device pointer (nullptr on failure)
+uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
+struct RaggedOffsets { uint32_t max_run = 0, total = 0; uint32_t* dev = nullptr; };   // longest run, off[n], the offsets on the device
+enum { RAGGED_START0 = 1,    // off[0] must be 0 (only the entry points that have always insisted on it)
+       RAGGED_EMPTY = 2 };   // upload even when every run is empty (the caller launches regardless)
+// The offsets array of entry point `name`: refuses it with "<name>: offsets not monotone" (RAGGED_START0: "<name>: offsets must start
+// at 0"), measures it and uploads its n + 1 entries into `slot`. When every run is empty nothing is uploaded and dev stays nullptr
+// (the callers return before any device work), unless RAGGED_EMPTY is set.
+int ism_ragged_offsets(ismhip_ctx* ctx, const std::string& name, const uint32_t* off_h, int n, int slot, int flags, RaggedOffsets* r);
+// per-run counts on the device -> offsets on the host (off_h_out[0 .. n], from 0) and the longest run; synchronises the stream
+int ism_offsets_from_counts(ismhip_ctx* ctx, int n, const uint32_t* cnt_d, uint32_t* off_h_out, uint32_t* max_run_out);
+// the cell-order permutation of a keypoint set on a cloud, or nullptr (see grid.hip)
+const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
+                             const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
+
 #define ISM_HIP(ctx, call)                                                                          \
     do {                                                                                            \
         hipError_t e__ = (call);                                                                    \
@@ -276,6 +292,34 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);
     return (uint32_t)x;
 }
+// Exclusive scan of a uint32_t array by ONE workgroup of NT threads (256 or 1024), a chunk of NT entries per step: step(v) takes
+// the thread's entry of this chunk and returns its exclusive prefix over the whole array so far, the earlier chunks included;
+// after the last step total() is the sum of all entries. Lives in LDS (`__shared__ BlockScan<NT> scan;`), init() comes first.
+// Precondition: all 64 lanes of every wave are active in step() (wave_incl_scan_u32 is a DPP sequence, and step() holds
+// barriers) -- the workgroup has NT threads, none returns before the chunk loop, and a thread past the end of the array still
+// calls step(0) for as many chunks as the others.
+template <int NT>
+struct BlockScan {
+    uint32_t wave[NT / 64];   // inclusive totals of this chunk's waves
+    uint32_t carry;           // sum of the earlier chunks
+    __device__ __forceinline__ void init() {
+        if (threadIdx.x == 0) carry = 0;
+        __syncthreads();
+    }
+    __device__ __forceinline__ uint32_t step(uint32_t v) {
+        const uint32_t incl = wave_incl_scan_u32(v);
+        const int w = threadIdx.x >> 6;
+        if (lane_id() == 63) wave[w] = incl;
+        __syncthreads();
+        uint32_t before = carry;
+        for (int k = 0; k < w; ++k) before += wave[k];
+        __syncthreads();
+        if (threadIdx.x == NT - 1) carry = before + incl;
+        __syncthreads();
+        return before + incl - v;
+    }
+    __device__ __forceinline__ uint32_t total() const { return carry; }
+};
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov0_d(double v) {
     const long long b = __double_as_longlong(v);

@@ -5,8 +5,6 @@
 // shot.hip), which leaves the same rows in the same order.
 #include "common.h"
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 namespace {
 
 // keep[k] = 1 when LRF (if given) is finite in its first component of every axis and no descriptor element is NaN
@@ -41,28 +39,14 @@ __global__ __launch_bounds__(256) void k_scan_obj(const uint32_t* __restrict__ k
                                                   uint32_t* __restrict__ pos, uint32_t* __restrict__ obj_count) {
     const int o = blockIdx.x;
     const uint32_t b = kp_off[o], e = kp_off[o + 1];
-    __shared__ uint32_t s_w[4];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
+    __shared__ BlockScan<256> scan;
+    scan.init();
     for (uint32_t base = b; base < e; base += 256) {
         const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < e ? keep[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(incl, off, 64); if (lane_id() >= off) incl += t; }
-        const int w = threadIdx.x >> 6;
-        if (lane_id() == 63) s_w[w] = incl;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (int k = 0; k < w; ++k) woff += s_w[k];
-        const uint32_t carry = s_carry;
-        if (i < e) pos[i] = carry + woff + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = carry + woff + incl;
-        __syncthreads();
+        const uint32_t p = scan.step(i < e ? keep[i] : 0u);
+        if (i < e) pos[i] = p;
     }
-    if (threadIdx.x == 0) obj_count[o] = s_carry;
+    if (threadIdx.x == 0) obj_count[o] = scan.total();
 }
 
 __global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ kp_off, const uint32_t* __restrict__ new_off,
@@ -84,6 +68,49 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t* __restrict__ kp_
 
 }  // namespace
 
+// What a compaction holds once its rows are flagged and scanned: the input offsets and its longest run, the output offsets, the flags
+// and the position of every kept row inside its object (all on the device)
+struct Compaction { uint32_t max_run; const uint32_t *off, *new_off, *keep, *pos; };
+
+// The driver of both compactions. flag(n, keep) launches the kernel that writes keep[0 .. n) and gather(c) the one that moves the
+// kept rows; each returns its kernel's name for the launch check. Between them: the per-object scan, the kept counts to the host,
+// the output offsets on the host (off_h_out) and on the device. all_kept_out (may be NULL): when nothing is dropped it is set, no
+// gather runs and src_index_out (may be NULL) is filled with 0 .. n - 1.
+template <class Flag, class Gather>
+static int compact_rows(ismhip_ctx* ctx, const std::string& who, int n_obj, const uint32_t* off_h, uint32_t* off_h_out, int* all_kept_out,
+                        uint32_t* src_index_out, Flag&& flag, Gather&& gather) {
+    RaggedOffsets in;
+    int rc = ism_ragged_offsets(ctx, who, off_h, n_obj, SCR_KP_OFF, 0, &in);
+    if (rc != ISMHIP_OK) return rc;
+    const uint32_t n = in.total;
+    if (n == 0) { for (int o = 0; o <= n_obj; ++o) off_h_out[o] = 0; return ISMHIP_OK; }
+    uint32_t* keep = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_KEEP, (size_t)n * 4);
+    uint32_t* pos = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_POS, (size_t)n * 4);
+    uint32_t* cnt = (uint32_t*)ism_scratch(ctx, SCR_OBJ_COUNT, (size_t)(2 * n_obj + 2) * 4);
+    if (!in.dev || !keep || !pos || !cnt) return ISMHIP_ERR_NOMEM;
+    const char* kernel = flag(n, keep);
+    ISM_CHECK_LAUNCH(ctx, kernel);
+    hipLaunchKernelGGL(k_scan_obj, dim3(n_obj), dim3(256), 0, ctx->stream, in.dev, keep, pos, cnt);
+    ISM_CHECK_LAUNCH(ctx, "k_scan_obj");
+    rc = ism_offsets_from_counts(ctx, n_obj, cnt, off_h_out, nullptr);
+    if (rc != ISMHIP_OK) return rc;
+    if (all_kept_out && off_h_out[n_obj] == n) {
+        // nothing to drop: the caller keeps using its input arrays (no 2.6 GB copy of the descriptor matrix onto itself)
+        *all_kept_out = 1;
+        if (src_index_out) {
+            hipLaunchKernelGGL(k_iota, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, src_index_out);
+            ISM_CHECK_LAUNCH(ctx, "k_iota");
+        }
+        return ISMHIP_OK;
+    }
+    uint32_t* new_off = cnt + n_obj;
+    ISM_HIP(ctx, hipMemcpyAsync(new_off, off_h_out, (size_t)(n_obj + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    kernel = gather(Compaction{in.max_run, in.dev, new_off, keep, pos});
+    ISM_CHECK_LAUNCH(ctx, kernel);
+    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));   // off_h_out is pageable memory read by the copy above, and the caller reads it right away
+    return ISMHIP_OK;
+}
+
 static int compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offsets_h, int dim,
                             const float* desc, const float* lrf9,
                             const float* kpx, const float* kpy, const float* kpz,
@@ -94,44 +121,17 @@ static int compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offse
     if (!ctx || n_obj <= 0 || !kp_offsets_h || dim <= 0 || !desc || !kpx || !kpy || !kpz || !desc_out || !kpx_out || !kpy_out ||
         !kpz_out || !keep_offsets_h_out)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "compact_features: bad argument");
-    const uint32_t nkp = kp_offsets_h[n_obj];
-    uint32_t maxk = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (kp_offsets_h[o + 1] < kp_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "compact_features: offsets not monotone");
-        maxk = std::max(maxk, kp_offsets_h[o + 1] - kp_offsets_h[o]);
-    }
-    keep_offsets_h_out[0] = 0;
-    if (nkp == 0) { for (int o = 0; o < n_obj; ++o) keep_offsets_h_out[o + 1] = 0; return ISMHIP_OK; }
-    uint32_t* ko = ism_upload_offsets(ctx, SCR_KP_OFF, kp_offsets_h, n_obj + 1);
-    uint32_t* keep = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_KEEP, (size_t)nkp * 4);
-    uint32_t* pos = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_POS, (size_t)nkp * 4);
-    uint32_t* cnt = (uint32_t*)ism_scratch(ctx, SCR_OBJ_COUNT, (size_t)(2 * n_obj + 2) * 4);
-    if (!ko || !keep || !pos || !cnt) return ISMHIP_ERR_NOMEM;
-    if (whole_rows) hipLaunchKernelGGL(k_keep_rows, dim3((nkp + 255) / 256), dim3(256), 0, ctx->stream, (int)nkp, dim, desc, lrf9, keep);
-    else hipLaunchKernelGGL(k_keep, dim3((nkp + 3) / 4), dim3(256), 0, ctx->stream, (int)nkp, dim, desc, lrf9, keep);
-    ISM_CHECK_LAUNCH(ctx, "k_keep");
-    hipLaunchKernelGGL(k_scan_obj, dim3(n_obj), dim3(256), 0, ctx->stream, ko, keep, pos, cnt);
-    ISM_CHECK_LAUNCH(ctx, "k_scan_obj");
-    std::vector<uint32_t> cnt_h(n_obj);
-    ISM_HIP(ctx, hipMemcpyAsync(cnt_h.data(), cnt, (size_t)n_obj * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int o = 0; o < n_obj; ++o) keep_offsets_h_out[o + 1] = keep_offsets_h_out[o] + cnt_h[o];
-    if (all_kept_out && keep_offsets_h_out[n_obj] == nkp) {
-        // nothing to drop: the caller keeps using its input arrays (no 2.6 GB copy of the descriptor matrix onto itself)
-        *all_kept_out = 1;
-        if (src_index_out) {
-            hipLaunchKernelGGL(k_iota, dim3((nkp + 255) / 256), dim3(256), 0, ctx->stream, nkp, src_index_out);
-            ISM_CHECK_LAUNCH(ctx, "k_iota");
-        }
-        return ISMHIP_OK;
-    }
-    uint32_t* new_off = cnt + n_obj;
-    ISM_HIP(ctx, hipMemcpyAsync(new_off, keep_offsets_h_out, (size_t)(n_obj + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather, dim3((maxk + 3) / 4, n_obj), dim3(256), 0, ctx->stream, ko, new_off, keep, pos, dim, desc, lrf9,
-                       kpx, kpy, kpz, desc_out, lrf9_out, kpx_out, kpy_out, kpz_out, src_index_out);
-    ISM_CHECK_LAUNCH(ctx, "k_gather");
-    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));   // keep_offsets_h_out is read by the caller right away; new_off copy must land
-    return ISMHIP_OK;
+    return compact_rows(ctx, "compact_features", n_obj, kp_offsets_h, keep_offsets_h_out, all_kept_out, src_index_out,
+        [&](uint32_t nkp, uint32_t* keep) {
+            if (whole_rows) hipLaunchKernelGGL(k_keep_rows, dim3((nkp + 255) / 256), dim3(256), 0, ctx->stream, (int)nkp, dim, desc, lrf9, keep);
+            else hipLaunchKernelGGL(k_keep, dim3((nkp + 3) / 4), dim3(256), 0, ctx->stream, (int)nkp, dim, desc, lrf9, keep);
+            return "k_keep";
+        },
+        [&](const Compaction& c) {
+            hipLaunchKernelGGL(k_gather, dim3((c.max_run + 3) / 4, n_obj), dim3(256), 0, ctx->stream, c.off, c.new_off, c.keep, c.pos, dim, desc, lrf9,
+                               kpx, kpy, kpz, desc_out, lrf9_out, kpx_out, kpy_out, kpz_out, src_index_out);
+            return "k_gather";
+        });
 }
 
 extern "C" int ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offsets_h, int dim,
@@ -185,34 +185,16 @@ static int compact_points(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": bad argument");
     if (in->x == out->x || in->y == out->y || in->z == out->z || in->nx == out->nx || in->ny == out->ny || in->nz == out->nz || (in->rgba && in->rgba == out->rgba))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": the output arrays must not alias the inputs");
-    const uint32_t n = pt_offsets_h[n_obj];
-    uint32_t maxn = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (pt_offsets_h[o + 1] < pt_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": offsets not monotone");
-        maxn = std::max(maxn, pt_offsets_h[o + 1] - pt_offsets_h[o]);
-    }
-    pt_offsets_h_out[0] = 0;
-    if (n == 0) { for (int o = 0; o < n_obj; ++o) pt_offsets_h_out[o + 1] = 0; return ISMHIP_OK; }
-    uint32_t* po = ism_upload_offsets(ctx, SCR_KP_OFF, pt_offsets_h, n_obj + 1);
-    uint32_t* keep = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_KEEP, (size_t)n * 4);
-    uint32_t* pos = (uint32_t*)ism_scratch(ctx, SCR_COMPACT_POS, (size_t)n * 4);
-    uint32_t* cnt = (uint32_t*)ism_scratch(ctx, SCR_OBJ_COUNT, (size_t)(2 * n_obj + 2) * 4);
-    if (!po || !keep || !pos || !cnt) return ISMHIP_ERR_NOMEM;
-    if (mask) hipLaunchKernelGGL(k_keep_mask, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, mask, keep);
-    else hipLaunchKernelGGL(k_keep_normals, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, in->nx, in->ny, in->nz, keep);
-    ISM_CHECK_LAUNCH(ctx, "k_keep_normals");
-    hipLaunchKernelGGL(k_scan_obj, dim3(n_obj), dim3(256), 0, ctx->stream, po, keep, pos, cnt);
-    ISM_CHECK_LAUNCH(ctx, "k_scan_obj");
-    std::vector<uint32_t> cnt_h(n_obj);
-    ISM_HIP(ctx, hipMemcpyAsync(cnt_h.data(), cnt, (size_t)n_obj * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int o = 0; o < n_obj; ++o) pt_offsets_h_out[o + 1] = pt_offsets_h_out[o] + cnt_h[o];
-    uint32_t* new_off = cnt + n_obj;
-    ISM_HIP(ctx, hipMemcpyAsync(new_off, pt_offsets_h_out, (size_t)(n_obj + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_points, dim3((maxn + 255) / 256, n_obj), dim3(256), 0, ctx->stream, po, new_off, keep, pos, *in, *out);
-    ISM_CHECK_LAUNCH(ctx, "k_gather_points");
-    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host copy of the offsets is pageable memory read by the H2D above
-    return ISMHIP_OK;
+    return compact_rows(ctx, who, n_obj, pt_offsets_h, pt_offsets_h_out, nullptr, nullptr,
+        [&](uint32_t n, uint32_t* keep) {
+            if (mask) hipLaunchKernelGGL(k_keep_mask, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, mask, keep);
+            else hipLaunchKernelGGL(k_keep_normals, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, in->nx, in->ny, in->nz, keep);
+            return "k_keep_normals";
+        },
+        [&](const Compaction& c) {
+            hipLaunchKernelGGL(k_gather_points, dim3((c.max_run + 255) / 256, n_obj), dim3(256), 0, ctx->stream, c.off, c.new_off, c.keep, c.pos, *in, *out);
+            return "k_gather_points";
+        });
 }
 
 extern "C" int ismhip_filter_normals(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const ismhip_point_arrays* in,

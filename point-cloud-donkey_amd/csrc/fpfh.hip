@@ -10,8 +10,6 @@
 #include "common.h"
 #include <cstdlib>
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 namespace {
 
 struct FpfhArgs {
@@ -324,14 +322,11 @@ extern "C" int ismhip_fpfh33(ismhip_ctx* ctx, const ismhip_cloud* cloud, const u
     if (!ctx || !cloud || !kp_offsets_h || !kpx || !kpy || !kpz || !desc_out || !(radius > 0.f))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "fpfh33: bad argument");
     const int n_obj = cloud->n_obj;
-    uint32_t maxk = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (kp_offsets_h[o + 1] < kp_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "fpfh33: offsets not monotone");
-        maxk = std::max(maxk, kp_offsets_h[o + 1] - kp_offsets_h[o]);
-    }
+    RaggedOffsets kp;
+    int rc = ism_ragged_offsets(ctx, "fpfh33", kp_offsets_h, n_obj, SCR_KP_OFF, 0, &kp);
+    if (rc != ISMHIP_OK) return rc;
+    const uint32_t maxk = kp.max_run;
     if (maxk == 0) return ISMHIP_OK;
-    uint32_t* ko = ism_upload_offsets(ctx, SCR_KP_OFF, kp_offsets_h, n_obj + 1);
-    if (!ko) return ISMHIP_ERR_HIP;
     const size_t np = cloud->n_pts ? cloud->n_pts : 1;
     uint8_t* flag = (uint8_t*)ism_scratch(ctx, SCR_FPFH_FLAG, np);
     float* spfh = (float*)ism_scratch(ctx, SCR_FPFH_SPFH, np * 33 * sizeof(float));
@@ -339,7 +334,7 @@ extern "C" int ismhip_fpfh33(ismhip_ctx* ctx, const ismhip_cloud* cloud, const u
     FpfhArgs a;
     a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.cell_start = cloud->cell_start;
     a.sp4 = cloud->sp4; a.sn4 = cloud->sn4;
-    a.kp_off = ko; a.kx = kpx; a.ky = kpy; a.kz = kpz;
+    a.kp_off = kp.dev; a.kx = kpx; a.ky = kpy; a.kz = kpz;
     a.radius = radius; a.r2 = (float)((double)radius * (double)radius);
     a.flag = flag; a.spfh = spfh; a.desc = desc_out; a.count = neighbour_count_out; a.max_pts = cloud->max_pts;
     { const char* e = getenv("ISMHIP_FPFH_DBG"); a.dbg = e ? atoi(e) : 0; }

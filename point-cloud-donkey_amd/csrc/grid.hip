@@ -116,31 +116,14 @@ __global__ __launch_bounds__(1024) void k_scan(const GridMeta* __restrict__ meta
     const GridMeta m = meta[o];
     const int ncell = m.dim[0] * m.dim[1] * m.dim[2];
     uint32_t* cs = cell_start + (size_t)o * ISM_GRID_STRIDE;
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
+    __shared__ BlockScan<1024> scan;
+    scan.init();
     for (int base = 0; base < ncell; base += 1024) {
         const int i = base + threadIdx.x;
-        const uint32_t v = i < ncell ? cs[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            uint32_t t = __shfl_up(incl, off, 64);
-            if (lane_id() >= off) incl += t;
-        }
-        const int w = threadIdx.x >> 6;
-        if (lane_id() == 63) s_wave[w] = incl;
-        __syncthreads();
-        uint32_t wave_off = 0;
-        for (int k = 0; k < w; ++k) wave_off += s_wave[k];
-        const uint32_t carry = s_carry;
-        if (i < ncell) cs[i] = carry + wave_off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
-        __syncthreads();
+        const uint32_t start = scan.step(i < ncell ? cs[i] : 0u);
+        if (i < ncell) cs[i] = start;
     }
-    if (threadIdx.x == 0) cs[ncell] = s_carry;
+    if (threadIdx.x == 0) cs[ncell] = scan.total();
 }
 
 // members[b + cell_start[c] + arrival rank] = object-local index: the points of every cell, grouped (arrival order)
@@ -471,7 +454,6 @@ __global__ __launch_bounds__(256) void k_center_dist(const GridMeta* __restrict_
 
 }  // namespace
 
-// uploads a small host offsets array into a scratch slot; returns device pointer (nullptr on failure)
 uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n) {
     uint32_t* d = (uint32_t*)ism_scratch(ctx, slot, (size_t)n * sizeof(uint32_t));
     if (!d) return nullptr;
@@ -480,6 +462,30 @@ uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, i
         return nullptr;
     }
     return d;
+}
+
+int ism_ragged_offsets(ismhip_ctx* ctx, const std::string& name, const uint32_t* off_h, int n, int slot, int flags, RaggedOffsets* r) {
+    *r = RaggedOffsets{};
+    for (int i = 0; i < n; ++i) {
+        if (off_h[i + 1] < off_h[i]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": offsets not monotone");
+        r->max_run = std::max(r->max_run, off_h[i + 1] - off_h[i]);
+    }
+    if ((flags & RAGGED_START0) && off_h[0] != 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": offsets must start at 0");
+    r->total = off_h[n];
+    if (r->max_run == 0 && !(flags & RAGGED_EMPTY)) return ISMHIP_OK;
+    r->dev = ism_upload_offsets(ctx, slot, off_h, n + 1);
+    return r->dev ? ISMHIP_OK : ISMHIP_ERR_HIP;
+}
+
+int ism_offsets_from_counts(ismhip_ctx* ctx, int n, const uint32_t* cnt_d, uint32_t* off_h_out, uint32_t* max_run_out) {
+    std::vector<uint32_t> cnt_h(n);
+    ISM_HIP(ctx, hipMemcpyAsync(cnt_h.data(), cnt_d, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t max_run = 0;
+    off_h_out[0] = 0;
+    for (int i = 0; i < n; ++i) { off_h_out[i + 1] = off_h_out[i] + cnt_h[i]; max_run = std::max(max_run, cnt_h[i]); }
+    if (max_run_out) *max_run_out = max_run;
+    return ISMHIP_OK;
 }
 
 // The cell-order permutation of a keypoint set on this cloud (device pointer), built on the ctx stream when the cloud does not hold it

@@ -19,10 +19,6 @@
 #include "common.h"
 #include "eigen3.h"
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
-                             const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
-
 namespace {
 
 
@@ -308,16 +304,12 @@ extern "C" int ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const
     if (!ctx || !cloud || !kp_offsets_h || !kpx || !kpy || !kpz || !lrf9_out || !(radius > 0.f))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "shot_lrf: bad argument");
     const int n_obj = cloud->n_obj;
-    uint32_t maxk = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (kp_offsets_h[o + 1] < kp_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "shot_lrf: offsets not monotone");
-        maxk = std::max(maxk, kp_offsets_h[o + 1] - kp_offsets_h[o]);
-    }
-    if (kp_offsets_h[0] != 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "shot_lrf: offsets must start at 0");
-    const uint32_t nkp = kp_offsets_h[n_obj];
-    if (nkp == 0 || maxk == 0) return ISMHIP_OK;
-    uint32_t* ko = ism_upload_offsets(ctx, SCR_KP_OFF, kp_offsets_h, n_obj + 1);
-    if (!ko) return ISMHIP_ERR_HIP;
+    RaggedOffsets kp;
+    int rc = ism_ragged_offsets(ctx, "shot_lrf", kp_offsets_h, n_obj, SCR_KP_OFF, RAGGED_START0, &kp);
+    if (rc != ISMHIP_OK) return rc;
+    const uint32_t maxk = kp.max_run, nkp = kp.total;
+    if (maxk == 0) return ISMHIP_OK;
+    const uint32_t* ko = kp.dev;
     uint32_t* tie_count = (uint32_t*)ism_scratch(ctx, SCR_COUNTERS, 64);
     TieRec* tie_rec = (TieRec*)ism_scratch(ctx, SCR_TIE_REC, (size_t)nkp * sizeof(TieRec));
     double* cov = (double*)ism_scratch(ctx, SCR_LRF_COV, (size_t)nkp * 14 * sizeof(double));

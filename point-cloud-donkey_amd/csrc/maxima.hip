@@ -61,23 +61,12 @@ __global__ __launch_bounds__(256) void k_class_counts(int n_classes, const uint3
     for (int c = threadIdx.x; c < n_classes; c += 256) counts[(size_t)o * n_classes + c] = s_c[c];
 }
 __global__ __launch_bounds__(1024) void k_work_offsets(uint32_t n_oc, const uint32_t* __restrict__ counts, uint32_t* __restrict__ work_off) {
-    __shared__ uint32_t s_w[16], s_base;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
+    __shared__ BlockScan<1024> scan;
+    scan.init();
     for (uint32_t c0 = 0; c0 < n_oc; c0 += 1024) {
         const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = i < n_oc && counts[i] ? (uint32_t)pow2_cap(counts[i]) : 0u;
-        uint32_t inc = v;                                         // inclusive wave scan
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d, 64); if (lane_id() >= d) inc += t; }
-        if (lane_id() == 63) s_w[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint32_t off = s_base;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) off += s_w[w];
-        if (i < n_oc) work_off[i] = off + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_base = off + inc;
-        __syncthreads();
+        const uint32_t off = scan.step(i < n_oc && counts[i] ? (uint32_t)pow2_cap(counts[i]) : 0u);
+        if (i < n_oc) work_off[i] = off;
     }
 }
 
@@ -910,8 +899,6 @@ __global__ __launch_bounds__(256) void k_hough3d_ransac(HoughArgs a, RansacKArgs
 
 }  // namespace
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 // workspace of the big-object kernels: counts[n_oc] | offsets[n_oc] | regions (<= 2 * slots + nothing for absent classes)
 static int big_object_workspace(ismhip_ctx* ctx, int n_obj, int n_classes, const uint32_t* slot_offsets_h, const uint32_t* slot_off_d, const int32_t* vote_class,
                                 unsigned char** work, const uint32_t** work_off, const uint32_t** class_count) {
@@ -975,20 +962,17 @@ static int maxima_setup(ismhip_ctx* ctx, const MaximaCall& io, const Params* P, 
         !io.max_n_votes || !io.class_score || P->n_classes <= 0 || P->max_maxima <= 0 || !size_given)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": bad argument");
     if (P->n_classes > MX_MAXC) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, name + ": more than 256 classes not built");
-    uint32_t max_slots = 0;
-    for (int o = 0; o < io.n_obj; ++o) {
-        if (io.slot_offsets_h[o + 1] < io.slot_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": offsets not monotone");
-        max_slots = std::max(max_slots, io.slot_offsets_h[o + 1] - io.slot_offsets_h[o]);
-    }
+    RaggedOffsets slots;
+    int rc = ism_ragged_offsets(ctx, name, io.slot_offsets_h, io.n_obj, SCR_SLOT_OFF, RAGGED_EMPTY, &slots);
+    if (rc != ISMHIP_OK) return rc;
     if (P->max_filter != ISMHIP_MAXFILTER_NONE && P->max_filter != ISMHIP_MAXFILTER_SIMPLE && P->max_filter != ISMHIP_MAXFILTER_MERGE)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": MaxFilterType");
     if ((P->vote_bbox_quat == nullptr) != (P->max_bbox_quat_out == nullptr)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, name + ": vote_bbox_quat and max_bbox_quat_out go together");
     MaxArgs& a = pl->a;
     a = MaxArgs{};
-    a.cap = 64; while ((uint32_t)a.cap < max_slots) a.cap <<= 1;
+    a.cap = 64; while ((uint32_t)a.cap < slots.max_run) a.cap <<= 1;
     pl->big = a.cap > MX_LDS_SLOTS;
-    uint32_t* so = ism_upload_offsets(ctx, SCR_SLOT_OFF, io.slot_offsets_h, io.n_obj + 1);
-    if (!so) return ISMHIP_ERR_HIP;
+    uint32_t* so = slots.dev;
     pl->class_val = nullptr;
     if (class_val_h) {
         pl->class_val = (float*)ism_scratch(ctx, SCR_CLASS_BW, (size_t)P->n_classes * 4);
@@ -1005,10 +989,10 @@ static int maxima_setup(ismhip_ctx* ctx, const MaximaCall& io, const Params* P, 
     a.rec = (float*)ism_scratch(ctx, SCR_MAX_REC, n_oc * MX_MAXM_C * MX_REC * sizeof(float) + n_oc * sizeof(int32_t));
     if (!a.rec) return ISMHIP_ERR_NOMEM;
     a.rec_count = (int32_t*)(a.rec + n_oc * MX_MAXM_C * MX_REC);
-    if (pl->big) { int rc = big_object_workspace(ctx, io.n_obj, P->n_classes, io.slot_offsets_h, so, io.vote_class, &a.work, &a.work_off, &a.class_count); if (rc != ISMHIP_OK) return rc; }
+    if (pl->big) { rc = big_object_workspace(ctx, io.n_obj, P->n_classes, io.slot_offsets_h, so, io.vote_class, &a.work, &a.work_off, &a.class_count); if (rc != ISMHIP_OK) return rc; }
     pl->rk = RansacKArgs{};
     if (io.ransac) {
-        int rc = ransac_kernel_args(ctx, (name + "_ransac").c_str(), io.R, P->n_classes, n_oc, io.max_transform != nullptr, &pl->rk);
+        rc = ransac_kernel_args(ctx, (name + "_ransac").c_str(), io.R, P->n_classes, n_oc, io.max_transform != nullptr, &pl->rk);
         if (rc != ISMHIP_OK) return rc;
         a.mtf = io.max_transform; a.rec_tf = pl->rk.rec_tf;
     }

@@ -80,8 +80,6 @@ __global__ __launch_bounds__(256) void k_vote_keypoints(const uint32_t* __restri
 
 }  // namespace
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 unsigned long long* ism_ransac_counters(ismhip_ctx* ctx) {
     if (!ctx->ransac_counters_d) {
         if (hipMalloc((void**)&ctx->ransac_counters_d, 4 * sizeof(unsigned long long)) != hipSuccess) { ism_set_err(ctx, ISMHIP_ERR_NOMEM, "ransac counters"); return nullptr; }
@@ -97,20 +95,18 @@ static int ransac_launch(ismhip_ctx* ctx, const char* what, int n_clusters, cons
     if (!ctx || n_clusters < 0 || !cluster_offsets_h || !threshold_h || !inlier_out || !kept_out || !n_inliers_out || max_iterations < 0)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(what) + ": bad argument");
     if (n_clusters == 0) return ISMHIP_OK;
-    for (int c = 0; c < n_clusters; ++c) {
-        if (cluster_offsets_h[c + 1] < cluster_offsets_h[c]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(what) + ": offsets not monotone");
-        if (cluster_offsets_h[c + 1] - cluster_offsets_h[c] > 0x7fffffffu) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, std::string(what) + ": a cluster of 2^31 votes or more is not built");
-    }
-    if (cluster_offsets_h[n_clusters] > 0 && (!src_xyz || !tgt_xyz)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(what) + ": bad argument");
-    uint32_t* off = ism_upload_offsets(ctx, SCR_SLOT_OFF, cluster_offsets_h, n_clusters + 1);
-    if (!off) return ISMHIP_ERR_HIP;
+    RaggedOffsets clusters;
+    int rc = ism_ragged_offsets(ctx, what, cluster_offsets_h, n_clusters, SCR_SLOT_OFF, RAGGED_EMPTY, &clusters);
+    if (rc != ISMHIP_OK) return rc;
+    if (clusters.max_run > 0x7fffffffu) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, std::string(what) + ": a cluster of 2^31 votes or more is not built");
+    if (clusters.total > 0 && (!src_xyz || !tgt_xyz)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(what) + ": bad argument");
     const size_t per = hypothesis_h ? 8 : 4;
     unsigned char* scr = (unsigned char*)ism_scratch(ctx, SCR_CLASS_BW, (size_t)n_clusters * per);
     if (!scr) return ISMHIP_ERR_NOMEM;
     ISM_HIP(ctx, hipMemcpyAsync(scr, threshold_h, (size_t)n_clusters * 4, hipMemcpyHostToDevice, ctx->stream));
     if (hypothesis_h) ISM_HIP(ctx, hipMemcpyAsync(scr + (size_t)n_clusters * 4, hypothesis_h, (size_t)n_clusters * 4, hipMemcpyHostToDevice, ctx->stream));
     RansacFilterArgs a;
-    a.off = off; a.src = src_xyz; a.tgt = tgt_xyz; a.thr = (const float*)scr; a.max_iter = std::min(max_iterations, 1 << 30); a.seed = seed;
+    a.off = clusters.dev; a.src = src_xyz; a.tgt = tgt_xyz; a.thr = (const float*)scr; a.max_iter = std::min(max_iterations, 1 << 30); a.seed = seed;
     a.only_hyp = hypothesis_h ? (const int32_t*)(scr + (size_t)n_clusters * 4) : nullptr;
     a.inl = inlier_out; a.kept = kept_out; a.n_inl = n_inliers_out; a.best_i = best_hypothesis_out; a.iters = iterations_out; a.tf = transform_out;
     a.d2 = d2_out; a.tf_d = transform_d_out;

@@ -14,10 +14,6 @@
 // L2-normalises and writes the row with coalesced stores.
 #include "common.h"
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
-                             const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
-
 namespace {
 
 #define PST_RAD_45f   0.78539816339744830962f
@@ -300,18 +296,15 @@ int launch_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_o
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": bad argument");
     if (COLOR && (!cloud->rgba || !kp_rgba)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": colour arrays missing");
     const int n_obj = cloud->n_obj;
-    uint32_t maxk = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (kp_offsets_h[o + 1] < kp_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": offsets not monotone");
-        maxk = std::max(maxk, kp_offsets_h[o + 1] - kp_offsets_h[o]);
-    }
+    RaggedOffsets kp;
+    int rc = ism_ragged_offsets(ctx, name, kp_offsets_h, n_obj, SCR_KP_OFF, 0, &kp);
+    if (rc != ISMHIP_OK) return rc;
+    const uint32_t maxk = kp.max_run;
     if (maxk == 0) return ISMHIP_OK;
-    uint32_t* ko = ism_upload_offsets(ctx, SCR_KP_OFF, kp_offsets_h, n_obj + 1);
-    if (!ko) return ISMHIP_ERR_HIP;
     ShotArgs a;
     a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.cell_start = cloud->cell_start;
     a.sp4 = cloud->sp4; a.sn4 = cloud->sn4; a.slab4 = cloud->slab4;
-    a.kp_off = ko; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.kp_rgba = kp_rgba; a.lrf = lrf9;
+    a.kp_off = kp.dev; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.kp_rgba = kp_rgba; a.lrf = lrf9;
     a.radius = radius; a.r2 = (float)((double)radius * (double)radius);
     {   // largest float <= (radius/2)^2 taken in double: the shell test (double)d2 > r12sq of the reference, as a float compare
         const double t = 0.25 * (double)radius * (double)radius;
@@ -323,7 +316,7 @@ int launch_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_o
     a.desc = desc_out; a.count = count_out;
     a.n_obj = ctx->xcd_map ? n_obj : 0; a.nbx = (int)((maxk + 3) / 4);
     TimerScope ts(ctx, name);
-    a.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, ko, kpx, kpy, kpz, maxk);
+    a.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, kp.dev, kpx, kpy, kpz, maxk);
     const dim3 grid(ctx->xcd_map ? xcd_object_grid((unsigned)a.nbx, n_obj) : (unsigned)a.nbx * (unsigned)n_obj);
     if (ctx->shot_var & 2) hipLaunchKernelGGL((k_shot<COLOR, 2>), grid, dim3(256), 0, ctx->stream, a);      // contiguous sweep (A/B runs)
     else hipLaunchKernelGGL((k_shot<COLOR, 0>), grid, dim3(256), 0, ctx->stream, a);

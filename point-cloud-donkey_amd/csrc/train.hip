@@ -17,8 +17,6 @@
 #include <cstring>
 #include <numeric>
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 namespace {
 
 #include "functor.h"
@@ -41,30 +39,17 @@ __global__ void k_tr_flags(int n, int clean_up, const uint32_t* __restrict__ cnt
 // exclusive scans of up to three arrays of n entries by ONE workgroup (n <= a few million: training is not the hot path);
 // out[n] = total
 __global__ __launch_bounds__(1024) void k_tr_scan(int n, const uint32_t* a0, uint32_t* o0, const uint32_t* a1, uint32_t* o1, const uint32_t* a2, uint32_t* o2) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
+    __shared__ BlockScan<1024> scan;
     const uint32_t* in[3] = {a0, a1, a2}; uint32_t* out[3] = {o0, o1, o2};
     for (int arr = 0; arr < 3; ++arr) {
-        if (!in[arr]) continue;
-        if (threadIdx.x == 0) s_carry = 0;
-        __syncthreads();
+        if (!in[arr]) continue;                                  // workgroup-uniform
+        scan.init();
         for (int base = 0; base < n; base += 1024) {
             const int i = base + threadIdx.x;
-            const uint32_t v = i < n ? in[arr][i] : 0u;
-            const uint32_t incl = wave_incl_scan_u32(v);
-            const int w = threadIdx.x >> 6;
-            if (lane_id() == 63) s_wave[w] = incl;
-            __syncthreads();
-            uint32_t wave_off = 0;
-            for (int k = 0; k < w; ++k) wave_off += s_wave[k];
-            const uint32_t carry = s_carry;
-            if (i < n) out[arr][i] = carry + wave_off + incl - v;
-            __syncthreads();
-            if (threadIdx.x == 1023) s_carry = carry + wave_off + incl;
-            __syncthreads();
+            const uint32_t start = scan.step(i < n ? in[arr][i] : 0u);
+            if (i < n) out[arr][i] = start;
         }
-        if (threadIdx.x == 0) out[arr][n] = s_carry;
-        __syncthreads();
+        if (threadIdx.x == 0) out[arr][n] = scan.total();        // thread 0 is also the one that clears the carry for the next array
     }
 }
 __global__ void k_tr_members(int na, const int32_t* __restrict__ act, const uint32_t* __restrict__ all_off, const uint32_t* __restrict__ rank,

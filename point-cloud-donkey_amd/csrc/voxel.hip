@@ -11,8 +11,6 @@
 // Memory-bound and small next to the descriptors: N points read once, sum(div0*div1*div2) table entries written and read once.
 #include "common.h"
 
-uint32_t* ism_upload_offsets(ismhip_ctx* ctx, int slot, const uint32_t* off_h, int n);
-
 namespace {
 
 struct VoxMeta {
@@ -98,24 +96,14 @@ __global__ __launch_bounds__(256) void k_vox_emit(const uint32_t* __restrict__ p
     const int o = blockIdx.x;
     const VoxObj ob = objs[o];
     const uint32_t out0 = pt_off[o];
-    __shared__ uint32_t s_w[4];
-    __shared__ uint32_t s_carry;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    const int lane = lane_id(), w = threadIdx.x >> 6;
+    __shared__ BlockScan<256> scan;
+    scan.init();
     for (unsigned long long b = 0; b < ob.n_vox; b += 256) {
         const unsigned long long v = b + threadIdx.x;
         const uint32_t c = v < ob.n_vox ? t.cnt[ob.base + v] : 0u;
-        const uint32_t f = c ? 1u : 0u;
-        uint32_t incl = f;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t u = __shfl_up(incl, off, 64); if (lane >= off) incl += u; }
-        if (lane == 63) s_w[w] = incl;
-        __syncthreads();
-        uint32_t pre = s_carry;
-        for (int j = 0; j < w; ++j) pre += s_w[j];
-        if (f) {
-            const uint32_t dst = out0 + pre + incl - 1;
+        const uint32_t before = scan.step(c ? 1u : 0u);            // occupied voxels of the object below this one
+        if (c) {
+            const uint32_t dst = out0 + before;
             const float fc = (float)c;
             // the reference divides the float sum by the float count; the fixed-point sum converts exactly to double first
             kx[dst] = (float)((double)(long long)t.sx[ob.base + v] * (double)ob.fix_inv) / fc;
@@ -131,11 +119,8 @@ __global__ __launch_bounds__(256) void k_vox_emit(const uint32_t* __restrict__ p
                 krgba[dst] = col;
             }
         }
-        __syncthreads();
-        if (threadIdx.x == 0) s_carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
     }
-    if (threadIdx.x == 0) obj_count[o] = s_carry;
+    if (threadIdx.x == 0) obj_count[o] = scan.total();
 }
 
 // final packing: object o's staged run (at pt_off[o]) moves to kp_off[o]
@@ -158,19 +143,15 @@ extern "C" int ismhip_voxel_keypoints(ismhip_ctx* ctx, int n_obj, const uint32_t
                                       uint32_t capacity, float* kx, float* ky, float* kz, uint32_t* krgba, uint32_t* kp_offsets_h_out) {
     if (!ctx || n_obj <= 0 || !pt_offsets_h || !x || !y || !z || !kx || !ky || !kz || !kp_offsets_h_out || !(leaf > 0.f))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "voxel_keypoints: bad argument");
-    if (pt_offsets_h[0] != 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "voxel_keypoints: offsets must start at 0");
-    uint32_t maxn = 0;
-    for (int o = 0; o < n_obj; ++o) {
-        if (pt_offsets_h[o + 1] < pt_offsets_h[o]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "voxel_keypoints: offsets not monotone");
-        maxn = std::max(maxn, pt_offsets_h[o + 1] - pt_offsets_h[o]);
-    }
-    const uint32_t n_pts = pt_offsets_h[n_obj];
+    ISM_HIP(ctx, hipSetDevice(ctx->device));
+    RaggedOffsets pts;
+    int rc = ism_ragged_offsets(ctx, "voxel_keypoints", pt_offsets_h, n_obj, SCR_KP_OFF, RAGGED_START0, &pts);
+    if (rc != ISMHIP_OK) return rc;
+    const uint32_t n_pts = pts.total, maxn = pts.max_run;
     for (int o = 0; o <= n_obj; ++o) kp_offsets_h_out[o] = 0;
     if (n_pts == 0) return ISMHIP_OK;
-    ISM_HIP(ctx, hipSetDevice(ctx->device));
     TimerScope ts(ctx, "voxel_keypoints");
-    uint32_t* po = ism_upload_offsets(ctx, SCR_KP_OFF, pt_offsets_h, n_obj + 1);
-    if (!po) return ISMHIP_ERR_HIP;
+    const uint32_t* po = pts.dev;
     VoxMeta* meta = (VoxMeta*)ism_scratch(ctx, SCR_COUNTERS, (size_t)n_obj * (sizeof(VoxMeta) + sizeof(VoxObj) + sizeof(uint32_t)) + 64);
     if (!meta) return ISMHIP_ERR_NOMEM;
     hipLaunchKernelGGL(k_vox_bbox, dim3(n_obj), dim3(256), 0, ctx->stream, po, x, y, z, meta);
@@ -220,11 +201,9 @@ extern "C" int ismhip_voxel_keypoints(ismhip_ctx* ctx, int n_obj, const uint32_t
     ISM_CHECK_LAUNCH(ctx, "k_vox_accum");
     hipLaunchKernelGGL(k_vox_emit, dim3(n_obj), dim3(256), 0, ctx->stream, po, objs, t, rgba != nullptr, stx, sty, stz, krgba ? stc : nullptr, obj_count);
     ISM_CHECK_LAUNCH(ctx, "k_vox_emit");
-    std::vector<uint32_t> ch(n_obj);
-    ISM_HIP(ctx, hipMemcpyAsync(ch.data(), obj_count, (size_t)n_obj * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint32_t maxk = 0;
-    for (int o = 0; o < n_obj; ++o) { kp_offsets_h_out[o + 1] = kp_offsets_h_out[o] + ch[o]; maxk = std::max(maxk, ch[o]); }
+    rc = ism_offsets_from_counts(ctx, n_obj, obj_count, kp_offsets_h_out, &maxk);
+    if (rc != ISMHIP_OK) return rc;
     if (kp_offsets_h_out[n_obj] > capacity) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "voxel_keypoints: output capacity too small (n_points always suffices)");
     if (maxk == 0) return ISMHIP_OK;
     uint32_t* ko = (uint32_t*)ism_scratch(ctx, SCR_SLOT_OFF, (size_t)(n_obj + 1) * 4);

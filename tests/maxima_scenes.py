@@ -333,6 +333,26 @@ def many_pairs():
     return concat(scenes)
 
 
+EDGE_CLASSES, EDGE_SIZES = 205, [2100, 150, 10, 150, 300]
+
+
+def chunk_edge_pairs():
+    """5 objects x 205 classes = 1025 (object, class) pairs: one more than a pass of k_work_offsets, so the pair (4, 204) alone -- flat
+    index 1024 -- takes its region from the carry of everything before it. Object 0 has 2100 slots (the workspace path); every class
+    of an object is one tight blob around the class's centre; object 4 has 40 votes each in classes 203 and 204, the pairs on
+    either side of the edge"""
+    rng = np.random.default_rng(21)
+    centres = rng.uniform(-2.5, 2.5, (EDGE_CLASSES, 3))
+    scenes = []
+    for o, n in enumerate(EDGE_SIZES):
+        c = rng.integers(0, EDGE_CLASSES, n)
+        if o == 4:
+            c[:40], c[40:80] = EDGE_CLASSES - 1, EDGE_CLASSES - 2
+        pos = centres[c] + 0.05 * rng.normal(size=(n, 3))
+        scenes.append((np.asarray([0, n], np.uint32), pack(pos, rng.uniform(0.2, 1.0, n), c, rng.integers(0, 4, n), rng.uniform(0.5, 1.5, (n, 3)))))
+    return concat(scenes)
+
+
 # the option sets of scene 10; every one runs on the LDS path (scene alone) and on the workspace path (2049-slot object appended)
 OPT_CLASS_BW = [0.3, 0.5, 0.8, 0.4]
 MS_BASE = dict(n_classes=OPT_CLASSES, bandwidth=0.5, max_maxima=16, min_votes_threshold=2)

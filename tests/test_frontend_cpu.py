@@ -49,6 +49,16 @@ def test_build_sizes_straddle_the_fused_limit():
     assert np.abs(far).min(0).max() >= 1000                                  # where |q| * 4e-7 exceeds r * 1e-5 in ball_cells
 
 
+def test_grid_build_scenes_lie_on_both_sides_of_the_scan_chunk():
+    """the five-kernel grid build scans an object's cell counts 1024 at a time (k_scan): the batches that test_gpu_grid_fused.py
+    compares byte for byte hold objects that need one pass, objects that need three or more, and the largest table there is"""
+    import test_gpu_grid_fused as gf
+    for seed in (11, 12, 13):                                                # the seeds of its comparisons
+        cells = [int(gm.Grid(p, gf.CELL).dim.prod()) for p, _ in gf._objects(np.random.default_rng(seed))]
+        assert min(cells) <= 1024 and sum(1024 < c < 2049 for c in cells) >= 1 and sum(c >= 2049 for c in cells) >= 3
+        assert max(cells) > 28 * 1024                                        # 29 carries in one object
+
+
 @pytest.mark.parametrize("xfrac", [None] + fs.XFRACS)
 def test_thin_batch_changes_its_grid_with_the_x_fraction(xfrac):
     """the scene of the ISMHIP_GRID_XFRAC cases: below the per-axis cap on x at every tested fraction, so each value builds another

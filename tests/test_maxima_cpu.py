@@ -314,3 +314,19 @@ def test_many_pairs_need_the_second_chunk_of_the_offsets(ora):
                 ora.hough3d_maxima(off, v, n_classes=128, bin_size=0.5, rel_threshold=0.5, max_maxima=160)):
         assert out["n"][ms.MANY_BIG] == 128 and sorted(out["cls"][ms.MANY_BIG, :128].tolist()) == list(range(128))
         assert out["n"][:8].min() >= 40 and out["n"].max() < 160
+
+
+def test_chunk_edge_pairs_put_one_pair_past_the_first_pass(ora):
+    """5 x 205 = 1025 pairs: the last one, (4, 204), is the only entry of the second pass of k_work_offsets and its region starts at
+    the sum of all the others; object 0 sends the call down the workspace path; both pairs beside the edge hold votes and a maximum"""
+    off, v = ms.chunk_edge_pairs()
+    cap, big = mm.launch(off)
+    assert big and np.diff(off.astype(np.int64)).tolist() == ms.EDGE_SIZES
+    counts = mm.class_counts(off, v["cls"], ms.EDGE_CLASSES)
+    assert counts.size == mm.OFFSET_CHUNK + 1
+    offs, chunk = mm.work_offsets(counts)
+    assert chunk.ravel().tolist() == [0] * mm.OFFSET_CHUNK + [1] and counts[4, -2:].min() >= 40
+    assert offs[4, -1] == offs[4, -2] + 64 and offs[4, -1] == sum(0 if c == 0 else max(64, 1 << int(c - 1).bit_length()) for c in counts.ravel()[:-1].tolist())
+    out = ora.find_maxima(off, v, n_classes=ms.EDGE_CLASSES, bandwidth=0.5, max_maxima=256)
+    assert out["n"][0] == ms.EDGE_CLASSES and {ms.EDGE_CLASSES - 2, ms.EDGE_CLASSES - 1} <= set(out["cls"][4, :out["n"][4]].tolist())
+
