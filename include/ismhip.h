@@ -67,6 +67,7 @@ extern "C" {
 #define ISMHIP_SHOT_DIM   352
 #define ISMHIP_CSHOT_DIM 1344
 #define ISMHIP_FPFH_DIM    33
+#define ISMHIP_SHORT_SHOT_MAX_DIM 256   /* r_bins * e_bins * a_bins of ismhip_short_shot */
 
 typedef struct ismhip_ctx      ismhip_ctx;
 typedef struct ismhip_cloud    ismhip_cloud;
@@ -86,7 +87,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -176,6 +177,30 @@ int  ismhip_cshot1344(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t
 int  ismhip_fpfh33(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                    const float* kpx, const float* kpy, const float* kpz,
                    float radius, float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesSHORTSHOT::compute_descriptor (features/features_short_shot.cpp:77-156) with compute_shape_descriptor (:159-243),
+ * linear_interpolation (:246-260) and correct_bin (:263-283): the generalised Short SHOT on a spherical grid of r_bins x e_bins x a_bins
+ * bins around the keypoint's frame. desc_out[nkp * r_bins*e_bins*a_bins]. Per keypoint with a finite frame [x;y;z]:
+ *  - neighbours: d2 < (float)((double)radius * radius), d2 the unfused float (dx*dx + dy*dy) + dz*dz -- the predicate and the
+ *    neighbour_count_out of ismhip_shot352; a neighbour with d2 <= 1e-15f (the SQUARED distance, :127) is skipped;
+ *  - x_l = (double)((v.x*X.x + v.y*X.y) + v.z*X.z) in float, unfused, in this order (the reference's Eigen Vector4f::dot does not state
+ *    its order: this one is the library's definition), likewise y_l, z_l; then in double r = sqrt(x_l^2 + y_l^2 + z_l^2), skipped if
+ *    r < (double)min_radius, theta = acos(z_l / r) * 57.29578, phi = atan2(y_l, x_l) * 57.29578 (pcl::rad2deg(double) of PCL 1.10);
+ *  - float raw_r = (float)(r_bins * r / (double)radius), or with log_radius (float)((r_bins - 1) * (log(r) - log(min_radius)) /
+ *    log(radius / min_radius) + 1); float raw_theta = (float)(e_bins * theta / 180); float raw_phi = (float)(a_bins * (phi + 180) / 360);
+ *    primary bins int(raw), r clamped to [0, r_bins - 1], theta and phi from above only; per axis decimals = raw - (int)raw (float),
+ *    share f = decimals + 0.5 towards -1 if decimals <= 0.5f, else (1 - decimals) + 0.5 towards +1; a secondary bin exists for an axis
+ *    with more than one bin when the corrected neighbour (r, theta clamp; phi wraps) differs from the primary; the primary bin receives
+ *    f_r + f_theta + f_phi, the secondary bin of an axis the same sum with that axis' share replaced by 1 - f;
+ *    bin index = bin_r + bin_theta * r_bins + bin_phi * r_bins * e_bins;
+ *  - the row is divided by its L2 norm (double) and cast to float. ONE contributing neighbour is enough (no five-neighbour rule); none
+ *    gives 0 / 0: the row is NaN AS A WHOLE (:143-152), as for a non-finite frame or keypoint (count 0).
+ * The caller derives min_radius (:88-103): Radius * ShortShotMinRadius with UseMinRadius, else 0.1 * Radius with ShortShotLogRadius, else 0.
+ * Refused: a bin count < 1 or min_radius < 0 (ISMHIP_ERR_INVALID), more than ISMHIP_SHORT_SHOT_MAX_DIM bins (ISMHIP_ERR_UNSUPPORTED),
+ * log_radius without 0 < min_radius < radius (ISMHIP_ERR_INVALID: the reference divides by log(radius / 0)-derived zeros). Timer "short_shot". */
+int  ismhip_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                       const float* kpx, const float* kpy, const float* kpz, const float* lrf9,
+                       float radius, float min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
+                       float* desc_out, uint32_t* neighbour_count_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
@@ -202,7 +227,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

@@ -31,7 +31,7 @@ EXPORTS = [
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
-    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac",
+    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -253,6 +253,41 @@ def cshot1344(ctx, cloud, kp_offsets, kpx, kpy, kpz, kp_rgba, lrf, radius, want_
     ctx.check(lib().ismhip_cshot1344(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(kp_rgba), _p(lrf), C.c_float(radius),
                                      _p(out), _p(cnt)), "ismhip_cshot1344")
     return (out, cnt) if want_counts else out
+
+
+def short_shot(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, bins=(2, 2, 8), min_radius=0.0, log_radius=False, want_counts=False):
+    """ismhip_short_shot on the (r, e, a) bins -> [nkp, r * e * a]; min_radius is the absolute one (short_shot_min_radius derives it)"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    r, e, a = (int(b) for b in bins)
+    out = torch.empty((n, max(r * e * a, 0) if min(r, e, a) > 0 else 0), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_short_shot(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(lrf), C.c_float(radius), C.c_float(min_radius),
+                                      C.c_int(1 if log_radius else 0), C.c_int(r), C.c_int(e), C.c_int(a), _p(out), _p(cnt)), "ismhip_short_shot")
+    return (out, cnt) if want_counts else out
+
+
+SHORT_SHOT_AUTO_BINS = {8: (1, 1, 8), 16: (2, 2, 4), 24: (2, 2, 6), 32: (2, 2, 8), 64: (2, 4, 8), 96: (3, 4, 8), 128: (4, 4, 8), 192: (6, 4, 8),
+                        256: (8, 4, 8)}
+
+
+def short_shot_grid(dims=32, bin_type="auto", bins=(2, 2, 8)):
+    """FeaturesSHORTSHOT::configureSphericalGrid (features_short_shot.cpp:285-366) -> (dims, (r, e, a)): "auto" maps the nine sizes,
+    "manual" takes the bins; an unknown size or bin type falls back to 32 / (2, 2, 8) as the reference does (with its LOG_ERROR)"""
+    if bin_type == "manual":
+        r, e, a = (int(b) for b in bins)
+        return r * e * a, (r, e, a)
+    if bin_type == "auto" and int(dims) in SHORT_SHOT_AUTO_BINS:
+        return int(dims), SHORT_SHOT_AUTO_BINS[int(dims)]
+    return 32, (2, 2, 8)
+
+
+def short_shot_min_radius(radius, use_min_radius=False, min_radius_relative=0.0, log_radius=False):
+    """the absolute minimum radius of compute_descriptor (:88-103) as the float the C ABI takes"""
+    if use_min_radius:
+        return float(np.float32(float(np.float32(radius)) * float(min_radius_relative)))
+    return float(np.float32(float(np.float32(radius)) * float(np.float32(0.1)))) if log_radius else 0.0
 
 
 def fpfh33(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False):

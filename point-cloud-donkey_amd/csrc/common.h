@@ -338,6 +338,23 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// atan2 to ~1e-7 absolute (Abramowitz & Stegun 4.4.49, |err| <= 2e-8 before rounding) without OCML's expansion: for weights that are
+// continuous in the angle (shot.hip) and for estimates whose hard decisions are re-taken exactly when they come close (short_shot.hip)
+__device__ __forceinline__ float shot_atan2(float y, float x) {
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
+    const float a = mn * __builtin_amdgcn_rcpf(mx);          // mx > 0: the caller excludes x == y == 0
+    const float z = a * a;
+    float p = 0.0028662257f;
+    p = __builtin_fmaf(p, z, -0.0161657367f); p = __builtin_fmaf(p, z, 0.0429096138f); p = __builtin_fmaf(p, z, -0.0752896400f);
+    p = __builtin_fmaf(p, z, 0.1065626393f); p = __builtin_fmaf(p, z, -0.1420889944f); p = __builtin_fmaf(p, z, 0.1999355085f);
+    p = __builtin_fmaf(p, z, -0.3333314528f); p = __builtin_fmaf(p, z, 1.0f);
+    float r = a * p;
+    if (ay > ax) r = 1.57079632679489661923f - r;
+    if (x < 0.f) r = 3.14159265358979323846f - r;
+    return y < 0.f ? -r : r;
+}
+
 // XCD-local block map for the per-object kernels. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs
 // (blocks b and b + 8 share one, MI355X_MICROARCH "Workgroup dispatch"), each with its own 4 MiB L2. With a (blocks, objects) 2-D
 // grid the blocks of ONE object land on all eight XCDs and every L2 pulls every object's cloud from beyond (measured round 1:

@@ -45,7 +45,7 @@ typedef unsigned long long shot_bin_t;
 // The interpolation weights are CONTINUOUS in distance / inclination / azimuth (all hard bin decisions are taken on the
 // signs and squares above them), so these three only need ~1e-7 absolute accuracy -- far inside the 1e-4 parity tolerance --
 // and not libm's last ulp: the IEEE division / sqrt expansions and OCML's acosf / atan2f were a quarter of the kernel's VALU.
-// acos: Abramowitz & Stegun 4.4.46 (|err| <= 2e-8 before rounding); atan: A&S 4.4.49 (|err| <= 2e-8).
+// acos: Abramowitz & Stegun 4.4.46 (|err| <= 2e-8 before rounding); atan: A&S 4.4.49 (|err| <= 2e-8), shot_atan2 in common.h.
 __device__ __forceinline__ float shot_acos(float x) {
     const float a = fabsf(x);
     float p = -0.0012624911f;
@@ -55,21 +55,6 @@ __device__ __forceinline__ float shot_acos(float x) {
     const float r = __builtin_amdgcn_sqrtf(fmaxf(1.0f - a, 0.f)) * p;
     return x < 0.f ? 3.14159265358979323846f - r : r;
 }
-__device__ __forceinline__ float shot_atan2(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    const float a = mn * __builtin_amdgcn_rcpf(mx);          // mx > 0: the caller excludes x == y == 0
-    const float z = a * a;
-    float p = 0.0028662257f;
-    p = __builtin_fmaf(p, z, -0.0161657367f); p = __builtin_fmaf(p, z, 0.0429096138f); p = __builtin_fmaf(p, z, -0.0752896400f);
-    p = __builtin_fmaf(p, z, 0.1065626393f); p = __builtin_fmaf(p, z, -0.1420889944f); p = __builtin_fmaf(p, z, 0.1999355085f);
-    p = __builtin_fmaf(p, z, -0.3333314528f); p = __builtin_fmaf(p, z, 1.0f);
-    float r = a * p;
-    if (ay > ax) r = 1.57079632679489661923f - r;
-    if (x < 0.f) r = 3.14159265358979323846f - r;
-    return y < 0.f ? -r : r;
-}
-
 // step = floor(m*x + c) and off = float((m*x + c0) - step) exactly as the reference's double arithmetic yields them, for a float x
 // whose product m*x (m = 5 or 30) is exact in double -- true wherever m*x + c can reach an integer. One fma rounds the exact value
 // once; floor of the rounded value differs from the true floor only if the rounding went UP onto an integer, which the sign of a

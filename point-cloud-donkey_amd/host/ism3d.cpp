@@ -357,6 +357,45 @@ std::shared_ptr<DeviceFeatures> Features::operator()(DeviceSession& s) const {  
 FeaturesSHOT::FeaturesSHOT() { addParameter(m_radius, "Radius", 0.1f); }
 FeaturesCSHOT::FeaturesCSHOT() { addParameter(m_radius, "Radius", 0.1f); }
 FeaturesFPFH::FeaturesFPFH() { addParameter(m_radius, "Radius", 0.1f); }
+FeaturesSHORTSHOT::FeaturesSHORTSHOT() {         // features_short_shot.cpp:21-32
+    addParameter(m_radius, "Radius", 0.1f);
+    addParameter(m_use_min_radius, "UseMinRadius", false);
+    addParameter(m_min_radius_relative, "ShortShotMinRadius", 0.0);
+    addParameter(m_feature_dims, "ShortShotDims", 32);
+    addParameter(m_log_radius, "ShortShotLogRadius", false);
+    addParameter(m_r_bins, "ShortShotRBins", 2);
+    addParameter(m_e_bins, "ShortShotEBins", 2);
+    addParameter(m_a_bins, "ShortShotABins", 8);
+    addParameter(m_bin_type, "ShortShotBinType", std::string("auto"));
+}
+float FeaturesSHORTSHOT::getMinRadius() const {  // :88-103 (the reference's default relative value is the float 0.1f)
+    if (m_use_min_radius) return (float)((double)m_radius * m_min_radius_relative);
+    return m_log_radius ? (float)((double)m_radius * (double)0.1f) : 0.0f;
+}
+void FeaturesSHORTSHOT::iPostInitConfig() {      // configureSphericalGrid, :285-366: run once the config has been read
+    static const int sizes[9][4] = {{8, 1, 1, 8}, {16, 2, 2, 4}, {24, 2, 2, 6}, {32, 2, 2, 8}, {64, 2, 4, 8}, {96, 3, 4, 8}, {128, 4, 4, 8}, {192, 6, 4, 8}, {256, 8, 4, 8}};
+    bool fallback = false;
+    if (m_bin_type == "auto") {
+        const int* row = nullptr;
+        for (const auto& r : sizes) if (r[0] == m_feature_dims) row = r;
+        if (row) { m_r_bins = row[1]; m_e_bins = row[2]; m_a_bins = row[3]; }
+        else { LOG_ERROR("Unsupported Short SHOT dimensions for automatic bin configuration: " << m_feature_dims << "! Setting to 32 dimensions with default bins."); fallback = true; }
+    } else if (m_bin_type == "manual") {
+        if (m_r_bins < 1 || m_e_bins < 1 || m_a_bins < 1) throw RuntimeException("SHORT_SHOT: fewer than one bin on an axis");
+        if ((long long)m_r_bins * m_e_bins * m_a_bins > ISMHIP_SHORT_SHOT_MAX_DIM)
+            throw RuntimeException("SHORT_SHOT: more than " + std::to_string(ISMHIP_SHORT_SHOT_MAX_DIM) + " bins are not built on the MI355X path");
+        m_feature_dims = m_r_bins * m_e_bins * m_a_bins;
+    } else {
+        LOG_ERROR("Unsupported Short SHOT bins configuration type: " << m_bin_type << "! Setting to 32 dimensions with default bins.");
+        fallback = true;
+    }
+    if (fallback) { m_r_bins = 2; m_e_bins = 2; m_a_bins = 8; m_feature_dims = 32; }
+    const float mr = getMinRadius();
+    if (!(mr >= 0.0f)) throw RuntimeException("SHORT_SHOT: negative minimum radius");
+    // the reference divides by log(Radius / min_radius) (0 for min_radius == 0) and converts the NaN to int: refused, never altered
+    if (m_log_radius && !(mr > 0.0f && mr < m_radius))
+        throw RuntimeException("SHORT_SHOT: ShortShotLogRadius needs a minimum radius inside (0, Radius); UseMinRadius with ShortShotMinRadius 0 leaves none");
+}
 
 void FeaturesSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_shot.cpp:28-81
     s.check(ismhip_shot352(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, desc_out, counts_out),
@@ -370,6 +409,10 @@ void FeaturesCSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, flo
 void FeaturesFPFH::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {        // features_fpfh.cpp:27-72
     s.check(ismhip_fpfh33(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, desc_out, counts_out),
             "ismhip_fpfh33");
+}
+void FeaturesSHORTSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_short_shot.cpp:38-156
+    s.check(ismhip_short_shot(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, getMinRadius(),
+                              m_log_radius ? 1 : 0, m_r_bins, m_e_bins, m_a_bins, desc_out, counts_out), "ismhip_short_shot");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1040,7 +1083,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesSHOT::getTypeStatic()) return new FeaturesSHOT();
     if (type == FeaturesCSHOT::getTypeStatic()) return new FeaturesCSHOT();
     if (type == FeaturesFPFH::getTypeStatic()) return new FeaturesFPFH();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH)");
+    if (type == FeaturesSHORTSHOT::getTypeStatic()) return new FeaturesSHORTSHOT();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH                   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT        features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   Voting, VotingMeanShift, Vote, VotingMaximum voting/voting.h:35, voting_mean_shift.cpp, voting_maximum.h:25-88
@@ -211,6 +211,25 @@ protected:
 ISM3D_FEATURE(FeaturesSHOT, "SHOT", 352, false)
 ISM3D_FEATURE(FeaturesCSHOT, "CSHOT", 1344, true)
 ISM3D_FEATURE(FeaturesFPFH, "FPFH", 33, false)
+// features/features_short_shot.{h,cpp}: the generalised Short SHOT. Not an ISM3D_FEATURE: its length follows the spherical grid.
+class FeaturesSHORTSHOT : public Features {
+public:
+    FeaturesSHORTSHOT();
+    static std::string getTypeStatic() { return "SHORT_SHOT"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return m_feature_dims; }
+    float getMinRadius() const;                      // compute_descriptor :88-103, as the float ismhip_short_shot takes
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+    void iPostInitConfig() override;                 // configureSphericalGrid (:285-366) + what the device refuses
+private:
+    float m_radius;
+    bool m_use_min_radius, m_log_radius;
+    double m_min_radius_relative;
+    int m_feature_dims, m_r_bins, m_e_bins, m_a_bins;
+    std::string m_bin_type;
+};
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------
 class ActivationStrategy : public JSONObject {

@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     distance: str = "Euclidean"      # DistanceType: "Euclidean" (FLANN L2, squared) | "ChiSquared"
@@ -65,9 +65,24 @@ class IsmConfig:
     use_random_codebook: bool = False
     random_codebook_size: int = 0    # fixed-size seeded subset (reference: UseRandomCodebook/RandomCodebookFactor, codebook.cpp:821-829)
     random_codebook_seed: int = 0x5EED
+    short_shot_dims: int = 32        # Features(SHORT_SHOT).ShortShotDims: 8 | 16 | 24 | 32 | 64 | 96 | 128 | 192 | 256 with bin type "auto"
+    short_shot_bin_type: str = "auto"   # ShortShotBinType: "auto" | "manual" (the three bin counts below)
+    short_shot_r_bins: int = 2       # ShortShotRBins / ShortShotEBins / ShortShotABins
+    short_shot_e_bins: int = 2
+    short_shot_a_bins: int = 8
+    use_min_radius: bool = False     # UseMinRadius: neighbours nearer than radius * short_shot_min_radius are skipped
+    short_shot_min_radius: float = 0.0   # ShortShotMinRadius (relative to radius)
+    short_shot_log_radius: bool = False  # ShortShotLogRadius (minimum radius 0.1 * radius unless use_min_radius)
+
+    @property
+    def short_shot_grid(self):
+        """(dims, (r, e, a)) of configureSphericalGrid (features_short_shot.cpp:285-366)"""
+        return capi.short_shot_grid(self.short_shot_dims, self.short_shot_bin_type, (self.short_shot_r_bins, self.short_shot_e_bins, self.short_shot_a_bins))
 
     @property
     def dim(self):
+        if self.feature == "SHORT_SHOT":
+            return self.short_shot_grid[0]
         return {"SHOT": 352, "CSHOT": 1344, "FPFH": 33}[self.feature]
 
     @property
@@ -173,9 +188,17 @@ class Recognizer:
             desc, cnt = capi.shot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
         elif c.feature == "CSHOT":
             desc, cnt = capi.cshot1344(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, b.kp_rgba, lrf, c.radius, want_counts=True)
-        else:
+        elif c.feature == "SHORT_SHOT":
+            min_radius = capi.short_shot_min_radius(c.radius, c.use_min_radius, c.short_shot_min_radius, c.short_shot_log_radius)
+            if c.short_shot_log_radius and not 0.0 < min_radius < c.radius:
+                raise capi.IsmHipError("short_shot_log_radius needs a minimum radius inside (0, radius)")
+            desc, cnt = capi.short_shot(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, bins=c.short_shot_grid[1], min_radius=min_radius,
+                                        log_radius=c.short_shot_log_radius, want_counts=True)
+        elif c.feature == "FPFH":
             # FPFH ignores the frames for description, but keypoints with an invalid frame are still dropped first
             desc, cnt = capi.fpfh33(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
+        else:
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, CSHOT, FPFH, SHORT_SHOT)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
