@@ -68,6 +68,7 @@ extern "C" {
 #define ISMHIP_CSHOT_DIM 1344
 #define ISMHIP_FPFH_DIM    33
 #define ISMHIP_SHORT_SHOT_MAX_DIM 256   /* r_bins * e_bins * a_bins of ismhip_short_shot */
+#define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
 typedef struct ismhip_cloud    ismhip_cloud;
@@ -87,7 +88,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -201,6 +202,31 @@ int  ismhip_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
                        const float* kpx, const float* kpy, const float* kpz, const float* lrf9,
                        float radius, float min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
                        float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesSHORTCSHOT::compute_descriptor (features/features_short_cshot.cpp:103-223) with compute_shape_descriptor (:225-310),
+ * compute_color_descriptor (:312-429), linear_interpolation (:432-443) and correct_bin (:487-507): the Short SHOT followed by its colour
+ * histogram. desc_out[nkp * D], D = r_bins*e_bins*a_bins + rc_bins*ec_bins*ac_bins*hist_size. Per keypoint with a finite frame:
+ *  - neighbours, local coordinates, r, theta, phi, the d2 <= 1e-15f and r < min_radius skips: those of ismhip_short_shot, for both parts;
+ *  - shape part, bins [0, r_bins*e_bins*a_bins): exactly the row ismhip_short_shot accumulates BEFORE its norm;
+ *  - colour part: the raw r / theta / phi values are formed again with the colour grid's bin counts (rc, ec, ac), so a neighbour takes
+ *    a second, independent set of primary bins, shares f and secondary bins; float raw_c = (float)(cd * hist_size) with cd the CSHOT
+ *    colour distance of ismhip_cshot1344 on normalised CIELab, (|dL| + (|da| + |db|) / 2) / 3 clamped to [0, 1], between the neighbour's
+ *    colour and the KEYPOINT's own colour kp_rgba (0x00RRGGBB); bin_c = int(raw_c) clamped from above only, its share and secondary bin
+ *    as for theta (clamps); an axis with one bin has no secondary bin; bin index = Ds + bin_c + hist_size * (bin_r + rc_bins *
+ *    (bin_theta + ec_bins * bin_phi)); up to five deposits, float sums in this order: primary (f_c + f_r) + f_theta + f_phi; phi's
+ *    secondary the same with 1 - f_phi; theta's with 1 - f_theta; r's with 1 - f_r; the secondary COLOUR bin receives
+ *    (1 - f_c) + (1 - f_r) + f_theta + f_phi -- with 1 - f_r, not f_r, exactly as the reference writes it (:424): bug-compatible;
+ *  - the two parts, shape first, are divided by their JOINT L2 norm (double) and cast to float; no contributing neighbour gives 0 / 0:
+ *    the row is NaN AS A WHOLE, as for a non-finite frame or keypoint (count 0).
+ * Deviations from the reference's text: the three of ismhip_short_shot (dot-product order, Radius and min_radius as float, 57.29578), and
+ * the colour distance is taken in float as in PCL's cshot.hpp and ismhip_cshot1344 (the reference's unqualified fabs pins neither).
+ * The caller derives min_radius as for ismhip_short_shot and the colour grid from ShortColorShotDims (configureSphericalColorGrid, :592-646).
+ * Refused, never altered: a bin count or hist_size < 1, min_radius negative or not finite, missing colour arrays (cloud made without
+ * rgba, or kp_rgba NULL), log_radius without 0 < min_radius < radius (ISMHIP_ERR_INVALID); more than ISMHIP_SHORT_SHOT_MAX_DIM shape
+ * bins or a row longer than ISMHIP_SHORT_CSHOT_MAX_DIM (ISMHIP_ERR_UNSUPPORTED). Timer "short_cshot". */
+int  ismhip_short_cshot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                        const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba, const float* lrf9,
+                        float radius, float min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
+                        int rc_bins, int ec_bins, int ac_bins, int hist_size, float* desc_out, uint32_t* neighbour_count_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
@@ -227,7 +253,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

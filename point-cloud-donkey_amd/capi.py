@@ -31,7 +31,7 @@ EXPORTS = [
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
-    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot",
+    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -288,6 +288,35 @@ def short_shot_min_radius(radius, use_min_radius=False, min_radius_relative=0.0,
     if use_min_radius:
         return float(np.float32(float(np.float32(radius)) * float(min_radius_relative)))
     return float(np.float32(float(np.float32(radius)) * float(np.float32(0.1)))) if log_radius else 0.0
+
+
+def short_cshot(ctx, cloud, kp_offsets, kpx, kpy, kpz, kp_rgba, lrf, radius, bins=(2, 2, 8), color_bins=(2, 2, 8), hist_size=15, min_radius=0.0,
+                log_radius=False, want_counts=False):
+    """ismhip_short_cshot on the shape bins (r, e, a), the colour grid (rc, ec, ac) and hist_size colour bins per cell ->
+    [nkp, r * e * a + rc * ec * ac * hist_size]; min_radius is the absolute one (short_shot_min_radius derives it)"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    r, e, a = (int(b) for b in bins)
+    rc, ec, ac = (int(b) for b in color_bins)
+    h = int(hist_size)
+    out = torch.empty((n, r * e * a + rc * ec * ac * h if min(r, e, a, rc, ec, ac, h) > 0 else 0), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_short_cshot(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(kp_rgba), _p(lrf), C.c_float(radius),
+                                       C.c_float(min_radius), C.c_int(1 if log_radius else 0), C.c_int(r), C.c_int(e), C.c_int(a), C.c_int(rc),
+                                       C.c_int(ec), C.c_int(ac), C.c_int(h), _p(out), _p(cnt)), "ismhip_short_cshot")
+    return (out, cnt) if want_counts else out
+
+
+SHORT_CSHOT_COLOR_BINS = {d: SHORT_SHOT_AUTO_BINS[d] for d in (8, 16, 24, 32, 64, 96, 128)}
+
+
+def short_cshot_color_grid(dims=32):
+    """FeaturesSHORTCSHOT::configureSphericalColorGrid (features_short_cshot.cpp:592-646) -> (dims, (rc, ec, ac)): the seven sizes; any
+    other falls back to 32 / (2, 2, 8) as the reference does (with its LOG_ERROR). There is no manual colour grid."""
+    if int(dims) in SHORT_CSHOT_COLOR_BINS:
+        return int(dims), SHORT_CSHOT_COLOR_BINS[int(dims)]
+    return 32, (2, 2, 8)
 
 
 def fpfh33(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False):

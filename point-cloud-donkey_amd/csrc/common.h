@@ -355,6 +355,23 @@ __device__ __forceinline__ float shot_atan2(float y, float x) {
     return y < 0.f ? -r : r;
 }
 
+// normalised CIELab of a packed 0x00RRGGBB colour through the context's two LUTs (PCL's RGB2CIELAB, then L / 100, a / 120, b / 120):
+// the keypoint's reference colour of k_shot<true> (shot.hip) and k_short_cshot (short_cshot.hip)
+__device__ __forceinline__ void rgb2lab_norm(const float* lut_srgb, const float* lut_sxyz, uint32_t c4, float& L, float& A, float& B) {
+    const float fr = lut_srgb[(c4 >> 16) & 0xff], fg = lut_srgb[(c4 >> 8) & 0xff], fb = lut_srgb[c4 & 0xff];
+    const float X = fr * 0.412453f + fg * 0.357580f + fb * 0.180423f;
+    const float Y = fr * 0.212671f + fg * 0.715160f + fb * 0.072169f;
+    const float Z = fr * 0.019334f + fg * 0.119193f + fb * 0.950227f;
+    float vx = X / 0.95047f, vy = Y, vz = Z / 1.08883f;
+    int ix = (int)(vx * 4000), iy = (int)(vy * 4000), iz = (int)(vz * 4000);
+    ix = ix < 0 ? 0 : (ix > 3999 ? 3999 : ix); iy = iy < 0 ? 0 : (iy > 3999 ? 3999 : iy); iz = iz < 0 ? 0 : (iz > 3999 ? 3999 : iz);
+    vx = lut_sxyz[ix]; vy = lut_sxyz[iy]; vz = lut_sxyz[iz];
+    L = 116.0f * vy - 16.0f; if (L > 100) L = 100.0f;
+    A = 500.0f * (vx - vy); if (A > 120) A = 120.0f; else if (A < -120) A = -120.0f;
+    B = 200.0f * (vy - vz); if (B > 120) B = 120.0f; else if (B < -120) B = -120.0f;
+    L /= 100.0f; A /= 120.0f; B /= 120.0f;
+}
+
 // XCD-local block map for the per-object kernels. The hardware deals consecutive workgroup ids round-robin over the 8 XCDs
 // (blocks b and b + 8 share one, MI355X_MICROARCH "Workgroup dispatch"), each with its own 4 MiB L2. With a (blocks, objects) 2-D
 // grid the blocks of ONE object land on all eight XCDs and every L2 pulls every object's cloud from beyond (measured round 1:

@@ -17,12 +17,12 @@
 // bins ride on the primary bin), so every hard decision must be the reference's. The reference's sequence -- steps 4 and 5 in FP64 with
 // libm's acos / atan2, then a cast to float -- costs ~400 FP64 lane-operations per neighbour: at bench size (1786 neighbours per
 // keypoint) that, not the gather, bounds the kernel (measured 5.9 ms per 256 objects against 2.9 ms for k_shot). So every neighbour is
-// first ESTIMATED in float (sshot_estimate: raw values to a few 1e-7 per bin, bound below); only where an estimate comes within eps of
+// first ESTIMATED in float (sshot_polar and sshot_scaled in short_common.h: raw values to a few 1e-7 per bin, bound there); only where an estimate comes within eps of
 // a value at which a decision changes -- an integer n >= 1, or n + 0.5 -- does the wave re-take that neighbour in FP64 exactly as
 // written in the reference (sqrt and division IEEE-exact; acos, atan2, log from the device's libm, a few ulp of double from the
 // host's, ~1e-13 in raw units). Away from the decisions the interpolation shares are continuous, and a raw value off by 1e-6 moves a
 // share by 1e-6: far inside the 1e-4 parity tolerance. A logarithmic radius always takes the FP64 sequence.
-#include "common.h"
+#include "short_common.h"
 
 namespace {
 
@@ -32,8 +32,8 @@ struct ShortShotArgs {
     const uint32_t* kp_off; const float *kx, *ky, *kz;
     const float* lrf; float radius, r2;
     double radius_d, min_radius, ln_rmin, ln_rmax_rmin;
-    float r_scale, t_scale, p_scale, p_off;    // float estimate: raw_r = r * r_scale, raw_theta = theta * t_scale, raw_phi = phi * p_scale + p_off
-    float eps_r, eps_t, eps_p, min_radius_f;   // and how close to a decision it may come before the FP64 sequence decides
+    SshotScale g;                              // the float estimate's scales and eps (short_common.h)
+    float min_radius_f;
     int log_radius, r_bins, e_bins, a_bins;
     float* desc; uint32_t* count;
     int n_obj, nbx;
@@ -41,10 +41,6 @@ struct ShortShotArgs {
 };
 
 #define SSHOT_MAX_DIM   256
-#define SSHOT_FIX_SCALE 268435456.0f              /* 2^28: an increment is in [0, 3], so round(v * 2^28) fits 32 bits */
-#define SSHOT_FIX_INV   3.7252902984619140625e-09 /* 2^-28 */
-#define SSHOT_RAD2DEG   57.29578                  /* pcl::rad2deg(double) of PCL 1.10 multiplies by this truncated constant (external) */
-typedef unsigned long long sshot_bin_t;
 
 struct ShortShotSmem {
     // A short histogram draws many lanes of one deposit onto the same address, and same-address LDS atomics of a wave instruction
@@ -55,61 +51,8 @@ struct ShortShotSmem {
     WaveRows rows[4];
 };
 
-// linear_interpolation (:246-260): decimals from the UNCLAMPED int; share of the primary bin and the side of the secondary one.
-// The reference forms decimals + 0.5 in double and rounds to float: both operands are floats whose sum is exact in double, so the
-// float addition rounds the same exact value once.
-__device__ __forceinline__ void sshot_interp(float raw, float& f, int& step) {
-    const float decimals = raw - (float)(int)raw;
-    if (decimals <= 0.5f) { f = decimals + 0.5f; step = -1; }
-    else { f = (1.0f - decimals) + 0.5f; step = 1; }
-}
-__device__ __forceinline__ void sshot_dep(sshot_bin_t* hist, int dim, int bin, float v) {
-    if ((unsigned)bin < (unsigned)dim) atomicAdd(&hist[bin], (sshot_bin_t)__float2uint_rn(v * SSHOT_FIX_SCALE));   // the guard never fails on finite frames
-}
-
-// true when the float estimate `raw` of a raw bin value is at least eps from every value at which int(raw) or `decimals <= 0.5f`
-// changes: the integers n >= 1 (int() truncates towards zero: nothing changes across 0, and no raw value is below -1) and n + 0.5.
-// A NaN estimate is not clear.
-__device__ __forceinline__ bool sshot_clear(float raw, float eps) {
-    const float fl = floorf(raw), d = raw - fl;
-    const bool below = fl < 1.f || d >= eps;                 // the integer at or below raw
-    const bool above = fl < 0.f || (1.f - d) >= eps;         // the integer above it
-    return below && above && fabsf(d - 0.5f) >= eps;
-}
-
-// Float estimate of the three raw values of a neighbour with local coordinates (x, y, z); returns false when the FP64 sequence has
-// to decide. Error of the estimate, in units of the float epsilon u = 6e-8: r^2 3 roundings and v_sqrt_f32 1 ulp -> r to 3.5 u
-// relative, raw_r = r * r_scale to 6 u * r_bins. theta = atan2(sqrt(x^2 + y^2), z) (well conditioned at the poles, unlike acos(z / r)):
-// 2 u from its first argument, shot_atan2 itself <= 10 u (v_rcp_f32 1 ulp, the polynomial 2e-8, two subtractions from constants near
-// pi), so raw_theta = theta * e_bins * 57.29578 / 180 to 5 u * e_bins; raw_phi likewise to 3 u * a_bins. eps = 2e-6 * (bins + 1) per
-// axis is four times that or more. With (2, 2, 8) bins one neighbour in ~8000 is re-taken in FP64.
-__device__ __forceinline__ bool sshot_estimate(const ShortShotArgs& a, float x, float y, float z, float& raw_r, float& raw_theta, float& raw_phi,
-                                               bool& below_min) {
-    const float rho2 = x * x + y * y;
-    const float r = __builtin_amdgcn_sqrtf(rho2 + z * z);
-    raw_r = r * a.r_scale;
-    raw_theta = shot_atan2(__builtin_amdgcn_sqrtf(rho2), z) * a.t_scale;
-    raw_phi = __builtin_fmaf(shot_atan2(y, x), a.p_scale, a.p_off);          // x == y == 0: NaN, not clear (the reference's atan2 gives 0)
-    below_min = r < a.min_radius_f;
-    const bool min_clear = a.min_radius_f == 0.f || fabsf(r - a.min_radius_f) >= r * 2e-6f;
-    return !a.log_radius && min_clear && sshot_clear(raw_r, a.eps_r) && sshot_clear(raw_theta, a.eps_t) && sshot_clear(raw_phi, a.eps_p);
-}
-
-// The reference's own sequence (:130-137, :166-179) for the neighbours whose estimate is not clear of a decision: the three float raw
-// values and, in w, whether r < min_radius. A CALL, not inlined: the three FP64 libm expansions would otherwise set the register
-// allocation (167 VGPRs: 3 waves per SIMD) of a kernel that runs them for one neighbour in thousands.
-__device__ __noinline__ float4 sshot_exact(float xf, float yf, float zf, double radius_d, double min_radius, double ln_rmin, double ln_rmax_rmin,
-                                           int log_radius, int rb, int eb, int ab) {
-    const double xl = (double)xf, yl = (double)yf, zl = (double)zf;
-    const double r = sqrt((xl * xl + yl * yl) + zl * zl);
-    const double theta = acos(zl / r) * SSHOT_RAD2DEG;
-    const double phi = atan2(yl, xl) * SSHOT_RAD2DEG;
-    const float raw_r = log_radius ? (float)(((double)(rb - 1) * (log(r) - ln_rmin)) / ln_rmax_rmin + 1.0)
-                                   : (float)(((double)rb * r) / radius_d);
-    return make_float4(raw_r, (float)(((double)eb * theta) / 180.0), (float)(((double)ab * (phi + 180.0)) / 360.0), r < min_radius ? 1.f : 0.f);
-}
-
-// Per-neighbour update (:125-140, :159-243). All 64 lanes call it; 'act' marks lanes that hold a neighbour.
+// Per-neighbour update (:125-140, :159-243). All 64 lanes call it; 'act' marks lanes that hold a neighbour. The steps are those of
+// short_common.h: estimate, FP64 re-take where the estimate is not clear of a decision, deposits.
 __device__ __forceinline__ void sshot_neighbour(const ShortShotArgs& a, sshot_bin_t* hist, int dim, bool act,
                                                 float dx, float dy, float dz, float d2,
                                                 const float fx[3], const float fy[3], const float fz[3]) {
@@ -119,34 +62,20 @@ __device__ __forceinline__ void sshot_neighbour(const ShortShotArgs& a, sshot_bi
     const float yf = (dx * fy[0] + dy * fy[1]) + dz * fy[2];
     const float zf = (dx * fz[0] + dy * fz[1]) + dz * fz[2];
     const int rb = a.r_bins, eb = a.e_bins, ab = a.a_bins;
-    float raw_r, raw_theta, raw_phi;
+    float r, theta, phi, raw_r, raw_theta, raw_phi;
     bool below_min;
-    if (!sshot_estimate(a, xf, yf, zf, raw_r, raw_theta, raw_phi, below_min)) {
+    sshot_polar(xf, yf, zf, r, theta, phi);
+    const bool clear = sshot_scaled(a.g, r, theta, phi, raw_r, raw_theta, raw_phi);
+    const bool min_clear = sshot_min_clear(r, a.min_radius_f, below_min);
+    if (a.log_radius || !min_clear || !clear) {
         const float4 e = sshot_exact(xf, yf, zf, a.radius_d, a.min_radius, a.ln_rmin, a.ln_rmax_rmin, a.log_radius, rb, eb, ab);
         raw_r = e.x; raw_theta = e.y; raw_phi = e.z; below_min = e.w != 0.f;
     }
     if (below_min) return;
-    int bin_r = (int)raw_r, bin_theta = (int)raw_theta, bin_phi = (int)raw_phi;
-    bin_r = bin_r >= 0 ? bin_r : 0;
-    bin_r = bin_r < rb ? bin_r : rb - 1;
-    bin_theta = bin_theta < eb ? bin_theta : eb - 1;                              // theta and phi: clamped from above only, as written
-    bin_phi = bin_phi < ab ? bin_phi : ab - 1;
-    float f_r, f_t, f_p; int s_r, s_t, s_p;
-    sshot_interp(raw_r, f_r, s_r);
-    sshot_interp(raw_theta, f_t, s_t);
-    sshot_interp(raw_phi, f_p, s_p);
-    // correct_bin (:263-283): r and theta clamp, phi wraps (one step past either end)
-    int r2b = bin_r + s_r;         r2b = r2b < 0 ? 0 : (r2b >= rb ? rb - 1 : r2b);
-    int t2b = bin_theta + s_t;     t2b = t2b < 0 ? 0 : (t2b >= eb ? eb - 1 : t2b);
-    int p2b = bin_phi + s_p;       p2b = p2b < 0 ? ab - 1 : (p2b >= ab ? 0 : p2b);
-    const int re = rb * eb;
-    sshot_dep(hist, dim, bin_r + bin_theta * rb + bin_phi * re, (f_r + f_t) + f_p);
-    if (ab > 1 && p2b != bin_phi)   sshot_dep(hist, dim, bin_r + bin_theta * rb + p2b * re, (f_r + f_t) + (1.0f - f_p));
-    if (eb > 1 && t2b != bin_theta) sshot_dep(hist, dim, bin_r + t2b * rb + bin_phi * re, (f_r + (1.0f - f_t)) + f_p);
-    if (rb > 1 && r2b != bin_r)     sshot_dep(hist, dim, r2b + bin_theta * rb + bin_phi * re, ((1.0f - f_r) + f_t) + f_p);
+    sshot_shape_deposits(hist, dim, rb, eb, ab, raw_r, raw_theta, raw_phi);
 }
 
-// 114 VGPRs, no scratch, 20 KiB LDS per workgroup: 4 waves per SIMD (the compiler's resource report; held to 96 it spills 16)
+// 108 VGPRs, no scratch, 20 KiB LDS per workgroup: 4 waves per SIMD (the compiler's resource report; held to 96 it spills 16)
 __global__ __launch_bounds__(256, 4) void k_short_shot(ShortShotArgs a) {
     __shared__ ShortShotSmem sm;
     int o, bx;
@@ -255,10 +184,7 @@ int ismhip_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t
     a.ln_rmin = min_radius == 0.f ? 0.0 : log((double)min_radius);
     a.ln_rmax_rmin = min_radius == 0.f ? 0.0 : log((double)radius / (double)min_radius);
     a.log_radius = log_radius ? 1 : 0; a.r_bins = r_bins; a.e_bins = e_bins; a.a_bins = a_bins;
-    a.r_scale = (float)((double)r_bins / (double)radius);
-    a.t_scale = (float)((double)e_bins * SSHOT_RAD2DEG / 180.0);
-    a.p_scale = (float)((double)a_bins * SSHOT_RAD2DEG / 360.0); a.p_off = (float)((double)a_bins * 0.5);
-    a.eps_r = 2e-6f * (float)(r_bins + 1); a.eps_t = 2e-6f * (float)(e_bins + 1); a.eps_p = 2e-6f * (float)(a_bins + 1);
+    a.g = sshot_scale_of(r_bins, e_bins, a_bins, radius);
     a.min_radius_f = min_radius;
     a.desc = desc_out; a.count = neighbour_count_out;
     a.n_obj = ctx->xcd_map ? n_obj : 0; a.nbx = (int)((maxk + 3) / 4);

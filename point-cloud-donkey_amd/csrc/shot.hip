@@ -181,21 +181,6 @@ __device__ __forceinline__ void shot_neighbour(const ShotArgs& a, shot_bin_t* hi
     if (COLOR) shot_dep(hist, vol_c + step_c, w_col + winc);
 }
 
-__device__ __forceinline__ void rgb2lab_norm(const float* lut_srgb, const float* lut_sxyz, uint32_t c4, float& L, float& A, float& B) {
-    const float fr = lut_srgb[(c4 >> 16) & 0xff], fg = lut_srgb[(c4 >> 8) & 0xff], fb = lut_srgb[c4 & 0xff];
-    const float X = fr * 0.412453f + fg * 0.357580f + fb * 0.180423f;
-    const float Y = fr * 0.212671f + fg * 0.715160f + fb * 0.072169f;
-    const float Z = fr * 0.019334f + fg * 0.119193f + fb * 0.950227f;
-    float vx = X / 0.95047f, vy = Y, vz = Z / 1.08883f;
-    int ix = (int)(vx * 4000), iy = (int)(vy * 4000), iz = (int)(vz * 4000);
-    ix = ix < 0 ? 0 : (ix > 3999 ? 3999 : ix); iy = iy < 0 ? 0 : (iy > 3999 ? 3999 : iy); iz = iz < 0 ? 0 : (iz > 3999 ? 3999 : iz);
-    vx = lut_sxyz[ix]; vy = lut_sxyz[iy]; vz = lut_sxyz[iz];
-    L = 116.0f * vy - 16.0f; if (L > 100) L = 100.0f;
-    A = 500.0f * (vx - vy); if (A > 120) A = 120.0f; else if (A < -120) A = -120.0f;
-    B = 200.0f * (vy - vz); if (B > 120) B = 120.0f; else if (B < -120) B = -120.0f;
-    L /= 100.0f; A /= 120.0f; B /= 120.0f;
-}
-
 // 6 workgroups (24 waves) per CU: the LDS budget (24.5 KB per workgroup) allows it, so the register allocation must too (<= 80)
 template <bool COLOR, int VAR>
 __global__ __launch_bounds__(256, COLOR ? 2 : 6) void k_shot(ShotArgs a) {

@@ -381,9 +381,9 @@ void FeaturesSHORTSHOT::iPostInitConfig() {      // configureSphericalGrid, :285
         if (row) { m_r_bins = row[1]; m_e_bins = row[2]; m_a_bins = row[3]; }
         else { LOG_ERROR("Unsupported Short SHOT dimensions for automatic bin configuration: " << m_feature_dims << "! Setting to 32 dimensions with default bins."); fallback = true; }
     } else if (m_bin_type == "manual") {
-        if (m_r_bins < 1 || m_e_bins < 1 || m_a_bins < 1) throw RuntimeException("SHORT_SHOT: fewer than one bin on an axis");
+        if (m_r_bins < 1 || m_e_bins < 1 || m_a_bins < 1) throw RuntimeException(getType() + ": fewer than one bin on an axis");
         if ((long long)m_r_bins * m_e_bins * m_a_bins > ISMHIP_SHORT_SHOT_MAX_DIM)
-            throw RuntimeException("SHORT_SHOT: more than " + std::to_string(ISMHIP_SHORT_SHOT_MAX_DIM) + " bins are not built on the MI355X path");
+            throw RuntimeException(getType() + ": more than " + std::to_string(ISMHIP_SHORT_SHOT_MAX_DIM) + " bins are not built on the MI355X path");
         m_feature_dims = m_r_bins * m_e_bins * m_a_bins;
     } else {
         LOG_ERROR("Unsupported Short SHOT bins configuration type: " << m_bin_type << "! Setting to 32 dimensions with default bins.");
@@ -391,10 +391,31 @@ void FeaturesSHORTSHOT::iPostInitConfig() {      // configureSphericalGrid, :285
     }
     if (fallback) { m_r_bins = 2; m_e_bins = 2; m_a_bins = 8; m_feature_dims = 32; }
     const float mr = getMinRadius();
-    if (!(mr >= 0.0f)) throw RuntimeException("SHORT_SHOT: negative minimum radius");
+    if (!(mr >= 0.0f)) throw RuntimeException(getType() + ": negative minimum radius");
     // the reference divides by log(Radius / min_radius) (0 for min_radius == 0) and converts the NaN to int: refused, never altered
     if (m_log_radius && !(mr > 0.0f && mr < m_radius))
-        throw RuntimeException("SHORT_SHOT: ShortShotLogRadius needs a minimum radius inside (0, Radius); UseMinRadius with ShortShotMinRadius 0 leaves none");
+        throw RuntimeException(getType() + ": ShortShotLogRadius needs a minimum radius inside (0, Radius); UseMinRadius with ShortShotMinRadius 0 leaves none");
+}
+FeaturesSHORTCSHOT::FeaturesSHORTCSHOT() {       // features_short_cshot.cpp:21-33: the nine of FeaturesSHORTSHOT and
+    addParameter(m_color_feature_dims, "ShortColorShotDims", 32);
+    addParameter(m_color_hist_size, "ShortColorShotHistSize", 15);
+}
+void FeaturesSHORTCSHOT::checkInput(const PointCloud& cloud) const {
+    if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("SHORT_CSHOT needs coloured point clouds");
+}
+void FeaturesSHORTCSHOT::iPostInitConfig() {     // configureSphericalGrid, then configureSphericalColorGrid (:592-646): automatic sizes only
+    FeaturesSHORTSHOT::iPostInitConfig();
+    static const int sizes[7][4] = {{8, 1, 1, 8}, {16, 2, 2, 4}, {24, 2, 2, 6}, {32, 2, 2, 8}, {64, 2, 4, 8}, {96, 3, 4, 8}, {128, 4, 4, 8}};
+    const int* row = nullptr;
+    for (const auto& r : sizes) if (r[0] == m_color_feature_dims) row = r;
+    if (row) { m_r_color_bins = row[1]; m_e_color_bins = row[2]; m_a_color_bins = row[3]; }
+    else {
+        LOG_ERROR("Unsupported Short Color SHOT dimensions for bin configuration: " << m_color_feature_dims << "! Setting to 32 dimensions.");
+        m_r_color_bins = 2; m_e_color_bins = 2; m_a_color_bins = 8; m_color_feature_dims = 32;
+    }
+    if (m_color_hist_size < 1) throw RuntimeException("SHORT_CSHOT: ShortColorShotHistSize below 1");
+    if ((long long)m_feature_dims + (long long)m_color_feature_dims * m_color_hist_size > ISMHIP_SHORT_CSHOT_MAX_DIM)
+        throw RuntimeException("SHORT_CSHOT: a descriptor longer than " + std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + " is not built on the MI355X path");
 }
 
 void FeaturesSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_shot.cpp:28-81
@@ -413,6 +434,12 @@ void FeaturesFPFH::iComputeDescriptors(DeviceSession& s, const float*, float* de
 void FeaturesSHORTSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_short_shot.cpp:38-156
     s.check(ismhip_short_shot(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, getMinRadius(),
                               m_log_radius ? 1 : 0, m_r_bins, m_e_bins, m_a_bins, desc_out, counts_out), "ismhip_short_shot");
+}
+void FeaturesSHORTCSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_short_cshot.cpp:62-223
+    if (!s.has_color) throw RuntimeException("SHORT_CSHOT needs coloured point clouds");
+    s.check(ismhip_short_cshot(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), s.krgba.as<uint32_t>(), lrf9, m_radius,
+                               getMinRadius(), m_log_radius ? 1 : 0, m_r_bins, m_e_bins, m_a_bins, m_r_color_bins, m_e_color_bins, m_a_color_bins,
+                               m_color_hist_size, desc_out, counts_out), "ismhip_short_cshot");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1084,7 +1111,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesCSHOT::getTypeStatic()) return new FeaturesCSHOT();
     if (type == FeaturesFPFH::getTypeStatic()) return new FeaturesFPFH();
     if (type == FeaturesSHORTSHOT::getTypeStatic()) return new FeaturesSHORTSHOT();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT)");
+    if (type == FeaturesSHORTCSHOT::getTypeStatic()) return new FeaturesSHORTCSHOT();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
@@ -1534,6 +1562,7 @@ void ImplicitShapeModel::train() {                // :252-500
     g_log_info = m_logging;
     if (m_bounding_box_type != "AABB")
         LOG_WARN("BoundingBoxType \"" << m_bounding_box_type << "\": MVBB is not built, using the axis-aligned box centre for the training votes");
+    for (auto& kv : m_training_clouds) for (auto& c : kv.second) m_feature_descriptor->checkInput(*c);
     DeviceSession& s = session();
     const int met = metric();
     // all training objects, class by class (std::map order), model by model
@@ -1593,6 +1622,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     if (m_single_object_mode_legacy)
         throw RuntimeException("The parameter for \"single object mode\" must be set inside the \"Voting\" section of the config file. You are using the \"Parameters\" section.");
     LapTimer complete{m_processing_times};
+    for (const PointCloud* c : clouds_in) m_feature_descriptor->checkInput(*c);
     DeviceSession& s = session();
     std::vector<const PointCloud*> nonempty;
     std::vector<int> map;

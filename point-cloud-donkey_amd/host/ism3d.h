@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT        features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   Voting, VotingMeanShift, Vote, VotingMaximum voting/voting.h:35, voting_mean_shift.cpp, voting_maximum.h:25-88
@@ -187,6 +187,8 @@ public:
     virtual float getRadius() const = 0;
     virtual int getDescriptorLength() const = 0;
     virtual bool needsColor() const { return false; }
+    // refuses an input cloud the descriptor cannot describe, on the host, before any device work (default: every cloud is taken)
+    virtual void checkInput(const PointCloud&) const {}
 protected:
     // writes descriptors [nkp x D] for every keypoint of the batch (NaN rows for failures, never an error)
     virtual void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const = 0;
@@ -223,12 +225,28 @@ public:
 protected:
     void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
     void iPostInitConfig() override;                 // configureSphericalGrid (:285-366) + what the device refuses
-private:
     float m_radius;
     bool m_use_min_radius, m_log_radius;
     double m_min_radius_relative;
     int m_feature_dims, m_r_bins, m_e_bins, m_a_bins;
     std::string m_bin_type;
+};
+// features/features_short_cshot.{h,cpp}: the Short SHOT followed by a colour histogram on a second spherical grid. The nine shape
+// parameters, configureSphericalGrid and the minimum radius are FeaturesSHORTSHOT's (the reference repeats their text, :23-33, :114-132,
+// :509-590); ShortColorShotDims and ShortColorShotHistSize are added.
+class FeaturesSHORTCSHOT : public FeaturesSHORTSHOT {
+public:
+    FeaturesSHORTCSHOT();
+    static std::string getTypeStatic() { return "SHORT_CSHOT"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getDescriptorLength() const override { return m_feature_dims + m_color_feature_dims * m_color_hist_size; }
+    bool needsColor() const override { return true; }
+    void checkInput(const PointCloud& cloud) const override;   // a cloud without colours throws
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+    void iPostInitConfig() override;                 // + configureSphericalColorGrid (:592-646) + what the device refuses
+private:
+    int m_color_feature_dims, m_color_hist_size, m_r_color_bins, m_e_color_bins, m_a_color_bins;
 };
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------

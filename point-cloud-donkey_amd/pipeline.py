@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     distance: str = "Euclidean"      # DistanceType: "Euclidean" (FLANN L2, squared) | "ChiSquared"
@@ -73,6 +73,8 @@ class IsmConfig:
     use_min_radius: bool = False     # UseMinRadius: neighbours nearer than radius * short_shot_min_radius are skipped
     short_shot_min_radius: float = 0.0   # ShortShotMinRadius (relative to radius)
     short_shot_log_radius: bool = False  # ShortShotLogRadius (minimum radius 0.1 * radius unless use_min_radius)
+    short_color_shot_dims: int = 32      # Features(SHORT_CSHOT).ShortColorShotDims: cells of the colour grid, 8 | 16 | 24 | 32 | 64 | 96 | 128
+    short_color_shot_hist_size: int = 15 # ShortColorShotHistSize: colour-distance bins per cell
 
     @property
     def short_shot_grid(self):
@@ -80,9 +82,16 @@ class IsmConfig:
         return capi.short_shot_grid(self.short_shot_dims, self.short_shot_bin_type, (self.short_shot_r_bins, self.short_shot_e_bins, self.short_shot_a_bins))
 
     @property
+    def short_cshot_color_grid(self):
+        """(dims, (rc, ec, ac)) of configureSphericalColorGrid (features_short_cshot.cpp:592-646)"""
+        return capi.short_cshot_color_grid(self.short_color_shot_dims)
+
+    @property
     def dim(self):
         if self.feature == "SHORT_SHOT":
             return self.short_shot_grid[0]
+        if self.feature == "SHORT_CSHOT":
+            return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
         return {"SHOT": 352, "CSHOT": 1344, "FPFH": 33}[self.feature]
 
     @property
@@ -182,23 +191,28 @@ class Recognizer:
     def compute_features(self, b: DeviceBatch, want_counts=False):
         c, ctx = self.cfg, self.ctx
         cell = min(c.radius, c.lrf_radius if c.feature != "FPFH" else c.radius) * float(os.environ.get("ISMHIP_CELL_SCALE", "0.4"))
-        cloud = capi.Cloud(ctx, b.pt_off, b.x, b.y, b.z, b.nx, b.ny, b.nz, cell, rgba=b.rgba if c.feature == "CSHOT" else None)
+        cloud = capi.Cloud(ctx, b.pt_off, b.x, b.y, b.z, b.nx, b.ny, b.nz, cell, rgba=b.rgba if c.feature in ("CSHOT", "SHORT_CSHOT") else None)
         lrf = capi.shot_lrf(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.lrf_radius)   # Features::operator() always computes LRFs
         if c.feature == "SHOT":
             desc, cnt = capi.shot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
         elif c.feature == "CSHOT":
             desc, cnt = capi.cshot1344(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, b.kp_rgba, lrf, c.radius, want_counts=True)
-        elif c.feature == "SHORT_SHOT":
+        elif c.feature in ("SHORT_SHOT", "SHORT_CSHOT"):
             min_radius = capi.short_shot_min_radius(c.radius, c.use_min_radius, c.short_shot_min_radius, c.short_shot_log_radius)
             if c.short_shot_log_radius and not 0.0 < min_radius < c.radius:
                 raise capi.IsmHipError("short_shot_log_radius needs a minimum radius inside (0, radius)")
-            desc, cnt = capi.short_shot(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, bins=c.short_shot_grid[1], min_radius=min_radius,
-                                        log_radius=c.short_shot_log_radius, want_counts=True)
+            if c.feature == "SHORT_SHOT":
+                desc, cnt = capi.short_shot(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, bins=c.short_shot_grid[1], min_radius=min_radius,
+                                            log_radius=c.short_shot_log_radius, want_counts=True)
+            else:
+                desc, cnt = capi.short_cshot(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, b.kp_rgba, lrf, c.radius, bins=c.short_shot_grid[1],
+                                             color_bins=c.short_cshot_color_grid[1], hist_size=c.short_color_shot_hist_size,
+                                             min_radius=min_radius, log_radius=c.short_shot_log_radius, want_counts=True)
         elif c.feature == "FPFH":
             # FPFH ignores the frames for description, but keypoints with an invalid frame are still dropped first
             desc, cnt = capi.fpfh33(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, CSHOT, FPFH, SHORT_SHOT)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
