@@ -3,12 +3,9 @@
 // interpolation share of a raw bin value, the exact fixed-point deposit, the float estimate of a neighbour's raw values with the test
 // that decides whether it may stand, the FP64 re-take of the reference's own sequence, and the three-axis deposits of the shape part.
 #pragma once
-#include "common.h"
+#include "shot_wave.h"
 
-#define SSHOT_FIX_SCALE 268435456.0f              /* 2^28: an increment is in [0, 4], so round(v * 2^28) fits 32 bits */
-#define SSHOT_FIX_INV   3.7252902984619140625e-09 /* 2^-28 */
 #define SSHOT_RAD2DEG   57.29578                  /* pcl::rad2deg(double) of PCL 1.10 multiplies by this truncated constant (external) */
-typedef unsigned long long sshot_bin_t;
 
 // One spherical grid as the float estimate sees it: raw_r = r * r_scale, raw_theta = theta * t_scale, raw_phi = phi * p_scale + p_off,
 // and how close to a decision each may come before the FP64 sequence decides
@@ -22,6 +19,22 @@ static inline SshotScale sshot_scale_of(int r_bins, int e_bins, int a_bins, floa
     return g;
 }
 
+// The radial parameters of both entry points. A min_radius that is negative or not finite is a bad argument (sshot_min_radius_ok, for
+// shot_check_call); with a logarithmic radius the reference divides by log(Radius / min_radius): 0 for min_radius == 0 (and NaN -> int);
+// refused, never altered.
+static inline bool sshot_min_radius_ok(float min_radius) { return min_radius >= 0.f && std::isfinite(min_radius); }
+template <class Args>
+int sshot_radial_args(const ShotCall& c, float min_radius, int log_radius, Args& a) {
+    if (log_radius && !(min_radius > 0.f && min_radius < c.radius))
+        return ism_set_err(c.ctx, ISMHIP_ERR_INVALID, std::string(c.name) + ": logarithmic radius needs 0 < min_radius < radius");
+    a.radius_d = (double)c.radius; a.min_radius = (double)min_radius;
+    a.ln_rmin = min_radius == 0.f ? 0.0 : log((double)min_radius);
+    a.ln_rmax_rmin = min_radius == 0.f ? 0.0 : log((double)c.radius / (double)min_radius);
+    a.min_radius_f = min_radius;
+    a.log_radius = log_radius ? 1 : 0;
+    return ISMHIP_OK;
+}
+
 #ifdef __HIPCC__
 // linear_interpolation (:246-260): decimals from the UNCLAMPED int; share of the primary bin and the side of the secondary one.
 // The reference forms decimals + 0.5 in double and rounds to float: both operands are floats whose sum is exact in double, so the
@@ -31,8 +44,8 @@ __device__ __forceinline__ void sshot_interp(float raw, float& f, int& step) {
     if (decimals <= 0.5f) { f = decimals + 0.5f; step = -1; }
     else { f = (1.0f - decimals) + 0.5f; step = 1; }
 }
-__device__ __forceinline__ void sshot_dep(sshot_bin_t* hist, int dim, int bin, float v) {
-    if ((unsigned)bin < (unsigned)dim) atomicAdd(&hist[bin], (sshot_bin_t)__float2uint_rn(v * SSHOT_FIX_SCALE));   // the guard never fails on finite frames
+__device__ __forceinline__ void sshot_dep(shot_bin_t* hist, int dim, int bin, float v) {
+    if ((unsigned)bin < (unsigned)dim) atomicAdd(&hist[bin], (shot_bin_t)__float2uint_rn(v * SHOT_FIX_SCALE));   // the guard never fails on finite frames
 }
 
 // true when the float estimate `raw` of a raw bin value is at least eps from every value at which int(raw) or `decimals <= 0.5f`
@@ -101,7 +114,7 @@ __device__ __forceinline__ SshotAxis sshot_axis(float raw, int n) {
 }
 
 // compute_shape_descriptor (:159-243) from the three float raw values on: up to four deposits into hist[0 .. dim)
-__device__ __forceinline__ void sshot_shape_deposits(sshot_bin_t* hist, int dim, int rb, int eb, int ab, float raw_r, float raw_theta, float raw_phi) {
+__device__ __forceinline__ void sshot_shape_deposits(shot_bin_t* hist, int dim, int rb, int eb, int ab, float raw_r, float raw_theta, float raw_phi) {
     const SshotAxis r = sshot_axis<true, false>(raw_r, rb), t = sshot_axis<false, false>(raw_theta, eb), p = sshot_axis<false, true>(raw_phi, ab);
     const int re = rb * eb;
     sshot_dep(hist, dim, r.bin + t.bin * rb + p.bin * re, (r.f + t.f) + p.f);

@@ -9,10 +9,10 @@
 // 16-byte point record of k_short_shot plus the neighbour's 16-byte normalised CIELab record (slab4, gathered by the queued index as
 // k_shot<true> does), the keypoint, its frame and colour, the row.
 //
-// Structure per wave: that of k_short_shot (the XCD block map, ball_for_each<16, true> over sp4, the ballot-compacted 128-entry queue,
-// full waves of neighbours, 2^-28 fixed-point ds_add_u64 deposits); the steps a neighbour takes are those of short_common.h. The
-// geometry is ESTIMATED once in float (r, theta, phi) and scaled per grid; where a raw value of EITHER grid comes within eps of a
-// decision the reference's FP64 sequence is taken for both. The colour side needs no estimate: float subtractions, fabsf, one
+// Structure per wave: that of the SHOT family (shot_wave.h: set-up, ball_for_each<16, true> over sp4, the ballot-compacted queue with
+// the neighbours' indices, full waves of neighbours); the steps a neighbour takes are those of short_common.h, their deposits 2^-28
+// fixed-point ds_add_u64. The geometry is ESTIMATED once in float (r, theta, phi) and scaled per grid; where a raw value of EITHER grid
+// comes within eps of a decision the reference's FP64 sequence is taken for both. The colour side needs no estimate: float subtractions, fabsf, one
 // multiplication by 0.5, two additions, an IEEE division by 3, the clamp and the product with (float)H are each exactly the
 // reference's operation (the product is the reference's double product rounded once: a 24-bit by <= 11-bit product is exact in double).
 // Deviation: the colour distance is taken in float as in PCL's cshot.hpp, from which the reference says it copied the
@@ -51,7 +51,7 @@ struct ShortCshotSmem {
 };
 
 // compute_color_descriptor (:312-429) from the float raw values on: up to five deposits into hist[ds .. dim)
-__device__ __forceinline__ void scshot_color_deposits(sshot_bin_t* hist, int dim, int ds, int rb, int eb, int ab, int hs,
+__device__ __forceinline__ void scshot_color_deposits(shot_bin_t* hist, int dim, int ds, int rb, int eb, int ab, int hs,
                                                       float raw_r, float raw_theta, float raw_phi, float raw_c) {
     const SshotAxis r = sshot_axis<true, false>(raw_r, rb), t = sshot_axis<false, false>(raw_theta, eb), p = sshot_axis<false, true>(raw_phi, ab);
     const SshotAxis c = sshot_axis<false, false>(raw_c, hs);
@@ -65,7 +65,7 @@ __device__ __forceinline__ void scshot_color_deposits(sshot_bin_t* hist, int dim
 }
 
 // Per-neighbour update (:167-202). All 64 lanes call it; 'act' marks lanes that hold a neighbour, gi its sorted point index.
-__device__ __forceinline__ void scshot_neighbour(const ShortCshotArgs& a, sshot_bin_t* hist, int dim, int ds, bool act, uint32_t gi,
+__device__ __forceinline__ void scshot_neighbour(const ShortCshotArgs& a, shot_bin_t* hist, int dim, int ds, bool act, uint32_t gi,
                                                  float dx, float dy, float dz, float d2,
                                                  const float fx[3], const float fy[3], const float fz[3], float LRef, float aRef, float bRef) {
     if (!act) return;
@@ -96,77 +96,32 @@ __device__ __forceinline__ void scshot_neighbour(const ShortCshotArgs& a, sshot_
     scshot_color_deposits(hist, dim, ds, a.rc_bins, a.ec_bins, a.ac_bins, a.hist_size, cr, ct, cp, cd * a.hist_size_f);
 }
 
-// 123 VGPRs (52 scalar registers kept in vector-register lanes), no scratch, 14 KiB static + 32 D bytes dynamic LDS per workgroup: 4 waves
+// 121 VGPRs (scalar registers kept in vector-register lanes), no scratch, 14 KiB static + 32 D bytes dynamic LDS per workgroup: 4 waves
 // per SIMD by registers (the compiler's resource report)
 __global__ __launch_bounds__(256, 4) void k_short_cshot(ShortCshotArgs a) {
     __shared__ ShortCshotSmem sm;
-    extern __shared__ sshot_bin_t scshot_hist[];                        // [4][D]
-    int o, bx;
-    if (!xcd_object_block(a.nbx, a.n_obj, o, bx)) return;
-    const int wv = threadIdx.x >> 6;
-    const int lane = lane_id();
-    if (a.kp_off[o] + bx * 4 + wv >= a.kp_off[o + 1]) return;          // wave-uniform; no block-level barrier below
-    const uint32_t k = ordered_keypoint(a.kp_perm, a.kp_off[o], (uint32_t)(bx * 4 + wv));
+    extern __shared__ shot_bin_t scshot_hist[];                        // [4][D]
     const int Ds = a.r_bins * a.e_bins * a.a_bins;                      // 1 .. 256
     const int D = Ds + a.rc_bins * a.ec_bins * a.ac_bins * a.hist_size; // .. 1344 (both checked by the launcher, which sizes the LDS by D)
-    float* out = a.desc + (size_t)k * D;
-    const float cx = a.kx[k], cy = a.ky[k], cz = a.kz[k];
-    const float* f = a.lrf + (size_t)k * 9;
-    const float fx[3] = {f[0], f[1], f[2]}, fy[3] = {f[3], f[4], f[5]}, fz[3] = {f[6], f[7], f[8]};
-    const GridMeta m = a.meta[o];
-    CellRange cr;
-    const bool ok = isfinite(fx[0]) && isfinite(fy[0]) && isfinite(fz[0]) && isfinite(cx) && isfinite(cy) && isfinite(cz);
-    if (!ok || !ball_cells(m, cx, cy, cz, a.radius, cr)) {
-        for (int i = lane; i < D; i += 64) out[i] = __builtin_nanf("");
-        if (a.count && lane == 0) a.count[k] = 0;
-        return;
-    }
-    sshot_bin_t* hist = scshot_hist + (size_t)wv * D;
+    ShotWave w;
+    if (!shot_wave_setup(a, D, w)) return;
+    const int wv = w.wv, lane = w.lane;
+    float* out = w.row;
+    shot_bin_t* hist = scshot_hist + (size_t)wv * D;
     for (int i = lane; i < D; i += 64) hist[i] = 0ull;
     float LRef, aRef, bRef;
-    rgb2lab_norm(a.lut_srgb, a.lut_sxyz, a.kp_rgba[k], LRef, aRef, bRef);   // the keypoint's own colour is the reference colour (:148-155)
-    const uint32_t* cs = a.cell_start + (size_t)o * ISM_GRID_STRIDE;
-    const uint32_t base = a.pt_off[o];
-    uint32_t qn = 0, qh = 0, total = 0;
-    ball_for_each<16, true>(m, cs, cr, cx, cy, cz, a.radius, lane, sm.rows[wv],
-                  [&](uint32_t i, bool) { return a.sp4[base + i]; },      // invalid lanes carry index 0 (common.h): no branch, no zero fill
-                  [&](const float4& p, uint32_t i, bool v) {
-        bool pass = false; float dx = 0, dy = 0, dz = 0, d2 = 0;
-        if (v) {
-            const float px = p.x, py = p.y, pz = p.z;
-            d2 = sqdist3(px, py, pz, cx, cy, cz);
-            dx = px - cx; dy = py - cy; dz = pz - cz;
-            pass = d2 < a.r2;
-        }
-        const unsigned long long mask = __ballot(pass);
-        if (pass) {
-            const uint32_t pos = (qh + qn + __popcll(mask & ((1ull << lane) - 1ull))) & 127u;      // 128-entry circular queue
-            sm.qd[wv][pos] = make_float4(dx, dy, dz, d2); sm.qi[wv][pos] = base + i;
-        }
-        const uint32_t c = __popcll(mask);
-        qn += c; total += c;
-        if (qn >= 64) {
-            // a full wave of neighbours (LDS traffic of one wave is ordered; no barrier needed)
-            const uint32_t at = (qh + lane) & 127u;
-            const float4 e = sm.qd[wv][at];
-            scshot_neighbour(a, hist, D, Ds, true, sm.qi[wv][at], e.x, e.y, e.z, e.w, fx, fy, fz, LRef, aRef, bRef);
-            qh = (qh + 64) & 127u; qn -= 64;
-        }
-    });
-    if (qn > 0) {
-        const bool act = (uint32_t)lane < qn;
-        const uint32_t at = (qh + lane) & 127u;
-        const float4 e = sm.qd[wv][at];
-        scshot_neighbour(a, hist, D, Ds, act, act ? sm.qi[wv][at] : 0u, e.x, e.y, e.z, e.w, fx, fy, fz, LRef, aRef, bRef);
-    }
-    if (a.count && lane == 0) a.count[k] = total;
+    rgb2lab_norm(a.lut_srgb, a.lut_sxyz, a.kp_rgba[w.k], LRef, aRef, bRef);   // the keypoint's own colour is the reference colour (:148-155)
+    shot_wave_neighbours<16, true>(a, w, sm.qd[wv], sm.qi[wv], sm.rows[wv],
+        [&](bool act, uint32_t gi, float dx, float dy, float dz, float d2) {
+            scshot_neighbour(a, hist, D, Ds, act, gi, dx, dy, dz, d2, w.fx, w.fy, w.fz, LRef, aRef, bRef);
+        });
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");             // the deposits of the other lanes are read below
     // L2 norm of the fused row (:204-220): double sum of squares, sqrt, double division, cast to float. No contributing neighbour:
     // 0 / 0, a NaN row. The bins are integers: reading them twice gives the same values.
     double acc = 0.0;
-    for (int i = lane; i < D; i += 64) { const double v = (double)hist[i] * SSHOT_FIX_INV; acc += v * v; }
+    for (int i = lane; i < D; i += 64) { const double v = (double)hist[i] * SHOT_FIX_INV; acc += v * v; }
     const double norm = sqrt(wave_sum_d(acc));
-    for (int i = lane; i < D; i += 64) out[i] = (float)(((double)hist[i] * SSHOT_FIX_INV) / norm);
+    for (int i = lane; i < D; i += 64) out[i] = (float)(((double)hist[i] * SHOT_FIX_INV) / norm);
 }
 
 }  // namespace
@@ -177,7 +132,6 @@ int ismhip_short_cshot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
                        const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba, const float* lrf9,
                        float radius, float min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
                        int rc_bins, int ec_bins, int ac_bins, int hist_size, float* desc_out, uint32_t* neighbour_count_out) {
-    const char* name = "short_cshot";
     if (!ctx) return ISMHIP_ERR_INVALID;
     if (r_bins < 1 || e_bins < 1 || a_bins < 1 || rc_bins < 1 || ec_bins < 1 || ac_bins < 1)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "short_cshot: fewer than one bin on an axis");
@@ -189,41 +143,22 @@ int ismhip_short_cshot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
     if (dc <= ISMHIP_SHORT_CSHOT_MAX_DIM) dc *= ac_bins;
     if (dc <= ISMHIP_SHORT_CSHOT_MAX_DIM) dc *= hist_size;
     if (ds + dc > ISMHIP_SHORT_CSHOT_MAX_DIM) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "short_cshot: row longer than 1344 bins");
-    if (!cloud || !kp_offsets_h || !kpx || !kpy || !kpz || !lrf9 || !desc_out || !(radius > 0.f) || !(min_radius >= 0.f) || !std::isfinite(min_radius))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "short_cshot: bad argument");
-    if (!cloud->rgba || !kp_rgba) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "short_cshot: colour arrays missing");
-    // the reference divides by log(Radius / min_radius): 0 for min_radius == 0 (and NaN -> int); refused, never altered
-    if (log_radius && !(min_radius > 0.f && min_radius < radius))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "short_cshot: logarithmic radius needs 0 < min_radius < radius");
-    const int n_obj = cloud->n_obj;
-    RaggedOffsets kp;
-    int rc = ism_ragged_offsets(ctx, name, kp_offsets_h, n_obj, SCR_KP_OFF, 0, &kp);
-    if (rc != ISMHIP_OK) return rc;
-    const uint32_t maxk = kp.max_run;
-    if (maxk == 0) return ISMHIP_OK;
+    const ShotCall c{ctx, cloud, kp_offsets_h, kpx, kpy, kpz, kp_rgba, lrf9, radius, desc_out, neighbour_count_out, "short_cshot"};
     ShortCshotArgs a;
-    a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.cell_start = cloud->cell_start; a.sp4 = cloud->sp4; a.slab4 = cloud->slab4;
-    a.kp_off = kp.dev; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.kp_rgba = kp_rgba; a.lrf = lrf9;
-    a.radius = radius; a.r2 = (float)((double)radius * (double)radius);
-    a.radius_d = (double)radius; a.min_radius = (double)min_radius;
-    a.ln_rmin = min_radius == 0.f ? 0.0 : log((double)min_radius);
-    a.ln_rmax_rmin = min_radius == 0.f ? 0.0 : log((double)radius / (double)min_radius);
-    a.log_radius = log_radius ? 1 : 0; a.r_bins = r_bins; a.e_bins = e_bins; a.a_bins = a_bins;
+    uint32_t maxk;
+    int rc = shot_check_call(c, sshot_min_radius_ok(min_radius), true);
+    if (rc == ISMHIP_OK) rc = sshot_radial_args(c, min_radius, log_radius, a);
+    if (rc == ISMHIP_OK) rc = shot_common_args(c, a, maxk);
+    if (rc != ISMHIP_OK || maxk == 0) return rc;
+    a.slab4 = cloud->slab4; a.kp_rgba = kp_rgba;
+    a.r_bins = r_bins; a.e_bins = e_bins; a.a_bins = a_bins;
     a.rc_bins = rc_bins; a.ec_bins = ec_bins; a.ac_bins = ac_bins; a.hist_size = hist_size; a.hist_size_f = (float)hist_size;
     a.same_grid = (r_bins == rc_bins && e_bins == ec_bins && a_bins == ac_bins) ? 1 : 0;
     a.gs = sshot_scale_of(r_bins, e_bins, a_bins, radius);
     a.gc = sshot_scale_of(rc_bins, ec_bins, ac_bins, radius);
-    a.min_radius_f = min_radius;
     a.lut_srgb = ctx->lut_srgb; a.lut_sxyz = ctx->lut_sxyz;
-    a.desc = desc_out; a.count = neighbour_count_out;
-    a.n_obj = ctx->xcd_map ? n_obj : 0; a.nbx = (int)((maxk + 3) / 4);
-    TimerScope ts(ctx, name);
-    a.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, kp.dev, kpx, kpy, kpz, maxk);
-    const dim3 grid(ctx->xcd_map ? xcd_object_grid((unsigned)a.nbx, n_obj) : (unsigned)a.nbx * (unsigned)n_obj);
-    const size_t lds = (size_t)4 * (size_t)(ds + dc) * sizeof(sshot_bin_t);          // <= 43 008 bytes: with the 14 KiB static part inside the 64 KiB default
-    hipLaunchKernelGGL(k_short_cshot, grid, dim3(256), lds, ctx->stream, a);
-    ISM_CHECK_LAUNCH(ctx, name);
-    return ISMHIP_OK;
+    const size_t lds = (size_t)4 * (size_t)(ds + dc) * sizeof(shot_bin_t);          // <= 43 008 bytes: with the 14 KiB static part inside the 64 KiB default
+    return shot_launch(c, a, maxk, k_short_cshot, lds);
 }
 
 }  // extern "C"

@@ -7,12 +7,11 @@
 // Roofline: HBM-bound gather. Algorithmic bytes per keypoint = M_k * 24 + 12 + 36 + 352*4 (SHOT) or
 // M_k * 28 + 12 + 36 + 4 + 1344*4 (CSHOT), M_k = radius neighbours.
 //
-// Structure per wave: stream the candidate x-runs of the query ball (coalesced SoA loads of the cell-sorted
-// cloud); lanes whose point is inside the ball are COMPACTED with a ballot + prefix popcount into a 128-entry
-// LDS queue; whenever 64 are queued, all 64 lanes run the per-neighbour math on a full wave (no divergence on
-// the radius test) and deposit into a per-wave LDS histogram (64-bit fixed point, ds_add_u64 — see ShotSmem). The wave then
-// L2-normalises and writes the row with coalesced stores.
-#include "common.h"
+// Structure per wave: set-up and the neighbour queue are those of the whole family (shot_wave.h: the candidate x-runs of the query
+// ball in 16 interleaved segments, the lanes inside the ball compacted into an LDS queue, the per-neighbour math on full waves);
+// here are the per-neighbour math (shot_neighbour), its deposits into a per-wave LDS histogram (64-bit fixed point, ds_add_u64 --
+// see shot_wave.h) and the L2 normalisation of the row, written with coalesced stores.
+#include "shot_wave.h"
 
 namespace {
 
@@ -32,16 +31,6 @@ struct ShotArgs {
     const uint32_t* kp_perm;   // keypoints in cell order (nullptr: as they come)
 };
 
-// The per-wave LDS histogram is kept in 64-bit FIXED POINT (2^-28 units) and updated with ds_add_u64.
-// Measured on gfx950 (tools/lds_atomic_bench.hip): ds_add_f32 costs ~195 CU-cycles per wave-instruction whatever the
-// addresses, ds_add_u64 17-24, ds_add_u32 15 — with float atomics the kernel spent 64 % of its wave cycles in
-// SQ_WAIT_INST_LDS. Every deposit is a non-negative interpolation weight < 8, so round(v * 2^28) fits 32 bits and a bin
-// (<= 4 * 2^14 neighbours) needs 46 bits. Integer adds are associative: the histogram no longer depends on the order in
-// which neighbours arrive (bitwise reproducible), and its error (<= 2^-29 per deposit) is far below the float
-// accumulation error of the reference itself.
-#define SHOT_FIX_SCALE 268435456.0f          /* 2^28 */
-#define SHOT_FIX_INV   3.7252902984619140625e-09 /* 2^-28 */
-typedef unsigned long long shot_bin_t;
 // The interpolation weights are CONTINUOUS in distance / inclination / azimuth (all hard bin decisions are taken on the
 // signs and squares above them), so these three only need ~1e-7 absolute accuracy -- far inside the 1e-4 parity tolerance --
 // and not libm's last ulp: the IEEE division / sqrt expansions and OCML's acosf / atan2f were a quarter of the kernel's VALU.
@@ -80,7 +69,7 @@ __device__ __forceinline__ void shot_dep(shot_bin_t* hist, int bin, float v) {
 }
 
 // Per-neighbour SHOT update. All 64 lanes call it; 'act' marks lanes that hold a neighbour.
-template <bool COLOR, int VAR>
+template <bool COLOR>
 __device__ __forceinline__ void shot_neighbour(const ShotArgs& a, shot_bin_t* hist, bool act, uint32_t gi,
                                                float dx, float dy, float dz, float d2,
                                                const float fx[3], const float fy[3], const float fz[3],
@@ -168,15 +157,11 @@ __device__ __forceinline__ void shot_neighbour(const ShotArgs& a, shot_bin_t* hi
         winc += 1.f - wa;
         sec_a = (ad > 0.f ? di + 4 : di - 4) & 31;
     }
-    if (VAR & 1) {
-        // unconditional deposits (measured SLOWER, 4.44 vs 4.06 ms: more lanes in every atomic = more same-address serialisation)
-        shot_dep(hist, sec_r * 11 + step, wr_); shot_dep(hist, sec_e * 11 + step, we); shot_dep(hist, sec_a * 11 + step, wa);
-        if (COLOR) { shot_dep(hist, 352 + sec_r * 31 + step_c, wr_); shot_dep(hist, 352 + sec_e * 31 + step_c, we); shot_dep(hist, 352 + sec_a * 31 + step_c, wa); }
-    } else {
+    // deposits only where there is a weight: unconditional ones measured SLOWER (4.44 vs 4.06 ms: more lanes in every atomic = more
+    // same-address serialisation)
     if (wr_ != 0.f) { shot_dep(hist, sec_r * 11 + step, wr_); if (COLOR) shot_dep(hist, 352 + sec_r * 31 + step_c, wr_); }
     if (we != 0.f) { shot_dep(hist, sec_e * 11 + step, we); if (COLOR) shot_dep(hist, 352 + sec_e * 31 + step_c, we); }
     if (wa != 0.f) { shot_dep(hist, sec_a * 11 + step, wa); if (COLOR) shot_dep(hist, 352 + sec_a * 31 + step_c, wa); }
-    }
     shot_dep(hist, vol + step, w_shape + winc);
     if (COLOR) shot_dep(hist, vol_c + step_c, w_col + winc);
 }
@@ -186,66 +171,21 @@ template <bool COLOR, int VAR>
 __global__ __launch_bounds__(256, COLOR ? 2 : 6) void k_shot(ShotArgs a) {
     constexpr int D = COLOR ? 1344 : 352;
     __shared__ ShotSmem<COLOR> sm;
-    int o, bx;
-    if (!xcd_object_block(a.nbx, a.n_obj, o, bx)) return;
-    const int wv = threadIdx.x >> 6;
-    const int lane = lane_id();
-    if (a.kp_off[o] + bx * 4 + wv >= a.kp_off[o + 1]) return;          // wave-uniform; no block-level barrier below
-    const uint32_t k = ordered_keypoint(a.kp_perm, a.kp_off[o], (uint32_t)(bx * 4 + wv));
-    shot_bin_t* hist = sm.hist[wv];
-    float* out = a.desc + (size_t)k * D;
-    const float cx = a.kx[k], cy = a.ky[k], cz = a.kz[k];
-    const float* f = a.lrf + (size_t)k * 9;
-    const float fx[3] = {f[0], f[1], f[2]}, fy[3] = {f[3], f[4], f[5]}, fz[3] = {f[6], f[7], f[8]};
-    const GridMeta m = a.meta[o];
-    CellRange cr;
-    const bool ok = isfinite(fx[0]) && isfinite(fy[0]) && isfinite(fz[0]) && isfinite(cx) && isfinite(cy) && isfinite(cz);
-    if (!ok || !ball_cells(m, cx, cy, cz, a.radius, cr)) {
-        for (int i = lane; i < D; i += 64) out[i] = __builtin_nanf("");
-        if (a.count && lane == 0) a.count[k] = 0;
-        return;
-    }
+    ShotWave w;
+    if (!shot_wave_setup(a, D, w)) return;
+    const int lane = w.lane;
+    shot_bin_t* hist = sm.hist[w.wv];
+    float* out = w.row;
     for (int i = lane; i < D; i += 64) hist[i] = 0ull;
     float LRef = 0.f, aRef = 0.f, bRef = 0.f;
-    if (COLOR) rgb2lab_norm(a.lut_srgb, a.lut_sxyz, a.kp_rgba[k], LRef, aRef, bRef);
+    if (COLOR) rgb2lab_norm(a.lut_srgb, a.lut_sxyz, a.kp_rgba[w.k], LRef, aRef, bRef);
     const float r12 = a.radius * 0.5f, r14 = a.radius * 0.25f, r34 = (a.radius * 3.0f) * 0.25f, inv_r12 = 1.0f / r12;
     const float r12sq_f = a.r12sq_f;
-    const uint32_t* cs = a.cell_start + (size_t)o * ISM_GRID_STRIDE;
-    const uint32_t base = a.pt_off[o];
-    uint32_t qn = 0, qh = 0, total = 0;
     // 16 interleaved segments: measured 4.18 (contiguous) -> 3.27 (8 segments) -> 2.96 ms (16 interleaved) per 256 objects; 32 lose to coalescing
-    ball_for_each<(VAR & 2) ? 1 : 16, true>(m, cs, cr, cx, cy, cz, a.radius, lane, sm.rows[wv],
-                  [&](uint32_t i, bool) { return a.sp4[base + i]; },      // invalid lanes carry index 0 (common.h): no branch, no zero fill
-                  [&](const float4& p, uint32_t i, bool v) {
-        bool pass = false; float dx = 0, dy = 0, dz = 0, d2 = 0;
-        if (v) {
-            const float px = p.x, py = p.y, pz = p.z;
-            d2 = sqdist3(px, py, pz, cx, cy, cz);
-            dx = px - cx; dy = py - cy; dz = pz - cz;
-            pass = d2 < a.r2;
-        }
-        const unsigned long long mask = __ballot(pass);
-        if (pass) {
-            const uint32_t pos = (qh + qn + __popcll(mask & ((1ull << lane) - 1ull))) & 127u;      // 128-entry circular queue
-            sm.qd[wv][pos] = make_float4(dx, dy, dz, d2); sm.qi[wv][pos] = base + i;
-        }
-        const uint32_t c = __popcll(mask);
-        qn += c; total += c;
-        if (qn >= 64) {
-            // a full wave of neighbours (LDS traffic of one wave is ordered; no barrier needed)
-            const uint32_t at = (qh + lane) & 127u;
-            const float4 e = sm.qd[wv][at];
-            shot_neighbour<COLOR, VAR>(a, hist, true, sm.qi[wv][at], e.x, e.y, e.z, e.w, fx, fy, fz, r12, r14, r34, inv_r12, r12sq_f, LRef, aRef, bRef);
-            qh = (qh + 64) & 127u; qn -= 64;
-        }
-    });
-    if (qn > 0) {
-        const bool act = (uint32_t)lane < qn;
-        const uint32_t at = (qh + lane) & 127u;
-        const float4 e = sm.qd[wv][at];
-        shot_neighbour<COLOR, VAR>(a, hist, act, act ? sm.qi[wv][at] : 0u, e.x, e.y, e.z, e.w, fx, fy, fz, r12, r14, r34, inv_r12, r12sq_f, LRef, aRef, bRef);
-    }
-    if (a.count && lane == 0) a.count[k] = total;
+    const uint32_t total = shot_wave_neighbours<(VAR & 2) ? 1 : 16, true>(a, w, sm.qd[w.wv], sm.qi[w.wv], sm.rows[w.wv],
+        [&](bool act, uint32_t gi, float dx, float dy, float dz, float d2) {
+            shot_neighbour<COLOR>(a, hist, act, gi, dx, dy, dz, d2, w.fx, w.fy, w.fz, r12, r14, r34, inv_r12, r12sq_f, LRef, aRef, bRef);
+        });
     if (total < 5) {                                    // computePointSHOT: fewer than 5 neighbours -> NaN descriptor
         for (int i = lane; i < D; i += 64) out[i] = __builtin_nanf("");
         return;
@@ -259,39 +199,23 @@ __global__ __launch_bounds__(256, COLOR ? 2 : 6) void k_shot(ShotArgs a) {
 }
 
 template <bool COLOR>
-int launch_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
-                const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba,
-                const float* lrf9, float radius, float* desc_out, uint32_t* count_out, const char* name) {
-    if (!ctx || !cloud || !kp_offsets_h || !kpx || !kpy || !kpz || !lrf9 || !desc_out || !(radius > 0.f))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": bad argument");
-    if (COLOR && (!cloud->rgba || !kp_rgba)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": colour arrays missing");
-    const int n_obj = cloud->n_obj;
-    RaggedOffsets kp;
-    int rc = ism_ragged_offsets(ctx, name, kp_offsets_h, n_obj, SCR_KP_OFF, 0, &kp);
+int launch_shot(const ShotCall& c) {
+    int rc = shot_check_call(c, true, COLOR);
     if (rc != ISMHIP_OK) return rc;
-    const uint32_t maxk = kp.max_run;
-    if (maxk == 0) return ISMHIP_OK;
     ShotArgs a;
-    a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.cell_start = cloud->cell_start;
-    a.sp4 = cloud->sp4; a.sn4 = cloud->sn4; a.slab4 = cloud->slab4;
-    a.kp_off = kp.dev; a.kx = kpx; a.ky = kpy; a.kz = kpz; a.kp_rgba = kp_rgba; a.lrf = lrf9;
-    a.radius = radius; a.r2 = (float)((double)radius * (double)radius);
+    uint32_t maxk;
+    rc = shot_common_args(c, a, maxk);
+    if (rc != ISMHIP_OK || maxk == 0) return rc;
+    a.sn4 = c.cloud->sn4; a.slab4 = c.cloud->slab4; a.kp_rgba = c.kp_rgba;
     {   // largest float <= (radius/2)^2 taken in double: the shell test (double)d2 > r12sq of the reference, as a float compare
-        const double t = 0.25 * (double)radius * (double)radius;
+        const double t = 0.25 * (double)c.radius * (double)c.radius;
         float tf = (float)t;
         if ((double)tf > t) tf = nextafterf(tf, -INFINITY);
         a.r12sq_f = tf;
     }
-    a.lut_srgb = ctx->lut_srgb; a.lut_sxyz = ctx->lut_sxyz;
-    a.desc = desc_out; a.count = count_out;
-    a.n_obj = ctx->xcd_map ? n_obj : 0; a.nbx = (int)((maxk + 3) / 4);
-    TimerScope ts(ctx, name);
-    a.kp_perm = ism_kp_order(ctx, cloud, kp_offsets_h, kp.dev, kpx, kpy, kpz, maxk);
-    const dim3 grid(ctx->xcd_map ? xcd_object_grid((unsigned)a.nbx, n_obj) : (unsigned)a.nbx * (unsigned)n_obj);
-    if (ctx->shot_var & 2) hipLaunchKernelGGL((k_shot<COLOR, 2>), grid, dim3(256), 0, ctx->stream, a);      // contiguous sweep (A/B runs)
-    else hipLaunchKernelGGL((k_shot<COLOR, 0>), grid, dim3(256), 0, ctx->stream, a);
-    ISM_CHECK_LAUNCH(ctx, name);
-    return ISMHIP_OK;
+    a.lut_srgb = c.ctx->lut_srgb; a.lut_sxyz = c.ctx->lut_sxyz;
+    // ISMHIP_SHOT_VAR=2: the contiguous sweep (A/B runs)
+    return shot_launch(c, a, maxk, (c.ctx->shot_var & 2) ? k_shot<COLOR, 2> : k_shot<COLOR, 0>, 0);
 }
 
 }  // namespace
@@ -301,13 +225,13 @@ extern "C" {
 int ismhip_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                    const float* kpx, const float* kpy, const float* kpz,
                    const float* lrf9, float radius, float* desc_out, uint32_t* neighbour_count_out) {
-    return launch_shot<false>(ctx, cloud, kp_offsets_h, kpx, kpy, kpz, nullptr, lrf9, radius, desc_out, neighbour_count_out, "shot352");
+    return launch_shot<false>({ctx, cloud, kp_offsets_h, kpx, kpy, kpz, nullptr, lrf9, radius, desc_out, neighbour_count_out, "shot352"});
 }
 
 int ismhip_cshot1344(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                      const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba,
                      const float* lrf9, float radius, float* desc_out, uint32_t* neighbour_count_out) {
-    return launch_shot<true>(ctx, cloud, kp_offsets_h, kpx, kpy, kpz, kp_rgba, lrf9, radius, desc_out, neighbour_count_out, "cshot1344");
+    return launch_shot<true>({ctx, cloud, kp_offsets_h, kpx, kpy, kpz, kp_rgba, lrf9, radius, desc_out, neighbour_count_out, "cshot1344"});
 }
 
 }  // extern "C"
