@@ -442,7 +442,8 @@ __global__ __launch_bounds__(256) void k_pca_normals(CloudView cv, float radius,
         const double inv = 1.0 / (double)cnt, mx = sx * inv, my = sy * inv, mz = sz * inv;
         double A[3][3] = {{xx * inv - mx * mx, xy * inv - mx * my, xz * inv - mx * mz}, {xy * inv - mx * my, yy * inv - my * my, yz * inv - my * mz},
                           {xz * inv - mx * mz, yz * inv - my * mz, zz * inv - mz * mz}};
-        double w[3], V[3][3];
+        double w[3], V[3][3], A0[3][3];                                        // eigen_sym3 destroys its input (it leaves the diagonal form):
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) A0[r][c] = A[r][c];   // the sign rule below needs the matrix itself
         eigen_sym3(A, w, V);
         n0 = (float)V[0][0]; n1 = (float)V[1][0]; n2 = (float)V[2][0];
         bool raw_neg = false;
@@ -450,10 +451,10 @@ __global__ __launch_bounds__(256) void k_pca_normals(CloudView cv, float radius,
             // the sign pcl::eigen33 gives its eigenvector (no viewpoint flip: NormalEstimation::computePointNormal): the largest of
             // the three cross products of rows of (A / scale - lambda I)
             double sc = 0;
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) sc = fmax(sc, fabs(A[r][c]));
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) sc = fmax(sc, fabs(A0[r][c]));
             if (!(sc > 0)) sc = 1.0;
             double B[3][3];
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) B[r][c] = A[r][c] / sc - (r == c ? w[0] / sc : 0.0);
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) B[r][c] = A0[r][c] / sc - (r == c ? w[0] / sc : 0.0);
             double c1[3], c2[3], c3[3];
             cross3(B[0], B[1], c1); cross3(B[0], B[2], c2); cross3(B[1], B[2], c3);
             const double l1 = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2], l2 = c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2], l3 = c3[0] * c3[0] + c3[1] * c3[1] + c3[2] * c3[2];
