@@ -163,6 +163,17 @@ int  ismhip_cloud_radii(ismhip_ctx* ctx, const ismhip_cloud* cloud, const float*
 int  ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                      const float* kpx, const float* kpy, const float* kpz,
                      float radius, float* lrf9_out);
+/* ReferenceFrameType "SHOTNA": Features::computeSHOTNAReferenceFrames (features/features.cpp:254-279) ->
+ * pcl::SHOTNALocalReferenceFrameEstimation::getLocalRF (third_party/pcl_shot_na_lrf/shot_na_lrf.hpp:48-178). The SHOT frame with one
+ * change: the sign of z is voted by the NORMALS of all points inside the ball (double(normal) . v3 >= 0; a point that coincides with
+ * the keypoint votes too, a NaN normal never counts as plus); a tied vote goes to the five median neighbours by position, as in SHOT.
+ * The normals are the ones the cloud holds when this is called: those given to ismhip_cloud_create, or the ones a later
+ * ismhip_estimate_normals / ismhip_estimate_normals_pca installed. The x sign counts the valid neighbours only (upstream PCL's loop
+ * bound; the reference's loop also reads rows of vij it never wrote). Arguments, output layout, NaN rows and the timer
+ * key "lrf" are those of ismhip_shot_lrf. */
+int  ismhip_shotna_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                       const float* kpx, const float* kpy, const float* kpz,
+                       float radius, float* lrf9_out);
 
 /* ---- descriptors: FeaturesSHOT::iComputeDescriptors (features/features_shot.cpp:28-81) ------
  * desc_out[nkp*352]; NaN row when LRF non-finite or <5 neighbours. neighbour_count_out may be NULL

@@ -24,7 +24,7 @@ EXPORTS = [
     "ismhip_abi_version", "ismhip_ctx_create", "ismhip_ctx_create_on_stream", "ismhip_ctx_destroy", "ismhip_sync", "ismhip_last_error",
     "ismhip_timers_enable", "ismhip_timers_reset", "ismhip_timer_get",
     "ismhip_cloud_create", "ismhip_cloud_destroy", "ismhip_cloud_centroids", "ismhip_cloud_radii", "ismhip_estimate_normals", "ismhip_estimate_normals_pca",
-    "ismhip_shot_lrf", "ismhip_shot352", "ismhip_cshot1344", "ismhip_fpfh33", "ismhip_center_dist",
+    "ismhip_shot_lrf", "ismhip_shotna_lrf", "ismhip_shot352", "ismhip_cshot1344", "ismhip_fpfh33", "ismhip_center_dist",
     "ismhip_compact_features", "ismhip_compact_descriptor_rows", "ismhip_filter_normals", "ismhip_voxel_keypoints", "ismhip_gather_columns",
     "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims",
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
@@ -231,6 +231,18 @@ def shot_lrf(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius):
     out = torch.empty((int(ko[-1]), 9), dtype=torch.float32, device=kpx.device)
     ctx.check(lib().ismhip_shot_lrf(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), _p(out)), "ismhip_shot_lrf")
     return out
+
+
+def shotna_lrf(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius):
+    """ismhip_shotna_lrf: the SHOT frame with the z sign voted by the normals the cloud holds at this moment (ReferenceFrameType "SHOTNA")"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    out = torch.empty((int(ko[-1]), 9), dtype=torch.float32, device=kpx.device)
+    ctx.check(lib().ismhip_shotna_lrf(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), _p(out)), "ismhip_shotna_lrf")
+    return out
+
+
+LRF_TYPES = {"SHOT": shot_lrf, "SHOTNA": shotna_lrf}      # Features.ReferenceFrameType -> the call ("BOARD" and "FLARE" are not built)
 
 
 def shot352(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, want_counts=False):

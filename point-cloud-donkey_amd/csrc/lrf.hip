@@ -1,4 +1,5 @@
-// lrf.hip — SHOT local reference frames.
+// lrf.hip — SHOT local reference frames, and the SHOTNA frame (ReferenceFrameType "SHOTNA", features.cpp:254-279: the arithmetic below
+// as the reference's shot_na_lrf.hpp states it, the z sign voted by the normals; k_lrf_sign_na).
 // Reference seam: Features::computeSHOTReferenceFrames (features/features.cpp:238-252) ->
 // pcl::SHOTLocalReferenceFrameEstimationOMP; arithmetic as third_party/pcl_shot_na_lrf/shot_na_lrf.hpp:48-178
 // with upstream's z-sign rule (vij . v3 >= 0), SURVEY Appendix A.1.
@@ -127,10 +128,16 @@ __global__ __launch_bounds__(256) void k_lrf_eig(uint32_t nkp, const double* __r
     a[3] = V[0][0]; a[4] = V[1][0]; a[5] = V[2][0];
 }
 
-__global__ __launch_bounds__(256, 4) void k_lrf_sign(CloudView cv, const uint32_t* __restrict__ kp_off,
-                                                  const float* __restrict__ kx, const float* __restrict__ ky, const float* __restrict__ kz,
-                                                  float radius, float r2, const double* __restrict__ cov, const double* __restrict__ axes,
-                                                  float* __restrict__ lrf_out, uint32_t* __restrict__ tie_count, TieRec* __restrict__ tie_rec) {
+// NA = false: the SHOT frame, both signs voted by the neighbours' positions. NA = true: the SHOTNA frame (shot_na_lrf.hpp:120-138), the
+// z sign voted by the NORMALS of every point inside the ball -- a point that coincides with the keypoint included: the reference's loop
+// runs over n_indices -- while the x sign stays with the positions of the valid neighbours. The sweep then gathers the cell-sorted
+// normal sn4 of the same slot beside the position (32 instead of 16 bytes per candidate).
+struct PN { float4 p, n; };
+template <bool NA>
+__device__ __forceinline__ void lrf_sign(const CloudView& cv, const float4* __restrict__ sn4, const uint32_t* __restrict__ kp_off,
+                                         const float* __restrict__ kx, const float* __restrict__ ky, const float* __restrict__ kz,
+                                         float radius, float r2, const double* __restrict__ cov, const double* __restrict__ axes,
+                                         float* __restrict__ lrf_out, uint32_t* __restrict__ tie_count, TieRec* __restrict__ tie_rec) {
     int o, bx;
     if (!xcd_object_block(cv.nbx, cv.n_obj, o, bx)) return;
     const uint32_t slot = bx * 4 + (threadIdx.x >> 6);
@@ -149,18 +156,35 @@ __global__ __launch_bounds__(256, 4) void k_lrf_sign(CloudView cv, const uint32_
     ball_cells(m, cx, cy, cz, radius, cr);
     int plusT = 0, plusN = 0;
     __shared__ WaveRows s_rows[4];
-    ball_for_each(m, cs, cr, cx, cy, cz, radius, lane, s_rows[threadIdx.x >> 6],
-                  [&](uint32_t t, bool) { return cv.sp4[base + t]; },
-                  [&](const float4& p, uint32_t, bool v) {
-        if (!v) return;
-        const float px = p.x, py = p.y, pz = p.z;
-        const float d2 = sqdist3(px, py, pz, cx, cy, cz);
-        if (d2 < r2 && !(px == cx && py == cy && pz == cz)) {
-            const double vx = (double)(px - cx), vy = (double)(py - cy), vz = (double)(pz - cz);
-            if (vx * v1[0] + vy * v1[1] + vz * v1[2] >= 0) plusT++;
-            if (vx * v3[0] + vy * v3[1] + vz * v3[2] >= 0) plusN++;
-        }
-    });
+    if constexpr (NA) {
+        ball_for_each(m, cs, cr, cx, cy, cz, radius, lane, s_rows[threadIdx.x >> 6],
+                      [&](uint32_t t, bool) { PN r; r.p = cv.sp4[base + t]; r.n = sn4[base + t]; return r; },
+                      [&](const PN& pn, uint32_t, bool v) {
+            if (!v) return;
+            const float px = pn.p.x, py = pn.p.y, pz = pn.p.z;
+            const float d2 = sqdist3(px, py, pz, cx, cy, cz);
+            if (d2 < r2) {
+                if ((double)pn.n.x * v3[0] + (double)pn.n.y * v3[1] + (double)pn.n.z * v3[2] >= 0) plusN++;   // a NaN normal never counts
+                if (!(px == cx && py == cy && pz == cz)) {
+                    const double vx = (double)(px - cx), vy = (double)(py - cy), vz = (double)(pz - cz);
+                    if (vx * v1[0] + vy * v1[1] + vz * v1[2] >= 0) plusT++;
+                }
+            }
+        });
+    } else {
+        ball_for_each(m, cs, cr, cx, cy, cz, radius, lane, s_rows[threadIdx.x >> 6],
+                      [&](uint32_t t, bool) { return cv.sp4[base + t]; },
+                      [&](const float4& p, uint32_t, bool v) {
+            if (!v) return;
+            const float px = p.x, py = p.y, pz = p.z;
+            const float d2 = sqdist3(px, py, pz, cx, cy, cz);
+            if (d2 < r2 && !(px == cx && py == cy && pz == cz)) {
+                const double vx = (double)(px - cx), vy = (double)(py - cy), vz = (double)(pz - cz);
+                if (vx * v1[0] + vy * v1[1] + vz * v1[2] >= 0) plusT++;
+                if (vx * v3[0] + vy * v3[1] + vz * v3[2] >= 0) plusN++;
+            }
+        });
+    }
     plusT = 2 * wave_sum_i(plusT) - valid;
     plusN = 2 * wave_sum_i(plusN) - valid;
     if (plusT < 0) { v1[0] = -v1[0]; v1[1] = -v1[1]; v1[2] = -v1[2]; }
@@ -176,6 +200,18 @@ __global__ __launch_bounds__(256, 4) void k_lrf_sign(CloudView cv, const uint32_
         return;   // finished by k_lrf_tie
     }
     if (lane == 0) write_lrf(lrf_out + (size_t)k * 9, v1, v3);
+}
+__global__ __launch_bounds__(256, 4) void k_lrf_sign(CloudView cv, const uint32_t* __restrict__ kp_off,
+                                                  const float* __restrict__ kx, const float* __restrict__ ky, const float* __restrict__ kz,
+                                                  float radius, float r2, const double* __restrict__ cov, const double* __restrict__ axes,
+                                                  float* __restrict__ lrf_out, uint32_t* __restrict__ tie_count, TieRec* __restrict__ tie_rec) {
+    lrf_sign<false>(cv, nullptr, kp_off, kx, ky, kz, radius, r2, cov, axes, lrf_out, tie_count, tie_rec);
+}
+__global__ __launch_bounds__(256, 4) void k_lrf_sign_na(CloudView cv, const float4* __restrict__ sn4, const uint32_t* __restrict__ kp_off,
+                                                     const float* __restrict__ kx, const float* __restrict__ ky, const float* __restrict__ kz,
+                                                     float radius, float r2, const double* __restrict__ cov, const double* __restrict__ axes,
+                                                     float* __restrict__ lrf_out, uint32_t* __restrict__ tie_count, TieRec* __restrict__ tie_rec) {
+    lrf_sign<true>(cv, sn4, kp_off, kx, ky, kz, radius, r2, cov, axes, lrf_out, tie_count, tie_rec);
 }
 
 #define TIE_LDS_KEYS 8192     // keys of one neighbourhood in LDS (64 KB, one wave per workgroup); larger ones go to a global scratch row
@@ -299,13 +335,14 @@ __global__ __launch_bounds__(64) void k_lrf_tie(CloudView cv, const float* __res
 
 }  // namespace
 
-extern "C" int ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
-                               const float* kpx, const float* kpy, const float* kpz, float radius, float* lrf9_out) {
+// the launcher of both frames: normal_votes = false is ismhip_shot_lrf, true ismhip_shotna_lrf (k_lrf_sign_na in place of k_lrf_sign)
+static int lrf_frames(ismhip_ctx* ctx, const ismhip_cloud* cloud, const char* what, bool normal_votes, const uint32_t* kp_offsets_h,
+                      const float* kpx, const float* kpy, const float* kpz, float radius, float* lrf9_out) {
     if (!ctx || !cloud || !kp_offsets_h || !kpx || !kpy || !kpz || !lrf9_out || !(radius > 0.f))
-        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "shot_lrf: bad argument");
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, normal_votes ? "shotna_lrf: bad argument" : "shot_lrf: bad argument");
     const int n_obj = cloud->n_obj;
     RaggedOffsets kp;
-    int rc = ism_ragged_offsets(ctx, "shot_lrf", kp_offsets_h, n_obj, SCR_KP_OFF, RAGGED_START0, &kp);
+    int rc = ism_ragged_offsets(ctx, what, kp_offsets_h, n_obj, SCR_KP_OFF, RAGGED_START0, &kp);
     if (rc != ISMHIP_OK) return rc;
     const uint32_t maxk = kp.max_run, nkp = kp.total;
     if (maxk == 0) return ISMHIP_OK;
@@ -329,11 +366,24 @@ extern "C" int ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const
     ISM_CHECK_LAUNCH(ctx, "k_lrf_cov");
     hipLaunchKernelGGL(k_lrf_eig, dim3((nkp + 255) / 256), dim3(256), 0, ctx->stream, nkp, cov, axes, lrf9_out);
     ISM_CHECK_LAUNCH(ctx, "k_lrf_eig");
-    hipLaunchKernelGGL(k_lrf_sign, grid, dim3(256), 0, ctx->stream, cv, ko, kpx, kpy, kpz, radius, r2, cov, axes, lrf9_out, tie_count, tie_rec);
-    ISM_CHECK_LAUNCH(ctx, "k_lrf_sign");
+    if (normal_votes) {
+        hipLaunchKernelGGL(k_lrf_sign_na, grid, dim3(256), 0, ctx->stream, cv, cloud->sn4, ko, kpx, kpy, kpz, radius, r2, cov, axes, lrf9_out, tie_count, tie_rec);
+        ISM_CHECK_LAUNCH(ctx, "k_lrf_sign_na");
+    } else {
+        hipLaunchKernelGGL(k_lrf_sign, grid, dim3(256), 0, ctx->stream, cv, ko, kpx, kpy, kpz, radius, r2, cov, axes, lrf9_out, tie_count, tie_rec);
+        ISM_CHECK_LAUNCH(ctx, "k_lrf_sign");
+    }
     hipLaunchKernelGGL(k_lrf_tie, dim3(tie_blocks), dim3(64), 0, ctx->stream, cv, kpx, kpy, kpz, radius, r2, lrf9_out, tie_count, tie_rec, keys, key_cap);
     ISM_CHECK_LAUNCH(ctx, "k_lrf_tie");
     return ISMHIP_OK;
+}
+extern "C" int ismhip_shot_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                               const float* kpx, const float* kpy, const float* kpz, float radius, float* lrf9_out) {
+    return lrf_frames(ctx, cloud, "shot_lrf", false, kp_offsets_h, kpx, kpy, kpz, radius, lrf9_out);
+}
+extern "C" int ismhip_shotna_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                                 const float* kpx, const float* kpy, const float* kpz, float radius, float* lrf9_out) {
+    return lrf_frames(ctx, cloud, "shotna_lrf", true, kp_offsets_h, kpx, kpy, kpz, radius, lrf9_out);
 }
 
 

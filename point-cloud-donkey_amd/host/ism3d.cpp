@@ -313,12 +313,16 @@ Features::Features() : m_numThreads(0) {
     addParameter(m_referenceFrameType, "ReferenceFrameType", std::string("SHOT"));
 }
 
+void Features::checkReferenceFrameType() const {   // features.cpp:153-179
+    if (m_referenceFrameType == "SHOT" || m_referenceFrameType == "SHOTNA") return;
+    if (m_referenceFrameType == "BOARD" || m_referenceFrameType == "FLARE")
+        throw RuntimeException("reference frame type \"" + m_referenceFrameType + "\" is not built on the MI355X path (built: \"SHOT\", \"SHOTNA\")");
+    throw BadParamExceptionType<std::string>("invalid reference frame type", m_referenceFrameType);   // features.cpp:178
+}
+
 std::shared_ptr<DeviceFeatures> Features::operator()(DeviceSession& s) const {   // features.cpp:40-116
-    if (m_referenceFrameType != "SHOT") {
-        if (m_referenceFrameType == "BOARD" || m_referenceFrameType == "FLARE" || m_referenceFrameType == "SHOTNA")
-            throw RuntimeException("reference frame type \"" + m_referenceFrameType + "\" is not built on the MI355X path (only \"SHOT\")");
-        throw BadParamExceptionType<std::string>("invalid reference frame type", m_referenceFrameType);   // features.cpp:178
-    }
+    checkReferenceFrameType();
+    const bool shotna = m_referenceFrameType == "SHOTNA";   // features.cpp:153-179: the z sign voted by the cloud's normals
     const uint32_t nkp = s.kp_off.back();
     const int D = getDescriptorLength();
     auto f = std::make_shared<DeviceFeatures>();
@@ -327,8 +331,9 @@ std::shared_ptr<DeviceFeatures> Features::operator()(DeviceSession& s) const {  
     if (nkp == 0) return f;
     LOG_INFO("computing reference frames");
     s.raw_lrf.reserve((size_t)nkp * 9 * 4); s.raw_desc.reserve((size_t)nkp * D * 4); s.raw_cnt.reserve((size_t)nkp * 4);
-    s.check(ismhip_shot_lrf(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_referenceFrameRadius,
-                            s.raw_lrf.as<float>()), "ismhip_shot_lrf");
+    s.check((shotna ? ismhip_shotna_lrf : ismhip_shot_lrf)(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(),
+                                                           m_referenceFrameRadius, s.raw_lrf.as<float>()),
+            shotna ? "ismhip_shotna_lrf" : "ismhip_shot_lrf");
     LOG_INFO("computing descriptors at keypoint positions");
     iComputeDescriptors(s, s.raw_lrf.as<float>(), s.raw_desc.as<float>(), s.raw_cnt.as<uint32_t>());
     // invalid frames and NaN descriptors are dropped, order preserved (features.cpp:66-76, implicit_shape_model.cpp:1276-1308)
@@ -373,6 +378,7 @@ float FeaturesSHORTSHOT::getMinRadius() const {  // :88-103 (the reference's def
     return m_log_radius ? (float)((double)m_radius * (double)0.1f) : 0.0f;
 }
 void FeaturesSHORTSHOT::iPostInitConfig() {      // configureSphericalGrid, :285-366: run once the config has been read
+    Features::iPostInitConfig();
     static const int sizes[9][4] = {{8, 1, 1, 8}, {16, 2, 2, 4}, {24, 2, 2, 6}, {32, 2, 2, 8}, {64, 2, 4, 8}, {96, 3, 4, 8}, {128, 4, 4, 8}, {192, 6, 4, 8}, {256, 8, 4, 8}};
     bool fallback = false;
     if (m_bin_type == "auto") {

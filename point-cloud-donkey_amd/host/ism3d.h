@@ -190,6 +190,9 @@ public:
     // refuses an input cloud the descriptor cannot describe, on the host, before any device work (default: every cloud is taken)
     virtual void checkInput(const PointCloud&) const {}
 protected:
+    void iPostInitConfig() override { checkReferenceFrameType(); }   // what the device does not compute is refused when the config is read
+    // ReferenceFrameType (features.cpp:153-179): "SHOT" and "SHOTNA" are built, "BOARD" and "FLARE" refused, anything else a bad parameter
+    void checkReferenceFrameType() const;
     // writes descriptors [nkp x D] for every keypoint of the batch (NaN rows for failures, never an error)
     virtual void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const = 0;
     float m_referenceFrameRadius;

@@ -20,6 +20,7 @@ class IsmConfig:
     feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
+    lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
     distance: str = "Euclidean"      # DistanceType: "Euclidean" (FLANN L2, squared) | "ChiSquared"
     activation: str = "KNN"          # ActivationStrategy.Type: "KNN" | "KNNRule"
     k: int = 1                       # ActivationStrategy.K
@@ -75,6 +76,10 @@ class IsmConfig:
     short_shot_log_radius: bool = False  # ShortShotLogRadius (minimum radius 0.1 * radius unless use_min_radius)
     short_color_shot_dims: int = 32      # Features(SHORT_CSHOT).ShortColorShotDims: cells of the colour grid, 8 | 16 | 24 | 32 | 64 | 96 | 128
     short_color_shot_hist_size: int = 15 # ShortColorShotHistSize: colour-distance bins per cell
+
+    def __post_init__(self):
+        if self.lrf_type not in capi.LRF_TYPES:
+            raise ValueError(f"lrf_type {self.lrf_type!r} is not built ({', '.join(capi.LRF_TYPES)})")
 
     @property
     def short_shot_grid(self):
@@ -192,7 +197,7 @@ class Recognizer:
         c, ctx = self.cfg, self.ctx
         cell = min(c.radius, c.lrf_radius if c.feature != "FPFH" else c.radius) * float(os.environ.get("ISMHIP_CELL_SCALE", "0.4"))
         cloud = capi.Cloud(ctx, b.pt_off, b.x, b.y, b.z, b.nx, b.ny, b.nz, cell, rgba=b.rgba if c.feature in ("CSHOT", "SHORT_CSHOT") else None)
-        lrf = capi.shot_lrf(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.lrf_radius)   # Features::operator() always computes LRFs
+        lrf = capi.LRF_TYPES[c.lrf_type](ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.lrf_radius)   # Features::operator() always computes LRFs
         if c.feature == "SHOT":
             desc, cnt = capi.shot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
         elif c.feature == "CSHOT":

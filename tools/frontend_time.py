@@ -2,7 +2,8 @@
 ismhip_shot352 on the batch of bench config 1 (908 objects x 16384 points, 1024 keypoints each in random order, cell 0.12, radii 0.3),
 once per setting of the A/B switches of the grid build and of the keypoint order. Every setting gets a context of its own (the switches are
 read when a context is created); the settings alternate over the repetitions. Prints one JSON line.
-usage: python tools/frontend_time.py [--objects 908 --points 16384 --keypoints 1024 --cell 0.12 --radius 0.3 --reps 5]"""
+--lrf-type SHOTNA times ismhip_shotna_lrf (the z sign voted by the normals) under the same "lrf" timer key.
+usage: python tools/frontend_time.py [--objects 908 --points 16384 --keypoints 1024 --cell 0.12 --radius 0.3 --reps 5 --lrf-type SHOT]"""
 import argparse
 import json
 import os
@@ -20,6 +21,7 @@ ap.add_argument("--keypoints", type=int, default=1024)
 ap.add_argument("--cell", type=float, default=0.12)
 ap.add_argument("--radius", type=float, default=0.3)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--lrf-type", choices=["SHOT", "SHOTNA"], default="SHOT")
 args = ap.parse_args()
 import torch
 pkg = ge.load_package()
@@ -53,7 +55,7 @@ for k in SWITCHES:
 
 def once(ctx):
     cloud = capi.Cloud(ctx, po, *pts, args.cell)
-    lrf = capi.shot_lrf(ctx, cloud, ko, *kps, args.radius)
+    lrf = capi.LRF_TYPES[args.lrf_type](ctx, cloud, ko, *kps, args.radius)
     desc = capi.shot352(ctx, cloud, ko, *kps, lrf, args.radius)
     ctx.sync()
     cloud.close()
@@ -73,5 +75,5 @@ for rep in range(args.reps):
         ctx.timers_reset()
         once(ctx)
         runs[name].append({t: round(ctx.timer(t)[0], 4) for t in ("grid", "lrf", "shot352")})
-print(json.dumps({"objects": args.objects, "points": int(po[-1]), "keypoints": int(ko[-1]), "cell": args.cell, "radius": args.radius,
+print(json.dumps({"objects": args.objects, "points": int(po[-1]), "keypoints": int(ko[-1]), "cell": args.cell, "radius": args.radius, "lrf_type": args.lrf_type,
                   "ms": runs, "outputs_identical": True}))
