@@ -148,6 +148,10 @@ __device__ __forceinline__ bool pair_bins_fast(float px, float py, float pz, flo
     const float f1 = fast_atan2(ay_, ax_);
     const float t1 = 11.0f * ((f1 + 3.14159265358979323846f) * 0.15915494309189535f);
     const float t2 = 11.0f * ((f2 + 1.0f) * 0.5f), t3 = 11.0f * ((f3 + 1.0f) * 0.5f);
+    // the seam of f1: for x < 0 the sign of y alone puts the pair into bin 10 (+pi) or bin 0 (-pi), so t1 = 0 and t1 = 11 are a bin
+    // edge like 1..10 although both are "clamped away". Inside the guard the fast y may carry the other sign than the exact one
+    // (rounding noise when n_t lies in the plane of u and v), and fast_atan2 reads y = -0.0f as +pi where atan2f says -pi.
+    if (ax_ < 0.f && !(t1 > FPFH_GUARD && t1 < 11.0f - FPFH_GUARD)) return false;
     if (!(fpfh_bin_sure(t1) && fpfh_bin_sure(t2) && fpfh_bin_sure(t3))) return false;
     h1 = clamp_bin((int)floorf(t1)); h2 = clamp_bin((int)floorf(t2)); h3 = clamp_bin((int)floorf(t3));
     return true;
