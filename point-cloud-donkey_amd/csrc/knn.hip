@@ -11,6 +11,9 @@
 //     matrix is never materialised. Every kernel keeps, per lane slot, the T best candidates AND the value of the best candidate
 //     it dropped (the slot's bound).
 //       knn_ring16.hip   k_knn_l2_ring16  f16 MFMA, 256x256 tile, LDS-DMA ring         default for launches >= 4096 queries x 4096 codewords
+//                                         (its tile epilogue: a scan that leaves the maximum of every 4-row group, one branch per tile, a walk of
+//                                         the flagged columns that starts from those maxima, thresholds swapped and published only where a
+//                                         wave inserted: knn_ring16.hip, DESIGN.md §4.1 "Hit path")
 //       knn_mfma16.hip   k_knn_l2_mfma16  f16 (or bf16x3) MFMA, register-staged tiles  smaller launches; ISMHIP_KNN_MODE=bf16x3 for A/B runs;
 //                                                                                      its EMIT variant lists rows below a per-query score
 //       knn_cand.hip     k_knn_l2_mfma    f32 MFMA (exact fma chain)                   ISMHIP_KNN_MODE=f32: the independent route used by the tests

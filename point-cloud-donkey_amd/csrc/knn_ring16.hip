@@ -34,9 +34,38 @@ namespace {
 // Shared thresholds: a value that is not better than the (T+1)-th best of ANY lane slot of its query column can be dropped by all
 // of them: thresholds only rise, every dropped value is <= the threshold its lane used at the time <= that lane's final
 // threshold, which is what the slot reports as its bound. Sharing cuts the insertions ~4x. Slots of the same wave: register
-// swaps once per tile; partner wave: a 4-byte slot in LDS (a stale value is only a lower, i.e. more conservative, threshold).
+// swaps in a column the wave has just inserted into (nothing else changes a wave's own thresholds); partner wave: a 4-byte slot in
+// LDS, written there and read at the top of every epilogue (a stale value is only a lower, i.e. more conservative, threshold).
 __device__ __forceinline__ void lds_dma16(const void* g, void* l) {
     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 16, 0, 0);
+}
+// the largest of a value over the four row groups of a wave (lanes fr, fr + 16, fr + 32, fr + 48) by two register swaps
+// (v_permlane32_swap / v_permlane16_swap: no LDS round trip)
+__device__ __forceinline__ float max_of_row_groups(float x) {
+    const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    float sh;
+    asm("v_max_f32 %0, %1, %2" : "=v"(sh) : "v"(__uint_as_float(h[0])), "v"(__uint_as_float(h[1])));
+    const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(sh), __float_as_uint(sh), false, false);
+    asm("v_max_f32 %0, %1, %2" : "=v"(sh) : "v"(__uint_as_float(q[0])), "v"(__uint_as_float(q[1])));
+    return sh;
+}
+// TopT::push_flat for the epilogue's walk, spelled in v_cmp / v_cndmask: from the nested selects the compiler builds exec-masked
+// branches around moves (measured in the ISA of the T = 2 instance: 22 VALU, two s_and_saveexec and a branch per insertion); this is
+// N compares and 4 N - 2 selects for a list of N, none of them under a branch. Same comparisons, same results; x = +inf leaves the list alone.
+__device__ __forceinline__ float sel_f(unsigned long long m, float t, float f) { float r; asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m)); return r; }
+__device__ __forceinline__ int sel_i(unsigned long long m, int t, int f) { int r; asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m)); return r; }
+template <int N>
+__device__ __forceinline__ void push_cnd(TopT<N>& tp, float x, int idx) {
+    unsigned long long c[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(c[t]) : "v"(x), "v"(tp.v[t]));
+#pragma unroll
+    for (int t = N - 1; t > 0; --t) {
+        tp.v[t] = sel_f(c[t - 1], tp.v[t - 1], sel_f(c[t], x, tp.v[t]));
+        tp.i[t] = sel_i(c[t - 1], tp.i[t - 1], sel_i(c[t], idx, tp.i[t]));
+    }
+    tp.v[0] = sel_f(c[0], x, tp.v[0]);
+    tp.i[0] = sel_i(c[0], idx, tp.i[0]);
 }
 // WR = 2: the 256 x 256 tile, 8 waves (2 x 4), one workgroup per CU, four ring stages (three slices in flight).
 // WR = 1 (stage-2 chunks of 4 096 - 32 767 queries, ISMHIP_KNN_HALF=1): a 128 x 256 tile, 4 waves, 76 KB of LDS: TWO independent
@@ -67,6 +96,9 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
     using L = Ring16Lds<WR, QP>;
     constexpr int WC = 4, MT = 8, NT = 4, KB = RG_KB, BM = WR * 128, BN = RG_BN;
     constexpr int STAGES = L::STAGES, STAGE_HALVES = L::STAGE_HALVES, CNS = 256;
+    // epilogue: the scan keeps its 32 group maxima for the walk and insertions are spelled in v_cndmask (push_cnd). T = 4 has 40 list
+    // registers: with either of the two the register allocator runs out (measured: 720 - 848 B of scratch), so it keeps the serial scan
+    constexpr bool LEAN_WALK = T <= 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char knn_smem[];
     u16* ring = (u16*)knn_smem;                                        // [STAGES][BM + BN rows][32 halves] (QP: codeword rows only)
     float* sCn = (float*)(knn_smem + L::cn);                           // [4][CNS]: |c|^2 of four tiles
@@ -232,21 +264,52 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
             } else {
                 // Epilogue. A lane inserts ~ (T+1)/n of the n values it has seen, so after the first tiles a column rarely holds an
                 // insertion. A scalar branch right behind the vector compare it depends on stalls ~19 cycles, and 128 of those pairs
-                // per tile were a good part of the kernel. So: the largest of a column's 32 scores by 16 v_max3_f32, ONE compare
-                // per column into its own SGPR pair, one branch per tile (measured: the test itself is free, 13.0 ms with and
-                // without it); only a column that does hold a score above its threshold is walked.
-                float mx[NT];
+                // per tile were a good part of the kernel. So: the largest of a column's 32 scores, ONE compare per column into its
+                // own SGPR pair, one branch per tile (measured: the test itself is free, 13.0 ms with and without it); only a column
+                // that does hold a score above its threshold is walked.
+                // The walk is NOT rare on truncated images (bench: one to three scores above a threshold per wave and tile, coming
+                // in bursts: DESIGN §5), so the scan is written for the walk: it leaves the maximum of every 4-row group (two
+                // instructions per group, four to fold the eight of a column: 20 per column instead of the 17 of a serial chain)
+                // and the walk starts from those instead of computing them again (16 per flagged column saved). The 32 maxima
+                // stay live across the walk: LEAN_WALK only (else the serial chain, and the walk computes the maxima of a flagged
+                // column itself).
+                // The partner wave row's thresholds are READ here, before the scan, and folded in behind it: the LDS round trip
+                // hides behind the 80 maxima, and what they publish is at worst one tile old (a stale value is only a lower, i.e.
+                // more conservative, threshold: header).
+                float other[NT];
+                if (WR == 2) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) other[nt] = sThr[(pw * NT + nt) * 64 + lane];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                float gm[LEAN_WALK ? NT : 1][MT], mx[NT];
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     float m;
-                    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(acc[0][nt][0]), "v"(acc[0][nt][1]), "v"(acc[0][nt][2]));
-                    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(acc[0][nt][3]));
+                    if (LEAN_WALK) {
 #pragma unroll
-                    for (int mt = 1; mt < MT; ++mt) {
-                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(acc[mt][nt][0]), "v"(acc[mt][nt][1]));
-                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(acc[mt][nt][2]), "v"(acc[mt][nt][3]));
+                        for (int mt = 0; mt < MT; ++mt) {
+                            asm("v_max3_f32 %0, %1, %2, %3" : "=v"(gm[nt][mt]) : "v"(acc[mt][nt][0]), "v"(acc[mt][nt][1]), "v"(acc[mt][nt][2]));
+                            asm("v_max_f32 %0, %1, %2" : "=v"(gm[nt][mt]) : "v"(gm[nt][mt]), "v"(acc[mt][nt][3]));
+                        }
+                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(gm[nt][0]), "v"(gm[nt][1]), "v"(gm[nt][2]));
+                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(gm[nt][3]), "v"(gm[nt][4]));
+                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(gm[nt][5]), "v"(gm[nt][6]));
+                        asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(gm[nt][7]));
+                    } else {
+                        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(acc[0][nt][0]), "v"(acc[0][nt][1]), "v"(acc[0][nt][2]));
+                        asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(m), "v"(acc[0][nt][3]));
+#pragma unroll
+                        for (int mt = 1; mt < MT; ++mt) {
+                            asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(acc[mt][nt][0]), "v"(acc[mt][nt][1]));
+                            asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(m), "v"(acc[mt][nt][2]), "v"(acc[mt][nt][3]));
+                        }
                     }
                     mx[nt] = m;
+                }
+                if (WR == 2) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) asm("v_max_f32 %0, %1, %2" : "=v"(thr[nt]) : "v"(thr[nt]), "v"(other[nt]));
                 }
                 unsigned long long hit[NT];
 #pragma unroll
@@ -254,25 +317,28 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
                 unsigned long long any_hit = 0ull;
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) any_hit |= hit[nt];
-                if (__builtin_expect(any_hit != 0ull, 0)) {
+                if (any_hit != 0ull) {
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         if (hit[nt] == 0ull) continue;
                         // Every step ends in a workgroup barrier, so a tile's epilogue costs what it costs the SLOWEST of the eight
-                        // waves: keep the walk of a flagged column short. The largest of each 4-row group (two instructions per
-                        // group), eight compares into eight SGPR pairs, eight scalar tests; only a group that holds a score above
-                        // the threshold has its four scores compared and inserted (the empty asm keeps the compiler from sinking
-                        // every compare next to its branch again). A score is re-tested against the threshold as it stands when
-                        // its turn comes; the insertion itself is branch-free.
-                        float gm[MT];
+                        // waves: keep the walk of a flagged column short. Eight compares of the group maxima into eight SGPR
+                        // pairs, eight scalar tests; only a group that holds a score above the threshold has its four scores
+                        // compared and inserted (the empty asm keeps the compiler from sinking every compare next to its branch
+                        // again). A score is re-tested against the threshold as it stands when its turn comes; the insertion
+                        // itself is branch-free.
+                        float gl[MT];
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
-                            asm("v_max3_f32 %0, %1, %2, %3" : "=v"(gm[mt]) : "v"(acc[mt][nt][0]), "v"(acc[mt][nt][1]), "v"(acc[mt][nt][2]));
-                            asm("v_max_f32 %0, %1, %2" : "=v"(gm[mt]) : "v"(gm[mt]), "v"(acc[mt][nt][3]));
+                            if (LEAN_WALK) gl[mt] = gm[nt][mt];
+                            else {
+                                asm("v_max3_f32 %0, %1, %2, %3" : "=v"(gl[mt]) : "v"(acc[mt][nt][0]), "v"(acc[mt][nt][1]), "v"(acc[mt][nt][2]));
+                                asm("v_max_f32 %0, %1, %2" : "=v"(gl[mt]) : "v"(gl[mt]), "v"(acc[mt][nt][3]));
+                            }
                         }
                         unsigned long long gk[MT];
 #pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) gk[mt] = __ballot(gm[mt] > thr[nt]);
+                        for (int mt = 0; mt < MT; ++mt) gk[mt] = __ballot(gl[mt] > thr[nt]);
                         asm volatile("" :: "s"(gk[0]), "s"(gk[1]), "s"(gk[2]), "s"(gk[3]), "s"(gk[4]), "s"(gk[5]), "s"(gk[6]), "s"(gk[7]));
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
@@ -285,40 +351,34 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
                             for (int j = 0; j < 4; ++j) {
                                 if (mk[j] == 0ull) continue;
                                 const float a = acc[mt][nt][j];
-                                top[nt].push_flat(a > thr[nt] ? -a : __builtin_inff(), row0 + mt * 16 + j);
+                                const float x = a > thr[nt] ? -a : __builtin_inff();
+                                if (LEAN_WALK) push_cnd(top[nt], x, row0 + mt * 16 + j); else top[nt].push_flat(x, row0 + mt * 16 + j);
                                 asm("v_max_f32_e64 %0, %1, -%2" : "=v"(thr[nt]) : "v"(thr[nt]), "v"(top[nt].v[T]));
                             }
                         }
+                        // Thresholds shared by the 8 lane slots of a query column. A wave's own thresholds change only in a column
+                        // it has just inserted into, so only here: the largest of the wave's four row groups, published to the
+                        // partner wave row through LDS, which reads it at the top of its next epilogue (above).
+                        // Every other column keeps a threshold that already is the same in its four row groups.
+                        thr[nt] = max_of_row_groups(thr[nt]);
+                        if (WR == 2) sThr[(wv * NT + nt) * 64 + lane] = thr[nt];
                     }
                 }
-            }
-            // thresholds shared by the 8 lane slots of a query column: the four row groups of this wave (lanes fr, fr+16, fr+32,
-            // fr+48) by two register swaps (v_permlane32_swap / v_permlane16_swap: no LDS round trip), then the partner wave row
-            // through LDS (see the header)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(thr[nt]), __float_as_uint(thr[nt]), false, false);
-                float sh;
-                asm("v_max_f32 %0, %1, %2" : "=v"(sh) : "v"(__uint_as_float(h[0])), "v"(__uint_as_float(h[1])));
-                const auto q = __builtin_amdgcn_permlane16_swap(__float_as_uint(sh), __float_as_uint(sh), false, false);
-                asm("v_max_f32 %0, %1, %2" : "=v"(sh) : "v"(__uint_as_float(q[0])), "v"(__uint_as_float(q[1])));
-                if (WR == 2) {
-                    sThr[(wv * NT + nt) * 64 + lane] = sh;
-                    const float other = sThr[(pw * NT + nt) * 64 + lane];
-                    asm("v_max_f32 %0, %1, %2" : "=v"(thr[nt]) : "v"(sh), "v"(other));
-                } else thr[nt] = sh;
             }
             kc = 0; ++t;
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // the clamped re-loads past the end: LDS must be quiet before exit
     if (PRE) {
-        // thr[] is the best over this wave's four row groups and (through sThr, one tile late) the partner wave row; one more exchange
-        // behind a barrier makes it the best of the whole sample: the nearest SAMPLED row in the stage-1 coordinates. The start value
+        // thr[] is the best score each lane slot has met: the largest of the wave's four row groups here (once, not per tile: nothing
+        // in the pre-pass reads a threshold) and one exchange with the partner wave row behind a barrier make it the best of the
+        // whole sample: the nearest SAMPLED row in the stage-1 coordinates. The start value
         // handed to the main launch is that score RELAXED by thr_relax (< 0 in accumulator units): the proof of a query needs every
         // row it drops to lie beyond the nearest neighbour's FULL distance, which exceeds its stage-1 distance by the energy the
         // truncation left out -- a start value right at the sample's best makes the proof fail whenever that best is (close to) the
         // nearest neighbour itself (measured: 15.7 % instead of 6.7 % of the queries).
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) thr[nt] = max_of_row_groups(thr[nt]);
         __syncthreads();
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) sThr[(wv * NT + nt) * 64 + lane] = thr[nt];
