@@ -68,6 +68,9 @@ extern "C" {
 #define ISMHIP_CSHOT_DIM 1344
 #define ISMHIP_FPFH_DIM    33
 #define ISMHIP_SHORT_SHOT_MAX_DIM 256   /* r_bins * e_bins * a_bins of ismhip_short_shot */
+#define ISMHIP_COSPAIR_LEVELS 7     /* concentric shells of ismhip_cospair */
+#define ISMHIP_COSPAIR_BINS   9     /* bins per pair feature and per colour channel */
+#define ISMHIP_COSPAIR_DIM  378     /* 7 levels x (27 geometry + 27 colour) */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -88,7 +91,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -238,6 +241,31 @@ int  ismhip_short_cshot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32
                         const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba, const float* lrf9,
                         float radius, float min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
                         int rc_bins, int ec_bins, int ac_bins, int hist_size, float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesCospair::iComputeDescriptors (features/features_cospair.cpp:28-77) -> COSPAIR::ComputeCOSPAIR (third_party/cospair/cospair.cpp:
+ * 18-294) with the parameters the reference hard-codes (7 levels, 9 bins, rgb_type 5 = CIELab, 9 colour bins). desc_out[nkp * 378]: for
+ * level l = 1..7 the block at (l - 1) * 54 holds a geometry array (f1 bins 0..8, f2 bins 9..17, f3 bins 18..26) and a colour array (L, a, b
+ * likewise). Needs no frame and no keypoint colour; the cloud must have been created with rgba. Per keypoint:
+ *  - the centre is the finite cloud point NEAREST to the keypoint (d2 the unfused float (dx*dx + dy*dy) + dz*dz; among equal distances
+ *    the lowest original index), however far away; its position and normal are the source of every pair;
+ *  - level l owns the points with r2_{l-1} <= d2 < r2_l, d2 to the CENTRE, r2_l = (float)(r_l * r_l), r_l = ((double)l / 7) * (double)radius,
+ *    r2_0 = 0; the centre itself is dropped by index (coincident duplicates of it are ordinary level-1 pairs);
+ *  - a neighbour whose normal is not finite is skipped and not counted; every other one counts in its level and deposits +1 at
+ *    bin_f1, 9 + bin_f2, 18 + bin_f3 of the geometry array: (f1, f2, f3) = PCL 1.10 computePairFeatures(centre, neighbour) in float, all
+ *    zero for a degenerate pair; deg_f1 = f1 * 57.29578f + 180, deg = acosf(clamp(f, -1, 1)) * 57.29578f for f2 and f3;
+ *    bin = int(floor((double)deg / 40.0)) for f1, / 20.0 for f2 and f3; and +1 at bin_l, 9 + bin_a, 18 + bin_b of the colour array:
+ *    (L, a, b) = PCL's RGB2CIELAB of the NEIGHBOUR's colour, l' = (float)(1.0 * L / 100), a' = (float)((a + 86.185) / 184.439),
+ *    b' = (float)((b + 107.863) / 202.345) (sums and divisions in double), bin = int(floor((double)x' / (1.0 / 9)));
+ *  - an index offset + bin that stays inside [0, 27) is used as it is (a bin 9 of f1, f2, L or a lands on bin 0 of the next feature, as
+ *    in the reference); one that leaves the array (undefined in the reference) is clamped to 0 or 26;
+ *  - every entry of a level with n pairs becomes ((float)count / (float)n) * (float)l; an empty level stays zero; no final normalisation.
+ * A keypoint that is not finite, an object without a finite point and a centre whose normal is not finite give a row that is NaN AS A WHOLE
+ * with counts 0. neighbour_count_out[nkp]: the sum of the level pair counts; level_count_out[nkp * 7]; snap_index_out[nkp]: the object-local
+ * original index of the centre, 0xffffffff for a NaN row; each may be NULL. Refused with ISMHIP_ERR_INVALID: a missing array or a
+ * radius that is not positive ("cospair: bad argument"), a cloud made without rgba ("cospair: colour arrays missing"). Timer "cospair".
+ * The per-point colour indices are built by the first call on a cloud and kept with it. */
+int  ismhip_cospair(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                    const float* kpx, const float* kpy, const float* kpz, float radius, float* desc_out,
+                    uint32_t* neighbour_count_out, uint32_t* level_count_out, uint32_t* snap_index_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
@@ -264,7 +292,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

@@ -31,7 +31,7 @@ EXPORTS = [
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
-    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot",
+    "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -329,6 +329,25 @@ def short_cshot_color_grid(dims=32):
     if int(dims) in SHORT_CSHOT_COLOR_BINS:
         return int(dims), SHORT_CSHOT_COLOR_BINS[int(dims)]
     return 32, (2, 2, 8)
+
+
+COSPAIR_LEVELS, COSPAIR_BINS, COSPAIR_DIM = 7, 9, 378
+
+
+def cospair(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False, want_levels=False, want_snap=False):
+    """ismhip_cospair -> [nkp, 378]; with want_counts the pairs per keypoint [nkp], with want_levels the pairs per level [nkp, 7], with
+    want_snap the object-local original index of the snapped cloud point [nkp] (-1 for a NaN row), appended in this order"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, COSPAIR_DIM), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    lev = torch.empty((n, COSPAIR_LEVELS), dtype=torch.int32, device=kpx.device) if want_levels else None
+    snap = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_snap else None
+    ctx.check(lib().ismhip_cospair(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), _p(out), _p(cnt), _p(lev), _p(snap)),
+              "ismhip_cospair")
+    extra = [t for t in (cnt, lev, snap) if t is not None]
+    return (out, *extra) if extra else out
 
 
 def fpfh33(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False):

@@ -55,6 +55,11 @@ struct ismhip_cloud {
     size_t kp_perm_cap = 0;
     const float* kp_perm_key = nullptr;   // the kpx pointer the order was built from (nullptr: none)
     std::vector<uint32_t> kp_perm_off;    // and its offsets
+    // CoSPAIR's colour codes (cospair.hip), cell-sorted like sp4: the three colour histogram indices of every point, 5 bits each. Built by
+    // the first ismhip_cospair on this cloud (cospair_code_valid), kept for the later ones; the allocation is recycled with the cloud.
+    uint16_t* cospair_code = nullptr;     // [cospair_code_cap]
+    size_t cospair_code_cap = 0;
+    bool cospair_code_valid = false;
     // capacities of the owned allocations (clouds are recycled through ismhip_ctx::cloud_pool)
     size_t cap_pts = 0; int cap_obj = 0; bool cap_color = false;
 };
@@ -175,7 +180,7 @@ struct ismhip_ctx {
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR
 };
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);
@@ -355,9 +360,9 @@ __device__ __forceinline__ float shot_atan2(float y, float x) {
     return y < 0.f ? -r : r;
 }
 
-// normalised CIELab of a packed 0x00RRGGBB colour through the context's two LUTs (PCL's RGB2CIELAB, then L / 100, a / 120, b / 120):
-// the keypoint's reference colour of k_shot<true> (shot.hip) and k_short_cshot (short_cshot.hip)
-__device__ __forceinline__ void rgb2lab_norm(const float* lut_srgb, const float* lut_sxyz, uint32_t c4, float& L, float& A, float& B) {
+// CIELab of a packed 0x00RRGGBB colour through the context's two LUTs: PCL's RGB2CIELAB as it returns them (L <= 100, |a|, |b| <= 120),
+// the values CoSPAIR rescales itself (cospair.hip)
+__device__ __forceinline__ void rgb2lab(const float* lut_srgb, const float* lut_sxyz, uint32_t c4, float& L, float& A, float& B) {
     const float fr = lut_srgb[(c4 >> 16) & 0xff], fg = lut_srgb[(c4 >> 8) & 0xff], fb = lut_srgb[c4 & 0xff];
     const float X = fr * 0.412453f + fg * 0.357580f + fb * 0.180423f;
     const float Y = fr * 0.212671f + fg * 0.715160f + fb * 0.072169f;
@@ -369,6 +374,10 @@ __device__ __forceinline__ void rgb2lab_norm(const float* lut_srgb, const float*
     L = 116.0f * vy - 16.0f; if (L > 100) L = 100.0f;
     A = 500.0f * (vx - vy); if (A > 120) A = 120.0f; else if (A < -120) A = -120.0f;
     B = 200.0f * (vy - vz); if (B > 120) B = 120.0f; else if (B < -120) B = -120.0f;
+}
+// the same normalised (L / 100, a / 120, b / 120): the keypoint's reference colour of k_shot<true> (shot.hip) and k_short_cshot (short_cshot.hip)
+__device__ __forceinline__ void rgb2lab_norm(const float* lut_srgb, const float* lut_sxyz, uint32_t c4, float& L, float& A, float& B) {
+    rgb2lab(lut_srgb, lut_sxyz, c4, L, A, B);
     L /= 100.0f; A /= 120.0f; B /= 120.0f;
 }
 

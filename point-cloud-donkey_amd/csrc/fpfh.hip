@@ -7,7 +7,7 @@
 //   k_spfh      : per flagged surface point p, SPFH(p) = 3x11 histogram of Darboux angles to its neighbours
 //   k_fpfh_sum  : per keypoint, FPFH = sum_nb SPFH(nb)/d^2, every 11-bin block rescaled to 100
 // Roofline (HBM gather model): sum_{p in U} M_p*24 + |U|*132 + sum_k M_k*136 + K*132 bytes.
-#include "common.h"
+#include "pair_features.h"
 #include <cstdlib>
 
 namespace {
@@ -55,61 +55,13 @@ __global__ __launch_bounds__(256) void k_fpfh_mark(FpfhArgs a) {
     if (a.count && lane == 0) a.count[k] = total;
 }
 
-// pcl::computePairFeatures in float; returns false when the pair is skipped
-__device__ __forceinline__ bool pair_features(float px, float py, float pz, float pnx, float pny, float pnz,
-                                              float qx, float qy, float qz, float qnx, float qny, float qnz,
-                                              float& f1, float& f2, float& f3) {
-    float dx = qx - px, dy = qy - py, dz = qz - pz;
-    const float f4 = sqrtf((dx * dx + dy * dy) + dz * dz);
-    if (f4 == 0.0f) return false;
-    float ax = pnx, ay = pny, az = pnz, bx = qnx, by = qny, bz = qnz;
-    const float angle1 = ((ax * dx + ay * dy) + az * dz) / f4;
-    const float angle2 = ((bx * dx + by * dy) + bz * dz) / f4;
-    // PCL swaps the roles when acos|a1| > acos|a2|. acos is decreasing with |slope| >= 1, so when the two absolute cosines differ
-    // by more than 1e-5 (hundreds of float acosf errors) the order of the acos values is the reverse order of the cosines and no
-    // acosf is needed; inside that band (and only there) the reference's own comparison of the two acosf values decides.
-    const float c1 = fabsf(angle1), c2 = fabsf(angle2);
-    const float gap = c2 - c1;
-    const bool swap_roles = fabsf(gap) > 1e-5f ? gap > 0.f : acosf(c1) > acosf(c2);
-    if (swap_roles) {
-        float t;
-        t = ax; ax = bx; bx = t; t = ay; ay = by; by = t; t = az; az = bz; bz = t;
-        dx = -dx; dy = -dy; dz = -dz;
-        f3 = -angle2;
-    } else f3 = angle1;
-    float vx = dy * az - dz * ay, vy = dz * ax - dx * az, vz = dx * ay - dy * ax;
-    const float vn = sqrtf((vx * vx + vy * vy) + vz * vz);
-    if (vn == 0.0f) return false;
-    vx /= vn; vy /= vn; vz /= vn;
-    const float wx = ay * vz - az * vy, wy = az * vx - ax * vz, wz = ax * vy - ay * vx;
-    f2 = (vx * bx + vy * by) + vz * bz;
-    f1 = atan2f((wx * bx + wy * by) + wz * bz, (ax * bx + ay * by) + az * bz);
-    return true;
-}
-
 __device__ __forceinline__ int clamp_bin(int h) { return h < 0 ? 0 : (h > 10 ? 10 : h); }
 
-// The same three features by FAST arithmetic (v_rsq_f32 / v_rcp_f32 instead of sqrt + IEEE divisions, a degree-13 odd polynomial
-// for the arctangent: max error 6.6e-7 rad over [0, 1], fitted and checked in tests/test_host_cpu.py) and the three bin
-// coordinates t = 11 (f + pi) / 2pi, 11 (f + 1) / 2 in float. The histogram only needs floor(t): when every t is at least
-// FPFH_GUARD away from the integers 1..10 the fast bins ARE the reference's bins (the fast values differ from the exact ones by
-// < 2e-5 in t), otherwise -- and for the degenerate pairs -- the caller evaluates pair_features + the double-precision bin formulas
-// exactly as the reference does. `sure` = the fast bins can be used. The role swap (which decides everything downstream) is
-// taken exactly as in pair_features.
+// The three bin coordinates t = 11 (f + pi) / 2pi, 11 (f + 1) / 2 in float from the FAST features of pair_features.h. The histogram
+// only needs floor(t): when every t is at least FPFH_GUARD away from the integers 1..10 the fast bins ARE the reference's bins (the
+// fast values differ from the exact ones by < 2e-5 in t), otherwise -- and for the pairs the fast features refuse -- the caller
+// evaluates pair_features + the double-precision bin formulas exactly as the reference does. true = the fast bins can be used.
 #define FPFH_GUARD 1e-4f
-__device__ __forceinline__ float fast_atan2(float y, float x) {
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    const float a = mn * __builtin_amdgcn_rcpf(mx);                     // 0/0 -> NaN: the caller's guard test fails and the exact path runs
-    const float z = a * a;
-    float p = 0.008097294718027115f;
-    p = fmaf(p, z, -0.037751708179712296f); p = fmaf(p, z, 0.08475969731807709f); p = fmaf(p, z, -0.13537675142288208f);
-    p = fmaf(p, z, 0.19895026087760925f); p = fmaf(p, z, -0.3332797586917877f); p = fmaf(p, z, 0.9999997019767761f);
-    float r = a * p;
-    r = ay > ax ? 1.57079632679489662f - r : r;
-    r = x < 0.f ? 3.14159265358979323846f - r : r;
-    return y < 0.f ? -r : r;
-}
 __device__ __forceinline__ bool fpfh_bin_sure(float t) {               // false for NaN
     const float fr = t - floorf(t);
     return (fr > FPFH_GUARD && fr < 1.0f - FPFH_GUARD) || t < 1.0f - FPFH_GUARD || t > 10.0f + FPFH_GUARD;   // only the integers 1..10 separate bins (0 and 11 are clamped away)
@@ -117,35 +69,8 @@ __device__ __forceinline__ bool fpfh_bin_sure(float t) {               // false 
 __device__ __forceinline__ bool pair_bins_fast(float px, float py, float pz, float pnx, float pny, float pnz,
                                                float qx, float qy, float qz, float qnx, float qny, float qnz,
                                                int& h1, int& h2, int& h3) {
-    float dx = qx - px, dy = qy - py, dz = qz - pz;
-    const float d2 = (dx * dx + dy * dy) + dz * dz;
-    if (d2 == 0.0f) return false;                                       // the exact path skips the pair: let it
-    const float inv_f4 = __builtin_amdgcn_rsqf(d2);
-    float ax = pnx, ay = pny, az = pnz, bx = qnx, by = qny, bz = qnz;
-    // the swap test needs the reference's own angle values near a tie: exact division there, reciprocal elsewhere
-    const float dot1 = (ax * dx + ay * dy) + az * dz, dot2 = (bx * dx + by * dy) + bz * dz;
-    float angle1 = dot1 * inv_f4, angle2 = dot2 * inv_f4;
-    const float gapf = fabsf(angle2) - fabsf(angle1);
-    if (!(fabsf(gapf) > 1e-4f)) return false;                           // near tie of the two cosines (or NaN): exact path decides the roles
-    float f3;
-    if (gapf > 0.f) {
-        float t;
-        t = ax; ax = bx; bx = t; t = ay; ay = by; by = t; t = az; az = bz; bz = t;
-        dx = -dx; dy = -dy; dz = -dz;
-        f3 = -angle2;
-    } else f3 = angle1;
-    float vx = dy * az - dz * ay, vy = dz * ax - dx * az, vz = dx * ay - dy * ax;
-    const float vn2 = (vx * vx + vy * vy) + vz * vz;
-    if (!(vn2 > 1e-30f)) return false;                                  // degenerate (or denormal): exact path
-    const float inv_vn = __builtin_amdgcn_rsqf(vn2);
-    vx *= inv_vn; vy *= inv_vn; vz *= inv_vn;
-    const float wx = ay * vz - az * vy, wy = az * vx - ax * vz, wz = ax * vy - ay * vx;
-    const float f2 = (vx * bx + vy * by) + vz * bz;
-    const float ay_ = (wx * bx + wy * by) + wz * bz, ax_ = (ax * bx + ay * by) + az * bz;
-    // the arctangent is only as well conditioned as |(x, y)| is large: the two arguments carry ~3e-7 of fast-arithmetic error, which
-    // is 1.5e-5 rad = 2.6e-5 of a bin at |(x, y)| = 0.02 (unit normals: |(x, y)|^2 = 1 - f2^2); closer to the pole the exact path runs
-    if (!((ax_ * ax_ + ay_ * ay_) > 4e-4f)) return false;
-    const float f1 = fast_atan2(ay_, ax_);
+    float f1, f2, f3, ax_;
+    if (!pair_features_fast(px, py, pz, pnx, pny, pnz, qx, qy, qz, qnx, qny, qnz, f1, f2, f3, ax_)) return false;
     const float t1 = 11.0f * ((f1 + 3.14159265358979323846f) * 0.15915494309189535f);
     const float t2 = 11.0f * ((f2 + 1.0f) * 0.5f), t3 = 11.0f * ((f3 + 1.0f) * 0.5f);
     // the seam of f1: for x < 0 the sign of y alone puts the pair into bin 10 (+pi) or bin 0 (-pi), so t1 = 0 and t1 = 11 are a bin

@@ -543,6 +543,7 @@ int ismhip_cloud_create(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h
     c->x = x; c->y = y; c->z = z; c->nx = nx; c->ny = ny; c->nz = nz; c->rgba = rgba;
     c->requested_cell = cell_size;
     c->kp_perm_key = nullptr;
+    c->cospair_code_valid = false;
     auto fail = [&](int code, const char* msg) { c->cap_pts = 0; ismhip_cloud_destroy(ctx, c); return ism_set_err(ctx, code, msg); };
     if (fresh) {
         const size_t capp = np + np / 8;
@@ -602,6 +603,7 @@ int ismhip_cloud_create(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h
 static void cloud_free(ismhip_cloud* c) {
     if (c->sp4) (void)hipFree(c->sp4);
     if (c->kp_perm) (void)hipFree(c->kp_perm);
+    if (c->cospair_code) (void)hipFree(c->cospair_code);
     if (c->members) (void)hipFree(c->members);
     if (c->cell_of_pt) (void)hipFree(c->cell_of_pt);
     if (c->rank_of_pt) (void)hipFree(c->rank_of_pt);

@@ -1,6 +1,6 @@
 // shot_wave.h — what the kernels of the SHOT family (shot.hip: k_shot; short_shot.hip: k_short_shot; short_cshot.hip: k_short_cshot)
-// have in common: one 64-lane wavefront per keypoint that sets itself up from the keypoint, its frame and the object's grid, streams
-// the points inside the query ball through an LDS queue to a per-neighbour function, and a launcher that checks the caller's arrays,
+// and CoSPAIR (cospair.hip: k_cospair, which has no frame) have in common: one 64-lane wavefront per keypoint that sets itself up
+// from the keypoint, its frame and the object's grid, streams the points inside the query ball through an LDS queue to a per-neighbour function, and a launcher that checks the caller's arrays,
 // uploads the keypoint offsets and starts a quarter as many workgroups as the longest keypoint run. The kernels differ in their
 // per-neighbour function, their histogram and their normalisation only; those stay in their units.
 #pragma once
@@ -29,12 +29,11 @@ struct ShotWave {
     CellRange cr;
 };
 
-// Set-up of one wave from any of the three argument structs (the common fields carry the same names), for rows of D floats: the XCD
-// block map, the keypoint of this wave in cell order, its centre, frame and ball. False when the wave has no row left to build: past
-// the object's keypoint run (wave-uniform; no block-level barrier may follow), or -- THE rule that compact.hip's k_keep_rows relies on
-// when it judges a row by its element 0 -- frame or centre not finite, or the ball misses the grid: the WHOLE row NaN, count 0.
+// The place of one wave, from any of the family's argument structs (the common fields carry the same names), for rows of D floats: the
+// XCD block map, the keypoint of this wave in cell order, its row, its centre and the object's grid. False when the wave has no row to
+// build: past the object's keypoint run (wave-uniform; no block-level barrier may follow).
 template <class Args>
-__device__ __forceinline__ bool shot_wave_setup(const Args& a, int D, ShotWave& w) {
+__device__ __forceinline__ bool shot_wave_place(const Args& a, int D, ShotWave& w) {
     int bx;
     if (!xcd_object_block(a.nbx, a.n_obj, w.o, bx)) return false;
     w.wv = threadIdx.x >> 6;
@@ -43,17 +42,32 @@ __device__ __forceinline__ bool shot_wave_setup(const Args& a, int D, ShotWave& 
     w.k = ordered_keypoint(a.kp_perm, a.kp_off[w.o], (uint32_t)(bx * 4 + w.wv));
     w.row = a.desc + (size_t)w.k * D;
     w.cx = a.kx[w.k]; w.cy = a.ky[w.k]; w.cz = a.kz[w.k];
-    const float* f = a.lrf + (size_t)w.k * 9;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { w.fx[i] = f[i]; w.fy[i] = f[3 + i]; w.fz[i] = f[6 + i]; }
     w.m = a.meta[w.o];
-    const bool ok = isfinite(w.fx[0]) && isfinite(w.fy[0]) && isfinite(w.fz[0]) && isfinite(w.cx) && isfinite(w.cy) && isfinite(w.cz);
+    return true;
+}
+
+// The cell range of the wave's ball, given `ok` = whatever else the descriptor needs to be finite. False -- THE rule that compact.hip's
+// k_keep_rows relies on when it judges a row by its element 0 -- when ok fails, the centre is not finite or the ball misses the grid:
+// the WHOLE row NaN, count 0.
+template <class Args>
+__device__ __forceinline__ bool shot_wave_ball(const Args& a, int D, ShotWave& w, bool ok) {
+    ok = ok && isfinite(w.cx) && isfinite(w.cy) && isfinite(w.cz);
     if (!ok || !ball_cells(w.m, w.cx, w.cy, w.cz, a.radius, w.cr)) {
         for (int i = w.lane; i < D; i += 64) w.row[i] = __builtin_nanf("");
         if (a.count && w.lane == 0) a.count[w.k] = 0;
         return false;
     }
     return true;
+}
+
+// Set-up of one wave of a descriptor that reads a frame: its place, the frame, the ball. False as the two steps say.
+template <class Args>
+__device__ __forceinline__ bool shot_wave_setup(const Args& a, int D, ShotWave& w) {
+    if (!shot_wave_place(a, D, w)) return false;
+    const float* f = a.lrf + (size_t)w.k * 9;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { w.fx[i] = f[i]; w.fy[i] = f[3 + i]; w.fz[i] = f[6 + i]; }
+    return shot_wave_ball(a, D, w, isfinite(w.fx[0]) && isfinite(w.fy[0]) && isfinite(w.fz[0]));
 }
 
 // The neighbours of the wave's keypoint: streams the candidate x-runs of the query ball (coalesced loads of the cell-sorted sp4) in NG

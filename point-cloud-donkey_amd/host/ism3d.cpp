@@ -423,6 +423,10 @@ void FeaturesSHORTCSHOT::iPostInitConfig() {     // configureSphericalGrid, then
     if ((long long)m_feature_dims + (long long)m_color_feature_dims * m_color_hist_size > ISMHIP_SHORT_CSHOT_MAX_DIM)
         throw RuntimeException("SHORT_CSHOT: a descriptor longer than " + std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + " is not built on the MI355X path");
 }
+FeaturesCospair::FeaturesCospair() { addParameter(m_radius, "Radius", 0.1f); }   // features_cospair.cpp:19-22
+void FeaturesCospair::checkInput(const PointCloud& cloud) const {
+    if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("CoSPAIR needs coloured point clouds");
+}
 
 void FeaturesSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_shot.cpp:28-81
     s.check(ismhip_shot352(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, desc_out, counts_out),
@@ -446,6 +450,11 @@ void FeaturesSHORTCSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9
     s.check(ismhip_short_cshot(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), s.krgba.as<uint32_t>(), lrf9, m_radius,
                                getMinRadius(), m_log_radius ? 1 : 0, m_r_bins, m_e_bins, m_a_bins, m_r_color_bins, m_e_color_bins, m_a_color_bins,
                                m_color_hist_size, desc_out, counts_out), "ismhip_short_cshot");
+}
+void FeaturesCospair::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {     // features_cospair.cpp:28-77
+    if (!s.has_color) throw RuntimeException("CoSPAIR needs coloured point clouds");
+    s.check(ismhip_cospair(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, desc_out, counts_out,
+                           nullptr, nullptr), "ismhip_cospair");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1118,7 +1127,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesFPFH::getTypeStatic()) return new FeaturesFPFH();
     if (type == FeaturesSHORTSHOT::getTypeStatic()) return new FeaturesSHORTSHOT();
     if (type == FeaturesSHORTCSHOT::getTypeStatic()) return new FeaturesSHORTCSHOT();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT)");
+    if (type == FeaturesCospair::getTypeStatic()) return new FeaturesCospair();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   Voting, VotingMeanShift, Vote, VotingMaximum voting/voting.h:35, voting_mean_shift.cpp, voting_maximum.h:25-88
@@ -250,6 +250,23 @@ protected:
     void iPostInitConfig() override;                 // + configureSphericalColorGrid (:592-646) + what the device refuses
 private:
     int m_color_feature_dims, m_color_hist_size, m_r_color_bins, m_e_color_bins, m_a_color_bins;
+};
+// features/features_cospair.{h,cpp} -> third_party/cospair: seven shells around the cloud point nearest to the keypoint, pair features
+// and CIELab colours, 378 floats. Levels, bins and colour type are hard-coded in the reference (:37-40); Radius is the one parameter.
+// Not an ISM3D_FEATURE: it checks its input cloud.
+class FeaturesCospair : public Features {
+public:
+    FeaturesCospair();
+    static std::string getTypeStatic() { return "CoSPAIR"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return ISMHIP_COSPAIR_DIM; }
+    bool needsColor() const override { return true; }
+    void checkInput(const PointCloud& cloud) const override;   // a cloud without colours throws
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+private:
+    float m_radius;
 };
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------
