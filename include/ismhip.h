@@ -65,6 +65,7 @@ extern "C" {
 #define ISMHIP_SOM_COMPLETE_VOTING_SPACE  3
 
 #define ISMHIP_SHOT_DIM   352
+#define ISMHIP_BSHOT_DIM  352     /* ismhip_bshot352: SHOT-352 binarised in groups of four */
 #define ISMHIP_CSHOT_DIM 1344
 #define ISMHIP_FPFH_DIM    33
 #define ISMHIP_SHORT_SHOT_MAX_DIM 256   /* r_bins * e_bins * a_bins of ismhip_short_shot */
@@ -91,7 +92,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","knn","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -184,6 +185,22 @@ int  ismhip_shotna_lrf(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
 int  ismhip_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                     const float* kpx, const float* kpy, const float* kpz,
                     const float* lrf9, float radius, float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesBSHOT::getBinaryVector (features/features_bshot.cpp:109-157) on n_rows rows of 352 floats, in groups of four (v0..v3); dst may be
+ * src. Every element of dst is 0.0f or 1.0f. Exactly the reference's text: sum = ((v0 + v1) + v2) + v3 in float, unfused; a group with
+ * sum == 0 gives 0000; every test is (double)lhs > (double)sum * 0.9 (the literal 0.9 is a double), the lhs of a pair vi + vj and of a
+ * triple (vi + vj) + vk in float in the written index order; case B sets the bit of every single element that passes and holds when one
+ * bit is set; otherwise case C runs the six pair tests in the order 01, 02, 03, 12, 13, 23, the last one that passes overwriting the
+ * result, and holds when two bits are set; otherwise case D runs the triples 012, 013, 023, 123 likewise and holds with three bits;
+ * otherwise 1111. The result carries over between the cases as the reference writes it, so two consequences are kept:
+ *  - two bits left by case B stand when no pair test passes, and count as case C (possible with negative elements only);
+ *  - a group that holds a NaN gives 1111 (sum != 0 is true, every comparison false): a SHOT row that is NaN as a whole becomes 352 ones
+ *    and is NOT removed by ismhip_compact_descriptor_rows. Timer "bshot". */
+int  ismhip_bshot_binarize(ismhip_ctx* ctx, int n_rows, const float* src, float* dst);
+/* FeaturesBSHOT::iComputeDescriptors (features/features_bshot.cpp:40-107): the arguments of ismhip_shot352; desc_out[nkp*352] =
+ * ismhip_bshot_binarize of the rows ismhip_shot352 writes on the same inputs (a separate kernel behind k_shot); neighbour_count_out as there. */
+int  ismhip_bshot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                     const float* kpx, const float* kpy, const float* kpz,
+                     const float* lrf9, float radius, float* desc_out, uint32_t* neighbour_count_out);
 /* FeaturesCSHOT::iComputeDescriptors (features/features_cshot.cpp:28-103); kp_rgba = keypoint colours */
 int  ismhip_cshot1344(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                       const float* kpx, const float* kpy, const float* kpz, const uint32_t* kp_rgba,
@@ -338,12 +355,30 @@ int  ismhip_codebook_stage1_dims(const ismhip_codebook* cb, float* energy_out);
 /* The same for the image the queries whose stage-1 proof failed are searched on again (0: all dimensions). */
 int  ismhip_codebook_stage2_dims(const ismhip_codebook* cb, float* energy_out);
 
+/* The resident integer image of a codebook whose every element is exactly 0.0f or 1.0f (-0.0f counts as 0), e.g. B-SHOT rows
+ * (features/features_bshot.cpp:96-99): int8 rows zero-padded to the search kernel's K step (128) and the number of ones per row.
+ * ISMHIP_ERR_INVALID, with the codebook unchanged, when any element is something else. ISMHIP_ERR_UNSUPPORTED when the search key does
+ * not fit: the key is a SIGNED 32-bit (distance << s) + row with s = ceil(log2(n_words rounded up to 256)), which needs
+ * (dim + 2) * 2^s <= 2^31 (at dim 1344: up to 2^20 words). A second call is a no-op. Synchronises. */
+int  ismhip_codebook_make_binary(ismhip_ctx* ctx, ismhip_codebook* cb);
+/* 1 when the codebook holds that image, else 0 */
+int  ismhip_codebook_has_binary(const ismhip_codebook* cb);
+
 /* ---- activation: ActivationStrategyKNN::activateKNN (activation_strategy/activation_strategy_knn.h:41-126)
  *      with FLANNExactMatch semantics (SearchParams(-1)): exact k nearest codewords, ascending distance,
  *      ties -> lowest row. idx_out[nq*k] (row in words, -1 when n_words < k), dist_out[nq*k] = the FLANN
  *      functor value (utils/distance.cpp:33-52), recomputed by direct summation for the winners. */
 int  ismhip_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q,
                 int k, int32_t* idx_out, float* dist_out);
+/* ismhip_knn for 0/1 rows on a codebook with a binary image (ismhip_codebook_make_binary), 1 <= k <= 16. Between such rows both FLANN
+ * functors (utils/distance.cpp:33-52) equal the Hamming distance, so there is no metric argument: the answers -- ascending (distance,
+ * row), -1 entries with a NaN distance when n_words < k, dist_out = the functor value -- are bit-identical to ismhip_knn's for
+ * ISMHIP_METRIC_L2SQ and for ISMHIP_METRIC_CHI2. The float query rows q[nq * dim] are packed on the device inside the call; the search
+ * is one exact pass of 8-bit integer matrix-core products with int32 accumulation. ISMHIP_ERR_INVALID: a query element that is not 0 or 1
+ * (the outputs are then void), a codebook without the image, k outside 1 .. 16. Any nq >= 0, n_words >= 1, dim >= 1; never falls back to
+ * ismhip_knn. Timer "knn_binary"; counter "knn_binary_launches" (ismhip_timer_get, valid without timers): the calls that searched.
+ * Synchronises. */
+int  ismhip_knn_binary(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out);
 #define ISMHIP_KNN_LARGE_K_MAX 1024
 /* ActivationStrategyKNN::activateKNN for any K (FLANNExactMatch semantics): the contract of ismhip_knn for
  * 1 <= k <= ISMHIP_KNN_LARGE_K_MAX. idx_out / dist_out device [nq*k]. Synchronises. k <= 16 is ismhip_knn itself. Larger k: squared-L2

@@ -32,6 +32,7 @@ EXPORTS = [
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
+    "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -208,6 +209,15 @@ class Codebook:
         assert kp.shape == (self.n_words, 3)
         self.ctx.check(lib().ismhip_codebook_set_word_keypoint(self.ctx._h, self._h, _p(kp)), "ismhip_codebook_set_word_keypoint")
 
+    def make_binary(self):
+        """ismhip_codebook_make_binary: the int8 image of a codebook of zeros and ones, which knn_binary searches. Raises IsmHipError
+        "(-1)" when an element is neither (the codebook stays as it was), "(-4)" when the search key does not fit."""
+        self.ctx.check(lib().ismhip_codebook_make_binary(self.ctx._h, self._h), "ismhip_codebook_make_binary")
+
+    @property
+    def has_binary(self):
+        return lib().ismhip_codebook_has_binary(self._h) == 1
+
     def close(self):
         if self._h:
             lib().ismhip_codebook_destroy(self.ctx._h, self._h)
@@ -253,6 +263,28 @@ def shot352(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, want_counts=Fals
     cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
     ctx.check(lib().ismhip_shot352(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(lrf), C.c_float(radius), _p(out), _p(cnt)),
               "ismhip_shot352")
+    return (out, cnt) if want_counts else out
+
+
+def bshot_binarize(ctx, src, out=None):
+    """ismhip_bshot_binarize of the rows src [n, 352] -> [n, 352] of 0.0 / 1.0; out may be src itself (in place)"""
+    torch = _torch()
+    assert src.dim() == 2 and src.shape[1] == 352 and src.dtype == torch.float32
+    if out is None:
+        out = torch.empty_like(src)
+    ctx.check(lib().ismhip_bshot_binarize(ctx._h, C.c_int(src.shape[0]), _p(src), _p(out)), "ismhip_bshot_binarize")
+    return out
+
+
+def bshot352(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, want_counts=False):
+    """ismhip_bshot352: the arguments and counts of shot352, the rows binarised"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, 352), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_bshot352(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(lrf), C.c_float(radius), _p(out), _p(cnt)),
+              "ismhip_bshot352")
     return (out, cnt) if want_counts else out
 
 
@@ -520,6 +552,13 @@ def _knn_outputs(q, k):
 def knn(ctx, cb, metric, q, k=1):
     nq, idx, dist = _knn_outputs(q, k)
     ctx.check(lib().ismhip_knn(ctx._h, cb._h, C.c_int(metric), C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn")
+    return idx, dist
+
+
+def knn_binary(ctx, cb, q, k=1):
+    """ismhip_knn_binary: knn for rows of zeros and ones on a codebook with a binary image (Codebook.make_binary), either metric; synchronises"""
+    nq, idx, dist = _knn_outputs(q, k)
+    ctx.check(lib().ismhip_knn_binary(ctx._h, cb._h, C.c_int(nq), _p(q), C.c_int(k), _p(idx), _p(dist)), "ismhip_knn_binary")
     return idx, dist
 
 

@@ -14,6 +14,7 @@
 int ism_codebook_split_bf16(ismhip_ctx* ctx, ismhip_codebook* cb, uint32_t absmax_bits);
 int ism_codebook_build_pca(ismhip_ctx* ctx, ismhip_codebook* cb);       // pca.hip: rotated, truncated stage-1 image
 void ism_codebook_free_pca(ismhip_codebook* cb);
+void ism_codebook_free_binary(ismhip_codebook* cb);                       // knn_binary.hip
 
 namespace {
 
@@ -232,6 +233,7 @@ int ismhip_codebook_destroy(ismhip_ctx* ctx, ismhip_codebook* cb) {
                     cb->vote_class, cb->vote_instance, cb->vote_bbox_quat, cb->vote_bbox_size, cb->class_sigma, cb->word_class, cb->words_bf16_hi, cb->words_f16t, cb->word_keypoint};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     ism_codebook_free_pca(cb);
+    ism_codebook_free_binary(cb);
     if (cb->chi_shadow) {
         ismhip_codebook* sh = cb->chi_shadow;
         void* sp[] = {sh->words, sh->word_norm, sh->words_bf16_hi, sh->words_f16t, sh->shadow_perm};

@@ -115,6 +115,10 @@ struct ismhip_codebook {
     // pca: the stage-1 image (leading coordinates that hold 97 % of the second moment); pca2: a longer one (99.7 %) for stage 2, the
     // queries whose stage-1 proof failed -- both cut from the same eigenbasis
     PcaImage pca, pca2;
+    // ---- the 0/1 image of the exact binary search (knn_binary.hip; ismhip_codebook_make_binary), nullptr: not built --------------------
+    int8_t* bin_words = nullptr;     // [n_words_pad x bin_ld] 0 / 1, zero padded
+    int32_t* bin_norm = nullptr;     // [n_words_pad] ones per row (dim + 1 for padding rows)
+    int bin_ld = 0, bin_shift = 0;   // row stride in bytes; row bits of the (distance, row) key
 };
 
 struct TimerAcc {
@@ -174,13 +178,14 @@ struct ismhip_ctx {
     bool knn_lk_exact = false;        // env ISMHIP_KNN_LARGE_K_EXACT=1: ismhip_knn_large_k takes the exact scan for every query (overrides _FAST)
     float knn_lk_seed_scale = 1.0f;   // env ISMHIP_KNN_LARGE_K_SEED_SCALE: multiplies the fast path's seed (tests: a wrong seed costs time, never correctness)
     uint32_t knn_lk_stats[3] = {0, 0, 0};   // last ismhip_knn_large_k: queries {certified by the fast path, retried, answered by the exact scan}
+    uint32_t knn_binary_launches = 0; // ismhip_knn_binary calls that searched (counter "knn_binary_launches"; tests of the host route)
     int knn_mode = 0;            // env ISMHIP_KNN_MODE = f16 (0, default) | bf16x3 (1) | f32 (2): squared-L2 candidate kernel (A/B runs, tests)
 };
 
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND
 };
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);

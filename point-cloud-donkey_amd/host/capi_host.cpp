@@ -51,6 +51,8 @@ int ism3d_load_cloud(const char* file, int cap, float* x, float* y, float* z, fl
 int ism3d_train(void* m) { GUARD(((ImplicitShapeModel*)m)->train(); return 0;) }
 int ism3d_codebook_size(void* m) { return ((ImplicitShapeModel*)m)->getCodebook()->getSize(); }
 int ism3d_num_classes(void* m) { return ((ImplicitShapeModel*)m)->numClasses(); }
+// Features::getDescriptorLength of the configured descriptor
+int ism3d_descriptor_length(void* m) { const Features* f = ((ImplicitShapeModel*)m)->getFeatures(); return f ? f->getDescriptorLength() : -1; }
 // copies the codebook tables out (for cross-checks against the Python harness); pass NULL to query sizes
 int ism3d_codebook_get(void* m, float* words, float* vote_xyz, uint32_t* vote_class, float* class_sigma) {
     const CodebookData& d = ((ImplicitShapeModel*)m)->getCodebook()->data();

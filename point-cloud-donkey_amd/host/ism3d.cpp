@@ -98,7 +98,11 @@ public:
     // scratch for raw (uncompacted) features
     DevBuf raw_lrf, raw_desc, raw_cnt;
 
+    // ISMHIP_KNN_BINARY=0, read when the context is created: BSHOT codebooks keep the float search (A/B runs, tests; same answers)
+    bool knn_binary_route = true;
+
     explicit DeviceSession(int device) {
+        { const char* e = getenv("ISMHIP_KNN_BINARY"); knn_binary_route = !(e && e[0] == '0'); }
         int rc = ismhip_ctx_create(device, nullptr, &ctx);
         if (rc == ISMHIP_ERR_NODEVICE) throw RuntimeException("no gfx950 device available: the recognition path has no CPU fallback");
         if (rc != ISMHIP_OK) throw RuntimeException("ismhip_ctx_create failed");
@@ -362,6 +366,7 @@ std::shared_ptr<DeviceFeatures> Features::operator()(DeviceSession& s) const {  
 FeaturesSHOT::FeaturesSHOT() { addParameter(m_radius, "Radius", 0.1f); }
 FeaturesCSHOT::FeaturesCSHOT() { addParameter(m_radius, "Radius", 0.1f); }
 FeaturesFPFH::FeaturesFPFH() { addParameter(m_radius, "Radius", 0.1f); }
+FeaturesBSHOT::FeaturesBSHOT() { addParameter(m_radius, "Radius", 0.1f); }       // features_bshot.cpp:31-34
 FeaturesSHORTSHOT::FeaturesSHORTSHOT() {         // features_short_shot.cpp:21-32
     addParameter(m_radius, "Radius", 0.1f);
     addParameter(m_use_min_radius, "UseMinRadius", false);
@@ -431,6 +436,10 @@ void FeaturesCospair::checkInput(const PointCloud& cloud) const {
 void FeaturesSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_shot.cpp:28-81
     s.check(ismhip_shot352(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, desc_out, counts_out),
             "ismhip_shot352");
+}
+void FeaturesBSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {  // features_bshot.cpp:40-107
+    s.check(ismhip_bshot352(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), lrf9, m_radius, desc_out, counts_out),
+            "ismhip_bshot352");
 }
 void FeaturesCSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {  // features_cshot.cpp:28-103
     if (!s.has_color) throw RuntimeException("CSHOT needs coloured point clouds");
@@ -536,9 +545,18 @@ void Codebook::upload(DeviceSession& s) const {
     if ((int)d.word_class.size() == d.numWords()) s.check(ismhip_codebook_set_word_class(s.ctx, m_dev, d.word_class.data()), "ismhip_codebook_set_word_class");
     if (d.word_keypoint.size() == (size_t)d.numWords() * 3)       // Codeword::getFeaturePosition: Vote::keypoint_training (voting.cpp:71)
         s.check(ismhip_codebook_set_word_keypoint(s.ctx, m_dev, d.word_keypoint.data()), "ismhip_codebook_set_word_keypoint");
+    if (m_binary_words && s.knn_binary_route) {
+        // BSHOT codewords are zeros and ones unless a k-means clustering averaged them (ISMHIP_ERR_INVALID) or the codebook outgrows the
+        // 32-bit key (ISMHIP_ERR_UNSUPPORTED): those keep the float search, which gives the same exact answers
+        const int rc = ismhip_codebook_make_binary(s.ctx, m_dev);
+        if (rc != ISMHIP_OK && rc != ISMHIP_ERR_INVALID && rc != ISMHIP_ERR_UNSUPPORTED) s.check(rc, "ismhip_codebook_make_binary");
+    }
     m_dirty = false;
 }
 
+// the metrics whose BSHOT searches take ismhip_knn_binary (bit ISMHIP_METRIC_*): those for which its slowest repetition beat the float
+// route's fastest (tools/bshot_time.py)
+static const unsigned KNN_BINARY_ROUTE_METRICS = (1u << ISMHIP_METRIC_L2SQ) | (1u << ISMHIP_METRIC_CHI2);
 int ActivationStrategyKNN::activateKNN(DeviceSession& s, const ismhip_codebook* codewords, const DeviceFeatures& f, int metric,
                                        int32_t* idx_out, float* dist_out, const float* desc) const {     // activation_strategy_knn.h:41-126
     if (m_k > ISMHIP_KNN_LARGE_K_MAX) throw RuntimeException("KNN activation with K > 1024 (ISMHIP_KNN_LARGE_K_MAX) is not built");
@@ -548,6 +566,9 @@ int ActivationStrategyKNN::activateKNN(DeviceSession& s, const ismhip_codebook* 
         s.check(ismhip_knn_ratio(s.ctx, codewords, metric, (int)f.n, desc, m_distance_ratio_threshold, idx_out, dist_out), "ismhip_knn_ratio");
     else if (m_k > 16)
         s.check(ismhip_knn_large_k(s.ctx, codewords, metric, (int)f.n, desc, m_k, idx_out, dist_out), "ismhip_knn_large_k");
+    else if (ismhip_codebook_has_binary(codewords) == 1 && (KNN_BINARY_ROUTE_METRICS >> metric & 1))
+        // a speed route like the library's own gates: both functors are the Hamming distance on 0/1 rows, the answers are bit-identical
+        s.check(ismhip_knn_binary(s.ctx, codewords, (int)f.n, desc, m_k, idx_out, dist_out), "ismhip_knn_binary");
     else
         s.check(ismhip_knn(s.ctx, codewords, metric, (int)f.n, desc, m_k, idx_out, dist_out), "ismhip_knn");
     return m_k;
@@ -1128,7 +1149,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesSHORTSHOT::getTypeStatic()) return new FeaturesSHORTSHOT();
     if (type == FeaturesSHORTCSHOT::getTypeStatic()) return new FeaturesSHORTCSHOT();
     if (type == FeaturesCospair::getTypeStatic()) return new FeaturesCospair();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)");
+    if (type == FeaturesBSHOT::getTypeStatic()) return new FeaturesBSHOT();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
@@ -1652,6 +1674,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     LapTimer stage{m_processing_times};
     LOG_INFO("activating codewords and casting votes");
     m_voting->clear();
+    m_codebook->setBinaryWords(m_feature_descriptor->getType() == FeaturesBSHOT::getTypeStatic());
     m_codebook->castVotes(s, *f, metric(), *m_voting);
     s.sync();
     m_last_detect = f;

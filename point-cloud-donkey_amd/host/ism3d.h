@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   Voting, VotingMeanShift, Vote, VotingMaximum voting/voting.h:35, voting_mean_shift.cpp, voting_maximum.h:25-88
@@ -216,6 +216,9 @@ protected:
 ISM3D_FEATURE(FeaturesSHOT, "SHOT", 352, false)
 ISM3D_FEATURE(FeaturesCSHOT, "CSHOT", 1344, true)
 ISM3D_FEATURE(FeaturesFPFH, "FPFH", 33, false)
+// features/features_bshot.{h,cpp}: SHOT-352 binarised in groups of four (getBinaryVector :109-157); rows of zeros and ones. The frames and
+// centerDist are FeaturesSHOT's. A NaN SHOT row becomes 352 ones and stays in the batch, as in the reference.
+ISM3D_FEATURE(FeaturesBSHOT, "BSHOT", ISMHIP_BSHOT_DIM, false)
 // features/features_short_shot.{h,cpp}: the generalised Short SHOT. Not an ISM3D_FEATURE: its length follows the spherical grid.
 class FeaturesSHORTSHOT : public Features {
 public:
@@ -426,6 +429,8 @@ public:
     int getDim() const { return m_data.dim; }
     const CodebookData& data() const { return m_data; }
     void setData(const CodebookData& d) { m_data = d; m_dirty = true; }
+    // the codewords are rows of zeros and ones (Features type "BSHOT"): upload() then asks for the binary image of the exact integer search
+    void setBinaryWords(bool b) { if (b != m_binary_words) { m_binary_words = b; m_dirty = true; } }
     const ActivationStrategy* getActivationStrategy() const { return m_activationStrategy.get(); }
     void save(BoostBinaryOArchive& oa) const;     // Codebook::iSaveData (codebook.cpp:739-761)
     bool load(BoostBinaryIArchive& ia);           // Codebook::iLoadData (codebook.cpp:763-950)
@@ -441,6 +446,7 @@ private:
     CodebookData m_data;
     mutable std::vector<int32_t> m_partial_cols;    // kept descriptor columns when UsePartialShot (empty otherwise)
     mutable bool m_dirty = true;
+    bool m_binary_words = false;
     mutable ismhip_codebook* m_dev = nullptr;
     mutable DeviceSession* m_dev_session = nullptr;
 };
@@ -549,6 +555,7 @@ public:
     // diagnostics (tests): a timer or counter of the device library's context (ismhip_timer_get); 0 before the first device call
     double deviceTimer(const std::string& name) const;
     const Voting* getVoting() const { return m_voting.get(); }
+    const Features* getFeatures() const { return m_feature_descriptor.get(); }
     void setSignalsState(bool) {}
     void setLogging(bool l) { m_logging = l; }
     void setLabels(std::map<unsigned, std::string>& c, std::map<unsigned, std::string>& i, std::map<unsigned, unsigned>& m) { m_class_labels = c; m_instance_labels = i; m_instance_to_class_map = m; }

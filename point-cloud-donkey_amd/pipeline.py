@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -97,7 +97,7 @@ class IsmConfig:
             return self.short_shot_grid[0]
         if self.feature == "SHORT_CSHOT":
             return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
-        return {"SHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM}[self.feature]
+        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM}[self.feature]
 
     @property
     def metric(self):
@@ -200,6 +200,9 @@ class Recognizer:
         lrf = capi.LRF_TYPES[c.lrf_type](ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.lrf_radius)   # Features::operator() always computes LRFs
         if c.feature == "SHOT":
             desc, cnt = capi.shot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
+        elif c.feature == "BSHOT":
+            # rows of zeros and ones; a NaN SHOT row becomes 352 ones and passes the NaN filter below, as in the reference
+            desc, cnt = capi.bshot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
         elif c.feature == "CSHOT":
             desc, cnt = capi.cshot1344(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, b.kp_rgba, lrf, c.radius, want_counts=True)
         elif c.feature in ("SHORT_SHOT", "SHORT_CSHOT"):
@@ -220,7 +223,7 @@ class Recognizer:
             # no frame enters the descriptor either; the reference computes and filters by them for every feature type
             desc, cnt = capi.cospair(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
