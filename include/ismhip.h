@@ -92,7 +92,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -571,6 +571,43 @@ int  ismhip_train_activate_lists(ismhip_ctx* ctx, int metric, int n, int dim, co
                                  const uint32_t* act_offsets, const int32_t* act_idx, int64_t n_act, int n_classes,
                                  int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
                                  float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out);
+
+/* ---- training-side feature ranking ("codebook cleaning"): FeatureRanking::operator() (feature_ranking/feature_ranking.cpp:37-118),
+ *      the step of ImplicitShapeModel::train() between feature extraction and clustering (implicit_shape_model.cpp:437-443).
+ *      ismhip_rank_scores is iComputeScores of one subclass, ismhip_rank_select is rankFeaturesWithScores +
+ *      extractSubsetFromRankedList (feature_ranking.cpp:121-203). Every search is exact (FLANNExactMatch semantics) and uses the
+ *      chi-square functor whatever the model's DistanceType says, as the reference's hard-coded flann::ChiSquareDistance does
+ *      (feature_ranking.cpp:35). Neighbour lists are in ismhip_knn's (distance, row) order. */
+#define ISMHIP_RANK_KNN_ACTIVATION 0   /* ranking_knn_activation.cpp:53-110 (UseFeaturePosition false) */
+#define ISMHIP_RANK_INCREMENTAL    1   /* ranking_incremental.cpp:51-84 */
+#define ISMHIP_RANK_STRANGENESS    2   /* ranking_strangeness.cpp:58-93 */
+#define ISMHIP_RANK_NAIVE_BAYES    3   /* ranking_naive_bayes.cpp:52-79, feature_ranking.cpp:346-363 */
+/* desc: device [n*dim], CLASS-MAJOR as in ismhip_train_activate; class_offsets_h: host [n_classes+1], from 0 to n, ascending (empty
+ * classes allowed); score_out: device [n]. With m = min(K, n) valid neighbours per query:
+ *   KNN_ACTIVATION  K = k_search + 1 in all features; each of the first m - 1 neighbours (the LAST one is dropped, not the self match)
+ *                   gets 1 (increment_type 1, and 0 which means 1), 1 / (d + 1) (2) or expf(d) (3) added to its score
+ *   INCREMENTAL     the same search; neighbour j < m - 1 gets d_j - d_(j+1)
+ *   both are float sums in the reference's sequential order (queries ascending, then rank), without float atomics: two calls give the
+ *   same bits
+ *   STRANGENESS     per class c the float sum, ascending, of the distances to the feature's k_search nearest rows of class c (fewer in a
+ *                   smaller class, 0 for an empty one); score = own-class sum / smallest sum of the other classes
+ *   NAIVE_BAYES     num_pos = those of the k_search nearest own-class rows with d < dist_threshold, num_neg = the same count over the
+ *                   k_search nearest rows of all other classes together (ties in global row order);
+ *                   score = (num_pos / num_current) / ((num_pos + num_neg) / (num_current + num_other)) in float, in that order
+ * ISMHIP_ERR_INVALID, with score_out unwritten: an unknown type, k_search < 1, increment_type outside 0 .. 3 (KNN_ACTIVATION), offsets that
+ * do not ascend from 0 to n, STRANGENESS with fewer than two non-empty classes (the reference would index past the end).
+ * ISMHIP_ERR_UNSUPPORTED: K > ISMHIP_KNN_LARGE_K_MAX, dim > ISMHIP_SHORT_CSHOT_MAX_DIM. K > 16 searches through ismhip_knn_large_k.
+ * Timers "rank_scores" (the searches included) and, of it, "rank_score_kernels" (everything after the searches); counter "rank_launches": calls of the two entries that reached the device. Synchronises. */
+int  ismhip_rank_scores(ismhip_ctx* ctx, int type, int n, int dim, const float* desc, int n_classes, const uint32_t* class_offsets_h,
+                        int k_search, float dist_threshold, int increment_type, float* score_out);
+/* Per class of size s: min_index = (float)s * extract_offset clamped at 0, max_index = (float)s * (factor + extract_offset) clamped at
+ * s; the feature of ascending rank j is kept iff (float)j >= min_index && (float)j < max_index. The reference sorts with an unstable
+ * std::sort on the score alone; here the order is DEFINED: ascending by (score, index within the class), -0 equal to +0, NaN after
+ * +inf. score: device [n]; keep_out: device [n], 1 = kept; n_keep_h_out: host [n_classes]. Two order statistics per class by a radix
+ * select over the 64-bit key (ordered score bits, index): linear in the class size. ISMHIP_ERR_INVALID, outputs unwritten: offsets
+ * that do not ascend from 0 to n. Timer "rank_select". Synchronises. */
+int  ismhip_rank_select(ismhip_ctx* ctx, int n, int n_classes, const uint32_t* class_offsets_h, const float* score,
+                        float factor, float extract_offset, uint8_t* keep_out, uint32_t* n_keep_h_out);
 
 /* ---- k-means codebook clustering: ClusteringKMeans::cluster (clustering/clustering_kmeans.h:53-131) =
  *      flann::hierarchicalClustering with branching == the cluster count (one level of Lloyd k-means: centre chooser, then

@@ -33,6 +33,7 @@ EXPORTS = [
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
+    "ismhip_rank_scores", "ismhip_rank_select",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -847,6 +848,34 @@ def kmeans(ctx, metric, desc, n_clusters, max_iterations=1000, centers_init="FLA
                                   C.c_int(CENTERS_INIT[centers_init] if isinstance(centers_init, str) else int(centers_init)), C.c_ulonglong(seed),
                                   _p(centers), _p(assign), _p(dist), C.byref(m), C.byref(it)), "ismhip_kmeans")
     return centers[:m.value], assign, dist, it.value
+
+
+RANK_TYPES = {"KNNActivation": 0, "Incremental": 1, "Strangeness": 2, "NaiveBayes": 3}
+
+
+def rank_scores(ctx, rank_type, desc, class_offsets, k_search=10, dist_threshold=0.1, increment_type=0, out=None):
+    """FeatureRanking::iComputeScores of one subclass on the device (desc [n, dim] class-major, class_offsets host [n_classes + 1])
+    -> score [n] device float32 (`out` when given: an error leaves it unwritten)"""
+    torch = _torch()
+    n, dim = desc.shape
+    off = _u32(class_offsets)
+    score = torch.empty(n, dtype=torch.float32, device=desc.device) if out is None else out
+    t = RANK_TYPES[rank_type] if isinstance(rank_type, str) else int(rank_type)
+    ctx.check(lib().ismhip_rank_scores(ctx._h, C.c_int(t), C.c_int(n), C.c_int(dim), _p(desc), C.c_int(len(off) - 1), _p(off), C.c_int(k_search),
+                                       C.c_float(dist_threshold), C.c_int(increment_type), _p(score)), "ismhip_rank_scores")
+    return score
+
+
+def rank_select(ctx, score, class_offsets, factor=0.75, extract_offset=0.0, out=None):
+    """rankFeaturesWithScores + extractSubsetFromRankedList -> (keep [n] device uint8, n_keep host [n_classes] uint32); `out` =
+    (keep, n_keep) buffers to write into (an error leaves them unwritten)"""
+    torch = _torch()
+    n = score.shape[0]
+    off = _u32(class_offsets)
+    keep, n_keep = out if out is not None else (torch.empty(n, dtype=torch.uint8, device=score.device), np.zeros(len(off) - 1, np.uint32))
+    ctx.check(lib().ismhip_rank_select(ctx._h, C.c_int(n), C.c_int(len(off) - 1), _p(off), _p(score), C.c_float(factor), C.c_float(extract_offset),
+                                       _p(keep), _p(n_keep)), "ismhip_rank_select")
+    return keep, n_keep
 
 
 PARTIAL_SHOT_SIGNATURES = {          # Codebook::getSignatureMask (codebook/codebook.cpp:952-1036): kept signatures of the 32

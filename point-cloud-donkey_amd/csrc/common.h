@@ -179,13 +179,14 @@ struct ismhip_ctx {
     float knn_lk_seed_scale = 1.0f;   // env ISMHIP_KNN_LARGE_K_SEED_SCALE: multiplies the fast path's seed (tests: a wrong seed costs time, never correctness)
     uint32_t knn_lk_stats[3] = {0, 0, 0};   // last ismhip_knn_large_k: queries {certified by the fast path, retried, answered by the exact scan}
     uint32_t knn_binary_launches = 0; // ismhip_knn_binary calls that searched (counter "knn_binary_launches"; tests of the host route)
+    uint32_t rank_launches = 0;       // ismhip_rank_scores / ismhip_rank_select calls that reached the device (counter "rank_launches"; tests of the host route)
     int knn_mode = 0;            // env ISMHIP_KNN_MODE = f16 (0, default) | bf16x3 (1) | f32 (2): squared-L2 candidate kernel (A/B runs, tests)
 };
 
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN
 };
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);

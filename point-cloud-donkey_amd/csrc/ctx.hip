@@ -190,6 +190,7 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
     resolve_timers(ctx);
     if (std::strcmp(name, "knn_seed_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_seed_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_binary_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_binary_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    if (std::strcmp(name, "rank_launches") == 0) { if (ms_out) *ms_out = (double)ctx->rank_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_pca_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_pca_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_overflow_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_overflow; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_threshold_mfma_launches") == 0) { if (ms_out) *ms_out = (double)ctx->knn_thr_mfma_launches; if (launches_out) *launches_out = 1; return ISMHIP_OK; }

@@ -1177,6 +1177,71 @@ template <> Clustering* Factory<Clustering>::createByType(const std::string& typ
     throw RuntimeException("clustering type \"" + type + "\" is not built (built: None, KMeansCount, KMeansFactor, KMeansThumbRule, KMeansHartigan)");
 }
 
+template <> FeatureRanking* Factory<FeatureRanking>::createByType(const std::string& type) {    // ranking_factory.h
+    if (type == RankingUniform::getTypeStatic()) return new RankingUniform();
+    if (type == RankingKnnActivation::getTypeStatic()) return new RankingKnnActivation();
+    if (type == RankingIncremental::getTypeStatic()) return new RankingIncremental();
+    if (type == RankingStrangeness::getTypeStatic()) return new RankingStrangeness();
+    if (type == RankingNaiveBayes::getTypeStatic()) return new RankingNaiveBayes();
+    throw RuntimeException("feature ranking type \"" + type + "\" is not built (built: Uniform, KNNActivation, Incremental, Strangeness, NaiveBayes)");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// FeatureRanking (feature_ranking/*.cpp): scores and selection run on the device (ismhip_rank_scores, ismhip_rank_select)
+// ---------------------------------------------------------------------------------------------------------------
+FeatureRanking::FeatureRanking() {                 // feature_ranking.cpp:21-29
+    addParameter(m_k_search, "KSearch", 10);
+    addParameter(m_dist_thresh, "DistanceThreshold", 0.1f);
+    addParameter(m_factor, "Factor", 0.75f);
+    addParameter(m_extract_list, "ExtractFromList", std::string("invalid"));
+    addParameter(m_extract_offset, "ExtractOffset", 0.0f);
+}
+void FeatureRanking::iPostInitConfig() {           // :135-148, applied when the configuration is read instead of at the first ranking
+    if (m_extract_list == "invalid") return;
+    LOG_WARN("Config parameter \"ExtractFromList\" is deprecated. Use \"ExtractOffset\" instead!");
+    LOG_WARN("For now, the given value for \"ExtractFromList\" will be automatically converted.");
+    if (m_extract_list == "front") m_extract_offset = 0.0f;
+    if (m_extract_list == "center" || m_extract_list == "middle") m_extract_offset = 0.5 * (1 - m_factor);
+    if (m_extract_list == "back") m_extract_offset = 1.0 - m_factor;
+}
+RankingKnnActivation::RankingKnnActivation() {     // ranking_knn_activation.cpp:15-19
+    addParameter(m_use_feature_position, "UseFeaturePosition", false);
+    addParameter(m_score_increment_type, "ScoreIncrementType", 0);
+}
+void RankingKnnActivation::iPostInitConfig() {
+    FeatureRanking::iPostInitConfig();
+    if (m_use_feature_position)
+        throw RuntimeException("feature ranking KNNActivation with UseFeaturePosition true is not built: the training batch carries no centerDist "
+                               "(built: Uniform, KNNActivation without UseFeaturePosition, Incremental, Strangeness, NaiveBayes)");
+}
+int RankingKnnActivation::incrementType() {        // :88-95
+    m_score_increment_type = m_score_increment_type == 0 ? 1 : m_score_increment_type;
+    if (m_score_increment_type > 3 || m_score_increment_type < 1) {
+        LOG_WARN("Invalid score increment type: " << m_score_increment_type << "! Using type 1 instead.");
+        m_score_increment_type = 1;
+    }
+    return m_score_increment_type;
+}
+std::vector<uint8_t> FeatureRanking::operator()(DeviceSession& s, const DeviceFeatures& f, const std::vector<uint32_t>& class_offsets) {
+    std::vector<uint8_t> mask;
+    if (f.n == 0 || class_offsets.size() < 2) return mask;
+    const int n_classes = (int)class_offsets.size() - 1;
+    LOG_INFO("starting " << getType() << " ranking");
+    if (m_k_search < 1) throw BadParamExceptionType<int>("invalid feature ranking KSearch", m_k_search);
+    DevBuf score, keep;
+    score.reserve((size_t)f.n * 4); keep.reserve(f.n);
+    s.check(ismhip_rank_scores(s.ctx, deviceType(), (int)f.n, f.dim, f.desc.as<float>(), n_classes, class_offsets.data(), m_k_search, m_dist_thresh,
+                               incrementType(), score.as<float>()), "ismhip_rank_scores");
+    std::vector<uint32_t> n_keep((size_t)n_classes, 0u);
+    s.check(ismhip_rank_select(s.ctx, (int)f.n, n_classes, class_offsets.data(), score.as<float>(), m_factor, m_extract_offset, keep.as<uint8_t>(),
+                               n_keep.data()), "ismhip_rank_select");
+    s.d2h(mask, keep, f.n);
+    size_t kept = 0;
+    for (uint32_t k : n_keep) kept += k;
+    LOG_INFO("input features: " << f.n << ", output features: " << kept << ", output ratio: " << (((float)kept) / (f.n)));   // :113-115
+    return mask;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Clustering (clustering/*.cpp): k-means runs on the device (ismhip_kmeans)
 // ---------------------------------------------------------------------------------------------------------------
@@ -1302,7 +1367,7 @@ Json ImplicitShapeModel::iChildConfigsToJson() const {   // :1070-1083
     if (!m_global_features_cfg.isNull()) c["GlobalFeatures"] = m_global_features_cfg;
     c["Clustering"] = m_clustering ? m_clustering->configToJson() : Json::parse("{\"Type\":\"None\"}");
     c["Voting"] = m_voting->configToJson();
-    c["FeatureWeighting"] = m_feature_ranking_cfg.isNull() ? Json::parse("{\"Type\":\"Uniform\"}") : m_feature_ranking_cfg;
+    c["FeatureWeighting"] = m_feature_ranking ? m_feature_ranking->configToJson() : Json::parse("{\"Type\":\"Uniform\"}");
     return c;
 }
 bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
@@ -1315,15 +1380,14 @@ bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
     m_voting.reset(Factory<Voting>::create(*vo));
     if (m_voting && m_voting->refineModelRequested())
         throw RuntimeException("Voting.RansacRefineModel is not built (PCL's sac.refineModel is not restated); RansacVoteFiltering runs without it");
-    m_clustering.reset(Factory<Clustering>::create(*cl)); m_feature_ranking_cfg = *fw;
+    m_clustering.reset(Factory<Clustering>::create(*cl));
+    m_feature_ranking.reset(Factory<FeatureRanking>::create(*fw));
     if (const Json* gf = c.find("GlobalFeatures")) m_global_features_cfg = *gf;
-    const Json* rt = fw->find("Type");
-    if (!rt || rt->str != "Uniform") throw RuntimeException("feature ranking type \"" + (rt ? rt->str : std::string()) + "\" is out of scope (built: Uniform)");
     if (m_use_smoothing || m_use_voxel_filtering) throw RuntimeException("point cloud pre-filters smoothing (UseSmoothing) and voxel filtering (UseVoxelFiltering) are not built");
     if (m_use_sor && (m_sor_mean_k < 1 || m_sor_mean_k > ISMHIP_SOR_MAX_MEAN_K))
         throw RuntimeException("OutlierRemovalMeanK " + std::to_string(m_sor_mean_k) + " is not built (built: 1 .. " + std::to_string(ISMHIP_SOR_MAX_MEAN_K) + ")");
     if (m_use_ror && !(m_ror_radius > 0.f)) throw BadParamExceptionType<float>("invalid outlier removal radius", m_ror_radius);
-    return m_codebook && m_keypoints_detector && m_feature_descriptor && m_voting && m_clustering;
+    return m_codebook && m_keypoints_detector && m_feature_descriptor && m_voting && m_clustering && m_feature_ranking;
 }
 
 void ImplicitShapeModel::iSaveData(std::ostream& os) const {      // :1144-1179, as a Boost binary archive (boost_archive.h)
@@ -1642,6 +1706,26 @@ void ImplicitShapeModel::train() {                // :252-500
         }
     }
     all->dim = D; all->n = (uint32_t)fclass.size();
+    if (m_feature_ranking && m_feature_ranking->ranks() && all->n > 0) {     // :437-443: rank, then cluster and activate the kept features only
+        LOG_INFO("ranking features");
+        std::vector<uint32_t> class_off((size_t)m_n_classes + 1, 0u);       // the features are class-major: the ranges of the class ids
+        for (unsigned c : fclass) ++class_off[c + 1];
+        for (int c = 0; c < m_n_classes; ++c) class_off[c + 1] += class_off[c];
+        DeviceSession::h2d(all->desc, hdesc);
+        const std::vector<uint8_t> mask = (*m_feature_ranking)(s, *all, class_off);
+        auto filter = [&](auto& v, size_t width) {                          // keeps the rows of the mask, in order
+            size_t o = 0;
+            for (size_t i = 0; i < mask.size(); ++i) {
+                if (!mask[i]) continue;
+                if (o != i) std::copy(v.begin() + i * width, v.begin() + (i + 1) * width, v.begin() + o * width);
+                ++o;
+            }
+            v.resize(o * width);
+        };
+        filter(hdesc, (size_t)D); filter(hlrf, 9); filter(hkx, 1); filter(hky, 1); filter(hkz, 1);
+        filter(fclass, 1); filter(finst, 1); filter(fmodel, 1); filter(fcenter, 1); filter(fbox, 1);
+        all->n = (uint32_t)fclass.size();
+    }
     DeviceSession::h2d(all->desc, hdesc); DeviceSession::h2d(all->lrf, hlrf); DeviceSession::h2d(all->kx, hkx); DeviceSession::h2d(all->ky, hky); DeviceSession::h2d(all->kz, hkz);
     LOG_INFO("activating codewords with " << all->n << " training features");
     m_voting->forwardBoxesAndRadii(box_sizes, object_radii);     // :433: bandwidth hints per class, persisted with the model

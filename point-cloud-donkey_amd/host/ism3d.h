@@ -7,6 +7,7 @@
 //   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
+//   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
 //   Voting, VotingMeanShift, Vote, VotingMaximum voting/voting.h:35, voting_mean_shift.cpp, voting_maximum.h:25-88
 //   ImplicitShapeModel                           implicit_shape_model.h:82-330
 // What differs by design: PCL/Eigen/Boost types are replaced by plain SoA containers, every plugin works on a BATCH of
@@ -396,6 +397,56 @@ protected:
     int m_maxK;
 };
 
+// ---- FeatureRanking (feature_ranking/feature_ranking.h, ranking_factory.h) --------------------------------------------------
+// operator() is the reference's (feature_ranking.cpp:37-118) on a class-major feature batch: scores (ismhip_rank_scores), then the
+// per-class window of the ranked list (ismhip_rank_select); it returns the keep mask, 1 = the feature stays. All searches are exact
+// and chi-square, whatever DistanceType says (feature_ranking.cpp:35). "Similarity" is not built.
+class FeatureRanking : public JSONObject {
+public:
+    FeatureRanking();
+    virtual ~FeatureRanking() {}
+    // class_offsets: [n_classes + 1] ranges of the classes in f (ascending class ids, empty classes allowed)
+    std::vector<uint8_t> operator()(DeviceSession& s, const DeviceFeatures& f, const std::vector<uint32_t>& class_offsets);
+    virtual bool ranks() const { return true; }        // false: Uniform, every feature stays and nothing is launched
+    float getExtractOffset() const { return m_extract_offset; }
+protected:
+    void iPostInitConfig() override;                   // the deprecated ExtractFromList -> ExtractOffset (:135-148)
+    virtual int deviceType() const = 0;                // ISMHIP_RANK_*
+    virtual int incrementType() { return 0; }
+    int m_k_search; float m_dist_thresh, m_factor; std::string m_extract_list; float m_extract_offset;
+};
+class RankingUniform : public FeatureRanking {         // ranking_uniform.cpp
+public:
+    static std::string getTypeStatic() { return "Uniform"; }
+    std::string getType() const override { return getTypeStatic(); }
+    bool ranks() const override { return false; }
+protected:
+    int deviceType() const override { return -1; }
+};
+class RankingKnnActivation : public FeatureRanking {   // ranking_knn_activation.cpp
+public:
+    RankingKnnActivation();
+    static std::string getTypeStatic() { return "KNNActivation"; }
+    std::string getType() const override { return getTypeStatic(); }
+protected:
+    void iPostInitConfig() override;                   // + UseFeaturePosition true is refused (the training batch carries no centerDist)
+    int deviceType() const override { return ISMHIP_RANK_KNN_ACTIVATION; }
+    int incrementType() override;                      // :88-95: 0 means 1, anything outside 1 .. 3 becomes 1 with a warning
+    bool m_use_feature_position; int m_score_increment_type;
+};
+#define ISM3D_RANKING(NAME, TYPESTR, DEVTYPE)                                                        \
+    class NAME : public FeatureRanking {                                                             \
+    public:                                                                                          \
+        static std::string getTypeStatic() { return TYPESTR; }                                       \
+        std::string getType() const override { return getTypeStatic(); }                             \
+    protected:                                                                                       \
+        int deviceType() const override { return DEVTYPE; }                                          \
+    };
+ISM3D_RANKING(RankingIncremental, "Incremental", ISMHIP_RANK_INCREMENTAL)      // ranking_incremental.cpp
+ISM3D_RANKING(RankingStrangeness, "Strangeness", ISMHIP_RANK_STRANGENESS)      // ranking_strangeness.cpp
+ISM3D_RANKING(RankingNaiveBayes, "NaiveBayes", ISMHIP_RANK_NAIVE_BAYES)        // ranking_naive_bayes.cpp
+#undef ISM3D_RANKING
+
 struct CodebookData {          // host copy of what Codebook::iSaveData persists (flattened CodewordDistributions)
     int dim = 0;
     std::vector<float> words, word_weight;
@@ -605,7 +656,8 @@ private:
     std::unique_ptr<Features> m_feature_descriptor;
     std::unique_ptr<Voting> m_voting;
     std::unique_ptr<Clustering> m_clustering;
-    Json m_feature_ranking_cfg, m_global_features_cfg;
+    std::unique_ptr<FeatureRanking> m_feature_ranking;
+    Json m_global_features_cfg;
     std::map<unsigned, std::vector<std::shared_ptr<PointCloud>>> m_training_clouds;     // class -> models
     std::map<unsigned, std::vector<unsigned>> m_training_instances;
     std::map<unsigned, std::string> m_class_labels, m_instance_labels;
