@@ -92,7 +92,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -286,6 +286,44 @@ int  ismhip_cospair(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* 
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
+
+/* ---- global (region) descriptors: the global features of Voting.UseGlobalFeatures. A REGION is (object index, selection centre,
+ *      selection radius): region_obj[n_regions] (device int32), region_center[n_regions*3], region_radius[n_regions] (device float).
+ *      A NEGATIVE selection radius selects the object's finite points as a whole; otherwise those with d2 < (float)((double)radius *
+ *      radius) to the centre, d2 the unfused float (dx*dx + dy*dy) + dz*dz (the rule of every ball sweep of this library). Several
+ *      regions may name the same object, in any order; a region whose object index is outside [0, n_obj) selects nothing.
+ *      Per region (all outputs device, all written): n_sel_out[n_regions] the number of selected points; centroid_out[n_regions*3] their
+ *      centroid (pcl::compute3DCentroid: double sums, one division, cast to float); radius_out[n_regions] the largest distance from that
+ *      centroid to a selected point (Features::getCloudRadius, features.cpp:128-151, the arithmetic of ismhip_cloud_radii); lrf9_out
+ *      [n_regions*9] the SHOT frame (ismhip_shot_lrf's arithmetic and layout) of ONE keypoint, that centroid, with that radius over the
+ *      selected points -- a sign tie goes to the five median neighbours by (distance, original index) whatever the region's size;
+ *      desc_out one row per region. For a whole-object region centroid and radius are bit-equal to ismhip_cloud_centroids /
+ *      ismhip_cloud_radii. n_sel = 0: NaN centroid, radius 0, NaN frame, NaN row. Fewer than five frame neighbours (selected points
+ *      inside the ball (centroid, radius) other than the centroid itself): NaN frame and NaN row. One workgroup per region, no float
+ *      atomics: every output is bitwise reproducible. Asynchronous.
+ *
+ * ismhip_global_short_shot: FeaturesSHORTSHOTGlobal::compute_descriptor (features/features_short_shot_global.cpp:94-165) on the grid of
+ * configureSphericalGrid (:168-249; the caller maps ShortShotDims / ShortShotBinType to the three bin counts). desc_out[n_regions * D],
+ * D = r_bins * e_bins * a_bins. Every selected point with d2 < (float)((double)R * R) to the centroid (R = radius_out) and (double)d2 >
+ * 1e-15: v = p - centroid in float; x_l = (double)((v.x*X.x + v.y*X.y) + v.z*X.z) in float, unfused, in this order (as ismhip_short_shot),
+ * likewise y_l, z_l; then in double r = sqrt((x_l^2 + y_l^2) + z_l^2), theta = acos(z_l / r) * 57.29578, phi = atan2(y_l, x_l) * 57.29578;
+ * bin_r = int((r_bins * r) / (double)R), or with log_radius int(((r_bins - 1) * (log(r) - log(min_radius))) / log((double)R / min_radius) + 1)
+ * -- min_radius is the parameter ShortShotMinRadius ITSELF, an absolute length, and no point is skipped for lying below it;
+ * bin_theta = int((e_bins * theta) / 180), bin_phi = int((a_bins * (phi + 180)) / 360); r clamped to [0, r_bins - 1], theta and phi from
+ * above only; +1 at bin_r + bin_theta * r_bins + bin_phi * r_bins * e_bins: NO interpolation (this is not ismhip_short_shot's arithmetic).
+ * int() of a NaN is taken as INT_MIN (x86-64): bin 0 for r, no count for an angle. The row is count / sqrt(sum count^2) in double, cast
+ * to float; no counted point gives 0 / 0, a NaN row. count_out: device [n_regions * D] or NULL, the integer histogram (0 for a NaN frame).
+ * Refused as ismhip_short_shot refuses: a bin count < 1 (ISMHIP_ERR_INVALID), more than ISMHIP_SHORT_SHOT_MAX_DIM bins
+ * (ISMHIP_ERR_UNSUPPORTED), log_radius without a finite min_radius > 0 (ISMHIP_ERR_INVALID). Timer "global_short_shot". */
+int  ismhip_global_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                              const float* region_radius, double min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
+                              uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out, uint32_t* count_out);
+/* ismhip_global_shot352: FeaturesSHOTGlobal::iComputeDescriptors (features/features_shot_global.cpp:27-99): SHOT-352 at the centroid with
+ * descriptor radius and frame radius both R, over the selected points -- the per-neighbour arithmetic, the 2^-28 fixed-point histogram
+ * and the normalisation of ismhip_shot352 (the same functions); fewer than five descriptor neighbours: NaN row. desc_out[n_regions*352].
+ * Timer "global_shot352". */
+int  ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                           const float* region_radius, uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out);
 
 /* ---- keypoints (the step in front of the path): KeypointsVoxelGrid::iComputeKeypoints
  *      (keypoints/keypoints_voxel_grid.cpp:30-46) -> pcl::VoxelGrid<PointXYZRGB> with a cubic leaf. Per object the

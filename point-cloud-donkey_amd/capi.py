@@ -33,7 +33,7 @@ EXPORTS = [
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
-    "ismhip_rank_scores", "ismhip_rank_select",
+    "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -381,6 +381,64 @@ def cospair(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False, wa
               "ismhip_cospair")
     extra = [t for t in (cnt, lev, snap) if t is not None]
     return (out, *extra) if extra else out
+
+
+GLOBAL_SHORT_SHOT_AUTO_BINS = dict(SHORT_SHOT_AUTO_BINS)
+GLOBAL_SHORT_SHOT_AUTO_BINS[64] = (4, 2, 8)       # the one size where the global grid differs from the local one (features_short_shot_global.cpp:197-202)
+
+
+def global_short_shot_grid(dims=32, bin_type="auto", bins=(1, 1, 8)):
+    """FeaturesSHORTSHOTGlobal::configureSphericalGrid (features_short_shot_global.cpp:168-249) -> (dims, (r, e, a)); an unknown size or
+    bin type falls back to 32 / (2, 2, 8) as the reference does (with its LOG_ERROR)"""
+    if bin_type == "manual":
+        r, e, a = (int(b) for b in bins)
+        return r * e * a, (r, e, a)
+    if bin_type == "auto" and int(dims) in GLOBAL_SHORT_SHOT_AUTO_BINS:
+        return int(dims), GLOBAL_SHORT_SHOT_AUTO_BINS[int(dims)]
+    return 32, (2, 2, 8)
+
+
+def _regions(cloud, region_obj, region_center, region_radius, dev):
+    """the three region arrays on the device; region_center None / region_radius None: whole objects"""
+    torch = _torch()
+    obj = torch.as_tensor(np.ascontiguousarray(np.asarray(region_obj, dtype=np.int32)), device=dev)
+    n = int(obj.shape[0])
+    cen = np.zeros((n, 3), np.float32) if region_center is None else np.ascontiguousarray(np.asarray(region_center, dtype=np.float32)).reshape(n, 3)
+    rad = np.full((n,), -1.0, np.float32) if region_radius is None else np.ascontiguousarray(np.asarray(region_radius, dtype=np.float32)).reshape(n)
+    return n, obj, torch.as_tensor(cen, device=dev), torch.as_tensor(rad, device=dev)
+
+
+def _global_outputs(n, dim, dev):
+    torch = _torch()
+    return dict(n_sel=torch.empty((n,), dtype=torch.int32, device=dev), centroid=torch.empty((n, 3), dtype=torch.float32, device=dev),
+                radius=torch.empty((n,), dtype=torch.float32, device=dev), lrf=torch.empty((n, 9), dtype=torch.float32, device=dev),
+                desc=torch.empty((n, dim), dtype=torch.float32, device=dev))
+
+
+def global_short_shot(ctx, cloud, dev, region_obj, region_center=None, region_radius=None, bins=(2, 2, 8), min_radius=0.1, log_radius=False,
+                      want_counts=False):
+    """ismhip_global_short_shot on regions (object, centre, radius; radius < 0 or None = the whole object) -> dict of device tensors n_sel [n],
+    centroid [n, 3], radius [n], lrf [n, 9], desc [n, r * e * a] and, with want_counts, counts [n, r * e * a] (int32)"""
+    torch = _torch()
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    r, e, a = (int(b) for b in bins)
+    out = _global_outputs(n, r * e * a if min(r, e, a) > 0 else 0, dev)
+    if want_counts:
+        out["counts"] = torch.empty_like(out["desc"], dtype=torch.int32)
+    ctx.check(lib().ismhip_global_short_shot(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), C.c_double(min_radius),
+                                             C.c_int(1 if log_radius else 0), C.c_int(r), C.c_int(e), C.c_int(a), _p(out["n_sel"]),
+                                             _p(out["centroid"]), _p(out["radius"]), _p(out["lrf"]), _p(out["desc"]), _p(out.get("counts"))),
+              "ismhip_global_short_shot")
+    return out
+
+
+def global_shot352(ctx, cloud, dev, region_obj, region_center=None, region_radius=None):
+    """ismhip_global_shot352 on regions as global_short_shot -> dict with desc [n, 352]"""
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    out = _global_outputs(n, 352, dev)
+    ctx.check(lib().ismhip_global_shot352(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), _p(out["n_sel"]), _p(out["centroid"]),
+                                          _p(out["radius"]), _p(out["lrf"]), _p(out["desc"])), "ismhip_global_shot352")
+    return out
 
 
 def fpfh33(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False):

@@ -1,0 +1,402 @@
+// global.hip — region descriptors: the global features of the reference's "extended pipeline" (UseGlobalFeatures), one 256-thread
+// workgroup per REGION = (object, selection centre, selection radius). Reference seams: FeaturesSHORTSHOTGlobal::iComputeDescriptors /
+// compute_descriptor (features/features_short_shot_global.cpp:36-165) and FeaturesSHOTGlobal::iComputeDescriptors
+// (features/features_shot_global.cpp:27-99), both on the cloud Voting hands them: the whole object (training, single-object mode) or the
+// points inside a ball round a maximum (voting.cpp:217-239).
+//
+// The shape is not that of the per-keypoint kernels (one wave per keypoint, one radius per call): there is ONE keypoint per region, the
+// centroid of the selected points; its support is every selected point; the radius is the region's own (the largest distance from that
+// centroid). So the workgroup STREAMS the object's cell-sorted span sp4 (coalesced float4 loads, the selection predicate evaluated on
+// the fly; the grid is not used) once per step, all steps in one kernel:
+//   1. count + coordinate sums (double)          -> n_sel, centroid      (a whole-object region takes both from the cloud's GridMeta:
+//                                                                          bit-equal to ismhip_cloud_centroids by construction)
+//   2. max |p - centroid| (k_cloud_radii's float arithmetic; max is order-free: bit-equal to ismhip_cloud_radii for a whole object)
+//   3. k_lrf_cov's weighted covariance in double -> eigen3.h on one thread -> axis candidates
+//   4. the two sign votes (integers); on a tie the five median neighbours by (d^2, original index) decide, found by bitwise bisection
+//      over the 64-bit keys with one more sweep of the span per bit -- no key store, so the region may hold any number of points
+//   5. the histogram: per-wave LDS copies of INTEGER bins (counts, or SHOT's 2^-28 fixed point), merged as integers, then the norm
+// Every reduction is a fixed-order tree in double (per thread in index order, DPP wave sum, the four waves in order) or an integer sum;
+// there is no float atomic: two calls give the same bits in every output.
+//
+// Byte model per region: 5 sweeps x 16 B x n_obj_points (6 for SHOT-352: + 16 B per descriptor neighbour for its normal), the first
+// from HBM, the later ones from L2 when the object's span fits (a 16 384-point object: 256 KiB); a tie adds ~50 sweeps from L2.
+// One region per workgroup: a region of a very large object is not split over several workgroups.
+#include "shot_deposit.h"
+#include "lrf_common.h"
+#include "eigen3.h"
+
+namespace {
+
+#define GLOBAL_SSHOT_RAD2DEG 57.29578     /* pcl::rad2deg(double) of PCL 1.10 multiplies by this truncated constant (external) */
+
+struct GlobalArgs {
+    const uint32_t* pt_off; const GridMeta* meta;
+    const float4 *sp4, *sn4, *slab4;          // slab4: never read (shot_neighbour<false>)
+    const float *x, *y, *z;                   // original order: the tie's five points
+    int n_obj;
+    const int32_t* reg_obj; const float* reg_center; const float* reg_radius;
+    uint32_t* n_sel; float* centroid; float* radius; float* lrf; float* desc; uint32_t* counts;
+    int r_bins, e_bins, a_bins, log_radius;   // SHORT_SHOT_GLOBAL only
+    double ln_rmin, min_radius;
+};
+
+template <bool SHOT>
+struct GlobalSmem {
+    double red_d[4];
+    unsigned long long red_k[4];
+    uint32_t red_u[4];
+    float red_f[4];
+    double axes[6];
+    float lrf[9];
+    int bad;
+    shot_bin_t hist[SHOT ? 4 * 352 : 1];
+    uint32_t cnt[SHOT ? 1 : 4 * ISMHIP_SHORT_SHOT_MAX_DIM];
+};
+
+// Fixed-order block reductions of a 256-thread workgroup; every thread gets the result. All threads must call them.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    v = wave_sum_d(v);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ uint32_t block_sum_u(uint32_t v, uint32_t* red) {
+    v = (uint32_t)wave_sum_i((int)v);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t s = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ float block_max_f(float v, float* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const float s = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ unsigned long long block_min_k(unsigned long long v, unsigned long long* red) {
+    v = wave_min_u64(v);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long s = red[0];
+    for (int k = 1; k < 4; ++k) s = red[k] < s ? red[k] : s;
+    __syncthreads();
+    return s;
+}
+
+// int(double) as the reference's x86-64 build takes it (cvttsd2si): NaN and values outside int give INT_MIN, which the clamps that
+// follow turn into bin 0 (r) or drop (theta, phi: the bin index is checked against the row)
+__device__ __forceinline__ int ref_int(double v) {
+    return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : (int)0x80000000;
+}
+
+template <bool SHOT>
+__global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
+    __shared__ GlobalSmem<SHOT> sm;
+    const int D = SHOT ? 352 : a.r_bins * a.e_bins * a.a_bins;
+    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    const uint32_t reg = blockIdx.x;
+    const float qnan = __builtin_nanf("");
+    float* row = a.desc + (size_t)reg * D;
+    uint32_t* crow = (!SHOT && a.counts) ? a.counts + (size_t)reg * D : nullptr;
+    auto nan_row = [&](bool frame) {
+        for (int i = tid; i < D; i += 256) { row[i] = qnan; if (crow) crow[i] = 0u; }
+        if (frame && tid < 9) a.lrf[(size_t)reg * 9 + tid] = qnan;
+    };
+
+    // ---- the region -------------------------------------------------------------------------------------------------------------
+    const int o = a.reg_obj[reg];
+    const bool obj_ok = o >= 0 && o < a.n_obj;
+    uint32_t base = 0, n = 0, npts = 0;
+    GridMeta m{};
+    if (obj_ok) {
+        m = a.meta[o];
+        base = a.pt_off[o]; npts = a.pt_off[o + 1] - base;
+        n = m.n_finite < npts ? m.n_finite : npts;            // the sorted span holds the finite points first
+    }
+    const float qx = a.reg_center[reg * 3], qy = a.reg_center[reg * 3 + 1], qz = a.reg_center[reg * 3 + 2];
+    const float rs = a.reg_radius[reg];
+    const bool whole = rs < 0.f;
+    const float r2s = (float)((double)rs * (double)rs);       // the ball sweeps' rule (shot_wave.h): d2 < (float)((double)r * r)
+    const float4* sp = a.sp4 + base;
+    auto selected = [&](const float4& p) { return whole || sqdist3(p.x, p.y, p.z, qx, qy, qz) < r2s; };
+
+    // ---- 1. count and centroid ----------------------------------------------------------------------------------------------------
+    uint32_t nsel; float cx, cy, cz;
+    if (whole) {
+        nsel = n; cx = m.centroid[0]; cy = m.centroid[1]; cz = m.centroid[2];
+    } else {
+        uint32_t c = 0; double sx = 0, sy = 0, sz = 0;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            if (selected(p)) { sx += (double)p.x; sy += (double)p.y; sz += (double)p.z; c++; }
+        }
+        nsel = block_sum_u(c, sm.red_u);
+        sx = block_sum_d(sx, sm.red_d); sy = block_sum_d(sy, sm.red_d); sz = block_sum_d(sz, sm.red_d);
+        cx = (float)(sx / (double)nsel); cy = (float)(sy / (double)nsel); cz = (float)(sz / (double)nsel);   // pcl::compute3DCentroid
+    }
+    if (tid == 0) a.n_sel[reg] = nsel;
+    if (nsel == 0) {                                          // workgroup-uniform
+        if (tid < 3) a.centroid[reg * 3 + tid] = qnan;
+        if (tid == 0) a.radius[reg] = 0.f;
+        nan_row(true);
+        return;
+    }
+    if (tid == 0) { a.centroid[reg * 3] = cx; a.centroid[reg * 3 + 1] = cy; a.centroid[reg * 3 + 2] = cz; }
+
+    // ---- 2. radius: k_cloud_radii's arithmetic -----------------------------------------------------------------------------------------
+    float R = 0.f;
+    for (uint32_t i = tid; i < n; i += 256) {
+        const float4 p = sp[i];
+        if (!selected(p)) continue;
+        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+        if (d > R) R = d;
+    }
+    R = block_max_f(R, sm.red_f);
+    if (tid == 0) a.radius[reg] = R;
+    const float r2 = (float)((double)R * (double)R);          // PCL: static_cast<float>(radius * radius) with a double radius
+    // a descriptor neighbour: selected and inside the ball (centroid, R); a frame neighbour: also not the centroid itself (k_lrf_cov)
+    auto neighbour = [&](const float4& p, float& d2) { d2 = sqdist3(p.x, p.y, p.z, cx, cy, cz); return d2 < r2 && selected(p); };
+    auto frame_nb = [&](const float4& p) { return !(p.x == cx && p.y == cy && p.z == cz); };
+
+    // ---- 3. covariance, eigenvectors ----------------------------------------------------------------------------------------------
+    {
+        double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0, sum = 0;
+        uint32_t valid = 0;
+        const double rd = (double)R;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            float d2;
+            if (!neighbour(p, d2) || !frame_nb(p)) continue;
+            const double vx = (double)(p.x - cx), vy = (double)(p.y - cy), vz = (double)(p.z - cz);
+            const double w = rd - sqrt_f32_as_f64(d2);
+            const double wx = w * vx, wy = w * vy, wz = w * vz;
+            c00 = fma(wx, vx, c00); c01 = fma(wx, vy, c01); c02 = fma(wx, vz, c02);
+            c11 = fma(wy, vy, c11); c12 = fma(wy, vz, c12); c22 = fma(wz, vz, c22);
+            sum += w; valid++;
+        }
+        c00 = block_sum_d(c00, sm.red_d); c01 = block_sum_d(c01, sm.red_d); c02 = block_sum_d(c02, sm.red_d);
+        c11 = block_sum_d(c11, sm.red_d); c12 = block_sum_d(c12, sm.red_d); c22 = block_sum_d(c22, sm.red_d);
+        sum = block_sum_d(sum, sm.red_d);
+        const uint32_t nvalid = block_sum_u(valid, sm.red_u);
+        if (tid == 0) {
+            bool bad = nvalid < 5u;                                                // shot_na_lrf.hpp:80-86
+            double w[3], V[3][3];
+            if (!bad) {
+                double A[3][3] = {{c00 / sum, c01 / sum, c02 / sum}, {c01 / sum, c11 / sum, c12 / sum}, {c02 / sum, c12 / sum, c22 / sum}};
+                eigen_sym3(A, w, V);
+                bad = !(isfinite(w[0]) && isfinite(w[1]) && isfinite(w[2]));
+            }
+            sm.bad = bad ? 1 : 0;
+            if (!bad) {
+                sm.axes[0] = V[0][2]; sm.axes[1] = V[1][2]; sm.axes[2] = V[2][2];     // x candidate: largest eigenvalue
+                sm.axes[3] = V[0][0]; sm.axes[4] = V[1][0]; sm.axes[5] = V[2][0];     // z candidate: smallest
+            }
+        }
+        __syncthreads();
+        if (sm.bad) { nan_row(true); return; }
+
+        // ---- 4. sign votes ------------------------------------------------------------------------------------------------------------
+        double v1[3] = {sm.axes[0], sm.axes[1], sm.axes[2]}, v3[3] = {sm.axes[3], sm.axes[4], sm.axes[5]};
+        uint32_t pt = 0, pn = 0;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            float d2;
+            if (!neighbour(p, d2) || !frame_nb(p)) continue;
+            const double vx = (double)(p.x - cx), vy = (double)(p.y - cy), vz = (double)(p.z - cz);
+            if (vx * v1[0] + vy * v1[1] + vz * v1[2] >= 0) pt++;
+            if (vx * v3[0] + vy * v3[1] + vz * v3[2] >= 0) pn++;
+        }
+        const int plusT = 2 * (int)block_sum_u(pt, sm.red_u) - (int)nvalid;
+        const int plusN = 2 * (int)block_sum_u(pn, sm.red_u) - (int)nvalid;
+        if (plusT < 0) { v1[0] = -v1[0]; v1[1] = -v1[1]; v1[2] = -v1[2]; }
+        if (plusN < 0) { v3[0] = -v3[0]; v3[1] = -v3[1]; v3[2] = -v3[2]; }
+        if (plusT == 0 || plusN == 0) {                                            // workgroup-uniform
+            // the five median neighbours by distance decide (shot_na_lrf.hpp:139-151): ranks n/2 - 2 .. n/2 + 2 of the keys
+            // (bits of d^2, original index). The key of rank t is the largest v with #(key < v) <= t: one sweep per bit.
+            auto key_of = [&](const float4& p, float d2) { return ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(p.w); };
+            int idx_bits = 1; while (idx_bits < 32 && (1u << idx_bits) < npts) ++idx_bits;
+            const uint32_t tsel = nvalid / 2 - 2;
+            unsigned long long five[5], sel = 0ull;
+            for (int bit = 62; bit >= 0; --bit) {
+                if (bit < 32 && bit >= idx_bits) continue;
+                const unsigned long long cand = sel | (1ull << bit);
+                uint32_t c = 0;
+                for (uint32_t i = tid; i < n; i += 256) {
+                    const float4 p = sp[i];
+                    float d2;
+                    if (neighbour(p, d2) && frame_nb(p)) c += key_of(p, d2) < cand;
+                }
+                if (block_sum_u(c, sm.red_u) <= tsel) sel = cand;
+            }
+            five[0] = sel;
+            for (int j = 1; j < 5; ++j) {
+                unsigned long long mn = ~0ull;
+                for (uint32_t i = tid; i < n; i += 256) {
+                    const float4 p = sp[i];
+                    float d2;
+                    if (!neighbour(p, d2) || !frame_nb(p)) continue;
+                    const unsigned long long kk = key_of(p, d2);
+                    if (kk > five[j - 1] && kk < mn) mn = kk;
+                }
+                five[j] = block_min_k(mn, sm.red_k);
+            }
+            int cntx = 0, cntz = 0;
+            for (int j = 0; j < 5; ++j) {
+                const uint32_t orig = (uint32_t)(five[j] & 0xffffffffull);
+                if (orig >= npts) continue;                                        // cannot happen: every key is a neighbour's
+                const double vx = (double)(a.x[base + orig] - cx), vy = (double)(a.y[base + orig] - cy), vz = (double)(a.z[base + orig] - cz);
+                if (vx * v1[0] + vy * v1[1] + vz * v1[2] > 0) cntx++;
+                if (vx * v3[0] + vy * v3[1] + vz * v3[2] > 0) cntz++;
+            }
+            if (plusT == 0 && cntx < 3) { v1[0] = -v1[0]; v1[1] = -v1[1]; v1[2] = -v1[2]; }
+            if (plusN == 0 && cntz < 3) { v3[0] = -v3[0]; v3[1] = -v3[1]; v3[2] = -v3[2]; }
+        }
+        if (tid == 0) write_lrf(sm.lrf, v1, v3);
+        __syncthreads();
+        if (tid < 9) a.lrf[(size_t)reg * 9 + tid] = sm.lrf[tid];
+    }
+    const float fx[3] = {sm.lrf[0], sm.lrf[1], sm.lrf[2]}, fy[3] = {sm.lrf[3], sm.lrf[4], sm.lrf[5]}, fz[3] = {sm.lrf[6], sm.lrf[7], sm.lrf[8]};
+
+    // ---- 5. the histogram and its norm ----------------------------------------------------------------------------------------------
+    if constexpr (SHOT) {
+        for (int i = tid; i < 4 * 352; i += 256) sm.hist[i] = 0ull;
+        __syncthreads();
+        shot_bin_t* hist = sm.hist + wv * 352;
+        const float r12 = R * 0.5f, r14 = R * 0.25f, r34 = (R * 3.0f) * 0.25f, inv_r12 = 1.0f / r12;
+        const float r12sq_f = shot_r12sq_f(R);
+        uint32_t total = 0;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            float d2;
+            if (!neighbour(p, d2)) continue;
+            total++;
+            shot_neighbour<false>(a, hist, true, base + i, p.x - cx, p.y - cy, p.z - cz, d2, fx, fy, fz, r12, r14, r34, inv_r12, r12sq_f, 0.f, 0.f, 0.f);
+        }
+        total = block_sum_u(total, sm.red_u);                                      // its barriers also publish the deposits
+        if (total < 5u) { nan_row(false); return; }                               // computePointSHOT: fewer than 5 neighbours
+        // normalizeHistogram: double accumulate of float squares, divide by float(norm)
+        float v[2] = {0.f, 0.f};
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int i = tid + 256 * j;
+            if (i < 352) {
+                const shot_bin_t h = sm.hist[i] + sm.hist[352 + i] + sm.hist[704 + i] + sm.hist[1056 + i];
+                v[j] = (float)((double)h * SHOT_FIX_INV);
+                acc += (double)(v[j] * v[j]);
+            }
+        }
+        const float fn = (float)sqrt(block_sum_d(acc, sm.red_d));
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; if (i < 352) row[i] = v[j] / fn; }
+    } else {
+        // A short histogram draws many lanes onto the same address, and same-address LDS atomics of a wave instruction serialise: the
+        // 256 slots a wave owns hold 256 / D copies of the D bins, lane l counts in copy l % copies (integers: the merge is exact)
+        const int copies = ISMHIP_SHORT_SHOT_MAX_DIM / D;
+        for (int i = tid; i < 4 * ISMHIP_SHORT_SHOT_MAX_DIM; i += 256) sm.cnt[i] = 0u;
+        __syncthreads();
+        uint32_t* hist = sm.cnt + wv * ISMHIP_SHORT_SHOT_MAX_DIM + (lane % copies) * D;
+        const int rb = a.r_bins, eb = a.e_bins, ab = a.a_bins;
+        const double radius_d = (double)R;
+        const double ln_rmax_rmin = a.log_radius ? log(radius_d / a.min_radius) : 1.0;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            float d2;
+            if (!neighbour(p, d2)) continue;
+            if (!((double)d2 > 1e-15)) continue;                                   // distances[j] > 1E-15 on the SQUARED distance (:124)
+            const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+            const double xl = (double)((dx * fx[0] + dy * fx[1]) + dz * fx[2]);    // float products, unfused, in short_shot.hip's order
+            const double yl = (double)((dx * fy[0] + dy * fy[1]) + dz * fy[2]);
+            const double zl = (double)((dx * fz[0] + dy * fz[1]) + dz * fz[2]);
+            const double r = sqrt((xl * xl + yl * yl) + zl * zl);
+            const double theta = acos(zl / r) * GLOBAL_SSHOT_RAD2DEG;
+            const double phi = atan2(yl, xl) * GLOBAL_SSHOT_RAD2DEG;
+            int bin_r = a.log_radius ? ref_int(((double)(rb - 1) * (log(r) - a.ln_rmin)) / ln_rmax_rmin + 1.0)
+                                     : ref_int(((double)rb * r) / radius_d);
+            int bin_theta = ref_int(((double)eb * theta) / 180.0);
+            int bin_phi = ref_int(((double)ab * (phi + 180.0)) / 360.0);
+            bin_r = bin_r >= 0 ? bin_r : 0;
+            bin_r = bin_r < rb ? bin_r : rb - 1;
+            bin_theta = bin_theta < eb ? bin_theta : eb - 1;
+            bin_phi = bin_phi < ab ? bin_phi : ab - 1;
+            if (bin_theta < 0 || bin_phi < 0) continue;                            // a NaN angle: outside the row in the reference (undefined there)
+            atomicAdd(&hist[bin_r + bin_theta * rb + bin_phi * rb * eb], 1u);
+        }
+        __syncthreads();
+        uint32_t c = 0;
+        if (tid < D) for (int k = 0; k < 4; ++k) for (int j = 0; j < copies; ++j) c += sm.cnt[k * ISMHIP_SHORT_SHOT_MAX_DIM + j * D + tid];
+        if (crow && tid < D) crow[tid] = c;
+        // the L2 norm (:151-161): double sum of squares (integers below 2^53: exact in any order), sqrt, double division, cast to float;
+        // no contributing point gives 0 / 0: a NaN row
+        const double cd = (double)c;
+        const double norm = sqrt(block_sum_d(cd * cd, sm.red_d));
+        if (tid < D) row[tid] = (float)(cd / norm);
+    }
+}
+
+int global_check(ismhip_ctx* ctx, const char* name, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                 const float* region_radius, const uint32_t* n_sel_out, const float* centroid_out, const float* radius_out, const float* lrf9_out,
+                 const float* desc_out) {
+    if (!ctx) return ISMHIP_ERR_INVALID;
+    const bool arrays = region_obj && region_center && region_radius && n_sel_out && centroid_out && radius_out && lrf9_out && desc_out;
+    if (!cloud || n_regions < 0 || (n_regions > 0 && !arrays))                     // no region: nothing is read or written
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, std::string(name) + ": bad argument");
+    return ISMHIP_OK;
+}
+
+GlobalArgs global_args(const ismhip_cloud* cloud, const int32_t* region_obj, const float* region_center, const float* region_radius,
+                       uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out) {
+    GlobalArgs a{};
+    a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.sp4 = cloud->sp4; a.sn4 = cloud->sn4; a.slab4 = cloud->slab4;
+    a.x = cloud->x; a.y = cloud->y; a.z = cloud->z; a.n_obj = cloud->n_obj;
+    a.reg_obj = region_obj; a.reg_center = region_center; a.reg_radius = region_radius;
+    a.n_sel = n_sel_out; a.centroid = centroid_out; a.radius = radius_out; a.lrf = lrf9_out; a.desc = desc_out;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ismhip_global_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                             const float* region_radius, double min_radius, int log_radius, int r_bins, int e_bins, int a_bins,
+                             uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out, uint32_t* count_out) {
+    int rc = global_check(ctx, "global_short_shot", cloud, n_regions, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out,
+                          lrf9_out, desc_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (r_bins < 1 || e_bins < 1 || a_bins < 1) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_short_shot: fewer than one bin on an axis");
+    if ((long long)r_bins * e_bins * a_bins > ISMHIP_SHORT_SHOT_MAX_DIM)
+        return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "global_short_shot: more than 256 bins");
+    if (log_radius && !(min_radius > 0.0 && std::isfinite(min_radius)))
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_short_shot: logarithmic radius needs min_radius > 0");
+    if (n_regions == 0) return ISMHIP_OK;
+    GlobalArgs a = global_args(cloud, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out, lrf9_out, desc_out);
+    a.counts = count_out;
+    a.r_bins = r_bins; a.e_bins = e_bins; a.a_bins = a_bins; a.log_radius = log_radius ? 1 : 0;
+    a.min_radius = min_radius; a.ln_rmin = log_radius ? log(min_radius) : 0.0;
+    TimerScope ts(ctx, "global_short_shot");
+    hipLaunchKernelGGL(k_global<false>, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
+    ISM_CHECK_LAUNCH(ctx, "k_global<short_shot>");
+    return ISMHIP_OK;
+}
+
+int ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                          const float* region_radius, uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out) {
+    int rc = global_check(ctx, "global_shot352", cloud, n_regions, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out,
+                          lrf9_out, desc_out);
+    if (rc != ISMHIP_OK || n_regions == 0) return rc;
+    GlobalArgs a = global_args(cloud, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out, lrf9_out, desc_out);
+    TimerScope ts(ctx, "global_shot352");
+    hipLaunchKernelGGL(k_global<true>, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
+    ISM_CHECK_LAUNCH(ctx, "k_global<shot352>");
+    return ISMHIP_OK;
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 //    of a workgroup then sweep overlapping balls; every keypoint's row is written at its own index, so the order changes no result)
 //   k_lrf_tie  : work-queue kernel for sign ties (~3 % of keypoints): the 5 median neighbours BY DISTANCE decide
 //                (shot_na_lrf.hpp:139-151); rank selection by bitwise bisection over 64-bit (d^2, index) keys
-#include "common.h"
+#include "lrf_common.h"
 #include "eigen3.h"
 
 namespace {
@@ -38,23 +38,7 @@ struct CloudView {
     const uint32_t* kp_perm;  // keypoints in cell order (k_lrf_cov / k_lrf_sign; nullptr: as they come)
 };
 
-__device__ __forceinline__ void write_lrf(float* out, const double v1[3], const double v3[3]) {
-    const float xf[3] = {(float)v1[0], (float)v1[1], (float)v1[2]};
-    const float zf[3] = {(float)v3[0], (float)v3[1], (float)v3[2]};
-    out[0] = xf[0]; out[1] = xf[1]; out[2] = xf[2];
-    out[3] = zf[1] * xf[2] - zf[2] * xf[1];     // y = z x x, in float (shot_na_lrf.hpp:170)
-    out[4] = zf[2] * xf[0] - zf[0] * xf[2];
-    out[5] = zf[0] * xf[1] - zf[1] * xf[0];
-    out[6] = zf[0]; out[7] = zf[1]; out[8] = zf[2];
-}
-
-// sqrt(double(d2)) to full double precision from the float estimate + one Newton step (v_sqrt_f64 is slow)
-__device__ __forceinline__ double sqrt_f32_as_f64(float d2) {
-    if (d2 <= 0.f) return 0.0;
-    const float s0f = sqrtf(d2);
-    const double s0 = (double)s0f, x = (double)d2;
-    return s0 + (x - s0 * s0) * (double)(0.5f / s0f);
-}
+// write_lrf (the frame's float form) and sqrt_f32_as_f64 (the distance weight): lrf_common.h, shared with global.hip
 
 // cov_out[k*8 + 0..6] = c00,c01,c02,c11,c12,c22,sum ; [7] = number of valid neighbours (as double), -1 = no search possible
 __global__ __launch_bounds__(256) void k_lrf_cov(CloudView cv, const uint32_t* __restrict__ kp_off,

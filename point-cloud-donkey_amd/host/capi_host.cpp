@@ -171,6 +171,98 @@ int ism3d_detect_batch(void* m, int n_obj, const uint32_t* pt_off, const float* 
         }
         return 0;)
 }
+// ---- global verification (Voting.UseGlobalFeatures) ----------------------------------------------------------------------------
+// the stored global features of the model, flattened in the data file's order (class, training cloud, row). Any array may be NULL.
+// Returns the number of rows; *dim_out their length (0 without rows), *n_clouds_out the training clouds over all classes.
+int ism3d_global_features_get(void* m, int* dim_out, int* n_clouds_out, uint32_t* cls, uint32_t* cloud, uint32_t* inst, float* rf9, float* desc, float* radius) {
+    GUARD(
+        const auto& g = ((ImplicitShapeModel*)m)->getVoting()->getGlobalFeatures();
+        int n = 0, dim = 0, clouds = 0;
+        for (auto& it : g) for (auto& c : it.second) {
+            for (auto& f : c) {
+                dim = (int)f.descriptor.size();
+                if (cls) cls[n] = it.first;
+                if (cloud) cloud[n] = (uint32_t)clouds;
+                if (inst) inst[n] = f.instanceId;
+                if (rf9) std::memcpy(rf9 + (size_t)n * 9, f.rf, 36);
+                if (desc) std::memcpy(desc + (size_t)n * dim, f.descriptor.data(), (size_t)dim * 4);
+                if (radius) radius[n] = f.radius;
+                ++n;
+            }
+            ++clouds;
+        }
+        if (dim_out) *dim_out = dim;
+        if (n_clouds_out) *n_clouds_out = clouds;
+        return n;)
+}
+// installs stored global features from flat arrays, one training cloud per row (persistence tests without a GPU)
+int ism3d_global_features_set(void* m, int n, int dim, const uint32_t* cls, const uint32_t* inst, const float* rf9, const float* desc, const float* radius) {
+    GUARD(
+        Voting::GlobalFeatureMap g;
+        for (int i = 0; i < n; ++i) {
+            StoredGlobalFeature f; f.classId = cls[i]; f.instanceId = inst[i]; f.radius = radius[i];
+            std::memcpy(f.rf, rf9 + (size_t)i * 9, 36);
+            f.descriptor.assign(desc + (size_t)i * dim, desc + (size_t)(i + 1) * dim);
+            g[cls[i]].push_back({f});
+        }
+        ((ImplicitShapeModel*)m)->getVoting()->forwardGlobalFeatures(g);
+        return 0;)
+}
+// diagnostics (tests): the global step of the last detectBatch(). Regions: object, index of the maximum among the object's maxima BEFORE
+// the merge (-1: the whole object), selected points, centroid [3], radius, descriptor row [dim], the k neighbours (row of the stored
+// features, functor distance) and the hypothesis (ids: class, instance; weights: class, instance). Maxima before the merge: max_off
+// [n_obj + 1], then class, instance, weight, instance weight, position [3] per maximum. Any array may be NULL. Returns the number of
+// regions; *k_out, *dim_out, *n_obj_out, *n_max_out the shapes.
+int ism3d_last_global(void* m, int* k_out, int* dim_out, int* n_obj_out, int* n_max_out, int32_t* region_obj, int32_t* region_max, uint32_t* n_sel, float* centroid,
+                      float* radius, float* desc, int32_t* knn_idx, float* knn_dist, uint32_t* hyp_id, float* hyp_w, uint32_t* max_off, int32_t* max_cls,
+                      int32_t* max_inst, float* max_w, float* max_iw, float* max_pos) {
+    GUARD(
+        const auto& d = ((ImplicitShapeModel*)m)->getVoting()->lastGlobal();
+        if (k_out) *k_out = d.k;
+        if (dim_out) *dim_out = d.dim;
+        if (n_obj_out) *n_obj_out = (int)d.max_off.size() - 1;
+        if (n_max_out) *n_max_out = (int)d.max_cls.size();
+        auto cp = [](auto* dst, const auto& v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+        cp(region_obj, d.region_obj); cp(region_max, d.region_max); cp(n_sel, d.n_sel); cp(centroid, d.centroid); cp(radius, d.radius); cp(desc, d.desc);
+        cp(knn_idx, d.knn_idx); cp(knn_dist, d.knn_dist); cp(hyp_id, d.hyp_id); cp(hyp_w, d.hyp_w); cp(max_off, d.max_off); cp(max_cls, d.max_cls);
+        cp(max_inst, d.max_inst); cp(max_w, d.max_w); cp(max_iw, d.max_iw); cp(max_pos, d.max_pos);
+        return (int)d.region_obj.size();)
+}
+// GlobalClassifier::classifyWithKNN on the k neighbours of one query (pure host code): out_id = {class, instance}, out_w = {class weight,
+// instance weight}
+int ism3d_classify_knn(int k, const uint32_t* n_class, const uint32_t* n_inst, const float* n_dist, uint32_t max_class, int single_object_mode, uint32_t* out_id, float* out_w) {
+    GUARD(
+        const auto g = Voting::classifyWithKNN(k, n_class, n_inst, n_dist, max_class, single_object_mode != 0);
+        out_id[0] = g.classId; out_id[1] = g.instanceId; out_w[0] = g.classWeight; out_w[1] = g.instanceWeight;
+        return 0;)
+}
+// The merge sequence of Voting::findMaxima (voting.cpp:272-323) on n maxima given as arrays (pure host code, no device): ids [n*2]
+// (class, instance), w [n*2] (weight, instance weight), pos [n*3], hypothesis ids [n*2] / weights [n*2], roi centroid [n*3]; params [6]:
+// radius, MinThreshold, BestK, GlobalParamMinSvmScore, GlobalParamRateLimit, GlobalParamWeightFactor. The arrays are rewritten with the
+// surviving maxima in their final order. Returns their number.
+int ism3d_merge_sequence(int function, int n, uint32_t* ids, float* w, float* pos, uint32_t* hyp_ids, float* hyp_w, float* roi, const float* params) {
+    GUARD(
+        std::vector<VotingMaximum> mx((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            VotingMaximum& v = mx[i];
+            v.classId = ids[2 * i]; v.instanceId = ids[2 * i + 1]; v.weight = w[2 * i]; v.instanceWeight = w[2 * i + 1];
+            v.position = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}; v.roiCentroid = {roi[3 * i], roi[3 * i + 1], roi[3 * i + 2]};
+            v.globalHypothesis.classId = hyp_ids[2 * i]; v.globalHypothesis.instanceId = hyp_ids[2 * i + 1];
+            v.globalHypothesis.classWeight = hyp_w[2 * i]; v.globalHypothesis.instanceWeight = hyp_w[2 * i + 1];
+        }
+        Voting::MergeParams P;
+        P.function = function; P.radius = params[0]; P.min_threshold = params[1]; P.best_k = (int)params[2];
+        P.min_svm_score = params[3]; P.rate_limit = params[4]; P.weight_factor = params[5];
+        Voting::mergeSequence(mx, P);
+        for (size_t i = 0; i < mx.size(); ++i) {
+            const VotingMaximum& v = mx[i];
+            ids[2 * i] = v.classId; ids[2 * i + 1] = v.instanceId; w[2 * i] = v.weight; w[2 * i + 1] = v.instanceWeight;
+            for (int d = 0; d < 3; ++d) { pos[3 * i + d] = v.position[d]; roi[3 * i + d] = v.roiCentroid[d]; }
+            hyp_ids[2 * i] = v.globalHypothesis.classId; hyp_ids[2 * i + 1] = v.globalHypothesis.instanceId;
+            hyp_w[2 * i] = v.globalHypothesis.classWeight; hyp_w[2 * i + 1] = v.globalHypothesis.instanceWeight;
+        }
+        return (int)mx.size();)
+}
 int ism3d_detect_file(void* m, const char* file, int32_t* cls_out, float* weight_out) {
     GUARD(std::vector<VotingMaximum> maxima; std::map<std::string, double> times;
           if (!((ImplicitShapeModel*)m)->detect(std::string(file), maxima, times)) return -2;

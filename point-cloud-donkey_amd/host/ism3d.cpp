@@ -911,6 +911,185 @@ bool Codebook::load(BoostBinaryIArchive& ia) {
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Global descriptors (features/features_short_shot_global.cpp, features_shot_global.cpp) on regions of the batch's search surface
+// ---------------------------------------------------------------------------------------------------------------
+struct GlobalRegions {
+    int n = 0, dim = 0;
+    DevBuf obj, cen, rad;                          // the regions
+    DevBuf n_sel, centroid, radius, lrf, desc;     // the outputs
+    // uploads the regions and reserves the outputs for rows of `dim` floats
+    void set(const std::vector<int32_t>& o, const std::vector<float>& c, const std::vector<float>& r, int D) {
+        n = (int)o.size(); dim = D;
+        DeviceSession::h2d(obj, o); DeviceSession::h2d(cen, c); DeviceSession::h2d(rad, r);
+        const size_t m = std::max<size_t>((size_t)n, 1);
+        n_sel.reserve(m * 4); centroid.reserve(m * 12); radius.reserve(m * 4); lrf.reserve(m * 36); desc.reserve(m * (size_t)D * 4);
+    }
+};
+GlobalFeaturesShortShot::GlobalFeaturesShortShot() {          // features_short_shot_global.cpp:21-30
+    addParameter(m_min_radius, "ShortShotMinRadius", 0.1);
+    addParameter(m_feature_dims, "ShortShotDims", 32);
+    addParameter(m_log_radius, "ShortShotLogRadius", false);
+    addParameter(m_r_bins, "ShortShotRBins", 1);
+    addParameter(m_e_bins, "ShortShotEBins", 1);
+    addParameter(m_a_bins, "ShortShotABins", 8);
+    addParameter(m_bin_type, "ShortShotBinType", std::string("auto"));
+}
+void GlobalFeaturesShortShot::iPostInitConfig() {             // configureSphericalGrid (:168-249); 64 is 4 x 2 x 8 here, unlike the local descriptor
+    static const int sizes[9][4] = {{8, 1, 1, 8}, {16, 2, 2, 4}, {24, 2, 2, 6}, {32, 2, 2, 8}, {64, 4, 2, 8}, {96, 3, 4, 8}, {128, 4, 4, 8}, {192, 6, 4, 8}, {256, 8, 4, 8}};
+    if (m_bin_type == "manual") {
+        if (m_r_bins < 1 || m_e_bins < 1 || m_a_bins < 1 || (long long)m_r_bins * m_e_bins * m_a_bins > ISMHIP_SHORT_SHOT_MAX_DIM)
+            throw RuntimeException("SHORT_SHOT_GLOBAL: " + std::to_string(m_r_bins) + " x " + std::to_string(m_e_bins) + " x " + std::to_string(m_a_bins) +
+                                   " bins are not built (built: 1 .. " + std::to_string(ISMHIP_SHORT_SHOT_MAX_DIM) + " bins)");
+        m_feature_dims = m_r_bins * m_e_bins * m_a_bins;
+        return;
+    }
+    const int* hit = nullptr;
+    if (m_bin_type == "auto") for (auto& row : sizes) if (row[0] == m_feature_dims) hit = row;
+    if (!hit) {
+        if (m_bin_type == "auto") LOG_ERROR("Unsupported Short SHOT dimensions for automatic bin configuration: " << m_feature_dims << "! Setting to 32 dimensions with default bins.");
+        else LOG_ERROR("Unsupported Short SHOT bins configuration type: " << m_bin_type << "! Setting to 32 dimensions with default bins.");
+        hit = sizes[3];
+    }
+    m_feature_dims = hit[0]; m_r_bins = hit[1]; m_e_bins = hit[2]; m_a_bins = hit[3];
+    if (m_log_radius && !(m_min_radius > 0)) throw RuntimeException("SHORT_SHOT_GLOBAL: ShortShotLogRadius needs ShortShotMinRadius > 0");
+}
+void GlobalFeaturesShortShot::describe(DeviceSession& s, GlobalRegions& r) const {
+    s.check(ismhip_global_short_shot(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), m_min_radius, m_log_radius ? 1 : 0,
+                                     m_r_bins, m_e_bins, m_a_bins, r.n_sel.as<uint32_t>(), r.centroid.as<float>(), r.radius.as<float>(), r.lrf.as<float>(),
+                                     r.desc.as<float>(), nullptr), "ismhip_global_short_shot");
+}
+void GlobalFeaturesShot::describe(DeviceSession& s, GlobalRegions& r) const {
+    s.check(ismhip_global_shot352(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), r.n_sel.as<uint32_t>(), r.centroid.as<float>(),
+                                  r.radius.as<float>(), r.lrf.as<float>(), r.desc.as<float>()), "ismhip_global_shot352");
+}
+GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
+    if (!object.isObject()) return nullptr;
+    const Json* t = object.find("Type");
+    if (!t || t->type != Json::String) return nullptr;
+    GlobalFeatures* g = nullptr;
+    if (t->str == GlobalFeaturesShortShot::getTypeStatic()) g = new GlobalFeaturesShortShot();
+    else if (t->str == GlobalFeaturesShot::getTypeStatic()) g = new GlobalFeaturesShot();
+    if (!g) return nullptr;
+    try { if (!g->configFromJson(object)) throw RuntimeException("could not create object of type: \"" + t->str + "\""); }
+    catch (...) { delete g; throw; }
+    return g;
+}
+
+// GlobalClassifier::classifyWithKNN (global_classifier.cpp:242-347) with insertGlobalResult / GlobalResultAccu (.h:33-62): per class the
+// occurrences and the float score sum, per instance of the class likewise; std::map order, so a tie goes to the lowest id
+VotingMaximum::GlobalHypothesis Voting::classifyWithKNN(int k, const unsigned* n_class, const unsigned* n_inst, const float* n_dist, unsigned max_class,
+                                                         bool single_object_mode) {
+    struct Accu { unsigned n = 0; float score = 0; std::map<unsigned, std::pair<int, float>> inst; };
+    std::map<unsigned, Accu> votes;
+    for (int i = 0; i < k; ++i) {
+        const float score = std::exp(-std::sqrt(n_dist[i]));            // float sqrt, float exp
+        Accu& a = votes[n_class[i]];
+        a.n++; a.score += score;
+        auto& e = a.inst[n_inst[i]];
+        e.first++; e.second += score;
+    }
+    VotingMaximum::GlobalHypothesis g; g.classId = max_class;
+    auto best_instance = [&](const Accu& a) {
+        int best = 0;
+        for (auto& it : a.inst) if (it.second.first > best) { best = it.second.first; g.instanceId = it.first; }
+        const auto& e = a.inst.at(g.instanceId);
+        g.instanceWeight = e.second / e.first;
+    };
+    if (single_object_mode) {
+        if (votes.empty()) return g;                                    // (the reference would throw from map::at)
+        unsigned best = 0;
+        for (auto& it : votes) if (it.second.n > best) { best = it.second.n; g.classId = it.first; }
+        const Accu& a = votes.at(g.classId);
+        g.classWeight = a.score / a.n;
+        best_instance(a);
+    } else {
+        auto it = votes.find(max_class);
+        if (it != votes.end()) { g.classWeight = it->second.n > 0 ? it->second.score / it->second.n : 0; best_instance(it->second); }
+    }
+    return g;
+}
+
+// Voting::normalizeWeights (voting.cpp:441-462)
+static void normalizeMaxima(std::vector<VotingMaximum>& maxima) {
+    float sum = 0, sum_instance = 0, sum_global = 0, sum_instance_global = 0;
+    for (const VotingMaximum& m : maxima) { sum += m.weight; sum_instance += m.instanceWeight; sum_global += m.globalHypothesis.classWeight; sum_instance_global += m.globalHypothesis.instanceWeight; }
+    for (VotingMaximum& m : maxima) {
+        m.weight = sum != 0 ? m.weight / sum : 0;
+        m.instanceWeight = sum_instance != 0 ? m.instanceWeight / sum_instance : 0;
+        m.globalHypothesis.classWeight = sum_global != 0 ? m.globalHypothesis.classWeight / sum_global : 0;
+        m.globalHypothesis.instanceWeight = sum_instance_global != 0 ? m.globalHypothesis.instanceWeight / sum_instance_global : 0;
+    }
+}
+// GlobalClassifier::useHighRankedGlobalHypothesis (global_classifier.cpp:579-601)
+static void useHighRankedGlobalHypothesis(std::vector<VotingMaximum>& maxima, float rate_limit) {
+    const float top_weight = maxima[0].weight;
+    const unsigned global_class = maxima[0].globalHypothesis.classId;
+    for (size_t i = 0; i < maxima.size(); ++i) {
+        const float cur_weight = maxima[i].weight;
+        if (cur_weight >= top_weight * rate_limit && maxima[i].classId == global_class) {
+            maxima[0].classId = maxima[0].globalHypothesis.classId; maxima[0].instanceId = maxima[0].globalHypothesis.instanceId;
+            break;
+        } else if (cur_weight < top_weight * rate_limit) break;
+    }
+}
+static float norm3(float x, float y, float z) { return std::sqrt(x * x + y * y + z * z); }
+void Voting::mergeSequence(std::vector<VotingMaximum>& maxima, const MergeParams& p) {
+    auto by_weight = [](const VotingMaximum& a, const VotingMaximum& b) { return a.weight > b.weight; };
+    std::stable_sort(maxima.begin(), maxima.end(), by_weight);                       // the reference's std::sort leaves the order of equal weights open
+    if (maxima.empty()) return;
+    if (p.function != 5) normalizeMaxima(maxima);                                    // :278-282
+    // mergeGlobalAndLocalHypotheses (global_classifier.cpp:457-577)
+    const int fn = p.function;
+    auto near = [&](const VotingMaximum& m) {
+        const auto& c = m.roiCentroid;
+        if (norm3(c[0], c[1], c[2]) == 0) return true;                               // classification, not detection
+        return norm3(m.position[0] - c[0], m.position[1] - c[1], m.position[2] - c[2]) < p.radius / 2.0f;
+    };
+    if (fn == 1) {
+        if (maxima[0].globalHypothesis.classWeight > p.min_svm_score) { maxima[0].classId = maxima[0].globalHypothesis.classId; maxima[0].instanceId = maxima[0].globalHypothesis.instanceId; }
+    } else if (fn == 2) {
+        if (maxima[0].globalHypothesis.classWeight > p.min_svm_score) useHighRankedGlobalHypothesis(maxima, p.rate_limit);
+    } else if (fn == 3) {
+        useHighRankedGlobalHypothesis(maxima, p.rate_limit);
+    } else if (fn == 4) {
+        for (VotingMaximum& m : maxima) {
+            const bool ok = near(m);
+            if (m.classId == m.globalHypothesis.classId && ok) { if (m.globalHypothesis.classWeight == 0) m.weight = 0; else m.weight *= p.weight_factor; }
+            if (m.instanceId == m.globalHypothesis.instanceId && ok) { if (m.globalHypothesis.instanceWeight == 0) m.instanceWeight = 0; else m.instanceWeight *= p.weight_factor; }
+        }
+    } else if (fn == 5) {
+        for (VotingMaximum& m : maxima)
+            if (near(m)) {
+                if (m.classId == m.globalHypothesis.classId) m.weight *= 1 + m.globalHypothesis.classWeight;
+                if (m.instanceId == m.globalHypothesis.instanceId) m.instanceWeight *= 1 + m.globalHypothesis.instanceWeight;
+            }
+    } else if (fn == 6) {
+        for (VotingMaximum& m : maxima) {
+            if (m.classId == m.globalHypothesis.classId) m.weight *= m.globalHypothesis.classWeight;
+            if (m.instanceId == m.globalHypothesis.instanceId) m.instanceWeight *= m.globalHypothesis.instanceWeight;
+        }
+    } else if (fn == 7) {
+        for (VotingMaximum& m : maxima)
+            if (m.classId == m.globalHypothesis.classId && near(m)) {
+                float w1 = m.weight, w2 = m.globalHypothesis.classWeight;
+                m.weight = w1 + w2 - w1 * w2;
+                if (m.instanceId == m.globalHypothesis.instanceId) { w1 = m.instanceWeight; w2 = m.globalHypothesis.instanceWeight; m.instanceWeight = w1 + w2 - w1 * w2; }
+            }
+    } else {
+        LOG_ERROR("Invalid merging function specified: " << fn << "! Not merging local and global hypotheses.");
+    }
+    std::stable_sort(maxima.begin(), maxima.end(), by_weight);                       // :287
+    maxima.erase(std::find_if(maxima.begin(), maxima.end(), [](const VotingMaximum& m) { return m.weight == 0; }), maxima.end());
+    normalizeMaxima(maxima);                                                         // :298
+    float weight_threshold = p.min_threshold;                                        // :304-323
+    if (weight_threshold < 0) weight_threshold = -weight_threshold * (maxima.empty() ? 0.0f : maxima.front().weight);
+    std::vector<VotingMaximum> kept;
+    for (const VotingMaximum& m : maxima) if (m.weight >= weight_threshold) kept.push_back(m);
+    maxima.swap(kept);
+    if (p.best_k > 0 && (int)maxima.size() >= p.best_k) maxima.erase(maxima.begin() + p.best_k, maxima.end());
+}
+
 // Voting::forwardBoxesAndRadii (voting.cpp:496-551)
 void Voting::forwardBoxesAndRadii(const std::map<unsigned, std::vector<std::array<float, 3>>>& box_sizes, const std::map<unsigned, std::vector<float>>& object_radii) {
     m_dimensions_map.clear(); m_variance_map.clear();
@@ -950,7 +1129,19 @@ void Voting::save(BoostBinaryOArchive& oa) const {
     for (auto& it : m_dimensions_map) oa << it.first << it.second.first << it.second.second;
     oa << (unsigned)m_variance_map.size();
     for (auto& it : m_variance_map) oa << it.first << it.second.first << it.second.second;
-    oa << 0u;                                                  // global features: none (out of scope)
+    // global features (voting.cpp:586-613): per class its training clouds, per cloud its rows -- nine frame floats, the descriptor
+    // vector, the radius, the instance id. A model without a built global descriptor writes none.
+    oa << (unsigned)m_global_features.size();
+    for (auto& it : m_global_features) {
+        oa << it.first << (unsigned)it.second.size();
+        for (auto& cloud : it.second) {
+            oa << (unsigned)cloud.size();
+            for (auto& f : cloud) {
+                for (int r = 0; r < 9; ++r) oa << f.rf[r];
+                oa << f.descriptor << f.radius << f.instanceId;
+            }
+        }
+    }
 }
 bool Voting::load(BoostBinaryIArchive& ia) {
     m_dimensions_map.clear(); m_variance_map.clear();
@@ -960,18 +1151,23 @@ bool Voting::load(BoostBinaryIArchive& ia) {
     ia >> n;
     if (!ia.plausible(n, 12)) return false;
     for (unsigned i = 0; i < n; ++i) { unsigned c = 0; float a = 0, b = 0; ia >> c >> a >> b; m_variance_map[c] = {a, b}; }
-    // global features must be deserialised completely even when unused (voting.cpp:652-705); they are read and dropped
+    // global features must be deserialised completely even when unused (voting.cpp:652-705); they are kept with the model
+    m_global_features.clear();
     unsigned n_glob = 0; ia >> n_glob;
     if (!ia.plausible(n_glob, 8)) return false;
     for (unsigned i = 0; i < n_glob && ia.ok(); ++i) {
         unsigned classId = 0, clouds = 0; ia >> classId >> clouds;
         if (!ia.plausible(clouds, 4)) return false;
+        auto& per_class = m_global_features[classId];
         for (unsigned j = 0; j < clouds && ia.ok(); ++j) {
             unsigned feats = 0; ia >> feats;
             if (!ia.plausible(feats, 52)) return false;
+            per_class.emplace_back();
             for (unsigned k = 0; k < feats && ia.ok(); ++k) {
-                float rf; for (int r = 0; r < 9; ++r) ia >> rf;
-                std::vector<float> desc; float radius; unsigned inst; ia >> desc >> radius >> inst;
+                StoredGlobalFeature f; f.classId = classId;
+                for (int r = 0; r < 9; ++r) ia >> f.rf[r];
+                ia >> f.descriptor >> f.radius >> f.instanceId;
+                per_class.back().push_back(f);
             }
         }
     }
@@ -981,7 +1177,7 @@ bool Voting::load(BoostBinaryIArchive& ia) {
 // ---------------------------------------------------------------------------------------------------------------
 // Voting (voting/voting.cpp, voting_mean_shift.cpp)
 // ---------------------------------------------------------------------------------------------------------------
-Voting::Voting() {                                // voting.cpp:28-50 (hot-path subset; the global-feature keys are accepted and must stay off)
+Voting::Voting() {                                // voting.cpp:28-50
     addParameter(m_minThreshold, "MinThreshold", 0.0f);
     addParameter(m_minVotesThreshold, "MinVotesThreshold", 1);
     addParameter(m_bestK, "BestK", -1);
@@ -992,6 +1188,13 @@ Voting::Voting() {                                // voting.cpp:28-50 (hot-path 
     addParameter(m_max_type_param, "SingleObjectMaxType", std::string("Default"));
     addParameter(m_single_object_mode, "SingleObjectMode", false);
     addParameter(m_use_global_features, "UseGlobalFeatures", false);
+    addParameter(m_global_feature_method, "GlobalFeaturesStrategy", std::string("KNN"));     // voting.cpp:39-45
+    addParameter(m_k_global_features, "GlobalFeaturesK", 1);
+    addParameter(m_merge_function, "GlobalFeatureInfluenceType", 3);
+    addParameter(m_min_svm_score, "GlobalParamMinSvmScore", 0.70f);
+    addParameter(m_rate_limit, "GlobalParamRateLimit", 0.60f);
+    addParameter(m_weight_factor, "GlobalParamWeightFactor", 1.5f);
+    addParameter(m_min_points, "GlobalFeatureMinPoints", 500);
     addParameter(m_vote_filtering_with_ransac, "RansacVoteFiltering", false);      // voting.cpp:47-50
     addParameter(m_refine_model, "RansacRefineModel", false);
     addParameter(m_inlier_threshold, "RansacInlierThreshold", 0.1f);
@@ -1017,22 +1220,127 @@ void Voting::fillRansacParams(DeviceSession& s, const std::vector<float>& class_
     R.seed = 12345ull;                                         // PCL seeds every cluster's generator with 12345; the draws are this library's
 }
 void Voting::clear() {}
-std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s) {
-    if (m_use_global_features) throw RuntimeException("UseGlobalFeatures is out of scope of the MI355X path (SURVEY §2 row 10)");
+std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds) {
     if (m_max_filter_type != "None" && m_max_filter_type != "Simple" && m_max_filter_type != "Merge")
         LOG_ERROR("Invalid maxima filter type specified: " << m_max_filter_type << "! No filtering is performed!");            // maxima_handler.cpp:292-295
     if (m_max_type_param != "None" && m_max_type_param != "Default" && m_max_type_param != "BandwidthVotes" && m_max_type_param != "VotingSpaceVotes" &&
         m_max_type_param != "ModelRadiusVotes")
         LOG_WARN("Invalid single object maximum type: " << m_max_type_param << "! Using default instead.");                   // maxima_handler.h:53-57
     std::vector<std::vector<VotingMaximum>> out(s.n_obj);
-    if (s.n_slots == 0) return out;
+    if (s.n_slots == 0) {                                      // no vote in the whole batch: no maxima; the global step may still speak
+        if (m_use_global_features) verifyWithGlobalFeatures(s, metric, clouds, out);
+        return out;
+    }
     if (singleObjectMaxType() != ISMHIP_SOM_MEANSHIFT) {       // voting_mean_shift.cpp:124-157: the query point is the centroid of the object's cloud
         s.obj_cen.reserve((size_t)s.n_obj * 12); s.obj_rad.reserve((size_t)s.n_obj * 4);
         s.check(ismhip_cloud_centroids(s.ctx, s.cloud, s.obj_cen.as<float>()), "ismhip_cloud_centroids");
         s.check(ismhip_cloud_radii(s.ctx, s.cloud, s.obj_cen.as<float>(), s.obj_rad.as<float>()), "ismhip_cloud_radii");
     }
     iFindMaxima(s, out);
+    if (m_use_global_features) verifyWithGlobalFeatures(s, metric, clouds, out);
     return out;
+}
+static void cloudAABB(const PointCloud& c, std::array<float, 3>& center, std::array<float, 3>& size);
+// The global step of Voting::findMaxima (voting.cpp:217-298) for a whole batch: one region per object (single-object mode) or per
+// maximum (its position, the class's median box edge as radius: global_radii, voting.cpp:634), ALL regions in one device call, one exact
+// kNN call on the stored training rows, then classifyWithKNN and the merge sequence on the host.
+void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds, std::vector<std::vector<VotingMaximum>>& out) {
+    if (!m_global_descriptor) throw RuntimeException("UseGlobalFeatures needs a built GlobalFeatures type (built: " + std::string(GlobalFeatures::builtTypes()) + ")");
+    // the stored rows in the order the reference concatenates them (voting.cpp:660-701): class, cloud, row
+    std::vector<float> rows; std::vector<unsigned> row_class, row_inst;
+    const int D = m_global_descriptor->getDescriptorLength();
+    for (auto& it : m_global_features) for (auto& cloud : it.second) for (auto& f : cloud) {
+        if ((int)f.descriptor.size() != D)
+            throw RuntimeException("the model's stored global features have " + std::to_string(f.descriptor.size()) + " dimensions, the configured GlobalFeatures type " + std::to_string(D));
+        rows.insert(rows.end(), f.descriptor.begin(), f.descriptor.end()); row_class.push_back(it.first); row_inst.push_back(f.instanceId);
+    }
+    const int n_rows = (int)row_class.size();
+    if (n_rows == 0) throw RuntimeException("UseGlobalFeatures: the model holds no global features (train it with a built GlobalFeatures type)");
+    const int K = std::min(std::max(m_k_global_features, 1), n_rows);                // FLANN returns what there is: clamp to the stored rows
+    if (K > ISMHIP_KNN_LARGE_K_MAX) throw RuntimeException("GlobalFeaturesK " + std::to_string(K) + " is not built (ismhip_knn_large_k: up to " + std::to_string(ISMHIP_KNN_LARGE_K_MAX) + ")");
+    if (D > ISMHIP_SHORT_CSHOT_MAX_DIM) throw RuntimeException("global descriptor length " + std::to_string(D) + " is not built (ismhip_knn: up to " + std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + ")");
+    // regions
+    std::vector<int32_t> r_obj, r_max; std::vector<float> r_cen, r_rad;
+    for (int o = 0; o < s.n_obj; ++o) {
+        if (m_single_object_mode) { r_obj.push_back(o); r_max.push_back(-1); r_cen.insert(r_cen.end(), 3, 0.f); r_rad.push_back(-1.f); continue; }
+        for (size_t i = 0; i < out[o].size(); ++i) {
+            const VotingMaximum& m = out[o][i];
+            auto dim = m_dimensions_map.find(m.classId);
+            r_obj.push_back(o); r_max.push_back((int32_t)i);
+            r_cen.insert(r_cen.end(), m.position.begin(), m.position.end());
+            r_rad.push_back(dim == m_dimensions_map.end() ? 0.f : dim->second.second);      // a class without dimensions selects nothing
+        }
+    }
+    GlobalDump dump; dump.k = K; dump.dim = D; dump.region_obj = r_obj; dump.region_max = r_max;
+    dump.max_off.assign(1, 0u);
+    for (int o = 0; o < s.n_obj; ++o) {
+        for (const VotingMaximum& m : out[o]) {
+            dump.max_cls.push_back((int32_t)m.classId); dump.max_inst.push_back((int32_t)m.instanceId); dump.max_w.push_back(m.weight); dump.max_iw.push_back(m.instanceWeight);
+            dump.max_pos.insert(dump.max_pos.end(), m.position.begin(), m.position.end());
+        }
+        dump.max_off.push_back((uint32_t)dump.max_cls.size());
+    }
+    const int R = (int)r_obj.size();
+    std::vector<VotingMaximum::GlobalHypothesis> hyp((size_t)R);
+    if (R > 0) {
+        GlobalRegions G; G.set(r_obj, r_cen, r_rad, D);
+        m_global_descriptor->describe(s, G);
+        std::vector<float> desc;
+        s.d2h(dump.n_sel, G.n_sel, (size_t)R); s.d2h(dump.centroid, G.centroid, (size_t)R * 3); s.d2h(dump.radius, G.radius, (size_t)R); s.d2h(desc, G.desc, (size_t)R * D);
+        dump.desc = desc;
+        // which regions are classified: enough points (classify(), global_classifier.cpp:181; single-object mode passes -1) and a row.
+        // The others get the zero-weight hypothesis of :229-239; their query row is zeroed so that the search sees no NaN.
+        std::vector<uint8_t> live((size_t)R, 0);
+        for (int r = 0; r < R; ++r) {
+            const bool enough = m_single_object_mode || (int)dump.n_sel[r] > m_min_points || m_min_points < 0;
+            live[r] = enough && !std::isnan(desc[(size_t)r * D]);
+            if (!live[r]) std::fill(desc.begin() + (size_t)r * D, desc.begin() + (size_t)(r + 1) * D, 0.f);
+        }
+        DevBuf q, idx, dist;
+        DeviceSession::h2d(q, desc);
+        idx.reserve((size_t)R * K * 4); dist.reserve((size_t)R * K * 4);
+        const TempCodebook cb = searchOnlyCodebook(s, (uint32_t)n_rows, D, rows.data());
+        if (K <= 16) s.check(ismhip_knn(s.ctx, cb.get(), metric, R, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn (global features)");
+        else s.check(ismhip_knn_large_k(s.ctx, cb.get(), metric, R, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn_large_k (global features)");
+        s.d2h(dump.knn_idx, idx, (size_t)R * K); s.d2h(dump.knn_dist, dist, (size_t)R * K);
+        for (int r = 0; r < R; ++r) {
+            const VotingMaximum* m = r_max[r] >= 0 ? &out[r_obj[r]][r_max[r]] : nullptr;
+            VotingMaximum::GlobalHypothesis g;
+            g.classId = m ? m->classId : (unsigned)-1; g.instanceId = m ? m->instanceId : (unsigned)-1;      // the zero-weight hypothesis
+            if (live[r]) {
+                std::vector<unsigned> nc((size_t)K), ni((size_t)K);
+                for (int j = 0; j < K; ++j) { const int32_t w = dump.knn_idx[(size_t)r * K + j]; nc[j] = row_class[w]; ni[j] = row_inst[w]; }
+                g = classifyWithKNN(K, nc.data(), ni.data(), &dump.knn_dist[(size_t)r * K], g.classId, m_single_object_mode);
+            }
+            hyp[r] = g;
+            dump.hyp_id.push_back(g.classId); dump.hyp_id.push_back(g.instanceId); dump.hyp_w.push_back(g.classWeight); dump.hyp_w.push_back(g.instanceWeight);
+        }
+    }
+    // hypotheses onto the maxima
+    for (int r = 0; r < R; ++r) {
+        const int o = r_obj[r];
+        if (!m_single_object_mode) {
+            VotingMaximum& m = out[o][r_max[r]];
+            m.globalHypothesis = hyp[r];
+            if (dump.n_sel[r] > 0) m.roiCentroid = {dump.centroid[(size_t)r * 3], dump.centroid[(size_t)r * 3 + 1], dump.centroid[(size_t)r * 3 + 2]};
+            continue;
+        }
+        for (VotingMaximum& m : out[o]) m.globalHypothesis = hyp[r];                 // voting.cpp:246-247
+        if (out[o].empty() && dump.n_sel[r] > 0) {                                   // :250-260; the box is axis-aligned (MVBB is not built)
+            VotingMaximum m;
+            m.globalHypothesis = hyp[r];
+            m.classId = hyp[r].classId; m.weight = hyp[r].classWeight; m.instanceId = hyp[r].instanceId;
+            m.position = {dump.centroid[(size_t)r * 3], dump.centroid[(size_t)r * 3 + 1], dump.centroid[(size_t)r * 3 + 2]};
+            m.boundingBox.position = m.position;
+            if (clouds && (size_t)o < clouds->size() && !(*clouds)[o]->empty()) cloudAABB(*(*clouds)[o], m.boundingBox.position, m.boundingBox.size);
+            out[o].push_back(m);
+        }
+    }
+    MergeParams P;
+    P.function = m_merge_function; P.radius = mergeRadius(); P.min_threshold = m_minThreshold; P.best_k = m_bestK;
+    P.min_svm_score = m_min_svm_score; P.rate_limit = m_rate_limit; P.weight_factor = m_weight_factor;
+    for (int o = 0; o < s.n_obj; ++o) mergeSequence(out[o], P);
+    m_last_global = dump;
 }
 int Voting::singleObjectMaxType() const {                      // maxima_handler.h:42-58; only consulted in single-object mode (voting_mean_shift.cpp:80)
     if (!m_single_object_mode) return ISMHIP_SOM_MEANSHIFT;
@@ -1056,6 +1364,8 @@ template <typename Params, typename Entry, typename RansacEntry>
 void Voting::searchMaxima(DeviceSession& s, Params P, Entry entry, RansacEntry ransac_entry, const char* what, std::vector<std::vector<VotingMaximum>>& out) const {
     P.n_classes = std::max(1, s.n_classes);
     P.min_votes_threshold = m_minVotesThreshold; P.min_threshold = m_minThreshold; P.best_k = m_bestK;
+    // with global verification the device does the first normalisation only: MinThreshold and BestK close the host's merge sequence
+    if (m_use_global_features) { P.min_threshold = 0.f; P.best_k = -1; }
     P.max_filter = maxFilter();
     for (int M : {32, 1024}) {
         MaximaBuffers B; B.M = M; B.reserve(s.n_obj, P.n_classes);
@@ -1383,6 +1693,19 @@ bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
     m_clustering.reset(Factory<Clustering>::create(*cl));
     m_feature_ranking.reset(Factory<FeatureRanking>::create(*fw));
     if (const Json* gf = c.find("GlobalFeatures")) m_global_features_cfg = *gf;
+    // the GlobalFeatures child: an object for the built types, the JSON carried through for every other one (an absent child is the
+    // reference's Dummy); what is not built is refused by name, but only when the configuration asks for global verification
+    m_global_descriptor.reset(GlobalFeatures::createIfBuilt(m_global_features_cfg));
+    if (m_voting && m_voting->useGlobalFeatures()) {
+        if (m_voting->globalStrategy() != "KNN")
+            throw RuntimeException("Voting.GlobalFeaturesStrategy \"" + m_voting->globalStrategy() + "\" is not built (built: KNN; the reference's SVM needs OpenCV and is not downgraded to KNN)");
+        if (!m_global_descriptor) {
+            const Json* t = m_global_features_cfg.isObject() ? m_global_features_cfg.find("Type") : nullptr;
+            const std::string type = t && t->type == Json::String ? t->str : std::string("Dummy");
+            throw RuntimeException("Voting.UseGlobalFeatures with GlobalFeatures type \"" + type + "\" is not built (built: " + GlobalFeatures::builtTypes() + ")");
+        }
+    }
+    if (m_voting) m_voting->setGlobalFeatureDescriptor(m_global_descriptor.get());
     if (m_use_smoothing || m_use_voxel_filtering) throw RuntimeException("point cloud pre-filters smoothing (UseSmoothing) and voxel filtering (UseVoxelFiltering) are not built");
     if (m_use_sor && (m_sor_mean_k < 1 || m_sor_mean_k > ISMHIP_SOR_MAX_MEAN_K))
         throw RuntimeException("OutlierRemovalMeanK " + std::to_string(m_sor_mean_k) + " is not built (built: 1 .. " + std::to_string(ISMHIP_SOR_MAX_MEAN_K) + ")");
@@ -1678,6 +2001,7 @@ void ImplicitShapeModel::train() {                // :252-500
     std::vector<float> hdesc, hlrf, hkx, hky, hkz;
     std::vector<unsigned> fclass, finst, fmodel; std::vector<std::array<float, 3>> fcenter, fbox;
     std::map<unsigned, std::vector<std::array<float, 3>>> box_sizes; std::map<unsigned, std::vector<float>> object_radii;
+    Voting::GlobalFeatureMap global_features;                   // :267, :394-415: one list per training cloud, NaN rows dropped
     const size_t chunk = 32;
     const int D = m_feature_descriptor->getDescriptorLength();
     for (size_t b = 0; b < clouds.size(); b += chunk) {
@@ -1695,6 +2019,25 @@ void ImplicitShapeModel::train() {                // :252-500
         auto append = [&](std::vector<float>& dst, const DevBuf& src, size_t n) { std::vector<float> t; s.d2h(t, src, n); dst.insert(dst.end(), t.begin(), t.end()); };
         append(hdesc, f->desc, (size_t)f->n * D); append(hlrf, f->lrf, (size_t)f->n * 9);
         append(hkx, f->kx, f->n); append(hky, f->ky, f->n); append(hkz, f->kz, f->n);
+        // global features (:908-919, in training always): one whole-object region per cloud of the chunk, on the search surface the
+        // local descriptors have just used
+        std::vector<uint32_t> g_nsel; std::vector<float> g_rad, g_lrf, g_desc;
+        const int GD = m_global_descriptor ? m_global_descriptor->getDescriptorLength() : 0;
+        if (m_global_descriptor && !live.empty()) {
+            std::vector<int32_t> r_obj(live.size()); std::iota(r_obj.begin(), r_obj.end(), 0);
+            GlobalRegions G; G.set(r_obj, std::vector<float>(live.size() * 3, 0.f), std::vector<float>(live.size(), -1.f), GD);
+            m_global_descriptor->describe(s, G);
+            s.d2h(g_nsel, G.n_sel, live.size()); s.d2h(g_rad, G.radius, live.size()); s.d2h(g_lrf, G.lrf, live.size() * 9); s.d2h(g_desc, G.desc, live.size() * GD);
+        }
+        for (size_t o = 0; m_global_descriptor && o < part.size(); ++o) {
+            global_features[obj_class[b + o]].emplace_back();
+            const int l = live_of[o];
+            if (l < 0 || std::isnan(g_desc[(size_t)l * GD])) continue;              // removeNaNFeatures: the rows are NaN as a whole
+            StoredGlobalFeature gf; gf.classId = obj_class[b + o]; gf.instanceId = obj_inst[b + o]; gf.radius = g_rad[l];
+            std::copy(g_lrf.begin() + (size_t)l * 9, g_lrf.begin() + (size_t)(l + 1) * 9, gf.rf);
+            gf.descriptor.assign(g_desc.begin() + (size_t)l * GD, g_desc.begin() + (size_t)(l + 1) * GD);
+            global_features[obj_class[b + o]].back().push_back(gf);
+        }
         for (size_t o = 0; o < part.size(); ++o) {
             std::array<float, 3> center, bsize;
             cloudAABB(*part[o], center, bsize);
@@ -1729,6 +2072,7 @@ void ImplicitShapeModel::train() {                // :252-500
     DeviceSession::h2d(all->desc, hdesc); DeviceSession::h2d(all->lrf, hlrf); DeviceSession::h2d(all->kx, hkx); DeviceSession::h2d(all->ky, hky); DeviceSession::h2d(all->kz, hkz);
     LOG_INFO("activating codewords with " << all->n << " training features");
     m_voting->forwardBoxesAndRadii(box_sizes, object_radii);     // :433: bandwidth hints per class, persisted with the model
+    m_voting->forwardGlobalFeatures(global_features);            // :435
     LOG_INFO("clustering");                                      // :445-449
     if (!m_clustering) m_clustering.reset(new ClusteringNone());
     (*m_clustering)(s, *all, met);
@@ -1764,7 +2108,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     m_last_detect = f;
     stage.lap("voting");
     LOG_INFO("finding maxima");
-    auto res = m_voting->findMaxima(s);
+    auto res = m_voting->findMaxima(s, metric(), &nonempty);
     stage.lap("maxima");
     complete.lap("complete");
     m_processing_times["normals"] += 0; m_processing_times["flann"] += 0;

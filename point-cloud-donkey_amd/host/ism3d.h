@@ -149,10 +149,51 @@ struct VotingMaximum {        // voting/voting_maximum.h:51-88
     float instanceWeight = 0;
     BoundingBox boundingBox;
     int numVotes = 0;
+    // the global classifier's answer for this maximum (voting_maximum.h:74-87); Voting.UseGlobalFeatures only
+    struct GlobalHypothesis { unsigned classId = 0; float classWeight = 0; unsigned instanceId = 0; float instanceWeight = 0; };
+    GlobalHypothesis globalHypothesis;
+    // centroid of the region the hypothesis was computed on (detection mode; zeros in single-object mode). The reference keeps ONE
+    // roi_centroid written by every maximum inside an OMP loop (voting.cpp:91, 226-229); here every maximum carries its own.
+    std::array<float, 3> roiCentroid{{0, 0, 0}};
 };
 
 class DeviceSession;          // ctx + device buffers (ism3d.cpp)
 struct DeviceFeatures;        // device-resident ISMFeature batch: descriptors, LRFs, keypoints, per-object offsets
+
+// ---- global descriptors (the GlobalFeatures child; features/features_short_shot_global.cpp, features_shot_global.cpp) ------------
+// One row per REGION of the batch's search surface (ismhip_global_short_shot / ismhip_global_shot352): the whole object in training and
+// in single-object mode, a ball round a maximum in detection mode. Any other type of the reference stays a pass-through of its JSON
+// (no object is created) and is refused by name only when Voting.UseGlobalFeatures asks for it.
+struct GlobalRegions;          // device arrays of a region batch and its outputs (ism3d.cpp)
+class GlobalFeatures : public JSONObject {
+public:
+    virtual ~GlobalFeatures() {}
+    virtual int getDescriptorLength() const = 0;
+    virtual void describe(DeviceSession& s, GlobalRegions& r) const = 0;     // fills r's outputs for r's regions on s.cloud
+    static const char* builtTypes() { return "SHORT_SHOT_GLOBAL, SHOT_GLOBAL"; }
+    static GlobalFeatures* createIfBuilt(const Json& object);                // nullptr for a type that is not built (or no object)
+};
+class GlobalFeaturesShortShot : public GlobalFeatures {      // features_short_shot_global.cpp:21-30, 168-249
+public:
+    GlobalFeaturesShortShot();
+    static std::string getTypeStatic() { return "SHORT_SHOT_GLOBAL"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getDescriptorLength() const override { return m_r_bins * m_e_bins * m_a_bins; }
+    void describe(DeviceSession& s, GlobalRegions& r) const override;
+protected:
+    void iPostInitConfig() override;                         // configureSphericalGrid
+private:
+    double m_min_radius; int m_feature_dims; bool m_log_radius; int m_r_bins, m_e_bins, m_a_bins; std::string m_bin_type;
+};
+class GlobalFeaturesShot : public GlobalFeatures {           // features_shot_global.cpp
+public:
+    static std::string getTypeStatic() { return "SHOT_GLOBAL"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getDescriptorLength() const override { return 352; }
+    void describe(DeviceSession& s, GlobalRegions& r) const override;
+};
+// one stored training row (ISMFeature of voting.cpp:586-613, 660-701)
+struct StoredGlobalFeature { unsigned classId = 0, instanceId = 0; float rf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; std::vector<float> descriptor; float radius = 0; };
 
 // ---- Keypoints (keypoints/keypoints.h) -----------------------------------------------------------------
 class Keypoints : public JSONObject {
@@ -507,8 +548,28 @@ class Voting : public JSONObject {
 public:
     Voting();
     virtual ~Voting() {}
-    // Voting::findMaxima for every object of the batch (voting.cpp:79-328)
-    std::vector<std::vector<VotingMaximum>> findMaxima(DeviceSession& s);
+    // Voting::findMaxima for every object of the batch (voting.cpp:79-328). metric and clouds (the batch's objects on the host, for the
+    // box of a hypothesis-only maximum) are read with UseGlobalFeatures only.
+    std::vector<std::vector<VotingMaximum>> findMaxima(DeviceSession& s, int metric = ISMHIP_METRIC_L2SQ, const std::vector<const PointCloud*>* clouds = nullptr);
+    // ---- global verification (voting.cpp:217-298; classifier/global_classifier.cpp) ----
+    bool useGlobalFeatures() const { return m_use_global_features; }
+    const std::string& globalStrategy() const { return m_global_feature_method; }
+    void setGlobalFeatureDescriptor(const GlobalFeatures* g) { m_global_descriptor = g; }
+    // Voting::forwardGlobalFeatures (voting.cpp:554-557): class -> one list per training cloud (empty when its row was NaN)
+    typedef std::map<unsigned, std::vector<std::vector<StoredGlobalFeature>>> GlobalFeatureMap;
+    void forwardGlobalFeatures(const GlobalFeatureMap& g) { m_global_features = g; }
+    const GlobalFeatureMap& getGlobalFeatures() const { return m_global_features; }
+    // GlobalClassifier::classifyWithKNN (:242-347) on the neighbours of one query, in the search's order
+    static VotingMaximum::GlobalHypothesis classifyWithKNN(int k, const unsigned* n_class, const unsigned* n_inst, const float* n_dist, unsigned max_class, bool single_object_mode);
+    // the merge sequence of voting.cpp:272-323 on maxima whose weights carry the first normalisation: normalizeWeights (except function
+    // 5), mergeGlobalAndLocalHypotheses, sort, erase zero weights, normalizeWeights, MinThreshold, BestK. Pure host code.
+    struct MergeParams { int function = 3; float radius = 0, min_threshold = 0; int best_k = -1; float min_svm_score = 0.70f, rate_limit = 0.60f, weight_factor = 1.5f; };
+    static void mergeSequence(std::vector<VotingMaximum>& maxima, const MergeParams& p);
+    // diagnostics (tests): what the global step of the last findMaxima saw and decided
+    struct GlobalDump { int k = 0, dim = 0; std::vector<int32_t> region_obj, region_max; std::vector<uint32_t> n_sel; std::vector<float> centroid, radius, desc;
+                        std::vector<int32_t> knn_idx; std::vector<float> knn_dist, hyp_w; std::vector<uint32_t> hyp_id;      // hyp_w / hyp_id: 2 per region
+                        std::vector<uint32_t> max_off; std::vector<int32_t> max_cls, max_inst; std::vector<float> max_w, max_iw, max_pos; };
+    const GlobalDump& lastGlobal() const { return m_last_global; }
     void clear();
     bool isSingleObjectMode() const { return m_single_object_mode; }
     bool refineModelRequested() const { return m_refine_model; }   // RansacRefineModel: refused when the config is read
@@ -525,6 +586,8 @@ protected:
     std::map<unsigned, std::pair<float, float>> m_dimensions_map, m_variance_map;
     friend class Codebook;
     virtual void iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) = 0;
+    virtual float mergeRadius() const = 0;                       // MaximaHandler::getRadius(): Bandwidth (mean shift), BinSize[0] / 2 (Hough)
+    void verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds, std::vector<std::vector<VotingMaximum>>& out);
     // device outputs of ismhip_find_maxima / ismhip_hough3d_maxima -> VotingMaximum lists
     struct MaximaBuffers;                                        // defined in ism3d.cpp (device buffers)
     static bool collectMaxima(DeviceSession& s, MaximaBuffers& b, std::vector<std::vector<VotingMaximum>>& out, bool with_quat);
@@ -540,6 +603,11 @@ protected:
     std::string m_radiusType; float m_radiusFactor; std::string m_max_filter_type, m_max_type_param;
     bool m_single_object_mode; bool m_use_global_features; bool m_vote_filtering_with_ransac;
     bool m_refine_model; float m_inlier_threshold; std::string m_inlier_threshold_type;      // RansacRefineModel, RansacInlierThreshold(Type)
+    std::string m_global_feature_method; int m_k_global_features, m_merge_function, m_min_points;             // voting.cpp:39-45
+    float m_min_svm_score, m_rate_limit, m_weight_factor;
+    const GlobalFeatures* m_global_descriptor = nullptr;         // owned by the model
+    GlobalFeatureMap m_global_features;
+    GlobalDump m_last_global;
 };
 class VotingHough3D : public Voting {             // voting/voting_hough_3d.{h,cpp}
 public:
@@ -548,6 +616,7 @@ public:
     std::string getType() const override { return getTypeStatic(); }
 protected:
     void iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) override;
+    float mergeRadius() const override { return (float)(m_binSize[0] / 2); }
 private:
     bool m_useInterpolation; Vec3d m_minCoord, m_maxCoord, m_binSize; float m_relThreshold;
 };
@@ -558,6 +627,7 @@ public:
     std::string getType() const override { return getTypeStatic(); }
 protected:
     void iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) override;
+    float mergeRadius() const override { return m_bandwidth; }
 private:
     float m_bandwidth, m_threshold; int m_maxIter; std::string m_kernel, m_maxima_suppression_type;
 };
@@ -606,6 +676,8 @@ public:
     // diagnostics (tests): a timer or counter of the device library's context (ismhip_timer_get); 0 before the first device call
     double deviceTimer(const std::string& name) const;
     const Voting* getVoting() const { return m_voting.get(); }
+    Voting* getVoting() { return m_voting.get(); }
+    const GlobalFeatures* getGlobalFeatures() const { return m_global_descriptor.get(); }
     const Features* getFeatures() const { return m_feature_descriptor.get(); }
     void setSignalsState(bool) {}
     void setLogging(bool l) { m_logging = l; }
@@ -657,7 +729,8 @@ private:
     std::unique_ptr<Voting> m_voting;
     std::unique_ptr<Clustering> m_clustering;
     std::unique_ptr<FeatureRanking> m_feature_ranking;
-    Json m_global_features_cfg;
+    Json m_global_features_cfg;                                  // the GlobalFeatures child as read: written back unchanged
+    std::unique_ptr<GlobalFeatures> m_global_descriptor;         // the object of a built type (nullptr: pass-through)
     std::map<unsigned, std::vector<std::shared_ptr<PointCloud>>> m_training_clouds;     // class -> models
     std::map<unsigned, std::vector<unsigned>> m_training_instances;
     std::map<unsigned, std::string> m_class_labels, m_instance_labels;
