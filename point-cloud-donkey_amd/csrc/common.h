@@ -296,6 +296,43 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffffull), 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
     return ((unsigned long long)hi << 32) | lo;
 }
+// wave-wide maxima and the 64-bit sum, the same way (identity: -inf / 0)
+__device__ __forceinline__ float wave_max_f(float v) {        // NaN-free inputs or NaN-last semantics of fmaxf
+    const int ninf = (int)0xff800000;
+    v = fmaxf(v, __int_as_float(dpp_movi<0xb1>(ninf, __float_as_int(v))));
+    v = fmaxf(v, __int_as_float(dpp_movi<0x4e>(ninf, __float_as_int(v))));
+    v = fmaxf(v, __int_as_float(dpp_movi<0x114>(ninf, __float_as_int(v))));
+    v = fmaxf(v, __int_as_float(dpp_movi<0x118>(ninf, __float_as_int(v))));
+    v = fmaxf(v, __int_as_float(dpp_movi<0x142>(ninf, __float_as_int(v))));
+    v = fmaxf(v, __int_as_float(dpp_movi<0x143>(ninf, __float_as_int(v))));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    v = max(v, (uint32_t)dpp_mov0<0xb1>((int)v)); v = max(v, (uint32_t)dpp_mov0<0x4e>((int)v)); v = max(v, (uint32_t)dpp_mov0<0x114>((int)v));
+    v = max(v, (uint32_t)dpp_mov0<0x118>((int)v)); v = max(v, (uint32_t)dpp_mov0<0x142>((int)v)); v = max(v, (uint32_t)dpp_mov0<0x143>((int)v));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_mov0_u64(unsigned long long v) {
+    const unsigned lo = (unsigned)dpp_mov0<CTRL>((int)(unsigned)(v & 0xffffffffull)), hi = (unsigned)dpp_mov0<CTRL>((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long readlane63_u64(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v & 0xffffffffull), 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_max_u64(unsigned long long v) { const unsigned long long o = dpp_mov0_u64<CTRL>(v); return o > v ? o : v; }
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    v = dpp_max_u64<0xb1>(v); v = dpp_max_u64<0x4e>(v); v = dpp_max_u64<0x114>(v);
+    v = dpp_max_u64<0x118>(v); v = dpp_max_u64<0x142>(v); v = dpp_max_u64<0x143>(v);
+    return readlane63_u64(v);
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+    v += dpp_mov0_u64<0xb1>(v); v += dpp_mov0_u64<0x4e>(v); v += dpp_mov0_u64<0x114>(v);
+    v += dpp_mov0_u64<0x118>(v); v += dpp_mov0_u64<0x142>(v); v += dpp_mov0_u64<0x143>(v);
+    return readlane63_u64(v);
+}
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     int x = (int)v;
     x += dpp_mov0<0x111>(x); x += dpp_mov0<0x112>(x); x += dpp_mov0<0x114>(x); x += dpp_mov0<0x118>(x);
@@ -331,6 +368,28 @@ struct BlockScan {
     }
     __device__ __forceinline__ uint32_t total() const { return carry; }
 };
+// Ordered compaction by ONE workgroup of NT threads, a chunk of NT entries per step: step(flag, total) returns the number of flagged
+// threads in front of this one over all chunks so far -- the position of a flagged thread's entry in the compacted list -- and adds
+// the chunk's flagged threads to `total`, a register that every thread keeps (0 before the first step). Lives in LDS like BlockScan
+// and has the same precondition: every thread of the workgroup calls step() for every chunk. Two barriers per step, the second after
+// the last read, so the next step (or another user of the same object) may follow at once. What the caller stores at the returned
+// positions is the caller's to publish: a barrier after the last step, where other threads read the list.
+template <int NT>
+struct BlockRank {
+    uint32_t wave[NT / 64];   // flagged threads of this chunk's waves
+    __device__ __forceinline__ uint32_t step(bool flag, uint32_t& total) {
+        const unsigned long long b = __ballot(flag);
+        const int w = threadIdx.x >> 6;
+        if (lane_id() == 0) wave[w] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = total, chunk = 0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; ++k) { const uint32_t c = wave[k]; chunk += c; if (k < w) before += c; }
+        __syncthreads();
+        total += chunk;
+        return before + (uint32_t)__popcll(b & ((1ull << lane_id()) - 1ull));
+    }
+};
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov0_d(double v) {
     const long long b = __double_as_longlong(v);
@@ -348,6 +407,63 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), 63), hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+
+// ---- workgroup reductions ---------------------------------------------------------------------------------------------------
+// block_<op><NW>(v, red): <op> over the NW waves (4: 256 threads, 16: 1024) of the workgroup, returned to every thread. `red` is the
+// caller's LDS scratch, one slot per wave; the helpers declare no __shared__ of their own. One barrier discipline: wave reduce (DPP),
+// lane 0 writes its slot, barrier, every thread reads and combines the NW slots, barrier -- so the same scratch serves the next call
+// at once and no caller adds a barrier for the helper. Its two barriers also order the caller's own LDS traffic round the call.
+// Precondition: every thread of the workgroup calls, from uniform control flow (a thread with nothing to add passes the identity).
+// block_fold combines the slots left to right: r = ((red[0] . red[1]) . red[2]) . red[3]
+template <int NW, class T, class F>
+__device__ __forceinline__ T block_fold(T wave_total, T* red, F&& combine) {
+    if (lane_id() == 0) red[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    T r = red[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) r = combine(r, red[k]);
+    __syncthreads();
+    return r;
+}
+// order-free combines: integer sums (T = int or uint32_t), minima and maxima
+template <int NW = 4, class T>
+__device__ __forceinline__ T block_sum_i(T v, T* red) { return block_fold<NW>((T)wave_sum_i((int)v), red, [](T a, T b) { return (T)(a + b); }); }
+template <int NW = 4>
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
+    return block_fold<NW>(wave_sum_u64(v), red, [](unsigned long long a, unsigned long long b) { return a + b; });
+}
+template <int NW = 4>
+__device__ __forceinline__ float block_min_f(float v, float* red) { return block_fold<NW>(wave_min_f(v), red, [](float a, float b) { return fminf(a, b); }); }
+template <int NW = 4>
+__device__ __forceinline__ float block_max_f(float v, float* red) { return block_fold<NW>(wave_max_f(v), red, [](float a, float b) { return fmaxf(a, b); }); }
+template <int NW = 4>
+__device__ __forceinline__ uint32_t block_max_u32(uint32_t v, uint32_t* red) { return block_fold<NW>(wave_max_u32(v), red, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); }
+template <int NW = 4>
+__device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v, unsigned long long* red) {
+    return block_fold<NW>(wave_min_u64(v), red, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
+}
+template <int NW = 4>
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* red) {
+    return block_fold<NW>(wave_max_u64(v), red, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });
+}
+// Float and double sums come in two associations of the wave partials, and results that are promised bit for bit depend on which:
+//  * left fold ((r0 + r1) + r2) + r3: the grid build's coordinate sums (grid.hip: GridMeta::centroid), which a region of global.hip
+//    must reproduce, every double sum of global.hip, and the mean / variance of k_sor_threshold (prefilter.hip)
+//  * pairwise (r0 + r1) + (r2 + r3), 256 threads: the per-maximum sums of maxima.hip (weights, positions, box and quaternion sums) and
+//    the covariance of the RANSAC sample-distance threshold (ransac.h), restated in that order by their host models
+// A call site keeps the one it has; a new one that promises nothing takes the left fold.
+template <int NW = 4>
+__device__ __forceinline__ double block_sum_d_left(double v, double* red) { return block_fold<NW>(wave_sum_d(v), red, [](double a, double b) { return a + b; }); }
+template <class T>
+__device__ __forceinline__ T block_sum_pairwise(T wave_total, T* red) {
+    if (lane_id() == 0) red[threadIdx.x >> 6] = wave_total;
+    __syncthreads();
+    const T r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ float block_sum_f_pairwise(float v, float* red) { return block_sum_pairwise(wave_sum_f(v), red); }
+__device__ __forceinline__ double block_sum_d_pairwise(double v, double* red) { return block_sum_pairwise(wave_sum_d(v), red); }
 
 // atan2 to ~1e-7 absolute (Abramowitz & Stegun 4.4.49, |err| <= 2e-8 before rounding) without OCML's expansion: for weights that are
 // continuous in the angle (shot.hip) and for estimates whose hard decisions are re-taken exactly when they come close (short_shot.hip)

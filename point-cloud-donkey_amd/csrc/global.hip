@@ -15,7 +15,7 @@
 //   4. the two sign votes (integers); on a tie the five median neighbours by (d^2, original index) decide, found by bitwise bisection
 //      over the 64-bit keys with one more sweep of the span per bit -- no key store, so the region may hold any number of points
 //   5. the histogram: per-wave LDS copies of INTEGER bins (counts, or SHOT's 2^-28 fixed point), merged as integers, then the norm
-// Every reduction is a fixed-order tree in double (per thread in index order, DPP wave sum, the four waves in order) or an integer sum;
+// Every reduction is a fixed-order tree in double (per thread in index order, DPP wave sum, the four waves in order: block_sum_d_left, common.h) or an integer sum;
 // there is no float atomic: two calls give the same bits in every output.
 //
 // Byte model per region: 5 sweeps x 16 B x n_obj_points (6 for SHOT-352: + 16 B per descriptor neighbour for its normal), the first
@@ -52,42 +52,6 @@ struct GlobalSmem {
     shot_bin_t hist[SHOT ? 4 * 352 : 1];
     uint32_t cnt[SHOT ? 1 : 4 * ISMHIP_SHORT_SHOT_MAX_DIM];
 };
-
-// Fixed-order block reductions of a 256-thread workgroup; every thread gets the result. All threads must call them.
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    v = wave_sum_d(v);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ uint32_t block_sum_u(uint32_t v, uint32_t* red) {
-    v = (uint32_t)wave_sum_i((int)v);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t s = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ float block_max_f(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float s = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ unsigned long long block_min_k(unsigned long long v, unsigned long long* red) {
-    v = wave_min_u64(v);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned long long s = red[0];
-    for (int k = 1; k < 4; ++k) s = red[k] < s ? red[k] : s;
-    __syncthreads();
-    return s;
-}
 
 // int(double) as the reference's x86-64 build takes it (cvttsd2si): NaN and values outside int give INT_MIN, which the clamps that
 // follow turn into bin 0 (r) or drop (theta, phi: the bin index is checked against the row)
@@ -136,8 +100,8 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
             const float4 p = sp[i];
             if (selected(p)) { sx += (double)p.x; sy += (double)p.y; sz += (double)p.z; c++; }
         }
-        nsel = block_sum_u(c, sm.red_u);
-        sx = block_sum_d(sx, sm.red_d); sy = block_sum_d(sy, sm.red_d); sz = block_sum_d(sz, sm.red_d);
+        nsel = block_sum_i(c, sm.red_u);
+        sx = block_sum_d_left(sx, sm.red_d); sy = block_sum_d_left(sy, sm.red_d); sz = block_sum_d_left(sz, sm.red_d);
         cx = (float)(sx / (double)nsel); cy = (float)(sy / (double)nsel); cz = (float)(sz / (double)nsel);   // pcl::compute3DCentroid
     }
     if (tid == 0) a.n_sel[reg] = nsel;
@@ -181,10 +145,10 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
             c11 = fma(wy, vy, c11); c12 = fma(wy, vz, c12); c22 = fma(wz, vz, c22);
             sum += w; valid++;
         }
-        c00 = block_sum_d(c00, sm.red_d); c01 = block_sum_d(c01, sm.red_d); c02 = block_sum_d(c02, sm.red_d);
-        c11 = block_sum_d(c11, sm.red_d); c12 = block_sum_d(c12, sm.red_d); c22 = block_sum_d(c22, sm.red_d);
-        sum = block_sum_d(sum, sm.red_d);
-        const uint32_t nvalid = block_sum_u(valid, sm.red_u);
+        c00 = block_sum_d_left(c00, sm.red_d); c01 = block_sum_d_left(c01, sm.red_d); c02 = block_sum_d_left(c02, sm.red_d);
+        c11 = block_sum_d_left(c11, sm.red_d); c12 = block_sum_d_left(c12, sm.red_d); c22 = block_sum_d_left(c22, sm.red_d);
+        sum = block_sum_d_left(sum, sm.red_d);
+        const uint32_t nvalid = block_sum_i(valid, sm.red_u);
         if (tid == 0) {
             bool bad = nvalid < 5u;                                                // shot_na_lrf.hpp:80-86
             double w[3], V[3][3];
@@ -213,8 +177,8 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
             if (vx * v1[0] + vy * v1[1] + vz * v1[2] >= 0) pt++;
             if (vx * v3[0] + vy * v3[1] + vz * v3[2] >= 0) pn++;
         }
-        const int plusT = 2 * (int)block_sum_u(pt, sm.red_u) - (int)nvalid;
-        const int plusN = 2 * (int)block_sum_u(pn, sm.red_u) - (int)nvalid;
+        const int plusT = 2 * (int)block_sum_i(pt, sm.red_u) - (int)nvalid;
+        const int plusN = 2 * (int)block_sum_i(pn, sm.red_u) - (int)nvalid;
         if (plusT < 0) { v1[0] = -v1[0]; v1[1] = -v1[1]; v1[2] = -v1[2]; }
         if (plusN < 0) { v3[0] = -v3[0]; v3[1] = -v3[1]; v3[2] = -v3[2]; }
         if (plusT == 0 || plusN == 0) {                                            // workgroup-uniform
@@ -233,7 +197,7 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
                     float d2;
                     if (neighbour(p, d2) && frame_nb(p)) c += key_of(p, d2) < cand;
                 }
-                if (block_sum_u(c, sm.red_u) <= tsel) sel = cand;
+                if (block_sum_i(c, sm.red_u) <= tsel) sel = cand;
             }
             five[0] = sel;
             for (int j = 1; j < 5; ++j) {
@@ -245,7 +209,7 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
                     const unsigned long long kk = key_of(p, d2);
                     if (kk > five[j - 1] && kk < mn) mn = kk;
                 }
-                five[j] = block_min_k(mn, sm.red_k);
+                five[j] = block_min_u64(mn, sm.red_k);
             }
             int cntx = 0, cntz = 0;
             for (int j = 0; j < 5; ++j) {
@@ -279,7 +243,7 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
             total++;
             shot_neighbour<false>(a, hist, true, base + i, p.x - cx, p.y - cy, p.z - cz, d2, fx, fy, fz, r12, r14, r34, inv_r12, r12sq_f, 0.f, 0.f, 0.f);
         }
-        total = block_sum_u(total, sm.red_u);                                      // its barriers also publish the deposits
+        total = block_sum_i(total, sm.red_u);                                      // its barriers also publish the deposits
         if (total < 5u) { nan_row(false); return; }                               // computePointSHOT: fewer than 5 neighbours
         // normalizeHistogram: double accumulate of float squares, divide by float(norm)
         float v[2] = {0.f, 0.f};
@@ -293,7 +257,7 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
                 acc += (double)(v[j] * v[j]);
             }
         }
-        const float fn = (float)sqrt(block_sum_d(acc, sm.red_d));
+        const float fn = (float)sqrt(block_sum_d_left(acc, sm.red_d));
 #pragma unroll
         for (int j = 0; j < 2; ++j) { const int i = tid + 256 * j; if (i < 352) row[i] = v[j] / fn; }
     } else {
@@ -336,7 +300,7 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
         // the L2 norm (:151-161): double sum of squares (integers below 2^53: exact in any order), sqrt, double division, cast to float;
         // no contributing point gives 0 / 0: a NaN row
         const double cd = (double)c;
-        const double norm = sqrt(block_sum_d(cd * cd, sm.red_d));
+        const double norm = sqrt(block_sum_d_left(cd * cd, sm.red_d));
         if (tid < D) row[tid] = (float)(cd / norm);
     }
 }

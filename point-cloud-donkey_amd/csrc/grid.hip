@@ -55,39 +55,19 @@ __global__ __launch_bounds__(256) void k_bbox_meta(const uint32_t* __restrict__ 
         mn[2] = fminf(mn[2], pz); mx[2] = fmaxf(mx[2], pz);
         s[0] += px; s[1] += py; s[2] += pz; cnt++;
     }
-    __shared__ float s_mn[4][3], s_mx[4][3];
-    __shared__ double s_s[4][3];
-    __shared__ uint32_t s_c[4];
-    __shared__ int s_ncell;
+    __shared__ float s_f[4];
+    __shared__ double s_d[4];
+    __shared__ uint32_t s_u[4];
+    float lo[3], hi[3];
+    double ss[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], off, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-        }
-        s[a] = wave_sum_d(s[a]);
-    }
-    cnt = (uint32_t)wave_sum_i((int)cnt);
-    const int w = threadIdx.x >> 6;
-    if (lane_id() == 0) {
-        for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; s_s[w][a] = s[a]; }
-        s_c[w] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int ncell;
-        uint32_t c = 0; double ss[3] = {0, 0, 0};
-        float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-        for (int k = 0; k < 4; ++k) {
-            c += s_c[k];
-            for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], s_mn[k][a]); hi[a] = fmaxf(hi[a], s_mx[k][a]); ss[a] += s_s[k][a]; }
-        }
-        meta[o] = make_grid_meta(c, ss, lo, hi, req_cell, x_frac, ncell);
-        s_ncell = ncell;
-    }
-    __syncthreads();
+    for (int a = 0; a < 3; ++a) { lo[a] = block_min_f(mn[a], s_f); hi[a] = block_max_f(mx[a], s_f); ss[a] = block_sum_d_left(s[a], s_d); }
+    const uint32_t c = block_sum_i(cnt, s_u);
+    int ncell;
+    const GridMeta m = make_grid_meta(c, ss, lo, hi, req_cell, x_frac, ncell);    // every thread: the same arithmetic on the same values
+    if (threadIdx.x == 0) meta[o] = m;
     uint32_t* cs = cell_start + (size_t)o * ISM_GRID_STRIDE;
-    for (int i = threadIdx.x; i <= s_ncell; i += blockDim.x) cs[i] = 0u;
+    for (int i = threadIdx.x; i <= ncell; i += blockDim.x) cs[i] = 0u;
 }
 
 // counts points per cell; remembers each point's cell and its arrival rank inside the cell
@@ -152,11 +132,8 @@ __global__ __launch_bounds__(256) void k_cloud_radii(const uint32_t* __restrict_
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);
         if (d > m) m = d;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) radius[o] = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+    m = block_max_f(m, s_m);
+    if (threadIdx.x == 0) radius[o] = m;
 }
 
 __device__ __forceinline__ float4 rgba_to_lab4(uint32_t c4, const float* __restrict__ lut_srgb, const float* __restrict__ lut_sxyz) {
@@ -365,15 +342,11 @@ __global__ __launch_bounds__(GRID_FUSED_THREADS) void k_grid_fused(const uint32_
             }
         __syncthreads();
     }
-    if (t < 256) {                                            // whole waves: the DPP sums need all 64 lanes
+    // Not common.h's block reductions: only waves 0 .. 3 of the 16 hold partials. block_*<16> over identities gives the same bits, but
+    // the sixteen slots of ten reductions, all used by thread 0 alone, cost the kernel its second workgroup per CU (127 VGPRs).
+    if (t < 256) {                                            // whole waves: the DPP reductions need all 64 lanes
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            for (int off = 32; off > 0; off >>= 1) {
-                mn[a] = fminf(mn[a], __shfl_xor(mn[a], off, 64));
-                mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-            }
-            s[a] = wave_sum_d(s[a]);
-        }
+        for (int a = 0; a < 3; ++a) { mn[a] = wave_min_f(mn[a]); mx[a] = wave_max_f(mx[a]); s[a] = wave_sum_d(s[a]); }
         cnt = (uint32_t)wave_sum_i((int)cnt);
         if (lane_id() == 0) {
             const int w = (int)(t >> 6);
@@ -384,7 +357,7 @@ __global__ __launch_bounds__(GRID_FUSED_THREADS) void k_grid_fused(const uint32_
     __syncthreads();
     if (t == 0) {
         int ncell;
-        uint32_t c = 0; double ss[3] = {0, 0, 0};
+        uint32_t c = 0; double ss[3] = {0, 0, 0};             // left fold, as block_sum_d_left (k_bbox_meta)
         float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
         for (int k = 0; k < 4; ++k) {
             c += s_c[k];

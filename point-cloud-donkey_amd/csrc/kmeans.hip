@@ -56,13 +56,8 @@ __global__ __launch_bounds__(256) void k_km_closest(int n, int dim, int metric, 
             best = key > best ? key : best;
         }
     }
-    if (lane == 0) s_best[wv] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long b = s_best[0];
-        for (int w = 1; w < 4; ++w) b = s_best[w] > b ? s_best[w] : b;
-        if (b) atomicMax(&slot[step], b);
-    }
+    best = block_max_u64(best, s_best);
+    if (threadIdx.x == 0 && best) atomicMax(&slot[step], best);
 }
 __device__ __forceinline__ unsigned long long km_pot(float d, float dmax0) {
     if (!(d > 0.f) || !(dmax0 > 0.f)) return 0ull;
@@ -77,30 +72,21 @@ __global__ __launch_bounds__(256) void k_km_block_sums(int n, const float* __res
     const float dmax0 = __uint_as_float((uint32_t)(slot[1] >> 32));
     unsigned long long s = 0ull;
     for (int t = 0; t < 4; ++t) { const int i = blockIdx.x * 1024 + t * 256 + threadIdx.x; if (i < n) s += km_pot(closest[i], dmax0); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane_id() == 0) s_p[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+    s = block_sum_u64(s, s_p);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s;
 }
 // one workgroup: total potential T, draw r = floor(rng * T / 2^64), first index whose running sum exceeds r
 __global__ __launch_bounds__(1024) void k_km_select(int n, int nb, const unsigned long long* __restrict__ bsum, const float* __restrict__ closest,
                                                     const unsigned long long* __restrict__ slot, unsigned long long seed, int step, uint32_t* __restrict__ chosen) {
-    __shared__ unsigned long long s_w[16], s_total, s_r, s_base;
+    __shared__ unsigned long long s_w[16], s_r, s_base;
     __shared__ int s_blk;
     __shared__ uint32_t s_pick;
     if (chosen[step - 1] == KM_INVALID) { if (threadIdx.x == 0) chosen[step] = KM_INVALID; return; }
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     unsigned long long part = 0ull;
     for (int b = tid; b < nb; b += 1024) part += bsum[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-    if (lane == 0) s_w[wv] = part;
-    __syncthreads();
+    const unsigned long long T = block_sum_u64<16>(part, s_w);
     if (tid == 0) {
-        unsigned long long T = 0ull;
-        for (int w = 0; w < 16; ++w) T += s_w[w];
-        s_total = T;
         s_r = T ? __umul64hi(km_splitmix64(seed + (unsigned long long)step), T) : 0ull;
         // the block holding r (sequential over the block sums: nb <= n / 1024)
         unsigned long long run = 0ull; int blk = nb - 1;
@@ -108,14 +94,13 @@ __global__ __launch_bounds__(1024) void k_km_select(int n, int nb, const unsigne
         s_blk = blk; s_base = run; s_pick = KM_INVALID;
     }
     __syncthreads();
-    if (s_total == 0ull) { if (tid == 0) chosen[step] = KM_INVALID; return; }       // every point coincides with a chosen centre
+    if (T == 0ull) { if (tid == 0) chosen[step] = KM_INVALID; return; }       // every point coincides with a chosen centre
     const float dmax0 = __uint_as_float((uint32_t)(slot[1] >> 32));
     const int i = s_blk * 1024 + tid;
     const unsigned long long q = i < n ? km_pot(closest[i], dmax0) : 0ull;
     unsigned long long inc = q;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const unsigned long long t = __shfl_up(inc, d, 64); if (lane >= d) inc += t; }
-    __syncthreads();
     if (lane == 63) s_w[wv] = inc;
     __syncthreads();
     unsigned long long off = s_base;
@@ -162,8 +147,7 @@ __global__ void k_km_absmax(size_t tot, const float* __restrict__ desc, uint32_t
         const uint32_t b = __float_as_uint(desc[t]) & 0x7fffffffu;
         if (b <= 0x7f800000u) m = b > m ? b : m;                      // NaN payloads do not count
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t x = __shfl_xor(m, o, 64); m = x > m ? x : m; }
+    m = wave_max_u32(m);
     if (lane_id() == 0 && m) atomicMax(out_bits, m);
 }
 // integer sums of the members of every cluster; counts

@@ -81,15 +81,9 @@ __global__ void k_absmax(const float* __restrict__ src, int n, int dim, int ld, 
         const uint32_t b = __float_as_uint(src[(size_t)row * ld + col]) & 0x7fffffffu;
         m = b > m ? b : m;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)m, o, 64); m = t > m ? t : m; }
     __shared__ uint32_t s_m[4];                        // one atomic per workgroup: thousands of same-address atomics serialise
-    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
-        if (m) atomicMax(out_bits, m);
-    }
+    m = block_max_u32(m, s_m);
+    if (threadIdx.x == 0 && m) atomicMax(out_bits, m);
 }
 // sc[0] = absmax bits (in), sc[1] = -2 / (s * other_scale) (out), sc[2] = 2^-14 / s (out: worst-case absolute element error);
 // returns s. Thread 0 of the grid writes the two.
@@ -687,9 +681,7 @@ __global__ __launch_bounds__(256) void k_knn_fallback_merge(int k, const uint32_
         for (uint32_t i = lane; i < ni * P; i += 64)
             for (int j = 0; j < k; ++j) { const unsigned long long key = outp[KM * ((size_t)ibase * P + i) + j]; if (key != ~0ull) ins(key); }
         for (int j = 0; j < k; ++j) {
-            unsigned long long mn = fin[0];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = __shfl_xor(mn, o, 64); mn = x < mn ? x : mn; }
+            const unsigned long long mn = wave_min_u64(fin[0]);
             if (lane == 0) {
                 if (mn == ~0ull) { idx_out[(size_t)qi * k + j] = -1; dist_out[(size_t)qi * k + j] = __builtin_nanf(""); }
                 else { idx_out[(size_t)qi * k + j] = (int)(mn & 0xffffffffull); dist_out[(size_t)qi * k + j] = __uint_as_float((unsigned)(mn >> 32)); }

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_thr_eval(int nq, const uint32_t* __rest
     __shared__ float s_d[THR_EMIT_CAP];
     __shared__ __attribute__((aligned(16))) float s_q[1344];
     __shared__ __attribute__((aligned(16))) float s_terms[4][KNN_TERMS];
-    __shared__ uint32_t s_w[4];
+    __shared__ BlockRank<256> s_rank;
     const int qi = blockIdx.x;
     const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;
     const uint32_t n = emit_cnt[qi];
@@ -86,14 +86,8 @@ __global__ __launch_bounds__(256) void k_thr_eval(int nq, const uint32_t* __rest
     for (int base = 0; base < THR_EMIT_CAP; base += 256) {
         const int i = base + t;
         const bool in = i < (int)n && s_d[i] < thr;
-        const unsigned long long b = __ballot(in);
-        if (lane == 0) s_w[wv] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t before = 0;
-        for (int w = 0; w < wv; ++w) before += s_w[w];
-        if (in) { const uint32_t o = total + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)); lr[o] = s_row[i]; dists[(size_t)qi * THR_EMIT_CAP + o] = s_d[i]; }
-        total += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
+        const uint32_t o = s_rank.step(in, total);
+        if (in) { lr[o] = s_row[i]; dists[(size_t)qi * THR_EMIT_CAP + o] = s_d[i]; }
     }
     if (t == 0) cnt_out[qi] = total;
 }
@@ -105,10 +99,10 @@ template <int PASS>
 __global__ __launch_bounds__(256) void k_thr_exact(const uint32_t* __restrict__ qlist, const float* __restrict__ q, int dim, const float* __restrict__ words,
                                                    int dim_pad, int n_words, int metric, float thr, uint32_t* __restrict__ cnt_out,
                                                    const unsigned long long* __restrict__ off, int32_t* __restrict__ idx_out, float* __restrict__ dist_out) {
-    __shared__ uint32_t s_w[4];
+    __shared__ BlockRank<256> s_rank;
     const uint32_t qi = qlist ? qlist[blockIdx.x] : blockIdx.x;
     const float* qp = q + (size_t)qi * dim;
-    const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;
+    const int t = threadIdx.x;
     const unsigned long long pos = PASS ? off[qi] : 0ull;
     uint32_t total = 0;
     for (int base = 0; base < n_words; base += 256) {
@@ -118,17 +112,8 @@ __global__ __launch_bounds__(256) void k_thr_exact(const uint32_t* __restrict__ 
             d = metric == ISMHIP_METRIC_CHI2 ? flann_chi2(qp, words + (size_t)row * dim_pad, dim) : flann_l2(qp, words + (size_t)row * dim_pad, dim);
             in = d < thr;
         }
-        const unsigned long long b = __ballot(in);
-        if (lane == 0) s_w[wv] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t before = 0;
-        for (int w = 0; w < wv; ++w) before += s_w[w];
-        if (PASS && in) {
-            const size_t o = (size_t)(pos + total + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull)));
-            idx_out[o] = row; dist_out[o] = d;
-        }
-        total += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
+        const uint32_t r = s_rank.step(in, total);
+        if (PASS && in) { idx_out[pos + r] = row; dist_out[pos + r] = d; }
     }
     if (!PASS && t == 0) cnt_out[qi] = total;
 }

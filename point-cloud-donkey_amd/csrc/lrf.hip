@@ -271,9 +271,7 @@ __global__ __launch_bounds__(64) void k_lrf_tie(CloudView cv, const float* __res
                 unsigned long long mn = ~0ull;
 #pragma unroll
                 for (int x = 0; x < TIE_REG_KEYS; ++x) { const unsigned long long kk = kr[x]; if (kk > five[j - 1] && kk < mn) mn = kk; }
-#pragma unroll
-                for (int o2 = 32; o2 > 0; o2 >>= 1) { const unsigned long long tt = __shfl_xor(mn, o2, 64); mn = tt < mn ? tt : mn; }
-                five[j] = mn;
+                five[j] = wave_min_u64(mn);
             }
         } else {
             unsigned long long sel = 0ull;
@@ -295,9 +293,7 @@ __global__ __launch_bounds__(64) void k_lrf_tie(CloudView cv, const float* __res
             for (int j = 1; j < 5; ++j) {
                 unsigned long long mn = ~0ull;
                 for (uint32_t i = lane; i < n; i += 64) { const unsigned long long kk = mykeys[i]; if (kk > five[j - 1] && kk < mn) mn = kk; }
-#pragma unroll
-                for (int o2 = 32; o2 > 0; o2 >>= 1) { const unsigned long long tt = __shfl_xor(mn, o2, 64); mn = tt < mn ? tt : mn; }
-                five[j] = mn;
+                five[j] = wave_min_u64(mn);
             }
         }
         int cntx = 0, cntz = 0;
@@ -384,34 +380,23 @@ __global__ __launch_bounds__(256) void k_normals_from_lrf(const uint32_t* __rest
                                                           const float* __restrict__ z, const float* __restrict__ lrf, const uint8_t* __restrict__ rawflip,
                                                           float* __restrict__ nx, float* __restrict__ ny, float* __restrict__ nz) {
     const uint32_t base = pt_off[blockIdx.x], n = pt_off[blockIdx.x + 1] - base;
-    __shared__ uint32_t s_cnt[4], s_inv;
+    __shared__ uint32_t s_cnt[4];
+    __shared__ BlockRank<256> s_rank;
     auto finite_pt = [&](uint32_t i) { return isfinite(x[base + i]) && isfinite(y[base + i]) && isfinite(z[base + i]); };
     auto frame_ok = [&](uint32_t i) { const float* f = lrf + (size_t)(base + i) * 9; return isfinite(f[0]) && isfinite(f[3]) && isfinite(f[6]); };
-    if (threadIdx.x == 0) s_inv = 0;
-    __syncthreads();
     uint32_t mine = 0;
     for (uint32_t i = threadIdx.x; i < n; i += 256) mine += (finite_pt(i) && !frame_ok(i)) ? 1u : 0u;
-    mine = (uint32_t)wave_sum_i((int)mine);
-    if (lane_id() == 0 && mine) atomicAdd(&s_inv, mine);
-    __syncthreads();
-    const uint32_t n_inv = s_inv;
-    uint32_t rank0 = 0;                                                         // finite points in front of this chunk
+    const uint32_t n_inv = block_sum_i(mine, s_cnt);
+    uint32_t n_fin = 0;                                                         // finite points so far
     for (uint32_t c = 0; c < n; c += 256) {
         const uint32_t i = c + threadIdx.x;
         const bool fin = i < n && finite_pt(i);
-        const unsigned long long b = __ballot(fin);
-        if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t r = rank0 + (uint32_t)__popcll(b & ((1ull << lane_id()) - 1ull));
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) r += s_cnt[w];
-        const uint32_t chunk = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        __syncthreads();
+        const uint32_t r = s_rank.step(fin, n_fin);                             // rank among the finite points, in input order
         if (fin) {
             const uint32_t g = base + i;
             if (r < n_inv) { if (rawflip[g]) { nx[g] = -nx[g]; ny[g] = -ny[g]; nz[g] = -nz[g]; } }
             else if (frame_ok(i)) { const float* f = lrf + (size_t)g * 9; nx[g] = -f[6]; ny[g] = -f[7]; nz[g] = -f[8]; }
         }
-        rank0 += chunk;
     }
 }
 // the cloud's cell-sorted normal copies follow (sorted position s of object o holds the original point in sp4[s].w)

@@ -123,24 +123,10 @@ __device__ __forceinline__ void quat_scatter_add(float* S, float w, const float*
     S[7] += w * q[2] * q[2]; S[8] += w * q[2] * q[3]; S[9] += w * q[3] * q[3];
 }
 
-__device__ __forceinline__ float block_sum_f(float v, float* s_red) {   // 256 threads
-    v = wave_sum_f(v);
-    __syncthreads();
-    if (lane_id() == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-__device__ __forceinline__ int block_sum_i(int v, int* s_red) {
-    v = wave_sum_i(v);
-    __syncthreads();
-    if (lane_id() == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // The per-(object, class) steps that both voting back ends take, written once. Args = MaxArgs or HoughArgs. The helpers declare
-// no __shared__ storage of their own: their LDS scratch (4 entries per array, one per wave) comes from the calling body.
+// no __shared__ storage of their own: their LDS scratch (4 entries per array, one per wave) comes from the calling body. The
+// workgroup sums (pairwise: block_sum_f_pairwise) and the ordered compaction step (BlockRank) are common.h's.
 // ---------------------------------------------------------------------------------------------------------------------------
 
 // The votes of one class, `cap` entries per array: in dynamic LDS, or (GM: objects with more than MX_LDS_SLOTS slots) in the
@@ -161,31 +147,22 @@ __device__ __forceinline__ ClassVotes class_votes_layout(const Args& a, unsigned
 
 // Ordered compaction of the votes of class blockIdx.y among the slots of object blockIdx.x: slot order is kept (the reference visits
 // the votes of a class in the order they were cast). [s0, s1): the object's slots, read by the caller before its first store so
-// that they stay scalar loads. s_n: zeroed by the caller before a barrier. Returns the number of votes held.
+// that they stay scalar loads. Returns the number of votes held.
 template <class Args>
-__device__ __forceinline__ int compact_class_votes(const Args& a, const ClassVotes& V, uint32_t s0, uint32_t s1, int& s_n, int* s_wcnt) {
+__device__ __forceinline__ int compact_class_votes(const Args& a, const ClassVotes& V, uint32_t s0, uint32_t s1, BlockRank<256>& rank) {
     const int c = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t total = 0;
     for (uint32_t base = s0; base < s1; base += 256) {
-        const uint32_t s = base + tid;
+        const uint32_t s = base + threadIdx.x;
         const bool f = s < s1 && a.vcls[s] == c;
-        const unsigned long long mask = __ballot(f);
-        if (lane == 0) s_wcnt[wv] = __popcll(mask);
-        __syncthreads();
-        int off = s_n;
-        for (int k = 0; k < wv; ++k) off += s_wcnt[k];
-        if (f) {
-            const int pos = off + __popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < V.cap) {
-                V.x[pos] = a.vpos[(size_t)s * 3]; V.y[pos] = a.vpos[(size_t)s * 3 + 1]; V.z[pos] = a.vpos[(size_t)s * 3 + 2];
-                V.w[pos] = a.vw[s]; V.inst[pos] = a.vinst[s]; V.slot[pos] = (int)s;
-            }
+        const uint32_t pos = rank.step(f, total);
+        if (f && pos < (uint32_t)V.cap) {
+            V.x[pos] = a.vpos[(size_t)s * 3]; V.y[pos] = a.vpos[(size_t)s * 3 + 1]; V.z[pos] = a.vpos[(size_t)s * 3 + 2];
+            V.w[pos] = a.vw[s]; V.inst[pos] = a.vinst[s]; V.slot[pos] = (int)s;
         }
-        __syncthreads();
-        if (tid == 0) s_n += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        __syncthreads();
     }
-    return min(s_n, V.cap);
+    __syncthreads();                            // the votes are in place for every thread
+    return (int)min(total, (uint32_t)V.cap);
 }
 
 // One member's share of the weighted box size and of the quaternion scatter matrix (voting.cpp:167-215); slot = its global vote slot
@@ -196,12 +173,11 @@ __device__ __forceinline__ void member_box_sums(const Args& a, int slot, float w
     if (a.vbq) quat_scatter_add(B.qs, w, a.vbq + (size_t)slot * 4);
 }
 __device__ __forceinline__ void block_sum_box(BoxSums& B, bool with_quat, float* s_redf) {
-    B.b0 = block_sum_f(B.b0, s_redf); B.b1 = block_sum_f(B.b1, s_redf); B.b2 = block_sum_f(B.b2, s_redf);
+    B.b0 = block_sum_f_pairwise(B.b0, s_redf); B.b1 = block_sum_f_pairwise(B.b1, s_redf); B.b2 = block_sum_f_pairwise(B.b2, s_redf);
     if (with_quat) {
 #pragma unroll
-        for (int e = 0; e < 10; ++e) B.qs[e] = block_sum_f(B.qs[e], s_redf);
+        for (int e = 0; e < 10; ++e) B.qs[e] = block_sum_f_pairwise(B.qs[e], s_redf);
     }
-    __syncthreads();
 }
 
 // filterVotesWithRansac (voting.cpp:356-433) on the members of one maximum, in slot order. Every member keeps the weight it has in
@@ -313,8 +289,8 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
     unsigned long long* keys = (unsigned long long*)V.rest;
     float4* ctr = (float4*)(keys + cap);    float4* ctr2 = ctr + cap;
     unsigned char* member = (unsigned char*)(ctr2 + cap);
-    __shared__ int s_nmax, s_n, s_ns, s_nc, s_np;
-    __shared__ int s_wcnt[4];
+    __shared__ int s_nmax, s_ns, s_nc, s_np;
+    __shared__ BlockRank<256> s_rank;
     __shared__ float s_redf[4];
     __shared__ int s_redi[4];
     __shared__ int s_bi[4];
@@ -334,9 +310,7 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
         float h = a.class_bw ? a.class_bw[c] : a.bandwidth;                // voting_mean_shift.cpp:48-49
         float h2 = (float)((double)h * (double)h);
         float hh = h * h;
-        if (tid == 0) s_n = 0;
-        __syncthreads();
-        const int n = compact_class_votes(a, V, s0, s1, s_n, s_wcnt);
+        const int n = compact_class_votes(a, V, s0, s1, s_rank);
         if (n == 0) return;                                       // class absent from m_votes (uniform across the block)
         const float* vx = V.x; const float* vy = V.y; const float* vz = V.z; float* vw = V.w;
         if (a.som_type != ISMHIP_SOM_MEANSHIFT) {
@@ -349,13 +323,7 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
             else if (a.som_type == ISMHIP_SOM_COMPLETE_VOTING_SPACE) {
                 float md = 0.f;
                 for (int i = tid; i < n; i += 256) { const float dx = vx[i] - qx, dy = vy[i] - qy, dz = vz[i] - qz; md = fmaxf(md, dx * dx + dy * dy + dz * dz); }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) md = fmaxf(md, __shfl_xor(md, off, 64));
-                __syncthreads();
-                if (lane == 0) s_redf[wv] = md;
-                __syncthreads();
-                h = sqrtf(fmaxf(fmaxf(s_redf[0], s_redf[1]), fmaxf(s_redf[2], s_redf[3])));
-                __syncthreads();
+                h = sqrtf(block_max_f(md, s_redf));
             }
             h2 = (float)((double)h * (double)h); hh = h * h;
             if (tid == 0) { ctr2[0] = make_float4(qx, qy, qz, 0.f); s_np = 1; }
@@ -519,7 +487,7 @@ __device__ __forceinline__ void find_maxima_body(const MaxArgs& a, const RansacK
             // RANSAC: every member keeps its reweighted weight (voting_mean_shift.cpp:161-176 ran before), the sums see inliers only.
             // keys / ctr are free once the final positions sit in ctr2
             if constexpr (RS) if (!ransac_filter_members(a, *rk, V, n, member, (int*)keys, *Lp, s_redi, cnt, sw, B)) continue;
-            sw = block_sum_f(sw, s_redf);
+            sw = block_sum_f_pairwise(sw, s_redf);
             block_sum_box(B, a.vbq != nullptr, s_redf);
             instance_tally(V, n, member, (int*)ctr, keys, s_bS, s_bi);
             if (tid == 0) write_maximum_record(rec, rec_tf, Lp, s_nmax, a.truncated, p.x, p.y, p.z, sw, cnt, best_of_waves(s_bS, s_bi), B, a.vbq ? B.qs : nullptr);
@@ -739,8 +707,8 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     int* hkey = (int*)(hval + cap);                                       // instance tally (keys)
     unsigned char* member = (unsigned char*)(hkey + cap);
     unsigned long long* tile = GM ? (unsigned long long*)smem : (unsigned long long*)(member + cap);     // tile_edge^3 bins, always in LDS
-    __shared__ int s_n, s_nmax, s_lo[3], s_hi[3], s_nm;
-    __shared__ int s_wcnt[4];
+    __shared__ int s_nmax, s_lo[3], s_hi[3], s_nm;
+    __shared__ BlockRank<256> s_rank;
     __shared__ float s_redf[4];
     __shared__ int s_redi[4];
     __shared__ int s_bi[4];
@@ -753,10 +721,10 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
     float* rec = a.rec + oc * MX_MAXM_C * MX_REC;
     float* rec_tf = nullptr;                                     // RANSAC entries: (R, t) records of this class, when asked for
     if constexpr (RS) if (rk->rec_tf) rec_tf = rk->rec_tf + oc * MX_MAXM_C * 12;
-    if (tid == 0) { s_nmax = 0; s_n = 0; s_nm = 0; s_hmax = 0ull; a.rec_count[oc] = 0;
+    if (tid == 0) { s_nmax = 0; s_nm = 0; s_hmax = 0ull; a.rec_count[oc] = 0;
                     for (int d = 0; d < 3; ++d) { s_lo[d] = 0x7fffffff; s_hi[d] = -1; } }
     __syncthreads();
-    const int n = compact_class_votes(a, V, s0, s1, s_n, s_wcnt);
+    const int n = compact_class_votes(a, V, s0, s1, s_rank);
     if (n == 0) return;                                       // class absent from m_votes (uniform across the block)
     const float* vx = V.x; const float* vy = V.y; const float* vz = V.z; const float* vw = V.w;
     const double bin = (double)(a.class_bin ? a.class_bin[c] : a.bin);
@@ -810,7 +778,7 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
             if (pass == 0) {
                 unsigned long long m = 0ull;
                 for (int i = tid; i < E * E * E; i += 256) m = tile[i] > m ? tile[i] : m;
-                m = wave_min_u64(~m); m = ~m;                             // wave max through the min helper
+                m = wave_max_u64(m);
                 if (lane == 0) atomicMax(&s_hmax, m);
             } else {
                 // interior bins >= threshold with no strictly greater 26-neighbour (halo bins are complete: every vote was scanned)
@@ -877,13 +845,13 @@ __device__ __forceinline__ void hough3d_body(const HoughArgs& a, const RansacKAr
         }
         vcnt = block_sum_i(vcnt, s_redi);
         if (vcnt < a.min_votes || vcnt == 0) continue;        // uniform across the block
-        sw = block_sum_f(sw, s_redf);
-        px = block_sum_f(px, s_redf); py = block_sum_f(py, s_redf); pz = block_sum_f(pz, s_redf);
+        sw = block_sum_f_pairwise(sw, s_redf);
+        px = block_sum_f_pairwise(px, s_redf); py = block_sum_f_pairwise(py, s_redf); pz = block_sum_f_pairwise(pz, s_redf);
         const float sw_pos = sw;                              // the maximum's position: the weighted centre of ALL voters (voting_hough_3d.cpp:70-93)
         if constexpr (RS) {
             // RANSAC on the voters: the position stays, every other sum sees inliers only. The instance tally's arrays are free until the tally
             if (!ransac_filter_members(a, *rk, V, n, member, (int*)hval, *Lp, s_redi, vcnt, sw, B)) continue;
-            sw = block_sum_f(sw, s_redf);
+            sw = block_sum_f_pairwise(sw, s_redf);
         }
         block_sum_box(B, a.vbq != nullptr, s_redf);
         instance_tally(V, n, member, hkey, hval, s_bS, s_bi);

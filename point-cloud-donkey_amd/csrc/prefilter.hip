@@ -204,31 +204,27 @@ __global__ __launch_bounds__(256) void k_sor_scan(SorView cv, int k, float* __re
 }
 
 // One block per object: mean and variance of the finite points' mean distances in double, in a FIXED order (thread t sums the
-// points t, t + 256, ... ascending; the DPP tree of wave_sum_d; the four wave partials in wave order), threshold, then the mask.
+// points t, t + 256, ... ascending; the DPP tree of wave_sum_d; the four wave partials in wave order: block_sum_d_left of common.h),
+// threshold, then the mask.
 __global__ __launch_bounds__(256) void k_sor_threshold(const uint32_t* __restrict__ pt_off, const float* __restrict__ x, const float* __restrict__ y,
                                                        const float* __restrict__ z, int k, double mul, float* __restrict__ mean_dist,
                                                        uint8_t* __restrict__ keep, double* __restrict__ thr_out) {
     const int o = blockIdx.x;
     const uint32_t b = pt_off[o], e = pt_off[o + 1];
-    __shared__ double s_s[4], s_q[4];
+    __shared__ double s_d[4];
     __shared__ uint32_t s_n[4];
-    double sum = 0.0, sq = 0.0; int n = 0;
+    double sum = 0.0, sq = 0.0; uint32_t n = 0;
     for (uint32_t i = b + threadIdx.x; i < e; i += 256)
         if (isfinite(x[i]) && isfinite(y[i]) && isfinite(z[i])) { n++; }
-    n = wave_sum_i(n);
-    if (lane_id() == 0) s_n[threadIdx.x >> 6] = (uint32_t)n;
-    __syncthreads();
-    const uint32_t nf = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const uint32_t nf = block_sum_i(n, s_n);
     const bool small = nf < (uint32_t)(k + 1);                 // fewer than MeanK + 1 finite points: the object is kept whole
     if (!small)
         for (uint32_t i = b + threadIdx.x; i < e; i += 256)
             if (isfinite(x[i]) && isfinite(y[i]) && isfinite(z[i])) { const double d = (double)mean_dist[i]; sum += d; sq += d * d; }
-    sum = wave_sum_d(sum); sq = wave_sum_d(sq);
-    if (lane_id() == 0) { s_s[threadIdx.x >> 6] = sum; s_q[threadIdx.x >> 6] = sq; }
-    __syncthreads();
+    const double S = block_sum_d_left(sum, s_d), Q = block_sum_d_left(sq, s_d);
     double thr = INFINITY;
     if (!small) {
-        const double S = ((s_s[0] + s_s[1]) + s_s[2]) + s_s[3], Q = ((s_q[0] + s_q[1]) + s_q[2]) + s_q[3], N = (double)nf;
+        const double N = (double)nf;
         const double mean = S / N, var = (Q - S * S / N) / (N - 1.0);
         thr = mean + mul * sqrt(var);
     }

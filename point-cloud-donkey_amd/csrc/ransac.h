@@ -25,7 +25,8 @@ struct RansacLds {
     double M[12];               // R (row-major) and t of the best hypothesis so far
     double sdt, k;
     int cnt[RS_CHUNK];
-    int best, best_i, lim, done, iters, changed, wcnt[4], ncompact;
+    int best, best_i, lim, done, iters, changed;
+    BlockRank<256> rank;        // rs_compact
     unsigned evaluated;
 };
 
@@ -47,32 +48,17 @@ __device__ __forceinline__ void rs_draw(unsigned long long seed, unsigned i, uns
     if (c >= lo) c += 1;
     if (c >= hi) c += 1;
 }
-__device__ __forceinline__ double rs_block_sum_d(double v, RansacLds& L) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if (lane_id() == 0) L.red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (L.red[0] + L.red[1]) + (L.red[2] + L.red[3]);
-}
 // ordered compaction: list[] = the positions i < n with flag[i] != 0, ascending; returns their number (to every thread)
 __device__ __forceinline__ int rs_compact(int n, const unsigned char* flag, int* list, RansacLds& L) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) L.ncompact = 0;
-    __syncthreads();
+    uint32_t total = 0;
     for (int base = 0; base < n; base += 256) {
-        const int i = base + tid;
+        const int i = base + (int)threadIdx.x;
         const bool f = i < n && flag[i] != 0;
-        const unsigned long long mask = __ballot(f);
-        if (lane == 0) L.wcnt[wv] = __popcll(mask);
-        __syncthreads();
-        int off = L.ncompact;
-        for (int k = 0; k < wv; ++k) off += L.wcnt[k];
-        if (f) list[off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
-        __syncthreads();
-        if (tid == 0) L.ncompact += L.wcnt[0] + L.wcnt[1] + L.wcnt[2] + L.wcnt[3];
-        __syncthreads();
+        const uint32_t pos = L.rank.step(f, total);
+        if (f) list[pos] = i;
     }
-    return L.ncompact;
+    __syncthreads();                            // the list is complete for every thread
+    return (int)total;
 }
 // one Hestenes rotation of the column pair (p, q) of A (and of V); returns whether it rotated
 __device__ __forceinline__ bool rs_rot(double& a0p, double& a1p, double& a2p, double& a0q, double& a1q, double& a2q,
@@ -178,7 +164,7 @@ __device__ __forceinline__ RansacResult ransac_cluster(int n, Fetch&& fetch, flo
         float s[3], t[3];
         double sx = 0, sy = 0, sz = 0;
         for (int j = tid; j < n; j += 256) { fetch(j, s, t); sx += (double)s[0]; sy += (double)s[1]; sz += (double)s[2]; }
-        const double mx = rs_block_sum_d(sx, L) / n, my = rs_block_sum_d(sy, L) / n, mz = rs_block_sum_d(sz, L) / n;
+        const double mx = block_sum_d_pairwise(sx, L.red) / n, my = block_sum_d_pairwise(sy, L.red) / n, mz = block_sum_d_pairwise(sz, L.red) / n;
         double c[6] = {0, 0, 0, 0, 0, 0};
         for (int j = tid; j < n; j += 256) {
             fetch(j, s, t);
@@ -186,7 +172,7 @@ __device__ __forceinline__ RansacResult ransac_cluster(int n, Fetch&& fetch, flo
             c[0] += dx * dx; c[1] += dx * dy; c[2] += dx * dz; c[3] += dy * dy; c[4] += dy * dz; c[5] += dz * dz;
         }
 #pragma unroll
-        for (int e = 0; e < 6; ++e) c[e] = rs_block_sum_d(c[e], L) / n;
+        for (int e = 0; e < 6; ++e) c[e] = block_sum_d_pairwise(c[e], L.red) / n;
         if (tid == 0) {
             double a[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}}, w[3], V[3][3];
             eigen_sym3(a, w, V);

@@ -202,12 +202,7 @@ __global__ __launch_bounds__(256) void k_tr_weights_big(const uint32_t* __restri
                 const uint32_t cand = sel | (1u << bit);
                 int c = 0;
                 for (uint32_t j = threadIdx.x; j < m; j += 256) c += s_big[j] < cand;
-                c = wave_sum_i(c);
-                __syncthreads();
-                if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = c;
-                __syncthreads();
-                c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-                if ((uint32_t)c <= rank) sel = cand;
+                if ((uint32_t)block_sum_i(c, s_cnt) <= rank) sel = cand;
             }
             return sel;
         };
