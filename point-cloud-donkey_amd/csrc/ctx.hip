@@ -84,6 +84,7 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_HELLINGER"); ctx->knn_hellinger = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_T1"); if (e) ctx->knn_t1 = atoi(e); }
     { const char* e = getenv("ISMHIP_KNN_STAGE2_T4"); if (e) ctx->knn_stage2_t4 = atoi(e) != 0; }
+    { const char* e = getenv("ISMHIP_KNN_STAGE2_SPLITS"); ctx->knn_stage2_splits = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_STAGE2_SEED"); ctx->knn_stage2_seed = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_PRE_STEP"); if (e && atoi(e) > 0) ctx->knn_pre_step = atoi(e); }
     { const char* e = getenv("ISMHIP_KNN_PRE_GAMMA"); if (e) ctx->knn_pre_gamma = (float)atof(e); }
@@ -211,6 +212,8 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
                 if (ms_out) *ms_out = (double)v[i]; if (launches_out) *launches_out = 1; return ISMHIP_OK;
             }
     }
+    if (std::strcmp(name, "knn_stage2_list_entries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_list_entries; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
+    if (std::strcmp(name, "knn_stage2_ranged") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_ranged; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_stage2_queries") == 0) { if (ms_out) *ms_out = (double)ctx->knn_stage2_queries; if (launches_out) *launches_out = 1; return ISMHIP_OK; }
     if (std::strcmp(name, "knn_flagged_queries") == 0 || std::strcmp(name, "knn_flagged_items") == 0) {     // counters, not times
         if (ms_out) *ms_out = (double)ctx->knn_stats[name[12] == 'q' ? 0 : 1];

@@ -31,7 +31,9 @@
 //  that order on one stream: knn_carve_scratch, knn_query_images, knn_launch_candidates, knn_rerank_prove, knn_exact_scan.
 //  Also here: the two-stage and the Hellinger (chi-square) drivers, ismhip_knn, _ratio, _rule. Stage 2 of the two-stage search is
 //  SEEDED: k_knn_seed_thr turns the k-th exact value stage 1 found for a query into the start threshold of all its lane slots (the
-//  slot proofs it inverts are written once, in knn_internal.h: knn_l2_slot_proven, pca_lb_of / pca_slot_proven).
+//  slot proofs it inverts are written once, in knn_internal.h: knn_l2_slot_proven, pca_lb_of / pca_slot_proven), and it searches a
+//  query again only on the rows of the stage-1 splits whose proof failed (run_knn_stage2_lists: per-split failure lists, ranged
+//  searches, one exact scan, stage 1's answer merged with the list results).
 //       knn_threshold.hip  ismhip_knn_threshold  radius search: EMIT sweep + k_thr_* 
 //       knn_large_k.hip    ismhip_knn_large_k    any K up to 1024: seeded EMIT sweep + certificate, exact top-K scan
 #include "knn_internal.h"
@@ -217,8 +219,20 @@ __device__ __forceinline__ bool knn_select_write(unsigned long long* key, int qi
     }
     return have_k;
 }
+// Several searches may fill ONE queue (the chunks of a ranged stage 2, scanned together): the queries of this search are numbered from
+// q_base in it, and its slots carry slot_tag (chunk << 8), which tells k_knn_fallback whose slot -> rows layout to decode. live !=
+// nullptr: query i is padding between two lists when live[i] == ~0u -- it has no answer to find and no record to leave.
+// known_dk != nullptr (a ranged search, whose rows need not hold the query's answer): an exact functor value the query's k-th best row
+// is KNOWN not to exceed -- stage 1's k-th value, whose rows the caller merges into the result (NaN: none). The proof then asks the
+// slots to clear the smaller of it and the k-th value found here: a dropped row beyond that value is beyond the final k-th value.
+struct KnnQueueTag { const uint32_t* live; int q_base, slot_tag; const float* known_dk; };
+__device__ __forceinline__ bool knn_is_padding(const KnnQueueTag& tg, int qi) { return tg.live && tg.live[qi] == ~0u; }
+__device__ __forceinline__ bool knn_proof_dk(const KnnQueueTag& tg, int qi, bool have_k, float& dk) {
+    if (tg.known_dk) { const float U = tg.known_dk[qi]; if (U == U) { dk = have_k ? fminf(dk, U) : U; return true; } }
+    return have_k;
+}
 // queue: one record per unproven query {query, first item, #items} and one work item {query, slot} per failing slot
-__device__ __forceinline__ void knn_queue_unproven(bool viol, int qi, int lane, uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
+__device__ __forceinline__ void knn_queue_unproven(bool viol, int qi, int lane, uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items, const KnnQueueTag& tg) {
     const unsigned long long vmask = __ballot(viol);
     if (vmask != 0ull) {
         const int nv = __popcll(vmask);
@@ -226,12 +240,12 @@ __device__ __forceinline__ void knn_queue_unproven(bool viol, int qi, int lane, 
         if (lane == 0) {
             const uint32_t qs = atomicAdd(&flag_count[KNN_CNT_QUERIES], 1u);
             ibase = atomicAdd(&flag_count[KNN_CNT_ITEMS], (uint32_t)nv);
-            qrec[3 * (size_t)qs] = (uint32_t)qi; qrec[3 * (size_t)qs + 1] = ibase; qrec[3 * (size_t)qs + 2] = (uint32_t)nv;
+            qrec[3 * (size_t)qs] = (uint32_t)(qi + tg.q_base); qrec[3 * (size_t)qs + 1] = ibase; qrec[3 * (size_t)qs + 2] = (uint32_t)nv;
         }
         ibase = __shfl(ibase, 0, 64);
         if (viol) {
             const uint32_t it = ibase + __popcll(vmask & ((1ull << lane) - 1ull));
-            items[2 * (size_t)it] = (uint32_t)qi; items[2 * (size_t)it + 1] = (uint32_t)lane;
+            items[2 * (size_t)it] = (uint32_t)(qi + tg.q_base); items[2 * (size_t)it + 1] = (uint32_t)(lane | tg.slot_tag);
         }
     }
 }
@@ -241,9 +255,9 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
                                                     const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
                                                     const float* __restrict__ cand_bound, int n_bound, VerifyParams vp,
                                                     int k, int32_t* __restrict__ idx_out, float* __restrict__ dist_out,
-                                                    uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
+                                                    uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items, KnnQueueTag tg) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qi >= nq) return;
+    if (qi >= nq || knn_is_padding(tg, qi)) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
     const float qn2 = wave_norm2(qp, dim, lane);          // needed by the error bounds below
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
     float bnd = __builtin_inff();
     if (lane < n_bound) bnd = cand_bound[(size_t)qi * n_bound + lane];
     float dk;
-    const bool have_k = knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk);
+    const bool have_k = knn_proof_dk(tg, qi, knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk), dk);
     // Proof of exactness, slot by slot. A codeword dropped by slot b has approximate score >= bnd_b, so
     //   L2  : true distance D >= |q|^2 (1 - 16u) + bnd_b - eps_s,  eps_s = 17u |c|max^2 + (2 dot_rel + 2u) |q||c|max
     //         (|c|^2 by a short tree sum: 16u; K-term fma chain: 1.01 K u on sum|q_i c_i| <= |q||c|; final subtraction: u)
@@ -298,7 +312,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
             viol = !(dk < lo);
         } else viol = !knn_l2_slot_proven(dk, bnd, qn2, vp);
     }
-    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
+    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items, tg);
 }
 
 // ---- re-rank + proof for a stage 1 that ran on the ROTATED, TRUNCATED image (pca.hip) --------------------------------------------
@@ -336,9 +350,9 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
                                                         const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
                                                         const float* __restrict__ cand_bound, int n_bound, PcaVerify pv,
                                                         int k, int32_t* __restrict__ idx_out, float* __restrict__ dist_out,
-                                                        uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
+                                                        uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items, KnnQueueTag tg) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qi >= nq) return;
+    if (qi >= nq || knn_is_padding(tg, qi)) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
     const PcaLb lbq = pca_lb_query(pv, qi, wave_norm2(qp, dim, lane), lane);
@@ -371,14 +385,14 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     float bnd = __builtin_inff();
     if (lane < n_bound) bnd = cand_bound[(size_t)qi * n_bound + lane];
     float dk;
-    const bool have_k = knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk);
+    const bool have_k = knn_proof_dk(tg, qi, knn_select_write<1>(&key, qi, k, lane, idx_out, dist_out, dk), dk);
     // a slot whose bound is still +inf dropped nothing -- unless scores overflowed, which needs a non-finite |q^|^2 or bound term
     bool viol = false;
     if (lane < n_bound && (bnd != __builtin_inff() || !(lbq.eps_s + lbq.qn2h + lbq.dlt < __builtin_inff()))) {
         if (!have_k) viol = true;
         else viol = !pca_slot_proven(dk, bnd, lbq, pv.ku);
     }
-    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
+    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items, tg);
 }
 
 // ---- start thresholds of a SEEDED search (stage 2 of the two-stage search) -------------------------------------------------------
@@ -393,9 +407,11 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
 // finite, an image row that overflowed -- is -inf, the cold start. One wave per query, as in the re-rank kernels: the proof's |q|^2
 // sums are the same bits.
 __global__ __launch_bounds__(256) void k_knn_seed_thr(const float* __restrict__ q, int nq, int ldq, int dim, const float* __restrict__ seed_dk,
-                                                      bool pca, PcaVerify pv, VerifyParams vp, const float* __restrict__ out_scale, float* __restrict__ thr) {
+                                                      bool pca, PcaVerify pv, VerifyParams vp, const float* __restrict__ out_scale, float* __restrict__ thr,
+                                                      const uint32_t* __restrict__ live /* padding (KnnQueueTag) starts at +inf: it inserts nothing */) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (qi >= nq) return;
+    if (live && live[qi] == ~0u) { if (lane_id() == 0) thr[qi] = __builtin_inff(); return; }
     const int lane = lane_id();
     const float qn2 = wave_norm2(q + (size_t)qi * ldq, dim, lane);
     PcaLb lbq{};
@@ -459,9 +475,9 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
                                                          const int* __restrict__ cand_idx, const float* __restrict__ cand_val, int cand_stride, int n_cand,
                                                          const float* __restrict__ cand_bound, int n_bound, VerifyParams vp,
                                                          int k, int32_t* __restrict__ idx_out, float* __restrict__ dist_out,
-                                                         uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items) {
+                                                         uint32_t* __restrict__ flag_count, uint32_t* __restrict__ qrec, uint32_t* __restrict__ items, KnnQueueTag tg) {
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qi >= nq) return;
+    if (qi >= nq || knn_is_padding(tg, qi)) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
     const float qn2 = wave_norm2(sq + (size_t)qi * dim_pad, dim, lane);   // |sqrt q|^2
@@ -562,7 +578,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank_hell(const float* __restrict
         if (!have_k) viol = true;
         else viol = !(dk < lb_of(bnd) * (1.f - vp.ku) - 1e-37f);
     }
-    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items);
+    knn_queue_unproven(viol, qi, lane, flag_count, qrec, items, tg);
 }
 
 // Exact scan for the slots that could not be proven. One WAVE per (query, slot) work item; the wave handles 4 codeword rows
@@ -577,10 +593,14 @@ __host__ __device__ inline uint32_t knn_fb_parts(uint32_t n_items) {
     const uint32_t p = KNN_FB_UNITS / n_items;
     return p > 256u ? 256u : p;
 }
+// How the slots of ONE search map to rows: its plan's tiles per split, tile count and tile rows, the slot -> rows layout (wr_rows: a
+// KnnFbLayout value) and, for a ranged search (qrange, knn_internal.h), the number of splits each query's own range was cut into.
+struct KnnFbDesc { int tiles_per_split, n_tiles, tile_rows, wr_rows, n_splits; };
+// One launch scans the items of up to two searches that shared a queue: bit 8 of an item's slot word picks d1 (KnnQueueTag).
 template <int KM>   // KM = capacity of the per-item result lists: 4 (k <= 4, every shipped configuration) or KNN_MAX_K
 __global__ __launch_bounds__(256) void k_knn_fallback(const float* __restrict__ words, int dim, int dim_pad, int n_words,
-                                                      const float* __restrict__ q, int ldq, int metric, int k, int tiles_per_split, int n_tiles,
-                                                      int tile_rows, int wr_rows /* rows per wave-row block = MI*32 (L2) */,
+                                                      const float* __restrict__ q, int ldq, int metric, int k, KnnFbDesc d0, KnnFbDesc d1,
+                                                      const int* __restrict__ qrange,
                                                       const uint32_t* __restrict__ flag_count, const uint32_t* __restrict__ items,
                                                       const int32_t* __restrict__ idx_in, const float* __restrict__ dist_in,
                                                       unsigned long long* __restrict__ item_out, size_t part_base) {
@@ -589,10 +609,6 @@ __global__ __launch_bounds__(256) void k_knn_fallback(const float* __restrict__ 
     const int g = lane >> 4, l16 = lane & 15;
     const uint32_t n_items = flag_count[KNN_CNT_ITEMS];
     const bool l2 = metric != ISMHIP_METRIC_CHI2;
-    const bool lay_all = l2 && wr_rows == KNN_FB_ALL;                     // merged splits (k_knn_merge_splits): the one slot owns every row
-    const bool lay16 = l2 && wr_rows == KNN_FB_RING;                       // k_knn_l2_ring16: slot b = split*8 + wr*4 + fq owns rows wr*128 + 16 m + 4 fq + j
-    const bool lay16h = l2 && wr_rows == KNN_FB_RING_HALF;                      // k_knn_l2_ring16<T, 1>: 128-row tiles, slot b = split*4 + fq owns rows 16 m + 4 fq + j
-    const int rows_per_tile = lay_all ? tile_rows : ((lay16 || lay16h) ? 32 : (l2 ? wr_rows / 2 : tile_rows));   // else a lane slot sees half of its wave-row block (bit 2 of the row == h)
     const int nj = dim_pad / 16;
     const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     // With few items a wave per item would leave the chip idle behind a handful of long scans: every item is cut into P row
@@ -601,11 +617,21 @@ __global__ __launch_bounds__(256) void k_knn_fallback(const float* __restrict__ 
     unsigned long long* outp = P > 1 ? item_out + KM * part_base : item_out;
     for (uint32_t u = gw; u < n_items * P; u += nw) {
         const uint32_t it = u / P, part_i = u % P;
-        const int qi = (int)items[2 * (size_t)it], b = (int)items[2 * (size_t)it + 1];
+        const int qi = (int)items[2 * (size_t)it], bt = (int)items[2 * (size_t)it + 1], b = bt & 255;
+        const KnnFbDesc d = (bt >> 8) ? d1 : d0;
+        const int wr_rows = d.wr_rows, tile_rows = d.tile_rows;
+        const bool lay_all = l2 && wr_rows == KNN_FB_ALL;                     // merged splits (k_knn_merge_splits): the one slot owns every row
+        const bool lay16 = l2 && wr_rows == KNN_FB_RING;                       // k_knn_l2_ring16: slot b = split*8 + wr*4 + fq owns rows wr*128 + 16 m + 4 fq + j
+        const bool lay16h = l2 && wr_rows == KNN_FB_RING_HALF;                      // k_knn_l2_ring16<T, 1>: 128-row tiles, slot b = split*4 + fq owns rows 16 m + 4 fq + j
+        const int rows_per_tile = lay_all ? tile_rows : ((lay16 || lay16h) ? 32 : (l2 ? wr_rows / 2 : tile_rows));   // else a lane slot sees half of its wave-row block (bit 2 of the row == h)
         const float* qp = q + (size_t)qi * ldq;
         const int split = lay_all ? 0 : (lay16 ? (b >> 3) : (l2 ? (b >> 2) : b));
         const int wr = lay16h ? 0 : (lay16 ? (b >> 2) & 1 : (b >> 1) & 1), h = b & 1, fq = b & 3;
-        const int mt0 = split * tiles_per_split, mt1 = min(n_tiles, mt0 + tiles_per_split);
+        int mt0 = split * d.tiles_per_split, mt1 = min(d.n_tiles, mt0 + d.tiles_per_split);
+        if (qrange) {                                                          // ranged search: the query's own rows, cut as the candidate kernel cut them
+            const int* rg = qrange + 4 * (qi >> 8);
+            knn_range_split(rg[0] / tile_rows, rg[1] / tile_rows, split, lay_all ? 1 : d.n_splits, mt0, mt1);
+        }
         const int total = (mt1 - mt0) * rows_per_tile;
         unsigned long long best[KM];
 #pragma unroll
@@ -736,8 +762,12 @@ __global__ void k_rule(int nq, float thr, const int32_t* __restrict__ idx3, cons
 }
 
 // stage1 != nullptr: FIRST stage of the two-stage search -- candidates + exact re-rank + proof only; the unproven queries are
-// left in the queue (*stage1 = {flag_count, qrec}) for the caller instead of going to the exact scan.
-struct KnnStage1 { uint32_t* flag_count; uint32_t* qrec; };
+// left in the queue (*stage1 = {flag_count, qrec, items}) for the caller instead of going to the exact scan; with them, how the
+// stage cut the codebook: item slot b belongs to split b / slots, and split s swept the rows [s, s + 1) * rows_per_split.
+struct KnnStage1 { uint32_t* flag_count; uint32_t* qrec; uint32_t* items; int n_splits, slots, rows_per_split; };
+// A queue of unproven work that several searches fill and ONE exact scan empties (knn_scan_queue): the counter block, records and
+// items as in KnnScratch, and the slot -> rows layout each search (chunk 0 / 1) leaves behind for the scan.
+struct KnnQueue { uint32_t *count, *qrec, *items; unsigned long long* item_out; size_t q_items; KnnFbDesc desc[2]; };
 // what the caller of run_knn asks for beyond the search itself
 struct KnnRequest {
     KnnStage1* stage1 = nullptr;
@@ -748,6 +778,13 @@ struct KnnRequest {
     bool half = false;                 // the 128 x 256 ring tile (k_knn_l2_ring16<T, 1>), as with ISMHIP_KNN_HALF=1
     const float* seed_dk = nullptr;    // per query, an exact functor value its k-th best row is known not to exceed (NaN: none): the ring
                                        // kernel starts from the thresholds k_knn_seed_thr derives from it
+    // A RANGED search (knn_internal.h: KnnCandArgs::qrange), chunk `chunk` of the run_knn_stage2_lists driver: the queries are the
+    // entries q_base ... of the concatenated failure lists (live[i] == ~0u: padding between two lists), every group of 256 sweeps its
+    // own row range (the shortest / longest of them: range_rows_min / _max), and what stays unproven goes to `queue`, not to a scan.
+    const int* qrange = nullptr; const uint32_t* live = nullptr; KnnQueue* queue = nullptr;
+    int q_base = 0, chunk = 0, range_rows_min = 0, range_rows_max = 0;
+    const float* known_dk = nullptr;   // per query, see KnnQueueTag (the ranged search's proofs); seed_dk only sets the start thresholds
+    int q_ld = 0;                      // row stride of the queries when they are already padded (dim_pad); 0: dim
 };
 
 // How run_knn runs one search. knn_plan decides it from the request, the ctx switches and the codebook, without side effects.
@@ -758,7 +795,7 @@ struct KnnPlan {
     KnnCand cand;
     const void* kern;           // KNN_CAND_MFMA16 / KNN_CAND_RING16: the kernel instance (nullptr: not built)
     int BM, BN, threads;        // codeword rows and queries per tile, threads per workgroup
-    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join;
+    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join, ranged;
     int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
     int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
     int fb_tiles_per_split; KnnFbLayout fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout
@@ -787,7 +824,7 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     const bool ring = p.big_tile && p.mode == 0 && xb->words_f16t && (cb->dim + 15) / 16 > 2;
     p.half = ring && (rq.half || ctx->knn_half);                       // 128 x 256 tile, two workgroups per CU (k_knn_l2_ring16<T, 1>)
     // 256 x 256 tile with the whole query panel resident (k_knn_l2_ring16<T, 2, 2>): stage 1 on a rotated image of <= 160 coordinates
-    p.qpanel2 = ring && !p.half && ctx->knn_qpanel2 && rq.use_pca && PI.m > 0 && PI.m <= 160;
+    p.qpanel2 = ring && !p.half && ctx->knn_qpanel2 && rq.use_pca && PI.m > 0 && PI.m <= 160 && !rq.range_rows_max;
     // stage 1 of the two-stage search on the rotated, truncated image (pca.hip): same kernel, pca_m / 32 slices instead of dim / 32
     p.pca = rq.use_pca && ring && PI.m > 0;
     p.ring_nk = p.pca ? PI.m / 32 : ((cb->dim + 15) / 16 + 1) / 2;     // 32-k slices per row in the tiled images
@@ -797,7 +834,9 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     p.BN = !l2 ? CHI_B : (p.big_tile ? 256 : KNN_BN);
     p.slots = ring && !p.half ? 8 : 4;                                 // 16x16x32 MFMA shape: 8 lane slots per query and split
     p.n_qt = (nq + p.BN - 1) / p.BN;
-    const int n_mt = cb->n_words_pad / p.BM;
+    // (a ranged search plans for its longest range, and keeps a tile for every split of its shortest)
+    p.ranged = rq.range_rows_max > 0 && l2 && use_lp;
+    const int n_mt = (p.ranged ? rq.range_rows_max : cb->n_words_pad) / p.BM;
     if (l2) {
         const int max_s = (p.hell ? 64 * KNN_HELL_CPL : 64) / (p.slots * T);
         // at least three codebook splits (two when the candidate slots allow no more): with one, the 32 workgroups of an XCD hold 32
@@ -825,8 +864,9 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
         if (k > T) p.n_splits = std::max(p.n_splits, std::min(std::min(max_s, n_mt), (2 * k + T - 1) / T));    // at least 2k candidates to re-rank
         p.cand_per_split = T;
     }
+    if (p.ranged) p.n_splits = std::max(1, std::min(p.n_splits, rq.range_rows_min / p.BM));
     p.tiles_per_split = (n_mt + p.n_splits - 1) / p.n_splits;
-    p.n_splits = (n_mt + p.tiles_per_split - 1) / p.tiles_per_split;
+    if (!p.ranged) p.n_splits = (n_mt + p.tiles_per_split - 1) / p.tiles_per_split;      // (a range is dealt evenly: knn_range_split)
     p.n_cand = p.n_splits * p.cand_per_split;
     p.n_bound = l2 ? p.n_splits * p.slots : p.n_splits;
     // sampling pre-pass (stage 1 of the two-stage search on the 256 x 256 kernel, codebooks of >= 128 tiles): the best score
@@ -843,9 +883,9 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     else if (ring) {
         p.cand = KNN_CAND_RING16;
         p.threads = p.half ? 256 : 512;
-        if (p.half) { p.kern = knn_ring16_kernel(T, 1, 0); p.lds = p.lds_cap = Ring16Lds<1, 0>::total(0); }
+        if (p.half) { p.kern = knn_ring16_kernel(T, 1, 0, 0, p.ranged); p.lds = p.lds_cap = Ring16Lds<1, 0>::total(0); }
         else if (p.qpanel2) { p.kern = knn_ring16_kernel(T, 2, 2); p.lds = Ring16Lds<2, 2>::total(p.ring_nk); p.lds_cap = Ring16Lds<2, 2>::total(160 / 32); }
-        else { p.kern = knn_ring16_kernel(T, 2, 0); p.lds = p.lds_cap = Ring16Lds<2, 0>::total(0); }
+        else { p.kern = knn_ring16_kernel(T, 2, 0, 0, p.ranged); p.lds = p.lds_cap = Ring16Lds<2, 0>::total(0); }
     } else {
         p.cand = KNN_CAND_MFMA16;
         p.threads = p.big_tile ? 512 : 256;
@@ -859,6 +899,7 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
 struct KnnScratch {
     float *cand_val, *cand_bound; int* cand_idx; int n_cand, n_bound;      // candidate lists and slot bounds (after a merge: the folded slot)
     uint32_t *flag_count, *qrec, *items; unsigned long long* item_out; size_t q_items;    // counter block and queue of unproven work
+    uint32_t* qcount;                    // the queue's counters: the block's own, or those of the request's shared queue
     uint32_t* qsc;                       // the counter block's f16 scalars
 };
 // One search in flight: what the phases of run_knn hand to each other.
@@ -881,6 +922,8 @@ int knn_carve_scratch(KnnRun& r) {
     r.qrec = r.flag_count + KNN_CNT_WORDS; r.items = r.qrec + 3 * nq; r.qsc = r.flag_count + KNN_CNT_QSC;
     r.item_out = (unsigned long long*)(((uintptr_t)(r.items + 2 * r.q_items) + 7) & ~(uintptr_t)7);
     ISM_HIP(r.ctx, hipMemsetAsync(r.flag_count, 0, KNN_CNT_WORDS * sizeof(uint32_t), r.ctx->stream));
+    r.qcount = r.flag_count;
+    if (const KnnQueue* Q = r.rq->queue) { r.qcount = Q->count; r.qrec = Q->qrec; r.items = Q->items; r.item_out = Q->item_out; r.q_items = Q->q_items; }
     return ISMHIP_OK;
 }
 
@@ -941,6 +984,7 @@ int knn_launch_candidates(KnnRun& r) {
         a.qh = r.q_hi; a.ql = r.q_lo; a.nq = nq; a.out_scale = (const float*)(r.qsc + 1);
         a.tiles_per_split = p.tiles_per_split; a.n_splits = p.n_splits;
         a.cand_val = r.cand_val; a.cand_idx = r.cand_idx; a.cand_stride = r.n_cand; a.cand_bound = r.cand_bound; a.bound_stride = r.n_bound;
+        a.qrange = p.ranged ? r.rq->qrange : nullptr;
         int rc = ISMHIP_OK;
         if (p.cand == KNN_CAND_RING16) {
             rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
@@ -972,7 +1016,7 @@ int knn_launch_candidates(KnnRun& r) {
             if (p.seeded) {                                                  // needs the query image and, on the original image, its scalars
                 const VerifyParams vp = knn_verify_params(xb, cb->dim_pad, p.mode, r.qsc, true);
                 hipLaunchKernelGGL(k_knn_seed_thr, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, r.qq, nq, r.ldq, cb->dim, r.rq->seed_dk,
-                                   p.pca, p.pca ? knn_pca_verify(r, vp) : PcaVerify{}, vp, a.out_scale, thr0);
+                                   p.pca, p.pca ? knn_pca_verify(r, vp) : PcaVerify{}, vp, a.out_scale, thr0, r.rq->live);
                 ISM_CHECK_LAUNCH(ctx, "k_knn_seed_thr");
                 ++ctx->knn_seed_launches;
             }
@@ -1006,34 +1050,40 @@ int knn_rerank_prove(KnnRun& r, int32_t* idx_out, float* dist_out) {
     ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p;
     const VerifyParams vp = knn_verify_params(r.xb, cb->dim_pad, p.mode, r.qsc, true);
     const dim3 grid((r.nq + 3) / 4), block(256);
+    const KnnQueueTag tg{r.rq->live, r.rq->q_base, r.rq->chunk << 8, r.rq->known_dk};
     TimerScope trr(ctx, "knn_rerank");
     if (p.pca) {
         const PcaVerify pv = knn_pca_verify(r, vp);
         hipLaunchKernelGGL(k_knn_rerank_pca, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                           r.qq, r.nq, r.ldq, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, pv, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
+                           r.qq, r.nq, r.ldq, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, pv, r.k, idx_out, dist_out, r.qcount, r.qrec, r.items, tg);
     } else if (p.hell) {
         hipLaunchKernelGGL(k_knn_rerank_hell, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                           r.qq, r.nq, r.ldq, r.rq->hell_q, r.xb->shadow_perm, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
+                           r.qq, r.nq, r.ldq, r.rq->hell_q, r.xb->shadow_perm, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.qcount, r.qrec, r.items, tg);
     } else
     hipLaunchKernelGGL(k_knn_rerank, grid, block, 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words,
-                       r.qq, r.nq, r.ldq, r.metric, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.flag_count, r.qrec, r.items);
+                       r.qq, r.nq, r.ldq, r.metric, r.cand_idx, r.cand_val, r.n_cand, r.n_cand, r.cand_bound, r.n_bound, vp, r.k, idx_out, dist_out, r.qcount, r.qrec, r.items, tg);
     ISM_CHECK_LAUNCH(ctx, "k_knn_rerank");
     return ISMHIP_OK;
 }
 
-// exact scan of the queued slots' rows, folded into the results of the unproven queries
-int knn_exact_scan(KnnRun& r, int32_t* idx_out, float* dist_out) {
-    ismhip_ctx* ctx = r.ctx; const ismhip_codebook* cb = r.cb; const KnnPlan& p = r.p; const int k = r.k;
+// exact scan of the queued slots' rows, folded into the results of the unproven queries: one scan and one merge launch for a
+// queue, whichever searches filled it (q, idx_out, dist_out are indexed by the queue's query numbers)
+int knn_scan_queue(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int k, const float* q, int ldq, const KnnQueue& Q, const int* qrange,
+                   int32_t* idx_out, float* dist_out) {
     TimerScope ts(ctx, "knn_fallback");
-    const int n_tiles = cb->n_words_pad / p.BM;
     const auto scan = k <= 4 ? k_knn_fallback<4> : k_knn_fallback<KNN_MAX_K>;      // capacity of the per-item result lists
     const auto merge = k <= 4 ? k_knn_fallback_merge<4> : k_knn_fallback_merge<KNN_MAX_K>;
-    hipLaunchKernelGGL(scan, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, r.qq, r.ldq, r.metric, k,
-                       p.fb_tiles_per_split, n_tiles, p.BM, (int)p.fb_layout, r.flag_count, r.items, idx_out, dist_out, r.item_out, r.q_items);
+    hipLaunchKernelGGL(scan, dim3(1024), dim3(256), 0, ctx->stream, cb->words, cb->dim, cb->dim_pad, cb->n_words, q, ldq, metric, k,
+                       Q.desc[0], Q.desc[1], qrange, Q.count, Q.items, idx_out, dist_out, Q.item_out, Q.q_items);
     ISM_CHECK_LAUNCH(ctx, "k_knn_fallback");
-    hipLaunchKernelGGL(merge, dim3(256), dim3(256), 0, ctx->stream, k, r.flag_count, r.qrec, r.item_out, r.q_items, idx_out, dist_out);
+    hipLaunchKernelGGL(merge, dim3(256), dim3(256), 0, ctx->stream, k, Q.count, Q.qrec, Q.item_out, Q.q_items, idx_out, dist_out);
     ISM_CHECK_LAUNCH(ctx, "k_knn_fallback_merge");
     return ISMHIP_OK;
+}
+KnnFbDesc knn_fb_desc(const KnnPlan& p, const ismhip_codebook* cb) { return KnnFbDesc{p.fb_tiles_per_split, cb->n_words_pad / p.BM, p.BM, (int)p.fb_layout, p.n_splits}; }
+int knn_exact_scan(KnnRun& r, int32_t* idx_out, float* dist_out) {
+    KnnQueue Q{r.qcount, r.qrec, r.items, r.item_out, r.q_items, {knn_fb_desc(r.p, r.cb), KnnFbDesc{}}};
+    return knn_scan_queue(r.ctx, r.cb, r.metric, r.k, r.qq, r.ldq, Q, nullptr, idx_out, dist_out);
 }
 
 int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k, int T,
@@ -1043,10 +1093,11 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
     r.ctx = ctx; r.cb = cb; r.rq = &rq; r.metric = metric; r.nq = nq; r.k = k; r.T = T;
     r.p = knn_plan(ctx, cb, metric, nq, k, T, rq);
     if (r.p.cand == KNN_CAND_MFMA16 && !r.p.kern) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: f16 256x256 tile without the ring not built");
+    if (r.p.cand == KNN_CAND_RING16 && !r.p.kern) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: ranged ring instance not built for this T");
     r.xb = r.p.hell ? cb->chi_shadow : cb;
     r.PI = rq.use_pca == 2 ? &cb->pca2 : &cb->pca;
-    r.qq = q; r.ldq = cb->dim;
-    if (cb->dim_pad != cb->dim) {
+    r.qq = q; r.ldq = rq.q_ld ? rq.q_ld : cb->dim;
+    if (cb->dim_pad != r.ldq) {
         float* qpad = (float*)ism_scratch(ctx, SCR_QPAD, (size_t)nq * cb->dim_pad * sizeof(float));
         if (!qpad) return ISMHIP_ERR_NOMEM;
         const size_t tot = (size_t)nq * cb->dim_pad;
@@ -1059,7 +1110,8 @@ int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, cons
     if (rc == ISMHIP_OK) rc = knn_launch_candidates(r);
     if (rc == ISMHIP_OK) rc = knn_rerank_prove(r, idx_out, dist_out);
     if (rc != ISMHIP_OK) return rc;
-    if (rq.stage1) { *rq.stage1 = KnnStage1{r.flag_count, r.qrec}; return ISMHIP_OK; }
+    if (rq.stage1) { *rq.stage1 = KnnStage1{r.flag_count, r.qrec, r.items, r.p.n_splits, r.p.slots, r.p.tiles_per_split * r.p.BM}; return ISMHIP_OK; }
+    if (rq.queue) { rq.queue->desc[rq.chunk] = knn_fb_desc(r.p, cb); return ISMHIP_OK; }      // the caller scans the queue once, after its last search
     rc = knn_exact_scan(r, idx_out, dist_out);
     if (rc != ISMHIP_OK) return rc;
     if (ctx->timers_on) ISM_HIP(ctx, hipMemcpyAsync(ctx->knn_stats, r.flag_count, 8, hipMemcpyDeviceToHost, ctx->stream));   // read back after a sync
@@ -1098,15 +1150,39 @@ __global__ void k_knn_scatter_results(const uint32_t* __restrict__ list2, int n2
 // call; n2 == 0: nothing left to do), their rows in q2, their ids in list2, and room for the second stage's results idx2 / dist2,
 // which knn_scatter_stage2 writes to the queries' places in the caller's arrays. dk2 = the k-th exact values of stage 1's results
 // idx1 / dist1 (the seeds of a seeded second search; nullptr: none wanted).
-struct KnnStage2 { int n2; float* q2; uint32_t* list2; int32_t* idx2; float* dist2; float* dk2; };
+// want_lists (set by the caller, nq = its query count): the per-split failure lists are made first (k_knn_split_lists: lists_d[s * nq
+// ...], head_d = {n2, |list 0|, ...}) and their sizes cnt travel in the same read-back; the caller then runs run_knn_stage2_lists
+// or, if that declines, knn_gather_unsplit.
+struct KnnStage2 { int n2; float* q2; uint32_t* list2; int32_t* idx2; float* dist2; float* dk2;
+                   bool want_lists = false; uint32_t *head_d = nullptr, *lists_d = nullptr; uint32_t cnt[16] = {}; };
+int knn_gather_unsplit(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const float* q, int k, KnnStage2& g, const int32_t* idx1, const float* dist1);
+__global__ void k_knn_split_lists(const uint32_t* __restrict__ flag_count, const uint32_t* __restrict__ qrec, const uint32_t* __restrict__ items,
+                                  int slots, int nq, uint32_t* __restrict__ head, uint32_t* __restrict__ lists);      // with the other kernels of the lists, below
 int knn_gather_stage2(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const float* q, int k, KnnStage2& g,
-                      const int32_t* idx1, const float* dist1) {
-    uint32_t n2u = 0;
-    ISM_HIP(ctx, hipMemcpyAsync(&n2u, s1.flag_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+                      const int32_t* idx1, const float* dist1, int nq = 0) {
+    uint32_t hb[17] = {0};
+    if (g.want_lists) {
+        g.head_d = (uint32_t*)ism_scratch(ctx, SCR_KNN_LISTS, (32 + (size_t)s1.n_splits * nq) * sizeof(uint32_t));
+        if (!g.head_d) return ISMHIP_ERR_NOMEM;
+        g.lists_d = g.head_d + 32;
+        ISM_HIP(ctx, hipMemsetAsync(g.head_d, 0, 32 * sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(k_knn_split_lists, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)s1.flag_count, (const uint32_t*)s1.qrec, (const uint32_t*)s1.items,
+                           s1.slots, nq, g.head_d, g.lists_d);
+        ISM_CHECK_LAUNCH(ctx, "k_knn_split_lists");
+        ISM_HIP(ctx, hipMemcpyAsync(hb, g.head_d, 17 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    } else ISM_HIP(ctx, hipMemcpyAsync(hb, s1.flag_count, 4, hipMemcpyDeviceToHost, ctx->stream));
     ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->knn_stage2_queries = n2u;
-    const int n2 = g.n2 = (int)n2u;
-    if (n2 == 0) { ctx->knn_stats[0] = ctx->knn_stats[1] = 0; return ISMHIP_OK; }
+    ctx->knn_stage2_queries = hb[0];
+    for (int s = 0; s < 16; ++s) g.cnt[s] = hb[1 + s];
+    ctx->knn_stage2_list_entries = 0;
+    for (int s = 0; s < 16; ++s) ctx->knn_stage2_list_entries += g.cnt[s];
+    g.n2 = (int)hb[0];
+    if (g.n2 == 0) { ctx->knn_stats[0] = ctx->knn_stats[1] = 0; return ISMHIP_OK; }
+    if (g.want_lists) return ISMHIP_OK;
+    return knn_gather_unsplit(ctx, cb, s1, q, k, g, idx1, dist1);
+}
+int knn_gather_unsplit(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const float* q, int k, KnnStage2& g, const int32_t* idx1, const float* dist1) {
+    const int n2 = g.n2;
     g.q2 = (float*)ism_scratch(ctx, SCR_KNN_Q2, (size_t)n2 * cb->dim * sizeof(float));
     g.list2 = (uint32_t*)ism_scratch(ctx, SCR_KNN_LIST2, (size_t)n2 * (sizeof(uint32_t) + (size_t)k * (sizeof(int32_t) + sizeof(float)) + (idx1 ? sizeof(float) : 0)));
     if (!g.q2 || !g.list2) return ISMHIP_ERR_NOMEM;
@@ -1123,6 +1199,184 @@ int knn_scatter_stage2(ismhip_ctx* ctx, const KnnStage2& g, int k, int32_t* idx_
     return ISMHIP_OK;
 }
 
+// ---- stage 2 on per-split failure lists ---------------------------------------------------------------------------------------------
+// Stage 1 proves a query split by split: all the slots of one split report the same bound, so a query whose proof failed has failed
+// it in some of stage 1's codebook splits and holds it in the others (bench data, two splits: 67 % of the stage-2 queries failed in
+// one split only). A split whose slots were proven needs no second look: every row stage 1 dropped there lies strictly beyond U, the
+// exact k-th value of stage 1's answer; stage 2 can only LOWER the query's k-th value, so that proof still stands afterwards. Hence
+// one failure list per stage-1 split, and a query is searched again only on the rows of the splits in whose lists it stands.
+//   k_knn_split_lists   from stage 1's queue: list s = the queries with an unproven slot of split s; head = {failing queries, |list s|}
+//                       (read back with the one round trip the gather makes anyway)
+//   k_knn_range_layout  the lists laid end to end, each padded to whole groups of 256 queries: the qrange table (knn_internal.h)
+//   k_knn_gather_lists  the rows, ids (~0u: padding) and seeds of the concatenated lists
+//   run_knn             RANGED searches over that array, cut into chunks and given their kernels by size exactly as an unsplit stage 2
+//                       is; their proofs cover the searched range, and what they cannot prove collects in ONE queue
+//   knn_scan_queue      one exact scan for the call
+//   k_knn_merge_lists   the answer of a query = the k smallest (distance, row) pairs of stage 1's answer and the result of every
+//                       list it stands in, rows unique, ties to the lower row: stage 1's rows may lie in a split that was not searched
+//                       again. One launch per list: a query stands in a list once, but may stand in several lists.
+__global__ void k_knn_split_lists(const uint32_t* __restrict__ flag_count, const uint32_t* __restrict__ qrec, const uint32_t* __restrict__ items,
+                                  int slots, int nq, uint32_t* __restrict__ head, uint32_t* __restrict__ lists) {
+    const uint32_t n = flag_count[KNN_CNT_QUERIES];
+    if (blockIdx.x == 0 && threadIdx.x == 0) head[0] = n;
+    const int lane = lane_id();
+    // a record per lane; whole waves stay in the loop: the places in a list are handed out with ONE atomic per wave and split (tens
+    // of thousands of same-address atomics serialise)
+    for (uint32_t t0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); t0 < n; t0 += gridDim.x * blockDim.x) {
+        const uint32_t t = t0 + lane;
+        uint32_t qi = 0u, mask = 0u;                                    // at most 64 slots of >= 4: at most 16 splits
+        if (t < n) {
+            qi = qrec[3 * (size_t)t];
+            const uint32_t ibase = qrec[3 * (size_t)t + 1], ni = qrec[3 * (size_t)t + 2];
+            for (uint32_t j = 0; j < ni; ++j) mask |= 1u << (items[2 * (size_t)(ibase + j) + 1] / (uint32_t)slots);
+        }
+        uint32_t any = mask;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) any |= __shfl_xor(any, o, 64);
+        while (any) {
+            const int s = __ffs((int)any) - 1; any &= any - 1u;
+            const unsigned long long in = __ballot((mask >> s) & 1u);
+            uint32_t base = 0u;
+            if (lane == 0) base = atomicAdd(&head[1 + s], (uint32_t)__popcll(in));
+            base = __shfl(base, 0, 64);
+            if ((mask >> s) & 1u) lists[(size_t)s * nq + base + __popcll(in & ((1ull << lane) - 1ull))] = qi;
+        }
+    }
+}
+__global__ void k_knn_range_layout(const uint32_t* __restrict__ head, int n_lists, int rows_per_split, int n_rows, int* __restrict__ qrange) {
+    int off = 0;
+    for (int s = 0; s < n_lists; ++s) {
+        const int groups = (int)((head[1 + s] + 255u) / 256u);
+        for (int g = threadIdx.x; g < groups; g += blockDim.x) {
+            int* e = qrange + 4 * (off / 256 + g);
+            e[0] = s * rows_per_split; e[1] = min(n_rows, (s + 1) * rows_per_split); e[2] = s; e[3] = off;
+        }
+        off += groups * 256;
+    }
+}
+// entry i of the concatenated lists (a workgroup each): row into q2 (ld floats apart, zero beyond dim and for padding), id, seed
+__global__ __launch_bounds__(256) void k_knn_gather_lists(const uint32_t* __restrict__ head, const uint32_t* __restrict__ lists, int nq, const int* __restrict__ qrange,
+                                                          const float* __restrict__ q, int dim, int ld, float* __restrict__ q2, uint32_t* __restrict__ list2,
+                                                          const int32_t* __restrict__ idx1, const float* __restrict__ dist1, int k, float* __restrict__ dk2) {
+    const int i = blockIdx.x;
+    const int* rg = qrange + 4 * (i >> 8);
+    const int s = rg[2], pos = i - rg[3];
+    const bool live = (uint32_t)pos < head[1 + s];
+    const uint32_t qi = live ? lists[(size_t)s * nq + pos] : ~0u;
+    if (threadIdx.x == 0) {
+        list2[i] = qi;
+        if (dk2) dk2[i] = live && idx1[(size_t)qi * k + (k - 1)] >= 0 ? dist1[(size_t)qi * k + (k - 1)] : __builtin_nanf("");
+    }
+    for (int c = threadIdx.x; c < ld; c += blockDim.x) q2[(size_t)i * ld + c] = live && c < dim ? q[(size_t)qi * dim + c] : 0.f;
+}
+// entries i0 .. i0 + n - 1 (one list: distinct queries) folded into the caller's results
+__global__ void k_knn_merge_lists(const uint32_t* __restrict__ list2, int i0, int n, int k, const int32_t* __restrict__ idx2, const float* __restrict__ dist2,
+                                  int32_t* __restrict__ idx_out, float* __restrict__ dist_out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const size_t a = (size_t)list2[i0 + t] * k, b = (size_t)(i0 + t) * k;
+    // both inputs are ascending in (distance bits, row) with the empty entries (-1) last, as knn_select_write leaves them
+    int32_t oi[KNN_MAX_K]; float od[KNN_MAX_K];
+    int ia = 0, ib = 0, no = 0;
+    while (no < k) {
+        const bool ha = ia < k && idx_out[a + ia] >= 0, hb = ib < k && idx2[b + ib] >= 0;
+        if (!ha && !hb) break;
+        const unsigned long long ka = ha ? ((unsigned long long)__float_as_uint(dist_out[a + ia]) << 32) | (unsigned)idx_out[a + ia] : ~0ull;
+        const unsigned long long kb = hb ? ((unsigned long long)__float_as_uint(dist2[b + ib]) << 32) | (unsigned)idx2[b + ib] : ~0ull;
+        const unsigned long long key = ka <= kb ? ka : kb;
+        if (ka <= kb) ++ia; else ++ib;
+        bool dup = false;                                               // a row both searches found
+        for (int j = 0; j < no; ++j) dup |= oi[j] == (int32_t)(key & 0xffffffffull);
+        if (!dup) { oi[no] = (int32_t)(key & 0xffffffffull); od[no] = __uint_as_float((unsigned)(key >> 32)); ++no; }
+    }
+    for (int j = 0; j < k; ++j) { idx_out[a + j] = j < no ? oi[j] : -1; dist_out[a + j] = j < no ? od[j] : __builtin_nanf(""); }
+}
+
+// the chunk of a stage 2 over n queries that starts at o: a multiple of 32 768 queries, or the remainder (run_knn_two_stage)
+inline int knn_stage2_chunk(int n_total, int o) { const int left = n_total - o; return left >= 32768 ? left / 32768 * 32768 : left; }
+// the request of a stage-2 chunk of n queries (run_knn_two_stage explains the chunks).
+// A chunk below one full round (a shard of the split on N GPUs: 8 300 stage-2 queries per rank at N = 8) would be 33 query tiles
+// x 2 codebook splits = 66 workgroups on 256 CUs. The 128-query tile variant (k_knn_l2_ring16<T, 1>: four lane slots per split,
+// so four splits) doubles the workgroups twice over instead.
+KnnRequest knn_stage2_request(const ismhip_ctx* ctx, const ismhip_codebook* cb, int n, const float* seed_dk) {
+    KnnRequest r2; r2.tname = "knn_stage2"; r2.many_splits = n < 4096;
+    // (on the stage-2 image, if the codebook has one: 8 slices per tile instead of 11 on the bench data)
+    r2.use_pca = cb->pca2.m > 0 && !(n < 4096) ? 2 : 0;
+    r2.half = n >= 4096 && n < 32768 && !ctx->knn_stage2_t4;
+    r2.seed_dk = seed_dk;
+    return r2;
+}
+
+// cnt[s] = |list s| (host copy of the head). taken = false: the lists would not save an eighth of the sweep (queries that failed
+// everywhere), or stage 1's splits do not end on 256-row tiles: the caller runs the unsplit stage 2.
+int run_knn_stage2_lists(ismhip_ctx* ctx, const ismhip_codebook* cb, const KnnStage1& s1, const uint32_t* head_d, const uint32_t* lists_d, const uint32_t* cnt, int n2,
+                         int nq, const float* q, int k, int32_t* idx_out, float* dist_out, bool& taken) {
+    taken = false;
+    const int S = s1.n_splits, rps = s1.rows_per_split, n_rows = cb->n_words_pad;
+    if (S < 2 || rps % 256 != 0 || n_rows % 256 != 0) return ISMHIP_OK;
+    int off[17] = {0}, rows_min = n_rows, rows_max = 0;
+    double work = 0.0;
+    for (int s = 0; s < S; ++s) {
+        const int rows = std::min(n_rows, (s + 1) * rps) - s * rps;
+        off[s + 1] = off[s] + (int)((cnt[s] + 255u) / 256u) * 256;
+        if (cnt[s]) { rows_min = std::min(rows_min, rows); rows_max = std::max(rows_max, rows); work += (double)(off[s + 1] - off[s]) * rows; }
+    }
+    if (work * 8.0 > (double)n2 * n_rows * 7.0) return ISMHIP_OK;
+    taken = true;
+    ++ctx->knn_stage2_ranged;
+    const int N = off[S], ld = cb->dim_pad;
+    // every chunk's plan first: the queue holds the slots of all of them
+    const bool seed = ctx->knn_stage2_seed;
+    size_t q_items = 0; int n_chunks = 0;
+    for (int o = 0; o < N; ++n_chunks) {
+        const int n = knn_stage2_chunk(N, o);
+        KnnRequest r2 = knn_stage2_request(ctx, cb, n, nullptr);
+        r2.range_rows_min = rows_min; r2.range_rows_max = rows_max;
+        q_items += (size_t)n * knn_plan(ctx, cb, ISMHIP_METRIC_L2SQ, n, k, 4, r2).n_bound;
+        o += n;
+    }
+    if (n_chunks > 2) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: more than two stage-2 chunks");       // (knn_stage2_chunk makes at most two)
+    const int KM = k > 4 ? KNN_MAX_K : 4;
+    float* q2 = (float*)ism_scratch(ctx, SCR_KNN_Q2, (size_t)N * ld * sizeof(float));
+    uint32_t* list2 = (uint32_t*)ism_scratch(ctx, SCR_KNN_LIST2, (size_t)N * (sizeof(uint32_t) + (size_t)k * (sizeof(int32_t) + sizeof(float)) + sizeof(float)) + (size_t)(N / 256) * 4 * sizeof(int));
+    uint32_t* qmem = (uint32_t*)ism_scratch(ctx, SCR_KNN_QUEUE, (KNN_CNT_WORDS + 3 * (size_t)N + 2 * q_items) * sizeof(uint32_t) + 8 + (q_items + KNN_FB_UNITS) * KM * sizeof(unsigned long long));
+    if (!q2 || !list2 || !qmem) return ISMHIP_ERR_NOMEM;
+    int32_t* idx2 = (int32_t*)(list2 + N);
+    float* dist2 = (float*)(idx2 + (size_t)N * k);
+    float* dk2 = dist2 + (size_t)N * k;
+    int* qrange = (int*)(dk2 + N);
+    KnnQueue Q{};
+    Q.count = qmem; Q.qrec = qmem + KNN_CNT_WORDS; Q.items = Q.qrec + 3 * (size_t)N; Q.q_items = q_items;
+    Q.item_out = (unsigned long long*)(((uintptr_t)(Q.items + 2 * q_items) + 7) & ~(uintptr_t)7);
+    ISM_HIP(ctx, hipMemsetAsync(Q.count, 0, KNN_CNT_WORDS * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_knn_range_layout, dim3(1), dim3(256), 0, ctx->stream, head_d, S, rps, n_rows, qrange);
+    ISM_CHECK_LAUNCH(ctx, "k_knn_range_layout");
+    hipLaunchKernelGGL(k_knn_gather_lists, dim3(N), dim3(256), 0, ctx->stream, head_d, lists_d, nq, (const int*)qrange, q, cb->dim, ld, q2, list2,
+                       (const int32_t*)idx_out, (const float*)dist_out, k, dk2);
+    ISM_CHECK_LAUNCH(ctx, "k_knn_gather_lists");
+    int chunk = 0;
+    for (int o = 0; o < N; ++chunk) {
+        const int n = knn_stage2_chunk(N, o);
+        KnnRequest r2 = knn_stage2_request(ctx, cb, n, seed ? dk2 + o : nullptr);
+        r2.qrange = qrange + 4 * (o / 256); r2.live = list2 + o; r2.queue = &Q; r2.q_base = o; r2.chunk = chunk;
+        r2.range_rows_min = rows_min; r2.range_rows_max = rows_max; r2.q_ld = ld; r2.known_dk = dk2 + o;
+        const int rc = run_knn(ctx, cb, ISMHIP_METRIC_L2SQ, n, q2 + (size_t)o * ld, k, 4, idx2 + (size_t)o * k, dist2 + (size_t)o * k, r2);
+        if (rc != ISMHIP_OK) return rc;
+        o += n;
+    }
+    // the scan's slots are slots of the searched ranges: what was not searched again stays proven (above)
+    int rc = knn_scan_queue(ctx, cb, ISMHIP_METRIC_L2SQ, k, q2, ld, Q, qrange, idx2, dist2);
+    if (rc != ISMHIP_OK) return rc;
+    if (ctx->timers_on) ISM_HIP(ctx, hipMemcpyAsync(ctx->knn_stats, Q.count, 8, hipMemcpyDeviceToHost, ctx->stream));   // read back after a sync
+    for (int s = 0; s < S; ++s) {
+        if (!cnt[s]) continue;
+        hipLaunchKernelGGL(k_knn_merge_lists, dim3((cnt[s] + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t*)list2, off[s], (int)cnt[s], k,
+                           (const int32_t*)idx2, (const float*)dist2, idx_out, dist_out);
+        ISM_CHECK_LAUNCH(ctx, "k_knn_merge_lists");
+    }
+    return ISMHIP_OK;
+}
+
 int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out) {
     KnnStage1 s1{};
     KnnRequest r1; r1.stage1 = &s1; r1.use_pca = 1;
@@ -1130,8 +1384,17 @@ int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const 
     if (rc != ISMHIP_OK) return rc;
     KnnStage2 g;
     const bool seed = ctx->knn_stage2_seed;
-    rc = knn_gather_stage2(ctx, cb, s1, q, k, g, seed ? idx_out : nullptr, seed ? dist_out : nullptr);
+    // ISMHIP_KNN_STAGE2_SPLITS=0: every stage-2 query sweeps the whole codebook again
+    g.want_lists = ctx->knn_stage2_splits && s1.n_splits >= 2 && s1.n_splits <= 16;
+    rc = knn_gather_stage2(ctx, cb, s1, q, k, g, seed ? idx_out : nullptr, seed ? dist_out : nullptr, nq);
     if (rc != ISMHIP_OK || g.n2 == 0) return rc;
+    if (g.want_lists) {
+        bool taken = false;
+        rc = run_knn_stage2_lists(ctx, cb, s1, g.head_d, g.lists_d, g.cnt, g.n2, nq, q, k, idx_out, dist_out, taken);
+        if (rc != ISMHIP_OK || taken) return rc;
+        rc = knn_gather_unsplit(ctx, cb, s1, q, k, g, seed ? idx_out : nullptr, seed ? dist_out : nullptr);
+        if (rc != ISMHIP_OK) return rc;
+    }
     const int n2 = g.n2;
     // Stage 2 is SEEDED (k_knn_seed_thr): every lane slot starts from the threshold that stage 1's k-th exact value allows, so a slot
     // that does not overflow is proven by construction and few scores ever reach the insertion code. Four candidates per slot and two
@@ -1142,15 +1405,8 @@ int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const 
     // (measured from a cold start: 4.5 vs 6.7 ms). So a large stage 2 is cut into a multiple of 32 768 queries and a remainder, which
     // (below 4096 queries) takes the merged-splits kernel that fills the chip with splits instead of query tiles.
     for (int o = 0; o < n2;) {
-        const int left = n2 - o, n = left >= 32768 ? left / 32768 * 32768 : left;
-        // a chunk below one full round (a shard of the split on N GPUs: 8 300 stage-2 queries per rank at N = 8) would be 33 query tiles
-        // x 2 codebook splits = 66 workgroups on 256 CUs. The 128-query tile variant (k_knn_l2_ring16<T, 1>: four lane slots per split,
-        // so four splits) doubles the workgroups twice over instead.
-        KnnRequest r2; r2.tname = "knn_stage2"; r2.many_splits = n < 4096;
-        // (on the stage-2 image, if the codebook has one: 8 slices per tile instead of 11 on the bench data)
-        r2.use_pca = cb->pca2.m > 0 && !(n < 4096) ? 2 : 0;
-        r2.half = n >= 4096 && n < 32768 && !ctx->knn_stage2_t4;
-        r2.seed_dk = g.dk2 ? g.dk2 + o : nullptr;
+        const int n = knn_stage2_chunk(n2, o);
+        const KnnRequest r2 = knn_stage2_request(ctx, cb, n, g.dk2 ? g.dk2 + o : nullptr);
         rc = run_knn(ctx, cb, ISMHIP_METRIC_L2SQ, n, g.q2 + (size_t)o * cb->dim, k, 4, g.idx2 + (size_t)o * k, g.dist2 + (size_t)o * k, r2);
         if (rc != ISMHIP_OK) return rc;
         o += n;

@@ -202,10 +202,19 @@ struct KnnCandArgs {
     const u16 *wh, *wl; const float* word_norm; int n_tiles_m, ld, k_steps;
     const u16 *qh, *ql; int nq; const float* out_scale; int tiles_per_split, n_splits;
     float* cand_val; int* cand_idx; int cand_stride; float* cand_bound; int bound_stride;
+    const int* qrange;      // ranged search (knn_range_split), else nullptr: every query sweeps the tiles [0, n_tiles_m)
 };
+// A RANGED search (stage 2 of the two-stage search on per-split failure lists, knn.hip): the queries come in groups of 256 and group
+// g sweeps only the codeword rows [qrange[4 g], qrange[4 g + 1]) (multiples of 256); qrange[4 g + 2] = the list the group belongs to,
+// qrange[4 g + 3] = the first query of that list. The tiles of a range are dealt to the launch's splits evenly (never an empty split:
+// the host keeps n_splits <= the tiles of the shortest range), and rows stay GLOBAL rows: only the sweep is shorter.
+__host__ __device__ inline void knn_range_split(int lo, int hi, int split, int n_splits, int& mt0, int& mt1) {
+    const long long len = hi - lo;
+    mt0 = lo + (int)(len * split / n_splits); mt1 = lo + (int)(len * (split + 1) / n_splits);
+}
 // the instance for T candidates per slot (1 .. 4, else nullptr): WR x 128 codeword rows per tile, QP = 2 with the resident query
-// panel, PRE = 1 the sampling pre-pass
-const void* knn_ring16_kernel(int T, int WR, int QP, int PRE = 0);
+// panel, PRE = 1 the sampling pre-pass, RNG = 1 the ranged sweep (KnnCandArgs::qrange; built for T = 4, QP = 0 only)
+const void* knn_ring16_kernel(int T, int WR, int QP, int PRE = 0, int RNG = 0);
 // one candidate launch of kern = knn_ring16_kernel(T, ...). thr0 != nullptr: every lane slot of query i starts from the threshold
 // thr0[i] (accumulator units) instead of -inf. pre_step > 0: the sampling pre-pass over every pre_step-th tile runs first and leaves
 // those thresholds in thr0[nq rounded up to 256], relaxed by pre_relax; pre_step == 0: the caller has written thr0[nq]

@@ -46,7 +46,8 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_knn_l2_mfma16(const u16* __
                                                           int tiles_per_split, int n_splits,
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int cand_stride,
                                                           float* __restrict__ cand_bound, int bound_stride,
-                                                          const float* __restrict__ emit_tau, uint32_t* __restrict__ emit_cnt, uint32_t* __restrict__ emit_list, int emit_cap) {
+                                                          const float* __restrict__ emit_tau, uint32_t* __restrict__ emit_cnt, uint32_t* __restrict__ emit_list, int emit_cap,
+                                                          const int* __restrict__ qrange /* ranged sweep (knn_internal.h), else nullptr */) {
     constexpr int BM = WR * MI * 32, BN = WC * NI * 32, NT = WR * WC * 64;
     constexpr int SEGS = KB / 8;                      // 16-byte segments per row
     constexpr int KS = KB / 16;                       // MFMA k-steps per slice
@@ -70,8 +71,9 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void k_knn_l2_mfma16(const u16* __
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
     const int split = jx % n_splits, qtile = (jx / n_splits) * 8 + xcd;
     if (qtile * BN >= nq) return;
-    const int mt0 = split * tiles_per_split;
-    const int mt1 = min(n_tiles_m, mt0 + tiles_per_split);
+    int mt0 = split * tiles_per_split;
+    int mt1 = min(n_tiles_m, mt0 + tiles_per_split);
+    if (qrange) { const int* rg = qrange + 4 * ((qtile * BN) >> 8); knn_range_split(rg[0] / BM, rg[1] / BM, split, n_splits, mt0, mt1); }
     const int nk = (k_steps + KS - 1) / KS;
 
     // staging: thread -> (row srow + p*RPP, segment sseg); RPP is a multiple of 16, so the swizzle term is the same for every pass
@@ -245,7 +247,7 @@ const void* knn_mfma16_kernel(int T, int mode, bool big_tile) {
 int knn_mfma16_launch(ismhip_ctx* ctx, const void* kern, unsigned grid, int threads, size_t lds, KnnCandArgs a,
                       const float* emit_tau, uint32_t* emit_cnt, uint32_t* emit_list, int emit_cap) {
     void* args[] = {&a.wh, &a.wl, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.ql, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits,
-                    &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &emit_tau, &emit_cnt, &emit_list, &emit_cap};
+                    &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &emit_tau, &emit_cnt, &emit_list, &emit_cap, &a.qrange};
     ISM_HIP(ctx, hipLaunchKernel(kern, dim3(grid), dim3(threads), args, lds, ctx->stream));
     ISM_CHECK_LAUNCH(ctx, (emit_tau ? "k_knn_l2_mfma16<emit>" : "k_knn_l2_mfma16"));
     return ISMHIP_OK;

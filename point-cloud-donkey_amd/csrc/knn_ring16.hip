@@ -86,13 +86,16 @@ __device__ __forceinline__ void push_cnd(TopT<N>& tp, float x, int idx) {
 // and refines itself independently (measured: 28 inserting lanes per wave and tile, 27 % of the kernel at 4 slices per tile); the
 // best of a 1/16 sample is about the 16th best score of the query overall, so with it as the start only a few dozen scores per
 // QUERY (not per list) ever reach the insertion code.
-template <int T, int WR = 2, int QP = 0, int PRE = 0>
+// RNG = 1 (stage 2 on per-split failure lists): a RANGED sweep -- the query tile's own row range from qrange (knn_internal.h), cut
+// evenly into the launch's splits. Only where the workgroup picks its tiles: loop and epilogue are the same code, and rows are global.
+template <int T, int WR = 2, int QP = 0, int PRE = 0, int RNG = 0>
 __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __restrict__ wh, const float* __restrict__ word_norm, int n_tiles_m, int ld, int k_steps,
                                                           const u16* __restrict__ qh, int nq, const float* __restrict__ out_scale,
                                                           int tiles_per_split, int n_splits,
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int cand_stride,
                                                           float* __restrict__ cand_bound, int bound_stride, unsigned int* __restrict__ stream_clock,
-                                                          const float* __restrict__ thr_init, float* __restrict__ thr_out, int tile_step, float thr_relax) {
+                                                          const float* __restrict__ thr_init, float* __restrict__ thr_out, int tile_step, float thr_relax,
+                                                          const int* __restrict__ qrange) {
     using L = Ring16Lds<WR, QP>;
     constexpr int WC = 4, MT = 8, NT = 4, KB = RG_KB, BM = WR * 128, BN = RG_BN;
     constexpr int STAGES = L::STAGES, STAGE_HALVES = L::STAGE_HALVES, CNS = 256;
@@ -114,8 +117,14 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
     const int split = jx % n_splits, qtile = (jx / n_splits) * 8 + xcd;
     if (qtile * BN >= nq) return;
-    const int mt0 = split * tiles_per_split;
-    const int n_t = PRE ? (n_tiles_m + tile_step - 1) / tile_step : min(n_tiles_m, mt0 + tiles_per_split) - mt0;
+    int mt0 = split * tiles_per_split, mt1 = min(n_tiles_m, mt0 + tiles_per_split);
+    int clk_slot = xcd * n_splits + split;
+    if (RNG) {                                                         // BN = 256: the query tile IS the group
+        const int* rg = qrange + 4 * qtile;
+        knn_range_split(rg[0] / BM, rg[1] / BM, split, n_splits, mt0, mt1);
+        clk_slot = xcd * 64 + ((rg[2] * n_splits + split) & 63);      // a clock per (XCD, list, split): the lists sweep different rows
+    }
+    const int n_t = PRE ? (n_tiles_m + tile_step - 1) / tile_step : mt1 - mt0;
     if (n_t <= 0) return;
     const int nk = (k_steps + 1) / 2;
     const int G = n_t * nk;
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
     // around. Nobody waits for anybody.
     int toff = 0; unsigned c0 = 0u;
     if (stream_clock) {
-        unsigned int* clk = stream_clock + xcd * n_splits + split;
+        unsigned int* clk = stream_clock + clk_slot;
         if (tid == 0) *(volatile unsigned*)ring = __hip_atomic_load(clk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         c0 = __builtin_amdgcn_readfirstlane(*(volatile unsigned*)ring);
@@ -421,7 +430,11 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
 }
 
 template <int T>
-const void* ring16_instance(int WR, int QP, int PRE) {
+const void* ring16_instance(int WR, int QP, int PRE, int RNG) {
+    if (RNG) {                                                         // stage 2 only: four candidates per slot
+        if constexpr (T == 4) return WR == 1 ? (const void*)k_knn_l2_ring16<4, 1, 0, 0, 1> : (const void*)k_knn_l2_ring16<4, 2, 0, 0, 1>;
+        else return nullptr;
+    }
     if (PRE) return (const void*)k_knn_l2_ring16<T, 2, 0, 1>;
     if (WR == 1) return (const void*)k_knn_l2_ring16<T, 1>;
     return QP ? (const void*)k_knn_l2_ring16<T, 2, 2> : (const void*)k_knn_l2_ring16<T, 2>;
@@ -429,12 +442,12 @@ const void* ring16_instance(int WR, int QP, int PRE) {
 
 }  // namespace
 
-const void* knn_ring16_kernel(int T, int WR, int QP, int PRE) {
+const void* knn_ring16_kernel(int T, int WR, int QP, int PRE, int RNG) {
     switch (T) {
-    case 1: return ring16_instance<1>(WR, QP, PRE);
-    case 2: return ring16_instance<2>(WR, QP, PRE);
-    case 3: return ring16_instance<3>(WR, QP, PRE);
-    case 4: return ring16_instance<4>(WR, QP, PRE);
+    case 1: return ring16_instance<1>(WR, QP, PRE, RNG);
+    case 2: return ring16_instance<2>(WR, QP, PRE, RNG);
+    case 3: return ring16_instance<3>(WR, QP, PRE, RNG);
+    case 4: return ring16_instance<4>(WR, QP, PRE, RNG);
     }
     return nullptr;
 }
@@ -447,14 +460,14 @@ int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, i
         const size_t plds = Ring16Lds<2, 0>::total(0);
         const int rc2 = ism_lds_cap(ctx, pk, plds);
         if (rc2 != ISMHIP_OK) return rc2;
-        int one = 1, all = a.n_tiles_m; unsigned int* noclk = nullptr; const float* noinit = nullptr;
-        void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax};
+        int one = 1, all = a.n_tiles_m; unsigned int* noclk = nullptr; const float* noinit = nullptr; const int* norange = nullptr;
+        void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax, &norange};
         ISM_HIP(ctx, hipLaunchKernel(pk, dim3(grid / a.n_splits), dim3(512), pargs, plds, ctx->stream));      // one split: a workgroup per query tile
         ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16<pre>");
     }
     thr_init = thr0;
     float no_relax = 0.f;
-    void* rargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &stream_clock, &thr_init, &thr_out, &tile_step, &no_relax};
+    void* rargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &stream_clock, &thr_init, &thr_out, &tile_step, &no_relax, &a.qrange};
     ISM_HIP(ctx, hipLaunchKernel(kern, dim3(grid), dim3(threads), rargs, lds, ctx->stream));
     ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16");
     return ISMHIP_OK;
