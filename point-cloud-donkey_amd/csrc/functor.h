@@ -1,5 +1,5 @@
-// functor.h — the FLANN distance functors (utils/distance.cpp:33-52) evaluated by a whole wave, shared by the kNN re-rank /
-// exact scan (knn.hip, knn_threshold.hip, knn_large_k.hip) and the training-side sigma computation (train.hip). Included inside an anonymous namespace.
+// functor.h — the FLANN distance functors (utils/distance.cpp:33-52) evaluated by a whole wave, shared by the kNN re-rank, exact scans
+// and EMIT evaluation (the knn units, through knn_internal.h) and the training-side sigma computation (train.hip). Included inside an anonymous namespace.
 #pragma once
 #ifndef ISM_F32X4_DEFINED
 #define ISM_F32X4_DEFINED

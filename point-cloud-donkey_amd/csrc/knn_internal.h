@@ -1,8 +1,8 @@
 // knn_internal.h — what more than one unit of the codeword search needs (the map of the units is at the top of knn.hip; pca.hip
 // includes it for the f16 images): the types and device helpers in an anonymous namespace (they appear in kernel signatures, so
 // every unit has its own) -- candidate lists, THE definition of the scaled f16 images and their tiled layout, the error model of
-// the proofs, the steps the re-rank kernels share -- then the host functions through which the units call each other. Each of
-// those is defined in the unit that holds the kernels it launches.
+// the proofs, the slot proofs, the counter block of the queue -- then the host-side records of a search (request, plan, run, queue)
+// and, unit by unit, the host functions through which the units call each other, each defined in the unit whose kernels it launches.
 #pragma once
 #include "common.h"
 
@@ -13,6 +13,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "functor.h"         // wave_functor: re-rank, exact scans, EMIT evaluation
 
 #define KNN_BM 128       // codeword rows per tile
 #define KNN_BN 128       // queries per tile
@@ -178,6 +179,36 @@ __device__ __forceinline__ float pca_lb_of(const PcaLb& b, float s) {
 }
 __device__ __forceinline__ bool pca_slot_proven(float dk, float bnd, const PcaLb& b, float ku) { return dk < pca_lb_of(b, bnd) * (1.f - ku) - 1e-37f; }
 
+// fast chi-square of one row by a whole wave: every lane owns the 16-byte chunks lane, lane + 64, ... of the (zero padded) rows, all
+// of a row's loads are issued before the first is used (a dependent load per element made this 10 us per row), tree sum at the end.
+// Differs from the functor's sequential sum by at most ~2 ku relative. dim_pad <= 1344 (checked by the caller): <= 6 chunks per lane.
+#define CHI_FAST_CH 6
+__device__ __forceinline__ void chi2_fast_load_q(const float* __restrict__ qp, int n4, int lane, f32x4* qv) {
+#pragma unroll
+    for (int j = 0; j < CHI_FAST_CH; ++j) { const int g = lane + 64 * j; qv[j] = g < n4 ? *(const f32x4*)(qp + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f}; }
+}
+__device__ __forceinline__ float chi2_fast(const f32x4* qv, const float* __restrict__ wp, int n4, int lane) {
+    f32x4 wv[CHI_FAST_CH];
+#pragma unroll
+    for (int j = 0; j < CHI_FAST_CH; ++j) { const int g = lane + 64 * j; wv[j] = g < n4 ? *(const f32x4*)(wp + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f}; }
+    float part = 0.f;
+#pragma unroll
+    for (int j = 0; j < CHI_FAST_CH; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float sm = qv[j][e] + wv[j][e], df = qv[j][e] - wv[j][e]; part += sm > 0.f ? df * df / sm : 0.f; }
+    return wave_sum_f(part);
+}
+// ---- the queue of unproven work: filled by the re-rank kernels (knn_rerank.hip), emptied by the exact scan (knn_scan.hip) -----------
+#define KNN_MERGE_KEEP 16         // candidates k_knn_merge_splits keeps of all the splits of a query
+#define KNN_HELL_CPL 4            // candidates per lane of k_knn_rerank_hell (256 per query)
+// The 16-word counter block at the head of the queue scratch (flag_count of the kernels), zeroed before every search:
+enum KnnCounter {
+    KNN_CNT_QUERIES = 0, KNN_CNT_ITEMS = 1,   // the queue: unproven queries, their (query, slot) work items (ctx->knn_stats reads both)
+    KNN_CNT_QSC = 4,                          // f16 mode, three words: absmax bits of the query batch, -2 / (s_q s_c), 2^-14 / s_q (k_to_f16)
+    KNN_CNT_NEGATIVE = 12,                    // chi-square: some query element is negative (k_any_negative)
+    KNN_CNT_WORDS = 16
+};
+
 // the conditions under which the searches run on the matrix cores (shared by ismhip_knn and ismhip_knn_threshold): a launch big
 // enough to fill the chip, whole 16-byte chunks per descriptor, no A/B override of the candidate kernel
 bool knn_matrix_gate(const ismhip_ctx* ctx, const ismhip_codebook* cb, int nq) {
@@ -186,7 +217,66 @@ bool knn_matrix_gate(const ismhip_ctx* ctx, const ismhip_codebook* cb, int nq) {
 
 }  // namespace
 
-// ---- knn.hip ------------------------------------------------------------------------------------------------------------------------
+// ---- the host-side records of a search (they cross units: every type in them has a name with linkage) -------------------------------------
+// Slot -> rows layout of the exact scan, chosen by knn_plan and decoded by k_knn_fallback (its wr_rows). The two positive values ARE
+// the rows per wave-row block of the 32x32 MFMA tile (MI * 32): 64 on the 128-row tile, 128 on the 256-row tile.
+enum KnnFbLayout { KNN_FB_TILE128 = 64, KNN_FB_TILE256 = 128, KNN_FB_RING = -1, KNN_FB_ALL = -2, KNN_FB_RING_HALF = -3 };
+// How the slots of ONE search map to rows: its plan's tiles per split, tile count and tile rows, the slot -> rows layout (wr_rows: a
+// KnnFbLayout value) and, for a ranged search (qrange, below), the number of splits each query's own range was cut into.
+struct KnnSlotRows { int tiles_per_split, n_tiles, tile_rows, wr_rows, n_splits; };
+// A queue of unproven work that several searches may fill and ONE exact scan empties: counter block, a record per unproven query, an item
+// per failing slot, the scan's per-item results (layout: knn_scan.hip), the slot -> rows layout each search (chunk 0 / 1) leaves behind
+struct KnnQueue { uint32_t *count, *qrec, *items; unsigned long long* item_out; size_t q_items; KnnSlotRows desc[2]; };
+// stage1 != nullptr: FIRST stage of the two-stage search -- candidates + exact re-rank + proof only; the unproven queries are
+// left in the queue (*stage1: its counter block, records and items) for the caller instead of going to the exact scan; with them, how
+// the stage cut the codebook: item slot b belongs to split b / slots, and split s swept the rows [s, s + 1) * rows_per_split.
+struct KnnStage1 { KnnQueue queue; int n_splits, slots, rows_per_split; };
+// A RANGED search (KnnCandArgs::qrange below), chunk `chunk` of the run_knn_stage2_lists driver: the queries are the entries q_base ...
+// of the concatenated failure lists (live[i] == ~0u: padding between two lists), every group of 256 sweeps its own row range (shortest /
+// longest: rows_min / rows_max; all a request for the plan alone fills in), and what stays unproven goes to `queue`, not to a scan.
+// known_dk: per query, an exact value its k-th best row is known not to exceed (KnnQueueTag, knn_rerank.hip: the ranged search's proofs).
+struct KnnRanged { const int* qrange; const uint32_t* live; KnnQueue* queue; int q_base, chunk, rows_min, rows_max; const float* known_dk; };
+// what the caller of run_knn asks for beyond the search itself
+struct KnnRequest {
+    KnnStage1* stage1 = nullptr;
+    const char* tname = nullptr;       // timer of the candidate kernel
+    bool many_splits = false;          // few queries: as many codebook splits as fill the chip, folded into one slot (k_knn_merge_splits)
+    int use_pca = 0;                   // 1: stage-1 image, 2: stage-2 image (pca.hip)
+    const float* hell_q = nullptr;     // chi-square only: sqrt(q) rows of dim_pad floats -> Hellinger candidates (k_knn_rerank_hell)
+    bool half = false;                 // the 128 x 256 ring tile (k_knn_l2_ring16<T, 1>), as with ISMHIP_KNN_HALF=1
+    const float* seed_dk = nullptr;    // per query, an exact functor value its k-th best row is known not to exceed (NaN: none): the ring
+                                       // kernel starts from the thresholds k_knn_seed_thr derives from it
+    const KnnRanged* ranged = nullptr; // a ranged search; seed_dk only sets its start thresholds, ranged->known_dk enters its proofs
+    int q_ld = 0;                      // row stride of the queries when they are already padded (dim_pad); 0: dim
+};
+// How run_knn runs one search. knn_plan decides it from the request, the ctx switches and the codebook, without side effects.
+enum KnnCand { KNN_CAND_F32, KNN_CAND_CHI2, KNN_CAND_MFMA16, KNN_CAND_RING16 };
+struct KnnPlan {
+    bool hell;                  // Hellinger candidates: squared L2 on the sqrt images of the shadow codebook
+    int mode;                   // squared-L2 candidates: 0 f16, 1 bf16x3, 2 exact f32; -1 chi-square
+    KnnCand cand;
+    const void* kern;           // KNN_CAND_MFMA16 / KNN_CAND_RING16: the kernel instance (nullptr: not built)
+    int BM, BN, threads;        // codeword rows and queries per tile, threads per workgroup
+    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join, ranged;
+    int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
+    int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
+    int fb_tiles_per_split; KnnFbLayout fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout
+    size_t lds, lds_cap;        // dynamic LDS of this launch, and the largest any launch of the kernel uses
+};
+// One search in flight: what the phases of run_knn hand to each other, the carve-up of its scratch (knn_carve_scratch) included.
+struct KnnRun {
+    ismhip_ctx* ctx; const ismhip_codebook *cb, *xb; const PcaImage* PI; const KnnRequest* rq; KnnPlan p;
+    int metric, nq, k, T;
+    const float* qq; int ldq;            // the query rows as the kernels read them (padded to dim_pad when dim is not)
+    u16 *q_hi, *q_lo;                    // 16-bit query images (knn_query_images; nullptr: the candidate kernel reads the rows themselves)
+    float *cand_val, *cand_bound; int* cand_idx; int n_cand, n_bound;      // candidate lists and slot bounds (after a merge: the folded slot)
+    uint32_t *counters, *qsc;            // the search's own counter block (KnnCounter) and, in it, the f16 scalars of the query batch
+    KnnQueue queue;                      // the queue of unproven work: carved behind the counter block, or the request's shared queue
+};
+
+// ---- knn.hip: one search (T = candidates kept per lane slot, 1 .. 4), and the images of other searches' query batches ----------------------
+KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, int k, int T, const KnnRequest& rq);
+int run_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k, int T, int32_t* idx_out, float* dist_out, const KnnRequest& rq = KnnRequest());
 // sq[nq x dim_pad] = sqrt of the query rows (zero padded; 4 more bytes behind them hold the flag); negative = some element is
 // negative or NaN, read back: the call synchronises the stream
 int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, float* sq, bool& negative);
@@ -195,6 +285,23 @@ int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const f
 // the caller launches its tau kernel with knn_verify_params(xb, dim_pad, 0, sc, cn_acc), knn_mfma16_emit lists the rows.
 int knn_f16_emit_image(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_codebook* xb, const float* qv, int n, int ldv, int n_pad,
                        uint32_t* sc, u16* qimg);
+int ism_pca_rotate_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, const PcaImage* P, const float* q, int nq, int ldq, unsigned short* dst);   // pca.hip
+// ---- knn_rerank.hip (phases of run_knn) ----------------------------------------------------------------------------------------------------
+// thr0[nq] = the start thresholds of a seeded search (k_knn_seed_thr; needs the query image and, on the original image, its scalars)
+int knn_seed_thresholds(KnnRun& r, const float* out_scale, float* thr0);
+// folds many splits into one slot first (it becomes the run's candidate list: r.cand_*, r.n_cand, r.n_bound change), then: exact functor
+// values of the candidates that matter, the k best, and the proof; what it cannot prove is queued
+int knn_rerank_prove(KnnRun& r, int32_t* idx_out, float* dist_out);
+// ---- knn_scan.hip: the exact scan and THE layout of its queue --------------------------------------------------------------------------------
+// bytes of a queue for n_queries queries with q_items slots between them (results of up to k rows per item), and its carve-up
+size_t knn_queue_bytes(size_t n_queries, size_t q_items, int k);
+KnnQueue knn_queue_carve(void* mem, size_t n_queries, size_t q_items);
+// exact scan of the queued slots' rows into the unproven queries' results: one scan and one merge launch for a queue, whichever
+// searches filled it (q, idx_out, dist_out are indexed by the queue's query numbers)
+int knn_scan_queue(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int k, const float* q, int ldq, const KnnQueue& Q, const int* qrange, int32_t* idx_out, float* dist_out);
+// ---- knn_two_stage.hip: the two-stage drivers; chi-square: taken = false: not histogram data, the caller takes the VALU kernel ------------
+int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out);
+int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out, bool& taken);
 
 // ---- the 16-bit candidate kernels: knn_ring16.hip, knn_mfma16.hip ---------------------------------------------------------------------
 // what k_knn_l2_ring16 and k_knn_l2_mfma16 both take, under the names of their parameter lists (the ring has no wl / ql)
@@ -204,7 +311,7 @@ struct KnnCandArgs {
     float* cand_val; int* cand_idx; int cand_stride; float* cand_bound; int bound_stride;
     const int* qrange;      // ranged search (knn_range_split), else nullptr: every query sweeps the tiles [0, n_tiles_m)
 };
-// A RANGED search (stage 2 of the two-stage search on per-split failure lists, knn.hip): the queries come in groups of 256 and group
+// A RANGED search (stage 2 of the two-stage search on per-split failure lists, knn_two_stage.hip): the queries come in groups of 256 and group
 // g sweeps only the codeword rows [qrange[4 g], qrange[4 g + 1]) (multiples of 256); qrange[4 g + 2] = the list the group belongs to,
 // qrange[4 g + 3] = the first query of that list. The tiles of a range are dealt to the launch's splits evenly (never an empty split:
 // the host keeps n_splits <= the tiles of the shortest range), and rows stay GLOBAL rows: only the sweep is shorter.

@@ -25,7 +25,10 @@ Base kinds (HALF = 4096 rows = one stage-1 split when the codebook is cut in two
   six        six rows of one lane slot: stage 2's four candidates overflow too, and the slot goes to the exact scan
 plus, in the larger data set, one query scaled by 400: its largest rotated coordinate is at least |q| / sqrt(128) = 40, beyond the
 fixed f16 scale of the rotated images (2 |c|max = 2.5 at 2^13 .. 2^14, so 20 at most): no seed, unproven in every split. (The smaller
-data set goes without: its stage 2 runs on the original f16 image, whose scale follows the batch.)"""
+data set goes without: its stage 2 runs on the original f16 image, whose scale follows the batch.)
+
+A third data set holds c01 bases only: every query built to fail fails in BOTH halves, the lists are made, would save nothing and
+DECLINE, and the unsplit stage 2 follows them in the same call (test_lists_decline_and_the_unsplit_stage2_follows)."""
 import numpy as np
 import pytest
 
@@ -68,13 +71,13 @@ def single_row(b, half, j=0):
     return slot_row(b, half, 28 + j)
 
 
-def make(per_base, big):
+def make(per_base, big, kinds=KINDS):
     """words, queries, {kind: [(base, its queries, expected rows for k = 2)]}, number of queries built to fail (big: the scaled one too)"""
     rng = np.random.default_rng(2024)
     words = natural(rng, N_WORDS)
     q = np.zeros((NQ, DIM), np.float32)
     info, b, nfail, used = {}, 0, 0, set()
-    for kind, count in KINDS:
+    for kind, count in kinds:
         for _ in range(count):
             v = natural(rng, 1)[0]
             def cluster(half, n, first=1.0):
@@ -122,8 +125,9 @@ def make(per_base, big):
 
 @pytest.fixture(scope="module")
 def datasets():
-    """46 queries per base: 4876 built to fail, stage 2 takes the ring; 8 per base: 848, the merged-splits kernel"""
-    return {"many": make(46, True), "few": make(8, False)}
+    """46 queries per base: 4876 built to fail, stage 2 takes the ring; 8 per base: 848, the merged-splits kernel; both: 106 bases of
+    kind c01 only, 4876 queries that fail in both halves, no scaled query"""
+    return {"many": make(46, True), "few": make(8, False), "both": make(46, False, [("c01", 106)])}
 
 
 def test_forced_rows_share_a_lane_slot_and_a_half():
@@ -218,3 +222,28 @@ def test_split_lists_match_exact_route_and_unsplit_stage2(pkg, gpu, datasets, mo
             assert g["entries"] + 256 * n_lists < 4096                        # padded to whole query tiles, still the merged-splits kernel
     assert got["ranged"] == 2 and off["ranged"] == 0, (got["ranged"], off["ranged"])
     assert got["scans"] == 2, got["scans"]                                    # ONE exact-scan launch per call
+
+
+@pytest.mark.gpu
+def test_lists_decline_and_the_unsplit_stage2_follows(pkg, gpu, datasets, monkeypatch):
+    """Queries that failed in every split: the failure lists are built (entries > 0) but cover the whole sweep, so the saving rule
+    declines them (ranged == 0) and the call goes on with the unsplit gather and stage 2. With two equal splits the rule declines when
+    the padded entries x half the rows exceed 7/8 of n2 x all rows: entries * 4 >= 7 * n2 is the precondition (padding only adds)."""
+    _, dev = gpu
+    env = {"ISMHIP_KNN_SPLITS": "2", "ISMHIP_KNN_PCA_M2": "192"}
+    words, q, info, nfail = datasets["both"]
+    got = search(pkg, dev, monkeypatch, "both", words, q, dict(env, ISMHIP_KNN_STAGE2_SPLITS="1"))
+    off = search(pkg, dev, monkeypatch, "both", words, q, dict(env, ISMHIP_KNN_STAGE2_SPLITS="0"))
+    exact = search(pkg, dev, monkeypatch, "both", words, q, {"ISMHIP_KNN_MODE": "f32"})
+    for k in (1, 2):
+        g, o, e = got[k], off[k], exact[k]
+        print(f"both k={k}: stage-2 queries {g['n2']} (unsplit {o['n2']}), list entries {g['entries']}, exact-scan items {g['items']} (unsplit {o['items']})")
+        assert g["entries"] * 4 >= 7 * g["n2"], (g["entries"], g["n2"])       # the data set's precondition: the lists must decline
+        assert g["entries"] > 0 and o["entries"] == 0                         # ... after they were built
+        assert nfail <= g["n2"] == o["n2"], (g["n2"], o["n2"], nfail)
+        assert np.array_equal(g["idx"], e["idx"]), f"rows differ from the f32 route in {int((g['idx'] != e['idx']).any(1).sum())} queries"
+        assert np.array_equal(g["dist"].view(np.uint32), e["dist"].view(np.uint32))
+        assert np.array_equal(g["idx"], o["idx"]) and np.array_equal(g["dist"].view(np.uint32), o["dist"].view(np.uint32))
+        for b, qs, exp in info["c01"]:
+            assert (g["idx"][qs] == np.asarray(exp[:k])).all(), (b, g["idx"][qs[0]], exp)
+    assert got["ranged"] == 0 and off["ranged"] == 0, (got["ranged"], off["ranged"])
