@@ -92,7 +92,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -334,6 +334,30 @@ int  ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_reg
 int  ismhip_voxel_keypoints(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h,
                             const float* x, const float* y, const float* z, const uint32_t* rgba, float leaf,
                             uint32_t capacity, float* kx, float* ky, float* kz, uint32_t* krgba,
+                            uint32_t* kp_offsets_h_out);
+
+/* ---- ISS3D keypoints: KeypointsISS3D::iComputeKeypoints (keypoints/keypoints_iss3d.cpp:31-72) -> pcl::ISSKeypoint3D without border
+ *      estimation. PCL is external; the arithmetic is this library's definition, restated from PCL 1.10 iss_3d.hpp (DESIGN.md section
+ *      4.14). Per object, on the finite points of the cloud; every neighbourhood by the rule of ismhip_filter_radius (unfused float d2,
+ *      STRICTLY below (float)((double)r * r), the query included). Results do not depend on the cell_size the cloud was created with,
+ *      and are the same bits from run to run.
+ * ismhip_iss3d_saliency (keypoints_iss3d.cpp:31-72): per point the scatter matrix C = sum d d^T, d = (double)p_j - (double)p_i over the
+ * salient_radius ball (about the query, not divided by the count; all zero with fewer than min_neighbors neighbours), its eigenvalues
+ * e1 >= e2 >= e3, and saliency = e3 when all three are finite, e3 >= 0, e2 / e1 < gamma21 and e3 / e2 < gamma32 (double compares, 0 / 0
+ * fails), else 0. saliency_out: device double[n_pts] in original point order; eig_out: device double[n_pts * 3] (e1, e2, e3) or NULL;
+ * count_out: device uint32[n_pts] neighbour counts or NULL. Non-finite points: all 0. Radii or gammas not > 0, min_neighbors < 0:
+ * ISMHIP_ERR_INVALID. Timer "iss3d_saliency". Asynchronous. */
+int  ismhip_iss3d_saliency(ismhip_ctx* ctx, const ismhip_cloud* cloud, float salient_radius, double gamma21, double gamma32, int min_neighbors,
+                           double* saliency_out, double* eig_out, uint32_t* count_out);
+/* ismhip_iss3d_keypoints (keypoints_iss3d.cpp:31-72): the saliency pass, then non-maximum suppression: a point with saliency > 0 is a
+ * keypoint iff its non_max_radius ball holds at least min_neighbors points and none with a strictly larger saliency (equal ones both
+ * survive). The keypoints are those points themselves, in ascending original index, packed object after object into kx|ky|kz (device,
+ * `capacity` entries; the number of points always suffices), krgba (or NULL; the points' colours, 0 for a cloud without) and
+ * src_index_out (or NULL; the point's index inside its object); kp_offsets_h_out[n_obj+1] (host) receives the per-object ranges. Empty
+ * clouds and objects give empty ranges. Errors as ismhip_iss3d_saliency; capacity too small: ISMHIP_ERR_INVALID, as in
+ * ismhip_voxel_keypoints. Timers "iss3d_saliency", "iss3d_nms". The call synchronises. */
+int  ismhip_iss3d_keypoints(ismhip_ctx* ctx, const ismhip_cloud* cloud, float salient_radius, float non_max_radius, double gamma21, double gamma32,
+                            int min_neighbors, uint32_t capacity, float* kx, float* ky, float* kz, uint32_t* krgba, uint32_t* src_index_out,
                             uint32_t* kp_offsets_h_out);
 
 /* ---- feature filtering: Features::operator() drops non-finite LRFs (features.cpp:66-76),

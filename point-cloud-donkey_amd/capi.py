@@ -34,6 +34,7 @@ EXPORTS = [
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352",
+    "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -567,6 +568,37 @@ def voxel_keypoints(ctx, pt_offsets, x, y, z, leaf, rgba=None):
                                            _p(kx), _p(ky), _p(kz), _p(kc), _p(ko)), "ismhip_voxel_keypoints")
     m = int(ko[-1])
     return ko, kx[:m], ky[:m], kz[:m], (kc[:m] if kc is not None else None)
+
+
+def iss3d_saliency(ctx, cloud, salient_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, want_eig=True, want_counts=True):
+    """ismhip_iss3d_saliency: returns (saliency float64[n_pts], eig float64[n_pts, 3] (e1 >= e2 >= e3) or None, counts int32[n_pts] or None)
+    in the cloud's original point order"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    sal = torch.zeros((n,), dtype=torch.float64, device=dev)
+    eig = torch.zeros((n, 3), dtype=torch.float64, device=dev) if want_eig else None
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_iss3d_saliency(ctx._h, cloud._h, C.c_float(salient_radius), C.c_double(gamma21), C.c_double(gamma32), C.c_int(min_neighbors),
+                                          _p(sal), _p(eig), _p(cnt)), "ismhip_iss3d_saliency")
+    return sal, eig, cnt
+
+
+def iss3d_keypoints(ctx, cloud, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, capacity=None):
+    """KeypointsISS3D on the device: returns (kp_offsets[n_obj+1] numpy, kx, ky, kz, krgba or None, src int32: the point's index inside its
+    object) packed object after object. capacity: entries of the output arrays (default: the number of points, which always suffices)"""
+    torch = _torch()
+    x, rgba = cloud._keep[0], cloud._keep[6]
+    n = int(cloud.pt_offsets[-1])
+    cap = n if capacity is None else int(capacity)
+    kx = torch.empty((max(cap, 1),), dtype=torch.float32, device=x.device); ky = torch.empty_like(kx); kz = torch.empty_like(kx)
+    kc = torch.empty((max(cap, 1),), dtype=torch.int32, device=x.device) if rgba is not None else None
+    src = torch.empty((max(cap, 1),), dtype=torch.int32, device=x.device)
+    ko = np.zeros(cloud.n_obj + 1, dtype=np.uint32)
+    ctx.check(lib().ismhip_iss3d_keypoints(ctx._h, cloud._h, C.c_float(salient_radius), C.c_float(non_max_radius), C.c_double(gamma21), C.c_double(gamma32),
+                                           C.c_int(min_neighbors), C.c_uint32(cap), _p(kx), _p(ky), _p(kz), _p(kc), _p(src), _p(ko)), "ismhip_iss3d_keypoints")
+    m = int(ko[-1])
+    return ko, kx[:m], ky[:m], kz[:m], (kc[:m] if kc is not None else None), src[:m]
 
 
 def _compact_feature_rows(ctx, symbol, report_all_kept, kp_offsets, desc, lrf, kpx, kpy, kpz):

@@ -183,13 +183,14 @@ struct ismhip_ctx {
     uint32_t knn_lk_stats[3] = {0, 0, 0};   // last ismhip_knn_large_k: queries {certified by the fast path, retried, answered by the exact scan}
     uint32_t knn_binary_launches = 0; // ismhip_knn_binary calls that searched (counter "knn_binary_launches"; tests of the host route)
     uint32_t rank_launches = 0;       // ismhip_rank_scores / ismhip_rank_select calls that reached the device (counter "rank_launches"; tests of the host route)
+    bool iss3d_wave = false;          // env ISMHIP_ISS3D_MAP=wave: the ISS3D saliency sweep with one wave per query (k_pca_normals' mapping) instead of one thread per query (A/B runs, tests; same bits: the scatter sums are order free, iss3d.hip)
     int knn_mode = 0;            // env ISMHIP_KNN_MODE = f16 (0, default) | bf16x3 (1) | f32 (2): squared-L2 candidate kernel (A/B runs, tests)
 };
 
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE, SCR_ISS3D
 };
 
 int  ism_set_err(ismhip_ctx* ctx, int code, const std::string& msg);
@@ -212,6 +213,12 @@ int ism_offsets_from_counts(ismhip_ctx* ctx, int n, const uint32_t* cnt_d, uint3
 // the cell-order permutation of a keypoint set on a cloud, or nullptr (see grid.hip)
 const uint32_t* ism_kp_order(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const uint32_t* ko,
                              const float* kpx, const float* kpy, const float* kpz, uint32_t maxk);
+
+// ISS3D's last step (compact.hip): the points of `cloud` whose mask entry (device, original order) is set, with their colours and their
+// index inside the object, in ascending index, object after object; kp_offsets_h_out[n_obj + 1] receives the ranges. More than
+// `capacity` of them: ISMHIP_ERR_INVALID, nothing written. Synchronises.
+int ism_compact_keypoints(ismhip_ctx* ctx, const std::string& who, const ismhip_cloud* cloud, const uint8_t* mask, uint32_t capacity,
+                          float* kx, float* ky, float* kz, uint32_t* krgba, uint32_t* src_index_out, uint32_t* kp_offsets_h_out);
 
 #define ISM_HIP(ctx, call)                                                                          \
     do {                                                                                            \
@@ -565,6 +572,22 @@ __device__ __forceinline__ bool row_cells(const GridMeta& m, const CellRange& cr
     lo = l < cr.lo[0] ? cr.lo[0] : l;
     hi = h > cr.hi[0] ? cr.hi[0] : h;
     return lo <= hi;
+}
+
+// One THREAD per query: the rows of cells that the ball (q, r) touches, one after the other, each clipped to its chord. f(b, e) takes
+// the row's span [b, e) of object-local sorted point indices and returns false to end the sweep early (k_ror_count of prefilter.hip,
+// the ISS3D sweeps of iss3d.hip: the queries are the cloud's own points in cell order, so the lanes of a wave read the same runs).
+template <class F>
+__device__ __forceinline__ void ball_rows_for_each(const GridMeta& m, const uint32_t* __restrict__ cs, float qx, float qy, float qz, float r, F&& f) {
+    CellRange cr;
+    if (!ball_cells(m, qx, qy, qz, r, cr)) return;
+    for (int gz = cr.lo[2]; gz <= cr.hi[2]; ++gz)
+        for (int gy = cr.lo[1]; gy <= cr.hi[1]; ++gy) {
+            int xl, xh;
+            if (!row_cells(m, cr, gy, gz, qx, qy, qz, r, xl, xh)) continue;
+            const int rb = (gz * m.dim[1] + gy) * m.dim[0];
+            if (!f(cs[rb + xl], cs[rb + xh + 1])) return;
+        }
 }
 
 // ---- flattened ball traversal ---------------------------------------------------------------------------------------------

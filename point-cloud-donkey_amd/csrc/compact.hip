@@ -211,6 +211,44 @@ extern "C" int ismhip_compact_points(ismhip_ctx* ctx, int n_obj, const uint32_t*
     return compact_points(ctx, n_obj, pt_offsets_h, in, keep, out, pt_offsets_h_out, "compact_points");
 }
 
+// ---- keypoints that are points of the cloud (iss3d.hip): the same flag / per-object scan / gather over x, y, z, the colour and the
+//      point's index inside its object
+namespace {
+__global__ __launch_bounds__(256) void k_gather_keypoints(const uint32_t* __restrict__ off, const uint32_t* __restrict__ new_off, const uint32_t* __restrict__ keep,
+                                                          const uint32_t* __restrict__ pos, const float* __restrict__ x, const float* __restrict__ y,
+                                                          const float* __restrict__ z, const uint32_t* __restrict__ rgba, float* __restrict__ kx,
+                                                          float* __restrict__ ky, float* __restrict__ kz, uint32_t* __restrict__ krgba, uint32_t* __restrict__ src) {
+    const int o = blockIdx.y;
+    const uint32_t i = off[o] + blockIdx.x * 256 + threadIdx.x;
+    if (i >= off[o + 1] || !keep[i]) return;
+    const uint32_t d = new_off[o] + pos[i];
+    kx[d] = x[i]; ky[d] = y[i]; kz[d] = z[i];
+    if (krgba) krgba[d] = rgba ? rgba[i] : 0u;
+    if (src) src[d] = i - off[o];
+}
+}  // namespace
+
+int ism_compact_keypoints(ismhip_ctx* ctx, const std::string& who, const ismhip_cloud* cloud, const uint8_t* mask, uint32_t capacity,
+                          float* kx, float* ky, float* kz, uint32_t* krgba, uint32_t* src_index_out, uint32_t* kp_offsets_h_out) {
+    const int n_obj = cloud->n_obj;
+    bool fits = true;
+    const int rc = compact_rows(ctx, who, n_obj, cloud->pt_off_h.data(), kp_offsets_h_out, nullptr, nullptr,
+        [&](uint32_t n, uint32_t* keep) {
+            hipLaunchKernelGGL(k_keep_mask, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, mask, keep);
+            return "k_keep_mask";
+        },
+        [&](const Compaction& c) {
+            fits = kp_offsets_h_out[n_obj] <= capacity;          // the offsets are known before anything is written
+            if (fits && kp_offsets_h_out[n_obj] > 0)
+                hipLaunchKernelGGL(k_gather_keypoints, dim3((c.max_run + 255) / 256, n_obj), dim3(256), 0, ctx->stream, c.off, c.new_off, c.keep, c.pos,
+                                   cloud->x, cloud->y, cloud->z, cloud->rgba, kx, ky, kz, krgba, src_index_out);
+            return "k_gather_keypoints";
+        });
+    if (rc != ISMHIP_OK) return rc;
+    if (!fits) return ism_set_err(ctx, ISMHIP_ERR_INVALID, who + ": output capacity too small (n_points always suffices)");
+    return ISMHIP_OK;
+}
+
 // ---- partial descriptors: Codebook::castVotes with UsePartialShot (codebook/codebook.cpp:416-475) keeps the histograms of a subset
 //      of the 32 SHOT signatures (getSignatureMask, :952-1036); on the device that is a column gather of the descriptor matrix.
 namespace {

@@ -237,7 +237,7 @@ __global__ __launch_bounds__(256) void k_sor_threshold(const uint32_t* __restric
 }
 
 // count of the object's finite points with d2 < r2 (the query included), one thread per query in cell-sorted order. The rows of
-// cells the ball touches and the chord of every row come from ball_cells / row_cells, as for the descriptors.
+// cells the ball touches and the chord of every row come from ball_cells / row_cells, as for the descriptors (ball_rows_for_each).
 template <bool FULL>
 __global__ __launch_bounds__(256) void k_ror_count(SorView cv, float radius, float r2, int min_nb,
                                                    uint8_t* __restrict__ keep, uint32_t* __restrict__ count_out) {
@@ -250,20 +250,14 @@ __global__ __launch_bounds__(256) void k_ror_count(SorView cv, float radius, flo
     const uint32_t* cs = cv.cell_start + (size_t)o * ISM_GRID_STRIDE;
     const float4 q = cv.sp4[base + t];
     int cnt = 0;
-    CellRange cr;
-    if (ball_cells(m, q.x, q.y, q.z, radius, cr)) {
-        for (int gz = cr.lo[2]; gz <= cr.hi[2] && (FULL || cnt <= min_nb); ++gz)
-            for (int gy = cr.lo[1]; gy <= cr.hi[1] && (FULL || cnt <= min_nb); ++gy) {
-                int xl, xh;
-                if (!row_cells(m, cr, gy, gz, q.x, q.y, q.z, radius, xl, xh)) continue;
-                const int rb = (gz * m.dim[1] + gy) * m.dim[0];
-                const uint32_t e = cs[rb + xh + 1];
-                for (uint32_t i = cs[rb + xl]; i < e; ++i) {
-                    const float4 p = cv.sp4[base + i];
-                    cnt += sqdist3(p.x, p.y, p.z, q.x, q.y, q.z) < r2 ? 1 : 0;
-                }
+    if (FULL || cnt <= min_nb)            // a negative min_nb keeps the point without a sweep
+        ball_rows_for_each(m, cs, q.x, q.y, q.z, radius, [&](uint32_t b, uint32_t e) {
+            for (uint32_t i = b; i < e; ++i) {
+                const float4 p = cv.sp4[base + i];
+                cnt += sqdist3(p.x, p.y, p.z, q.x, q.y, q.z) < r2 ? 1 : 0;
             }
-    }
+            return FULL || cnt <= min_nb;
+        });
     const uint32_t me = base + __float_as_uint(q.w);
     keep[me] = cnt > min_nb ? 1 : 0;
     if (FULL) count_out[me] = (uint32_t)cnt;

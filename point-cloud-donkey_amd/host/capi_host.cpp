@@ -129,6 +129,14 @@ int ism3d_last_votes(void* m, uint32_t* slot_off, float* pos, float* weight, int
 }
 // diagnostics (tests): a timer (ms) or counter of the model's device context by its ismhip_timer_get name, e.g. "ransac_clusters"
 int ism3d_device_timer(void* m, const char* name, double* out) { GUARD(*out = ((ImplicitShapeModel*)m)->deviceTimer(name); return 0;) }
+// diagnostics (tests): an entry of getProcessingTimes() in ms ("keypoints", "features", ...); -2 when the model has not reported that key
+int ism3d_processing_time(void* m, const char* key, double* out) {
+    const auto& t = ((ImplicitShapeModel*)m)->getProcessingTimes();
+    const auto it = t.find(key);
+    if (it == t.end()) return -2;
+    *out = it->second;
+    return 0;
+}
 // label maps and the per-class size hints (Voting::forwardBoxesAndRadii) that travel with the model
 int ism3d_set_labels(void* m, int n_classes, const char* const* class_labels, int n_inst, const char* const* inst_labels, const unsigned* inst_to_class) {
     GUARD(((ImplicitShapeModel*)m)->setLabels(std::vector<std::string>(class_labels, class_labels + n_classes), std::vector<std::string>(inst_labels, inst_labels + n_inst),

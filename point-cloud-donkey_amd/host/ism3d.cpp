@@ -152,8 +152,8 @@ public:
         if (with_color) h2d(pts.rgba, hrgba);
     }
     // uploads the batch and builds the search surface
-    // kps == nullptr: voxel-grid keypoints are computed on the device (ismhip_voxel_keypoints) with leaf `device_leaf`
-    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps, float cell, bool with_color, float device_leaf = 0.f) {
+    // kps == nullptr: the keypoints are computed on the device by `detector` (finishBatch)
+    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps, float cell, bool with_color, const Keypoints* detector = nullptr) {
         uploadPoints(clouds, with_color, false);
         if (kps) {
             kp_off.assign(1, 0);
@@ -166,22 +166,31 @@ public:
             h2d(kx, hkx); h2d(ky, hky); h2d(kz, hkz);
             if (with_color) h2d(krgba, hkrgba);
         }
-        finishBatch(kps == nullptr, cell, device_leaf);
+        finishBatch(kps ? nullptr : detector, cell);
     }
-    // the point arrays of the batch are in HBM (pts, pt_off): keypoints (device voxel grid when dev_kp) and the search surface
-    void finishBatch(bool dev_kp, float cell, float device_leaf) {
+    // the point arrays of the batch are in HBM (pts, pt_off): the keypoints of a device detector (nullptr: they have been uploaded) and
+    // the search surface. A voxel grid needs no surface and keeps its place in front of it; ISS3D sweeps the surface, so it comes after.
+    void finishBatch(const Keypoints* detector, float cell) {
         const ismhip_point_arrays p = pts.view(has_color);
         dropCloud();
-        if (dev_kp) {
-            // KeypointsVoxelGrid::iComputeKeypoints on the device: centroids stay in HBM, only the per-object counts come back
-            const size_t n_pts = pt_off.back();
+        const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(detector);
+        const auto* iss = dynamic_cast<const KeypointsISS3D*>(detector);
+        if (detector && !vg && !iss) throw RuntimeException("keypoint type \"" + detector->getType() + "\" has no device route");
+        const size_t n_pts = pt_off.back();
+        if (detector) {
+            // the keypoints stay in HBM, only the per-object counts come back
             kx.reserve(std::max<size_t>(n_pts, 1) * 4); ky.reserve(std::max<size_t>(n_pts, 1) * 4); kz.reserve(std::max<size_t>(n_pts, 1) * 4);
             if (has_color) krgba.reserve(std::max<size_t>(n_pts, 1) * 4);
             kp_off.assign((size_t)n_obj + 1, 0);
-            check(ismhip_voxel_keypoints(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.rgba, device_leaf, (uint32_t)n_pts, kx.as<float>(), ky.as<float>(),
-                                         kz.as<float>(), has_color ? krgba.as<uint32_t>() : nullptr, kp_off.data()), "ismhip_voxel_keypoints");
         }
+        if (vg)       // KeypointsVoxelGrid::iComputeKeypoints on the device
+            check(ismhip_voxel_keypoints(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.rgba, vg->getLeafSize(), (uint32_t)n_pts, kx.as<float>(), ky.as<float>(),
+                                         kz.as<float>(), has_color ? krgba.as<uint32_t>() : nullptr, kp_off.data()), "ismhip_voxel_keypoints");
         check(ismhip_cloud_create(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.nx, p.ny, p.nz, p.rgba, cell, &cloud), "ismhip_cloud_create");
+        if (iss)      // KeypointsISS3D::iComputeKeypoints on the device: points of the cloud the descriptors will see
+            check(ismhip_iss3d_keypoints(ctx, cloud, (float)iss->getSalientRadius(), (float)iss->getNonMaxRadius(), iss->getGamma21(), iss->getGamma32(),
+                                         iss->getMinNeighbors(), (uint32_t)n_pts, kx.as<float>(), ky.as<float>(), kz.as<float>(),
+                                         has_color ? krgba.as<uint32_t>() : nullptr, nullptr, kp_off.data()), "ismhip_iss3d_keypoints");
     }
     // one compaction of the batch's points: reserves the spare arrays, runs `call` (which writes them and the new offsets), makes them
     // the current ones and replaces pt_off
@@ -307,6 +316,26 @@ KeypointSet KeypointsVoxelGrid::iComputeKeypoints(const PointCloud& c) const {
         i = j;
     }
     return out;
+}
+
+// Keypoints: pcl::ISSKeypoint3D (keypoints/keypoints_iss3d.cpp:17-72). The detector itself is ismhip_iss3d_keypoints on the batch's search
+// surface (DeviceSession::finishBatch); this class holds the configuration.
+KeypointsISS3D::KeypointsISS3D() {
+    addParameter(m_salientRadius, "SalientRadius", 0.1);
+    addParameter(m_nonMaxRadius, "NonMaxRadius", 0.05);
+    addParameter(m_gamma21, "Gamma21", 0.975);
+    addParameter(m_gamma32, "Gamma32", 0.975);
+    addParameter(m_minNeighbors, "MinNeighbors", 5);
+}
+void KeypointsISS3D::iPostInitConfig() {
+    const std::pair<const char*, double> positive[] = {{"invalid ISS3D SalientRadius", m_salientRadius}, {"invalid ISS3D NonMaxRadius", m_nonMaxRadius},
+                                                      {"invalid ISS3D Gamma21", m_gamma21}, {"invalid ISS3D Gamma32", m_gamma32}};
+    for (const auto& p : positive)
+        if (!(p.second > 0.0) || !std::isfinite(p.second) || !((float)p.second > 0.f)) throw BadParamExceptionType<double>(p.first, p.second);
+    if (m_minNeighbors < 0) throw BadParamExceptionType<int>("invalid ISS3D MinNeighbors", m_minNeighbors);
+}
+KeypointSet KeypointsISS3D::iComputeKeypoints(const PointCloud&) const {
+    throw RuntimeException("KeypointsISS3D has no host implementation: the detector runs on the device with the batch (ismhip_iss3d_keypoints)");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1464,7 +1493,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
-    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid)");
+    if (type == KeypointsISS3D::getTypeStatic()) return new KeypointsISS3D();
+    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid, ISS3D)");
 }
 template <> ActivationStrategy* Factory<ActivationStrategy>::createByType(const std::string& type) {
     if (type == ActivationStrategyKNN::getTypeStatic()) return new ActivationStrategyKNN();
@@ -1879,10 +1909,18 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
     std::vector<std::unique_ptr<PointCloud>> completed;
     const float cell = descriptorSearchCell(*m_feature_descriptor);
     // VoxelGrid keypoints are taken on the device with the batch (ismhip_voxel_keypoints); any other detector, or
-    // ISM3D_HOST_KEYPOINTS=1, runs the host implementation per object and uploads its result
+    // ISM3D_HOST_KEYPOINTS=1, runs the host implementation per object and uploads its result. ISS3D keypoints
+    // (ismhip_iss3d_keypoints) are taken on the batch's search surface and have no host implementation: the switch does not apply.
     const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(m_keypoints_detector.get());
+    const auto* iss = dynamic_cast<const KeypointsISS3D*>(m_keypoints_detector.get());
     const char* host_kp = getenv("ISM3D_HOST_KEYPOINTS");
-    const bool dev_kp = vg && !(host_kp && host_kp[0] == '1');
+    const bool dev_kp = iss || (vg && !(host_kp && host_kp[0] == '1'));
+    if (iss)
+        for (const PointCloud* c : clouds)
+            if (c->organized) {   // keypoints_iss3d.cpp:45-48 hands PCL the unfiltered organised cloud
+                LOG_WARN("organized input cloud: the reference runs ISS3D on the unfiltered depth image; here the cloud is treated as an unorganized one");
+                break;
+            }
     auto describe = [&]() {
         auto f = (*m_feature_descriptor)(s);
         s.sync();
@@ -1924,7 +1962,7 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
                 return ismhip_filter_normals(s.ctx, s.n_obj, s.pt_off.data(), in, out, new_off);
             });
             timer.lap("normals");
-            s.finishBatch(true, cell, vg->getLeafSize());
+            s.finishBatch(m_keypoints_detector.get(), cell);
             timer.lap("keypoints");
             return describe();
         }
@@ -1948,7 +1986,7 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
         }
     }
     if (dev_kp) {
-        s.uploadBatch(clouds, nullptr, cell, m_feature_descriptor->needsColor(), vg->getLeafSize());
+        s.uploadBatch(clouds, nullptr, cell, m_feature_descriptor->needsColor(), m_keypoints_detector.get());
         timer.lap("keypoints");
     } else {
         std::vector<KeypointSet> kps;

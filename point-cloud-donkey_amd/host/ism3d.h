@@ -214,6 +214,29 @@ protected:
 private:
     float m_leafSize;
 };
+// keypoints/keypoints_iss3d.cpp:17-72 -> pcl::ISSKeypoint3D without border estimation (ismhip_iss3d_keypoints):
+// the reference's parameter names and defaults. Non-positive radii or gammas and a negative MinNeighbors are refused when the
+// configuration is read. There is NO host implementation: the detector runs on the batch's search surface on the device
+// (ImplicitShapeModel::computeFeatures), iComputeKeypoints(const PointCloud&) throws by name, and ISM3D_HOST_KEYPOINTS=1 -- the switch
+// that sends VoxelGrid to its host implementation -- does not apply to ISS3D. Organised clouds are treated as unorganised ones (the
+// reference hands PCL the unfiltered cloud there); computeFeatures warns.
+class KeypointsISS3D : public Keypoints {
+public:
+    KeypointsISS3D();
+    static std::string getTypeStatic() { return "ISS3D"; }
+    std::string getType() const override { return getTypeStatic(); }
+    double getSalientRadius() const { return m_salientRadius; }
+    double getNonMaxRadius() const { return m_nonMaxRadius; }
+    double getGamma21() const { return m_gamma21; }
+    double getGamma32() const { return m_gamma32; }
+    int getMinNeighbors() const { return m_minNeighbors; }
+protected:
+    KeypointSet iComputeKeypoints(const PointCloud& points) const override;
+    void iPostInitConfig() override;
+private:
+    double m_salientRadius, m_nonMaxRadius, m_gamma21, m_gamma32;
+    int m_minNeighbors;
+};
 
 // ---- Features (features/features.h) -------------------------------------------------------------------
 class Features : public JSONObject {
