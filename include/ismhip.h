@@ -72,6 +72,8 @@ extern "C" {
 #define ISMHIP_COSPAIR_LEVELS 7     /* concentric shells of ismhip_cospair */
 #define ISMHIP_COSPAIR_BINS   9     /* bins per pair feature and per colour channel */
 #define ISMHIP_COSPAIR_DIM  378     /* 7 levels x (27 geometry + 27 colour) */
+#define ISMHIP_SPIN_IMAGE_WIDTH 8   /* setImageWidth(8), features_spin_image.cpp:67 */
+#define ISMHIP_SPIN_IMAGE_DIM 153   /* (8 + 1) * (2 * 8 + 1) */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -92,7 +94,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -283,6 +285,37 @@ int  ismhip_short_cshot(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32
 int  ismhip_cospair(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                     const float* kpx, const float* kpy, const float* kpz, float radius, float* desc_out,
                     uint32_t* neighbour_count_out, uint32_t* level_count_out, uint32_t* snap_index_out);
+/* The normal lookup of FeaturesSpinImage::iComputeDescriptors (features/features_spin_image.cpp:36-53): for every keypoint the installed
+ * normal of the LOWEST original index among the object's finite points whose three coordinates compare == to the keypoint's -> knx_out,
+ * kny_out, knz_out [nkp]; src_index_out[nkp] (may be NULL): that object-local index, -1 when nothing matches. No match (and a keypoint that
+ * is not finite) gives the normal (0, 0, 0), the reference's default-constructed pcl::Normal. A matched point's normal is handed over as
+ * it is, finite or not (the host filters such points before this step). Only the keypoint's own grid cell is read. Refused with
+ * ISMHIP_ERR_INVALID: a missing array ("keypoint_normals: bad argument"). Timer "keypoint_normals". */
+int  ismhip_keypoint_normals(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                             const float* kpx, const float* kpy, const float* kpz,
+                             float* knx_out, float* kny_out, float* knz_out, int32_t* src_index_out);
+/* FeaturesSpinImage::iComputeDescriptors (features/features_spin_image.cpp:28-87) -> PCL 1.10 SpinImageEstimation::computeSiForPoint as
+ * :61-69 configure it: rectangular image, support-angle cosine 0 (neighbour normals are never read), min_pts_neighb 0; the reference's
+ * image_width is 8 (ISMHIP_SPIN_IMAGE_WIDTH, 153 floats). desc_out[nkp * (w + 1)(2w + 1)], w = image_width: element ia * (2w + 1) + ib is
+ * entry (ia, ib) of the image. Per keypoint with centre c and axis n = (ax, ay, az)[k] (every float product and sum unfused, as written):
+ *  - neighbours: the finite cloud points with d2 < (float)((double)radius * radius), d = p - c, d2 = (d.x*d.x + d.y*d.y) + d.z*d.z in float;
+ *    neighbour_count_out[nkp] (may be NULL) counts them all, the skipped ones too;
+ *  - norm = sqrtf(d2); (double)norm < 10 * DBL_EPSILON: skipped; dot = (d.x*n.x + d.y*n.y) + d.z*n.z in float; from here in double:
+ *    cos = dot / norm; |cos| > 1 + 10 * FLT_EPSILON (or cos no number): the keypoint's WHOLE row is NaN (PCL throws); else cos clamped to [-1, 1],
+ *    beta = norm * cos, alpha = norm * sqrt(1 - cos * cos), bin = (double)radius / w / sqrt(2.0), lim = bin * w; |beta| >= lim or
+ *    alpha >= lim: skipped; ib = (int)floor(beta / bin) + w, ia = (int)floor(alpha / bin), a = alpha / bin - ia, b = beta / bin - (ib - w);
+ *    deposits (1-a)(1-b), a(1-b), (1-a)b, ab at (ia, ib), (ia+1, ib), (ia, ib+1), (ia+1, ib+1); an entry outside the matrix (reached only
+ *    when a quotient rounds up onto w, with a weight of rounding size) is dropped;
+ *  - every deposit enters a 64-bit integer bin as round(v * 2^28); S = the integer sum of the bins. More than one neighbour:
+ *    row[i] = (float)((double)h_i / (double)S), S == 0 giving the reference's NaN row; otherwise row[i] = (float)(h_i * 2^-28).
+ * A ball that holds no point gives a ZERO row and count 0. A keypoint or an axis that is not finite gives a row that is NaN AS A WHOLE
+ * and count 0. An axis of (0, 0, 0) -- what ismhip_keypoint_normals returns for a keypoint that is no cloud point -- is used as it is:
+ * every cosine is 0 and only column w fills. Two calls give the same bits. Refused: a missing array, a radius that is not positive,
+ * image_width < 1 (ISMHIP_ERR_INVALID, "spin_image: bad argument"); image_width > 25, whose rows ismhip_knn would not take
+ * (ISMHIP_ERR_UNSUPPORTED). Timer "spin_image". */
+int  ismhip_spin_image(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                       const float* kpx, const float* kpy, const float* kpz, const float* ax, const float* ay, const float* az,
+                       float radius, int image_width, float* desc_out, uint32_t* neighbour_count_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
@@ -371,7 +404,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

@@ -34,7 +34,7 @@ EXPORTS = [
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352",
-    "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints",
+    "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -382,6 +382,36 @@ def cospair(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, want_counts=False, wa
               "ismhip_cospair")
     extra = [t for t in (cnt, lev, snap) if t is not None]
     return (out, *extra) if extra else out
+
+
+SPIN_IMAGE_WIDTH = 8                                                   # setImageWidth(8), features_spin_image.cpp:67
+SPIN_IMAGE_DIM = (SPIN_IMAGE_WIDTH + 1) * (2 * SPIN_IMAGE_WIDTH + 1)   # 153
+
+
+def keypoint_normals(ctx, cloud, kp_offsets, kpx, kpy, kpz, want_index=False):
+    """ismhip_keypoint_normals -> (nx, ny, nz) [nkp] each: the installed normal of the lowest-index cloud point whose coordinates equal the
+    keypoint's, (0, 0, 0) when there is none; with want_index also that object-local index [nkp] int32 (-1: none)"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    nx, ny, nz = (torch.empty((n,), dtype=torch.float32, device=kpx.device) for _ in range(3))
+    src = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_index else None
+    ctx.check(lib().ismhip_keypoint_normals(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(nx), _p(ny), _p(nz), _p(src)),
+              "ismhip_keypoint_normals")
+    return (nx, ny, nz, src) if want_index else (nx, ny, nz)
+
+
+def spin_image(ctx, cloud, kp_offsets, kpx, kpy, kpz, ax, ay, az, radius, image_width=SPIN_IMAGE_WIDTH, want_counts=False):
+    """ismhip_spin_image about the axes (ax, ay, az) -> [nkp, (w + 1)(2w + 1)]; with want_counts the neighbours per keypoint [nkp]"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    w = int(image_width)
+    out = torch.empty((n, (w + 1) * (2 * w + 1) if w >= 1 else 0), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_spin_image(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(ax), _p(ay), _p(az), C.c_float(radius), C.c_int(w),
+                                      _p(out), _p(cnt)), "ismhip_spin_image")
+    return (out, cnt) if want_counts else out
 
 
 GLOBAL_SHORT_SHOT_AUTO_BINS = dict(SHORT_SHOT_AUTO_BINS)

@@ -39,6 +39,10 @@ __device__ __forceinline__ void shot_hard_bin(float m, float x, float c, float c
 __device__ __forceinline__ void shot_dep(shot_bin_t* hist, int bin, float v) {
     atomicAdd(&hist[bin], (shot_bin_t)__float2uint_rn(v * SHOT_FIX_SCALE));
 }
+// the same for a weight held in double (spin_image.hip): round(v * 2^28), at most 2^-29 off
+__device__ __forceinline__ void shot_dep(shot_bin_t* hist, int bin, double v) {
+    atomicAdd(&hist[bin], (shot_bin_t)__double2ull_rn(v * (double)SHOT_FIX_SCALE));
+}
 
 // Per-neighbour SHOT update. All 64 lanes call it; 'act' marks lanes that hold a neighbour. Args: anything with the cell-sorted
 // normals sn4 and, for COLOR, the normalised CIELab slab4.

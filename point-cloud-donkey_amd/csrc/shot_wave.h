@@ -1,5 +1,6 @@
-// shot_wave.h — what the kernels of the SHOT family (shot.hip: k_shot; short_shot.hip: k_short_shot; short_cshot.hip: k_short_cshot)
-// and CoSPAIR (cospair.hip: k_cospair, which has no frame) have in common: one 64-lane wavefront per keypoint that sets itself up
+// shot_wave.h — what the kernels of the SHOT family (shot.hip: k_shot; short_shot.hip: k_short_shot; short_cshot.hip: k_short_cshot),
+// CoSPAIR (cospair.hip: k_cospair, which has no frame) and SpinImage (spin_image.hip: k_spin_image, an axis in place of the frame) have
+// in common: one 64-lane wavefront per keypoint that sets itself up
 // from the keypoint, its frame and the object's grid, streams the points inside the query ball through an LDS queue to a per-neighbour function, and a launcher that checks the caller's arrays,
 // uploads the keypoint offsets and starts a quarter as many workgroups as the longest keypoint run. The kernels differ in their
 // per-neighbour function, their histogram and their normalisation only; those stay in their units.

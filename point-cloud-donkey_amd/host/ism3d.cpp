@@ -97,6 +97,7 @@ public:
     int n_classes = 0;
     // scratch for raw (uncompacted) features
     DevBuf raw_lrf, raw_desc, raw_cnt;
+    DevBuf raw_axis;      // SpinImage: the keypoints' looked-up normals, three runs of nkp floats
 
     // ISMHIP_KNN_BINARY=0, read when the context is created: BSHOT codebooks keep the float search (A/B runs, tests; same answers)
     bool knn_binary_route = true;
@@ -458,6 +459,7 @@ void FeaturesSHORTCSHOT::iPostInitConfig() {     // configureSphericalGrid, then
         throw RuntimeException("SHORT_CSHOT: a descriptor longer than " + std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + " is not built on the MI355X path");
 }
 FeaturesCospair::FeaturesCospair() { addParameter(m_radius, "Radius", 0.1f); }   // features_cospair.cpp:19-22
+FeaturesSpinImage::FeaturesSpinImage() { addParameter(m_radius, "Radius", 0.1f); }   // features_spin_image.cpp:19-22
 void FeaturesCospair::checkInput(const PointCloud& cloud) const {
     if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("CoSPAIR needs coloured point clouds");
 }
@@ -493,6 +495,16 @@ void FeaturesCospair::iComputeDescriptors(DeviceSession& s, const float*, float*
     if (!s.has_color) throw RuntimeException("CoSPAIR needs coloured point clouds");
     s.check(ismhip_cospair(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, desc_out, counts_out,
                            nullptr, nullptr), "ismhip_cospair");
+}
+// features_spin_image.cpp:28-87: the keypoints' normals by coordinate equality (:36-53), then the spin images about them (:61-69)
+void FeaturesSpinImage::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    const size_t nkp = s.kp_off.back();
+    s.raw_axis.reserve(nkp * 3 * 4);
+    float *ax = s.raw_axis.as<float>(), *ay = ax + nkp, *az = ay + nkp;
+    s.check(ismhip_keypoint_normals(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), ax, ay, az, nullptr),
+            "ismhip_keypoint_normals");
+    s.check(ismhip_spin_image(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), ax, ay, az, m_radius,
+                              ISMHIP_SPIN_IMAGE_WIDTH, desc_out, counts_out), "ismhip_spin_image");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1489,7 +1501,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesSHORTCSHOT::getTypeStatic()) return new FeaturesSHORTCSHOT();
     if (type == FeaturesCospair::getTypeStatic()) return new FeaturesCospair();
     if (type == FeaturesBSHOT::getTypeStatic()) return new FeaturesBSHOT();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)");
+    if (type == FeaturesSpinImage::getTypeStatic()) return new FeaturesSpinImage();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

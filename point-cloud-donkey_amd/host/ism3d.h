@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -284,6 +284,10 @@ ISM3D_FEATURE(FeaturesFPFH, "FPFH", 33, false)
 // features/features_bshot.{h,cpp}: SHOT-352 binarised in groups of four (getBinaryVector :109-157); rows of zeros and ones. The frames and
 // centerDist are FeaturesSHOT's. A NaN SHOT row becomes 352 ones and stays in the batch, as in the reference.
 ISM3D_FEATURE(FeaturesBSHOT, "BSHOT", ISMHIP_BSHOT_DIM, false)
+// features/features_spin_image.{h,cpp}: PCL's spin image (width 8, rectangular, support-angle cosine 0) about the normal of the cloud point
+// the keypoint coincides with, 153 floats; a keypoint that is no cloud point gets the zero axis, as in the reference (DESIGN.md section
+// 4.15), so the type wants keypoints taken from the cloud (ISS3D). The frames only decide which keypoints stay; centerDist is not set.
+ISM3D_FEATURE(FeaturesSpinImage, "SpinImage", ISMHIP_SPIN_IMAGE_DIM, false)
 // features/features_short_shot.{h,cpp}: the generalised Short SHOT. Not an ISM3D_FEATURE: its length follows the spherical grid.
 class FeaturesSHORTSHOT : public Features {
 public:

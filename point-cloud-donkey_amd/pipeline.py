@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -97,7 +97,7 @@ class IsmConfig:
             return self.short_shot_grid[0]
         if self.feature == "SHORT_CSHOT":
             return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
-        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM}[self.feature]
+        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM}[self.feature]
 
     @property
     def metric(self):
@@ -222,8 +222,13 @@ class Recognizer:
         elif c.feature == "CoSPAIR":
             # no frame enters the descriptor either; the reference computes and filters by them for every feature type
             desc, cnt = capi.cospair(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
+        elif c.feature == "SpinImage":
+            # the axis is the normal of the cloud point the keypoint coincides with (features_spin_image.cpp:36-53): zero for a keypoint
+            # that is no cloud point, so this descriptor wants keypoints taken from the cloud (ISS3D)
+            ax, ay, az = capi.keypoint_normals(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz)
+            desc, cnt = capi.spin_image(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, ax, ay, az, c.radius, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
