@@ -449,6 +449,15 @@ int  ismhip_codebook_max_votes_per_word(const ismhip_codebook* cb);
 int  ismhip_codebook_stage1_dims(const ismhip_codebook* cb, float* energy_out);
 /* The same for the image the queries whose stage-1 proof failed are searched on again (0: all dimensions). */
 int  ismhip_codebook_stage2_dims(const ismhip_codebook* cb, float* energy_out);
+/* Diagnostic: the rotated f16 image ismhip_knn makes of a query batch for stage 1 (stage = 1) or stage 2 (stage = 2), as the proofs
+ * see it. q: device [nq x dim]. image_out: device [nq x m] f16 bits, row-major (the search's tiled layout undone); qn2_out / qn2h_out:
+ * device [nq], |q|^2 of the rows and the sums of squares of the image rows as stored. r_out_h (host [m x dim_pad], may be NULL): the
+ * fp32 rotation R the bound refers to. consts_out_h (host [3], may be NULL): the image scale s and the constants of
+ * |image / s - R q|_2 <= d_rel |q|_2 + d_abs that the proofs use on this ctx (ISMHIP_KNN_ROTATE_F32 read at its creation).
+ * Returns m (0: the codebook has no such image, nothing written) or a negative error. q == NULL or nq == 0: only m, R and the
+ * constants. Synchronises. */
+int  ismhip_codebook_rotate_probe(ismhip_ctx* ctx, const ismhip_codebook* cb, int stage, int nq, const float* q, uint16_t* image_out,
+                                  float* qn2_out, float* qn2h_out, float* r_out_h, float* consts_out_h);
 
 /* The resident integer image of a codebook whose every element is exactly 0.0f or 1.0f (-0.0f counts as 0), e.g. B-SHOT rows
  * (features/features_bshot.cpp:96-99): int8 rows zero-padded to the search kernel's K step (128) and the number of ones per row.

@@ -26,7 +26,7 @@ EXPORTS = [
     "ismhip_cloud_create", "ismhip_cloud_destroy", "ismhip_cloud_centroids", "ismhip_cloud_radii", "ismhip_estimate_normals", "ismhip_estimate_normals_pca",
     "ismhip_shot_lrf", "ismhip_shotna_lrf", "ismhip_shot352", "ismhip_cshot1344", "ismhip_fpfh33", "ismhip_center_dist",
     "ismhip_compact_features", "ismhip_compact_descriptor_rows", "ismhip_filter_normals", "ismhip_voxel_keypoints", "ismhip_gather_columns",
-    "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims",
+    "ismhip_codebook_create", "ismhip_codebook_set_word_class", "ismhip_codebook_destroy", "ismhip_codebook_max_votes_per_word", "ismhip_codebook_stage1_dims", "ismhip_codebook_stage2_dims", "ismhip_codebook_rotate_probe",
     "ismhip_knn", "ismhip_knn_ratio", "ismhip_knn_rule", "ismhip_cast_votes", "ismhip_find_maxima", "ismhip_hough3d_maxima", "ismhip_train_activate", "ismhip_kmeans",
     "ismhip_knn_threshold", "ismhip_cast_votes_csr", "ismhip_train_activate_lists", "ismhip_knn_large_k",
     "ismhip_filter_statistical", "ismhip_filter_radius", "ismhip_filter_passthrough_z", "ismhip_compact_points",
@@ -201,6 +201,27 @@ class Codebook:
         self.stage1_energy = float(e.value)
         self.stage2_dims = int(lib().ismhip_codebook_stage2_dims(self._h, C.byref(e)))     # 0: stage 2 of the squared-L2 search on all dimensions
         self.stage2_energy = float(e.value)
+
+    def rotate_probe(self, q, stage=1):
+        """ismhip_codebook_rotate_probe: (image [nq, m] float16, |q|^2 [nq], sums of squares of the image rows [nq], R [m, dim_pad],
+        scale, d_rel, d_abs) of the rotated image the search makes of the device rows q [nq, dim]; None when the codebook has none."""
+        torch = _torch()
+        consts = np.zeros(3, np.float32)
+        m = lib().ismhip_codebook_rotate_probe(self.ctx._h, self._h, C.c_int(stage), C.c_int(0), None, None, None, None, None, _p(consts))
+        if m < 0:
+            self.ctx.check(m, "ismhip_codebook_rotate_probe")
+        if m == 0:
+            return None
+        nq = int(q.shape[0])
+        dim_pad = (self.dim + 31) // 32 * 32
+        R = np.zeros((m, dim_pad), np.float32)
+        img = torch.empty((nq, m), dtype=torch.float16, device=q.device)
+        qn2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+        qn2h = torch.empty(nq, dtype=torch.float32, device=q.device)
+        rc = lib().ismhip_codebook_rotate_probe(self.ctx._h, self._h, C.c_int(stage), C.c_int(nq), _p(q), _p(img), _p(qn2), _p(qn2h), _p(R), _p(consts))
+        if rc < 0:
+            self.ctx.check(rc, "ismhip_codebook_rotate_probe")
+        return img.cpu().numpy(), qn2.cpu().numpy(), qn2h.cpu().numpy(), R, float(consts[0]), float(consts[1]), float(consts[2])
 
     def set_word_class(self, word_class):
         self.ctx.check(lib().ismhip_codebook_set_word_class(self.ctx._h, self._h, _p(_u32(word_class))), "ismhip_codebook_set_word_class")

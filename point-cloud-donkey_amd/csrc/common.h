@@ -78,6 +78,10 @@ struct PcaImage {
     float inv_sig2 = 1.f;            // 1 / (upper bound of sigma_max(R)^2), rounded down
     float d_rel = 0.f;               // |x^ - R x|_2 <= d_rel |x|_2 + dq_abs (queries) / dc_abs (codewords): rotation + f16 rounding
     float dq_abs = 0.f, dc_abs = 0.f;
+    // the query batches' rotation on the f16 matrix cores (pca.hip, k_rotate_split16): R split into two f16 halves, its own error constants
+    unsigned short* R16 = nullptr;   // [dim_pad/32][m/16][hi, lo][64 lanes][8] f16(R 2^r16_shift) and f16 of what that leaves, in MFMA A-fragment order
+    int r16_shift = 0;
+    float dq_rel16 = 0.f, dq_abs16 = 0.f;   // |x^ - R x|_2 <= dq_rel16 |x|_2 + dq_abs16 for a query image made from R16
     float resid2 = 0.f;              // mean second moment per codeword OUTSIDE the leading m coordinates (the pre-pass relaxes its start thresholds by it)
     float energy = 0.f;              // share of the codebook's second moment in the leading m coordinates (diagnostic)
 };
@@ -173,6 +177,7 @@ struct ismhip_ctx {
     int knn_pca_m = -1;          // env ISMHIP_KNN_PCA_M: leading rotated coordinates of the stage-1 image (0 = no rotated image, -1 = chosen from the spectrum)
     bool knn_stage2_t4 = false;       // env ISMHIP_KNN_STAGE2_T4=1: partial stage-2 chunks on the 256-query tiles of full ones (A/B runs)
     bool codebook_light = false;      // set around ismhip_codebook_create by ism_knn_only_codebook: skip the rotated image and the chi-square shadow
+    bool knn_rotate_f32 = false;      // env ISMHIP_KNN_ROTATE_F32=1: query batches are rotated on the FP32 matrix cores (k_rotate_f16t) and the re-rank sums their norms itself, as the codebook images always are (A/B runs, tests; same results)
     int knn_pca_m2 = -1;         // env ISMHIP_KNN_PCA_M2: coordinates of the stage-2 image (0 = stage 2 on all dimensions, -1 = chosen from the spectrum)
     uint32_t knn_pca_launches = 0;    // squared-L2 searches whose stage 1 ran on the rotated image (tests / bench)
     uint32_t knn_thr_overflow = 0;        // last ismhip_knn_threshold on the matrix cores: queries whose list exceeded the emit cap (answered by the exact scan)

@@ -95,6 +95,7 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_LARGE_K_SEED_SCALE"); if (e) ctx->knn_lk_seed_scale = (float)atof(e); }
     { const char* e = getenv("ISMHIP_ISS3D_MAP"); ctx->iss3d_wave = e && !strcmp(e, "wave"); }
     { const char* e = getenv("ISMHIP_KNN_PCA_M2"); ctx->knn_pca_m2 = e ? atoi(e) : -1; }
+    { const char* e = getenv("ISMHIP_KNN_ROTATE_F32"); ctx->knn_rotate_f32 = e && e[0] == '1'; }
     if (!own) { ctx->stream = (hipStream_t)stream; ctx->own_stream = false; }
     else {
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return ISMHIP_ERR_HIP; }

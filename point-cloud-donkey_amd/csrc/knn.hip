@@ -188,8 +188,10 @@ int knn_query_images(KnnRun& r) {
     r.q_lo = r.q_hi + tot;
     if (p.pca) {
         TimerScope tr(ctx, "knn_rotate");
-        const int rc = ism_pca_rotate_queries(ctx, cb, r.PI, r.qq, nq, r.ldq, r.q_hi);
+        float* norms = (float*)r.q_lo;                                    // (no second image on this route: nq_pad * 2 floats fit in its place)
+        const int rc = ism_pca_rotate_queries(ctx, cb, r.PI, r.qq, nq, r.ldq, r.q_hi, norms, norms + nq_pad);
         if (rc != ISMHIP_OK) return rc;
+        if (ism_pca_split_queries(ctx, r.PI)) { r.qn2 = norms; r.qn2h = norms + nq_pad; }
         ++ctx->knn_pca_launches;
     } else if (p.mode == 0) {
         const float* cq = p.hell ? r.rq->hell_q : r.qq; const int cldq = p.hell ? cb->dim_pad : r.ldq;     // Hellinger: the images are made from sqrt(q)

@@ -269,6 +269,7 @@ struct KnnRun {
     int metric, nq, k, T;
     const float* qq; int ldq;            // the query rows as the kernels read them (padded to dim_pad when dim is not)
     u16 *q_hi, *q_lo;                    // 16-bit query images (knn_query_images; nullptr: the candidate kernel reads the rows themselves)
+    const float *qn2, *qn2h;             // rotated image made on the f16 matrix cores: |q|^2 and the image rows' sums of squares, behind the image (else nullptr)
     float *cand_val, *cand_bound; int* cand_idx; int n_cand, n_bound;      // candidate lists and slot bounds (after a merge: the folded slot)
     uint32_t *counters, *qsc;            // the search's own counter block (KnnCounter) and, in it, the f16 scalars of the query batch
     KnnQueue queue;                      // the queue of unproven work: carved behind the counter block, or the request's shared queue
@@ -285,7 +286,10 @@ int knn_sqrt_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const f
 // the caller launches its tau kernel with knn_verify_params(xb, dim_pad, 0, sc, cn_acc), knn_mfma16_emit lists the rows.
 int knn_f16_emit_image(ismhip_ctx* ctx, const ismhip_codebook* cb, const ismhip_codebook* xb, const float* qv, int n, int ldv, int n_pad,
                        uint32_t* sc, u16* qimg);
-int ism_pca_rotate_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, const PcaImage* P, const float* q, int nq, int ldq, unsigned short* dst);   // pca.hip
+// pca.hip: the rotated f16 image of a query batch; when ism_pca_split_queries (the f16 matrix-core route) it also leaves |q|^2 of the rows
+// and the sums of squares of the image rows as stored in qn2 / qn2h [nq rounded up to 256], which the proofs then read (PcaVerify)
+int ism_pca_rotate_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, const PcaImage* P, const float* q, int nq, int ldq, unsigned short* dst, float* qn2, float* qn2h);
+bool ism_pca_split_queries(const ismhip_ctx* ctx, const PcaImage* P);
 // ---- knn_rerank.hip (phases of run_knn) ----------------------------------------------------------------------------------------------------
 // thr0[nq] = the start thresholds of a seeded search (k_knn_seed_thr; needs the query image and, on the original image, its scalars)
 int knn_seed_thresholds(KnnRun& r, const float* out_scale, float* thr0);

@@ -187,20 +187,28 @@ __global__ __launch_bounds__(256) void k_knn_rerank(const float* __restrict__ wo
 //   * a slot whose dropped-score bound b has LB(b) (1 - ku) above the k-th exact value cannot hide a better row: proven.
 struct PcaVerify {
     const u16* qimg; int nk;          // rotated f16 query image (tiled), slices per row
+    const float *qn2, *qn2h;          // the rotation pass's |q|^2 and sums of squares of the image rows (k_rotate_split16); nullptr: summed here
     float inv_sq2;                    // 1 / scale^2 of that image
     float inv_sig2, d_rel, dq_abs, dc;   // 1 / sigma_max^2 (rounded down); |x^ - R x| <= d_rel |x| + abs; dc = the codeword side for |c| = |c|max
     float eps_c2, dot2, cmax2;        // eps_acc = eps_c2 + dot2 |q^||c^|max;  cmax2 = max |c^|^2
     float ku;
 };
-// what LB(s) takes of query qi (row qp, |q|^2 = qn2 by wave_norm2), by the whole wave
-__device__ __forceinline__ PcaLb pca_lb_query(const PcaVerify& pv, int qi, float qn2, int lane) {
-    float qn2h = 0.f;                                                  // |q^|^2 from the image itself (the halves as stored: any element order)
-    for (int i = lane; i < pv.nk * F16T_KB; i += 64) {
-        const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[f16t_stored(qi, pv.nk, i)]);
-        qn2h += v * v;
+// what LB(s) takes of query qi (row qp of dim floats), by the whole wave: |q|^2 and |q^|^2 as the rotation pass left them, or (the
+// FP32 rotation) by wave_norm2 and from the image itself. Every kernel that calls this for a query gets the same bits.
+__device__ __forceinline__ PcaLb pca_lb_query(const PcaVerify& pv, int qi, const float* __restrict__ qp, int dim, int lane) {
+    float qn2, qn2h;
+    if (pv.qn2) { qn2 = pv.qn2[qi]; qn2h = pv.qn2h[qi]; }
+    else {
+        qn2 = wave_norm2(qp, dim, lane);
+        float s = 0.f;                                                 // |q^|^2 from the image itself (the halves as stored: any element order)
+        for (int i = lane; i < pv.nk * F16T_KB; i += 64) {
+            const float v = (float)__builtin_bit_cast(_Float16, pv.qimg[f16t_stored(qi, pv.nk, i)]);
+            s += v * v;
+        }
+        qn2h = wave_sum_f(s);
     }
     PcaLb b;
-    b.qn2h = wave_sum_f(qn2h) * pv.inv_sq2;
+    b.qn2h = qn2h * pv.inv_sq2;
     b.dlt = pv.d_rel * (sqrtf(qn2) * 1.00001f) + pv.dq_abs + pv.dc;
     b.eps_s = (pv.eps_c2 + pv.dot2 * sqrtf(b.qn2h * pv.cmax2)) * 1.00001f;
     b.inv_sig2 = pv.inv_sig2;
@@ -216,7 +224,7 @@ __global__ __launch_bounds__(256) void k_knn_rerank_pca(const float* __restrict_
     if (qi >= nq || knn_is_padding(tg, qi)) return;
     const int lane = lane_id();
     const float* qp = q + (size_t)qi * ldq;
-    const PcaLb lbq = pca_lb_query(pv, qi, wave_norm2(qp, dim, lane), lane);
+    const PcaLb lbq = pca_lb_query(pv, qi, qp, dim, lane);
     float av;
     const int id = knn_load_cand(cand_idx, cand_val, qi, cand_stride, lane, n_cand, n_words, av);
     const float lb = id >= 0 ? pca_lb_of(lbq, av) : __builtin_inff();
@@ -274,9 +282,10 @@ __global__ __launch_bounds__(256) void k_knn_seed_thr(const float* __restrict__ 
     if (qi >= nq) return;
     if (live && live[qi] == ~0u) { if (lane_id() == 0) thr[qi] = __builtin_inff(); return; }
     const int lane = lane_id();
-    const float qn2 = wave_norm2(q + (size_t)qi * ldq, dim, lane);
+    float qn2 = 0.f;
     PcaLb lbq{};
-    if (pca) lbq = pca_lb_query(pv, qi, qn2, lane);
+    if (pca) lbq = pca_lb_query(pv, qi, q + (size_t)qi * ldq, dim, lane);
+    else qn2 = wave_norm2(q + (size_t)qi * ldq, dim, lane);
     if (lane != 0) return;
     const float U = seed_dk[qi], osc = out_scale[0];
     float t0 = -__builtin_inff();
@@ -428,7 +437,9 @@ PcaVerify knn_pca_verify(const KnnRun& r, const VerifyParams& vp) {
     PcaVerify pv;
     const float acc_rel = 1.01f * (float)PI.m * 1.1920929e-07f;            // accumulation only: products of f16 values are exact in fp32
     pv.qimg = r.q_hi; pv.nk = r.p.ring_nk; pv.inv_sq2 = 1.0f / (PI.sq * PI.sq);
-    pv.inv_sig2 = PI.inv_sig2; pv.d_rel = PI.d_rel; pv.dq_abs = PI.dq_abs;
+    pv.qn2 = r.qn2; pv.qn2h = r.qn2h;
+    const bool split = r.qn2 != nullptr;                                   // the query image came from the f16 matrix cores: its own constants
+    pv.inv_sig2 = PI.inv_sig2; pv.d_rel = split ? PI.dq_rel16 : PI.d_rel; pv.dq_abs = split ? PI.dq_abs16 : PI.dq_abs;
     pv.dc = (PI.d_rel * sqrtf(r.cb->max_norm2) + PI.dc_abs) * 1.00001f;
     pv.cmax2 = PI.cmax2;
     // subnormal f16 operands may be flushed to zero by the matrix cores: |dq_i| <= 2^-14 / sq, |dc_i| <= 2^-14 / sc per element

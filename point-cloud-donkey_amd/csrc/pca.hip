@@ -18,6 +18,25 @@
 // The query image uses a scale FIXED per codebook (queries are assumed to be at most twice as long as the longest codeword; three
 // more bits of f16 headroom above that; a query beyond it overflows to inf, fails its proof and is searched by stage 2 in the
 // original coordinates): no pass over the query batch to find its largest element.
+//
+// Query batches on the f16 matrix cores (k_rotate_split16; the codebook's own images keep the FP32 rotation, they are made once per model).
+// The image is rounded to f16 anyway (2^-11 |x| above), so the product only needs to be good to well below that: R and x are split into
+// two f16 halves each and three f16 products are accumulated in fp32. With the fp32 R as the reference:
+//   Rh = f16(R 2^k), Rl = f16(R 2^k - Rh), k the largest shift with |R| 2^k <= 2^15; a half below the smallest normal f16 is stored as 0
+//            (split_r16: what is uploaded does not depend on how the matrix cores treat subnormal operands). Rs = (Rh + Rl) 2^-k, E = R - Rs
+//   v = s x  (s = the image's fixed scale, a power of two: exact), xh = f16(v), xl = f16(v - xh), xs = xh + xl, e = v - xs
+//   accumulated: Rh xh + Rh xl + Rl xh = 2^k (Rs xs - (Rl 2^-k) xl)  =>  R v - 2^-k acc = E v + Rs e + (Rl 2^-k) xl + accumulation error
+//   |E v| <= |E|_F |v|                                   (split residual of R; |E|_F in fp64 from the halves as uploaded)
+//   |e_i| <= 2^-22 |v_i| + 2^-14                         (two roundings to nearest; a half below 2^-14 charged in full, flushed or not)
+//            => |Rs e| <= (sigma + |E|_F) (2^-22 |v| + sqrt(D) 2^-14)
+//   |xl_i| <= 1.001 2^-11 |v_i| + 2^-24                  => the dropped |(Rl 2^-k) xl| <= |Rl 2^-k|_F (1.001 2^-11 |v| + sqrt(D) 2^-24)
+//   products of f16 values are exact in fp32; 3 D of them added in any order, 2^-23 per add: g3 = 1.01 3 D 2^-23 on
+//            sum |r||x| <= (|Rh 2^-k|_F + |Rl 2^-k|_F) (1.002 |v| + sqrt(D) 2^-13); the final scaling by 2^-k is exact
+//   A = |E|_F + (sigma + |E|_F) 2^-22 + 1.001 2^-11 |Rl 2^-k|_F + 1.002 g3 (|Rh 2^-k|_F + |Rl 2^-k|_F), B = the absolute parts;
+//   rounding the result to f16 adds 2^-11 (sigma + A) |v| + 2^-11 B + sqrt(m) 2^-14, as for the FP32 kernel
+//   => |x^ - R x| <= dq_rel16 |x| + dq_abs16,  dq_rel16 = 1.001 (A + 2^-11 (sigma + A)),  dq_abs16 = 1.001 ((1 + 2^-11) B + sqrt(m) 2^-14) / s
+// The codeword side keeps d_rel and dc_abs. ISMHIP_KNN_ROTATE_F32=1 (read when the context is created) rotates the queries with the FP32
+// kernel too; the proofs then use d_rel / dq_abs for them and sum the norms themselves, as before.
 #include "knn_internal.h"
 #include <cmath>
 #include <algorithm>
@@ -129,6 +148,140 @@ __global__ __launch_bounds__(256, 2) void k_rotate_f16t(const float* __restrict_
     }
 }
 
+// ---- the same image for QUERY batches on the f16 matrix cores (header: "Query batches on the f16 matrix cores") ---------------------
+// v_mfma_f32_16x16x32_f16, basis vectors as rows and descriptors as columns again: a lane holds, for ONE descriptor (column lane & 15),
+// the rotated coordinates 16 mt + 4 g + 0..3 (g = lane >> 4) of every 16-row output tile mt -- four consecutive halves of the image
+// row, one 8-byte store. 128 descriptors per workgroup, 32 per wave (two column tiles), all m outputs per wave; K walked in chunks of
+// 32. The descriptor fragments come straight from global memory (the four lanes of a descriptor take the floats 4 g .. 4 g + 3 and
+// 16 + 4 g .. of a chunk, so that each load instruction reads 64 contiguous bytes of a row -- the MFMA only asks that R's fragments
+// pair the same k with the same lane element; the next chunk is in flight while this one is multiplied) and are split in registers; the two halves of R arrive in fragment order (split_r16) and are
+// staged through LDS, a 32-k chunk at a time in two buffers: one barrier per chunk.
+// Behind the image: qn2[row] = |x|^2 of the f32 row and qn2h[row] = the sum of squares of the halves as stored (k_knn_rerank_pca's
+// |q|^2 and |q^|^2 sq^2). Depth of the sums (the proofs charge 16 u on |q^|^2 and 1e-5 on |q|): |q^|^2 is a tree of exact squares,
+// 2 + log2(m / 16) + 2 additions deep; |q|^2 adds a chunk's 8 squares to a lane's running sum, K / 32 + 10 roundings deep.
+// A row with a NaN element is NaN in every coordinate, as a product with NaN is; an element beyond the f16 range after scaling (the
+// row is then more than four times as long as the scale is made for) makes the row +inf, as its leading coordinates would be.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int NT>
+__global__ __launch_bounds__(256, 2) void k_rotate_split16(const float* __restrict__ x, int n, int ldx, int kdim, const u16* __restrict__ r16, int m,
+                                                            float sx, float out_mul, u16* __restrict__ dst, float* __restrict__ qn2_out, float* __restrict__ qn2h_out) {
+    extern __shared__ __attribute__((aligned(16))) float rot_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int c16 = lane & 15, g = lane >> 4;
+    const int nct = m >> 5;                     // 32-wide output tiles in use (<= NT): 2 nct MFMA row tiles, nct 16-byte units per thread and chunk of R
+    const size_t row0 = (size_t)blockIdx.x * 128;
+    const u32x4* rsrc = (const u32x4*)r16;      // a chunk: nct * 256 units of 16 bytes, [row tile][hi, lo][lane]
+    u32x4* sR = (u32x4*)rot_smem;               // [2][NT * 256]
+    const float* xrow[2];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        size_t r = row0 + wv * 32 + nt * 16 + c16; r = r < (size_t)n ? r : (size_t)n - 1;          // clamped duplicates are zeroed on store
+        xrow[nt] = x + r * ldx + 4 * g;
+    }
+    f32x4 acc[2 * NT][2];
+#pragma unroll
+    for (int t = 0; t < 2 * NT; ++t)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) acc[t][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    u32x4 rs[NT];
+    f32x4 xn[2][2];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) if (i < nct) rs[i] = rsrc[tid + 256 * i];
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) { xn[nt][0] = *(const f32x4*)(xrow[nt]); xn[nt][1] = *(const f32x4*)(xrow[nt] + 16); }
+#pragma unroll
+    for (int i = 0; i < NT; ++i) if (i < nct) sR[tid + 256 * i] = rs[i];
+    float qs[2] = {0.f, 0.f};
+    bool bad[2] = {false, false}, isnan_[2] = {false, false};
+    const int nkc = kdim >> 5;
+    for (int kc = 0; kc < nkc; ++kc) {
+        const u32x4* sRb = sR + (kc & 1) * (NT * 256);
+        f32x4 xr[2][2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) { xr[nt][0] = xn[nt][0]; xr[nt][1] = xn[nt][1]; }
+        __syncthreads();                        // chunk kc is in its buffer, and nobody reads the other one (chunk kc - 1) any more
+        if (kc + 1 < nkc) {                     // (never beyond the row: the last row's end may be the end of the array)
+#pragma unroll
+            for (int i = 0; i < NT; ++i) if (i < nct) rs[i] = rsrc[(size_t)(kc + 1) * nct * 256 + tid + 256 * i];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) { xn[nt][0] = *(const f32x4*)(xrow[nt] + (kc + 1) * 32); xn[nt][1] = *(const f32x4*)(xrow[nt] + (kc + 1) * 32 + 16); }
+        }
+        f16x8 bh[2], bl[2];
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            float part = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float xv = xr[nt][j >> 2][j & 3];
+                part += xv * xv;
+                float v = xv * sx;
+                const bool ok = fabsf(v) <= 65504.f;                 // false for NaN
+                bad[nt] |= !ok; isnan_[nt] |= v != v;
+                v = ok ? v : 0.f;
+                const _Float16 hi = (_Float16)v;                     // round to nearest even; v - hi is exact in fp32
+                bh[nt][j] = hi; bl[nt][j] = (_Float16)(v - (float)hi);
+            }
+            qs[nt] += part;
+        }
+#pragma unroll
+        for (int t = 0; t < 2 * NT; ++t) {
+            if (t >= 2 * nct) continue;                               // uniform
+            const f16x8 ah = __builtin_bit_cast(f16x8, sRb[(2 * t) * 64 + lane]), al = __builtin_bit_cast(f16x8, sRb[(2 * t + 1) * 64 + lane]);
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[nt], acc[t][nt], 0, 0, 0);
+                acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[nt], acc[t][nt], 0, 0, 0);
+                acc[t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[nt], acc[t][nt], 0, 0, 0);
+            }
+        }
+        if (kc + 1 < nkc) {
+            u32x4* sRn = sR + ((kc + 1) & 1) * (NT * 256);
+#pragma unroll
+            for (int i = 0; i < NT; ++i) if (i < nct) sRn[tid + 256 * i] = rs[i];
+        }
+    }
+    // C layout of the 16x16 tile: column = lane & 15 (descriptor), row = 4 g + e (rotated coordinate 16 t + 4 g + e)
+    const size_t n_img = ((size_t)n + F16T_ROWS - 1) / F16T_ROWS * F16T_ROWS;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        // the four lanes of a descriptor (g = 0 .. 3) hold a quarter of its elements each (every lane takes part in the exchanges)
+        float q2 = qs[nt]; int fl = (bad[nt] ? 1 : 0) | (isnan_[nt] ? 2 : 0);
+        q2 += __shfl_xor(q2, 16, 64); q2 += __shfl_xor(q2, 32, 64);
+        fl |= __shfl_xor(fl, 16, 64); fl |= __shfl_xor(fl, 32, 64);
+        const size_t row = row0 + wv * 32 + nt * 16 + c16;
+        const bool in_img = row < n_img, live = row < (size_t)n;
+        const size_t tile = row / F16T_ROWS; const int r = (int)(row % F16T_ROWS);
+        const int fsw = f16t_swizzle(r);
+        float sq4[16];
+#pragma unroll
+        for (int t = 0; t < 16; ++t) sq4[t] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2 * NT; ++t) {
+            if (t >= 2 * nct) continue;
+            union { _Float16 hf[4]; uint2 u; } pk;
+            float hs[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                _Float16 hv = (_Float16)(acc[t][nt][e] * out_mul);
+                if (fl & 1) hv = (_Float16)__builtin_inff();
+                if (fl & 2) hv = (_Float16)__builtin_nanf("");
+                if (!live) hv = (_Float16)0.f;
+                pk.hf[e] = hv; hs[e] = (float)hv;
+            }
+            sq4[t] = (hs[0] * hs[0] + hs[1] * hs[1]) + (hs[2] * hs[2] + hs[3] * hs[3]);
+            const int seg = ((t & 1) << 1) | (g >> 1);
+            if (in_img) *(uint2*)(dst + f16t_row(tile, r, nct, t >> 1) + ((seg ^ fsw) << 3) + 4 * (g & 1)) = pk.u;
+        }
+#pragma unroll
+        for (int w = 8; w >= 1; w >>= 1)                              // pairwise, four rounds
+#pragma unroll
+            for (int t = 0; t < w; ++t) sq4[t] += sq4[t + w];
+        float h2 = sq4[0];
+        h2 += __shfl_xor(h2, 16, 64); h2 += __shfl_xor(h2, 32, 64);
+        if (in_img && g == 0) { qn2_out[row] = live ? q2 : 0.f; qn2h_out[row] = h2; }
+    }
+}
+
 // sum of squares of every image row (one wave per row): sumsq[row] = sum h^2 (h = stored f16 value), and the ring kernel's
 // pre-scaled C operand cn[row] = -sumsq * cn_factor (= |c^|^2 / out_scale), -inf for the padding rows (they can never win)
 __global__ __launch_bounds__(256) void k_f16t_norms(const u16* __restrict__ img, int n_rows_pad, int n_rows, int nk, float cn_factor,
@@ -187,11 +340,135 @@ int launch_rotate(ismhip_ctx* ctx, const float* x, int n, int ldx, int kdim, con
     return ISMHIP_OK;
 }
 
+int launch_rotate_split(ismhip_ctx* ctx, const float* x, int n, int ldx, int kdim, const PcaImage& P, u16* dst, float* qn2, float* qn2h) {
+    int m = P.m; const int nct = m / 32;
+    const void* kern = nct <= 4 ? (const void*)k_rotate_split16<4> : nct <= 6 ? (const void*)k_rotate_split16<6> : (const void*)k_rotate_split16<8>;
+    const int nt = nct <= 4 ? 4 : nct <= 6 ? 6 : 8;
+    const size_t lds = (size_t)2 * nt * 256 * 16;                  // two buffers of a 32-k chunk of both halves of R
+    { const int rc = ism_lds_cap(ctx, kern, lds); if (rc != ISMHIP_OK) return rc; }
+    const unsigned blocks = (unsigned)((((size_t)n + 255) / 256 * 256) / 128);
+    const u16* r16 = P.R16; float sx = P.sq, out_mul = std::ldexp(1.0f, -P.r16_shift);
+    void* args[] = {&x, &n, &ldx, &kdim, &r16, &m, &sx, &out_mul, &dst, &qn2, &qn2h};
+    ISM_HIP(ctx, hipLaunchKernel(kern, dim3(blocks), dim3(256), args, lds, ctx->stream));
+    ISM_CHECK_LAUNCH(ctx, "k_rotate_split16");
+    return ISMHIP_OK;
+}
+
+// host f16 (round to nearest even) of a float, subnormal results flushed to zero: what is uploaded never depends on how the matrix
+// cores treat subnormal operands
+// (|v| <= 2^15, finite: split_r16 scales R into that range)
+u16 f16_bits_ftz(float v) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, v), sign = (b >> 16) & 0x8000u, man = b & 0x7fffffu;
+    const int e = (int)((b >> 23) & 0xffu) - 127;
+    if (e < -14) return (u16)sign;
+    uint32_t h = ((uint32_t)(e + 15) << 10) | (man >> 13);
+    const uint32_t rem = man & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;       // (a carry moves into the exponent field as it should)
+    return (u16)(sign | h);
+}
+float f16_bits_value(u16 h) {                                     // zero or a normal number, by construction
+    if ((h & 0x7fffu) == 0) return 0.f;
+    const float v = std::ldexp((float)(0x400 | (h & 0x3ff)), ((h >> 10) & 0x1f) - 25);
+    return (h & 0x8000u) ? -v : v;
+}
+
+// R = (Rh + Rl) 2^-shift + E: the halves in k_rotate_split16's fragment order, and the query side's error constants from the halves as
+// uploaded (header: "Query batches on the f16 matrix cores"). sig = the bound on sigma_max(R) of build_image.
+int split_r16(ismhip_ctx* ctx, PcaImage& P, const std::vector<float>& R, int m, int dp, double sig) {
+    float amax = 0.f;
+    for (float v : R) amax = std::max(amax, std::fabs(v));
+    int shift = 15;                                               // |R| 2^shift <= 2^15: inside f16, and the low halves as far from its subnormals as they can be
+    while (shift > -40 && std::ldexp((double)amax, shift) > 32768.0) --shift;
+    const int mt_n = m / 16, kc_n = dp / 32;
+    std::vector<u16> frag((size_t)kc_n * mt_n * 2 * 64 * 8);
+    double e2 = 0, fh2 = 0, fl2 = 0;
+    for (int kc = 0; kc < kc_n; ++kc) for (int mt = 0; mt < mt_n; ++mt) for (int lane = 0; lane < 64; ++lane) for (int j = 0; j < 8; ++j) {
+        const int row = 16 * mt + (lane & 15), col = 32 * kc + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3);      // element j of lane group g: k = 16 (j / 4) + 4 g + j % 4
+        const float rs = std::ldexp(R[(size_t)row * dp + col], shift);          // exact
+        const u16 hb = f16_bits_ftz(rs); const float hi = f16_bits_value(hb);
+        const u16 lb = f16_bits_ftz(rs - hi); const float lo = f16_bits_value(lb);      // rs - hi is exact in fp32
+        const size_t at = ((((size_t)kc * mt_n + mt) * 2) * 64 + lane) * 8 + j;
+        frag[at] = hb; frag[at + 64 * 8] = lb;
+        const double e = std::ldexp((double)rs - (double)hi - (double)lo, -shift);
+        e2 += e * e; fh2 += std::ldexp((double)hi, -shift) * std::ldexp((double)hi, -shift); fl2 += std::ldexp((double)lo, -shift) * std::ldexp((double)lo, -shift);
+    }
+    const double eR = std::sqrt(e2), fh = std::sqrt(fh2), fl = std::sqrt(fl2), sD = std::sqrt((double)dp);
+    const double gamma3 = 1.01 * 3.0 * dp * 1.1920929e-07;          // fp32 accumulation of 3 K exact products, any order, 2^-23 per add
+    const double u22 = 2.384185791015625e-07, u11 = 4.8828125e-04;
+    const double rel = eR + (sig + eR) * u22 + fl * 1.001 * u11 + gamma3 * (fh + fl) * 1.002;
+    const double abs_s = (sig + eR) * sD * (double)F16_FLUSH + fl * sD * 5.9604645e-08 + gamma3 * (fh + fl) * sD * 2.0 * (double)F16_FLUSH;   // in units of the scaled image
+    P.dq_rel16 = (float)(1.001 * (rel + u11 * (sig + rel)));
+    P.dq_abs16 = (float)(1.001 * ((1.0 + u11) * abs_s + std::sqrt((double)m) * (double)F16_FLUSH) / P.sq);
+    P.r16_shift = shift;
+    if (hipMalloc((void**)&P.R16, frag.size() * sizeof(u16)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook split rotation matrix");
+    ISM_HIP(ctx, hipMemcpy(P.R16, frag.data(), frag.size() * sizeof(u16), hipMemcpyHostToDevice));
+    return ISMHIP_OK;
+}
+
+// image row `row`, coordinates 0 .. m - 1, out of the tiled layout (diagnostic entry)
+__global__ void k_f16t_detile(const u16* __restrict__ img, int n, int m, u16* __restrict__ dense) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * m) return;
+    const unsigned row = (unsigned)(i / m); const int c = (int)(i % m), r = (int)(row % F16T_ROWS);
+    dense[i] = img[f16t_row(row / F16T_ROWS, r, m / F16T_KB, c / F16T_KB) + ((((c % F16T_KB) >> 3) ^ f16t_swizzle(r)) << 3) + (c & 7)];
+}
+__global__ void k_probe_pad_rows(const float* __restrict__ src, int n, int dim, float* __restrict__ dst, int dim_pad) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * dim_pad) return;
+    const int row = (int)(i / dim_pad), col = (int)(i % dim_pad);
+    dst[i] = col < dim ? src[(size_t)row * dim + col] : 0.f;
+}
+
 }  // namespace
 
-// the query batch -> rotated f16 image (stage 1 of the two-stage search); q rows of ldq >= dim_pad floats, zero beyond dim
-int ism_pca_rotate_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, const PcaImage* P, const float* q, int nq, int ldq, unsigned short* dst) {
-    return launch_rotate(ctx, q, nq, ldq, cb->dim_pad, P->R, P->m, P->sq, dst);
+// the query batch -> rotated f16 image (stage 1 of the two-stage search); q rows of ldq >= dim_pad floats, zero beyond dim. On the f16
+// matrix cores (default) the pass also leaves |q|^2 and the image rows' sums of squares in qn2 / qn2h [nq rounded up to 256];
+// ISMHIP_KNN_ROTATE_F32=1: the FP32 kernel of the codebook images, which writes neither
+int ism_pca_rotate_queries(ismhip_ctx* ctx, const ismhip_codebook* cb, const PcaImage* P, const float* q, int nq, int ldq, unsigned short* dst, float* qn2, float* qn2h) {
+    if (ctx->knn_rotate_f32 || !P->R16) return launch_rotate(ctx, q, nq, ldq, cb->dim_pad, P->R, P->m, P->sq, dst);
+    return launch_rotate_split(ctx, q, nq, ldq, cb->dim_pad, *P, dst, qn2, qn2h);
+}
+bool ism_pca_split_queries(const ismhip_ctx* ctx, const PcaImage* P) { return !ctx->knn_rotate_f32 && P->R16; }
+
+namespace {
+__global__ __launch_bounds__(256) void k_probe_row_norms(const float* __restrict__ x, int n, int ld, int dim, float* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float s = wave_norm2(x + (size_t)row * ld, dim, lane_id());
+    if (lane_id() == 0) out[row] = s;
+}
+}  // namespace
+
+extern "C" int ismhip_codebook_rotate_probe(ismhip_ctx* ctx, const ismhip_codebook* cb, int stage, int nq, const float* q, uint16_t* image_out,
+                                            float* qn2_out, float* qn2h_out, float* r_out_h, float* consts_out_h) {
+    if (!ctx || !cb || (stage != 1 && stage != 2) || nq < 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "codebook_rotate_probe: bad argument");
+    const PcaImage& P = stage == 2 ? cb->pca2 : cb->pca;
+    if (P.m == 0) return 0;
+    const int dp = cb->dim_pad, m = P.m;
+    const bool split = ism_pca_split_queries(ctx, &P);
+    if (consts_out_h) { consts_out_h[0] = P.sq; consts_out_h[1] = split ? P.dq_rel16 : P.d_rel; consts_out_h[2] = split ? P.dq_abs16 : P.dq_abs; }
+    if (r_out_h) ISM_HIP(ctx, hipMemcpy(r_out_h, P.R, (size_t)m * dp * sizeof(float), hipMemcpyDeviceToHost));
+    if (nq == 0 || !q || !image_out || !qn2_out || !qn2h_out) return m;
+    const size_t nq_pad = ((size_t)nq + F16T_ROWS - 1) / F16T_ROWS * F16T_ROWS;
+    const size_t b_q = nq_pad * dp * sizeof(float), b_img = nq_pad * m * sizeof(u16), b_n = nq_pad * sizeof(float);
+    char* buf = (char*)ism_scratch(ctx, SCR_PCA, b_q + b_img + 3 * b_n);
+    if (!buf) return ISMHIP_ERR_NOMEM;
+    float* qpad = (float*)buf; u16* img = (u16*)(buf + b_q); float* n2 = (float*)(buf + b_q + b_img); float* n2h = n2 + nq_pad; float* dummy = n2h + nq_pad;
+    hipLaunchKernelGGL(k_probe_pad_rows, dim3((unsigned)(((size_t)nq * dp + 255) / 256)), dim3(256), 0, ctx->stream, q, nq, cb->dim, qpad, dp);
+    ISM_CHECK_LAUNCH(ctx, "k_probe_pad_rows");
+    int rc = ism_pca_rotate_queries(ctx, cb, &P, qpad, nq, dp, img, n2, n2h);
+    if (rc != ISMHIP_OK) return rc;
+    if (!split) {                                                         // what the re-rank sums for itself on this route
+        hipLaunchKernelGGL(k_probe_row_norms, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, (const float*)qpad, nq, dp, cb->dim, n2);
+        hipLaunchKernelGGL(k_f16t_norms, dim3((unsigned)((nq_pad + 3) / 4)), dim3(256), 0, ctx->stream, (const u16*)img, (int)nq_pad, nq, m / F16T_KB, 0.f, n2h, dummy);
+        ISM_CHECK_LAUNCH(ctx, "k_f16t_norms");
+    }
+    hipLaunchKernelGGL(k_f16t_detile, dim3((unsigned)(((size_t)nq * m + 255) / 256)), dim3(256), 0, ctx->stream, (const u16*)img, nq, m, image_out);
+    ISM_CHECK_LAUNCH(ctx, "k_f16t_detile");
+    ISM_HIP(ctx, hipMemcpyAsync(qn2_out, n2, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    ISM_HIP(ctx, hipMemcpyAsync(qn2h_out, n2h, (size_t)nq * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    ISM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return m;
 }
 
 // One image from the leading m rows of the eigenbasis (R: [m x dim_pad] fp32 as uploaded): scales, error constants, the f16 image in the
@@ -223,6 +500,7 @@ static int build_image(ismhip_ctx* ctx, ismhip_codebook* cb, PcaImage& P, const 
     if (hipMalloc((void**)&P.f16t, f16t_halves(n_tiles, nk) * sizeof(u16)) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotated f16 image");
     if (hipMalloc((void**)&P.cn_scaled, ((size_t)cb->n_words_pad + 256) * sizeof(float) + 16) != hipSuccess) return ism_set_err(ctx, ISMHIP_ERR_NOMEM, "codebook rotated norms");
     P.osc = P.cn_scaled + cb->n_words_pad + 256;
+    { const int rc = split_r16(ctx, P, R, m, dp, sig); if (rc != ISMHIP_OK) return rc; }
     P.m = m;
     int rc = launch_rotate(ctx, cb->words, cb->n_words_pad, dp, dp, P.R, m, P.sc, P.f16t);
     if (rc != ISMHIP_OK) { P.m = 0; return rc; }
@@ -334,6 +612,7 @@ int ism_codebook_build_pca(ismhip_ctx* ctx, ismhip_codebook* cb) {
 void ism_codebook_free_pca(ismhip_codebook* cb) {
     for (PcaImage* P : {&cb->pca, &cb->pca2}) {
         if (P->R) (void)hipFree(P->R);
+        if (P->R16) (void)hipFree(P->R16);
         if (P->f16t) (void)hipFree(P->f16t);
         if (P->cn_scaled) (void)hipFree(P->cn_scaled);
         *P = PcaImage();
