@@ -74,6 +74,8 @@ extern "C" {
 #define ISMHIP_COSPAIR_DIM  378     /* 7 levels x (27 geometry + 27 colour) */
 #define ISMHIP_SPIN_IMAGE_WIDTH 8   /* setImageWidth(8), features_spin_image.cpp:67 */
 #define ISMHIP_SPIN_IMAGE_DIM 153   /* (8 + 1) * (2 * 8 + 1) */
+#define ISMHIP_RSD_DIM 25           /* ismhip_rsd, full_histogram: 5 angle bins x 5 distance bins */
+#define ISMHIP_RSD_RADII_DIM 2      /* ismhip_rsd without it: the two principal radii */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -94,7 +96,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -316,6 +318,30 @@ int  ismhip_keypoint_normals(ismhip_ctx* ctx, const ismhip_cloud* cloud, const u
 int  ismhip_spin_image(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                        const float* kpx, const float* kpy, const float* kpz, const float* ax, const float* ay, const float* az,
                        float radius, int image_width, float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesRSD::iComputeDescriptors (features/features_rsd.cpp:29-103) -> PCL 1.10 RSDEstimation::computeFeature / computeRSD as :41-56
+ * configure it (5 subdivisions, max_dist = the search radius, plane_radius = Radius), then, for the histogram, normalizeDescriptors
+ * (features/features.cpp:282-297). desc_out[nkp * 25] (ISMHIP_RSD_DIM) when full_histogram is not 0, else desc_out[nkp * 2]
+ * (ISMHIP_RSD_RADII_DIM). Per keypoint with centre q, R = radius, D = (double)R; every float product and sum unfused, as written:
+ *  - neighbours N: the finite cloud points with d2 < (float)(D * D), d = p - q, d2 = (d.x*d.x + d.y*d.y) + d.z*d.z in float, the
+ *    keypoint's own cloud point included when it is one; neighbour_count_out[nkp] (may be NULL) = |N|;
+ *  - for every unordered pair {i, j} of N, i != j by cloud index (coincident coordinates are still a pair), with normals ni, nj:
+ *    c = (ni.x*nj.x + ni.y*nj.y) + ni.z*nj.z and d2 of the two points in float; c or d2 not finite: the pair is skipped;
+ *    a = min(|c|, 1), theta = acos((double)a) in [0, pi/2], dist = sqrt((double)d2); dist > D: the pair is neglected;
+ *    bd = floor(5 * dist / D), 5 (dist == D) becoming 4; ba = min(4, floor(5 * theta / (pi / 2))); count[ba + 5 * bd] += 1 (Eigen's
+ *    column-major histogram(ba, bd)); per distance bin bd, amin[bd] = min a and amax[bd] = max a;
+ *  - full_histogram: row[j] = (float)count[j] / 300.0f -- the reference divides by the sum of the INDICES 0..24; counts are uint32;
+ *  - otherwise: theta_min[d] = acos(amax[d]), theta_max[d] = acos(amin[d]); bin 0 starts at theta_min = theta_max = 0, a bin without
+ *    pairs is left out; in double and in bin order, f_d = (d + 0.5) * D / 5: Amin2 = sum theta_min^2, Amind = sum theta_min * f_d, Amax2
+ *    and Amaxd likewise; rmin = Amin2 == 0 ? (float)D : (float)min(Amind / Amin2, D), rmax likewise, each times 1.1f in float; the row is
+ *    [smaller, larger], not normalised.
+ * |N| = 1: a zero row in either mode. |N| = 0, a keypoint that is not finite or a ball that misses the grid: the row NaN AS A WHOLE,
+ * count 0 (PCL gives zeros for an empty neighbourhood). The row is made of integer counts and of minima and maxima only: two calls, any
+ * grid cell size and any staging capacity (env ISMHIP_RSD_CAP, 64..256 in steps of 64; default 256) give the same bytes; larger
+ * neighbourhoods are tiled, never truncated. Refused with ISMHIP_ERR_INVALID: a missing array, a radius that is not positive and finite
+ * ("rsd: bad argument"). Timer "rsd". */
+int  ismhip_rsd(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                const float* kpx, const float* kpy, const float* kpz, float radius, int full_histogram,
+                float* desc_out, uint32_t* neighbour_count_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);
@@ -404,7 +430,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image / ismhip_rsd, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

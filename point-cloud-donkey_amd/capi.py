@@ -34,7 +34,7 @@ EXPORTS = [
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352",
-    "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image",
+    "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
@@ -432,6 +432,22 @@ def spin_image(ctx, cloud, kp_offsets, kpx, kpy, kpz, ax, ay, az, radius, image_
     cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
     ctx.check(lib().ismhip_spin_image(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(ax), _p(ay), _p(az), C.c_float(radius), C.c_int(w),
                                       _p(out), _p(cnt)), "ismhip_spin_image")
+    return (out, cnt) if want_counts else out
+
+
+RSD_DIM, RSD_RADII_DIM = 25, 2
+
+
+def rsd(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, full_histogram=True, want_counts=False):
+    """ismhip_rsd -> [nkp, 25] (the angle-distance histogram of all neighbour pairs over 300) or, without full_histogram, [nkp, 2] (the
+    two principal radii); with want_counts the neighbours per keypoint [nkp]"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, RSD_DIM if full_histogram else RSD_RADII_DIM), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_rsd(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(1 if full_histogram else 0),
+                               _p(out), _p(cnt)), "ismhip_rsd")
     return (out, cnt) if want_counts else out
 
 

@@ -460,6 +460,10 @@ void FeaturesSHORTCSHOT::iPostInitConfig() {     // configureSphericalGrid, then
 }
 FeaturesCospair::FeaturesCospair() { addParameter(m_radius, "Radius", 0.1f); }   // features_cospair.cpp:19-22
 FeaturesSpinImage::FeaturesSpinImage() { addParameter(m_radius, "Radius", 0.1f); }   // features_spin_image.cpp:19-22
+FeaturesRSD::FeaturesRSD() {                     // features_rsd.cpp:19-23
+    addParameter(m_radius, "Radius", 0.1f);
+    addParameter(m_use_hist, "UseFullRSDHistogram", true);
+}
 void FeaturesCospair::checkInput(const PointCloud& cloud) const {
     if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("CoSPAIR needs coloured point clouds");
 }
@@ -505,6 +509,11 @@ void FeaturesSpinImage::iComputeDescriptors(DeviceSession& s, const float*, floa
             "ismhip_keypoint_normals");
     s.check(ismhip_spin_image(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), ax, ay, az, m_radius,
                               ISMHIP_SPIN_IMAGE_WIDTH, desc_out, counts_out), "ismhip_spin_image");
+}
+// features_rsd.cpp:29-103: search radius and plane radius are both Radius (:49-51); the histogram is normalised (:99-100), the radii are not
+void FeaturesRSD::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    s.check(ismhip_rsd(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, m_use_hist ? 1 : 0, desc_out,
+                       counts_out), "ismhip_rsd");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1502,7 +1511,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesCospair::getTypeStatic()) return new FeaturesCospair();
     if (type == FeaturesBSHOT::getTypeStatic()) return new FeaturesBSHOT();
     if (type == FeaturesSpinImage::getTypeStatic()) return new FeaturesSpinImage();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, CoSPAIR)");
+    if (type == FeaturesRSD::getTypeStatic()) return new FeaturesRSD();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, RSD, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

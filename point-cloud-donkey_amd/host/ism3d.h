@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -339,6 +339,23 @@ protected:
     void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
 private:
     float m_radius;
+};
+// features/features_rsd.{h,cpp} -> PCL's RSDEstimation over every pair of the ball's points (ismhip_rsd): the
+// 5 x 5 angle-distance histogram over 300 (25 floats) or, with UseFullRSDHistogram false, the two principal radii (2 floats). The frames
+// only decide which keypoints stay. Not an ISM3D_FEATURE: its length follows the switch.
+class FeaturesRSD : public Features {
+public:
+    FeaturesRSD();
+    static std::string getTypeStatic() { return "RSD"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return m_use_hist ? ISMHIP_RSD_DIM : ISMHIP_RSD_RADII_DIM; }
+    bool useFullHistogram() const { return m_use_hist; }
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+private:
+    float m_radius;
+    bool m_use_hist;
 };
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------

@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -76,6 +76,7 @@ class IsmConfig:
     short_shot_log_radius: bool = False  # ShortShotLogRadius (minimum radius 0.1 * radius unless use_min_radius)
     short_color_shot_dims: int = 32      # Features(SHORT_CSHOT).ShortColorShotDims: cells of the colour grid, 8 | 16 | 24 | 32 | 64 | 96 | 128
     short_color_shot_hist_size: int = 15 # ShortColorShotHistSize: colour-distance bins per cell
+    use_full_rsd_histogram: bool = True  # Features(RSD).UseFullRSDHistogram: the 25-bin pair histogram; false: the two principal radii
 
     def __post_init__(self):
         if self.lrf_type not in capi.LRF_TYPES:
@@ -97,6 +98,8 @@ class IsmConfig:
             return self.short_shot_grid[0]
         if self.feature == "SHORT_CSHOT":
             return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
+        if self.feature == "RSD":
+            return capi.RSD_DIM if self.use_full_rsd_histogram else capi.RSD_RADII_DIM
         return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM}[self.feature]
 
     @property
@@ -227,8 +230,11 @@ class Recognizer:
             # that is no cloud point, so this descriptor wants keypoints taken from the cloud (ISS3D)
             ax, ay, az = capi.keypoint_normals(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz)
             desc, cnt = capi.spin_image(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, ax, ay, az, c.radius, want_counts=True)
+        elif c.feature == "RSD":
+            # no frame enters the descriptor (as for FPFH and CoSPAIR); every pair of the ball's points does (features_rsd.cpp:41-56)
+            desc, cnt = capi.rsd(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, full_histogram=c.use_full_rsd_histogram, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, RSD, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
