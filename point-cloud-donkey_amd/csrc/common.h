@@ -162,6 +162,7 @@ struct ismhip_ctx {
     bool knn_qpanel2 = true;     // env ISMHIP_KNN_QPANEL2=0: stage 1 on <= 160 rotated coordinates WITHOUT the 256-query panel resident in LDS (A/B runs; default on: 27.5 -> 25.4 ms per bench launch)
     bool knn_half = false;       // env ISMHIP_KNN_HALF=1: the ring kernel on 128 x 256 tiles, two workgroups per CU (A/B runs; stage-2 chunks of 4096-32767 queries take them anyway)
     int knn_splits = 0;          // env ISMHIP_KNN_SPLITS: force the number of codebook splits of the squared-L2 candidate kernels (A/B runs)
+    int knn_split_major = -1;    // env ISMHIP_KNN_SPLIT_MAJOR = 0 | 1: the ring kernel's block -> (query tile, split) map with the split as the fast / slow index for every launch (A/B runs; default: knn_plan's rule)
     int knn_t = 0;               // env ISMHIP_KNN_T = 1 | 2 | 3: candidates kept per slot (default 4 on the 16-bit paths); fewer = cheaper epilogue, more unproven slots
     bool xcd_map = true;         // env ISMHIP_XCD_MAP=0: per-object kernels on the plain object-major block order instead of the XCD-local map (A/B runs)
     bool grid_fused = true;      // env ISMHIP_GRID_FUSED=0: ismhip_cloud_create on the five-kernel grid build instead of one workgroup per object (A/B runs, tests; same bytes)

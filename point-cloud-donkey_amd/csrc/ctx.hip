@@ -80,6 +80,7 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     { const char* e = getenv("ISMHIP_KNN_HALF"); ctx->knn_half = e && e[0] == '1'; }
     { const char* e = getenv("ISMHIP_KNN_SPLITS"); ctx->knn_splits = e ? atoi(e) : 0; }
     { const char* e = getenv("ISMHIP_KNN_T"); ctx->knn_t = e ? atoi(e) : 0; }
+    { const char* e = getenv("ISMHIP_KNN_SPLIT_MAJOR"); ctx->knn_split_major = e ? (atoi(e) != 0) : -1; }
     { const char* e = getenv("ISMHIP_KNN_HELL_EMIT"); ctx->knn_hell_emit = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_HELLINGER"); ctx->knn_hellinger = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KNN_T1"); if (e) ctx->knn_t1 = atoi(e); }

@@ -219,6 +219,7 @@ int knn_launch_candidates(KnnRun& r) {
         a.tiles_per_split = p.tiles_per_split; a.n_splits = p.n_splits;
         a.cand_val = r.cand_val; a.cand_idx = r.cand_idx; a.cand_stride = r.n_cand; a.cand_bound = r.cand_bound; a.bound_stride = r.n_bound;
         a.qrange = p.ranged ? r.rq->ranged->qrange : nullptr;
+        a.split_major = p.split_major;
         int rc = ISMHIP_OK;
         if (p.cand == KNN_CAND_RING16) {
             rc = ism_lds_cap(ctx, p.kern, p.lds_cap);
@@ -300,6 +301,13 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
     p.BN = !l2 ? CHI_B : (p.big_tile ? 256 : KNN_BN);
     p.slots = ring && !p.half ? 8 : 4;                                 // 16x16x32 MFMA shape: 8 lane slots per query and split
     p.n_qt = (nq + p.BN - 1) / p.BN;
+    // The ring kernel's block -> (query tile, split) map: with the split as the SLOW index of an XCD's queue the workgroups resident on
+    // the XCD sweep one split, 32 on one joined codeword stream instead of 32 / n_splits on each of n_splits streams, and a codeword
+    // tile comes from beyond the L2 once for all of them. Only where the query panel is resident in LDS: the other ring kernels re-read
+    // their query tile from the L2 for every codeword tile and want FEW query tiles per XCD, which is what the split as the fast index
+    // gives them (measured with the map forced on everywhere, bench configuration 4: stage 1 117.9 -> 118.1 ms, its ranged stage 2 13.27 -> 13.63).
+    // Bench launch, two splits: stage 1 23.97 -> 23.23 ms; four splits: 25.51 -> 23.96.
+    p.split_major = ctx->knn_split_major >= 0 ? ctx->knn_split_major != 0 : p.qpanel2;
     // (a ranged search plans for its longest range, and keeps a tile for every split of its shortest)
     p.ranged = rq.ranged && l2 && use_lp;
     const int n_mt = (p.ranged ? rq.ranged->rows_max : cb->n_words_pad) / p.BM;
@@ -311,7 +319,14 @@ KnnPlan knn_plan(const ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, i
         // beyond the L2 (joined streams); four are 1.5 % slower
         // (stage 1 on the rotated image: two -- with 4-6 slices per tile the epilogue is a larger share of the kernel, and every split
         // is another eight candidate lists per query to fill: 29.8 -> 28.1 ms per bench launch)
-        p.n_splits = std::max(1, std::min(std::min(max_s, n_mt), std::max(p.pca ? 2 : 3, (1024 + p.n_qt - 1) / p.n_qt)));
+        int want = std::max(p.pca ? 2 : 3, (1024 + p.n_qt - 1) / p.n_qt);
+        // (... on the split-major map (above): FOUR wherever filling the chip asks for more than two. A proof fails per split, so stage 2
+        // searches a quarter of the rows per failed entry and fewer queries fail at all. 114-object shard of the bench, 454 query
+        // tiles, ms per step: three splits 6.91 / 6.97, four 6.87 / 6.85, two 7.78 / 7.71. Not the full launch of 3 632 query tiles: two
+        // splits 44.56 / 44.57, three 44.94 / 44.78, four 44.62 / 44.51 -- stage 2 and the scan give back 0.85 ms, the second set of
+        // workgroup prologues, candidate lists and re-rank candidates takes 0.85: it stays at two. DESIGN §5 "Stage 1 on four splits")
+        if (p.pca && p.split_major && want > 2) want = 4;
+        p.n_splits = std::max(1, std::min(std::min(max_s, n_mt), want));
         // ... as long as a workgroup still has a few dozen tiles to amortise its prologue over (10 k-word codebook, 40 tiles: 1 / 2 / 3
         // splits = 3.81 / 4.18 / 4.51 ms) and the launch fills the chip without them
         if (p.big_tile && p.n_qt >= 512) p.n_splits = std::min(p.n_splits, std::max(1, n_mt / 32));

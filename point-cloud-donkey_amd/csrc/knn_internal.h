@@ -257,7 +257,7 @@ struct KnnPlan {
     KnnCand cand;
     const void* kern;           // KNN_CAND_MFMA16 / KNN_CAND_RING16: the kernel instance (nullptr: not built)
     int BM, BN, threads;        // codeword rows and queries per tile, threads per workgroup
-    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join, ranged;
+    bool big_tile, half, qpanel2, pca, merged, prepass, seeded, join, ranged, split_major;
     int slots, ring_nk;         // lane slots per codebook split (squared L2), 32-k slices per row of the tiled images
     int n_qt, n_splits, tiles_per_split, cand_per_split, n_cand, n_bound;
     int fb_tiles_per_split; KnnFbLayout fb_layout;   // exact scan: tiles per slot's split and the slot -> rows layout
@@ -314,6 +314,7 @@ struct KnnCandArgs {
     const u16 *qh, *ql; int nq; const float* out_scale; int tiles_per_split, n_splits;
     float* cand_val; int* cand_idx; int cand_stride; float* cand_bound; int bound_stride;
     const int* qrange;      // ranged search (knn_range_split), else nullptr: every query sweeps the tiles [0, n_tiles_m)
+    int split_major;        // ring kernel: the split is the slow index of the block -> (query tile, split) map (KnnPlan::split_major)
 };
 // A RANGED search (stage 2 of the two-stage search on per-split failure lists, knn_two_stage.hip): the queries come in groups of 256 and group
 // g sweeps only the codeword rows [qrange[4 g], qrange[4 g + 1]) (multiples of 256); qrange[4 g + 2] = the list the group belongs to,

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int cand_stride,
                                                           float* __restrict__ cand_bound, int bound_stride, unsigned int* __restrict__ stream_clock,
                                                           const float* __restrict__ thr_init, float* __restrict__ thr_out, int tile_step, float thr_relax,
-                                                          const int* __restrict__ qrange) {
+                                                          const int* __restrict__ qrange, int split_major) {
     using L = Ring16Lds<WR, QP>;
     constexpr int WC = 4, MT = 8, NT = 4, KB = RG_KB, BM = WR * 128, BN = RG_BN;
     constexpr int STAGES = L::STAGES, STAGE_HALVES = L::STAGE_HALVES, CNS = 256;
@@ -114,8 +114,12 @@ __global__ __launch_bounds__(WR * 256, 2) void k_knn_l2_ring16(const u16* __rest
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // wave-uniform values must live in SGPRs (DMA bases, ring pointers)
     const int wr = wv / WC, wc = wv % WC;
     const int fr = lane & 15, fq = lane >> 4;
+    // Workgroups go to the XCDs round-robin and start in the order of jx within one. split_major: the split is the SLOW index of an
+    // XCD's queue, so the workgroups resident on it at the same time (32, or 64 of WR = 1) sweep the same split and share ONE codeword
+    // stream in its L2 instead of n_splits streams of 1 / n_splits as many workgroups each. The result does not depend on the order.
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int split = jx % n_splits, qtile = (jx / n_splits) * 8 + xcd;
+    const int n_jq = (int)(gridDim.x >> 3) / n_splits;
+    const int split = split_major ? jx / n_jq : jx % n_splits, qtile = (split_major ? jx % n_jq : jx / n_splits) * 8 + xcd;
     if (qtile * BN >= nq) return;
     int mt0 = split * tiles_per_split, mt1 = min(n_tiles_m, mt0 + tiles_per_split);
     int clk_slot = xcd * n_splits + split;
@@ -460,14 +464,14 @@ int knn_ring16_launch(ismhip_ctx* ctx, int T, const void* kern, unsigned grid, i
         const size_t plds = Ring16Lds<2, 0>::total(0);
         const int rc2 = ism_lds_cap(ctx, pk, plds);
         if (rc2 != ISMHIP_OK) return rc2;
-        int one = 1, all = a.n_tiles_m; unsigned int* noclk = nullptr; const float* noinit = nullptr; const int* norange = nullptr;
-        void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax, &norange};
+        int one = 1, all = a.n_tiles_m, no_major = 0; unsigned int* noclk = nullptr; const float* noinit = nullptr; const int* norange = nullptr;
+        void* pargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &all, &one, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &noclk, &noinit, &thr0, &pre_step, &pre_relax, &norange, &no_major};
         ISM_HIP(ctx, hipLaunchKernel(pk, dim3(grid / a.n_splits), dim3(512), pargs, plds, ctx->stream));      // one split: a workgroup per query tile
         ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16<pre>");
     }
     thr_init = thr0;
     float no_relax = 0.f;
-    void* rargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &stream_clock, &thr_init, &thr_out, &tile_step, &no_relax, &a.qrange};
+    void* rargs[] = {&a.wh, &a.word_norm, &a.n_tiles_m, &a.ld, &a.k_steps, &a.qh, &a.nq, &a.out_scale, &a.tiles_per_split, &a.n_splits, &a.cand_val, &a.cand_idx, &a.cand_stride, &a.cand_bound, &a.bound_stride, &stream_clock, &thr_init, &thr_out, &tile_step, &no_relax, &a.qrange, &a.split_major};
     ISM_HIP(ctx, hipLaunchKernel(kern, dim3(grid), dim3(threads), rargs, lds, ctx->stream));
     ISM_CHECK_LAUNCH(ctx, "k_knn_l2_ring16");
     return ISMHIP_OK;
