@@ -76,6 +76,7 @@ extern "C" {
 #define ISMHIP_SPIN_IMAGE_DIM 153   /* (8 + 1) * (2 * 8 + 1) */
 #define ISMHIP_RSD_DIM 25           /* ismhip_rsd, full_histogram: 5 angle bins x 5 distance bins */
 #define ISMHIP_RSD_RADII_DIM 2      /* ismhip_rsd without it: the two principal radii */
+#define ISMHIP_VFH_DIM 308          /* ismhip_global_vfh: 4 shape blocks of 45 bins + 128 viewpoint bins */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -96,7 +97,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -383,6 +384,28 @@ int  ismhip_global_short_shot(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_
  * Timer "global_shot352". */
 int  ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
                            const float* region_radius, uint32_t* n_sel_out, float* centroid_out, float* radius_out, float* lrf9_out, float* desc_out);
+/* ismhip_global_vfh: FeaturesVFH::iComputeDescriptors (features/features_vfh.cpp:27-70): pcl::VFHEstimation over the region with
+ * setNormalizeBins(true), setNormalizeDistance(false), the size component off and the viewpoint the caller's (the reference leaves PCL's
+ * (0, 0, 0)). PCL is external: this is the library's own statement of PCL 1.10 vfh.hpp (DESIGN.md section 4.17 names the deviations).
+ * Region, n_sel, centroid c and radius are those of the two entries above, bit for bit on the same regions; there is NO frame.
+ * normal_centroid_out[n_regions*3]: nc = (float)(sum / m) per component over the m selected points whose normal is finite, double sums in
+ * a fixed order, NOT normalised. m < 2: NaN row. View direction d = viewpoint - c in float, divided by its float norm (a zero norm
+ * leaves d = 0). desc_out[n_regions*308] from INTEGER counts (count_out: device [n_regions*308] or NULL):
+ *   bins 0..179, four blocks of 45: every selected point p with a finite normal n is evaluated with pcl::computePairFeatures(c, nc, p, n)
+ *     in float (the arithmetic of ismhip_fpfh33's exact path); a pair it rejects (f4 == 0 or a zero cross product) deposits nothing here.
+ *     From the float features, in double: b1 = floor(45 * ((f1 + M_PI) * dpi)), dpi = (double)(1.0f / (2.0f * (float)M_PI));
+ *     b2 = floor(45 * ((f2 + 1.0) * 0.5)); b3 likewise from f3; b4 = floor((double)(f4 * 100.0f) + 0.5), f4 = |p - c| in float (hundredths
+ *     of a unit, not normalised); each clamped to [0, 44]; a NaN feature deposits nothing.
+ *   bins 180..307, the viewpoint block: every selected point with a finite normal (its pair rejected or not):
+ *     floor((((double)(float)dot(n, d) + 1.0) * 0.5) * 128.0) clamped to [0, 127].
+ *   row: blocks f1..f3 (float)((double)count * (double)incr), incr = 100.0f / (float)(m - 1) in float; block f4 all zeros unless
+ *     fill_size_component (then as f1..f3; its counts are reported either way); viewpoint block (float)((double)count *
+ *     (double)(float)(100.0 / (double)m)). One product per bin: order-free, the same bits on every call.
+ * n_sel = 0: NaN centroid, radius 0, NaN normal centroid, NaN row. viewpoint: HOST float[3]; a non-finite one is ISMHIP_ERR_INVALID.
+ * Otherwise checked as the two entries above. Timer "global_vfh". */
+int  ismhip_global_vfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                       const float* region_radius, const float viewpoint[3], int fill_size_component, uint32_t* n_sel_out, float* centroid_out,
+                       float* radius_out, float* normal_centroid_out, float* desc_out, uint32_t* count_out);
 
 /* ---- keypoints (the step in front of the path): KeypointsVoxelGrid::iComputeKeypoints
  *      (keypoints/keypoints_voxel_grid.cpp:30-46) -> pcl::VoxelGrid<PointXYZRGB> with a cubic leaf. Per object the

@@ -33,7 +33,7 @@ EXPORTS = [
     "ismhip_codebook_set_word_keypoint", "ismhip_vote_keypoints", "ismhip_vote_keypoints_csr", "ismhip_ransac_filter", "ismhip_ransac_hypothesis",
     "ismhip_find_maxima_ransac", "ismhip_hough3d_maxima_ransac", "ismhip_short_shot", "ismhip_short_cshot", "ismhip_cospair",
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
-    "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352",
+    "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352", "ismhip_global_vfh",
     "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
 ]
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
@@ -506,6 +506,24 @@ def global_shot352(ctx, cloud, dev, region_obj, region_center=None, region_radiu
     out = _global_outputs(n, 352, dev)
     ctx.check(lib().ismhip_global_shot352(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), _p(out["n_sel"]), _p(out["centroid"]),
                                           _p(out["radius"]), _p(out["lrf"]), _p(out["desc"])), "ismhip_global_shot352")
+    return out
+
+
+def global_vfh(ctx, cloud, dev, region_obj, region_center=None, region_radius=None, viewpoint=(0.0, 0.0, 0.0), fill_size_component=False,
+               want_counts=False):
+    """ismhip_global_vfh on regions as global_short_shot -> dict of device tensors n_sel [n], centroid [n, 3], radius [n], normal_centroid
+    [n, 3], desc [n, 308] and, with want_counts, counts [n, 308] (int32); there is no frame"""
+    torch = _torch()
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    out = _global_outputs(n, 308, dev)
+    del out["lrf"]
+    out["normal_centroid"] = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if want_counts:
+        out["counts"] = torch.empty_like(out["desc"], dtype=torch.int32)
+    vp = (C.c_float * 3)(*[float(v) for v in viewpoint])
+    ctx.check(lib().ismhip_global_vfh(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vp, C.c_int(1 if fill_size_component else 0),
+                                      _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["normal_centroid"]), _p(out["desc"]),
+                                      _p(out.get("counts"))), "ismhip_global_vfh")
     return out
 
 

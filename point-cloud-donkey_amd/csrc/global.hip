@@ -21,9 +21,11 @@
 // Byte model per region: 5 sweeps x 16 B x n_obj_points (6 for SHOT-352: + 16 B per descriptor neighbour for its normal), the first
 // from HBM, the later ones from L2 when the object's span fits (a 16 384-point object: 256 KiB); a tie adds ~50 sweeps from L2.
 // One region per workgroup: a region of a very large object is not split over several workgroups.
+// k_vfh (further down) is the frame-free third descriptor on the same regions: ismhip_global_vfh.
 #include "shot_deposit.h"
 #include "lrf_common.h"
 #include "eigen3.h"
+#include "pair_features.h"
 
 namespace {
 
@@ -305,6 +307,174 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
     }
 }
 
+// ---- VFH (features/features_vfh.cpp:27-70 -> pcl::VFHEstimation, PCL 1.10 vfh.hpp restated in include/ismhip.h) ----------------------
+// The same region, count, centroid and radius as k_global (steps 1 and 2, the same arithmetic: bit-equal outputs), but NO frame: the
+// pair (centroid, normal centroid) against every selected point with a finite normal, pair_features.h's exact evaluation, four 45-bin
+// blocks and a 128-bin viewpoint block of INTEGER counts. Sweeps: count + centroid (skipped for a whole object), radius fused with the
+// normal sums (32 B per point: position and normal), histogram (32 B per point). Byte model per whole-object region: 64 B x n.
+// A 45-bin block -- and a viewpoint block that a planar patch drives into ONE bin -- is the same-address case of the short histogram
+// above: each wave owns VFH_COPIES copies of the 308 bins, lane l counts in copy l % VFH_COPIES; integers, so the merge is exact.
+#define VFH_COPIES 8
+#define VFH_SHAPE_BINS 45
+#define VFH_VP_BINS 128
+
+struct VfhArgs {
+    const uint32_t* pt_off; const GridMeta* meta;
+    const float4 *sp4, *sn4;
+    int n_obj;
+    const int32_t* reg_obj; const float* reg_center; const float* reg_radius;
+    float vpx, vpy, vpz; int fill_size;
+    uint32_t* n_sel; float* centroid; float* radius; float* ncen; float* desc; uint32_t* counts;
+};
+
+struct VfhSmem {
+    double red_d[4];
+    uint32_t red_u[4];
+    float red_f[4];
+    uint32_t cnt[4 * VFH_COPIES * ISMHIP_VFH_DIM];
+};
+
+// floor(v) clamped to [0, last] as a bin index; -1 for a NaN (no deposit). The clamp is taken in double: no int conversion of a
+// value outside int.
+__device__ __forceinline__ int vfh_bin(double v, int last) {
+    if (!(v == v)) return -1;
+    v = floor(v);
+    return v < 0.0 ? 0 : (v > (double)last ? last : (int)v);
+}
+
+// One sweep of a region's span, position and normal of each record, in the order i = tid, tid + 256, ... per thread (the order of
+// the double sums). The loop of k_global issues one load and waits for it, ~64 dependent round trips per sweep of a 16 384-point
+// object with one wave per SIMD; here four records' eight loads are issued before the first is used.
+template <class F>
+__device__ __forceinline__ void vfh_sweep(const float4* __restrict__ sp, const float4* __restrict__ sn, uint32_t n, int tid, F&& f) {
+    for (uint32_t i0 = tid; i0 < n; i0 += 4 * 256) {
+        float4 p[4], nr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t i = (uint64_t)i0 + 256u * j;                          // past the end: a record that is there, not used
+            p[j] = sp[i < n ? i : i0]; nr[j] = sn[i < n ? i : i0];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if ((uint64_t)i0 + 256u * j < n) f(p[j], nr[j]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
+    __shared__ VfhSmem sm;
+    constexpr int D = ISMHIP_VFH_DIM;
+    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    const uint32_t reg = blockIdx.x;
+    const float qnan = __builtin_nanf("");
+    float* row = a.desc + (size_t)reg * D;
+    uint32_t* crow = a.counts ? a.counts + (size_t)reg * D : nullptr;
+    auto nan_row = [&]() { for (int i = tid; i < D; i += 256) { row[i] = qnan; if (crow) crow[i] = 0u; } };
+
+    // ---- the region: as k_global ---------------------------------------------------------------------------------------------------
+    const int o = a.reg_obj[reg];
+    const bool obj_ok = o >= 0 && o < a.n_obj;
+    uint32_t base = 0, n = 0;
+    GridMeta m{};
+    if (obj_ok) {
+        m = a.meta[o];
+        base = a.pt_off[o];
+        const uint32_t npts = a.pt_off[o + 1] - base;
+        n = m.n_finite < npts ? m.n_finite : npts;            // the sorted span holds the finite points first
+    }
+    const float qx = a.reg_center[reg * 3], qy = a.reg_center[reg * 3 + 1], qz = a.reg_center[reg * 3 + 2];
+    const float rs = a.reg_radius[reg];
+    const bool whole = rs < 0.f;
+    const float r2s = (float)((double)rs * (double)rs);
+    const float4* sp = a.sp4 + base;
+    const float4* sn = a.sn4 + base;
+    auto selected = [&](const float4& p) { return whole || sqdist3(p.x, p.y, p.z, qx, qy, qz) < r2s; };
+
+    // ---- 1. count and centroid: k_global's step 1 ---------------------------------------------------------------------------------
+    uint32_t nsel; float cx, cy, cz;
+    if (whole) {
+        nsel = n; cx = m.centroid[0]; cy = m.centroid[1]; cz = m.centroid[2];
+    } else {
+        uint32_t c = 0; double sx = 0, sy = 0, sz = 0;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const float4 p = sp[i];
+            if (selected(p)) { sx += (double)p.x; sy += (double)p.y; sz += (double)p.z; c++; }
+        }
+        nsel = block_sum_i(c, sm.red_u);
+        sx = block_sum_d_left(sx, sm.red_d); sy = block_sum_d_left(sy, sm.red_d); sz = block_sum_d_left(sz, sm.red_d);
+        cx = (float)(sx / (double)nsel); cy = (float)(sy / (double)nsel); cz = (float)(sz / (double)nsel);
+    }
+    if (tid == 0) a.n_sel[reg] = nsel;
+    if (nsel == 0) {                                          // workgroup-uniform
+        if (tid < 3) { a.centroid[reg * 3 + tid] = qnan; a.ncen[reg * 3 + tid] = qnan; }
+        if (tid == 0) a.radius[reg] = 0.f;
+        nan_row();
+        return;
+    }
+    if (tid == 0) { a.centroid[reg * 3] = cx; a.centroid[reg * 3 + 1] = cy; a.centroid[reg * 3 + 2] = cz; }
+
+    // ---- 2. radius (k_global's step 2) and the normal centroid: double sums over the finite normals, fixed order ------------------------
+    float R = 0.f;
+    uint32_t mt = 0; double snx = 0, sny = 0, snz = 0;
+    vfh_sweep(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
+        if (!selected(p)) return;
+        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+        if (d > R) R = d;
+        if (isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z)) { snx += (double)nr.x; sny += (double)nr.y; snz += (double)nr.z; mt++; }
+    });
+    R = block_max_f(R, sm.red_f);
+    const uint32_t mfin = block_sum_i(mt, sm.red_u);
+    snx = block_sum_d_left(snx, sm.red_d); sny = block_sum_d_left(sny, sm.red_d); snz = block_sum_d_left(snz, sm.red_d);
+    const float ncx = (float)(snx / (double)mfin), ncy = (float)(sny / (double)mfin), ncz = (float)(snz / (double)mfin);   // m = 0: NaN
+    if (tid == 0) {
+        a.radius[reg] = R;
+        a.ncen[reg * 3] = ncx; a.ncen[reg * 3 + 1] = ncy; a.ncen[reg * 3 + 2] = ncz;
+    }
+    if (mfin < 2u) { nan_row(); return; }                     // workgroup-uniform
+
+    // ---- the view direction: (viewpoint - centroid) / |.| in float; a zero norm leaves 0 ----------------------------------------------
+    float vdx = a.vpx - cx, vdy = a.vpy - cy, vdz = a.vpz - cz;
+    const float vn = sqrtf((vdx * vdx + vdy * vdy) + vdz * vdz);
+    if (vn != 0.0f) { vdx /= vn; vdy /= vn; vdz /= vn; }
+
+    // ---- 3. the histogram ----------------------------------------------------------------------------------------------------------------
+    for (int i = tid; i < 4 * VFH_COPIES * D; i += 256) sm.cnt[i] = 0u;
+    __syncthreads();
+    uint32_t* hist = sm.cnt + (wv * VFH_COPIES + (lane % VFH_COPIES)) * D;
+    const double dpi = (double)(1.0f / (2.0f * (float)M_PI));
+    vfh_sweep(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
+        if (!selected(p)) return;
+        if (!(isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z))) return;
+        // viewpoint block: every such point, whatever becomes of its pair
+        const float dv = (nr.x * vdx + nr.y * vdy) + nr.z * vdz;
+        const int bv = vfh_bin((((double)dv + 1.0) * 0.5) * (double)VFH_VP_BINS, VFH_VP_BINS - 1);
+        if (bv >= 0) atomicAdd(&hist[4 * VFH_SHAPE_BINS + bv], 1u);
+        // shape blocks: computePairFeatures(centroid, normal centroid, p, n); f4 is its own first expression
+        float f1, f2, f3;
+        if (!pair_features(cx, cy, cz, ncx, ncy, ncz, p.x, p.y, p.z, nr.x, nr.y, nr.z, f1, f2, f3)) return;
+        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+        const float f4 = sqrtf((dx * dx + dy * dy) + dz * dz);
+        const int b1 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f1 + M_PI) * dpi), VFH_SHAPE_BINS - 1);
+        const int b2 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f2 + 1.0) * 0.5), VFH_SHAPE_BINS - 1);
+        const int b3 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f3 + 1.0) * 0.5), VFH_SHAPE_BINS - 1);
+        const int b4 = vfh_bin((double)(f4 * 100.0f) + 0.5, VFH_SHAPE_BINS - 1);
+        if (b1 >= 0) atomicAdd(&hist[b1], 1u);
+        if (b2 >= 0) atomicAdd(&hist[VFH_SHAPE_BINS + b2], 1u);
+        if (b3 >= 0) atomicAdd(&hist[2 * VFH_SHAPE_BINS + b3], 1u);
+        if (b4 >= 0) atomicAdd(&hist[3 * VFH_SHAPE_BINS + b4], 1u);
+    });
+    __syncthreads();
+    // counts -> row: one product per bin (order-free); the distance block stays zero unless the size component is asked for
+    const float incr = 100.0f / (float)(mfin - 1u);
+    const double incr_shape = (double)incr, incr_vp = (double)(float)(100.0 / (double)mfin);
+    for (int b = tid; b < D; b += 256) {
+        uint32_t c = 0;
+        for (int k = 0; k < 4 * VFH_COPIES; ++k) c += sm.cnt[k * D + b];
+        if (crow) crow[b] = c;
+        const bool size_block = b >= 3 * VFH_SHAPE_BINS && b < 4 * VFH_SHAPE_BINS;
+        row[b] = (size_block && !a.fill_size) ? 0.f : (float)((double)c * (b < 4 * VFH_SHAPE_BINS ? incr_shape : incr_vp));
+    }
+}
+
 int global_check(ismhip_ctx* ctx, const char* name, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
                  const float* region_radius, const uint32_t* n_sel_out, const float* centroid_out, const float* radius_out, const float* lrf9_out,
                  const float* desc_out) {
@@ -360,6 +530,27 @@ int ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regi
     TimerScope ts(ctx, "global_shot352");
     hipLaunchKernelGGL(k_global<true>, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_global<shot352>");
+    return ISMHIP_OK;
+}
+
+int ismhip_global_vfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                      const float* region_radius, const float viewpoint[3], int fill_size_component, uint32_t* n_sel_out, float* centroid_out,
+                      float* radius_out, float* normal_centroid_out, float* desc_out, uint32_t* count_out) {
+    // global_check's rules; there is no frame: the normal centroid is the fourth per-region output it asks for
+    int rc = global_check(ctx, "global_vfh", cloud, n_regions, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out,
+                          normal_centroid_out, desc_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (!viewpoint || !(std::isfinite(viewpoint[0]) && std::isfinite(viewpoint[1]) && std::isfinite(viewpoint[2])))
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_vfh: the viewpoint is not finite");
+    if (n_regions == 0) return ISMHIP_OK;
+    VfhArgs a{};
+    a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.sp4 = cloud->sp4; a.sn4 = cloud->sn4; a.n_obj = cloud->n_obj;
+    a.reg_obj = region_obj; a.reg_center = region_center; a.reg_radius = region_radius;
+    a.vpx = viewpoint[0]; a.vpy = viewpoint[1]; a.vpz = viewpoint[2]; a.fill_size = fill_size_component ? 1 : 0;
+    a.n_sel = n_sel_out; a.centroid = centroid_out; a.radius = radius_out; a.ncen = normal_centroid_out; a.desc = desc_out; a.counts = count_out;
+    TimerScope ts(ctx, "global_vfh");
+    hipLaunchKernelGGL(k_vfh, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
+    ISM_CHECK_LAUNCH(ctx, "k_vfh");
     return ISMHIP_OK;
 }
 

@@ -203,6 +203,12 @@ int ism3d_global_features_get(void* m, int* dim_out, int* n_clouds_out, uint32_t
         if (n_clouds_out) *n_clouds_out = clouds;
         return n;)
 }
+// the row length of the configured GlobalFeatures type; 0 when the child is a pass-through (no built type)
+int ism3d_global_descriptor_length(void* m) {
+    GUARD(
+        const GlobalFeatures* g = ((ImplicitShapeModel*)m)->getGlobalFeatures();
+        return g ? g->getDescriptorLength() : 0;)
+}
 // installs stored global features from flat arrays, one training cloud per row (persistence tests without a GPU)
 int ism3d_global_features_set(void* m, int n, int dim, const uint32_t* cls, const uint32_t* inst, const float* rf9, const float* desc, const float* radius) {
     GUARD(

@@ -962,7 +962,7 @@ bool Codebook::load(BoostBinaryIArchive& ia) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Global descriptors (features/features_short_shot_global.cpp, features_shot_global.cpp) on regions of the batch's search surface
+// Global descriptors (features/features_short_shot_global.cpp, features_shot_global.cpp, features_vfh.cpp) on regions of the batch's search surface
 // ---------------------------------------------------------------------------------------------------------------
 struct GlobalRegions {
     int n = 0, dim = 0;
@@ -1013,6 +1013,14 @@ void GlobalFeaturesShot::describe(DeviceSession& s, GlobalRegions& r) const {
     s.check(ismhip_global_shot352(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), r.n_sel.as<uint32_t>(), r.centroid.as<float>(),
                                   r.radius.as<float>(), r.lrf.as<float>(), r.desc.as<float>()), "ismhip_global_shot352");
 }
+void GlobalFeaturesVFH::describe(DeviceSession& s, GlobalRegions& r) const {
+    const float viewpoint[3] = {0.f, 0.f, 0.f};                                       // PCL's default, which features_vfh.cpp leaves
+    DevBuf ncen; ncen.reserve(std::max<size_t>((size_t)r.n, 1) * 12);
+    s.check(ismhip_global_vfh(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), viewpoint, 0, r.n_sel.as<uint32_t>(),
+                              r.centroid.as<float>(), r.radius.as<float>(), ncen.as<float>(), r.desc.as<float>(), nullptr), "ismhip_global_vfh");
+    DeviceSession::h2d(r.lrf, std::vector<float>((size_t)r.n * 9, 0.f));             // VFH has no frame: the stored rf of a row is zeros
+    s.sync();                                                                         // ncen is released on return
+}
 GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     if (!object.isObject()) return nullptr;
     const Json* t = object.find("Type");
@@ -1020,6 +1028,7 @@ GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     GlobalFeatures* g = nullptr;
     if (t->str == GlobalFeaturesShortShot::getTypeStatic()) g = new GlobalFeaturesShortShot();
     else if (t->str == GlobalFeaturesShot::getTypeStatic()) g = new GlobalFeaturesShot();
+    else if (t->str == GlobalFeaturesVFH::getTypeStatic()) g = new GlobalFeaturesVFH();
     if (!g) return nullptr;
     try { if (!g->configFromJson(object)) throw RuntimeException("could not create object of type: \"" + t->str + "\""); }
     catch (...) { delete g; throw; }

@@ -3,11 +3,12 @@ Workload: --objects skewed blobs of --points points each (tests/global_scenes.bl
 cloud in the same process, device events (the library timers), --warmup runs, then --reps repetitions of
   ismhip_global_short_shot   timer "global_short_shot" (2 x 2 x 8 bins)
   ismhip_global_shot352      timer "global_shot352"
+  ismhip_global_vfh          timer "global_vfh" (viewpoint (0, 0, 0), size component off)
   the per-keypoint route     timers "lrf" + "shot352": ismhip_shot_lrf + ismhip_shot352 with ONE keypoint per object at its centroid and
                              the batch's LARGEST radius -- the only way the per-keypoint entries reach the same neighbourhood (they take
                              one radius per call); its rows equal the region rows only for the object that has that radius
 reported as median [min .. max] milliseconds, with the bytes one region streams by the model of csrc/global.hip (16 B per point and
-sweep, 5 sweeps, 6 + normals for SHOT-352) and the share of the HBM peak (--peak-gbs) those bytes would be at the measured time. The
+sweep, 5 sweeps, 6 + normals for SHOT-352; VFH: 2 sweeps of a whole object, each with the 16 B normal beside the 16 B position) and the share of the HBM peak (--peak-gbs) those bytes would be at the measured time. The
 outputs of the repetitions are compared bit for bit.
 
     python tools/global_time.py [--objects 256] [--points 16384] [--reps 20] [--warmup 3]
@@ -75,6 +76,7 @@ def main():
     g = timed("global_short_shot", ("global_short_shot",),
               lambda: list(capi.global_short_shot(ctx, cloud, dev, regions, bins=(2, 2, 8)).values()))
     timed("global_shot352", ("global_shot352",), lambda: list(capi.global_shot352(ctx, cloud, dev, regions).values()))
+    timed("global_vfh", ("global_vfh",), lambda: list(capi.global_vfh(ctx, cloud, dev, regions).values()))
     cen = capi.cloud_centroids(ctx, cloud, dev)
     rmax = float(capi.cloud_radii(ctx, cloud, cen).max())
     kp_off = np.arange(n_obj + 1, dtype=np.uint32)
@@ -86,7 +88,8 @@ def main():
     timed(f"per-keypoint route (one keypoint per object, radius {rmax:.3f})", ("lrf", "shot352"), per_keypoint)
     ctx.timers_enable(False)
 
-    for label, sweeps, extra in (("global_short_shot", 5, 0), ("global_shot352", 6, 16)):
+    # VFH on a whole object: radius + normal sums, histogram; each sweep reads position and normal
+    for label, sweeps, extra in (("global_short_shot", 5, 0), ("global_shot352", 6, 16), ("global_vfh", 2, 32)):
         b = n * (16 * sweeps + extra)
         gbs = b * n_obj / (results[label] * 1e-3) / 1e9
         print(f"{label}: {b} bytes streamed per region by the model ({sweeps} sweeps), {gbs:.1f} GB/s = {100 * gbs / args.peak_gbs:.2f} % of the HBM peak; "
