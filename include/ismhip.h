@@ -97,7 +97,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -441,6 +441,68 @@ int  ismhip_iss3d_saliency(ismhip_ctx* ctx, const ismhip_cloud* cloud, float sal
 int  ismhip_iss3d_keypoints(ismhip_ctx* ctx, const ismhip_cloud* cloud, float salient_radius, float non_max_radius, double gamma21, double gamma32,
                             int min_neighbors, uint32_t capacity, float* kx, float* ky, float* kz, uint32_t* krgba, uint32_t* src_index_out,
                             uint32_t* kp_offsets_h_out);
+
+/* ---- VoxelGridCulling keypoints: KeypointsVoxelGridCulling (keypoints/keypoints_voxel_grid_culling.cpp): the voxel-grid keypoints of
+ *      ismhip_voxel_keypoints at LeafSize, a geometry and a colour score per keypoint over its LeafSize ball of the search surface, and the
+ *      better-scoring share kept (restated in tests/culling_ref.py). PCL is external: where it decides the
+ *      arithmetic (normal curvature, principal curvatures) the definition is this library's own, written from knowledge of PCL 1.10; where
+ *      the reference's own source decides it (kpq, colour score, combined score, thresholds, acceptance) the text is followed as written.
+ *      Every ball: unfused float d2 STRICTLY below (float)((double)r * r), non-finite points are never neighbours. Every
+ *      order-dependent sum is taken on an integer grid: the same bits for any cell_size, lane mapping and run, and an object's results do
+ *      not depend on the other objects of the batch.
+ * ismhip_principal_curvatures (:136-153 -> pcl::PrincipalCurvaturesEstimation, dense): per surface point i with normal n, over its
+ * radius ball N (i included; a neighbour with a non-finite normal is skipped and not counted): v_j = n_j - n (n . n_j) in double from the
+ * float normals, c their mean, S = sum (v_j - c)(v_j - c)^T (not divided), eigenvalues l0 <= l1 <= l2; pc1 = (float)(l2 / |N|), pc2 =
+ * (float)(l1 / |N|). Normals need not be unit: the grid's scale comes from B (1 + B)^2 >= |v_j|^2, B the object's largest squared normal
+ * length (a per-object reduction). pc1_out, pc2_out: device float[n_pts], count_out: device uint32[n_pts] (|N|) or NULL, original point
+ * order; a point whose position or own normal is not finite: NaN, NaN, 0. radius not > 0: ISMHIP_ERR_INVALID. Timer "culling_pc".
+ * Asynchronous. */
+int  ismhip_principal_curvatures(ismhip_ctx* ctx, const ismhip_cloud* cloud, float radius, float* pc1_out, float* pc2_out, uint32_t* count_out);
+#define ISMHIP_CULLING_GEOMETRY_NONE 0
+#define ISMHIP_CULLING_GEOMETRY_CURVATURE 1
+#define ISMHIP_CULLING_GEOMETRY_KPQ 2
+#define ISMHIP_CULLING_COLOR_NONE 0
+#define ISMHIP_CULLING_COLOR_DISTANCE 1
+/* ismhip_culling_scores (getScoresForKeypoints :280-329): per keypoint k (kx|ky|kz|krgba: device, kp_offsets_h[n_obj+1] host ranges,
+ * object o's keypoints on object o of the cloud) one sweep over its `leaf` ball of n points fills
+ *   geometry CURVATURE (:156-194 -> pcl::NormalEstimation): n < 3: NaN; else C = sum (p - m)(p - m)^T / n about the neighbours' mean m
+ *     (sum d, sum d d^T about the keypoint on the grid, mean correction and eigen-solve in double), e3 its smallest eigenvalue:
+ *     (float)|e3 / trace(C)|, 0 when the trace is 0;
+ *   geometry KPQ (computeKPQ :441-471, as written): k1 = pc1, k2 = pc2 of the ball's points, K = k1 * k2 in float; max_k1, max_K from
+ *     FLT_MIN and min_k2, min_K from FLT_MAX by the comparisons as written (a NaN never updates them); the score, in float, left to right:
+ *     (1000.0f / num * num) * sum K + 100.0f * max_K + |100.0f * min_K| + 10 * max_k1 + |10 * min_k2|. sum K on the grid of the object's
+ *     largest finite |K|, rounded once to float; NaN when any K is NaN. n = 0: NaN. pc1, pc2: device float[n_pts], original order;
+ *   colour DISTANCE (computeColorScore :474-506): the keypoint's colour through RGB -> normalised CIELab is the reference; per ball point
+ *     the distance (|dL| + (|da| + |db|) / 2) / 3 in double from the float differences, clamped to [0, 1], as float;
+ *     (float)count(distance > max_similar_color_distance) / (float)n; n = 0: NaN. Needs a cloud with colours and krgba.
+ * A method NONE leaves its score 0. geo_out, color_out: device float[n_keypoints]; count_out: device uint32 (n) or NULL. A keypoint that
+ * is not finite has an empty ball. Errors: ISMHIP_ERR_INVALID. Timer "culling_scores". Asynchronous. */
+int  ismhip_culling_scores(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h, const float* kx, const float* ky, const float* kz,
+                           const uint32_t* krgba, float leaf, int geometry_method, int color_method, float max_similar_color_distance,
+                           const float* pc1, const float* pc2, float* geo_out, float* color_out, uint32_t* count_out);
+#define ISMHIP_CULLING_TYPE_CUTOFF 0
+#define ISMHIP_CULLING_TYPE_THRESHOLD 1
+#define ISMHIP_CULLING_REQUIRE_ONE 0
+#define ISMHIP_CULLING_REQUIRE_BOTH 1
+#define ISMHIP_CULLING_REQUIRE_COMBINED_LIST 2
+/* ismhip_culling_select (:331-340, computeThresholds :346-432, :204-272): per object, on its score lists g = geo, c = color (device):
+ *   combined = (g - gmin) / gmax + (c - cmin) / cmax in float (the division IS by the maximum), gmin / gmax the first smallest / largest
+ *     of the object's non-NaN scores (none: +inf / -inf);
+ *   a CUTOFF threshold of a method that is on: the element at index min((unsigned)(cutoff_ratio * (float)size), size - 1) of the list in
+ *     ascending order, NaN behind +inf, -0 and +0 equal, ties by index; a THRESHOLD type: the given value; the combined threshold exists
+ *     only when both methods are on and both types are CUTOFF. Every threshold that is not set stays FLT_MIN, as written;
+ *   a test passes iff !(score < threshold) (a NaN score passes); both methods on: combine = REQUIRE_ONE: geo || colour, REQUIRE_BOTH:
+ *     geo && colour, REQUIRE_COMBINED_LIST: the combined test; else geo && colour (a method that is off passes).
+ * The accepted keypoints go, in their order and with their colours, to kx_out|ky_out|kz_out[|krgba_out] (device, `capacity` entries, must
+ * not alias the inputs); kp_offsets_h_out[n_obj+1] (host) receives their ranges. keep_mask_out: device uint8[n_keypoints] or NULL;
+ * combined_out: device float[n_keypoints] or NULL; thresholds_out: device float[3 * n_obj] (geometry, colour, combined) or NULL. An
+ * object without keypoints gives an empty range (the reference's .at(0) throws there). Objects of any size. cutoff_ratio outside [0, 1),
+ * more than `capacity` accepted (nothing written): ISMHIP_ERR_INVALID. Timer "culling_select". The call synchronises. */
+int  ismhip_culling_select(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offsets_h, const float* geo, const float* color, int geometry_on, int color_on,
+                           int geometry_type, int color_type, float geometry_threshold, float color_threshold, float cutoff_ratio, int combine,
+                           const float* kx, const float* ky, const float* kz, const uint32_t* krgba, uint32_t capacity, float* kx_out, float* ky_out,
+                           float* kz_out, uint32_t* krgba_out, uint8_t* keep_mask_out, float* combined_out, float* thresholds_out,
+                           uint32_t* kp_offsets_h_out);
 
 /* ---- feature filtering: Features::operator() drops non-finite LRFs (features.cpp:66-76),
  *      ImplicitShapeModel::removeNaNFeatures drops NaN descriptors (implicit_shape_model.cpp:1276-1308).

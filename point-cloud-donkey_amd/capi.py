@@ -35,7 +35,13 @@ EXPORTS = [
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352", "ismhip_global_vfh",
     "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
+    "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select",
 ]
+# KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
+CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
+CULLING_COLOR = {"none": 0, "colordistance": 1}
+CULLING_TYPE = {"cutoff": 0, "threshold": 1}
+CULLING_COMBINE = {"RequireOne": 0, "RequireBoth": 1, "RequireCombinedList": 2}
 RANSAC_MAX_ITERATIONS = 10000      # corr_rejector.setMaximumIterations (voting.cpp:398)
 RANSAC_SEED = 12345                # PCL seeds mt19937(12345) per cluster; the draws themselves are this library's
 
@@ -684,6 +690,89 @@ def iss3d_keypoints(ctx, cloud, salient_radius, non_max_radius, gamma21=0.975, g
                                            C.c_int(min_neighbors), C.c_uint32(cap), _p(kx), _p(ky), _p(kz), _p(kc), _p(src), _p(ko)), "ismhip_iss3d_keypoints")
     m = int(ko[-1])
     return ko, kx[:m], ky[:m], kz[:m], (kc[:m] if kc is not None else None), src[:m]
+
+
+def principal_curvatures(ctx, cloud, radius, want_counts=True):
+    """ismhip_principal_curvatures: returns (pc1 float32[n_pts], pc2 float32[n_pts], counts int32[n_pts] or None) in the cloud's original
+    point order; NaN, NaN, 0 where the position or the point's own normal is not finite"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    pc1 = torch.zeros((n,), dtype=torch.float32, device=dev); pc2 = torch.zeros_like(pc1)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_principal_curvatures(ctx._h, cloud._h, C.c_float(radius), _p(pc1), _p(pc2), _p(cnt)), "ismhip_principal_curvatures")
+    return pc1, pc2, cnt
+
+
+def _culling_code(table, value, what):
+    key = value if what == "CombineFilters" else str(value).lower()       # method and type strings are lower-cased, CombineFilters is not
+    if key not in table:
+        raise ValueError(f"VoxelGridCulling {what} {value!r} (one of {sorted(table)})")
+    return table[key]
+
+
+def culling_scores(ctx, cloud, kp_offsets, kx, ky, kz, krgba, leaf, geometry="none", color="none", max_similar_color_distance=0.01, pc1=None, pc2=None,
+                   want_counts=True):
+    """ismhip_culling_scores: returns (geo float32[n_kp], color float32[n_kp], counts int32[n_kp] or None); a method "none" leaves zeros.
+    geometry "kpq" takes pc1, pc2 of principal_curvatures"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    dev = cloud._keep[0].device
+    geo = torch.zeros((n,), dtype=torch.float32, device=dev); col = torch.zeros_like(geo)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_culling_scores(ctx._h, cloud._h, _p(ko), _p(kx), _p(ky), _p(kz), _p(krgba), C.c_float(leaf),
+                                          C.c_int(_culling_code(CULLING_GEOMETRY, geometry, "FilterMethodGeometry")),
+                                          C.c_int(_culling_code(CULLING_COLOR, color, "FilterMethodColor")), C.c_float(max_similar_color_distance),
+                                          _p(pc1), _p(pc2), _p(geo), _p(col), _p(cnt)), "ismhip_culling_scores")
+    return geo, col, cnt
+
+
+def culling_select(ctx, kp_offsets, geo, color, kx, ky, kz, krgba=None, geometry_on=True, color_on=True, geometry_type="cutoff", color_type="cutoff",
+                   geometry_threshold=0.005, color_threshold=0.02, cutoff_ratio=0.5, combine="RequireCombinedList", capacity=None):
+    """ismhip_culling_select: returns a dict with kp_offsets (numpy [n_obj+1]), kx, ky, kz, krgba (or None): the accepted keypoints in their
+    order; keep uint8[n_kp], combined float32[n_kp], thresholds float32[n_obj, 3] (geometry, colour, combined)"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n_obj, n = len(ko) - 1, int(ko[-1])
+    dev = geo.device
+    cap = n if capacity is None else int(capacity)
+    ox = torch.empty((max(cap, 1),), dtype=torch.float32, device=dev); oy = torch.empty_like(ox); oz = torch.empty_like(ox)
+    oc = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev) if krgba is not None else None
+    keep = torch.zeros((max(n, 1),), dtype=torch.uint8, device=dev)
+    comb = torch.zeros((max(n, 1),), dtype=torch.float32, device=dev)
+    thr = torch.zeros((n_obj, 3), dtype=torch.float32, device=dev)
+    out = np.zeros(n_obj + 1, dtype=np.uint32)
+    ctx.check(lib().ismhip_culling_select(ctx._h, C.c_int(n_obj), _p(ko), _p(geo), _p(color), C.c_int(1 if geometry_on else 0), C.c_int(1 if color_on else 0),
+                                          C.c_int(_culling_code(CULLING_TYPE, geometry_type, "FilterTypeGeometry")),
+                                          C.c_int(_culling_code(CULLING_TYPE, color_type, "FilterTypeColor")), C.c_float(geometry_threshold),
+                                          C.c_float(color_threshold), C.c_float(cutoff_ratio), C.c_int(_culling_code(CULLING_COMBINE, combine, "CombineFilters")),
+                                          _p(kx), _p(ky), _p(kz), _p(krgba), C.c_uint32(cap), _p(ox), _p(oy), _p(oz), _p(oc), _p(keep), _p(comb), _p(thr),
+                                          _p(out)), "ismhip_culling_select")
+    m = int(out[-1])
+    return dict(kp_offsets=out, kx=ox[:m], ky=oy[:m], kz=oz[:m], krgba=(oc[:m] if oc is not None else None), keep=keep[:n], combined=comb[:n],
+                thresholds=thr)
+
+
+def voxel_culling_keypoints(ctx, cloud, leaf, geometry="none", color="none", geometry_type="cutoff", color_type="cutoff", geometry_threshold=0.005,
+                            color_threshold=0.02, max_similar_color_distance=0.01, cutoff_ratio=0.5, combine="RequireCombinedList",
+                            disable_filter_in_training=True, is_training=False):
+    """KeypointsVoxelGridCulling on the device, on the points the cloud was created with: the voxel keypoints at `leaf`, their scores and the
+    selection; returns (kp_offsets[n_obj+1] numpy, kx, ky, kz, krgba or None). Both methods "none", or training with
+    disable_filter_in_training: the plain voxel grid"""
+    x, y, z, rgba = cloud._keep[0], cloud._keep[1], cloud._keep[2], cloud._keep[6]
+    ko, kx, ky, kz, kc = voxel_keypoints(ctx, cloud.pt_offsets, x, y, z, leaf, rgba=rgba)
+    g, c = str(geometry).lower(), str(color).lower()
+    _culling_code(CULLING_GEOMETRY, g, "FilterMethodGeometry"); _culling_code(CULLING_COLOR, c, "FilterMethodColor")
+    if (is_training and disable_filter_in_training) or (g == "none" and c == "none"):
+        return ko, kx, ky, kz, kc
+    pc1 = pc2 = None
+    if g == "kpq":
+        pc1, pc2, _ = principal_curvatures(ctx, cloud, leaf, want_counts=False)
+    geo, col, _ = culling_scores(ctx, cloud, ko, kx, ky, kz, kc, leaf, g, c, max_similar_color_distance, pc1, pc2, want_counts=False)
+    r = culling_select(ctx, ko, geo, col, kx, ky, kz, kc, g != "none", c != "none", geometry_type, color_type, geometry_threshold, color_threshold,
+                       cutoff_ratio, combine)
+    return r["kp_offsets"], r["kx"], r["ky"], r["kz"], r["krgba"]
 
 
 def _compact_feature_rows(ctx, symbol, report_all_kept, kp_offsets, desc, lrf, kpx, kpy, kpz):

@@ -85,6 +85,7 @@ public:
     std::vector<uint32_t> pt_off, kp_off;
     PointArrays pts, spare;               // the batch's points; spare: target of a compaction (compactPoints), swapped in afterwards
     DevBuf kx, ky, kz, krgba;
+    DevBuf vox_x, vox_y, vox_z, vox_rgba, cull_pc1, cull_pc2, cull_geo, cull_col;   // VoxelGridCulling: the voxel keypoints before the culling, curvatures, scores
     ismhip_cloud* cloud = nullptr;
     bool has_color = false;
     // vote space of the current batch (Voting::m_votes)
@@ -154,7 +155,8 @@ public:
     }
     // uploads the batch and builds the search surface
     // kps == nullptr: the keypoints are computed on the device by `detector` (finishBatch)
-    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps, float cell, bool with_color, const Keypoints* detector = nullptr) {
+    void uploadBatch(const std::vector<const PointCloud*>& clouds, const std::vector<KeypointSet>* kps, float cell, bool with_color, const Keypoints* detector = nullptr,
+                     bool is_training = false) {
         uploadPoints(clouds, with_color, false);
         if (kps) {
             kp_off.assign(1, 0);
@@ -167,17 +169,52 @@ public:
             h2d(kx, hkx); h2d(ky, hky); h2d(kz, hkz);
             if (with_color) h2d(krgba, hkrgba);
         }
-        finishBatch(kps ? nullptr : detector, cell);
+        finishBatch(kps ? nullptr : detector, cell, is_training);
     }
     // the point arrays of the batch are in HBM (pts, pt_off): the keypoints of a device detector (nullptr: they have been uploaded) and
     // the search surface. A voxel grid needs no surface and keeps its place in front of it; ISS3D sweeps the surface, so it comes after.
-    void finishBatch(const Keypoints* detector, float cell) {
+    // VoxelGridCulling does both: its voxel keypoints in front, their scores and the selection behind (is_training: DisableFilterInTraining).
+    void finishBatch(const Keypoints* detector, float cell, bool is_training = false) {
         const ismhip_point_arrays p = pts.view(has_color);
         dropCloud();
         const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(detector);
         const auto* iss = dynamic_cast<const KeypointsISS3D*>(detector);
-        if (detector && !vg && !iss) throw RuntimeException("keypoint type \"" + detector->getType() + "\" has no device route");
+        const auto* cull = dynamic_cast<const KeypointsVoxelGridCulling*>(detector);
+        if (detector && !vg && !iss && !cull) throw RuntimeException("keypoint type \"" + detector->getType() + "\" has no device route");
         const size_t n_pts = pt_off.back();
+        if (cull) {
+            const size_t cap = std::max<size_t>(n_pts, 1) * 4;
+            kx.reserve(cap); ky.reserve(cap); kz.reserve(cap);
+            if (has_color) krgba.reserve(cap);
+            kp_off.assign((size_t)n_obj + 1, 0);
+            const bool plain = cull->isPlainVoxelGrid(is_training);
+            if (!plain && cull->needsColor() && !has_color)
+                throw RuntimeException("VoxelGridCulling FilterMethodColor \"colordistance\" needs clouds with colours");
+            if (!plain) { vox_x.reserve(cap); vox_y.reserve(cap); vox_z.reserve(cap); if (has_color) vox_rgba.reserve(cap); }
+            float* vx = plain ? kx.as<float>() : vox_x.as<float>(); float* vy = plain ? ky.as<float>() : vox_y.as<float>();
+            float* vz = plain ? kz.as<float>() : vox_z.as<float>();
+            uint32_t* vc = !has_color ? nullptr : (plain ? krgba.as<uint32_t>() : vox_rgba.as<uint32_t>());
+            std::vector<uint32_t> vox_off((size_t)n_obj + 1, 0);
+            check(ismhip_voxel_keypoints(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.rgba, cull->getLeafSize(), (uint32_t)n_pts, vx, vy, vz, vc,
+                                         plain ? kp_off.data() : vox_off.data()), "ismhip_voxel_keypoints");
+            check(ismhip_cloud_create(ctx, n_obj, pt_off.data(), p.x, p.y, p.z, p.nx, p.ny, p.nz, p.rgba, cell, &cloud), "ismhip_cloud_create");
+            if (plain) return;
+            const size_t nkp = std::max<size_t>(vox_off.back(), 1) * 4;
+            cull_geo.reserve(nkp); cull_col.reserve(nkp);
+            const bool kpq = cull->geometryMethod() == ISMHIP_CULLING_GEOMETRY_KPQ;
+            if (kpq) {
+                cull_pc1.reserve(cap); cull_pc2.reserve(cap);
+                check(ismhip_principal_curvatures(ctx, cloud, cull->getLeafSize(), cull_pc1.as<float>(), cull_pc2.as<float>(), nullptr), "ismhip_principal_curvatures");
+            }
+            check(ismhip_culling_scores(ctx, cloud, vox_off.data(), vx, vy, vz, vc, cull->getLeafSize(), cull->geometryMethod(), cull->colorMethod(),
+                                        cull->maxSimilarColorDistance(), kpq ? cull_pc1.as<float>() : nullptr, kpq ? cull_pc2.as<float>() : nullptr,
+                                        cull_geo.as<float>(), cull_col.as<float>(), nullptr), "ismhip_culling_scores");
+            check(ismhip_culling_select(ctx, n_obj, vox_off.data(), cull_geo.as<float>(), cull_col.as<float>(), cull->geometryMethod() != 0, cull->colorMethod() != 0,
+                                        cull->geometryType(), cull->colorType(), cull->geometryThreshold(), cull->colorThreshold(), cull->cutoffRatio(),
+                                        cull->combine(), vx, vy, vz, vc, (uint32_t)n_pts, kx.as<float>(), ky.as<float>(), kz.as<float>(),
+                                        has_color ? krgba.as<uint32_t>() : nullptr, nullptr, nullptr, nullptr, kp_off.data()), "ismhip_culling_select");
+            return;
+        }
         if (detector) {
             // the keypoints stay in HBM, only the per-object counts come back
             kx.reserve(std::max<size_t>(n_pts, 1) * 4); ky.reserve(std::max<size_t>(n_pts, 1) * 4); kz.reserve(std::max<size_t>(n_pts, 1) * 4);
@@ -337,6 +374,61 @@ void KeypointsISS3D::iPostInitConfig() {
 }
 KeypointSet KeypointsISS3D::iComputeKeypoints(const PointCloud&) const {
     throw RuntimeException("KeypointsISS3D has no host implementation: the detector runs on the device with the batch (ismhip_iss3d_keypoints)");
+}
+
+// Keypoints: voxel-grid keypoints culled by quality scores (keypoints/keypoints_voxel_grid_culling.cpp:27-44). The detector itself is
+// ismhip_voxel_keypoints + ismhip_principal_curvatures / ismhip_culling_scores / ismhip_culling_select on the batch's search surface
+// (DeviceSession::finishBatch); this class holds the configuration and refuses, by name, what is not built.
+KeypointsVoxelGridCulling::KeypointsVoxelGridCulling() {
+    addParameter(m_leafSize, "LeafSize", 0.1f);
+    addParameter(m_filter_method_geometry, "FilterMethodGeometry", std::string("None"));
+    addParameter(m_filter_type_geometry, "FilterTypeGeometry", std::string("CutOff"));
+    addParameter(m_filter_threshold_geometry, "FilterThresholdGeometry", 0.005f);
+    addParameter(m_filter_method_color, "FilterMethodColor", std::string("None"));
+    addParameter(m_filter_type_color, "FilterTypeColor", std::string("CutOff"));
+    addParameter(m_filter_threshold_color, "FilterThresholdColor", 0.02f);
+    addParameter(m_max_similar_color_distance, "MaxSimilarColorDistance", 0.01f);
+    addParameter(m_filter_cutoff_ratio, "FilterCutoffRatio", 0.5f);
+    addParameter(m_disable_filter_in_training, "DisableFilterInTraining", true);
+    addParameter(m_combine_filters, "CombineFilters", std::string("RequireCombinedList"));
+    addParameter(m_refine_position, "RefineKeypointPosition", false);
+}
+void KeypointsVoxelGridCulling::iPostInitConfig() {
+    auto lower = [](std::string s) { for (char& c : s) c = (char)std::tolower((unsigned char)c); return s; };   // :62-65
+    const std::string mg = lower(m_filter_method_geometry), tg = lower(m_filter_type_geometry), mc = lower(m_filter_method_color), tc = lower(m_filter_type_color);
+    if (!(m_leafSize > 0.f) || !std::isfinite(m_leafSize)) throw BadParamExceptionType<float>("invalid VoxelGridCulling LeafSize: the voxel edge and ball radius must be positive", m_leafSize);
+    if (mg == "gaussian")
+        throw BadParamExceptionType<std::string>("VoxelGridCulling FilterMethodGeometry \"gaussian\" is not built: PCL takes the query's normal from the surface "
+                                                 "normals at the keypoint's index, an unrelated point since keypoints are not surface points, so the reference's "
+                                                 "result is noise (built: none, curvature, kpq)", m_filter_method_geometry);
+    if (mg == "none") m_geometry = ISMHIP_CULLING_GEOMETRY_NONE;
+    else if (mg == "curvature") m_geometry = ISMHIP_CULLING_GEOMETRY_CURVATURE;
+    else if (mg == "kpq") m_geometry = ISMHIP_CULLING_GEOMETRY_KPQ;
+    else throw BadParamExceptionType<std::string>("unsupported VoxelGridCulling FilterMethodGeometry (built: none, curvature, kpq)", m_filter_method_geometry);
+    if (tg == "auto")
+        throw BadParamExceptionType<std::string>("VoxelGridCulling FilterTypeGeometry \"auto\" is not built: the source marks it experimental and it is undefined "
+                                                 "for a zero histogram step (built: cutoff, threshold)", m_filter_type_geometry);
+    if (tg == "cutoff") m_geometry_type = ISMHIP_CULLING_TYPE_CUTOFF;
+    else if (tg == "threshold") m_geometry_type = ISMHIP_CULLING_TYPE_THRESHOLD;
+    else throw BadParamExceptionType<std::string>("unsupported VoxelGridCulling FilterTypeGeometry (built: cutoff, threshold)", m_filter_type_geometry);
+    if (mc == "none") m_color = ISMHIP_CULLING_COLOR_NONE;
+    else if (mc == "colordistance") m_color = ISMHIP_CULLING_COLOR_DISTANCE;
+    else throw BadParamExceptionType<std::string>("unsupported VoxelGridCulling FilterMethodColor (built: none, colordistance)", m_filter_method_color);
+    if (tc == "cutoff") m_color_type = ISMHIP_CULLING_TYPE_CUTOFF;
+    else if (tc == "threshold") m_color_type = ISMHIP_CULLING_TYPE_THRESHOLD;
+    else throw BadParamExceptionType<std::string>("unsupported VoxelGridCulling FilterTypeColor (built: cutoff, threshold)", m_filter_type_color);
+    if (m_refine_position) throw BadParamException("VoxelGridCulling RefineKeypointPosition is not built: position refinement is a later change");
+    if (!(m_filter_cutoff_ratio >= 0.f && m_filter_cutoff_ratio < 1.f))
+        throw BadParamExceptionType<float>("invalid VoxelGridCulling FilterCutoffRatio: the share of keypoints to omit must lie in [0, 1)", m_filter_cutoff_ratio);
+    if (m_combine_filters == "RequireOne") m_combine = ISMHIP_CULLING_REQUIRE_ONE;          // case-sensitive, as :240-251 compares
+    else if (m_combine_filters == "RequireBoth") m_combine = ISMHIP_CULLING_REQUIRE_BOTH;
+    else if (m_combine_filters == "RequireCombinedList") m_combine = ISMHIP_CULLING_REQUIRE_COMBINED_LIST;
+    else throw BadParamExceptionType<std::string>("unknown VoxelGridCulling CombineFilters: the reference silently drops every keypoint "
+                                                  "(one of RequireOne, RequireBoth, RequireCombinedList)", m_combine_filters);
+}
+KeypointSet KeypointsVoxelGridCulling::iComputeKeypoints(const PointCloud&) const {
+    throw RuntimeException("KeypointsVoxelGridCulling has no host implementation: the detector runs on the device with the batch "
+                           "(ismhip_voxel_keypoints, ismhip_culling_scores, ismhip_culling_select)");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1526,7 +1618,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
     if (type == KeypointsISS3D::getTypeStatic()) return new KeypointsISS3D();
-    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid, ISS3D)");
+    if (type == KeypointsVoxelGridCulling::getTypeStatic()) return new KeypointsVoxelGridCulling();
+    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid, ISS3D, VoxelGridCulling)");
 }
 template <> ActivationStrategy* Factory<ActivationStrategy>::createByType(const std::string& type) {
     if (type == ActivationStrategyKNN::getTypeStatic()) return new ActivationStrategyKNN();
@@ -1932,7 +2025,7 @@ std::vector<const PointCloud*> ImplicitShapeModel::preFilterClouds(const std::ve
     return out;
 }
 
-std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::vector<const PointCloud*>& clouds_in, bool) {   // :733-927
+std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::vector<const PointCloud*>& clouds_in, bool is_training) {   // :733-927
     DeviceSession& s = session();
     LapTimer timer{m_processing_times};
     // clouds that come without normals get them on the device (computeNormals :940-1032, ConsistentNormalsMethod 2), then lose the
@@ -1945,8 +2038,14 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
     // (ismhip_iss3d_keypoints) are taken on the batch's search surface and have no host implementation: the switch does not apply.
     const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(m_keypoints_detector.get());
     const auto* iss = dynamic_cast<const KeypointsISS3D*>(m_keypoints_detector.get());
+    // VoxelGridCulling keypoints (ismhip_culling_scores, ismhip_culling_select) likewise; its colour score wants the clouds' colours
+    const auto* cull = dynamic_cast<const KeypointsVoxelGridCulling*>(m_keypoints_detector.get());
+    const bool with_color = m_feature_descriptor->needsColor() || (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training));
+    if (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training))
+        for (const PointCloud* c : clouds)
+            if (c->rgba.size() != c->size()) throw RuntimeException("VoxelGridCulling FilterMethodColor \"colordistance\" needs clouds with colours");
     const char* host_kp = getenv("ISM3D_HOST_KEYPOINTS");
-    const bool dev_kp = iss || (vg && !(host_kp && host_kp[0] == '1'));
+    const bool dev_kp = iss || cull || (vg && !(host_kp && host_kp[0] == '1'));
     if (iss)
         for (const PointCloud* c : clouds)
             if (c->organized) {   // keypoints_iss3d.cpp:45-48 hands PCL the unfiltered organised cloud
@@ -1983,7 +2082,7 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
         std::vector<const PointCloud*> part;
         for (size_t i : need) { tmp.push_back(withZeroedNormals(*clouds[i])); part.push_back(&tmp.back()); }
         const std::vector<KeypointSet> none(part.size());
-        s.uploadBatch(part, &none, m_normal_radius * 0.5f, on_device && m_feature_descriptor->needsColor());
+        s.uploadBatch(part, &none, m_normal_radius * 0.5f, on_device && with_color);
         if (m_consistent_normals_method == 2)
             s.check(ismhip_estimate_normals(s.ctx, s.cloud, m_normal_radius, s.pts.nx.as<float>(), s.pts.ny.as<float>(), s.pts.nz.as<float>()), "ismhip_estimate_normals");
         else                                                // :969-1003
@@ -1994,7 +2093,7 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
                 return ismhip_filter_normals(s.ctx, s.n_obj, s.pt_off.data(), in, out, new_off);
             });
             timer.lap("normals");
-            s.finishBatch(m_keypoints_detector.get(), cell);
+            s.finishBatch(m_keypoints_detector.get(), cell, is_training);
             timer.lap("keypoints");
             return describe();
         }
@@ -2018,13 +2117,13 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
         }
     }
     if (dev_kp) {
-        s.uploadBatch(clouds, nullptr, cell, m_feature_descriptor->needsColor(), m_keypoints_detector.get());
+        s.uploadBatch(clouds, nullptr, cell, with_color, m_keypoints_detector.get(), is_training);
         timer.lap("keypoints");
     } else {
         std::vector<KeypointSet> kps;
         for (const PointCloud* c : clouds) kps.push_back((*m_keypoints_detector)(*c));
         timer.lap("keypoints");
-        s.uploadBatch(clouds, &kps, cell, m_feature_descriptor->needsColor());
+        s.uploadBatch(clouds, &kps, cell, with_color);
     }
     return describe();
 }

@@ -245,6 +245,42 @@ private:
     int m_minNeighbors;
 };
 
+// keypoints/keypoints_voxel_grid_culling.cpp:27-44: the reference's 13 parameter names and defaults (ismhip_principal_curvatures,
+// ismhip_culling_scores, ismhip_culling_select). Method and type strings are lower-cased when the configuration is
+// read, as the reference lower-cases them before it compares; CombineFilters is case-sensitive. Refused by name there, each with its
+// reason: FilterMethodGeometry "gaussian", FilterTypeGeometry "auto", RefineKeypointPosition, a FilterCutoffRatio outside [0, 1), an
+// unknown method, type or CombineFilters, a non-positive LeafSize. There is NO host implementation of the culling: the detector runs on
+// the batch's search surface on the device (DeviceSession::finishBatch), iComputeKeypoints(const PointCloud&) throws by name, and
+// ISM3D_HOST_KEYPOINTS=1 does not apply.
+class KeypointsVoxelGridCulling : public Keypoints {
+public:
+    KeypointsVoxelGridCulling();
+    static std::string getTypeStatic() { return "VoxelGridCulling"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getLeafSize() const { return m_leafSize; }
+    // both methods "none", or training with DisableFilterInTraining: the plain voxel grid (:76-87)
+    bool isPlainVoxelGrid(bool is_training) const { return (is_training && m_disable_filter_in_training) || (m_geometry == 0 && m_color == 0); }
+    bool needsColor() const { return m_color != 0; }
+    int geometryMethod() const { return m_geometry; }      // ISMHIP_CULLING_GEOMETRY_*
+    int colorMethod() const { return m_color; }            // ISMHIP_CULLING_COLOR_*
+    int geometryType() const { return m_geometry_type; }   // ISMHIP_CULLING_TYPE_*
+    int colorType() const { return m_color_type; }
+    int combine() const { return m_combine; }              // ISMHIP_CULLING_REQUIRE_*
+    float geometryThreshold() const { return m_filter_threshold_geometry; }
+    float colorThreshold() const { return m_filter_threshold_color; }
+    float maxSimilarColorDistance() const { return m_max_similar_color_distance; }
+    float cutoffRatio() const { return m_filter_cutoff_ratio; }
+protected:
+    KeypointSet iComputeKeypoints(const PointCloud& points) const override;
+    void iPostInitConfig() override;
+private:
+    float m_leafSize;
+    std::string m_filter_method_geometry, m_filter_type_geometry, m_filter_method_color, m_filter_type_color, m_combine_filters;
+    float m_filter_threshold_geometry, m_filter_threshold_color, m_max_similar_color_distance, m_filter_cutoff_ratio;
+    bool m_disable_filter_in_training, m_refine_position;
+    int m_geometry = 0, m_color = 0, m_geometry_type = 0, m_color_type = 0, m_combine = 2;
+};
+
 // ---- Features (features/features.h) -------------------------------------------------------------------
 class Features : public JSONObject {
 public:
