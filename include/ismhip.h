@@ -76,7 +76,10 @@ extern "C" {
 #define ISMHIP_SPIN_IMAGE_DIM 153   /* (8 + 1) * (2 * 8 + 1) */
 #define ISMHIP_RSD_DIM 25           /* ismhip_rsd, full_histogram: 5 angle bins x 5 distance bins */
 #define ISMHIP_RSD_RADII_DIM 2      /* ismhip_rsd without it: the two principal radii */
-#define ISMHIP_VFH_DIM 308          /* ismhip_global_vfh: 4 shape blocks of 45 bins + 128 viewpoint bins */
+#define ISMHIP_RIFT_DISTANCE_BINS 8  /* rift_distance_bins, features_rift.cpp:38 */
+#define ISMHIP_RIFT_GRADIENT_BINS 16 /* rift_gradient_bins, :39 */
+#define ISMHIP_RIFT_DIM 128         /* 8 * 16 */
+#define ISMHIP_VFH_DIM 308         /* ismhip_global_vfh: 4 shape blocks of 45 bins + 128 viewpoint bins */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -97,7 +100,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select","intensity_gradients","rift"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -343,6 +346,35 @@ int  ismhip_spin_image(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
 int  ismhip_rsd(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                 const float* kpx, const float* kpy, const float* kpz, float radius, int full_histogram,
                 float* desc_out, uint32_t* neighbour_count_out);
+/* The dense first half of FeaturesRIFT::iComputeDescriptors (features/features_rift.cpp:29-96): PointCloudXYZRGBtoXYZI (:47-51), then PCL 1.10
+ * IntensityGradientEstimation (:53-62) over the Radius ball of every cloud point. This library's definition (deviations D1, D2):
+ *  - intensity I = (0.299f*R + 0.587f*G) + 0.114f*B in float, unfused, from the 8-bit channels of the cloud's 0x00RRGGBB colours;
+ *  - ball of point i: the finite cloud points with d2 < (float)((double)radius * radius), d2 = (dx*dx + dy*dy) + dz*dz in float, i itself
+ *    included; count_out[n_pts] (may be NULL) = cp, 0 for a point that is not finite;
+ *  - cp < 3 or a normal that is not finite: (NaN, NaN, NaN); else A = sum (p_j - c)(p_j - c)^T, b = sum (p_j - c)(I_j - m), c and m the
+ *    ball's means, from the moments about the query (positions and intensities both), differences and products in double, every term
+ *    rounded to a fixed quantum and added as a 64-bit integer: the sums do not depend on the order (D1);
+ *  - x = pseudo-inverse of A over the eigenvalues above 1e-12 of the largest (eigen3.h; x = 0 when that is not positive) times b (D2);
+ *  - g = x - n (n . x) with the point's normal n, in double; grad_out[n_pts * 3] floats in the cloud's original point order.
+ * Two calls and any grid cell size give the same bits. Refused with ISMHIP_ERR_INVALID: a radius that is not positive and finite
+ * ("intensity_gradients: bad argument"), a cloud made without rgba ("intensity_gradients: colour arrays missing"), grad_out NULL with
+ * points to describe. Timer "intensity_gradients". Asynchronous. */
+int  ismhip_intensity_gradients(ismhip_ctx* ctx, const ismhip_cloud* cloud, float radius, float* grad_out, uint32_t* count_out);
+/* The second half (features/features_rift.cpp:66-78 -> PCL 1.10 RIFTEstimation::computeRIFT): desc_out[nkp * n_distance_bins *
+ * n_gradient_bins], the reference's 8 x 16 (ISMHIP_RIFT_DISTANCE_BINS, ISMHIP_RIFT_GRADIENT_BINS, 128 floats). grad: the array
+ * ismhip_intensity_gradients wrote for this cloud. Per keypoint p0 (the keypoint itself, D5) and ball point j (same ball rule), in float:
+ * u = p_j - p0, dist = sqrtf(d2), mag = |g_j|, angle = atan2(|g_j x u|, g_j . u) (D3; 0 when both vanish), d = nd * dist / (radius +
+ * FLT_EPSILON), a = ng * angle / ((float)M_PI + FLT_EPSILON); the deposit (1 - |d - d_idx|)(1 - |a - g_idx|) * mag goes to bin
+ * g_idx mod ng * nd + d_idx for the d_idx in [0, nd - 1] and the g_idx within 1 of d and a. Deposits enter 64-bit integer bins scaled per
+ * object by a power of two above its largest |g|; the row is divided by its L2 norm (double), an all-zero row stays zero. An empty ball,
+ * a ball point whose gradient is not finite and a keypoint that is not finite give a row that is NaN AS A WHOLE (D4);
+ * neighbour_count_out[nkp] (may be NULL) = the ball's points, 0 for a ball that misses the object. Two calls and any grid cell size give
+ * the same bits. Refused with ISMHIP_ERR_INVALID: a radius that is not positive and finite, a bin count below 1 ("rift: bad argument"),
+ * a cloud made without rgba ("rift: colour arrays missing"), a missing array with keypoints to describe, offsets that are not monotone;
+ * with ISMHIP_ERR_UNSUPPORTED: n_distance_bins * n_gradient_bins > 256. Timer "rift". */
+int  ismhip_rift(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                 const float* kpx, const float* kpy, const float* kpz, float radius, int n_distance_bins, int n_gradient_bins,
+                 const float* grad, float* desc_out, uint32_t* neighbour_count_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);

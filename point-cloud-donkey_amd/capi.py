@@ -35,7 +35,7 @@ EXPORTS = [
     "ismhip_bshot_binarize", "ismhip_bshot352", "ismhip_codebook_make_binary", "ismhip_codebook_has_binary", "ismhip_knn_binary",
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352", "ismhip_global_vfh",
     "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
-    "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select",
+    "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
 ]
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
@@ -454,6 +454,37 @@ def rsd(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, full_histogram=True, want
     cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
     ctx.check(lib().ismhip_rsd(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(1 if full_histogram else 0),
                                _p(out), _p(cnt)), "ismhip_rsd")
+    return (out, cnt) if want_counts else out
+
+
+RIFT_DISTANCE_BINS, RIFT_GRADIENT_BINS = 8, 16       # features_rift.cpp:38-39
+RIFT_DIM = RIFT_DISTANCE_BINS * RIFT_GRADIENT_BINS   # 128
+
+
+def intensity_gradients(ctx, cloud, radius, want_counts=False):
+    """ismhip_intensity_gradients -> [n_pts, 3] float32 in the cloud's original point order (NaN where the ball holds fewer than three
+    points or the position or normal is not finite); with want_counts the ball's points per cloud point [n_pts] int32"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    grad = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_intensity_gradients(ctx._h, cloud._h, C.c_float(radius), _p(grad), _p(cnt)), "ismhip_intensity_gradients")
+    return (grad, cnt) if want_counts else grad
+
+
+def rift(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, grad, n_distance_bins=RIFT_DISTANCE_BINS, n_gradient_bins=RIFT_GRADIENT_BINS,
+         want_counts=False):
+    """ismhip_rift from the gradients of intensity_gradients -> [nkp, n_distance_bins * n_gradient_bins], gradient-major; with want_counts
+    the neighbours per keypoint [nkp]"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    nd, ng = int(n_distance_bins), int(n_gradient_bins)
+    out = torch.empty((n, max(nd, 0) * max(ng, 0)), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_rift(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(nd), C.c_int(ng), _p(grad),
+                                _p(out), _p(cnt)), "ismhip_rift")
     return (out, cnt) if want_counts else out
 
 

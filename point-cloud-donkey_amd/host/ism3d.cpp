@@ -99,6 +99,7 @@ public:
     // scratch for raw (uncompacted) features
     DevBuf raw_lrf, raw_desc, raw_cnt;
     DevBuf raw_axis;      // SpinImage: the keypoints' looked-up normals, three runs of nkp floats
+    DevBuf raw_grad;      // RIFT: the intensity gradient of every point of the batch, three floats each
 
     // ISMHIP_KNN_BINARY=0, read when the context is created: BSHOT codebooks keep the float search (A/B runs, tests; same answers)
     bool knn_binary_route = true;
@@ -556,8 +557,12 @@ FeaturesRSD::FeaturesRSD() {                     // features_rsd.cpp:19-23
     addParameter(m_radius, "Radius", 0.1f);
     addParameter(m_use_hist, "UseFullRSDHistogram", true);
 }
+FeaturesRIFT::FeaturesRIFT() { addParameter(m_radius, "Radius", 0.1f); }   // features_rift.cpp:20-23
 void FeaturesCospair::checkInput(const PointCloud& cloud) const {
     if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("CoSPAIR needs coloured point clouds");
+}
+void FeaturesRIFT::checkInput(const PointCloud& cloud) const {
+    if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("RIFT needs coloured point clouds");
 }
 
 void FeaturesSHOT::iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const {   // features_shot.cpp:28-81
@@ -606,6 +611,14 @@ void FeaturesSpinImage::iComputeDescriptors(DeviceSession& s, const float*, floa
 void FeaturesRSD::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
     s.check(ismhip_rsd(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, m_use_hist ? 1 : 0, desc_out,
                        counts_out), "ismhip_rsd");
+}
+// features_rift.cpp:29-96: the intensity gradients of the whole cloud (:53-62), then the 8 x 16 RIFT rows of the keypoints (:66-78)
+void FeaturesRIFT::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    if (!s.has_color) throw RuntimeException("RIFT needs coloured point clouds");
+    s.raw_grad.reserve(std::max<size_t>(s.pt_off.back(), 1) * 3 * 4);
+    s.check(ismhip_intensity_gradients(s.ctx, s.cloud, m_radius, s.raw_grad.as<float>(), nullptr), "ismhip_intensity_gradients");
+    s.check(ismhip_rift(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, ISMHIP_RIFT_DISTANCE_BINS,
+                        ISMHIP_RIFT_GRADIENT_BINS, s.raw_grad.as<float>(), desc_out, counts_out), "ismhip_rift");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1613,7 +1626,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesBSHOT::getTypeStatic()) return new FeaturesBSHOT();
     if (type == FeaturesSpinImage::getTypeStatic()) return new FeaturesSpinImage();
     if (type == FeaturesRSD::getTypeStatic()) return new FeaturesRSD();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, RSD, CoSPAIR)");
+    if (type == FeaturesRIFT::getTypeStatic()) return new FeaturesRIFT();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, RIFT, SpinImage, RSD, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

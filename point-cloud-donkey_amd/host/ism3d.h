@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -399,6 +399,24 @@ protected:
 private:
     float m_radius;
     bool m_use_hist;
+};
+// features/features_rift.{h,cpp} -> PCL's IntensityGradientEstimation and RIFTEstimation (ismhip_intensity_gradients, ismhip_rift, DESIGN.md
+// section 4.19): the intensity gradients of the coloured cloud, then per keypoint the 8 x 16 histogram of (distance, gradient angle), 128
+// floats. The bin counts are hard-coded in the reference (:38-39); Radius is the one parameter. The frames only decide which keypoints
+// stay. Not an ISM3D_FEATURE: it checks its input cloud.
+class FeaturesRIFT : public Features {
+public:
+    FeaturesRIFT();
+    static std::string getTypeStatic() { return "RIFT"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return ISMHIP_RIFT_DIM; }
+    bool needsColor() const override { return true; }
+    void checkInput(const PointCloud& cloud) const override;   // a cloud without colours throws
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+private:
+    float m_radius;
 };
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------

@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD" | "RIFT"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -100,7 +100,7 @@ class IsmConfig:
             return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
         if self.feature == "RSD":
             return capi.RSD_DIM if self.use_full_rsd_histogram else capi.RSD_RADII_DIM
-        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM}[self.feature]
+        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM, "RIFT": capi.RIFT_DIM}[self.feature]
 
     @property
     def metric(self):
@@ -199,7 +199,7 @@ class Recognizer:
     def compute_features(self, b: DeviceBatch, want_counts=False):
         c, ctx = self.cfg, self.ctx
         cell = min(c.radius, c.lrf_radius if c.feature != "FPFH" else c.radius) * float(os.environ.get("ISMHIP_CELL_SCALE", "0.4"))
-        cloud = capi.Cloud(ctx, b.pt_off, b.x, b.y, b.z, b.nx, b.ny, b.nz, cell, rgba=b.rgba if c.feature in ("CSHOT", "SHORT_CSHOT", "CoSPAIR") else None)
+        cloud = capi.Cloud(ctx, b.pt_off, b.x, b.y, b.z, b.nx, b.ny, b.nz, cell, rgba=b.rgba if c.feature in ("CSHOT", "SHORT_CSHOT", "CoSPAIR", "RIFT") else None)
         lrf = capi.LRF_TYPES[c.lrf_type](ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.lrf_radius)   # Features::operator() always computes LRFs
         if c.feature == "SHOT":
             desc, cnt = capi.shot352(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, lrf, c.radius, want_counts=True)
@@ -233,8 +233,12 @@ class Recognizer:
         elif c.feature == "RSD":
             # no frame enters the descriptor (as for FPFH and CoSPAIR); every pair of the ball's points does (features_rsd.cpp:41-56)
             desc, cnt = capi.rsd(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, full_histogram=c.use_full_rsd_histogram, want_counts=True)
+        elif c.feature == "RIFT":
+            # no frame enters the descriptor; the dense intensity gradients of the cloud first, then the 8 x 16 histogram (features_rift.cpp:53-78)
+            grad = capi.intensity_gradients(ctx, cloud, c.radius)
+            desc, cnt = capi.rift(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, grad, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, SpinImage, RSD, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, RIFT, SpinImage, RSD, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
