@@ -20,6 +20,7 @@
 #ifndef ISMHIP_H_
 #define ISMHIP_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -100,7 +101,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select","intensity_gradients","rift"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select","intensity_gradients","rift","keypoint_normals_pca","cgf_raw","mlp_forward"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -375,6 +376,64 @@ int  ismhip_intensity_gradients(ismhip_ctx* ctx, const ismhip_cloud* cloud, floa
 int  ismhip_rift(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                  const float* kpx, const float* kpy, const float* kpz, float radius, int n_distance_bins, int n_gradient_bins,
                  const float* grad, float* desc_out, uint32_t* neighbour_count_out);
+/* ---- CGF (features/features_cgf.cpp -> third_party/cgf/cgf.cpp:64-165 and third_party/cgf/embedding.py:103-108) ----------
+ * The PCA normal of cgf.cpp:87-94 at every KEYPOINT over the `radius` ball of the cloud: the arithmetic of ismhip_estimate_normals_pca with
+ * orientation 0 (FP64 moments about the query, eigen3.h, at least 3 ball points, flipped towards (0,0,0)); NaN for fewer than 3 points, for a
+ * keypoint that is not finite and for a ball that misses the object. Writes three arrays of nkp floats. Refused with ISMHIP_ERR_INVALID
+ * ("keypoint_normals_pca: bad argument"): a missing array, a radius that is not positive and finite. Timer "keypoint_normals_pca". */
+int  ismhip_keypoint_normals_pca(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                                 const float* kpx, const float* kpy, const float* kpz, float radius,
+                                 float* knx_out, float* kny_out, float* knz_out);
+/* The raw spherical histogram of cgf.cpp:98-161: desc_out[nkp * ISMHIP_CGF_RAW_DIM], bin = bin_r + 17 bin_theta + 187 bin_phi.
+ *  - lrf9: the frames of ismhip_shot_lrf at radius_lrf (the caller's 0.75 R); a frame with a NaN in its x axis becomes the identity; else,
+ *    with n = (knx, kny, knz)[k] (ismhip_keypoint_normals_pca at 0.1 R), all three axes are negated when (z.x n.x + z.y n.y) + z.z n.z < 0
+ *    in float (a NaN normal negates nothing);
+ *  - ball: the finite cloud points with d2 < (float)((double)radius * radius), d2 as in every sweep of this library. THE SKIP RULE (cgf.cpp's
+ *    loop starts at j = 1 of a distance-sorted list): the ball point with the smallest d2, ties to the lowest original index, is left out
+ *    whether or not it coincides with the keypoint; so is every point whose (double)d2 > 1e-15 is false;
+ *  - per remaining point: v = p - k in float; x, y, z = (v.x a.x + v.y a.y) + v.z a.z in unfused float against the three axes, widened to
+ *    double; r = sqrt(x x + y y + z z), theta = acos(z / r) * 57.29578, phi = atan2(y, x) * 57.29578 (PCL's rad2deg);
+ *    bin_r = (int)(16 (ln r - ln rmin) / ln(radius / rmin) + 1) clamped to [0, 16], bin_theta = (int)(11 theta / 180) at most 10,
+ *    bin_phi = (int)(12 (phi + 180) / 360) at most 11; an angle that is NaN goes to bin 0;
+ *  - row = (float)((double)count / (double)sum); sum == 0 (an empty ball, a ball that misses the object): a row of zeros, as in the
+ *    reference. A keypoint that is not finite gives a row that is NaN as a whole. neighbour_count_out[nkp] (may be NULL) = sum.
+ * radius and rmin arrive as doubles already rounded by the caller (the reference passes them through std::to_string). Integer counts only:
+ * two calls and any grid cell size give the same bytes. Refused with ISMHIP_ERR_INVALID ("cgf_raw: bad argument"): a missing array, radius
+ * or rmin not positive and finite, rmin >= radius. Timer "cgf_raw". */
+#define ISMHIP_CGF_RADIAL_BINS 17
+#define ISMHIP_CGF_POLAR_BINS 11
+#define ISMHIP_CGF_AZIMUTH_BINS 12
+#define ISMHIP_CGF_RAW_DIM 2244     /* 17 * 11 * 12 */
+int  ismhip_cgf_raw(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                    const float* kpx, const float* kpy, const float* kpz, const float* lrf9,
+                    const float* knx, const float* kny, const float* knz, double radius, double rmin,
+                    float* desc_out, uint32_t* neighbour_count_out);
+/* A small perceptron on the exact FP32 matrix cores (mlp.hip): n_layers <= ISMHIP_MLP_MAX_LAYERS layers y = act(x W + b), W[in][out]
+ * row-major (TensorFlow's layout), act = ReLU (relu[l] != 0) or the identity; in[0] from 1 to 4096, every out from 1 to 512, in[l] =
+ * out[l - 1]. W, b: host arrays, copied. forward maps x[n_rows * in[0]] to y[n_rows * out[last]] (device floats, row-major); odd widths and
+ * row counts are padded inside the call. A row's result does not depend on the other rows of the call. Every sum is an FP32 fma chain in a
+ * fixed order; bias and ReLU in float; a NaN stays NaN. Refused with ISMHIP_ERR_INVALID ("mlp_create: ..."). Timer "mlp_forward". */
+#define ISMHIP_MLP_MAX_LAYERS 8
+#define ISMHIP_MLP_MAX_IN 4096
+#define ISMHIP_MLP_MAX_OUT 512
+typedef struct ismhip_mlp ismhip_mlp;
+int  ismhip_mlp_create(ismhip_ctx* ctx, int n_layers, const int* in, const int* out, const int* relu,
+                       const float* const* W_h, const float* const* b_h, ismhip_mlp** mlp_out);
+int  ismhip_mlp_destroy(ismhip_mlp* mlp);
+int  ismhip_mlp_in(const ismhip_mlp* mlp);     /* in[0] */
+int  ismhip_mlp_out(const ismhip_mlp* mlp);    /* out[last] */
+int  ismhip_mlp_forward(ismhip_ctx* ctx, const ismhip_mlp* mlp, const float* x, size_t n_rows, float* y);
+/* The weights container ".cgfw" (little endian): char magic[4] = "CGFW", uint32 version = 1, uint32 n_layers; per layer uint32 in, uint32
+ * out, uint32 activation (1 ReLU, 0 identity), float32 W[in][out], float32 b[out]. No device is touched. expect_in > 0: the first layer's
+ * `in` must equal it. Refusals (ISMHIP_ERR_INVALID, the reason in err[err_len], each with its name): "cannot open", "wrong magic",
+ * "unsupported version", "layer count", "truncated file", "width out of range", "inconsistent widths", "first layer width", "unknown
+ * activation", "non-finite weight", "trailing bytes". */
+typedef struct ismhip_cgfw ismhip_cgfw;
+int  ismhip_cgfw_open(const char* path, int expect_in, ismhip_cgfw** out, char* err, int err_len);
+int  ismhip_cgfw_close(ismhip_cgfw* w);
+int  ismhip_cgfw_layers(const ismhip_cgfw* w);
+int  ismhip_cgfw_layer(const ismhip_cgfw* w, int layer, int* in, int* out, int* relu, const float** W, const float** b);
+int  ismhip_mlp_from_cgfw(ismhip_ctx* ctx, const ismhip_cgfw* w, ismhip_mlp** mlp_out);
 /* ISMFeature::centerDist (features_shot.cpp:77): |keypoint - centroid(object)| -> out[nkp] */
 int  ismhip_center_dist(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                         const float* kpx, const float* kpy, const float* kpz, float* out);

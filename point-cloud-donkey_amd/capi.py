@@ -36,6 +36,8 @@ EXPORTS = [
     "ismhip_rank_scores", "ismhip_rank_select", "ismhip_global_short_shot", "ismhip_global_shot352", "ismhip_global_vfh",
     "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
+    "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
+    "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw",
 ]
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
@@ -485,6 +487,156 @@ def rift(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, grad, n_distance_bins=RI
     cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
     ctx.check(lib().ismhip_rift(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(nd), C.c_int(ng), _p(grad),
                                 _p(out), _p(cnt)), "ismhip_rift")
+    return (out, cnt) if want_counts else out
+
+
+CGF_RADIAL_BINS, CGF_POLAR_BINS, CGF_AZIMUTH_BINS = 17, 11, 12   # cgf.cpp:205-207 as features_cgf.cpp leaves them
+CGF_RAW_DIM = CGF_RADIAL_BINS * CGF_POLAR_BINS * CGF_AZIMUTH_BINS  # 2244
+CGF_CHUNK_ROWS = 32768                               # keypoints per raw + embedding chunk of cgf(): 294 MB of raw rows
+
+
+def cgf_radii(radius):
+    """the three lengths of features_cgf.cpp:50-52 after their trip through std::to_string ("%f") and stod: (R, rmin, LRF radius) as
+    doubles; the normal radius is 0.1 times the first (cgf.cpp:93)"""
+    r = float(np.float32(radius))
+    return float("%f" % r), float("%f" % (r * 0.05)), float("%f" % (r * 0.75))
+
+
+def keypoint_normals_pca(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius):
+    """ismhip_keypoint_normals_pca -> (nx, ny, nz) [nkp] each: the PCA normal of the `radius` ball about every keypoint, towards (0,0,0)"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    nx, ny, nz = (torch.empty((n,), dtype=torch.float32, device=kpx.device) for _ in range(3))
+    ctx.check(lib().ismhip_keypoint_normals_pca(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), _p(nx), _p(ny), _p(nz)),
+              "ismhip_keypoint_normals_pca")
+    return nx, ny, nz
+
+
+def cgf_raw(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, knx, kny, knz, radius, rmin, want_counts=False):
+    """ismhip_cgf_raw -> [nkp, 2244]; radius and rmin as cgf_radii returns them; with want_counts the deposits per keypoint [nkp]"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, CGF_RAW_DIM), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    ctx.check(lib().ismhip_cgf_raw(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(lrf), _p(knx), _p(kny), _p(knz), C.c_double(radius),
+                                   C.c_double(rmin), _p(out), _p(cnt)), "ismhip_cgf_raw")
+    return (out, cnt) if want_counts else out
+
+
+class Mlp:
+    """ismhip_mlp: layers = [(W [in, out] float32, b [out] float32, relu), ...] on the host, or from_file(ctx, path) for a .cgfw"""
+
+    def __init__(self, ctx, layers=None, _handle=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            n = len(layers)
+            Ws = [np.ascontiguousarray(np.asarray(w, np.float32)) for w, _b, _r in layers]
+            bs = [np.ascontiguousarray(np.asarray(b, np.float32)) for _w, b, _r in layers]
+            for w, b in zip(Ws, bs):
+                if w.ndim != 2 or b.shape != (w.shape[1],):
+                    raise IsmHipError("Mlp: W must be [in, out] and b [out]")
+            ins = (C.c_int * n)(*[w.shape[0] for w in Ws]); outs = (C.c_int * n)(*[w.shape[1] for w in Ws])
+            relu = (C.c_int * n)(*[1 if r else 0 for _w, _b, r in layers])
+            wp = (C.c_void_p * n)(*[w.ctypes.data for w in Ws]); bp = (C.c_void_p * n)(*[b.ctypes.data for b in bs])
+            ctx.check(lib().ismhip_mlp_create(ctx._h, C.c_int(n), ins, outs, relu, wp, bp, C.byref(self._h)), "ismhip_mlp_create")
+        self.n_in = lib().ismhip_mlp_in(self._h)
+        self.n_out = lib().ismhip_mlp_out(self._h)
+
+    @classmethod
+    def from_file(cls, ctx, path, expect_in=0):
+        w = cgfw_open(path, expect_in)
+        try:
+            h = C.c_void_p()
+            ctx.check(lib().ismhip_mlp_from_cgfw(ctx._h, w, C.byref(h)), "ismhip_mlp_from_cgfw")
+        finally:
+            lib().ismhip_cgfw_close(w)
+        return cls(ctx, _handle=h)
+
+    def forward(self, x, out=None):
+        """x [n_rows, in] float32 on the device -> [n_rows, out]"""
+        torch = _torch()
+        assert x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.n_in
+        y = torch.empty((x.shape[0], self.n_out), dtype=torch.float32, device=x.device) if out is None else out
+        self.ctx.check(lib().ismhip_mlp_forward(self.ctx._h, self._h, _p(x), C.c_size_t(x.shape[0]), _p(y)), "ismhip_mlp_forward")
+        return y
+
+    def close(self):
+        if self._h:
+            lib().ismhip_mlp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def cgfw_open(path, expect_in=0):
+    """ismhip_cgfw_open -> an opaque handle (close it with lib().ismhip_cgfw_close); raises IsmHipError with the loader's reason"""
+    h = C.c_void_p()
+    err = C.create_string_buffer(512)
+    rc = lib().ismhip_cgfw_open(os.fsencode(path), C.c_int(expect_in), C.byref(h), err, C.c_int(len(err)))
+    if rc != 0:
+        raise IsmHipError(err.value.decode())
+    return h
+
+
+def cgfw_read(path, expect_in=0):
+    """the layers of a .cgfw through the library's loader: [(W [in, out], b [out], relu), ...] as numpy copies"""
+    h = cgfw_open(path, expect_in)
+    try:
+        layers = []
+        for l in range(lib().ismhip_cgfw_layers(h)):
+            i, o, r = C.c_int(), C.c_int(), C.c_int()
+            wp, bp = C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
+            lib().ismhip_cgfw_layer(h, C.c_int(l), C.byref(i), C.byref(o), C.byref(r), C.byref(wp), C.byref(bp))
+            W = np.ctypeslib.as_array(wp, shape=(i.value, o.value)).copy()
+            b = np.ctypeslib.as_array(bp, shape=(o.value,)).copy()
+            layers.append((W, b, bool(r.value)))
+        return layers
+    finally:
+        lib().ismhip_cgfw_close(h)
+
+
+def cgfw_write(path, layers):
+    """writes [(W [in, out], b [out], relu), ...] as a .cgfw: "CGFW", version 1, the layer count, then per layer in, out, activation,
+    W row-major, b -- all little endian (include/ismhip.h)"""
+    import struct
+    with open(path, "wb") as f:
+        f.write(b"CGFW" + struct.pack("<II", 1, len(layers)))
+        for W, b, relu in layers:
+            W = np.asarray(W, "<f4"); b = np.asarray(b, "<f4")
+            if W.ndim != 2 or b.shape != (W.shape[1],):
+                raise IsmHipError("cgfw_write: W must be [in, out] and b [out]")
+            f.write(struct.pack("<III", W.shape[0], W.shape[1], 1 if relu else 0))
+            f.write(np.ascontiguousarray(W).tobytes()); f.write(np.ascontiguousarray(b).tobytes())
+
+
+def cgf(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, mlp, chunk_rows=CGF_CHUNK_ROWS, want_counts=False):
+    """The CGF rows [nkp, mlp.n_out] of features_cgf.cpp: SHOT frames at 0.75 R, keypoint normals at 0.1 R, raw histograms and the
+    embedding. Raw rows exist for chunk_rows keypoints at a time (whole objects are cut where the chunk ends); the result does not depend
+    on the chunk size."""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    R, rmin, rl = cgf_radii(radius)
+    lrf = shot_lrf(ctx, cloud, ko, kpx, kpy, kpz, rl)
+    knx, kny, knz = keypoint_normals_pca(ctx, cloud, ko, kpx, kpy, kpz, 0.1 * R)
+    out = torch.empty((n, mlp.n_out), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device)
+    step = max(1, int(chunk_rows))
+    for b in range(0, n, step):
+        e = min(n, b + step)
+        sub = (np.clip(ko.astype(np.int64), b, e) - b).astype(np.uint32)      # the keypoints [b, e) of every object
+        raw, c = cgf_raw(ctx, cloud, sub, kpx[b:e], kpy[b:e], kpz[b:e], lrf[b:e], knx[b:e], kny[b:e], knz[b:e], R, rmin, want_counts=True)
+        mlp.forward(raw, out=out[b:e])
+        cnt[b:e] = c
     return (out, cnt) if want_counts else out
 
 

@@ -100,6 +100,9 @@ public:
     DevBuf raw_lrf, raw_desc, raw_cnt;
     DevBuf raw_axis;      // SpinImage: the keypoints' looked-up normals, three runs of nkp floats
     DevBuf raw_grad;      // RIFT: the intensity gradient of every point of the batch, three floats each
+    DevBuf cgf_lrf, cgf_normal, cgf_rows;   // CGF: its own frames, the keypoints' PCA normals (three runs of nkp floats), a chunk of raw rows
+    ismhip_mlp* cgf_mlp = nullptr;          // CGF: the embedding of cgf_mlp_file on this context
+    std::string cgf_mlp_file;
 
     // ISMHIP_KNN_BINARY=0, read when the context is created: BSHOT codebooks keep the float search (A/B runs, tests; same answers)
     bool knn_binary_route = true;
@@ -112,6 +115,7 @@ public:
     }
     ~DeviceSession() {
         dropCloud();
+        if (cgf_mlp) ismhip_mlp_destroy(cgf_mlp);
         if (ctx) ismhip_ctx_destroy(ctx);
     }
     void check(int rc, const char* what) const {
@@ -558,6 +562,21 @@ FeaturesRSD::FeaturesRSD() {                     // features_rsd.cpp:19-23
     addParameter(m_use_hist, "UseFullRSDHistogram", true);
 }
 FeaturesRIFT::FeaturesRIFT() { addParameter(m_radius, "Radius", 0.1f); }   // features_rift.cpp:20-23
+FeaturesCGF::FeaturesCGF() {                     // features_cgf.cpp:22-25
+    addParameter(m_radius, "Radius", 0.1f);
+    addParameter(m_model_file, "CgfModelFile", std::string("embed_model_910000.cgfw"));
+}
+FeaturesCGF::~FeaturesCGF() { if (m_weights) ismhip_cgfw_close(m_weights); }
+void FeaturesCGF::iPostInitConfig() {
+    Features::iPostInitConfig();
+    if (m_weights) { ismhip_cgfw_close(m_weights); m_weights = nullptr; m_dim = 0; }
+    char err[512] = "";
+    if (ismhip_cgfw_open(m_model_file.c_str(), ISMHIP_CGF_RAW_DIM, &m_weights, err, (int)sizeof(err)) != ISMHIP_OK)
+        throw RuntimeException(std::string("CGF: CgfModelFile: ") + err);
+    int out = 0;
+    ismhip_cgfw_layer(m_weights, ismhip_cgfw_layers(m_weights) - 1, nullptr, &out, nullptr, nullptr, nullptr);
+    m_dim = out;
+}
 void FeaturesCospair::checkInput(const PointCloud& cloud) const {
     if (!cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("CoSPAIR needs coloured point clouds");
 }
@@ -619,6 +638,37 @@ void FeaturesRIFT::iComputeDescriptors(DeviceSession& s, const float*, float* de
     s.check(ismhip_intensity_gradients(s.ctx, s.cloud, m_radius, s.raw_grad.as<float>(), nullptr), "ismhip_intensity_gradients");
     s.check(ismhip_rift(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, ISMHIP_RIFT_DISTANCE_BINS,
                         ISMHIP_RIFT_GRADIENT_BINS, s.raw_grad.as<float>(), desc_out, counts_out), "ismhip_rift");
+}
+
+// features_cgf.cpp:46-68 -> cgf.cpp:64-165 and embedding.py: the three lengths after their trip through std::to_string, CGF's own frames and
+// keypoint normals, then raw rows and embedding in chunks of keypoints (262 144 raw rows would be 2.35 GB; the chunk size does not show)
+void FeaturesCGF::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    if (!m_weights) throw RuntimeException("CGF: no weights loaded (CgfModelFile)");
+    if (!s.cgf_mlp || s.cgf_mlp_file != m_model_file) {
+        if (s.cgf_mlp) { ismhip_mlp_destroy(s.cgf_mlp); s.cgf_mlp = nullptr; }
+        s.check(ismhip_mlp_from_cgfw(s.ctx, m_weights, &s.cgf_mlp), "ismhip_mlp_from_cgfw");
+        s.cgf_mlp_file = m_model_file;
+    }
+    auto rounded = [](double v) { char b[64]; snprintf(b, sizeof(b), "%f", v); return strtod(b, nullptr); };   // std::to_string, std::stod
+    const double R = rounded((double)m_radius), rmin = rounded(m_radius * 0.05), rl = rounded(m_radius * 0.75);
+    const uint32_t nkp = s.kp_off.back();
+    const float *kx = s.kx.as<float>(), *ky = s.ky.as<float>(), *kz = s.kz.as<float>();
+    s.cgf_lrf.reserve((size_t)nkp * 9 * 4); s.cgf_normal.reserve((size_t)nkp * 3 * 4);
+    float* nrm = s.cgf_normal.as<float>();
+    s.check(ismhip_shot_lrf(s.ctx, s.cloud, s.kp_off.data(), kx, ky, kz, (float)rl, s.cgf_lrf.as<float>()), "ismhip_shot_lrf");
+    s.check(ismhip_keypoint_normals_pca(s.ctx, s.cloud, s.kp_off.data(), kx, ky, kz, (float)(0.1 * R), nrm, nrm + nkp, nrm + 2 * (size_t)nkp),
+            "ismhip_keypoint_normals_pca");
+    uint32_t chunk = 32768;
+    if (const char* e = getenv("ISMHIP_CGF_CHUNK")) { const long v = atol(e); if (v > 0) chunk = (uint32_t)v; }   // tests: the result must not move
+    s.cgf_rows.reserve((size_t)std::min(chunk, nkp) * ISMHIP_CGF_RAW_DIM * 4);
+    std::vector<uint32_t> sub(s.kp_off.size());
+    for (uint32_t b = 0; b < nkp; b += chunk) {
+        const uint32_t e = std::min(nkp, b + chunk);
+        for (size_t o = 0; o < sub.size(); ++o) sub[o] = std::min(std::max(s.kp_off[o], b), e) - b;   // the keypoints [b, e) of every object
+        s.check(ismhip_cgf_raw(s.ctx, s.cloud, sub.data(), kx + b, ky + b, kz + b, s.cgf_lrf.as<float>() + (size_t)b * 9, nrm + b, nrm + nkp + b,
+                               nrm + 2 * (size_t)nkp + b, R, rmin, s.cgf_rows.as<float>(), counts_out + b), "ismhip_cgf_raw");
+        s.check(ismhip_mlp_forward(s.ctx, s.cgf_mlp, s.cgf_rows.as<float>(), e - b, desc_out + (size_t)b * m_dim), "ismhip_mlp_forward");
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1627,7 +1677,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesSpinImage::getTypeStatic()) return new FeaturesSpinImage();
     if (type == FeaturesRSD::getTypeStatic()) return new FeaturesRSD();
     if (type == FeaturesRIFT::getTypeStatic()) return new FeaturesRIFT();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, RIFT, SpinImage, RSD, CoSPAIR)");
+    if (type == FeaturesCGF::getTypeStatic()) return new FeaturesCGF();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CGF, RIFT, SpinImage, RSD, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT/CGF   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp, features_cgf.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -417,6 +417,31 @@ protected:
     void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
 private:
     float m_radius;
+};
+
+// features/features_cgf.{h,cpp} -> third_party/cgf/cgf.cpp and embedding.py (ismhip_keypoint_normals_pca, ismhip_cgf_raw, ismhip_mlp_forward,
+// DESIGN.md section 4.20): the 2244-bin spherical histogram of the Radius ball in CGF's own frame (SHOT at 0.75 Radius, negated against a PCA
+// normal at 0.1 Radius), embedded by the perceptron of CgfModelFile. Radius is the reference's one parameter; CgfModelFile is this library's
+// (the reference hard-codes "embed_model_910000.ckpt" in the working directory and leaves the process to run it): a .cgfw container
+// (include/ismhip.h, tools/cgf_weights.py), read when the configuration is read -- the descriptor's length is the file's. The frames of
+// ReferenceFrameRadius / ReferenceFrameType only decide which keypoints stay, as for every Features type. Not an ISM3D_FEATURE: its length
+// follows the file.
+class FeaturesCGF : public Features {
+public:
+    FeaturesCGF();
+    ~FeaturesCGF() override;
+    static std::string getTypeStatic() { return "CGF"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return m_dim; }
+protected:
+    void iPostInitConfig() override;                 // + the weights file: every refusal of the loader, and the length
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+private:
+    float m_radius;
+    std::string m_model_file;
+    int m_dim = 0;
+    ismhip_cgfw* m_weights = nullptr;
 };
 
 // ---- activation strategy + codebook ----------------------------------------------------------------------

@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD" | "RIFT"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD" | "RIFT" | "CGF"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -77,6 +77,8 @@ class IsmConfig:
     short_color_shot_dims: int = 32      # Features(SHORT_CSHOT).ShortColorShotDims: cells of the colour grid, 8 | 16 | 24 | 32 | 64 | 96 | 128
     short_color_shot_hist_size: int = 15 # ShortColorShotHistSize: colour-distance bins per cell
     use_full_rsd_histogram: bool = True  # Features(RSD).UseFullRSDHistogram: the 25-bin pair histogram; false: the two principal radii
+    cgf_model: str = "embed_model_910000.cgfw"   # Features(CGF).CgfModelFile: the embedding's weights (.cgfw, tools/cgf_weights.py); sets dim
+    cgf_chunk_rows: int = capi.CGF_CHUNK_ROWS     # keypoints whose 2244-float raw rows exist at a time (no effect on the result)
 
     def __post_init__(self):
         if self.lrf_type not in capi.LRF_TYPES:
@@ -100,6 +102,8 @@ class IsmConfig:
             return self.short_shot_grid[0] + self.short_cshot_color_grid[0] * self.short_color_shot_hist_size
         if self.feature == "RSD":
             return capi.RSD_DIM if self.use_full_rsd_histogram else capi.RSD_RADII_DIM
+        if self.feature == "CGF":
+            return capi.cgfw_read(self.cgf_model, capi.CGF_RAW_DIM)[-1][0].shape[1]      # D is the file's (32 or 40 in the reference's models)
         return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM, "RIFT": capi.RIFT_DIM}[self.feature]
 
     @property
@@ -194,6 +198,7 @@ class Recognizer:
     def __init__(self, ctx, cfg: IsmConfig):
         self.ctx, self.cfg = ctx, cfg
         self.codebook = None
+        self._cgf_mlp = None             # the CGF embedding, loaded with the first batch
 
     # -- ImplicitShapeModel::computeFeatures step f + removeNaNFeatures -------------------------------------
     def compute_features(self, b: DeviceBatch, want_counts=False):
@@ -237,8 +242,14 @@ class Recognizer:
             # no frame enters the descriptor; the dense intensity gradients of the cloud first, then the 8 x 16 histogram (features_rift.cpp:53-78)
             grad = capi.intensity_gradients(ctx, cloud, c.radius)
             desc, cnt = capi.rift(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, grad, want_counts=True)
+        elif c.feature == "CGF":
+            # its own frame (SHOT at 0.75 Radius, negated against a PCA normal at 0.1 Radius), the 2244-bin spherical histogram, then the
+            # embedding, in chunks of keypoints (features_cgf.cpp:46-68)
+            if self._cgf_mlp is None:
+                self._cgf_mlp = capi.Mlp.from_file(ctx, c.cgf_model, capi.CGF_RAW_DIM)
+            desc, cnt = capi.cgf(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, self._cgf_mlp, chunk_rows=c.cgf_chunk_rows, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, RIFT, SpinImage, RSD, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CGF, RIFT, SpinImage, RSD, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
