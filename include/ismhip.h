@@ -660,6 +660,11 @@ int  ismhip_codebook_stage2_dims(const ismhip_codebook* cb, float* energy_out);
  * constants. Synchronises. */
 int  ismhip_codebook_rotate_probe(ismhip_ctx* ctx, const ismhip_codebook* cb, int stage, int nq, const float* q, uint16_t* image_out,
                                   float* qn2_out, float* qn2h_out, float* r_out_h, float* consts_out_h);
+/* Diagnostic: the CIELab conversion every colour feature shares (PCL's RGB2CIELAB through the context's two LUTs, LUT index clamped to
+ * 0..3999), one thread per colour. rgba: device [n] packed 0x00RRGGBB, bits 24..31 ignored. out: device [3 n], (L, a, b) per colour as
+ * CoSPAIR takes them (L <= 100, |a|, |b| <= 120), or, with normalised != 0, (L / 100, a / 120, b / 120) as CSHOT, SHORT_CSHOT and the
+ * culling colour score take them. Asynchronous on the ctx stream. Off every hot path. */
+int  ismhip_rgb2lab(ismhip_ctx* ctx, int n, const uint32_t* rgba, int normalised, float* out);
 
 /* The resident integer image of a codebook whose every element is exactly 0.0f or 1.0f (-0.0f counts as 0), e.g. B-SHOT rows
  * (features/features_bshot.cpp:96-99): int8 rows zero-padded to the search kernel's K step (128) and the number of ones per row.

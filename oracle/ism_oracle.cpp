@@ -1117,6 +1117,18 @@ void ismref_rgb2lab(uint32_t rgba, float* L, float* a, float* b) {
     unsigned char r, g, bb; unpack_rgb(rgba, r, g, bb);
     rgb2lab(r, g, bb, *L, *a, *b);
 }
+// the same for n packed colours in one call: out[3 i .. 3 i + 2] = (L, a, b), divided by (100, 120, 120) when normalised != 0
+int ismref_rgb2lab_n(int64_t n, const uint32_t* rgba, int normalised, float* out) {
+    if (n < 0 || (n > 0 && (!rgba || !out))) return -1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+        unsigned char r, g, bb; unpack_rgb(rgba[i], r, g, bb);
+        float L, a, b; rgb2lab(r, g, bb, L, a, b);
+        if (normalised) { L /= 100.0f; a /= 120.0f; b /= 120.0f; }
+        out[3 * i] = L; out[3 * i + 1] = a; out[3 * i + 2] = b;
+    }
+    return 0;
+}
 int ismref_pair_features(const float* p1, const float* n1, const float* p2, const float* n2, float* f4_out) {
     return pair_features(p1, n1, p2, n2, f4_out[0], f4_out[1], f4_out[2], f4_out[3]) ? 1 : 0;
 }

@@ -70,6 +70,8 @@ int  ismref_centroids(int n_obj, const uint32_t* pt_offsets, const float* x, con
 int  ismref_center_dist(int n_obj, const uint32_t* pt_offsets, const float* x, const float* y, const float* z,
                         const uint32_t* kp_offsets, const float* kpx, const float* kpy, const float* kpz, float* out);
 void ismref_rgb2lab(uint32_t rgba, float* L, float* a, float* b);
+/* n colours in one call: out[3 n] = (L, a, b) per colour, normalised (L / 100, a / 120, b / 120) when normalised != 0 */
+int  ismref_rgb2lab_n(int64_t n, const uint32_t* rgba, int normalised, float* out);
 /* single pair feature of FPFH (pcl::computePairFeatures); returns 1 when valid */
 int  ismref_pair_features(const float* p1, const float* n1, const float* p2, const float* n2, float* f4_out);
 

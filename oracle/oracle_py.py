@@ -137,6 +137,15 @@ def rgb2lab(rgba):
     return L.value, a.value, b.value
 
 
+def rgb2lab_n(rgba, normalised=False):
+    """ismref_rgb2lab_n: CIELab of every packed colour in one call -> float32 [n, 3]"""
+    c = _u(rgba).reshape(-1)
+    out = np.empty((len(c), 3), np.float32)
+    rc = lib().ismref_rgb2lab_n(C.c_int64(len(c)), _p(c), C.c_int(1 if normalised else 0), _p(out))
+    assert rc == 0
+    return out
+
+
 def pair_features(p1, n1, p2, n2):
     p1, n1, p2, n2 = map(_f, (p1, n1, p2, n2))
     out = np.zeros(4, np.float32)

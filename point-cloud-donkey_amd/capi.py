@@ -37,7 +37,7 @@ EXPORTS = [
     "ismhip_iss3d_saliency", "ismhip_iss3d_keypoints", "ismhip_keypoint_normals", "ismhip_spin_image", "ismhip_rsd",
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
-    "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw",
+    "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
 ]
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
@@ -328,6 +328,15 @@ def cshot1344(ctx, cloud, kp_offsets, kpx, kpy, kpz, kp_rgba, lrf, radius, want_
     ctx.check(lib().ismhip_cshot1344(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(kp_rgba), _p(lrf), C.c_float(radius),
                                      _p(out), _p(cnt)), "ismhip_cshot1344")
     return (out, cnt) if want_counts else out
+
+
+def rgb2lab(ctx, rgba, normalised=False):
+    """ismhip_rgb2lab (diagnostic): CIELab of the packed colours rgba (int32 device tensor [n]) -> float32 [n, 3] on the same device"""
+    torch = _torch()
+    assert rgba.dim() == 1 and rgba.dtype == torch.int32
+    out = torch.empty((rgba.shape[0], 3), dtype=torch.float32, device=rgba.device)
+    ctx.check(lib().ismhip_rgb2lab(ctx._h, C.c_int(rgba.shape[0]), _p(rgba), C.c_int(1 if normalised else 0), _p(out)), "ismhip_rgb2lab")
+    return out
 
 
 def short_shot(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, bins=(2, 2, 8), min_radius=0.0, log_radius=False, want_counts=False):

@@ -230,3 +230,26 @@ int ismhip_timer_get(ismhip_ctx* ctx, const char* name, double* ms_out, int64_t*
 }
 
 }  // extern "C"
+
+namespace {
+// one thread per colour: rgb2lab / rgb2lab_norm of common.h on the context's LUTs, as every descriptor kernel calls them
+__global__ __launch_bounds__(256) void k_rgb2lab_probe(int n, const uint32_t* __restrict__ rgba, int normalised,
+                                                       const float* __restrict__ lut_srgb, const float* __restrict__ lut_sxyz, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float L, A, B;
+    if (normalised) rgb2lab_norm(lut_srgb, lut_sxyz, rgba[i], L, A, B);
+    else rgb2lab(lut_srgb, lut_sxyz, rgba[i], L, A, B);
+    float* o = out + (size_t)i * 3;
+    o[0] = L; o[1] = A; o[2] = B;
+}
+}  // namespace
+
+extern "C" int ismhip_rgb2lab(ismhip_ctx* ctx, int n, const uint32_t* rgba, int normalised, float* out) {
+    if (!ctx || n < 0 || (n > 0 && (!rgba || !out))) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "rgb2lab: bad argument");
+    if (n == 0) return ISMHIP_OK;
+    hipLaunchKernelGGL(k_rgb2lab_probe, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, ctx->stream, n, rgba, normalised,
+                       (const float*)ctx->lut_srgb, (const float*)ctx->lut_sxyz, out);
+    ISM_CHECK_LAUNCH(ctx, "k_rgb2lab_probe");
+    return ISMHIP_OK;
+}

@@ -204,7 +204,7 @@ def test_oracle_shot352_matches_the_restatement_on_the_boundary_lattice(ora):
         p, n = fs.lattice(fr)
         for r in fs.LATTICE_RADII:
             od, oc = ora.shot352(np.array([0, len(p)], np.uint32), *fs.cols(p), *fs.cols(n), np.array([0, 1], np.uint32), z, z, z, fr.reshape(1, 9), r)
-            rd, rc = shot_ref.shot352(p, n, np.zeros(3), fr, r)
+            rd, rc, _ = shot_ref.shot352(p, n, np.zeros(3), fr, r)
             assert oc[0] == rc
             worst = max(worst, float(np.abs(od[0] - rd).max()))
     print("lattice: oracle vs restatement", worst)
@@ -221,7 +221,7 @@ def test_oracle_shot352_matches_the_restatement_on_dense_balls(ora):
     od, oc = ora.shot352(po, *fs.cols(p), *fs.cols(n), ko, *fs.cols(sel), lrf, fs.DENSE_RADIUS)
     worst = 0.0
     for i in range(3):
-        rd, rc = shot_ref.shot352(p, n, sel[i], lrf[i], fs.DENSE_RADIUS)
+        rd, rc, _ = shot_ref.shot352(p, n, sel[i], lrf[i], fs.DENSE_RADIUS)
         assert rc == oc[i] and rc > 5000
         worst = max(worst, float(np.abs(od[i] - rd).max()))
     print("dense: oracle vs restatement", worst)

@@ -149,6 +149,23 @@ def test_thin_dense_batch_matches_oracle(pkg, gpu, ora):
     assert np.isfinite(want_lrf).all() and wcnt[:80].max() > 40000 and np.isfinite(want_fpfh).all()
 
 
+@pytest.mark.parametrize("key", [WIDE_FUSED, WIDE_FIVE, THIN])
+def test_cshot_sector_sums_agree_between_the_channels(pkg, gpu, key):
+    """In every sector the 11 shape bins and the 31 colour bins of a CSHOT row sum to the same value: a home neighbour adds 1 + winc to
+    either channel and the side deposits are the same numbers. Needs no reference; the bound (shot_ref_scenes.sector_sum_bound: float
+    rounding of the two home weights, 2^-29 per fixed-point deposit, the output's cast and divide) is derived there. Balls of 5 000 to
+    40 000 neighbours: a deposit lost in one channel of a sector moves its sum by 1 / N, a thousand bounds."""
+    import shot_ref_scenes as srs
+    _, got = default_outputs(pkg, gpu, key)
+    fin = np.isfinite(got["cshot"][:, 0])
+    a, c = srs.sector_sums(got["cshot"][fin])
+    diff, bound = np.abs(a - c), srs.sector_sum_bound(a, c)
+    print("%s: largest sector-sum difference %.3g (bound there %.3g) at sector sums up to %.3g, %d rows, up to %d neighbours"
+          % (key, diff.max(), bound.flat[np.argmax(diff)], a.max(), fin.sum(), got["ccnt"].max()))
+    assert fin.sum() >= 80 and got["ccnt"].max() > 20000
+    assert (diff <= bound).all()
+
+
 @pytest.mark.parametrize("env,value,key", [("ISMHIP_SHOT_VAR", "2", WIDE_FUSED), ("ISMHIP_XCD_MAP", "0", WIDE_FUSED)] +
                          [("ISMHIP_GRID_XFRAC", str(v), THIN) for v in fs.XFRACS])
 def test_switches_leave_the_bytes_alone(pkg, gpu, ora, env, value, key, monkeypatch):
