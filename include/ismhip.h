@@ -101,7 +101,7 @@ int  ismhip_ctx_destroy(ismhip_ctx* ctx);
 int  ismhip_sync(ismhip_ctx* ctx);
 const char* ismhip_last_error(const ismhip_ctx* ctx);
 /* per-kernel device timers (hipEvent on the ctx stream). Enable, run, sync, then read.
- * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select","intensity_gradients","rift","keypoint_normals_pca","cgf_raw","mlp_forward"; ismhip_knn_threshold: "knn_threshold" and its
+ * name: "grid","lrf","shot352","cshot1344","fpfh33","short_shot","short_cshot","cospair","bshot","knn","knn_binary","cast_votes","maxima","filter_sor","filter_ror","filter_compact","rank_scores","rank_select","global_short_shot","global_shot352","global_vfh","iss3d_saliency","iss3d_nms","keypoint_normals","spin_image","rsd","culling_pc","culling_scores","culling_select","intensity_gradients","rift","keypoint_normals_pca","cgf_raw","mlp_forward","esf_local"; ismhip_knn_threshold: "knn_threshold" and its
  * parts "knn_threshold_sweep", "knn_threshold_eval", "knn_threshold_exact", "knn_threshold_compact". Returns accumulated
  * milliseconds and launch count since the last reset. "knn_threshold_mfma_launches" is a counter (ms_out = number of radius
  * searches whose candidate sweep ran on the matrix cores), valid without timers; "knn_threshold_overflow_queries" the number of
@@ -347,6 +347,49 @@ int  ismhip_spin_image(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_
 int  ismhip_rsd(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                 const float* kpx, const float* kpy, const float* kpz, float radius, int full_histogram,
                 float* desc_out, uint32_t* neighbour_count_out);
+/* FeaturesESFLocal::iComputeDescriptors (features/features_esf_local.cpp:28-100) -> PCL 1.10 ESFEstimation (computeESF, lci, voxelize9,
+ * scale_points_unit_sphere) on the Radius ball of every keypoint: the "ensemble of shape functions", desc_out[nkp * 640] (ISMHIP_ESF_DIM).
+ * PCL draws with an unseeded rand(); this is the library's definition (deviations E1-E9). Per keypoint q, float32
+ * throughout, every product and sum unfused and in the written order:
+ *  1 neighbours N: the finite cloud points with d2 < (float)((double)radius * radius), d2 = (dx*dx + dy*dy) + dz*dz, the keypoint's own
+ *    cloud point included; n = |N| -> neighbour_count_out[nkp] (may be NULL); N is indexed 0..n-1 in ASCENDING CLOUD INDEX; any n is
+ *    taken: the first 1024 of them (the staging capacity; env ISMHIP_ESF_CAP = 1..1024 lowers it) are read from LDS, the others through
+ *    a work list in device memory, never truncated;
+ *  2 the row is NaN AS A WHOLE (and its bin counts 0) when n < 3, the keypoint is not finite, the ball misses the object (n = 0), the
+ *    scale of step 3 is degenerate or the attempt cap of step 5 is reached;
+ *  3 centroid c = (float)((double)q + mean(p - q)), the sum of the (double) differences in 64-bit fixed point, hence free of order;
+ *    m = max |p - c|, |v| = sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z) of the float differences; m = 0, m or 32.0f / m not finite: NaN row;
+ *    g = (p - c) * (32.0f / m) per coordinate; scale_out[nkp * 4] (may be NULL) = c.x, c.y, c.z, m (NaN where n < 3 or q is not finite);
+ *  4 voxel per axis v = g < 0 ? floorf(g) + 32 : ceilf(g) + 31, clamped to 0..63; every point sets the cells v + {-1,0,1}^3 that lie in
+ *    the 64^3 bit set;
+ *  5 attempt t = 0, 1, 2, ... draws i_k = mulhi32(h(seed, 3t + k), n), k = 0, 1, 2 (mulhi32: the upper half of the 64-bit product) with
+ *      h(s, x): v = x * 0x9E3779B1 + s;  v ^= v >> 16;  v *= 0x7FEB352D;  v ^= v >> 15;  v *= 0x846CA68B;  v ^= v >> 16   (mod 2^32)
+ *    p1, p2, p3 = g[i_0], g[i_1], g[i_2]; v21 = p2 - p1, v31 = p3 - p1, v23 = p2 - p3; a, b, c = |v21|, |v31|, |v23|;
+ *    s = ((a + b) + c) * 0.5f; H = ((s*(s-a))*(s-b))*(s-c). Rejected: two equal indices; H <= 0.001f or not finite; one of
+ *    th = (int)floorf(acosf(|u . w|) / (float)(pi/2) * 63.0f + 0.5f) outside 0..63 or NaN, for (u, w) = (v21, v31), (v23, v31), (v23, v21)
+ *    each divided by its length. The samples are the first n_samples accepted attempts in order of t; fewer than n_samples among the
+ *    attempts t < 8 * n_samples: NaN row;
+ *  6 per sample the lines p1 -> p2 (length a), p1 -> p3 (b), p2 -> p3 (c) are walked from voxel to voxel by PCL's lci: a 3-D Bresenham
+ *    line whose driving axis is the longest (ties x, then y, then z), L its length in cells; the cells at steps 0 .. max(L, 1) - 1 are
+ *    visited (as PCL's loop, the walk stops one step short of the end voxel); visited = max(L, 1), inside = the occupied ones. Line
+ *    class: IN if inside >= visited - 1, else OUT if inside <= 7, else MIXED with ratio = (float)inside / (float)visited, which adds to
+ *    the ratio block at floorf(ratio * 63.0f + 0.5f). Triangle class over the three lines: OUT if sum inside <= 21, else IN if
+ *    sum visited - sum inside < 4, else MIXED. A3: bins th1, th2, th3 of the triangle's class, a third each;
+ *  7 after all samples, D3 = sqrtf(sqrtf(H)) goes to bin floorf(D3 / max D3 * 63.0f + 0.5f) of the triangle's class, every line's length d
+ *    to bin floorf(d / max d * 63.0f + 0.5f) of the D2 block of the line's class, the maxima over all samples;
+ *  8 ten blocks of 64 bins: A3 in, out, mixed (weight 0.5 each), D3 in (0.5), out (0.5), mixed (1), D2 in (0.5), out (2), mixed (2), ratio
+ *    (1). In sixths every deposit is an integer: A3 1, D3 3 / 3 / 6, D2 3 / 12 / 12, ratio 6; N_i -> bin_counts_out[nkp * 640] (may be
+ *    NULL), row[i] = (float)N_i / (float)sum N.
+ * Integer counts, float maxima and fixed-point sums only: two calls, any grid cell size and any staging capacity give the same bytes, and
+ * two identical neighbourhoods anywhere in a batch get identical rows. The host layer calls with ISMHIP_ESF_SAMPLES and ISMHIP_ESF_SEED.
+ * Refused with ISMHIP_ERR_INVALID ("esf_local: bad argument"): a missing array, a radius that is not positive and finite, n_samples
+ * outside 1..65536. Timer "esf_local". */
+#define ISMHIP_ESF_DIM 640          /* ismhip_esf_local: 10 blocks of 64 bins */
+#define ISMHIP_ESF_SAMPLES 20000    /* PCL's sample_size */
+#define ISMHIP_ESF_SEED 0x45534631u /* "ESF1" */
+int  ismhip_esf_local(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                      const float* kpx, const float* kpy, const float* kpz, float radius, int n_samples, uint32_t seed,
+                      float* desc_out, uint32_t* neighbour_count_out, uint32_t* bin_counts_out, float* scale_out);
 /* The dense first half of FeaturesRIFT::iComputeDescriptors (features/features_rift.cpp:29-96): PointCloudXYZRGBtoXYZI (:47-51), then PCL 1.10
  * IntensityGradientEstimation (:53-62) over the Radius ball of every cloud point. This library's definition (deviations D1, D2):
  *  - intensity I = (0.299f*R + 0.587f*G) + 0.114f*B in float, unfused, from the 8-bit channels of the cloud's 0x00RRGGBB colours;
@@ -606,7 +649,7 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image / ismhip_rsd, whose rows are NaN AS A WHOLE
+/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image / ismhip_rsd / ismhip_esf_local, whose rows are NaN AS A WHOLE
  * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
  * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
  * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */

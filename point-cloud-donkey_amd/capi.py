@@ -38,6 +38,7 @@ EXPORTS = [
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
+    "ismhip_esf_local",
 ]
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
@@ -466,6 +467,29 @@ def rsd(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, full_histogram=True, want
     ctx.check(lib().ismhip_rsd(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(1 if full_histogram else 0),
                                _p(out), _p(cnt)), "ismhip_rsd")
     return (out, cnt) if want_counts else out
+
+
+ESF_DIM = 640                # ten blocks of 64 bins
+ESF_SAMPLES = 20000          # PCL's sample_size (ISMHIP_ESF_SAMPLES)
+ESF_SEED = 0x45534631        # ISMHIP_ESF_SEED
+
+
+def esf_local(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, n_samples=ESF_SAMPLES, seed=ESF_SEED, want_counts=False, want_bins=False,
+              want_scale=False):
+    """ismhip_esf_local -> [nkp, 640] (the ensemble of shape functions of every keypoint's ball); then, for every want_* set and in this
+    order: the neighbours per keypoint [nkp] int32, the integer numerators of the bins in sixths [nkp, 640] int32, and (centroid x, y, z,
+    largest distance from it) [nkp, 4] float32"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, ESF_DIM), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    bins = torch.empty((n, ESF_DIM), dtype=torch.int32, device=kpx.device) if want_bins else None
+    scale = torch.empty((n, 4), dtype=torch.float32, device=kpx.device) if want_scale else None
+    ctx.check(lib().ismhip_esf_local(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(int(n_samples)),
+                                     C.c_uint32(int(seed) & 0xffffffff), _p(out), _p(cnt), _p(bins), _p(scale)), "ismhip_esf_local")
+    extra = [t for t in (cnt, bins, scale) if t is not None]
+    return (out, *extra) if extra else out
 
 
 RIFT_DISTANCE_BINS, RIFT_GRADIENT_BINS = 8, 16       # features_rift.cpp:38-39

@@ -562,6 +562,7 @@ FeaturesRSD::FeaturesRSD() {                     // features_rsd.cpp:19-23
     addParameter(m_use_hist, "UseFullRSDHistogram", true);
 }
 FeaturesRIFT::FeaturesRIFT() { addParameter(m_radius, "Radius", 0.1f); }   // features_rift.cpp:20-23
+FeaturesESFLocal::FeaturesESFLocal() { addParameter(m_radius, "Radius", 0.1f); }   // features_esf_local.cpp:21
 FeaturesCGF::FeaturesCGF() {                     // features_cgf.cpp:22-25
     addParameter(m_radius, "Radius", 0.1f);
     addParameter(m_model_file, "CgfModelFile", std::string("embed_model_910000.cgfw"));
@@ -638,6 +639,11 @@ void FeaturesRIFT::iComputeDescriptors(DeviceSession& s, const float*, float* de
     s.check(ismhip_intensity_gradients(s.ctx, s.cloud, m_radius, s.raw_grad.as<float>(), nullptr), "ismhip_intensity_gradients");
     s.check(ismhip_rift(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, ISMHIP_RIFT_DISTANCE_BINS,
                         ISMHIP_RIFT_GRADIENT_BINS, s.raw_grad.as<float>(), desc_out, counts_out), "ismhip_rift");
+}
+// features_esf_local.cpp: PCL's ESFEstimation per keypoint ball; the sample count and the seed of the draws are the library's constants
+void FeaturesESFLocal::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    s.check(ismhip_esf_local(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, ISMHIP_ESF_SAMPLES,
+                             ISMHIP_ESF_SEED, desc_out, counts_out, nullptr, nullptr), "ismhip_esf_local");
 }
 
 // features_cgf.cpp:46-68 -> cgf.cpp:64-165 and embedding.py: the three lengths after their trip through std::to_string, CGF's own frames and
@@ -1678,7 +1684,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesRSD::getTypeStatic()) return new FeaturesRSD();
     if (type == FeaturesRIFT::getTypeStatic()) return new FeaturesRIFT();
     if (type == FeaturesCGF::getTypeStatic()) return new FeaturesCGF();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CGF, RIFT, SpinImage, RSD, CoSPAIR)");
+    if (type == FeaturesESFLocal::getTypeStatic()) return new FeaturesESFLocal();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR)");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();

@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT/CGF   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp, features_cgf.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT/CGF/ESF_LOCAL   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp, features_cgf.cpp, features_esf_local.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -413,6 +413,21 @@ public:
     int getDescriptorLength() const override { return ISMHIP_RIFT_DIM; }
     bool needsColor() const override { return true; }
     void checkInput(const PointCloud& cloud) const override;   // a cloud without colours throws
+protected:
+    void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
+private:
+    float m_radius;
+};
+// features/features_esf_local.{h,cpp} -> PCL's ESFEstimation on the Radius ball of every keypoint (ismhip_esf_local, DESIGN.md section
+// 4.21): twenty thousand point triples, their lines traced through a 64^3 occupancy grid of the ball, 640 floats. Radius is the one
+// parameter; no normals, no colour and no frame enter the row. The frames only decide which keypoints stay.
+class FeaturesESFLocal : public Features {
+public:
+    FeaturesESFLocal();
+    static std::string getTypeStatic() { return "ESF_LOCAL"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const override { return m_radius; }
+    int getDescriptorLength() const override { return ISMHIP_ESF_DIM; }
 protected:
     void iComputeDescriptors(DeviceSession& s, const float* lrf9, float* desc_out, uint32_t* counts_out) const override;
 private:

@@ -17,7 +17,7 @@ from . import capi
 
 @dataclass
 class IsmConfig:
-    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD" | "RIFT" | "CGF"   (Features.Type)
+    feature: str = "SHOT"            # "SHOT" | "CSHOT" | "FPFH" | "SHORT_SHOT" | "SHORT_CSHOT" | "CoSPAIR" | "BSHOT" | "SpinImage" | "RSD" | "RIFT" | "CGF" | "ESF_LOCAL"   (Features.Type)
     radius: float = 0.4              # Features.Radius
     lrf_radius: float = 0.3          # Features.ReferenceFrameRadius
     lrf_type: str = "SHOT"           # Features.ReferenceFrameType: "SHOT" | "SHOTNA" (z sign voted by the cloud's normals)
@@ -104,7 +104,8 @@ class IsmConfig:
             return capi.RSD_DIM if self.use_full_rsd_histogram else capi.RSD_RADII_DIM
         if self.feature == "CGF":
             return capi.cgfw_read(self.cgf_model, capi.CGF_RAW_DIM)[-1][0].shape[1]      # D is the file's (32 or 40 in the reference's models)
-        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM, "RIFT": capi.RIFT_DIM}[self.feature]
+        return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM, "RIFT": capi.RIFT_DIM,
+                "ESF_LOCAL": capi.ESF_DIM}[self.feature]
 
     @property
     def metric(self):
@@ -248,8 +249,12 @@ class Recognizer:
             if self._cgf_mlp is None:
                 self._cgf_mlp = capi.Mlp.from_file(ctx, c.cgf_model, capi.CGF_RAW_DIM)
             desc, cnt = capi.cgf(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, self._cgf_mlp, chunk_rows=c.cgf_chunk_rows, want_counts=True)
+        elif c.feature == "ESF_LOCAL":
+            # no normal, no colour and no frame enters the descriptor: point triples of the ball and their lines through its occupancy
+            # grid (features_esf_local.cpp); the sample count and the seed are the library's constants, for train() and detect() alike
+            desc, cnt = capi.esf_local(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, CGF, RIFT, SpinImage, RSD, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
