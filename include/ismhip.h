@@ -81,6 +81,8 @@ extern "C" {
 #define ISMHIP_RIFT_GRADIENT_BINS 16 /* rift_gradient_bins, :39 */
 #define ISMHIP_RIFT_DIM 128         /* 8 * 16 */
 #define ISMHIP_VFH_DIM 308         /* ismhip_global_vfh: 4 shape blocks of 45 bins + 128 viewpoint bins */
+#define ISMHIP_GASD_DIM 984        /* ismhip_global_gasd with colour: 6^3 shape bins + 4^3 cells x 12 hue bins */
+#define ISMHIP_GASD_SHAPE_DIM 512  /* without colour: the 216 shape bins followed by 296 zeros (pcl::GASDSignature512) */
 #define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
 
 typedef struct ismhip_ctx      ismhip_ctx;
@@ -540,6 +542,38 @@ int  ismhip_global_shot352(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_reg
 int  ismhip_global_vfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
                        const float* region_radius, const float viewpoint[3], int fill_size_component, uint32_t* n_sel_out, float* centroid_out,
                        float* radius_out, float* normal_centroid_out, float* desc_out, uint32_t* count_out);
+/* ismhip_global_gasd: FeaturesGASD::iComputeDescriptors (features/features_gasd.cpp:25-91): pcl::GASDColorEstimation with its default
+ * constructor (shape half-grid 3, colour half-grid 2, 12 hue bins, NO interpolation on either grid) over the region, the view direction
+ * the caller's (PCL's default is (0, 0, 1)). PCL is external: this is the library's own statement of PCL 1.10 gasd.hpp (DESIGN.md
+ * section 4.22 names the deviations); parity with PCL is not pinned. Region, n_sel, centroid c and radius are those of the three entries
+ * above, bit for bit on the same regions. n_sel = 0: NaN centroid, radius 0, NaN frame, NaN row. n_sel < 2: NaN frame and NaN row
+ * (PCL's increment 100 / (n - 1) is infinite there). Otherwise, over the selected points p, d = p - c per component in float:
+ *   covariance: the six products of d in double, summed in a fixed order, NOT normalised (pcl::computeCovarianceMatrix).
+ *   frame (frame9_out[n_regions*9], rows x, y, z; double eigenvectors cast to float): z = eigenvector of the smallest eigenvalue,
+ *     negated if z . view_direction > 0; x = eigenvector of the largest; the sign of x (PCL leaves it to its solver) is defined here:
+ *     with t = (x.x*d.x + x.y*d.y) + x.z*d.z in float, unfused, x is negated if more selected points have t < 0 than t > 0; on equal
+ *     counts x is signed so that its component of largest magnitude (lowest index on a tie) is positive; y = z cross x.
+ *   max_coord_out[n_regions]: the float maximum over the points of |t.x|, |t.y|, |t.z|, t = (x . d, y . d, z . d) each as above (PCL
+ *     rotates p and c separately and subtracts); NaN with a NaN frame. max_coord = 0 or not finite: NaN row, the frame stays.
+ *   bins 0..215, the shape block: per axis coord = (t / max_coord) * 3.0f + 3.0f in float, b = floor(coord); a b outside 0..5 or a NaN on
+ *     any axis deposits nothing (PCL's padding cell, which its copy to the output drops: the point that attains +max_coord is lost);
+ *     otherwise +1 at (bx*6 + by)*6 + bz.
+ *   bins 216..983, the colour block, only with with_color: cells as above with * 2.0f + 2.0f and 0..3; the hue of the point's 8-bit
+ *     (r, g, b) -- the caller's rgba at the original index -- as GASDColorEstimation::computeFeature writes it: diff_inv = 1.f /
+ *     (float)(max - min); not finite: hue 0; max == r: 60.f * ((float)(g - b) * diff_inv); else max == g: 60.f * (2.f + (float)(b - r) *
+ *     diff_inv); else 60.f * (4.f + (float)(r - g) * diff_inv); hue < 0: + 360.f; hb = floor((hue / 360.f) * 12.f) in float, unfused;
+ *     hb outside 0..11 deposits nothing; otherwise +1 at 216 + ((cx*4 + cy)*4 + cz)*12 + hb.
+ *   row: (float)((double)count * (double)incr), incr = 100.0f / (float)(n_sel - 1): one product per bin, order-free, the same bits on
+ *     every call (PCL adds incr once per deposit in float). desc_out and count_out (device uint32 or NULL; 0 for a NaN row) have row
+ *     length ISMHIP_GASD_DIM with with_color, else ISMHIP_GASD_SHAPE_DIM: the 216 shape bins followed by 296 zeros.
+ * view_direction: HOST float[3]; a non-finite or zero one is ISMHIP_ERR_INVALID, as is with_color on a cloud made without rgba
+ * ("global_gasd: colour arrays missing"). Otherwise checked as the entries above. Timer "global_gasd". */
+int  ismhip_global_gasd(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                        const float* region_radius, const float view_direction[3], int with_color, uint32_t* n_sel_out, float* centroid_out,
+                        float* radius_out, float* frame9_out, float* max_coord_out, float* desc_out, uint32_t* count_out);
+/* Diagnostic: the hue bin of ismhip_global_gasd's colour block alone, one thread per colour. rgba: device [n] packed 0x00RRGGBB, bits
+ * 24..31 ignored. out: device uint8 [n], the bin 0..11, or 255 where the rule deposits nothing. Asynchronous. Off every hot path. */
+int  ismhip_gasd_hue_bins(ismhip_ctx* ctx, int n, const uint32_t* rgba, uint8_t* out);
 
 /* ---- keypoints (the step in front of the path): KeypointsVoxelGrid::iComputeKeypoints
  *      (keypoints/keypoints_voxel_grid.cpp:30-46) -> pcl::VoxelGrid<PointXYZRGB> with a cubic leaf. Per object the

@@ -38,7 +38,7 @@ EXPORTS = [
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
-    "ismhip_esf_local",
+    "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins",
 ]
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
@@ -746,6 +746,35 @@ def global_vfh(ctx, cloud, dev, region_obj, region_center=None, region_radius=No
     ctx.check(lib().ismhip_global_vfh(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vp, C.c_int(1 if fill_size_component else 0),
                                       _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["normal_centroid"]), _p(out["desc"]),
                                       _p(out.get("counts"))), "ismhip_global_vfh")
+    return out
+
+
+def global_gasd(ctx, cloud, dev, region_obj, region_center=None, region_radius=None, view_direction=(0.0, 0.0, 1.0), with_color=True,
+                want_counts=False):
+    """ismhip_global_gasd on regions as global_short_shot -> dict of device tensors n_sel [n], centroid [n, 3], radius [n], frame [n, 9] (the
+    covariance frame, rows x, y, z), max_coord [n], desc [n, D] and, with want_counts, counts [n, D] (int32); D = 984 with_color
+    (the cloud must have been made with rgba), else 512"""
+    torch = _torch()
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    out = _global_outputs(n, 984 if with_color else 512, dev)
+    out["frame"] = out.pop("lrf")
+    out["max_coord"] = torch.empty((n,), dtype=torch.float32, device=dev)
+    if want_counts:
+        out["counts"] = torch.empty_like(out["desc"], dtype=torch.int32)
+    vd = (C.c_float * 3)(*[float(v) for v in view_direction])
+    ctx.check(lib().ismhip_global_gasd(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vd, C.c_int(1 if with_color else 0),
+                                       _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["frame"]), _p(out["max_coord"]),
+                                       _p(out["desc"]), _p(out.get("counts"))), "ismhip_global_gasd")
+    return out
+
+
+def gasd_hue_bins(ctx, rgba):
+    """ismhip_gasd_hue_bins (diagnostic): the hue bin 0..11 of ismhip_global_gasd's colour block for the packed colours rgba (int32 device
+    tensor [n]) -> uint8 [n] on the same device, 255 where the rule deposits nothing"""
+    torch = _torch()
+    assert rgba.dim() == 1 and rgba.dtype == torch.int32
+    out = torch.empty((rgba.shape[0],), dtype=torch.uint8, device=rgba.device)
+    ctx.check(lib().ismhip_gasd_hue_bins(ctx._h, C.c_int(rgba.shape[0]), _p(rgba), _p(out)), "ismhip_gasd_hue_bins")
     return out
 
 

@@ -22,6 +22,7 @@
 // from HBM, the later ones from L2 when the object's span fits (a 16 384-point object: 256 KiB); a tie adds ~50 sweeps from L2.
 // One region per workgroup: a region of a very large object is not split over several workgroups.
 // k_vfh (further down) is the frame-free third descriptor on the same regions: ismhip_global_vfh.
+// k_gasd (after it) is the fourth, in the region's own covariance frame and with colour: ismhip_global_gasd.
 #include "shot_deposit.h"
 #include "lrf_common.h"
 #include "eigen3.h"
@@ -342,17 +343,19 @@ __device__ __forceinline__ int vfh_bin(double v, int last) {
     return v < 0.0 ? 0 : (v > (double)last ? last : (int)v);
 }
 
-// One sweep of a region's span, position and normal of each record, in the order i = tid, tid + 256, ... per thread (the order of
-// the double sums). The loop of k_global issues one load and waits for it, ~64 dependent round trips per sweep of a 16 384-point
-// object with one wave per SIMD; here four records' eight loads are issued before the first is used.
-template <class F>
-__device__ __forceinline__ void vfh_sweep(const float4* __restrict__ sp, const float4* __restrict__ sn, uint32_t n, int tid, F&& f) {
+// One sweep of a region's span, position and (with NORMALS) normal of each record, in the order i = tid, tid + 256, ... per thread (the
+// order of the double sums). The loop of k_global issues one load and waits for it, ~64 dependent round trips per sweep of a
+// 16 384-point object with one wave per SIMD; here four records' loads (eight with normals) are issued before the first is used.
+// Without NORMALS sn is not read and f gets a zero normal. k_vfh and k_gasd sweep with it.
+template <bool NORMALS, class F>
+__device__ __forceinline__ void span_sweep(const float4* __restrict__ sp, const float4* __restrict__ sn, uint32_t n, int tid, F&& f) {
     for (uint32_t i0 = tid; i0 < n; i0 += 4 * 256) {
         float4 p[4], nr[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint64_t i = (uint64_t)i0 + 256u * j;                          // past the end: a record that is there, not used
-            p[j] = sp[i < n ? i : i0]; nr[j] = sn[i < n ? i : i0];
+            p[j] = sp[i < n ? i : i0];
+            if constexpr (NORMALS) nr[j] = sn[i < n ? i : i0]; else nr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) if ((uint64_t)i0 + 256u * j < n) f(p[j], nr[j]);
@@ -414,7 +417,7 @@ __global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
     // ---- 2. radius (k_global's step 2) and the normal centroid: double sums over the finite normals, fixed order ------------------------
     float R = 0.f;
     uint32_t mt = 0; double snx = 0, sny = 0, snz = 0;
-    vfh_sweep(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
+    span_sweep<true>(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
         if (!selected(p)) return;
         const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -441,7 +444,7 @@ __global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
     __syncthreads();
     uint32_t* hist = sm.cnt + (wv * VFH_COPIES + (lane % VFH_COPIES)) * D;
     const double dpi = (double)(1.0f / (2.0f * (float)M_PI));
-    vfh_sweep(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
+    span_sweep<true>(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
         if (!selected(p)) return;
         if (!(isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z))) return;
         // viewpoint block: every such point, whatever becomes of its pair
@@ -473,6 +476,219 @@ __global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
         const bool size_block = b >= 3 * VFH_SHAPE_BINS && b < 4 * VFH_SHAPE_BINS;
         row[b] = (size_block && !a.fill_size) ? 0.f : (float)((double)c * (b < 4 * VFH_SHAPE_BINS ? incr_shape : incr_vp));
     }
+}
+
+// ---- GASD (features/features_gasd.cpp:25-91 -> pcl::GASDColorEstimation, PCL 1.10 gasd.hpp restated in include/ismhip.h) -------------
+// The same region, count, centroid and radius as k_global (steps 1 and 2, the same arithmetic: bit-equal outputs); the frame is the
+// region's own covariance frame (eigen3.h on one thread), the histograms two regular grids in that frame: 6^3 cells of positions and
+// 4^3 cells x 12 hue bins, INTEGER counts. Sweeps, 16 B per point each: count + centroid (skipped for a whole object), radius fused
+// with the six covariance sums, max_coord fused with the sign counts of x, histogram (+ 4 B per point for its colour).
+// Byte model per whole-object region: 48 B x n, 52 B x n with colour.
+// A planar region drives every point into one z layer of cells, the same-address case of the short histogram above. Each wave owns
+// GASD_COPIES copies of the 984 bins, lane l counts in copy l % GASD_COPIES; integers, so the merge is exact. ONE copy per wave is
+// kept: measured against two on planes and on blobs, the times are equal within their spread, and one copy
+// is half the LDS. Static LDS 15 848 bytes, below k_vfh's 39 488.
+#ifndef GASD_COPIES
+#define GASD_COPIES 1
+#endif
+#define GASD_SHAPE_BINS 216
+#define GASD_HUE_BINS 12
+
+struct GasdArgs {
+    const uint32_t* pt_off; const GridMeta* meta;
+    const float4* sp4; const uint32_t* rgba;  // rgba: the caller's colours in original order (with_color), read at the index sp4.w carries
+    int n_obj;
+    const int32_t* reg_obj; const float* reg_center; const float* reg_radius;
+    float vdx, vdy, vdz; int with_color;
+    uint32_t* n_sel; float* centroid; float* radius; float* frame; float* max_coord; float* desc; uint32_t* counts;
+};
+
+struct GasdSmem {
+    double red_d[4];
+    uint32_t red_u[4];
+    float red_f[4];
+    float frame[9];
+    int bad;
+    uint32_t cnt[4 * GASD_COPIES * ISMHIP_GASD_DIM];
+};
+
+// the hue bin of a packed colour by GASDColorEstimation::computeFeature's float arithmetic (include/ismhip.h); -1: no deposit
+__device__ __forceinline__ int gasd_hue_bin(uint32_t c4) {
+    const int r = (int)((c4 >> 16) & 0xffu), g = (int)((c4 >> 8) & 0xffu), b = (int)(c4 & 0xffu);
+    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+    const float diff_inv = 1.f / (float)(mx - mn);
+    float hue;
+    if (!isfinite(diff_inv)) hue = 0.f;
+    else if (mx == r) hue = 60.f * ((float)(g - b) * diff_inv);
+    else if (mx == g) hue = 60.f * (2.f + (float)(b - r) * diff_inv);
+    else hue = 60.f * (4.f + (float)(r - g) * diff_inv);
+    if (hue < 0.f) hue += 360.f;
+    const float hb = floorf((hue / 360.f) * (float)GASD_HUE_BINS);
+    return (hb >= 0.f && hb < (float)GASD_HUE_BINS) ? (int)hb : -1;
+}
+
+// floor((q * half) + half) as a cell index; -1 outside 0 .. 2 * half - 1 and for a NaN (PCL's padding cell: no deposit)
+__device__ __forceinline__ int gasd_cell(float q, float half) {
+    const float coord = floorf(q * half + half);               // unfused (-ffp-contract=off)
+    return (coord >= 0.f && coord < 2.f * half) ? (int)coord : -1;
+}
+
+__global__ __launch_bounds__(256) void k_gasd(GasdArgs a) {
+    __shared__ GasdSmem sm;
+    const int D = a.with_color ? ISMHIP_GASD_DIM : ISMHIP_GASD_SHAPE_DIM;
+    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    const uint32_t reg = blockIdx.x;
+    const float qnan = __builtin_nanf("");
+    float* row = a.desc + (size_t)reg * D;
+    uint32_t* crow = a.counts ? a.counts + (size_t)reg * D : nullptr;
+    auto nan_row = [&](bool frame) {
+        for (int i = tid; i < D; i += 256) { row[i] = qnan; if (crow) crow[i] = 0u; }
+        if (frame && tid < 9) a.frame[(size_t)reg * 9 + tid] = qnan;
+        if (frame && tid == 0) a.max_coord[reg] = qnan;
+    };
+
+    // ---- the region: as k_global ---------------------------------------------------------------------------------------------------
+    const int o = a.reg_obj[reg];
+    const bool obj_ok = o >= 0 && o < a.n_obj;
+    uint32_t base = 0, n = 0;
+    GridMeta m{};
+    if (obj_ok) {
+        m = a.meta[o];
+        base = a.pt_off[o];
+        const uint32_t npts = a.pt_off[o + 1] - base;
+        n = m.n_finite < npts ? m.n_finite : npts;            // the sorted span holds the finite points first
+    }
+    const float qx = a.reg_center[reg * 3], qy = a.reg_center[reg * 3 + 1], qz = a.reg_center[reg * 3 + 2];
+    const float rs = a.reg_radius[reg];
+    const bool whole = rs < 0.f;
+    const float r2s = (float)((double)rs * (double)rs);
+    const float4* sp = a.sp4 + base;
+    auto selected = [&](const float4& p) { return whole || sqdist3(p.x, p.y, p.z, qx, qy, qz) < r2s; };
+
+    // ---- 1. count and centroid: k_global's step 1 ---------------------------------------------------------------------------------
+    uint32_t nsel; float cx, cy, cz;
+    if (whole) {
+        nsel = n; cx = m.centroid[0]; cy = m.centroid[1]; cz = m.centroid[2];
+    } else {
+        uint32_t c = 0; double sx = 0, sy = 0, sz = 0;
+        span_sweep<false>(sp, sp, n, tid, [&](const float4& p, const float4&) {
+            if (selected(p)) { sx += (double)p.x; sy += (double)p.y; sz += (double)p.z; c++; }
+        });
+        nsel = block_sum_i(c, sm.red_u);
+        sx = block_sum_d_left(sx, sm.red_d); sy = block_sum_d_left(sy, sm.red_d); sz = block_sum_d_left(sz, sm.red_d);
+        cx = (float)(sx / (double)nsel); cy = (float)(sy / (double)nsel); cz = (float)(sz / (double)nsel);
+    }
+    if (tid == 0) a.n_sel[reg] = nsel;
+    if (nsel == 0) {                                          // workgroup-uniform
+        if (tid < 3) a.centroid[reg * 3 + tid] = qnan;
+        if (tid == 0) a.radius[reg] = 0.f;
+        nan_row(true);
+        return;
+    }
+    if (tid == 0) { a.centroid[reg * 3] = cx; a.centroid[reg * 3 + 1] = cy; a.centroid[reg * 3 + 2] = cz; }
+
+    // ---- 2. radius (k_global's step 2) and the covariance sums: products of the float differences in double (exact), fixed order ------
+    float R = 0.f;
+    double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+    span_sweep<false>(sp, sp, n, tid, [&](const float4& p, const float4&) {
+        if (!selected(p)) return;
+        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+        if (d > R) R = d;
+        const double vx = (double)dx, vy = (double)dy, vz = (double)dz;
+        c00 += vx * vx; c01 += vx * vy; c02 += vx * vz; c11 += vy * vy; c12 += vy * vz; c22 += vz * vz;
+    });
+    R = block_max_f(R, sm.red_f);
+    if (tid == 0) a.radius[reg] = R;
+    if (nsel < 2u) { nan_row(true); return; }                 // workgroup-uniform: PCL's increment 100 / (n - 1) is infinite
+    c00 = block_sum_d_left(c00, sm.red_d); c01 = block_sum_d_left(c01, sm.red_d); c02 = block_sum_d_left(c02, sm.red_d);
+    c11 = block_sum_d_left(c11, sm.red_d); c12 = block_sum_d_left(c12, sm.red_d); c22 = block_sum_d_left(c22, sm.red_d);
+
+    // ---- 3. the frame, up to the sign of x: z the smallest eigenvalue's vector, turned away from the view direction; x the largest's -----
+    if (tid == 0) {
+        double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}}, w[3], V[3][3];
+        eigen_sym3(A, w, V);
+        double z[3] = {V[0][0], V[1][0], V[2][0]};
+        const double x[3] = {V[0][2], V[1][2], V[2][2]};
+        if ((z[0] * (double)a.vdx + z[1] * (double)a.vdy) + z[2] * (double)a.vdz > 0.0) { z[0] = -z[0]; z[1] = -z[1]; z[2] = -z[2]; }
+        const double y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) {
+            sm.frame[k] = (float)x[k]; sm.frame[3 + k] = (float)y[k]; sm.frame[6 + k] = (float)z[k];
+            ok = ok && isfinite(x[k]) && isfinite(y[k]) && isfinite(z[k]);
+        }
+        sm.bad = ok ? 0 : 1;
+    }
+    __syncthreads();
+    if (sm.bad) { nan_row(true); return; }                    // a covariance that overflowed: no frame
+    float fx[3] = {sm.frame[0], sm.frame[1], sm.frame[2]}, fy[3] = {sm.frame[3], sm.frame[4], sm.frame[5]};
+    const float fz[3] = {sm.frame[6], sm.frame[7], sm.frame[8]};
+    auto rotate = [&](const float4& p, float& tx, float& ty, float& tz) {       // float products, unfused, in this order
+        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+        tx = (fx[0] * dx + fx[1] * dy) + fx[2] * dz;
+        ty = (fy[0] * dx + fy[1] * dy) + fy[2] * dz;
+        tz = (fz[0] * dx + fz[1] * dy) + fz[2] * dz;
+    };
+
+    // ---- 4. max_coord and the sign of x: neither |t| nor the two counts' roles depend on the sign the sweep runs with -------------------
+    float mc = 0.f;
+    uint32_t pos = 0, neg = 0;
+    span_sweep<false>(sp, sp, n, tid, [&](const float4& p, const float4&) {
+        if (!selected(p)) return;
+        float tx, ty, tz;
+        rotate(p, tx, ty, tz);
+        mc = fmaxf(mc, fmaxf(fabsf(tx), fmaxf(fabsf(ty), fabsf(tz))));
+        pos += tx > 0.f; neg += tx < 0.f;
+    });
+    mc = block_max_f(mc, sm.red_f);
+    const uint32_t npos = block_sum_i(pos, sm.red_u), nneg = block_sum_i(neg, sm.red_u);
+    bool flip = nneg > npos;
+    if (nneg == npos) {                                       // a tie: the component of largest magnitude (lowest index) becomes positive
+        int k = 0;
+        if (fabsf(fx[1]) > fabsf(fx[k])) k = 1;
+        if (fabsf(fx[2]) > fabsf(fx[k])) k = 2;
+        flip = fx[k] < 0.f;
+    }
+    if (flip) for (int k = 0; k < 3; ++k) { fx[k] = -fx[k]; fy[k] = -fy[k]; }   // y = z cross x changes sign with x, exactly
+    if (tid < 3) { a.frame[(size_t)reg * 9 + tid] = fx[tid]; a.frame[(size_t)reg * 9 + 3 + tid] = fy[tid]; a.frame[(size_t)reg * 9 + 6 + tid] = fz[tid]; }
+    if (tid == 0) a.max_coord[reg] = mc;
+    if (!(mc > 0.f && isfinite(mc))) { nan_row(false); return; }                // workgroup-uniform: coincident points, or an overflow
+
+    // ---- 5. the histograms --------------------------------------------------------------------------------------------------------------
+    for (int i = tid; i < 4 * GASD_COPIES * ISMHIP_GASD_DIM; i += 256) sm.cnt[i] = 0u;
+    __syncthreads();
+    uint32_t* hist = sm.cnt + (wv * GASD_COPIES + (lane % GASD_COPIES)) * ISMHIP_GASD_DIM;
+    const uint32_t* rgba = a.with_color ? a.rgba + base : nullptr;
+    span_sweep<false>(sp, sp, n, tid, [&](const float4& p, const float4&) {
+        if (!selected(p)) return;
+        float tx, ty, tz;
+        rotate(p, tx, ty, tz);
+        const float ux = tx / mc, uy = ty / mc, uz = tz / mc;
+        const int bx = gasd_cell(ux, 3.0f), by = gasd_cell(uy, 3.0f), bz = gasd_cell(uz, 3.0f);
+        if ((bx | by | bz) >= 0) atomicAdd(&hist[(bx * 6 + by) * 6 + bz], 1u);
+        if (!rgba) return;
+        const int gx = gasd_cell(ux, 2.0f), gy = gasd_cell(uy, 2.0f), gz = gasd_cell(uz, 2.0f);
+        if ((gx | gy | gz) < 0) return;
+        const int hb = gasd_hue_bin(rgba[__float_as_uint(p.w)]);
+        if (hb >= 0) atomicAdd(&hist[GASD_SHAPE_BINS + ((gx * 4 + gy) * 4 + gz) * GASD_HUE_BINS + hb], 1u);
+    });
+    __syncthreads();
+    // counts -> row: one product per bin (order-free); without colour the bins past the shape block are zeros
+    const double incr = (double)(100.0f / (float)(nsel - 1u));
+    const int live = a.with_color ? ISMHIP_GASD_DIM : GASD_SHAPE_BINS;
+    for (int b = tid; b < D; b += 256) {
+        uint32_t c = 0;
+        if (b < live) for (int k = 0; k < 4 * GASD_COPIES; ++k) c += sm.cnt[k * ISMHIP_GASD_DIM + b];
+        if (crow) crow[b] = c;
+        row[b] = (float)((double)c * incr);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gasd_hue_probe(int n, const uint32_t* __restrict__ rgba, uint8_t* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int hb = gasd_hue_bin(rgba[i]);
+    out[i] = hb < 0 ? (uint8_t)255 : (uint8_t)hb;
 }
 
 int global_check(ismhip_ctx* ctx, const char* name, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
@@ -551,6 +767,38 @@ int ismhip_global_vfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions,
     TimerScope ts(ctx, "global_vfh");
     hipLaunchKernelGGL(k_vfh, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_vfh");
+    return ISMHIP_OK;
+}
+
+int ismhip_global_gasd(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                       const float* region_radius, const float view_direction[3], int with_color, uint32_t* n_sel_out, float* centroid_out,
+                       float* radius_out, float* frame9_out, float* max_coord_out, float* desc_out, uint32_t* count_out) {
+    int rc = global_check(ctx, "global_gasd", cloud, n_regions, region_obj, region_center, region_radius, n_sel_out, centroid_out, radius_out,
+                          frame9_out, desc_out);
+    if (rc != ISMHIP_OK) return rc;
+    if (n_regions > 0 && !max_coord_out) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_gasd: bad argument");
+    const float* v = view_direction;
+    if (!v || !(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2])) || (v[0] == 0.f && v[1] == 0.f && v[2] == 0.f))
+        return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_gasd: the view direction is zero or not finite");
+    if (with_color && !cloud->rgba) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "global_gasd: colour arrays missing");
+    if (n_regions == 0) return ISMHIP_OK;
+    GasdArgs a{};
+    a.pt_off = cloud->pt_off; a.meta = cloud->meta; a.sp4 = cloud->sp4; a.rgba = cloud->rgba; a.n_obj = cloud->n_obj;
+    a.reg_obj = region_obj; a.reg_center = region_center; a.reg_radius = region_radius;
+    a.vdx = v[0]; a.vdy = v[1]; a.vdz = v[2]; a.with_color = with_color ? 1 : 0;
+    a.n_sel = n_sel_out; a.centroid = centroid_out; a.radius = radius_out; a.frame = frame9_out; a.max_coord = max_coord_out;
+    a.desc = desc_out; a.counts = count_out;
+    TimerScope ts(ctx, "global_gasd");
+    hipLaunchKernelGGL(k_gasd, dim3((unsigned)n_regions), dim3(256), 0, ctx->stream, a);
+    ISM_CHECK_LAUNCH(ctx, "k_gasd");
+    return ISMHIP_OK;
+}
+
+int ismhip_gasd_hue_bins(ismhip_ctx* ctx, int n, const uint32_t* rgba, uint8_t* out) {
+    if (!ctx || n < 0 || (n > 0 && (!rgba || !out))) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "gasd_hue_bins: bad argument");
+    if (n == 0) return ISMHIP_OK;
+    hipLaunchKernelGGL(k_gasd_hue_probe, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, ctx->stream, n, rgba, out);
+    ISM_CHECK_LAUNCH(ctx, "k_gasd_hue_probe");
     return ISMHIP_OK;
 }
 

@@ -1123,7 +1123,7 @@ bool Codebook::load(BoostBinaryIArchive& ia) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Global descriptors (features/features_short_shot_global.cpp, features_shot_global.cpp, features_vfh.cpp) on regions of the batch's search surface
+// Global descriptors (features/features_short_shot_global.cpp, features_shot_global.cpp, features_vfh.cpp, features_gasd.cpp) on regions of the batch's search surface
 // ---------------------------------------------------------------------------------------------------------------
 struct GlobalRegions {
     int n = 0, dim = 0;
@@ -1182,6 +1182,22 @@ void GlobalFeaturesVFH::describe(DeviceSession& s, GlobalRegions& r) const {
     DeviceSession::h2d(r.lrf, std::vector<float>((size_t)r.n * 9, 0.f));             // VFH has no frame: the stored rf of a row is zeros
     s.sync();                                                                         // ncen is released on return
 }
+GlobalFeaturesGASD::GlobalFeaturesGASD() { addParameter(m_use_color, "GasdWithColor", true); }   // features_gasd.cpp:16-19
+void GlobalFeaturesGASD::checkInput(const PointCloud& cloud) const {
+    if (m_use_color && !cloud.empty() && cloud.rgba.size() != cloud.size()) throw RuntimeException("GASD needs coloured point clouds");
+}
+void GlobalFeaturesGASD::describe(DeviceSession& s, GlobalRegions& r) const {
+    if (m_use_color && !s.has_color) throw RuntimeException("GASD needs coloured point clouds");
+    const float view_direction[3] = {0.f, 0.f, 1.f};                                  // PCL's default, which features_gasd.cpp leaves
+    DevBuf frame, max_coord;
+    frame.reserve(std::max<size_t>((size_t)r.n, 1) * 36); max_coord.reserve(std::max<size_t>((size_t)r.n, 1) * 4);
+    s.check(ismhip_global_gasd(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), view_direction, m_use_color ? 1 : 0,
+                               r.n_sel.as<uint32_t>(), r.centroid.as<float>(), r.radius.as<float>(), frame.as<float>(), max_coord.as<float>(),
+                               r.desc.as<float>(), nullptr), "ismhip_global_gasd");
+    // the reference leaves ISMFeature::referenceFrame untouched for this type (its constructor does not initialise it): zeros, as for VFH
+    DeviceSession::h2d(r.lrf, std::vector<float>((size_t)r.n * 9, 0.f));
+    s.sync();                                                                         // frame and max_coord are released on return
+}
 GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     if (!object.isObject()) return nullptr;
     const Json* t = object.find("Type");
@@ -1190,6 +1206,7 @@ GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     if (t->str == GlobalFeaturesShortShot::getTypeStatic()) g = new GlobalFeaturesShortShot();
     else if (t->str == GlobalFeaturesShot::getTypeStatic()) g = new GlobalFeaturesShot();
     else if (t->str == GlobalFeaturesVFH::getTypeStatic()) g = new GlobalFeaturesVFH();
+    else if (t->str == GlobalFeaturesGASD::getTypeStatic()) g = new GlobalFeaturesGASD();
     if (!g) return nullptr;
     try { if (!g->configFromJson(object)) throw RuntimeException("could not create object of type: \"" + t->str + "\""); }
     catch (...) { delete g; throw; }
@@ -2112,7 +2129,8 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
     const auto* iss = dynamic_cast<const KeypointsISS3D*>(m_keypoints_detector.get());
     // VoxelGridCulling keypoints (ismhip_culling_scores, ismhip_culling_select) likewise; its colour score wants the clouds' colours
     const auto* cull = dynamic_cast<const KeypointsVoxelGridCulling*>(m_keypoints_detector.get());
-    const bool with_color = m_feature_descriptor->needsColor() || (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training));
+    const bool with_color = m_feature_descriptor->needsColor() || (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training)) ||
+                            (m_global_descriptor && m_global_descriptor->needsColor());      // the region descriptor reads the same cloud
     if (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training))
         for (const PointCloud* c : clouds)
             if (c->rgba.size() != c->size()) throw RuntimeException("VoxelGridCulling FilterMethodColor \"colordistance\" needs clouds with colours");
@@ -2228,7 +2246,10 @@ void ImplicitShapeModel::train() {                // :252-500
     g_log_info = m_logging;
     if (m_bounding_box_type != "AABB")
         LOG_WARN("BoundingBoxType \"" << m_bounding_box_type << "\": MVBB is not built, using the axis-aligned box centre for the training votes");
-    for (auto& kv : m_training_clouds) for (auto& c : kv.second) m_feature_descriptor->checkInput(*c);
+    for (auto& kv : m_training_clouds) for (auto& c : kv.second) {
+        m_feature_descriptor->checkInput(*c);
+        if (m_global_descriptor) m_global_descriptor->checkInput(*c);              // training describes every cloud globally as well
+    }
     DeviceSession& s = session();
     const int met = metric();
     // all training objects, class by class (std::map order), model by model
@@ -2329,7 +2350,10 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     if (m_single_object_mode_legacy)
         throw RuntimeException("The parameter for \"single object mode\" must be set inside the \"Voting\" section of the config file. You are using the \"Parameters\" section.");
     LapTimer complete{m_processing_times};
-    for (const PointCloud* c : clouds_in) m_feature_descriptor->checkInput(*c);
+    for (const PointCloud* c : clouds_in) {
+        m_feature_descriptor->checkInput(*c);
+        if (m_global_descriptor && m_voting->useGlobalFeatures()) m_global_descriptor->checkInput(*c);
+    }
     DeviceSession& s = session();
     std::vector<const PointCloud*> nonempty;
     std::vector<int> map;

@@ -160,8 +160,10 @@ struct VotingMaximum {        // voting/voting_maximum.h:51-88
 class DeviceSession;          // ctx + device buffers (ism3d.cpp)
 struct DeviceFeatures;        // device-resident ISMFeature batch: descriptors, LRFs, keypoints, per-object offsets
 
-// ---- global descriptors (the GlobalFeatures child; features/features_short_shot_global.cpp, features_shot_global.cpp, features_vfh.cpp)
-// One row per REGION of the batch's search surface (ismhip_global_short_shot / ismhip_global_shot352 / ismhip_global_vfh): the whole object in training and
+// ---- global descriptors (the GlobalFeatures child; features/features_short_shot_global.cpp, features_shot_global.cpp, features_vfh.cpp,
+// features_gasd.cpp)
+// One row per REGION of the batch's search surface (ismhip_global_short_shot / ismhip_global_shot352 / ismhip_global_vfh /
+// ismhip_global_gasd): the whole object in training and
 // in single-object mode, a ball round a maximum in detection mode. Any other type of the reference stays a pass-through of its JSON
 // (no object is created) and is refused by name only when Voting.UseGlobalFeatures asks for it.
 struct GlobalRegions;          // device arrays of a region batch and its outputs (ism3d.cpp)
@@ -170,7 +172,9 @@ public:
     virtual ~GlobalFeatures() {}
     virtual int getDescriptorLength() const = 0;
     virtual void describe(DeviceSession& s, GlobalRegions& r) const = 0;     // fills r's outputs for r's regions on s.cloud
-    static const char* builtTypes() { return "SHORT_SHOT_GLOBAL, SHOT_GLOBAL, VFH"; }
+    virtual bool needsColor() const { return false; }                        // the batch is uploaded with its colours
+    virtual void checkInput(const PointCloud&) const {}                      // refuses a cloud the descriptor cannot describe, on the host
+    static const char* builtTypes() { return "SHORT_SHOT_GLOBAL, SHOT_GLOBAL, VFH, GASD"; }
     static GlobalFeatures* createIfBuilt(const Json& object);                // nullptr for a type that is not built (or no object)
 };
 class GlobalFeaturesShortShot : public GlobalFeatures {      // features_short_shot_global.cpp:21-30, 168-249
@@ -198,6 +202,18 @@ public:
     std::string getType() const override { return getTypeStatic(); }
     int getDescriptorLength() const override { return ISMHIP_VFH_DIM; }
     void describe(DeviceSession& s, GlobalRegions& r) const override;    // there is no frame: r.lrf is filled with zeros
+};
+class GlobalFeaturesGASD : public GlobalFeatures {           // features_gasd.cpp:16-91: pcl::GASDColorEstimation, view direction (0, 0, 1)
+public:
+    GlobalFeaturesGASD();
+    static std::string getTypeStatic() { return "GASD"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getDescriptorLength() const override { return m_use_color ? ISMHIP_GASD_DIM : ISMHIP_GASD_SHAPE_DIM; }
+    bool needsColor() const override { return m_use_color; }
+    void checkInput(const PointCloud& cloud) const override;             // GasdWithColor: a cloud without colours throws
+    void describe(DeviceSession& s, GlobalRegions& r) const override;    // the stored rf of a row is zeros, as for VFH
+private:
+    bool m_use_color;
 };
 // one stored training row (ISMFeature of voting.cpp:586-613, 660-701)
 struct StoredGlobalFeature { unsigned classId = 0, instanceId = 0; float rf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; std::vector<float> descriptor; float radius = 0; };
