@@ -672,6 +672,65 @@ int  ismhip_culling_select(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offset
                            float* kz_out, uint32_t* krgba_out, uint8_t* keep_mask_out, float* combined_out, float* thresholds_out,
                            uint32_t* kp_offsets_h_out);
 
+/* ---- SIFT3D keypoints: KeypointsSIFT3D::iComputeKeypoints (keypoints/keypoints_sift3d.cpp:24-86) -> pcl::SIFTKeypoint on an XYZI cloud
+ *      whose intensity is the normal's curvature, setScales(Radius, 4, 3), setMinimumContrast(0). PCL is external; the arithmetic is this
+ *      library's definition, restated from PCL 1.10 sift_keypoint.hpp (tests/sift3d_ref.py). Per object, on finite
+ *      points only; every squared distance is the unfused float (dx*dx + dy*dy) + dz*dz. Every order-dependent sum is taken on an integer
+ *      grid: the same bits for any cell_size, lane mapping and run.
+ * ismhip_normal_curvature: dense, per surface point the CURVATURE geometry score of ismhip_culling_scores with that point as the keypoint
+ * and `radius` as the leaf (the same device function): (float)|l0 / trace| over its radius ball, NaN with fewer than 3 ball points.
+ * curv_out: device float[n_pts], count_out: device uint32[n_pts] (ball points) or NULL, original point order; a point that is not finite:
+ * NaN, 0. radius not > 0: ISMHIP_ERR_INVALID. Timer "normal_curvature". Asynchronous. */
+int  ismhip_normal_curvature(ismhip_ctx* ctx, const ismhip_cloud* cloud, float radius, float* curv_out, uint32_t* count_out);
+/* ismhip_voxel_downsample_xyzi: one octave's downsampling. Positions exactly those of ismhip_voxel_keypoints on the same input (occupied
+ * voxels in ascending voxel index, the 2^-40 fixed-point centroid); ki the mean of the voxel's intensities, summed on an integer grid of
+ * its own: round(I * s), s the power of two with s * 2^e = 2^40, 2^e the power of two above the object's largest finite |I|, and
+ * ki = (float)((double)sum / s) / (float)count. A point whose position or intensity is not finite is left out. x, y, z, intensity: device
+ * float[n_pts]; kx|ky|kz|ki: device, `capacity` entries (the number of points always suffices); kp_offsets_h_out[n_obj+1] (host).
+ * Errors as ismhip_voxel_keypoints. Timer "voxel_downsample_xyzi". The call synchronises. */
+int  ismhip_voxel_downsample_xyzi(ismhip_ctx* ctx, int n_obj, const uint32_t* pt_offsets_h, const float* x, const float* y, const float* z,
+                                  const float* intensity, float leaf, uint32_t capacity, float* kx, float* ky, float* kz, float* ki,
+                                  uint32_t* kp_offsets_h_out);
+/* ismhip_sift3d_scale_space: the difference-of-Gaussians columns of one octave. scales: host float[n_scales] (the caller's
+ * base_scale * powf(2.0f, (i - 1.0f) / nr_scales)), 3 <= n_scales <= 16 else ISMHIP_ERR_INVALID, every scale > 0 and finite.
+ * intensity: device float[n_pts], the cloud's original point order. Per point p and scale i, in float: s2 = scales[i] * scales[i],
+ * over the cloud's points q with d2 <= 9.0f * s2 (p included, so the denominator is never 0): w = expf((-0.5f * d2) / s2),
+ * response_i = (float)(sum (w * I_q) / sum w), both sums on integer grids (terms rounded to 2^(e - bits), 2^e the power of two above the
+ * object's largest finite |I| for the numerator and 2 for the denominator, bits = 48 for objects below 2^14 points, one fewer per
+ * doubling), the quotient in double; dog[p][i - 1] = response_i - response_{i-1} in float. A neighbour whose intensity is not finite is
+ * skipped. dog_out: device float[n_pts * (n_scales - 1)], count_out: device uint32[n_pts] (points within the largest scale's bound) or
+ * NULL; a point whose position or intensity is not finite: NaN row, count 0. One sweep of the 3 * scales[n_scales - 1] ball serves all
+ * scales. Timer "sift3d_scale_space". Asynchronous. */
+int  ismhip_sift3d_scale_space(ismhip_ctx* ctx, const ismhip_cloud* cloud, const float* intensity, const float* scales_h, int n_scales,
+                               float* dog_out, uint32_t* count_out);
+/* ismhip_sift3d_extrema: per point p its k nearest points of its object, itself included, ordered by (d2, index inside the object)
+ * ascending -- ties go to the lowest index --, an object of fewer than k finite points uses all of them. For each column c = 1 ..
+ * n_cols - 2 with fabsf(v) >= min_contrast, v = dog[p][c] (a NaN never passes): p is a MAXIMUM iff v > dog[q][c'] for every neighbour
+ * q != p and c' in {c-1, c, c+1}, and v > dog[p][c-1], v > dog[p][c+1]; a MINIMUM with < throughout. The comparisons are STRICT: a
+ * plateau yields neither (a decision of this library). dog: device float[n_pts * n_cols], 3 <= n_cols <= 15; flags_out: device
+ * uint8[n_pts * n_cols]: 0 none, 1 minimum, 2 maximum, the border columns always 0; nn_idx_out: device int32[n_pts * k] or NULL, the
+ * neighbours' indices inside the object in that order, padded with -1; rows of points that are not finite: 0 / -1.
+ * 1 <= k <= ISMHIP_SOR_MAX_MEAN_K; larger k: ISMHIP_ERR_UNSUPPORTED. Timer "sift3d_extrema". Asynchronous. */
+int  ismhip_sift3d_extrema(ismhip_ctx* ctx, const ismhip_cloud* cloud, const float* dog, int n_cols, int k, float min_contrast,
+                           uint8_t* flags_out, int32_t* nn_idx_out);
+#define ISMHIP_SIFT3D_MIN_POINTS 25   /* pcl::SIFTKeypoint: an octave below this many points ends the object; also its nr of neighbours */
+#define ISMHIP_SIFT3D_MAX_OCTAVES 16
+/* ismhip_sift3d_keypoints: the detector. cloud: the surface; intensity: device float[n_pts] in its point order (the reference: the
+ * normals' curvature, ismhip_normal_curvature). scale = min_scale; for octave = 0 .. nr_octaves - 1: the current cloud (octave 0: the
+ * surface's points with a finite intensity) is downsampled at leaf `scale` (ismhip_voxel_downsample_xyzi); an object left with fewer
+ * than ISMHIP_SIFT3D_MIN_POINTS points stops there; on the others the scale space with scales[i] = scale * powf(2.0f, (i - 1.0f) /
+ * nr_scales), i = 0 .. nr_scales + 2 (host, float) and the extrema with k = ISMHIP_SIFT3D_MIN_POINTS, on a search grid of cell size
+ * 0.4f * (3.0f * scales[nr_scales + 2]) built and freed inside; scale *= 2.0f; the next octave downsamples THIS octave's cloud.
+ * Output per object: octave ascending, then the octave's points in voxel order, then the column c ascending; each extremum one
+ * keypoint: the octave point's position and scales[c] (kscale_out, or NULL). A position may appear more than once. kx|ky|kz|kscale_out:
+ * device, `capacity` entries; kp_offsets_h_out[n_obj+1] (host); octave_sizes_h_out: host uint32[n_obj * nr_octaves] or NULL, the size
+ * of the object's cloud at every octave it reached (the one that stopped it included), 0 behind. 1 <= nr_octaves <=
+ * ISMHIP_SIFT3D_MAX_OCTAVES, 1 <= nr_scales <= 13, min_scale > 0, min_contrast >= 0 else ISMHIP_ERR_INVALID; more than `capacity`
+ * keypoints: ISMHIP_ERR_INVALID, nothing written. Timers of the stages. The call synchronises. */
+int  ismhip_sift3d_keypoints(ismhip_ctx* ctx, const ismhip_cloud* cloud, const float* intensity, float min_scale, int nr_octaves, int nr_scales,
+                             float min_contrast, uint32_t capacity, float* kx, float* ky, float* kz, float* kscale_out,
+                             uint32_t* kp_offsets_h_out, uint32_t* octave_sizes_h_out);
+
 /* ---- feature filtering: Features::operator() drops non-finite LRFs (features.cpp:66-76),
  *      ImplicitShapeModel::removeNaNFeatures drops NaN descriptors (implicit_shape_model.cpp:1276-1308).
  *      Stable stream compaction of rows; keep_offsets_h_out[n_obj+1] (host) receives the new per-object

@@ -39,7 +39,9 @@ EXPORTS = [
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
     "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins",
+    "ismhip_normal_curvature", "ismhip_voxel_downsample_xyzi", "ismhip_sift3d_scale_space", "ismhip_sift3d_extrema", "ismhip_sift3d_keypoints",
 ]
+SIFT3D_MIN_POINTS = 25             # ISMHIP_SIFT3D_MIN_POINTS: an octave below it ends the object; also the extrema's number of neighbours
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
 CULLING_GEOMETRY = {"none": 0, "curvature": 1, "kpq": 2}
 CULLING_COLOR = {"none": 0, "colordistance": 1}
@@ -1018,6 +1020,83 @@ def voxel_culling_keypoints(ctx, cloud, leaf, geometry="none", color="none", geo
     r = culling_select(ctx, ko, geo, col, kx, ky, kz, kc, g != "none", c != "none", geometry_type, color_type, geometry_threshold, color_threshold,
                        cutoff_ratio, combine)
     return r["kp_offsets"], r["kx"], r["ky"], r["kz"], r["krgba"]
+
+
+def normal_curvature(ctx, cloud, radius, want_counts=True):
+    """ismhip_normal_curvature: returns (curvature float32[n_pts], counts int32[n_pts] or None) in the cloud's original point order; NaN
+    where the point is not finite or its ball holds fewer than 3 points"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    curv = torch.zeros((n,), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_normal_curvature(ctx._h, cloud._h, C.c_float(radius), _p(curv), _p(cnt)), "ismhip_normal_curvature")
+    return curv, cnt
+
+
+def voxel_downsample_xyzi(ctx, pt_offsets, x, y, z, intensity, leaf):
+    """ismhip_voxel_downsample_xyzi: returns (offsets[n_obj+1] numpy, kx, ky, kz, ki) packed object after object"""
+    torch = _torch()
+    po = _u32(pt_offsets)
+    n_obj = len(po) - 1
+    n = int(po[-1])
+    kx = torch.empty((max(n, 1),), dtype=torch.float32, device=x.device); ky = torch.empty_like(kx); kz = torch.empty_like(kx); ki = torch.empty_like(kx)
+    ko = np.zeros(n_obj + 1, dtype=np.uint32)
+    ctx.check(lib().ismhip_voxel_downsample_xyzi(ctx._h, C.c_int(n_obj), _p(po), _p(x), _p(y), _p(z), _p(intensity), C.c_float(leaf), C.c_uint32(n),
+                                                 _p(kx), _p(ky), _p(kz), _p(ki), _p(ko)), "ismhip_voxel_downsample_xyzi")
+    m = int(ko[-1])
+    return ko, kx[:m], ky[:m], kz[:m], ki[:m]
+
+
+def sift3d_scales(base_scale, nr_scales):
+    """scales[i] = base_scale * powf(2.0f, (i - 1.0f) / nr_scales), i = 0 .. nr_scales + 2, every step in float and with the C library's
+    powf, as ismhip_sift3d_keypoints takes them"""
+    import ctypes.util
+    libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    libm.powf.restype = C.c_float
+    libm.powf.argtypes = [C.c_float, C.c_float]
+    f = np.float32
+    return np.array([f(base_scale) * f(libm.powf(2.0, f(f(i) - f(1.0)) / f(nr_scales))) for i in range(nr_scales + 3)], dtype=np.float32)
+
+
+def sift3d_scale_space(ctx, cloud, intensity, scales, want_counts=True):
+    """ismhip_sift3d_scale_space: returns (dog float32[n_pts, len(scales) - 1], counts int32[n_pts] or None), original point order"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float32))
+    dog = torch.zeros((n, max(len(sc) - 1, 1)), dtype=torch.float32, device=dev)
+    cnt = torch.zeros((n,), dtype=torch.int32, device=dev) if want_counts else None
+    ctx.check(lib().ismhip_sift3d_scale_space(ctx._h, cloud._h, _p(intensity), _p(sc), C.c_int(len(sc)), _p(dog), _p(cnt)), "ismhip_sift3d_scale_space")
+    return dog, cnt
+
+
+def sift3d_extrema(ctx, cloud, dog, k=SIFT3D_MIN_POINTS, min_contrast=0.0, want_nn=True):
+    """ismhip_sift3d_extrema: returns (flags uint8[n_pts, n_cols]: 0 none, 1 minimum, 2 maximum; nn int32[n_pts, k] padded with -1, or None)"""
+    torch = _torch()
+    n, n_cols = dog.shape
+    flags = torch.zeros((n, n_cols), dtype=torch.uint8, device=dog.device)
+    nn = torch.full((n, max(k, 1)), -1, dtype=torch.int32, device=dog.device) if want_nn else None
+    ctx.check(lib().ismhip_sift3d_extrema(ctx._h, cloud._h, _p(dog), C.c_int(n_cols), C.c_int(k), C.c_float(min_contrast), _p(flags), _p(nn)),
+              "ismhip_sift3d_extrema")
+    return flags, nn
+
+
+def sift3d_keypoints(ctx, cloud, intensity, min_scale, nr_octaves=4, nr_scales=3, min_contrast=0.0, capacity=None):
+    """KeypointsSIFT3D on the device: returns (kp_offsets[n_obj+1] numpy, kx, ky, kz, kscale, octave_sizes uint32[n_obj, nr_octaves]).
+    capacity: entries of the output arrays (default: 4 * nr_scales per point; the count is not bounded by the number of points)"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    cap = n * 4 * nr_scales if capacity is None else int(capacity)
+    kx = torch.zeros((max(cap, 1),), dtype=torch.float32, device=dev); ky = torch.zeros_like(kx); kz = torch.zeros_like(kx); ks = torch.zeros_like(kx)
+    ko = np.zeros(cloud.n_obj + 1, dtype=np.uint32)
+    sizes = np.zeros((cloud.n_obj, max(nr_octaves, 1)), dtype=np.uint32)
+    ctx.check(lib().ismhip_sift3d_keypoints(ctx._h, cloud._h, _p(intensity), C.c_float(min_scale), C.c_int(nr_octaves), C.c_int(nr_scales),
+                                            C.c_float(min_contrast), C.c_uint32(cap), _p(kx), _p(ky), _p(kz), _p(ks), _p(ko), _p(sizes)),
+              "ismhip_sift3d_keypoints")
+    m = int(ko[-1])
+    return ko, kx[:m], ky[:m], kz[:m], ks[:m], sizes
 
 
 def _compact_feature_rows(ctx, symbol, report_all_kept, kp_offsets, desc, lrf, kpx, kpy, kpz):

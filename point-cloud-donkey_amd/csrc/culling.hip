@@ -23,6 +23,7 @@
 // depend on the other objects of the batch.
 #include "common.h"
 #include "eigen3.h"
+#include "moments.h"
 #include <cfloat>
 #include <cmath>
 
@@ -32,48 +33,6 @@ struct CullView {
     const uint32_t* pt_off; const GridMeta* meta; const uint32_t* cell_start;
     const float4* sp4;
     int n_obj, nbx;
-};
-
-// the two grids of a set of moments: products below 2^e2, components below 2^e1
-struct GridScale { double magic2, q2, magic1, q1; };
-
-__host__ __device__ inline int grid_bits(uint32_t n_points) {
-    int bits = 48;
-    while (bits > 24 && ((unsigned long long)n_points + 1ull) >= (1ull << (62 - bits))) --bits;
-    return bits;
-}
-// power of two strictly above v (v >= 0, finite), kept inside the range where the magic constants stay finite
-__device__ __forceinline__ int exp_above(double v) {
-    int e = 0; (void)frexp(v, &e);
-    return e < -900 ? -900 : (e > 900 ? 900 : e);
-}
-__device__ __forceinline__ int half_exp_up(int e) { return e >= 0 ? (e + 1) / 2 : -((-e) / 2); }   // ceil(e / 2)
-__device__ __forceinline__ GridScale grid_scale(int e2, int e1, int bits) {
-    GridScale g;
-    g.magic2 = ldexp(1.5, e2 - bits + 52); g.q2 = ldexp(1.0, e2 - bits);
-    g.magic1 = ldexp(1.5, e1 - bits + 52); g.q1 = ldexp(1.0, e1 - bits);
-    return g;
-}
-__device__ __forceinline__ long long on_grid(double v, double magic) { return __double_as_longlong(v + magic) - __double_as_longlong(magic); }
-
-// sum v and sum v v^T on the integer grids
-struct Moments {
-    long long x = 0, y = 0, z = 0, xx = 0, xy = 0, xz = 0, yy = 0, yz = 0, zz = 0;
-    __device__ __forceinline__ void add(const GridScale& G, double vx, double vy, double vz) {
-        x += on_grid(vx, G.magic1); y += on_grid(vy, G.magic1); z += on_grid(vz, G.magic1);
-        xx += on_grid(vx * vx, G.magic2); xy += on_grid(vx * vy, G.magic2); xz += on_grid(vx * vz, G.magic2);
-        yy += on_grid(vy * vy, G.magic2); yz += on_grid(vy * vz, G.magic2); zz += on_grid(vz * vz, G.magic2);
-    }
-    // S = sum (v - c)(v - c)^T = sum v v^T - (sum v)(sum v)^T / n, c the mean; eigenvalues ascending in w, trace in tr
-    __device__ __forceinline__ void centred_eigenvalues(const GridScale& G, int n, double w[3], double& tr) const {
-        const double sx = (double)x * G.q1, sy = (double)y * G.q1, sz = (double)z * G.q1, inv = 1.0 / (double)n;
-        double A[3][3], V[3][3];
-        A[0][0] = (double)xx * G.q2 - sx * sx * inv; A[0][1] = A[1][0] = (double)xy * G.q2 - sx * sy * inv;
-        A[0][2] = A[2][0] = (double)xz * G.q2 - sx * sz * inv; A[1][1] = (double)yy * G.q2 - sy * sy * inv;
-        A[1][2] = A[2][1] = (double)yz * G.q2 - sy * sz * inv; A[2][2] = (double)zz * G.q2 - sz * sz * inv;
-        tr = (A[0][0] + A[1][1]) + A[2][2];
-        eigen_sym3(A, w, V);
-    }
 };
 
 __device__ __forceinline__ bool fin3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
@@ -178,8 +137,7 @@ __global__ __launch_bounds__(256) void k_cull_scores(CullView cv, ScoreArgs a) {
     const int bits = grid_bits(m.n_finite);
     GridScale G = {};
     if (a.geometry == ISMHIP_CULLING_GEOMETRY_CURVATURE) {
-        const int e2 = exp_above((double)a.r2);
-        G = grid_scale(e2, half_exp_up(e2), bits);
+        G = ball_grid_scale(a.r2, bits);
     }
     double k_magic = 0.0, k_q = 0.0;
     if (a.geometry == ISMHIP_CULLING_GEOMETRY_KPQ) {
@@ -231,12 +189,7 @@ __global__ __launch_bounds__(256) void k_cull_scores(CullView cv, ScoreArgs a) {
         s.xy = (long long)wave_sum_u64((unsigned long long)s.xy); s.xz = (long long)wave_sum_u64((unsigned long long)s.xz);
         s.yy = (long long)wave_sum_u64((unsigned long long)s.yy); s.yz = (long long)wave_sum_u64((unsigned long long)s.yz);
         s.zz = (long long)wave_sum_u64((unsigned long long)s.zz);
-        g = __builtin_nanf("");
-        if (cnt >= 3) {
-            double w[3], tr;
-            s.centred_eigenvalues(G, cnt, w, tr);            // the common factor 1 / n leaves the quotient
-            g = tr == 0.0 ? 0.f : (float)fabs(w[0] / tr);
-        }
+        g = s.curvature(G, cnt);
     }
     if (a.geometry == ISMHIP_CULLING_GEOMETRY_KPQ) {
         sum_K = (long long)wave_sum_u64((unsigned long long)sum_K);

@@ -8,6 +8,7 @@
 // queries of a wave sit in the same or in adjacent cells and read the same x-runs of candidate records (the wave-per-query sweep of
 // lrf.hip / shot.hip is laid out for a few thousand keypoints per object, not for every point).
 #include "common.h"
+#include "knn_box.h"
 #include <cfloat>
 #include <cmath>
 
@@ -31,15 +32,9 @@ __device__ __forceinline__ float sor_mean(int k, G&& get) {
     return (float)(s / (double)k);
 }
 
-// Exact (k + 1) smallest squared distances of every finite point to the finite points of its object, by growing a box of cells
-// around the query. Invariant after step s: every point of the box [lo, hi] has been read OR lies at a squared distance >= the
-// current (k + 1)-th one (inside the box, cells that cannot hold a closer point are clipped away: cell_coord is monotone and is
-// the very function that binned the points, so a point with |p_a - q_a| <= rk lies in a cell of [cell_coord(q_a - rk), cell_coord(q_a +
-// rk)]). A point outside the box is at least as far as the nearest box face that still has cells behind it. The search stops when
-// the (k + 1)-th squared distance is <= the square of that face distance (taken conservatively: the padding absorbs the rounding of
-// the cell bounds), or when the box holds the whole grid. Which cells were read therefore never shows in the result. Queries still
-// open after SOR_STEPS steps (isolated outliers: their neighbours are many cells away, and a lane that walked there would hold its
-// whole wave) are appended to `open_list` for k_sor_scan.
+// Exact (k + 1) smallest squared distances of every finite point to the finite points of its object, by the growing box of cells of
+// knn_box.h. Queries still open after SOR_STEPS steps (isolated outliers: their neighbours are many cells away, and a lane that walked
+// there would hold its whole wave) are appended to `open_list` for k_sor_scan.
 __global__ __launch_bounds__(SOR_BLOCK) void k_sor_meandist(SorView cv, int k, float* __restrict__ mean_dist,
                                                             uint32_t* __restrict__ open_count, uint32_t* __restrict__ open_list) {
     extern __shared__ float s_list[];                     // [k + 1][SOR_BLOCK]: slot j of thread t at j * SOR_BLOCK + t (conflict free)
@@ -83,57 +78,7 @@ __global__ __launch_bounds__(SOR_BLOCK) void k_sor_meandist(SorView cv, int k, f
                 if (i + u < e) consider(sqdist3(p[u].x, p[u].y, p[u].z, q[0], q[1], q[2]));
         }
     };
-    const float cmax = fmaxf(m.cell[0], fmaxf(m.cell[1], m.cell[2])), cmin = fminf(m.cell[0], fminf(m.cell[1], m.cell[2]));
-    int plo[3] = {0, 0, 0}, phi[3] = {-1, -1, -1};          // previous box (empty)
-    bool done = false;
-    for (int s = 0; s < SOR_STEPS && !done; ++s) {
-        const float R = s == 0 ? 0.f : (s == 1 ? 0.5f * cmin : (float)(s - 1) * cmax);
-        int lo[3], hi[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = cell_coord(q[a] - R, m.minv[a], m.inv_cell[a], m.dim[a]);
-            hi[a] = cell_coord(q[a] + R, m.minv[a], m.inv_cell[a], m.dim[a]);
-            if (s > 0) { lo[a] = min(lo[a], plo[a]); hi[a] = max(hi[a], phi[a]); }      // boxes are nested whatever the rounding does
-        }
-        // the cells that can hold a point closer than the current (k + 1)-th distance; refreshed whenever that distance has dropped
-        int clo[3] = {lo[0], lo[1], lo[2]}, chi[3] = {hi[0], hi[1], hi[2]};
-        float kth_seen = INFINITY;
-        auto clip = [&]() {
-            if (kth == kth_seen) return;
-            kth_seen = kth;
-            const float rk = sqrtf(kth) * 1.00001f + 1e-30f;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float ra = rk + fabsf(q[a]) * 4e-7f;                      // the rounding of q -+ rk itself
-                clo[a] = max(lo[a], cell_coord(q[a] - ra, m.minv[a], m.inv_cell[a], m.dim[a]));
-                chi[a] = min(hi[a], cell_coord(q[a] + ra, m.minv[a], m.inv_cell[a], m.dim[a]));
-            }
-        };
-        clip();
-        for (int gz = lo[2]; gz <= hi[2]; ++gz)
-            for (int gy = lo[1]; gy <= hi[1]; ++gy) {
-                if (gz < clo[2] || gz > chi[2] || gy < clo[1] || gy > chi[1]) continue;
-                const int rb = (gz * m.dim[1] + gy) * m.dim[0];
-                const bool seen = s > 0 && gz >= plo[2] && gz <= phi[2] && gy >= plo[1] && gy <= phi[1];
-                if (!seen) span(cs[rb + clo[0]], cs[rb + chi[0] + 1]);           // x is the fastest cell axis: a row of cells is one span
-                else {
-                    if (clo[0] < plo[0]) span(cs[rb + clo[0]], cs[rb + min(plo[0], chi[0] + 1)]);
-                    if (chi[0] > phi[0]) span(cs[rb + max(phi[0], clo[0] - 1) + 1], cs[rb + chi[0] + 1]);
-                }
-                clip();
-            }
-        // nearest face of the box that has unread cells behind it
-        float face = INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float pad = (fabsf(q[a]) + fabsf(m.minv[a]) + m.cell[a] * (float)m.dim[a]) * 4e-6f;
-            if (lo[a] > 0) face = fminf(face, q[a] - (m.minv[a] + (float)lo[a] * m.cell[a]) - pad);
-            if (hi[a] < m.dim[a] - 1) face = fminf(face, (m.minv[a] + (float)(hi[a] + 1) * m.cell[a]) - q[a] - pad);
-            plo[a] = lo[a]; phi[a] = hi[a];
-        }
-        if (face == INFINITY) done = true;                                       // the box is the whole grid
-        else if (face > 0.f && kth <= face * face * 0.99999f) done = true;
-    }
+    const bool done = knn_box_search(m, cs, q, SOR_STEPS, kth, span);
     const uint32_t me = __float_as_uint(q4.w);
     if (done) {
         for (int i = 1; i <= k; ++i) {                      // insertion sort, ascending

@@ -86,6 +86,8 @@ public:
     PointArrays pts, spare;               // the batch's points; spare: target of a compaction (compactPoints), swapped in afterwards
     DevBuf kx, ky, kz, krgba;
     DevBuf vox_x, vox_y, vox_z, vox_rgba, cull_pc1, cull_pc2, cull_geo, cull_col;   // VoxelGridCulling: the voxel keypoints before the culling, curvatures, scores
+    DevBuf sift_curv;                     // SIFT3D: the normal curvature of every point of the batch
+    float normal_radius = 0.05f;          // the model's NormalRadius (SIFT3D's curvature); set by ImplicitShapeModel::computeFeatures
     ismhip_cloud* cloud = nullptr;
     bool has_color = false;
     // vote space of the current batch (Voting::m_votes)
@@ -185,7 +187,8 @@ public:
         const auto* vg = dynamic_cast<const KeypointsVoxelGrid*>(detector);
         const auto* iss = dynamic_cast<const KeypointsISS3D*>(detector);
         const auto* cull = dynamic_cast<const KeypointsVoxelGridCulling*>(detector);
-        if (detector && !vg && !iss && !cull) throw RuntimeException("keypoint type \"" + detector->getType() + "\" has no device route");
+        const auto* sift = dynamic_cast<const KeypointsSIFT3D*>(detector);
+        if (detector && !vg && !iss && !cull && !sift) throw RuntimeException("keypoint type \"" + detector->getType() + "\" has no device route");
         const size_t n_pts = pt_off.back();
         if (cull) {
             const size_t cap = std::max<size_t>(n_pts, 1) * 4;
@@ -220,10 +223,13 @@ public:
                                         has_color ? krgba.as<uint32_t>() : nullptr, nullptr, nullptr, nullptr, kp_off.data()), "ismhip_culling_select");
             return;
         }
+        // SIFT3D: every point of an octave can be an extremum in every inner column, and no octave is larger than the cloud
+        const size_t kp_cap = std::max<size_t>(n_pts, 1) * (sift ? (size_t)(KeypointsSIFT3D::kOctaves * KeypointsSIFT3D::kScalesPerOctave) : 1);
+        if (kp_cap > 0xffffffffull) throw RuntimeException("batch too large for the keypoint arrays");
         if (detector) {
             // the keypoints stay in HBM, only the per-object counts come back
-            kx.reserve(std::max<size_t>(n_pts, 1) * 4); ky.reserve(std::max<size_t>(n_pts, 1) * 4); kz.reserve(std::max<size_t>(n_pts, 1) * 4);
-            if (has_color) krgba.reserve(std::max<size_t>(n_pts, 1) * 4);
+            kx.reserve(kp_cap * 4); ky.reserve(kp_cap * 4); kz.reserve(kp_cap * 4);
+            if (has_color) krgba.reserve(kp_cap * 4);
             kp_off.assign((size_t)n_obj + 1, 0);
         }
         if (vg)       // KeypointsVoxelGrid::iComputeKeypoints on the device
@@ -234,6 +240,15 @@ public:
             check(ismhip_iss3d_keypoints(ctx, cloud, (float)iss->getSalientRadius(), (float)iss->getNonMaxRadius(), iss->getGamma21(), iss->getGamma32(),
                                          iss->getMinNeighbors(), (uint32_t)n_pts, kx.as<float>(), ky.as<float>(), kz.as<float>(),
                                          has_color ? krgba.as<uint32_t>() : nullptr, nullptr, kp_off.data()), "ismhip_iss3d_keypoints");
+        if (sift) {   // KeypointsSIFT3D::iComputeKeypoints on the device: the curvature of the surface at NormalRadius, then the detector
+            sift_curv.reserve(std::max<size_t>(n_pts, 1) * 4);
+            check(ismhip_normal_curvature(ctx, cloud, normal_radius, sift_curv.as<float>(), nullptr), "ismhip_normal_curvature");
+            check(ismhip_sift3d_keypoints(ctx, cloud, sift_curv.as<float>(), sift->getRadius(), KeypointsSIFT3D::kOctaves, KeypointsSIFT3D::kScalesPerOctave,
+                                          0.0f, (uint32_t)kp_cap, kx.as<float>(), ky.as<float>(), kz.as<float>(), nullptr, kp_off.data(), nullptr),
+                  "ismhip_sift3d_keypoints");
+            // copyPointCloud from XYZI leaves no colour (keypoints_sift3d.cpp:78)
+            if (has_color && kp_off.back() > 0 && hipMemset(krgba.p, 0, (size_t)kp_off.back() * 4) != hipSuccess) throw RuntimeException("hipMemset failed");
+        }
     }
     // one compaction of the batch's points: reserves the spare arrays, runs `call` (which writes them and the new offsets), makes them
     // the current ones and replaces pt_off
@@ -379,6 +394,17 @@ void KeypointsISS3D::iPostInitConfig() {
 }
 KeypointSet KeypointsISS3D::iComputeKeypoints(const PointCloud&) const {
     throw RuntimeException("KeypointsISS3D has no host implementation: the detector runs on the device with the batch (ismhip_iss3d_keypoints)");
+}
+
+// Keypoints: pcl::SIFTKeypoint on the normals' curvature (keypoints/keypoints_sift3d.cpp:17-86). The detector itself is
+// ismhip_normal_curvature + ismhip_sift3d_keypoints on the batch's search surface (DeviceSession::finishBatch); this class holds the
+// configuration.
+KeypointsSIFT3D::KeypointsSIFT3D() { addParameter(m_radius, "Radius", 0.05f); }
+void KeypointsSIFT3D::iPostInitConfig() {
+    if (!(m_radius > 0.f) || !std::isfinite(m_radius)) throw BadParamExceptionType<float>("invalid SIFT3D Radius", m_radius);
+}
+KeypointSet KeypointsSIFT3D::iComputeKeypoints(const PointCloud&) const {
+    throw RuntimeException("KeypointsSIFT3D has no host implementation: the detector runs on the device with the batch (ismhip_sift3d_keypoints)");
 }
 
 // Keypoints: voxel-grid keypoints culled by quality scores (keypoints/keypoints_voxel_grid_culling.cpp:27-44). The detector itself is
@@ -1708,7 +1734,8 @@ template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type)
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
     if (type == KeypointsISS3D::getTypeStatic()) return new KeypointsISS3D();
     if (type == KeypointsVoxelGridCulling::getTypeStatic()) return new KeypointsVoxelGridCulling();
-    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid, ISS3D, VoxelGridCulling)");
+    if (type == KeypointsSIFT3D::getTypeStatic()) return new KeypointsSIFT3D();
+    throw RuntimeException("keypoint type \"" + type + "\" is not built (built: VoxelGrid, ISS3D, VoxelGridCulling) and SIFT3D");
 }
 template <> ActivationStrategy* Factory<ActivationStrategy>::createByType(const std::string& type) {
     if (type == ActivationStrategyKNN::getTypeStatic()) return new ActivationStrategyKNN();
@@ -2134,8 +2161,11 @@ std::shared_ptr<DeviceFeatures> ImplicitShapeModel::computeFeatures(const std::v
     if (cull && cull->needsColor() && !cull->isPlainVoxelGrid(is_training))
         for (const PointCloud* c : clouds)
             if (c->rgba.size() != c->size()) throw RuntimeException("VoxelGridCulling FilterMethodColor \"colordistance\" needs clouds with colours");
+    // SIFT3D keypoints (ismhip_normal_curvature, ismhip_sift3d_keypoints) likewise, with the curvature taken at NormalRadius
+    const auto* sift = dynamic_cast<const KeypointsSIFT3D*>(m_keypoints_detector.get());
+    s.normal_radius = m_normal_radius;
     const char* host_kp = getenv("ISM3D_HOST_KEYPOINTS");
-    const bool dev_kp = iss || cull || (vg && !(host_kp && host_kp[0] == '1'));
+    const bool dev_kp = iss || cull || sift || (vg && !(host_kp && host_kp[0] == '1'));
     if (iss)
         for (const PointCloud* c : clouds)
             if (c->organized) {   // keypoints_iss3d.cpp:45-48 hands PCL the unfiltered organised cloud

@@ -261,6 +261,26 @@ private:
     int m_minNeighbors;
 };
 
+// keypoints/keypoints_sift3d.cpp:17-86 -> pcl::SIFTKeypoint on the cloud's normal curvature, setScales(Radius, 4, 3), minimum contrast 0
+// (ismhip_normal_curvature, ismhip_sift3d_keypoints): the reference's one parameter and its default. A Radius that
+// is not > 0, or not a number, is refused when the configuration is read. There is NO host implementation: the detector runs on the
+// batch's search surface on the device (DeviceSession::finishBatch), iComputeKeypoints(const PointCloud&) throws by name, and
+// ISM3D_HOST_KEYPOINTS=1 does not apply. The curvature is always computed there, at the model's NormalRadius, on the NaN-free surface the
+// descriptors will see; organised clouds take the same route. The keypoints carry no colour.
+class KeypointsSIFT3D : public Keypoints {
+public:
+    KeypointsSIFT3D();
+    static std::string getTypeStatic() { return "SIFT3D"; }
+    std::string getType() const override { return getTypeStatic(); }
+    float getRadius() const { return m_radius; }
+    static constexpr int kOctaves = 4, kScalesPerOctave = 3;     // setScales(m_radius, 4, 3), keypoints_sift3d.cpp:60
+protected:
+    KeypointSet iComputeKeypoints(const PointCloud& points) const override;
+    void iPostInitConfig() override;
+private:
+    float m_radius;
+};
+
 // keypoints/keypoints_voxel_grid_culling.cpp:27-44: the reference's 13 parameter names and defaults (ismhip_principal_curvatures,
 // ismhip_culling_scores, ismhip_culling_select). Method and type strings are lower-cased when the configuration is
 // read, as the reference lower-cases them before it compares; CombineFilters is case-sensitive. Refused by name there, each with its
