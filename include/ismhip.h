@@ -742,10 +742,19 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
                              float* kpx_out, float* kpy_out, float* kpz_out,
                              uint32_t* src_index_out, uint32_t* keep_offsets_h_out);
 
-/* The same filter for descriptor matrices written by ismhip_shot352 / ismhip_cshot1344 / ismhip_fpfh33 / ismhip_short_shot / ismhip_short_cshot / ismhip_cospair / ismhip_spin_image / ismhip_rsd / ismhip_esf_local, whose rows are NaN AS A WHOLE
- * (invalid frame, empty neighbourhood, zero norm): one element per row is tested instead of the matrix, and when nothing is dropped
- * *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays; src_index_out, if given, is 0..nkp-1)
- * and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features. */
+/* The same filter for the descriptor matrices of THIS library: one element per row (desc[k * dim]) is tested instead of the matrix,
+ * and when nothing is dropped *all_kept_out = 1, the *_out arrays are NOT written (the caller goes on with its input arrays;
+ * src_index_out, if given, is 0..nkp-1) and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features.
+ * THE ROW CONTRACT it rests on: a row is finite throughout or NaN throughout (invalid frame, keypoint not finite, empty
+ * neighbourhood, zero norm, a NaN input reaching the histogram) -- never a finite first element with a NaN behind it, and never an
+ * infinity. It covers the rows of all twelve local Features entry points: ismhip_shot352 / ismhip_bshot352 / ismhip_cshot1344 /
+ * ismhip_short_shot / ismhip_short_cshot / ismhip_fpfh33 / ismhip_cospair / ismhip_spin_image / ismhip_rsd / ismhip_rift /
+ * ismhip_esf_local / ismhip_cgf_raw followed by ismhip_mlp_forward. Of these, FPFH rescales its three 11-bin blocks
+ * independently, and they are NaN together; BSHOT holds no NaN at all (a NaN SHOT row is 352 ones and stays); a NaN raw CGF row gives
+ * a NaN output row of the embedding, and only that row. tests/test_gpu_feature_batch.py holds every one of them to the contract on a
+ * ragged batch with every kind of special row, and holds this call to ismhip_compact_features on those rows. A descriptor matrix from
+ * anywhere else (a file, another library, rows edited by the caller) is filtered with ismhip_compact_features, which reads every
+ * element. */
 int  ismhip_compact_descriptor_rows(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offsets_h, int dim,
                                     const float* desc, const float* lrf9,
                                     const float* kpx, const float* kpy, const float* kpz,

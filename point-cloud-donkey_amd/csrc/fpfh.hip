@@ -276,7 +276,9 @@ extern "C" int ismhip_fpfh33(ismhip_ctx* ctx, const ismhip_cloud* cloud, const u
     const unsigned g_kp = ctx->xcd_map ? xcd_object_grid((unsigned)a.nbx_kp, n_obj) : (unsigned)a.nbx_kp * (unsigned)n_obj;
     hipLaunchKernelGGL(k_fpfh_mark, dim3(g_kp), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_fpfh_mark");
-    hipLaunchKernelGGL(k_spfh, dim3((cloud->max_pts + 3) / 4, n_obj), dim3(256), 0, ctx->stream, a);
+    // a cloud without a single point (one empty object on its own) still gets one block per object: a grid of zero blocks is no launch,
+    // and its keypoints are owed their NaN rows (k_fpfh_sum)
+    hipLaunchKernelGGL(k_spfh, dim3((cloud->max_pts + 3) / 4 ? (cloud->max_pts + 3) / 4 : 1, n_obj), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_spfh");
     hipLaunchKernelGGL(k_fpfh_sum, dim3(g_kp), dim3(256), 0, ctx->stream, a);
     ISM_CHECK_LAUNCH(ctx, "k_fpfh_sum");

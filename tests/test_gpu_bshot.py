@@ -82,6 +82,24 @@ def bshot_scene():
     return p, n, np.concatenate([kp, thin[None, :]]).astype(f32), cnt
 
 
+def check_bshot_rows(got, shot, ref):
+    """device BSHOT rows against the device's own SHOT rows `shot` (bit-equal to the restatement's binarisation; a NaN row is 352 ones) and
+    against the float64 SHOT reference rows `ref`, binarised by the restatement: every group it decides with a margin of four elements x the
+    project's 1e-4 descriptor tolerance, and every zero-sum group -> (share of the non-zero groups left out, groups, zero-sum groups)"""
+    assert np.array_equal(bits(got), bits(br.binarize(shot)))
+    assert set(np.unique(got)) <= {0.0, 1.0}
+    nan = np.isnan(ref[:, 0])
+    assert (got[nan] == 1).all() and (br.binarize(ref[nan]) == 1).all()     # NaN row -> ones in the reference too
+    live = ref[~nan].astype(np.float64)
+    s, margin = br.margins(live)
+    zero = s == 0
+    decided = zero | (margin >= 4e-4)
+    want = br.binarize(ref[~nan]).reshape(len(live), -1, 4)
+    have = got[~nan].reshape(len(live), -1, 4)
+    assert np.array_equal(have[decided], want[decided])
+    return (~decided).sum() / max((~zero).sum(), 1), decided.size, int(zero.sum())
+
+
 def test_bshot352_is_the_binarised_shot352_and_agrees_with_the_float64_reference(pkg, gpu):
     ctx, dev = gpu
     p, n, kp, thin_cnt = bshot_scene()
@@ -104,17 +122,10 @@ def test_bshot352_is_the_binarised_shot352_and_agrees_with_the_float64_reference
     # four elements x the project's 1e-4 descriptor tolerance, and every zero-sum group
     ref, rcnt = shot_ref.describe([(p, n)], [kp], [lrf], RADIUS)
     assert np.array_equal(rcnt, cnt.astype(np.uint32))
-    live = ref[:40].astype(np.float64)
-    s, margin = br.margins(live)
-    zero = s == 0
-    decided = zero | (margin >= 4e-4)
-    left_out = (~decided).sum() / max((~zero).sum(), 1)
-    print(f"groups: {decided.size}, zero-sum {zero.sum()}, non-zero left out {(~decided).sum()} ({left_out:.3f})")
+    assert np.isnan(ref[40]).all() and np.isfinite(ref[:40]).all()
+    left_out, groups, zero = check_bshot_rows(got, shot, ref)
+    print(f"groups: {groups}, zero-sum {zero}, non-zero left out share {left_out:.3f}")
     assert left_out <= 0.30
-    want = br.binarize(ref[:40]).reshape(40, -1, 4)
-    have = got[:40].reshape(40, -1, 4)
-    assert np.array_equal(have[decided], want[decided])
-    assert (got[40] == br.binarize(ref[40:41])[0]).all()                   # NaN row -> ones in the reference too
 
 
 # ------------------------------------------------------------------------------------------------ ismhip_knn_binary

@@ -47,18 +47,26 @@ def runs(pkg, gpu):
     return out
 
 
-@pytest.mark.parametrize("k", range(scenes.N_SCENES))
-def test_rows_are_bit_equal_to_the_restatement(runs, k):
-    s, got, _, want = runs[k]
+def check_raw_rows(got, want):
+    """device raw rows and counts (dict rows, count) against cgf_ref.raw's answer: counts equal and rows bit-equal on every decided keypoint
+    -> the decided mask"""
     dec = ~want["undecided"]
-    print("scene %d: %d keypoints, %d undecided; frames %s" % (k, len(dec), (~dec).sum(), {kd: want["kind"].count(kd) for kd in set(want["kind"])}))
-    assert (~dec).sum() <= scenes.MAX_UNDECIDED * len(dec)
     assert np.array_equal(got["count"][dec], want["sum"][dec])
     bad = [i for i in np.flatnonzero(dec) if not np.array_equal(got["rows"][i].view(np.uint32), want["rows"][i].view(np.uint32))]
     for i in bad[:5]:
         d = np.flatnonzero(got["rows"][i] != want["rows"][i])
         print("keypoint %d (ball %d): bins %s device %s restatement %s" % (i, want["ball"][i], d[:6], got["rows"][i][d[:6]], want["rows"][i][d[:6]]))
     assert not bad
+    return dec
+
+
+@pytest.mark.parametrize("k", range(scenes.N_SCENES))
+def test_rows_are_bit_equal_to_the_restatement(runs, k):
+    s, got, _, want = runs[k]
+    dec = ~want["undecided"]
+    print("scene %d: %d keypoints, %d undecided; frames %s" % (k, len(dec), (~dec).sum(), {kd: want["kind"].count(kd) for kd in set(want["kind"])}))
+    assert (~dec).sum() <= scenes.MAX_UNDECIDED * len(dec)
+    check_raw_rows(got, want)
     assert np.isfinite(got["rows"]).all()                                     # an empty ball is a row of zeros, never NaN
     assert not got["rows"][want["sum"] == 0].any()
 
@@ -119,17 +127,25 @@ def test_same_frames_any_cell_size_same_bytes(pkg, gpu):
     assert np.array_equal(rows[0].view(np.uint32), rows[1].view(np.uint32)) and np.array_equal(rows[0].view(np.uint32), rows[2].view(np.uint32))
 
 
+def check_keypoint_normals(normals, want, cnt, gap):
+    """device PCA keypoint normals against cgf_ref.pca_normal: NaN below three points, else within 1e-5 / gap + 2^-23, unit length
+    -> (compared mask, errors, tolerances)"""
+    assert np.array_equal(np.isnan(normals).any(1), cnt < 3)
+    ok = (cnt >= 3) & (gap > 1e-6)
+    err = np.abs(normals[ok].astype(np.float64) - want[ok]).max(1)
+    tol = 1e-5 / np.minimum(gap[ok], 1.0) + 2.0 ** -23
+    assert (err <= tol).all()
+    assert np.allclose(np.linalg.norm(normals[cnt >= 3], axis=1), 1.0, atol=1e-6)
+    return ok, err, tol
+
+
 @pytest.mark.parametrize("k", range(scenes.N_SCENES))
 def test_keypoint_normals_against_the_float64_pca(runs, k):
     s, got, _, _ = runs[k]
     want, cnt, gap = scenes.keypoint_normals(s)
-    assert np.array_equal(np.isnan(got["normals"]).any(1), cnt < 3)
-    ok = (cnt >= 3) & (gap > 1e-6)
-    err = np.abs(got["normals"][ok].astype(np.float64) - want[ok]).max(1)
-    tol = 1e-5 / np.minimum(gap[ok], 1.0) + 2.0 ** -23
+    ok, err, tol = check_keypoint_normals(got["normals"], want, cnt, gap)
     print("scene %d: %d normals, largest error %.3g (%.3g of its tolerance)" % (k, ok.sum(), err.max() if ok.any() else 0.0, (err / tol).max() if ok.any() else 0.0))
-    assert (err <= tol).all() and (k != 0 or ok.sum() >= 20)                  # scene 0: the keypoints of both patches
-    assert np.allclose(np.linalg.norm(got["normals"][cnt >= 3], axis=1), 1.0, atol=1e-6)
+    assert k != 0 or ok.sum() >= 20                                           # scene 0: the keypoints of both patches
 
 
 def test_refusals(pkg, gpu):

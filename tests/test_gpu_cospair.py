@@ -40,6 +40,23 @@ def counts_of(got, n):
     return np.rint(got.astype(np.float64) * np.repeat(n, cr.LEVEL, axis=1) / lev).astype(np.int64)
 
 
+def check_rows(ref, got, cnt, lev, snap):
+    """device rows, pair counts, level counts and snap indices against cospair_ref.Result: everything integer exact, NaN rows as a whole,
+    decided entries bit for bit, the others inside their interval, 3 n deposits per level and half -> rows with an undecided deposit"""
+    assert got.shape == (len(ref.nan), cr.DIM)
+    assert np.array_equal(snap, ref.snap)
+    assert np.array_equal(lev, ref.n) and np.array_equal(cnt, ref.n.sum(1))
+    assert np.array_equal(np.isnan(got), np.repeat(ref.nan[:, None], cr.DIM, axis=1))
+    live = ~ref.nan
+    decided = (ref.lo == ref.hi) & live[:, None]
+    assert np.array_equal(got.view(np.uint32)[decided], ref.want_lo.view(np.uint32)[decided])
+    open_ = ~decided & live[:, None]
+    assert ((got[open_] >= ref.want_lo[open_]) & (got[open_] <= ref.want_hi[open_])).all()
+    c = counts_of(got[live], ref.n[live]).reshape(-1, cr.LEVELS, 2, cr.BLOCK).sum(3)
+    assert np.array_equal(c[:, :, 0], 3 * ref.n[live]) and np.array_equal(c[:, :, 1], 3 * ref.n[live])
+    return int((~ref.decided_row & live).sum())
+
+
 @pytest.mark.parametrize("name", list(cs.SCENES))
 def test_cospair_matches_the_interval_reference(pkg, gpu, ora, name):
     """shells (points exactly on r_l, an empty level, coincident duplicates, snap ties, a keypoint 100 radii away), queue (1 .. 129
@@ -48,19 +65,9 @@ def test_cospair_matches_the_interval_reference(pkg, gpu, ora, name):
     (ragged runs, no keypoints, one point, a NaN normal at the snapped point, a NaN keypoint, a ball of >= 50 000 pairs), generic"""
     got, cnt, lev, snap = run_scene(pkg, gpu, name)
     ref = cs.reference(name, ora.rgb2lab)
-    assert got.shape == (len(ref.nan), cr.DIM)
-    assert np.array_equal(snap, ref.snap)
-    assert np.array_equal(lev, ref.n) and np.array_equal(cnt, ref.n.sum(1))
-    assert np.array_equal(np.isnan(got), np.repeat(ref.nan[:, None], cr.DIM, axis=1))
+    und_rows = check_rows(ref, got, cnt, lev, snap)
     live = ~ref.nan
-    decided = (ref.lo == ref.hi) & live[:, None]
-    und_rows = int((~ref.decided_row & live).sum())
     print(f"{name}: {live.sum()} rows, {und_rows} with an undecided deposit ({und_rows / max(live.sum(), 1):.3f}), {ref.n.sum()} pairs")
-    assert np.array_equal(got.view(np.uint32)[decided], ref.want_lo.view(np.uint32)[decided])
-    open_ = ~decided & live[:, None]
-    assert ((got[open_] >= ref.want_lo[open_]) & (got[open_] <= ref.want_hi[open_])).all()
-    c = counts_of(got[live], ref.n[live]).reshape(-1, cr.LEVELS, 2, cr.BLOCK).sum(3)
-    assert np.array_equal(c[:, :, 0], 3 * ref.n[live]) and np.array_equal(c[:, :, 1], 3 * ref.n[live])
     if name == "hard":
         geo = counts_of(got, ref.n).reshape(-1, cr.LEVELS, 2, cr.BLOCK)[:, :, 0, :]
         for (o, level), want in cs.scene(name)["want"].items():          # one keypoint per object: row o

@@ -98,6 +98,35 @@ def check_within(label, got, want64, bound):
         assert (err <= bound[~nan]).all(), label
 
 
+def check_scores(name, d, arrays, rgb2lab, pc1, pc2, pcn, g_curv, col, cnt, g_kpq, pcs=None):
+    """the principal curvatures and both geometry scores and the colour score of the Device d (on its own voxel keypoints, at its leaf)
+    against the restatement, object by object: counts and the colour score exact, pc1, pc2, curvature and kpq within their derived bounds.
+    pcs: ref.principal_curvatures per object where the caller has them -> the number of keypoints compared"""
+    off, xyz, nrm, rgba = arrays
+    lab = ref.lab_table(rgb2lab, rgba)
+    kp_lab = ref.lab_table(rgb2lab, d.kp_rgba) if len(d.kp_rgba) else np.zeros((0, 3), f32)
+    n_kp = 0
+    for o, (p, nr, lb) in objects(off, xyz, nrm, lab):
+        kb, ke = int(d.ko[o]), int(d.ko[o + 1])
+        b, e = int(off[o]), int(off[o + 1])
+        pc = ref.principal_curvatures(p, nr, d.leaf) if pcs is None else pcs[o]
+        assert np.array_equal(pcn[b:e], pc["count"]), (name, o)
+        check_within("%s object %d pc1" % (name, o), pc1[b:e], pc["pc1_64"], ref.pc_bound(pc["pc1_64"], pc["pc1_64"], pc["floor"]))
+        check_within("%s object %d pc2" % (name, o), pc2[b:e], pc["pc2_64"], ref.pc_bound(pc["pc1_64"], pc["pc2_64"], pc["floor"]))
+        if ke == kb:
+            continue
+        n_kp += ke - kb
+        a = ref.scores(p, d.kp[kb:ke], d.leaf, "curvature", "colordistance", MAX_DIST, lab=lb, kp_lab=kp_lab[kb:ke])
+        assert np.array_equal(cnt[kb:ke], a["count"]), (name, o)
+        assert same_bits(col[kb:ke], a["color"]), (name, o)              # integer counts: bit-exact, NaN for an empty ball included
+        nan = np.isnan(a["geo"])
+        check_within("%s object %d curvature" % (name, o), g_curv[kb:ke], np.where(nan, np.nan, a["geo64"]), a["bound"])
+        # kpq from the restatement's own curvatures; the bound carries both sides' pc error through the expression
+        k = ref.scores(p, d.kp[kb:ke], d.leaf, "kpq", pc=pc)
+        check_within("%s object %d kpq" % (name, o), g_kpq[kb:ke], np.where(np.isnan(k["geo"]), np.nan, k["geo64"]), k["bound"])
+    return n_kp
+
+
 @pytest.mark.parametrize("name", ["generic", "sizes", "gap", "holes", "non_unit"])
 def test_scores_against_restatement(pkg, gpu, ora, name):
     off, xyz, nrm, rgba = batch(name)
@@ -107,27 +136,7 @@ def test_scores_against_restatement(pkg, gpu, ora, name):
     g_kpq, col2, cnt2 = d.scores("kpq")
     d.ctx.sync()
     assert same_bits(col, col2) and same_bits(cnt, cnt2)
-    lab = ref.lab_table(ora.rgb2lab, rgba)
-    kp_lab = ref.lab_table(ora.rgb2lab, d.kp_rgba) if len(d.kp_rgba) else np.zeros((0, 3), f32)
-    n_kp = 0
-    for o, (p, nr, lb) in objects(off, xyz, nrm, lab):
-        kb, ke = int(d.ko[o]), int(d.ko[o + 1])
-        b, e = int(off[o]), int(off[o + 1])
-        pc = ref.principal_curvatures(p, nr, LEAF)
-        assert np.array_equal(pcn[b:e], pc["count"]), (name, o)
-        check_within("%s object %d pc1" % (name, o), pc1[b:e], pc["pc1_64"], ref.pc_bound(pc["pc1_64"], pc["pc1_64"], pc["floor"]))
-        check_within("%s object %d pc2" % (name, o), pc2[b:e], pc["pc2_64"], ref.pc_bound(pc["pc1_64"], pc["pc2_64"], pc["floor"]))
-        if ke == kb:
-            continue
-        n_kp += ke - kb
-        a = ref.scores(p, d.kp[kb:ke], LEAF, "curvature", "colordistance", MAX_DIST, lab=lb, kp_lab=kp_lab[kb:ke])
-        assert np.array_equal(cnt[kb:ke], a["count"]), (name, o)
-        assert same_bits(col[kb:ke], a["color"]), (name, o)              # integer counts: bit-exact, NaN for an empty ball included
-        nan = np.isnan(a["geo"])
-        check_within("%s object %d curvature" % (name, o), g_curv[kb:ke], np.where(nan, np.nan, a["geo64"]), a["bound"])
-        # kpq from the restatement's own curvatures; the bound carries both sides' pc error through the expression
-        k = ref.scores(p, d.kp[kb:ke], LEAF, "kpq", pc=pc)
-        check_within("%s object %d kpq" % (name, o), g_kpq[kb:ke], np.where(np.isnan(k["geo"]), np.nan, k["geo64"]), k["bound"])
+    n_kp = check_scores(name, d, batch(name), ora.rgb2lab, pc1, pc2, pcn, g_curv, col, cnt, g_kpq)
     print("%s: %d keypoints in %d objects" % (name, n_kp, len(off) - 1))
     assert n_kp >= 20
     d.close()

@@ -68,22 +68,29 @@ def same_bytes(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.parametrize("name", list(sc.SCENES))
-def test_fpfh33_inside_the_float64_intervals(pkg, gpu, ora, name):
-    ref = sc.reference(name)
-    got, cnt = device_rows(pkg, gpu, name)
+def check_rows(ref, got, cnt):
+    """device rows and counts against the intervals of fpfh_ref.Result: NaN rows as a whole, exact counts, every value of a keypoint that is
+    not exempt inside [lo, hi] within TOL, block sums 0 or 100 -> the excesses"""
     assert np.array_equal(np.isnan(got).any(1), ref.nan) and np.array_equal(np.isnan(got).all(1), ref.nan)
     assert np.array_equal(cnt, ref.count)
     ex = excess(ref, got)
-    ok = ~ref.nan & ~ref.exempt
-    print(f"{name}: largest excess {ex.max(initial=0.0):.3g}, undecided {int(ref.undecided.sum())} of {int(ref.deposits.sum())} deposits, "
-          f"min_move {ref.min_move[ok].min(initial=np.inf):.3g}, exempt keypoints {int(ref.exempt.sum())}")
     assert ex.max(initial=0.0) <= TOL, np.argwhere(ex > TOL)[:10]
     sums = got[~ref.nan].reshape(-1, 3, 11).sum(2)
     zero = (ref.hi[~ref.nan].reshape(-1, 3, 11).sum(2) == 0) & ~ref.exempt[~ref.nan][:, None]
     assert (sums[zero] == 0).all()
     nonzero = ~zero & ~ref.exempt[~ref.nan][:, None]
     assert (np.abs(sums - 100) <= 1e-3)[nonzero].all()
+    return ex
+
+
+@pytest.mark.parametrize("name", list(sc.SCENES))
+def test_fpfh33_inside_the_float64_intervals(pkg, gpu, ora, name):
+    ref = sc.reference(name)
+    got, cnt = device_rows(pkg, gpu, name)
+    ex = check_rows(ref, got, cnt)
+    ok = ~ref.nan & ~ref.exempt
+    print(f"{name}: largest excess {ex.max(initial=0.0):.3g}, undecided {int(ref.undecided.sum())} of {int(ref.deposits.sum())} deposits, "
+          f"min_move {ref.min_move[ok].min(initial=np.inf):.3g}, exempt keypoints {int(ref.exempt.sum())}")
     # only the degenerate pairs exempt a keypoint from the intervals; there the oracle's row decides
     assert int(ref.exempt.sum()) == (len(sc.scene(name)["degenerate"]) if name == "pole_and_degenerate" else 0)
     if ref.exempt.any():

@@ -17,6 +17,7 @@ import short_shot_scenes as sss
 from test_gpu_frontend import TOL, Batch, T, assert_close_nan
 from test_gpu_host_routes import _split
 from test_gpu_parity import _cb
+from test_gpu_short_shot import check_rows
 
 pytestmark = pytest.mark.gpu
 _frames = {}
@@ -52,11 +53,7 @@ def test_short_cshot_matches_the_restatement(pkg, gpu, ora, case):
     finite = ~np.isnan(want).any(1)
     err = np.abs(got[finite] - want[finite]).max() if finite.any() else 0.0
     print(f"{case.name}: {finite.sum()} of {len(want)} rows finite, max |device - restatement| {err:.3g}, switch margin on these frames {switch.min():.3g}")
-    assert got.shape == (len(want), case.dim)
-    assert np.array_equal(cnt, wcnt)
-    assert_close_nan(got, want, TOL)
-    if finite.any():
-        assert np.abs(np.linalg.norm(got[finite].astype(np.float64), axis=1) - 1).max() < 1e-6
+    check_rows(got, cnt, want, wcnt, case.dim)
     if case.geo.name.startswith("queue") and case.geo.min_radius_relative < 0.9:
         assert finite.all() and wcnt.min() == 4
 

@@ -36,6 +36,16 @@ def run_case(pkg, gpu, case):
         s.close()
 
 
+def check_rows(got, cnt, want, wcnt, dim):
+    """device rows and counts against the restatement's: shape, exact counts and NaN pattern, values within TOL, finite rows of unit norm"""
+    assert got.shape == (len(want), dim)
+    assert np.array_equal(cnt, wcnt)
+    assert_close_nan(got, want, TOL)
+    finite = ~np.isnan(want).any(1)
+    if finite.any():
+        assert np.abs(np.linalg.norm(got[finite].astype(np.float64), axis=1) - 1).max() < 1e-6
+
+
 @pytest.mark.parametrize("case", sss.all_cases(), ids=lambda c: c.name)
 def test_short_shot_matches_the_restatement(pkg, gpu, case):
     """the four grids on the mid object (a keypoint on a cloud point, a NaN frame row, an empty ball inside the grid and one off the
@@ -47,11 +57,7 @@ def test_short_shot_matches_the_restatement(pkg, gpu, case):
     finite = ~np.isnan(want).any(1)
     err = np.abs(got[finite] - want[finite]).max() if finite.any() else 0.0
     print(f"{case.name}: {finite.sum()} of {len(want)} rows finite, max |device - restatement| {err:.3g}, switch margin on these frames {switch.min():.3g}")
-    assert got.shape == (len(want), case.bins[0] * case.bins[1] * case.bins[2])
-    assert np.array_equal(cnt, wcnt)
-    assert_close_nan(got, want, TOL)
-    if finite.any():
-        assert np.abs(np.linalg.norm(got[finite].astype(np.float64), axis=1) - 1).max() < 1e-6
+    check_rows(got, cnt, want, wcnt, case.bins[0] * case.bins[1] * case.bins[2])
     if case.name.startswith("queue") and case.min_radius_relative < 0.9:
         assert finite.all() and wcnt.min() == 4
 
