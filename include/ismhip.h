@@ -574,6 +574,52 @@ int  ismhip_global_gasd(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_region
 /* Diagnostic: the hue bin of ismhip_global_gasd's colour block alone, one thread per colour. rgba: device [n] packed 0x00RRGGBB, bits
  * 24..31 ignored. out: device uint8 [n], the bin 0..11, or 255 where the rule deposits nothing. Asynchronous. Off every hot path. */
 int  ismhip_gasd_hue_bins(ismhip_ctx* ctx, int n, const uint32_t* rgba, uint8_t* out);
+/* ismhip_region_mvbb: the minimum-volume bounding box of a region, Utils::computeMVBB (utils/utils.cpp:242-293), which is
+ * gdiam_approx_mvbb(points, n, 0.0) of libgdiam-1.3: stated here as this library's own arithmetic (DESIGN.md section 4.24 names the
+ * deviations and pins the result against the real library's). The region and its finite points are those of the entries above;
+ * n_sel_out likewise. A point is its three floats converted to double (utils.cpp:249-257), its INDEX the one inside its object.
+ * Everything below is double, unfused, in the written order; dot(a, b) = (a0*b0 + a1*b1) + a2*b2; normalise(v): len = sqrt(dot(v, v)),
+ * v / len per component unless len == 0; cross(a, b) = (a1*b2 - a2*b1, -(a0*b2 - a2*b0), a0*b1 - a1*b0). bound(axes): per axis k
+ * lo_k / hi_k = the minimum / maximum over the points of dot(p, axis_k); volume = ((hi0 - lo0) * (hi1 - lo1)) * (hi2 - lo2).
+ * base(u): gdiam_generate_orthonormal_base (gdiam.cpp:1226-1270) on normalise(u), its case list as written, giving (bx, by).
+ *   A (gdiam.cpp:1138-1149, eps 0: exact). Over all pairs i < j: d2 = (dx*dx + dy*dy) + dz*dz of d = p_i - p_j; the pair of largest d2,
+ *     ties to the lowest (i, j). d1 = normalise(p_i - p_j).
+ *   B (:1151-1169). The same over the projected points p' = p - dot(p, d1) * d1 (per component). With v = p'_i - p'_j of that pair:
+ *     q = v - dot(v, d1) * d1, len = sqrt(dot(q, q)); len < 1e-6 (collinear points): (d2, d3) = base(d1); else d2 = q / len,
+ *     d3 = normalise(cross(d1, d2)).
+ *   C (:1191-1200). best = bound(d1, d2, d3); if bound(identity) has a strictly smaller volume, best = that, with identity axes.
+ *   D (gdiam_mvbb_optimize, :2245-2270), rounds r = 0 .. ISMHIP_MVBB_ROUNDS - 1: u = normalise(axis r % 3 of best), (bx, by) = base(u);
+ *     every point (x, y) = (dot(p, bx), dot(p, by)). The convex hull of these, STRICT vertices only, counter-clockwise from the lowest
+ *     (x, y): monotone chain over the points sorted by (x, y, index), a point that repeats the (x, y) of the one before it skipped,
+ *     turn(o, a, b) = (a.x - o.x)*(b.y - o.y) - (a.y - o.y)*(b.x - o.x), a vertex popped while turn <= 0. (The kernel first drops
+ *     points inside the polygon of the extremes in eight directions by a margin of 2^-40 M^2, M the larger extent in x and y: a
+ *     thousand times the rounding of the test, so no hull vertex is lost.) For every hull edge from vertex a to its successor b:
+ *     e = (b - a) / sqrt(ex*ex + ey*ey); over the hull's vertices s = x*e.x + y*e.y and t = y*e.x - x*e.y; area = (max s - min s) *
+ *     (max t - min t). The edge of smallest area, ties to the lowest point index of its start vertex. (Equal to the reference's
+ *     rotating calipers, :1977-2022, in exact arithmetic; not its tan / atan2 arithmetic.) A hull of one vertex: e = (1, 0).
+ *     o1 = normalise((-e.y) * bx + e.x * by) across the edge, o2 = normalise(e.x * bx + e.y * by) along it (the order in which the
+ *     reference lifts its rectangle, :2161-2192: it decides which axis a later round takes); cand = bound(u, o1, o2); best = cand if
+ *     cand's volume < best's volume * (1 - 2^-36). (The reference asks for strictly smaller. A box that has converged is found again
+ *     by later rounds, from either of its two flush hull edges, with a volume that differs in the last bits: there "strictly" is
+ *     decided by rounding, in the reference too, and with it the axis order of every later round. An improvement below 1.5e-11 of
+ *     the volume is declined instead.)
+ *   Output (the reference's axis order, signs and handedness are accidents of its traversal): axes ordered by descending extent
+ *     hi - lo, ties to the earlier axis; axes 1 and 2 negated (with their lo / hi) where their component of largest magnitude (lowest
+ *     index on a tie) is negative; axis 3 = cross(axis 1, axis 2), its lo / hi negated and swapped if that reverses the old axis 3.
+ *     axes9_out: rows = axes. size_out = hi - lo per axis. center_out (world) = (mid0*axis1 + mid1*axis2) + mid2*axis3 per component,
+ *     mid = (lo + hi) * 0.5. volume_out (device double [n_regions] or NULL): best's volume. Float outputs are the doubles cast once.
+ *   Degenerate: n_sel = 1 or all points coincident (the reference asserts): identity axes, zero size, centre the point, volume 0.
+ *     n_sel = 0: NaN centre and axes, zero size, volume 0.
+ * trace_out (device int32 [n_regions * ISMHIP_MVBB_TRACE] or NULL): [0, 1] the pair of A, [2, 3] of B, [4] C took the axis-aligned box,
+ * [5] B found the points collinear, [6] degenerate, [7] a diagnostic that is no part of the definition: the most points the kernel's
+ * pre-filter left in a round (above 768 they went through the work buffer); round r at [8 + 4 r]: taken, hull size, the chosen edge's two point indices.
+ * Indices that do not exist are -1. One workgroup per region, a region of any size; no float atomics: the same bits on every call.
+ * Checked as the entries above ("region_mvbb: bad argument"). Timer "region_mvbb". Asynchronous. */
+#define ISMHIP_MVBB_ROUNDS 10
+#define ISMHIP_MVBB_TRACE  48
+int  ismhip_region_mvbb(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                        const float* region_radius, uint32_t* n_sel_out, float* center_out /*[n*3], world*/, float* size_out /*[n*3]*/,
+                        float* axes9_out /*[n*9], rows = axes*/, double* volume_out /*[n] or NULL*/, int32_t* trace_out /*[n*48] or NULL*/);
 
 /* ---- keypoints (the step in front of the path): KeypointsVoxelGrid::iComputeKeypoints
  *      (keypoints/keypoints_voxel_grid.cpp:30-46) -> pcl::VoxelGrid<PointXYZRGB> with a cubic leaf. Per object the

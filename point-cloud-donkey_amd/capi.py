@@ -38,7 +38,7 @@ EXPORTS = [
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
-    "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins",
+    "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins", "ismhip_region_mvbb",
     "ismhip_normal_curvature", "ismhip_voxel_downsample_xyzi", "ismhip_sift3d_scale_space", "ismhip_sift3d_extrema", "ismhip_sift3d_keypoints",
 ]
 SIFT3D_MIN_POINTS = 25             # ISMHIP_SIFT3D_MIN_POINTS: an octave below it ends the object; also the extrema's number of neighbours
@@ -767,6 +767,25 @@ def global_gasd(ctx, cloud, dev, region_obj, region_center=None, region_radius=N
     ctx.check(lib().ismhip_global_gasd(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vd, C.c_int(1 if with_color else 0),
                                        _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["frame"]), _p(out["max_coord"]),
                                        _p(out["desc"]), _p(out.get("counts"))), "ismhip_global_gasd")
+    return out
+
+
+MVBB_ROUNDS, MVBB_TRACE = 10, 48   # ISMHIP_MVBB_ROUNDS, ISMHIP_MVBB_TRACE
+
+
+def region_mvbb(ctx, cloud, dev, region_obj, region_center=None, region_radius=None, want_volume=True, want_trace=True):
+    """ismhip_region_mvbb on regions as global_short_shot -> dict of device tensors n_sel [n], center [n, 3] (world), size [n, 3]
+    (descending), axes [n, 9] (rows = axes) and, unless switched off, volume [n] (float64) and trace [n, 48] (int32)"""
+    torch = _torch()
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    out = dict(n_sel=torch.empty((n,), dtype=torch.int32, device=dev), center=torch.empty((n, 3), dtype=torch.float32, device=dev),
+               size=torch.empty((n, 3), dtype=torch.float32, device=dev), axes=torch.empty((n, 9), dtype=torch.float32, device=dev))
+    if want_volume:
+        out["volume"] = torch.empty((n,), dtype=torch.float64, device=dev)
+    if want_trace:
+        out["trace"] = torch.empty((n, MVBB_TRACE), dtype=torch.int32, device=dev)
+    ctx.check(lib().ismhip_region_mvbb(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), _p(out["n_sel"]), _p(out["center"]),
+                                       _p(out["size"]), _p(out["axes"]), _p(out.get("volume")), _p(out.get("trace"))), "ismhip_region_mvbb")
     return out
 
 

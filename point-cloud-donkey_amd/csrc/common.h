@@ -190,13 +190,14 @@ struct ismhip_ctx {
     uint32_t knn_binary_launches = 0; // ismhip_knn_binary calls that searched (counter "knn_binary_launches"; tests of the host route)
     uint32_t rank_launches = 0;       // ismhip_rank_scores / ismhip_rank_select calls that reached the device (counter "rank_launches"; tests of the host route)
     bool iss3d_wave = false;          // env ISMHIP_ISS3D_MAP=wave: the ISS3D saliency sweep with one wave per query (k_pca_normals' mapping) instead of one thread per query (A/B runs, tests; same bits: the scatter sums are order free, iss3d.hip)
+    int mvbb_work_mb = 512;      // env ISMHIP_MVBB_WORK_MB: work buffer of one ismhip_region_mvbb launch in MiB; a batch that needs more takes several launches (tests; same results)
     int knn_mode = 0;            // env ISMHIP_KNN_MODE = f16 (0, default) | bf16x3 (1) | f32 (2): squared-L2 candidate kernel (A/B runs, tests)
 };
 
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE, SCR_ISS3D, SCR_CULL_SCALE, SCR_CULL_SELECT, SCR_RIFT, SCR_RIFT_SCALE, SCR_ESF_LIST, SCR_SIFT3D, SCR_SIFT3D_SCALE, SCR_SIFT3D_DRIVER,
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE, SCR_ISS3D, SCR_CULL_SCALE, SCR_CULL_SELECT, SCR_RIFT, SCR_RIFT_SCALE, SCR_ESF_LIST, SCR_SIFT3D, SCR_SIFT3D_SCALE, SCR_SIFT3D_DRIVER, SCR_MVBB,
     SCR_SIFT3D_OCTAVE    // the last one: octave i of ismhip_sift3d_keypoints takes slot SCR_SIFT3D_OCTAVE + i
 };
 

@@ -69,6 +69,7 @@ static int ctx_create_impl(int device, void* stream, bool own, ismhip_ctx** out)
     ismhip_ctx* ctx = new ismhip_ctx();
     ctx->device = device;
     { const char* e = getenv("ISMHIP_KNN_MODE"); ctx->knn_mode = !e ? 0 : (!strcmp(e, "bf16x3") ? 1 : (!strcmp(e, "f32") ? 2 : 0)); }
+    { const char* e = getenv("ISMHIP_MVBB_WORK_MB"); if (e && atoi(e) > 0) ctx->mvbb_work_mb = atoi(e); }
     { const char* e = getenv("ISMHIP_XCD_MAP"); ctx->xcd_map = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_GRID_FUSED"); ctx->grid_fused = !(e && e[0] == '0'); }
     { const char* e = getenv("ISMHIP_KP_ORDER"); ctx->kp_order = !(e && e[0] == '0'); }

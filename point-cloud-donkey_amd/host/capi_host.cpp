@@ -1,5 +1,6 @@
 // capi_host.cpp — small C shim over the C++ host classes so that the Python test-suite can drive ImplicitShapeModel
 // (train / write / read / detectBatch) through ctypes. Not part of the drop-in boundary (that is include/ismhip.h).
+#include <algorithm>
 #include <cstring>
 #include <string>
 
@@ -117,6 +118,25 @@ int ism3d_last_features(void* m, int which, int* dim_out, int* n_obj_out, uint32
         cp(off_out, d.off); cp(desc, d.desc); cp(lrf9, d.lrf); cp(cls, d.cls); cp(model, d.model); cp(center, d.center);
         if (kxyz) for (uint32_t i = 0; i < d.n; ++i) { kxyz[3 * i] = d.kx[i]; kxyz[3 * i + 1] = d.ky[i]; kxyz[3 * i + 2] = d.kz[i]; }
         return (int)d.n;)
+}
+// diagnostics (tests): the box of every training object of the last train(), in training order (class by class, model by model):
+// out10 [n * 10] = position, size, rotQuat (w, x, y, z); may be NULL. Returns their number.
+int ism3d_last_train_boxes(void* m, float* out10) {
+    GUARD(
+        const auto& b = ((ImplicitShapeModel*)m)->lastTrainingBoxes();
+        for (size_t i = 0; out10 && i < b.size(); ++i) {
+            std::copy(b[i].position.begin(), b[i].position.end(), out10 + i * 10); std::copy(b[i].size.begin(), b[i].size.end(), out10 + i * 10 + 3);
+            std::copy(b[i].rotQuat.begin(), b[i].rotQuat.end(), out10 + i * 10 + 6);
+        }
+        return (int)b.size();)
+}
+// diagnostics (tests): per region of the last detectBatch()'s global step (ism3d_last_global's order) the box made for an object without
+// maxima: out10 [n * 10] as above, NaN where no box was made; may be NULL. Returns the number of regions.
+int ism3d_last_global_boxes(void* m, float* out10) {
+    GUARD(
+        const auto& d = ((ImplicitShapeModel*)m)->getVoting()->lastGlobal();
+        if (out10 && !d.box.empty()) std::memcpy(out10, d.box.data(), d.box.size() * 4);
+        return (int)d.region_obj.size();)
 }
 // diagnostics (tests): the vote space of the last detectBatch(): slot_off [n_obj+1], pos [n*3], weight, cls, inst [n]. Any array may be
 // NULL. Returns the number of vote slots.

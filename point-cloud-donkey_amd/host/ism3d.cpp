@@ -889,7 +889,8 @@ static float hostDistance(int metric, const float* a, const float* b, int n) {
 
 void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::vector<unsigned>& feat_class, const std::vector<unsigned>& feat_instance,
                         const std::vector<unsigned>& feat_model, const std::vector<std::array<float, 3>>& feat_center,
-                        const std::vector<std::array<float, 3>>& feat_bbox_size, int metric, int n_classes, const Clustering& clustering) {
+                        const std::vector<std::array<float, 3>>& feat_bbox_size, int metric, int n_classes, const Clustering& clustering,
+                        const std::vector<std::array<float, 4>>* feat_bbox_quat) {
     // codebook.cpp:64-368 with KNN / KNNRule activation; codewords = cluster centres (implicit_shape_model.cpp:445-475), or one per
     // training feature for Clustering "None" (clustering_none.cpp:25-35)
     const uint32_t n = f.n;
@@ -960,7 +961,16 @@ void Codebook::activate(DeviceSession& s, const DeviceFeatures& f, const std::ve
             out.vote_weight.push_back(vote_weight[v]); out.vote_class_weight.push_back(vote_cw[v]);
             // addCodeword (codeword_distribution.cpp:63-70): the box in the keypoint's frame, rotQuat = box.rotQuat * conj(q(LRF)); AABB boxes carry (1,0,0,0)
             float q[4]; hostRotQuaternion(&lrf[(size_t)fi * 9], q);
-            out.vote_bbox_quat.push_back(q[0]); out.vote_bbox_quat.push_back(-q[1]); out.vote_bbox_quat.push_back(-q[2]); out.vote_bbox_quat.push_back(-q[3]);
+            float bq[4] = {q[0], -q[1], -q[2], -q[3]};
+            if (feat_bbox_quat) {                             // the quaternion product a * conj(q), a the box's (MVBB)
+                const std::array<float, 4>& a = (*feat_bbox_quat)[fi];
+                const float b[4] = {bq[0], bq[1], bq[2], bq[3]};
+                bq[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+                bq[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+                bq[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
+                bq[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+            }
+            out.vote_bbox_quat.insert(out.vote_bbox_quat.end(), bq, bq + 4);
             for (int d = 0; d < 3; ++d) out.vote_bbox_size.push_back(feat_bbox_size[fi][d]);
         }
         out.vote_offsets.push_back((uint32_t)out.vote_class.size());
@@ -1483,7 +1493,7 @@ void Voting::fillRansacParams(DeviceSession& s, const std::vector<float>& class_
     R.seed = 12345ull;                                         // PCL seeds every cluster's generator with 12345; the draws are this library's
 }
 void Voting::clear() {}
-std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds) {
+std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s, int metric) {
     if (m_max_filter_type != "None" && m_max_filter_type != "Simple" && m_max_filter_type != "Merge")
         LOG_ERROR("Invalid maxima filter type specified: " << m_max_filter_type << "! No filtering is performed!");            // maxima_handler.cpp:292-295
     if (m_max_type_param != "None" && m_max_type_param != "Default" && m_max_type_param != "BandwidthVotes" && m_max_type_param != "VotingSpaceVotes" &&
@@ -1491,7 +1501,7 @@ std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s, int
         LOG_WARN("Invalid single object maximum type: " << m_max_type_param << "! Using default instead.");                   // maxima_handler.h:53-57
     std::vector<std::vector<VotingMaximum>> out(s.n_obj);
     if (s.n_slots == 0) {                                      // no vote in the whole batch: no maxima; the global step may still speak
-        if (m_use_global_features) verifyWithGlobalFeatures(s, metric, clouds, out);
+        if (m_use_global_features) verifyWithGlobalFeatures(s, metric, out);
         return out;
     }
     if (singleObjectMaxType() != ISMHIP_SOM_MEANSHIFT) {       // voting_mean_shift.cpp:124-157: the query point is the centroid of the object's cloud
@@ -1500,14 +1510,36 @@ std::vector<std::vector<VotingMaximum>> Voting::findMaxima(DeviceSession& s, int
         s.check(ismhip_cloud_radii(s.ctx, s.cloud, s.obj_cen.as<float>(), s.obj_rad.as<float>()), "ismhip_cloud_radii");
     }
     iFindMaxima(s, out);
-    if (m_use_global_features) verifyWithGlobalFeatures(s, metric, clouds, out);
+    if (m_use_global_features) verifyWithGlobalFeatures(s, metric, out);
     return out;
 }
-static void cloudAABB(const PointCloud& c, std::array<float, 3>& center, std::array<float, 3>& size);
+// Utils::computeMVBB (utils.cpp:242-293) of regions of a search surface (ismhip_region_mvbb): position in the world, size, and rotQuat =
+// matrix2Quat of the matrix whose COLUMNS are the axes (:275-287), which that function reads as memory rows: hostRotQuaternion of the
+// axes rows. quatRotateInv (:290) of the centre in box coordinates is then the world centre the device returns.
+static std::vector<BoundingBox> regionMVBBs(DeviceSession& s, const ismhip_cloud* cloud, const std::vector<int32_t>& r_obj, const std::vector<float>& r_cen,
+                                            const std::vector<float>& r_rad, std::vector<uint32_t>* n_sel_out = nullptr) {
+    const size_t R = r_obj.size();
+    std::vector<BoundingBox> boxes(R);
+    if (R == 0) return boxes;
+    DevBuf obj, cen, rad, n_sel, center, size, axes;
+    DeviceSession::h2d(obj, r_obj); DeviceSession::h2d(cen, r_cen); DeviceSession::h2d(rad, r_rad);
+    n_sel.reserve(R * 4); center.reserve(R * 12); size.reserve(R * 12); axes.reserve(R * 36);
+    s.check(ismhip_region_mvbb(s.ctx, cloud, (int)R, obj.as<int32_t>(), cen.as<float>(), rad.as<float>(), n_sel.as<uint32_t>(), center.as<float>(),
+                               size.as<float>(), axes.as<float>(), nullptr, nullptr), "ismhip_region_mvbb");
+    std::vector<uint32_t> hn; std::vector<float> hc, hs, ha;
+    s.d2h(hn, n_sel, R); s.d2h(hc, center, R * 3); s.d2h(hs, size, R * 3); s.d2h(ha, axes, R * 9);
+    for (size_t r = 0; r < R; ++r) {
+        if (hn[r] == 0) continue;                             // nothing selected: the default box
+        for (int d = 0; d < 3; ++d) { boxes[r].position[d] = hc[r * 3 + d]; boxes[r].size[d] = hs[r * 3 + d]; }
+        hostRotQuaternion(&ha[r * 9], boxes[r].rotQuat.data());
+    }
+    if (n_sel_out) *n_sel_out = hn;
+    return boxes;
+}
 // The global step of Voting::findMaxima (voting.cpp:217-298) for a whole batch: one region per object (single-object mode) or per
 // maximum (its position, the class's median box edge as radius: global_radii, voting.cpp:634), ALL regions in one device call, one exact
 // kNN call on the stored training rows, then classifyWithKNN and the merge sequence on the host.
-void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds, std::vector<std::vector<VotingMaximum>>& out) {
+void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, std::vector<std::vector<VotingMaximum>>& out) {
     if (!m_global_descriptor) throw RuntimeException("UseGlobalFeatures needs a built GlobalFeatures type (built: " + std::string(GlobalFeatures::builtTypes()) + ")");
     // the stored rows in the order the reference concatenates them (voting.cpp:660-701): class, cloud, row
     std::vector<float> rows; std::vector<unsigned> row_class, row_inst;
@@ -1580,6 +1612,7 @@ void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::v
         }
     }
     // hypotheses onto the maxima
+    std::vector<int> boxless;                                                        // single-object mode: regions of objects without maxima
     for (int r = 0; r < R; ++r) {
         const int o = r_obj[r];
         if (!m_single_object_mode) {
@@ -1589,13 +1622,23 @@ void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::v
             continue;
         }
         for (VotingMaximum& m : out[o]) m.globalHypothesis = hyp[r];                 // voting.cpp:246-247
-        if (out[o].empty() && dump.n_sel[r] > 0) {                                   // :250-260; the box is axis-aligned (MVBB is not built)
+        if (out[o].empty() && dump.n_sel[r] > 0) boxless.push_back(r);                // :250-260
+    }
+    dump.box.assign((size_t)R * 10, std::numeric_limits<float>::quiet_NaN());
+    if (!boxless.empty()) {                                                          // their boxes: Utils::computeMVBB of the region (:258), one call
+        std::vector<int32_t> b_obj; std::vector<float> b_cen, b_rad;
+        for (int r : boxless) { b_obj.push_back(r_obj[r]); b_cen.insert(b_cen.end(), r_cen.begin() + (size_t)r * 3, r_cen.begin() + (size_t)r * 3 + 3); b_rad.push_back(r_rad[r]); }
+        const std::vector<BoundingBox> boxes = regionMVBBs(s, s.cloud, b_obj, b_cen, b_rad);
+        for (size_t i = 0; i < boxless.size(); ++i) {
+            const int r = boxless[i], o = r_obj[r];
             VotingMaximum m;
             m.globalHypothesis = hyp[r];
             m.classId = hyp[r].classId; m.weight = hyp[r].classWeight; m.instanceId = hyp[r].instanceId;
             m.position = {dump.centroid[(size_t)r * 3], dump.centroid[(size_t)r * 3 + 1], dump.centroid[(size_t)r * 3 + 2]};
-            m.boundingBox.position = m.position;
-            if (clouds && (size_t)o < clouds->size() && !(*clouds)[o]->empty()) cloudAABB(*(*clouds)[o], m.boundingBox.position, m.boundingBox.size);
+            m.boundingBox = boxes[i];
+            float* b = &dump.box[(size_t)r * 10];
+            std::copy(boxes[i].position.begin(), boxes[i].position.end(), b); std::copy(boxes[i].size.begin(), boxes[i].size.end(), b + 3);
+            std::copy(boxes[i].rotQuat.begin(), boxes[i].rotQuat.end(), b + 6);
             out[o].push_back(m);
         }
     }
@@ -2274,8 +2317,9 @@ static float cloudRadius(const PointCloud& c) {
 void ImplicitShapeModel::train() {                // :252-500
     if (m_training_clouds.empty()) { LOG_WARN("no training objects found"); return; }
     g_log_info = m_logging;
-    if (m_bounding_box_type != "AABB")
-        LOG_WARN("BoundingBoxType \"" << m_bounding_box_type << "\": MVBB is not built, using the axis-aligned box centre for the training votes");
+    if (m_bounding_box_type != "AABB" && m_bounding_box_type != "MVBB")                // :324-333
+        throw RuntimeException("invalid bounding box type: " + m_bounding_box_type);
+    const bool mvbb = m_bounding_box_type == "MVBB";
     for (auto& kv : m_training_clouds) for (auto& c : kv.second) {
         m_feature_descriptor->checkInput(*c);
         if (m_global_descriptor) m_global_descriptor->checkInput(*c);              // training describes every cloud globally as well
@@ -2292,6 +2336,8 @@ void ImplicitShapeModel::train() {                // :252-500
     auto all = std::make_shared<DeviceFeatures>();
     std::vector<float> hdesc, hlrf, hkx, hky, hkz;
     std::vector<unsigned> fclass, finst, fmodel; std::vector<std::array<float, 3>> fcenter, fbox;
+    std::vector<std::array<float, 4>> fquat;                    // MVBB only: the box's rotQuat per feature
+    m_last_boxes.clear();
     std::map<unsigned, std::vector<std::array<float, 3>>> box_sizes; std::map<unsigned, std::vector<float>> object_radii;
     Voting::GlobalFeatureMap global_features;                   // :267, :394-415: one list per training cloud, NaN rows dropped
     const size_t chunk = 32;
@@ -2300,6 +2346,18 @@ void ImplicitShapeModel::train() {                // :252-500
         std::vector<const PointCloud*> part(clouds.begin() + b, clouds.begin() + std::min(clouds.size(), b + chunk));
         // pre-filters first (:739-821); the bounding box and the radius below are taken from the unfiltered cloud, as the reference does
         // (:296-336 run before computeFeatures). An object a filter empties contributes no features.
+        std::vector<BoundingBox> boxes(part.size());
+        if (mvbb) {                                             // Utils::computeMVBB of every unfiltered cloud of the chunk: one whole-object region each
+            s.uploadPoints(part, false, true);
+            const ismhip_point_arrays p = s.pts.view(false);
+            ismhip_cloud* whole = nullptr;
+            // the kernel reads the object's span (finite points first), never the grid: a cell this coarse puts every object into one
+            s.check(ismhip_cloud_create(s.ctx, s.n_obj, s.pt_off.data(), p.x, p.y, p.z, p.nx, p.ny, p.nz, nullptr, 1e6f, &whole), "ismhip_cloud_create");
+            std::vector<int32_t> r_obj(part.size()); std::iota(r_obj.begin(), r_obj.end(), 0);
+            try { boxes = regionMVBBs(s, whole, r_obj, std::vector<float>(part.size() * 3, 0.f), std::vector<float>(part.size(), -1.f)); }
+            catch (...) { ismhip_cloud_destroy(s.ctx, whole); throw; }
+            ismhip_cloud_destroy(s.ctx, whole);
+        }
         std::vector<std::unique_ptr<PointCloud>> filtered_store;
         const std::vector<const PointCloud*> filtered = preFilterClouds(part, filtered_store);
         std::vector<const PointCloud*> live; std::vector<int> live_of(part.size(), -1);
@@ -2332,12 +2390,15 @@ void ImplicitShapeModel::train() {                // :252-500
         }
         for (size_t o = 0; o < part.size(); ++o) {
             std::array<float, 3> center, bsize;
-            cloudAABB(*part[o], center, bsize);
+            if (mvbb) { center = boxes[o].position; bsize = boxes[o].size; }
+            else { cloudAABB(*part[o], center, bsize); boxes[o].position = center; boxes[o].size = bsize; }
+            m_last_boxes.push_back(boxes[o]);
             box_sizes[obj_class[b + o]].push_back(bsize); object_radii[obj_class[b + o]].push_back(cloudRadius(*part[o]));
             if (live_of[o] < 0) continue;
             const uint32_t cnt = f->off[live_of[o] + 1] - f->off[live_of[o]];
             fclass.insert(fclass.end(), cnt, obj_class[b + o]); finst.insert(finst.end(), cnt, obj_inst[b + o]);
             fmodel.insert(fmodel.end(), cnt, (unsigned)(b + o)); fcenter.insert(fcenter.end(), cnt, center); fbox.insert(fbox.end(), cnt, bsize);
+            if (mvbb) fquat.insert(fquat.end(), cnt, boxes[o].rotQuat);
         }
     }
     all->dim = D; all->n = (uint32_t)fclass.size();
@@ -2359,6 +2420,7 @@ void ImplicitShapeModel::train() {                // :252-500
         };
         filter(hdesc, (size_t)D); filter(hlrf, 9); filter(hkx, 1); filter(hky, 1); filter(hkz, 1);
         filter(fclass, 1); filter(finst, 1); filter(fmodel, 1); filter(fcenter, 1); filter(fbox, 1);
+        if (mvbb) filter(fquat, 1);
         all->n = (uint32_t)fclass.size();
     }
     DeviceSession::h2d(all->desc, hdesc); DeviceSession::h2d(all->lrf, hlrf); DeviceSession::h2d(all->kx, hkx); DeviceSession::h2d(all->ky, hky); DeviceSession::h2d(all->kz, hkz);
@@ -2368,7 +2430,7 @@ void ImplicitShapeModel::train() {                // :252-500
     LOG_INFO("clustering");                                      // :445-449
     if (!m_clustering) m_clustering.reset(new ClusteringNone());
     (*m_clustering)(s, *all, met);
-    m_codebook->activate(s, *all, fclass, finst, fmodel, fcenter, fbox, met, m_n_classes, *m_clustering);
+    m_codebook->activate(s, *all, fclass, finst, fmodel, fcenter, fbox, met, m_n_classes, *m_clustering, mvbb ? &fquat : nullptr);
     m_last_train = all; m_last_fclass = fclass; m_last_fmodel = fmodel;
     m_last_fcenter.clear();
     for (const auto& c : fcenter) m_last_fcenter.insert(m_last_fcenter.end(), c.begin(), c.end());
@@ -2403,7 +2465,7 @@ std::vector<std::vector<VotingMaximum>> ImplicitShapeModel::detectBatch(const st
     m_last_detect = f;
     stage.lap("voting");
     LOG_INFO("finding maxima");
-    auto res = m_voting->findMaxima(s, metric(), &nonempty);
+    auto res = m_voting->findMaxima(s, metric());
     stage.lap("maxima");
     complete.lap("complete");
     m_processing_times["normals"] += 0; m_processing_times["flann"] += 0;

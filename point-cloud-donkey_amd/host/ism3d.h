@@ -694,7 +694,8 @@ public:
     // training: Codebook::activate (codebook.cpp:64-368); the codewords are the clustering's centres (one per feature for "None")
     void activate(DeviceSession& s, const DeviceFeatures& f, const std::vector<unsigned>& feat_class, const std::vector<unsigned>& feat_instance,
                   const std::vector<unsigned>& feat_model, const std::vector<std::array<float, 3>>& feat_center,
-                  const std::vector<std::array<float, 3>>& feat_bbox_size, int metric, int n_classes, const Clustering& clustering);
+                  const std::vector<std::array<float, 3>>& feat_bbox_size, int metric, int n_classes, const Clustering& clustering,
+                  const std::vector<std::array<float, 4>>* feat_bbox_quat = nullptr);   // nullptr: axis-aligned boxes, (1, 0, 0, 0)
     // detection: Codebook::castVotes (codebook.cpp:403-555): activate every feature, emit the votes into the voting space
     void castVotes(DeviceSession& s, const DeviceFeatures& f, int metric, Voting& voting) const;
     bool isEmpty() const { return m_data.numWords() == 0; }
@@ -729,9 +730,9 @@ class Voting : public JSONObject {
 public:
     Voting();
     virtual ~Voting() {}
-    // Voting::findMaxima for every object of the batch (voting.cpp:79-328). metric and clouds (the batch's objects on the host, for the
-    // box of a hypothesis-only maximum) are read with UseGlobalFeatures only.
-    std::vector<std::vector<VotingMaximum>> findMaxima(DeviceSession& s, int metric = ISMHIP_METRIC_L2SQ, const std::vector<const PointCloud*>* clouds = nullptr);
+    // Voting::findMaxima for every object of the batch (voting.cpp:79-328). metric is read with UseGlobalFeatures only (the box of a
+    // hypothesis-only maximum comes from the session's search surface).
+    std::vector<std::vector<VotingMaximum>> findMaxima(DeviceSession& s, int metric = ISMHIP_METRIC_L2SQ);
     // ---- global verification (voting.cpp:217-298; classifier/global_classifier.cpp) ----
     bool useGlobalFeatures() const { return m_use_global_features; }
     const std::string& globalStrategy() const { return m_global_feature_method; }
@@ -749,7 +750,8 @@ public:
     // diagnostics (tests): what the global step of the last findMaxima saw and decided
     struct GlobalDump { int k = 0, dim = 0; std::vector<int32_t> region_obj, region_max; std::vector<uint32_t> n_sel; std::vector<float> centroid, radius, desc;
                         std::vector<int32_t> knn_idx; std::vector<float> knn_dist, hyp_w; std::vector<uint32_t> hyp_id;      // hyp_w / hyp_id: 2 per region
-                        std::vector<uint32_t> max_off; std::vector<int32_t> max_cls, max_inst; std::vector<float> max_w, max_iw, max_pos; };
+                        std::vector<uint32_t> max_off; std::vector<int32_t> max_cls, max_inst; std::vector<float> max_w, max_iw, max_pos;
+                        std::vector<float> box; };   // 10 per region: position, size, rotQuat of the box made for an object without maxima, NaN where none was
     const GlobalDump& lastGlobal() const { return m_last_global; }
     void clear();
     bool isSingleObjectMode() const { return m_single_object_mode; }
@@ -768,7 +770,7 @@ protected:
     friend class Codebook;
     virtual void iFindMaxima(DeviceSession& s, std::vector<std::vector<VotingMaximum>>& out) = 0;
     virtual float mergeRadius() const = 0;                       // MaximaHandler::getRadius(): Bandwidth (mean shift), BinSize[0] / 2 (Hough)
-    void verifyWithGlobalFeatures(DeviceSession& s, int metric, const std::vector<const PointCloud*>* clouds, std::vector<std::vector<VotingMaximum>>& out);
+    void verifyWithGlobalFeatures(DeviceSession& s, int metric, std::vector<std::vector<VotingMaximum>>& out);
     // device outputs of ismhip_find_maxima / ismhip_hough3d_maxima -> VotingMaximum lists
     struct MaximaBuffers;                                        // defined in ism3d.cpp (device buffers)
     static bool collectMaxima(DeviceSession& s, MaximaBuffers& b, std::vector<std::vector<VotingMaximum>>& out, bool with_quat);
@@ -853,6 +855,7 @@ public:
                          std::vector<unsigned> cls, model; std::vector<float> center; };
     struct VoteDump { std::vector<uint32_t> slot_off; std::vector<float> pos, weight; std::vector<int32_t> cls, inst; };
     FeatureDump lastFeatures(int which) const;
+    const std::vector<BoundingBox>& lastTrainingBoxes() const { return m_last_boxes; }
     VoteDump lastVotes() const;
     // diagnostics (tests): a timer or counter of the device library's context (ismhip_timer_get); 0 before the first device call
     double deviceTimer(const std::string& name) const;
@@ -923,6 +926,7 @@ private:
     std::unique_ptr<DeviceSession> m_session;
     std::shared_ptr<DeviceFeatures> m_last_train, m_last_detect;            // for lastFeatures()
     std::vector<unsigned> m_last_fclass, m_last_fmodel; std::vector<float> m_last_fcenter;
+    std::vector<BoundingBox> m_last_boxes;                                  // the last train()'s box per training object, in training order
 };
 
 // list files of eval_tool (eval_tool/eval_helpers.h:100-177)
