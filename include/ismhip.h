@@ -571,6 +571,53 @@ int  ismhip_global_vfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions
 int  ismhip_global_gasd(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
                         const float* region_radius, const float view_direction[3], int with_color, uint32_t* n_sel_out, float* centroid_out,
                         float* radius_out, float* frame9_out, float* max_coord_out, float* desc_out, uint32_t* count_out);
+/* ismhip_global_cvfh: FeaturesCVFH::iComputeDescriptors (features/features_cvfh.cpp) -> pcl::CVFHEstimation, the clustered viewpoint
+ * feature histogram: the one region descriptor with MORE THAN ONE ROW per region, one per smooth cluster. PCL is external: this is the
+ * library's own statement of PCL 1.10 cvfh.hpp / vfh.hpp (DESIGN.md section 4.25 names the deviations); parity with PCL is not pinned.
+ * Region, n_sel, centroid and radius are those of the entries above, bit for bit on the same regions. "Selected" below: a finite point of
+ * the region. features_cvfh.cpp has no parameters (angle 10 degrees, curvature threshold 1.0, which keeps every point; PCL's defaults
+ * otherwise: tolerance and normal radius 0.015, 50 points, viewpoint (0, 0, 0)); here they are arguments.
+ *   a. clustering normals. normal_radius > 0 and n_sel >= min_points: for every selected point q the PCA normal over the SELECTED points p
+ *      with d2(p, q) < (float)((double)normal_radius * normal_radius), q included: v = (double)p - (double)q per component; the three
+ *      components and six products, each rounded to the integer grids of csrc/moments.h (2^e2 the power of two above the squared radius,
+ *      2^e1 its root; 48 bits, fewer for objects beyond 2^14 points) and added as integers: ORDER FREE. Covariance E[vv^T] - E[v]E[v]^T with
+ *      inv = 1.0 / count, the Jacobi solver of ismhip_estimate_normals_pca; the smallest eigenvalue's vector cast to float and negated when
+ *      ((vp - q) . n) < 0 in float (method 0 of ismhip_estimate_normals_pca, with the caller's viewpoint). Fewer than three such points: NaN.
+ *      Otherwise (normal_radius <= 0, or n_sel < min_points) the clustering normals are the cloud's own.
+ *   b. links. Two selected points i != j link iff d2(i, j) < (float)((double)cluster_tolerance * cluster_tolerance), both clustering normals
+ *      are finite, and c > cos(angle_threshold), c = ((double)n1.x*n2.x + (double)n1.y*n2.y) + (double)n1.z*n2.z clamped to [-1, 1]
+ *      (float components converted to double; cos() once on the host in double). Comparing cosines is acos(c) < angle_threshold without the
+ *      acos; the clamp keeps two equal normals whose product rounds past 1 linked (PCL's unclamped acos gives NaN there). Clusters are the
+ *      CONNECTED COMPONENTS of that symmetric relation (PCL's region growing yields the same sets: the predicate is pairwise). A component
+ *      of at least min_points points is kept; kept clusters are ordered by their smallest ORIGINAL point index (PCL's seed order).
+ *      label_out (device uint32 [n_regions * S], S = the cloud's largest object, or NULL): per region and original point index the smallest
+ *      original index of the point's component (a selected point with a NaN normal is a component of its own); 0xffffffff for a point that
+ *      is not selected, not finite or past the object's end.
+ *   c. per kept cluster: centroid = the mean of its points, normal = the mean of its clustering normals, normalised: coordinates and
+ *      components rounded to integer grids (coordinates: 2^e above twice the largest |region centroid| component plus the region radius;
+ *      normal components: below 4, a longer normal is left out) and added as integers, order free; mean = (double)sum * q / count, cast to
+ *      float; the normal divided by its double length first. No cluster kept and n_sel > 0: ONE row (the fallback) from the mean of ALL
+ *      selected points and the mean of their FINITE clustering normals (non-finite ones are left out of sum and count), root 0xffffffff,
+ *      size n_sel.
+ *   d. one row of 308 per kept cluster: ismhip_global_vfh's deposits over ALL selected points of the region with a finite CLOUD normal,
+ *      evaluated against the row's centroid and normal, view direction (viewpoint - row centroid) normalised in float, with the distance
+ *      block b4 = floor((45.0 * (double)f4) / (double)dmax) clamped to [0, 44], dmax the largest float f4 = |p - row centroid| over those
+ *      points (dmax = 0: no deposit). count_out: the integer counts. desc = (float)count / 47278.0f, one division per bin (the reference's
+ *      normalizeDescriptors, features/features.cpp:282-297, divides the raw counts by the sum of the bin INDICES).
+ *      Fewer than two points with a finite cloud normal, or a row centroid or row normal that is not finite: a NaN row with zero counts
+ *      (k_vfh's rule; the host drops a NaN row).
+ * Outputs per region: n_sel_out, centroid_out, radius_out as above; n_clusters_out[n_regions] the TRUE number of rows, never clipped by
+ * max_rows (0 iff n_sel = 0); rows k < min(n_clusters, max_rows) at slot region * max_rows + k: row_centroid_out[.*3], row_normal_out[.*3],
+ * row_size_out[.] (points of the cluster), desc_out[.*308], count_out[.*308] (or NULL). The other slots: NaN, size 0, zero counts. A caller
+ * that finds n_clusters > max_rows asks again with a larger capacity. viewpoint: HOST float[3], finite. cluster_tolerance > 0,
+ * min_points >= 1, max_rows >= 1, 0 < angle_threshold < pi (the reference: 10.0 / 180.0 * M_PI), else ISMHIP_ERR_INVALID. Integer atomics
+ * only: every output is the same bits on every call and for every grid cell size of the cloud. Asynchronous. Timers "global_cvfh" and,
+ * inside it, "cvfh_normals", "cvfh_label", "cvfh_stats", "cvfh_rows". */
+int  ismhip_global_cvfh(ismhip_ctx* ctx, const ismhip_cloud* cloud, int n_regions, const int32_t* region_obj, const float* region_center,
+                        const float* region_radius, const float viewpoint[3], float cluster_tolerance, float normal_radius, int min_points,
+                        double angle_threshold, int max_rows, uint32_t* n_sel_out, float* centroid_out, float* radius_out,
+                        uint32_t* n_clusters_out, float* row_centroid_out, float* row_normal_out, uint32_t* row_size_out, float* desc_out,
+                        uint32_t* count_out, uint32_t* label_out);
 /* Diagnostic: the hue bin of ismhip_global_gasd's colour block alone, one thread per colour. rgba: device [n] packed 0x00RRGGBB, bits
  * 24..31 ignored. out: device uint8 [n], the bin 0..11, or 255 where the rule deposits nothing. Asynchronous. Off every hot path. */
 int  ismhip_gasd_hue_bins(ismhip_ctx* ctx, int n, const uint32_t* rgba, uint8_t* out);

@@ -38,7 +38,7 @@ EXPORTS = [
     "ismhip_principal_curvatures", "ismhip_culling_scores", "ismhip_culling_select", "ismhip_intensity_gradients", "ismhip_rift",
     "ismhip_keypoint_normals_pca", "ismhip_cgf_raw", "ismhip_mlp_create", "ismhip_mlp_destroy", "ismhip_mlp_in", "ismhip_mlp_out", "ismhip_mlp_forward",
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
-    "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins", "ismhip_region_mvbb",
+    "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins", "ismhip_region_mvbb", "ismhip_global_cvfh",
     "ismhip_normal_curvature", "ismhip_voxel_downsample_xyzi", "ismhip_sift3d_scale_space", "ismhip_sift3d_extrema", "ismhip_sift3d_keypoints",
 ]
 SIFT3D_MIN_POINTS = 25             # ISMHIP_SIFT3D_MIN_POINTS: an octave below it ends the object; also the extrema's number of neighbours
@@ -767,6 +767,36 @@ def global_gasd(ctx, cloud, dev, region_obj, region_center=None, region_radius=N
     ctx.check(lib().ismhip_global_gasd(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vd, C.c_int(1 if with_color else 0),
                                        _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["frame"]), _p(out["max_coord"]),
                                        _p(out["desc"]), _p(out.get("counts"))), "ismhip_global_gasd")
+    return out
+
+
+def global_cvfh(ctx, cloud, dev, region_obj, region_center=None, region_radius=None, viewpoint=(0.0, 0.0, 0.0), cluster_tolerance=0.015,
+                normal_radius=0.015, min_points=50, angle_threshold=10.0 / 180.0 * np.pi, max_rows=4, want_counts=False, label_stride=0):
+    """ismhip_global_cvfh on regions as global_short_shot -> dict of device tensors n_sel [n], centroid [n, 3], radius [n], n_clusters [n]
+    (never clipped by max_rows), row_centroid / row_normal [n, max_rows, 3], row_size [n, max_rows], desc [n, max_rows, 308] and, with
+    want_counts, counts [n, max_rows, 308] (int32); label_stride = the cloud's largest object asks for labels [n, label_stride] (int64 view
+    of the uint32 labels, 0xffffffff for an unselected point)"""
+    torch = _torch()
+    n, obj, cen, rad = _regions(cloud, region_obj, region_center, region_radius, dev)
+    m = int(max_rows)
+    out = _global_outputs(n, 1, dev)
+    del out["lrf"]
+    out["desc"] = torch.empty((n, max(m, 0), 308), dtype=torch.float32, device=dev)
+    out["n_clusters"] = torch.empty((n,), dtype=torch.int32, device=dev)
+    out["row_centroid"] = torch.empty((n, max(m, 0), 3), dtype=torch.float32, device=dev)
+    out["row_normal"] = torch.empty((n, max(m, 0), 3), dtype=torch.float32, device=dev)
+    out["row_size"] = torch.empty((n, max(m, 0)), dtype=torch.int32, device=dev)
+    if want_counts:
+        out["counts"] = torch.empty_like(out["desc"], dtype=torch.int32)
+    labels = torch.empty((n, int(label_stride)), dtype=torch.int32, device=dev) if label_stride else None
+    vp = (C.c_float * 3)(*[float(v) for v in viewpoint])
+    ctx.check(lib().ismhip_global_cvfh(ctx._h, cloud._h, C.c_int(n), _p(obj), _p(cen), _p(rad), vp, C.c_float(cluster_tolerance),
+                                       C.c_float(normal_radius), C.c_int(int(min_points)), C.c_double(angle_threshold), C.c_int(m),
+                                       _p(out["n_sel"]), _p(out["centroid"]), _p(out["radius"]), _p(out["n_clusters"]), _p(out["row_centroid"]),
+                                       _p(out["row_normal"]), _p(out["row_size"]), _p(out["desc"]), _p(out.get("counts")), _p(labels)),
+              "ismhip_global_cvfh")
+    if labels is not None:
+        out["labels"] = labels.to(torch.int64) & 0xffffffff
     return out
 
 

@@ -197,7 +197,7 @@ struct ismhip_ctx {
 enum ScratchSlot {
     SCR_KP_OFF = 1, SCR_TIE_LIST, SCR_TIE_REC, SCR_TIE_KEYS, SCR_COUNTERS, SCR_KNN_CAND_IDX, SCR_KNN_CAND_VAL,
     SCR_QNORM, SCR_FPFH_FLAG, SCR_FPFH_LIST, SCR_FPFH_SPFH, SCR_FPFH_LOOKUP, SCR_SLOT_OFF, SCR_CLASS_BW,
-    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE, SCR_ISS3D, SCR_CULL_SCALE, SCR_CULL_SELECT, SCR_RIFT, SCR_RIFT_SCALE, SCR_ESF_LIST, SCR_SIFT3D, SCR_SIFT3D_SCALE, SCR_SIFT3D_DRIVER, SCR_MVBB,
+    SCR_COMPACT_KEEP, SCR_COMPACT_POS, SCR_OBJ_COUNT, SCR_QPAD, SCR_LRF_COV, SCR_KNN_FLAGS, SCR_KNN_QSPLIT, SCR_MAX_REC, SCR_QNORM2, SCR_KNN_Q2, SCR_KNN_LIST2, SCR_TRAIN, SCR_TRAIN2, SCR_MAX_WORK, SCR_KMEANS, SCR_KNN_CLOCK, SCR_PCA, SCR_KNN_THR0, SCR_KNN_QSQRT, SCR_KNN_HELL_EMIT, SCR_KNN_THR, SCR_KNN_THR2, SCR_TRAIN_ACT, SCR_KNN_LK, SCR_KNN_LK2, SCR_KNN_LK3, SCR_PREFILTER, SCR_RANSAC, SCR_COSPAIR, SCR_KNNB_FLAG, SCR_KNNB_Q, SCR_KNNB_CAND, SCR_RANK, SCR_RANK_KNN, SCR_KNN_LISTS, SCR_KNN_QUEUE, SCR_ISS3D, SCR_CULL_SCALE, SCR_CULL_SELECT, SCR_RIFT, SCR_RIFT_SCALE, SCR_ESF_LIST, SCR_SIFT3D, SCR_SIFT3D_SCALE, SCR_SIFT3D_DRIVER, SCR_MVBB, SCR_CVFH,
     SCR_SIFT3D_OCTAVE    // the last one: octave i of ismhip_sift3d_keypoints takes slot SCR_SIFT3D_OCTAVE + i
 };
 

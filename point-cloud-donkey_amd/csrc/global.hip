@@ -23,10 +23,12 @@
 // One region per workgroup: a region of a very large object is not split over several workgroups.
 // k_vfh (further down) is the frame-free third descriptor on the same regions: ismhip_global_vfh.
 // k_gasd (after it) is the fourth, in the region's own covariance frame and with colour: ismhip_global_gasd.
+// The clustered fifth, ismhip_global_cvfh, is cvfh.hip; it shares vfh_deposit.h with k_vfh.
 #include "shot_deposit.h"
 #include "lrf_common.h"
 #include "eigen3.h"
 #include "pair_features.h"
+#include "vfh_deposit.h"
 
 namespace {
 
@@ -315,10 +317,6 @@ __global__ __launch_bounds__(256) void k_global(GlobalArgs a) {
 // normal sums (32 B per point: position and normal), histogram (32 B per point). Byte model per whole-object region: 64 B x n.
 // A 45-bin block -- and a viewpoint block that a planar patch drives into ONE bin -- is the same-address case of the short histogram
 // above: each wave owns VFH_COPIES copies of the 308 bins, lane l counts in copy l % VFH_COPIES; integers, so the merge is exact.
-#define VFH_COPIES 8
-#define VFH_SHAPE_BINS 45
-#define VFH_VP_BINS 128
-
 struct VfhArgs {
     const uint32_t* pt_off; const GridMeta* meta;
     const float4 *sp4, *sn4;
@@ -335,33 +333,7 @@ struct VfhSmem {
     uint32_t cnt[4 * VFH_COPIES * ISMHIP_VFH_DIM];
 };
 
-// floor(v) clamped to [0, last] as a bin index; -1 for a NaN (no deposit). The clamp is taken in double: no int conversion of a
-// value outside int.
-__device__ __forceinline__ int vfh_bin(double v, int last) {
-    if (!(v == v)) return -1;
-    v = floor(v);
-    return v < 0.0 ? 0 : (v > (double)last ? last : (int)v);
-}
-
-// One sweep of a region's span, position and (with NORMALS) normal of each record, in the order i = tid, tid + 256, ... per thread (the
-// order of the double sums). The loop of k_global issues one load and waits for it, ~64 dependent round trips per sweep of a
-// 16 384-point object with one wave per SIMD; here four records' loads (eight with normals) are issued before the first is used.
-// Without NORMALS sn is not read and f gets a zero normal. k_vfh and k_gasd sweep with it.
-template <bool NORMALS, class F>
-__device__ __forceinline__ void span_sweep(const float4* __restrict__ sp, const float4* __restrict__ sn, uint32_t n, int tid, F&& f) {
-    for (uint32_t i0 = tid; i0 < n; i0 += 4 * 256) {
-        float4 p[4], nr[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t i = (uint64_t)i0 + 256u * j;                          // past the end: a record that is there, not used
-            p[j] = sp[i < n ? i : i0];
-            if constexpr (NORMALS) nr[j] = sn[i < n ? i : i0]; else nr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if ((uint64_t)i0 + 256u * j < n) f(p[j], nr[j]);
-    }
-}
-
+// vfh_bin, span_sweep and the per-point deposit vfh_deposit: vfh_deposit.h (shared with cvfh.hip)
 __global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
     __shared__ VfhSmem sm;
     constexpr int D = ISMHIP_VFH_DIM;
@@ -435,35 +407,18 @@ __global__ __launch_bounds__(256) void k_vfh(VfhArgs a) {
     if (mfin < 2u) { nan_row(); return; }                     // workgroup-uniform
 
     // ---- the view direction: (viewpoint - centroid) / |.| in float; a zero norm leaves 0 ----------------------------------------------
-    float vdx = a.vpx - cx, vdy = a.vpy - cy, vdz = a.vpz - cz;
-    const float vn = sqrtf((vdx * vdx + vdy * vdy) + vdz * vdz);
-    if (vn != 0.0f) { vdx /= vn; vdy /= vn; vdz /= vn; }
+    float vdx, vdy, vdz;
+    vfh_view_direction(a.vpx, a.vpy, a.vpz, cx, cy, cz, vdx, vdy, vdz);
 
     // ---- 3. the histogram ----------------------------------------------------------------------------------------------------------------
     for (int i = tid; i < 4 * VFH_COPIES * D; i += 256) sm.cnt[i] = 0u;
     __syncthreads();
     uint32_t* hist = sm.cnt + (wv * VFH_COPIES + (lane % VFH_COPIES)) * D;
-    const double dpi = (double)(1.0f / (2.0f * (float)M_PI));
     span_sweep<true>(sp, sn, n, tid, [&](const float4& p, const float4& nr) {
         if (!selected(p)) return;
-        if (!(isfinite(nr.x) && isfinite(nr.y) && isfinite(nr.z))) return;
-        // viewpoint block: every such point, whatever becomes of its pair
-        const float dv = (nr.x * vdx + nr.y * vdy) + nr.z * vdz;
-        const int bv = vfh_bin((((double)dv + 1.0) * 0.5) * (double)VFH_VP_BINS, VFH_VP_BINS - 1);
-        if (bv >= 0) atomicAdd(&hist[4 * VFH_SHAPE_BINS + bv], 1u);
-        // shape blocks: computePairFeatures(centroid, normal centroid, p, n); f4 is its own first expression
-        float f1, f2, f3;
-        if (!pair_features(cx, cy, cz, ncx, ncy, ncz, p.x, p.y, p.z, nr.x, nr.y, nr.z, f1, f2, f3)) return;
-        const float dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
-        const float f4 = sqrtf((dx * dx + dy * dy) + dz * dz);
-        const int b1 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f1 + M_PI) * dpi), VFH_SHAPE_BINS - 1);
-        const int b2 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f2 + 1.0) * 0.5), VFH_SHAPE_BINS - 1);
-        const int b3 = vfh_bin((double)VFH_SHAPE_BINS * (((double)f3 + 1.0) * 0.5), VFH_SHAPE_BINS - 1);
-        const int b4 = vfh_bin((double)(f4 * 100.0f) + 0.5, VFH_SHAPE_BINS - 1);
-        if (b1 >= 0) atomicAdd(&hist[b1], 1u);
-        if (b2 >= 0) atomicAdd(&hist[VFH_SHAPE_BINS + b2], 1u);
-        if (b3 >= 0) atomicAdd(&hist[2 * VFH_SHAPE_BINS + b3], 1u);
-        if (b4 >= 0) atomicAdd(&hist[3 * VFH_SHAPE_BINS + b4], 1u);
+        // b4: hundredths of a unit, not normalised
+        vfh_deposit(hist, cx, cy, cz, ncx, ncy, ncz, vdx, vdy, vdz, p, nr,
+                    [](float f4) { return vfh_bin((double)(f4 * 100.0f) + 0.5, VFH_SHAPE_BINS - 1); });
     });
     __syncthreads();
     // counts -> row: one product per bin (order-free); the distance block stays zero unless the size component is asked for

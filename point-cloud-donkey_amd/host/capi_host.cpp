@@ -242,6 +242,30 @@ int ism3d_global_features_set(void* m, int n, int dim, const uint32_t* cls, cons
         ((ImplicitShapeModel*)m)->getVoting()->forwardGlobalFeatures(g);
         return 0;)
 }
+// as ism3d_global_features_set with several rows per training cloud (CVFH): cloud[n] names each row's cloud; rows of one cloud are
+// consecutive and share its class
+int ism3d_global_features_set_clouds(void* m, int n, int dim, const uint32_t* cls, const uint32_t* cloud, const uint32_t* inst, const float* rf9, const float* desc,
+                                     const float* radius) {
+    GUARD(
+        Voting::GlobalFeatureMap g;
+        for (int i = 0; i < n; ++i) {
+            StoredGlobalFeature f; f.classId = cls[i]; f.instanceId = inst[i]; f.radius = radius[i];
+            std::memcpy(f.rf, rf9 + (size_t)i * 9, 36);
+            f.descriptor.assign(desc + (size_t)i * dim, desc + (size_t)(i + 1) * dim);
+            if (i == 0 || cloud[i] != cloud[i - 1]) g[cls[i]].emplace_back();
+            g[cls[i]].back().push_back(f);
+        }
+        ((ImplicitShapeModel*)m)->getVoting()->forwardGlobalFeatures(g);
+        return 0;)
+}
+// diagnostics (tests): the rows of the last global step: row_off [regions + 1] (may be NULL). ism3d_last_global's desc, knn_idx and
+// knn_dist are per ROW: one row per region but for CVFH. Returns the number of rows.
+int ism3d_last_global_rows(void* m, uint32_t* row_off) {
+    GUARD(
+        const auto& d = ((ImplicitShapeModel*)m)->getVoting()->lastGlobal();
+        if (row_off && !d.row_off.empty()) std::memcpy(row_off, d.row_off.data(), d.row_off.size() * 4);
+        return d.row_off.empty() ? 0 : (int)d.row_off.back();)
+}
 // diagnostics (tests): the global step of the last detectBatch(). Regions: object, index of the maximum among the object's maxima BEFORE
 // the merge (-1: the whole object), selected points, centroid [3], radius, descriptor row [dim], the k neighbours (row of the stored
 // features, functor distance) and the hypothesis (ids: class, instance; weights: class, instance). Maxima before the merge: max_off

@@ -1165,9 +1165,13 @@ struct GlobalRegions {
     int n = 0, dim = 0;
     DevBuf obj, cen, rad;                          // the regions
     DevBuf n_sel, centroid, radius, lrf, desc;     // the outputs
+    // rows of region r: row_off[r] .. row_off[r + 1] of desc and lrf. One each, set here; only CVFH's describe() rewrites it
+    std::vector<uint32_t> row_off;
+    size_t rows() const { return row_off.empty() ? 0 : row_off.back(); }
     // uploads the regions and reserves the outputs for rows of `dim` floats
     void set(const std::vector<int32_t>& o, const std::vector<float>& c, const std::vector<float>& r, int D) {
         n = (int)o.size(); dim = D;
+        row_off.resize((size_t)n + 1); std::iota(row_off.begin(), row_off.end(), 0u);
         DeviceSession::h2d(obj, o); DeviceSession::h2d(cen, c); DeviceSession::h2d(rad, r);
         const size_t m = std::max<size_t>((size_t)n, 1);
         n_sel.reserve(m * 4); centroid.reserve(m * 12); radius.reserve(m * 4); lrf.reserve(m * 36); desc.reserve(m * (size_t)D * 4);
@@ -1234,6 +1238,44 @@ void GlobalFeaturesGASD::describe(DeviceSession& s, GlobalRegions& r) const {
     DeviceSession::h2d(r.lrf, std::vector<float>((size_t)r.n * 9, 0.f));
     s.sync();                                                                         // frame and max_coord are released on return
 }
+GlobalFeaturesCVFH::GlobalFeaturesCVFH() {                    // PCL's defaults for a leaf size of 0.005 (cvfh.h); the reference sets none of them
+    addParameter(m_cluster_tolerance, "CvfhClusterTolerance", 0.015);
+    addParameter(m_normal_radius, "CvfhNormalRadius", 0.015);
+    addParameter(m_min_points, "CvfhMinPoints", 50);
+}
+void GlobalFeaturesCVFH::describe(DeviceSession& s, GlobalRegions& r) const {
+    if (!(m_cluster_tolerance > 0) || m_min_points < 1) throw RuntimeException("CVFH: CvfhClusterTolerance must be positive and CvfhMinPoints at least 1");
+    const float viewpoint[3] = {0.f, 0.f, 0.f};                                       // PCL's default, which features_cvfh.cpp leaves
+    const double angle = 10.0 / 180.0 * M_PI;                                         // features_cvfh.cpp
+    const size_t n = (size_t)r.n, m = std::max<size_t>(n, 1);
+    DevBuf ncl, rcen, rnrm, rsize, rows;
+    std::vector<uint32_t> counts;
+    int cap = 4;                                                                      // rows per region the buffers hold; a region with more: once more
+    for (;;) {
+        ncl.reserve(m * 4); rcen.reserve(m * cap * 12); rnrm.reserve(m * cap * 12); rsize.reserve(m * cap * 4);
+        rows.reserve(m * cap * (size_t)ISMHIP_VFH_DIM * 4);
+        s.check(ismhip_global_cvfh(s.ctx, s.cloud, r.n, r.obj.as<int32_t>(), r.cen.as<float>(), r.rad.as<float>(), viewpoint, (float)m_cluster_tolerance,
+                                   (float)m_normal_radius, m_min_points, angle, cap, r.n_sel.as<uint32_t>(), r.centroid.as<float>(), r.radius.as<float>(),
+                                   ncl.as<uint32_t>(), rcen.as<float>(), rnrm.as<float>(), rsize.as<uint32_t>(), rows.as<float>(), nullptr, nullptr),
+                "ismhip_global_cvfh");
+        s.d2h(counts, ncl, n);
+        uint32_t most = 0;
+        for (uint32_t c : counts) most = std::max(most, c);
+        if (most <= (uint32_t)cap) break;
+        cap = (int)most;
+    }
+    std::vector<float> all, packed;
+    s.d2h(all, rows, n * cap * (size_t)ISMHIP_VFH_DIM);
+    r.row_off.assign(1, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        packed.insert(packed.end(), all.begin() + i * cap * ISMHIP_VFH_DIM, all.begin() + (i * cap + counts[i]) * ISMHIP_VFH_DIM);
+        r.row_off.push_back(r.row_off.back() + counts[i]);
+    }
+    if (packed.empty()) packed.assign(1, 0.f);
+    DeviceSession::h2d(r.desc, packed);
+    DeviceSession::h2d(r.lrf, std::vector<float>(std::max<size_t>(r.rows(), 1) * 9, 0.f));   // no frame: the stored rf of a row is zeros, as for VFH
+    s.sync();
+}
 GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     if (!object.isObject()) return nullptr;
     const Json* t = object.find("Type");
@@ -1243,6 +1285,7 @@ GlobalFeatures* GlobalFeatures::createIfBuilt(const Json& object) {
     else if (t->str == GlobalFeaturesShot::getTypeStatic()) g = new GlobalFeaturesShot();
     else if (t->str == GlobalFeaturesVFH::getTypeStatic()) g = new GlobalFeaturesVFH();
     else if (t->str == GlobalFeaturesGASD::getTypeStatic()) g = new GlobalFeaturesGASD();
+    else if (t->str == GlobalFeaturesCVFH::getTypeStatic()) g = new GlobalFeaturesCVFH();
     if (!g) return nullptr;
     try { if (!g->configFromJson(object)) throw RuntimeException("could not create object of type: \"" + t->str + "\""); }
     catch (...) { delete g; throw; }
@@ -1581,32 +1624,45 @@ void Voting::verifyWithGlobalFeatures(DeviceSession& s, int metric, std::vector<
         GlobalRegions G; G.set(r_obj, r_cen, r_rad, D);
         m_global_descriptor->describe(s, G);
         std::vector<float> desc;
-        s.d2h(dump.n_sel, G.n_sel, (size_t)R); s.d2h(dump.centroid, G.centroid, (size_t)R * 3); s.d2h(dump.radius, G.radius, (size_t)R); s.d2h(desc, G.desc, (size_t)R * D);
+        const size_t T = G.rows();                                                   // query rows: one per region, but for CVFH (G.row_off)
+        dump.row_off = G.row_off;
+        s.d2h(dump.n_sel, G.n_sel, (size_t)R); s.d2h(dump.centroid, G.centroid, (size_t)R * 3); s.d2h(dump.radius, G.radius, (size_t)R);
+        if (T > 0) s.d2h(desc, G.desc, T * D);
         dump.desc = desc;
-        // which regions are classified: enough points (classify(), global_classifier.cpp:181; single-object mode passes -1) and a row.
-        // The others get the zero-weight hypothesis of :229-239; their query row is zeroed so that the search sees no NaN.
-        std::vector<uint8_t> live((size_t)R, 0);
+        // which rows are searched: their region has enough points (classify(), global_classifier.cpp:181; single-object mode passes -1)
+        // and the row is not NaN. A region without such a row gets the zero-weight hypothesis of :229-239; a row that is not searched is
+        // zeroed so that the search sees no NaN.
+        std::vector<uint8_t> live(T, 0);
         for (int r = 0; r < R; ++r) {
             const bool enough = m_single_object_mode || (int)dump.n_sel[r] > m_min_points || m_min_points < 0;
-            live[r] = enough && !std::isnan(desc[(size_t)r * D]);
-            if (!live[r]) std::fill(desc.begin() + (size_t)r * D, desc.begin() + (size_t)(r + 1) * D, 0.f);
+            for (size_t t = G.row_off[r]; t < G.row_off[r + 1]; ++t) {
+                live[t] = enough && !std::isnan(desc[t * D]);
+                if (!live[t]) std::fill(desc.begin() + t * D, desc.begin() + (t + 1) * D, 0.f);
+            }
         }
-        DevBuf q, idx, dist;
-        DeviceSession::h2d(q, desc);
-        idx.reserve((size_t)R * K * 4); dist.reserve((size_t)R * K * 4);
-        const TempCodebook cb = searchOnlyCodebook(s, (uint32_t)n_rows, D, rows.data());
-        if (K <= 16) s.check(ismhip_knn(s.ctx, cb.get(), metric, R, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn (global features)");
-        else s.check(ismhip_knn_large_k(s.ctx, cb.get(), metric, R, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn_large_k (global features)");
-        s.d2h(dump.knn_idx, idx, (size_t)R * K); s.d2h(dump.knn_dist, dist, (size_t)R * K);
+        if (T > 0) {                                                                 // ALL rows of all regions: one search
+            DevBuf q, idx, dist;
+            DeviceSession::h2d(q, desc);
+            idx.reserve(T * K * 4); dist.reserve(T * K * 4);
+            const TempCodebook cb = searchOnlyCodebook(s, (uint32_t)n_rows, D, rows.data());
+            if (K <= 16) s.check(ismhip_knn(s.ctx, cb.get(), metric, (int)T, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn (global features)");
+            else s.check(ismhip_knn_large_k(s.ctx, cb.get(), metric, (int)T, q.as<float>(), K, idx.as<int32_t>(), dist.as<float>()), "ismhip_knn_large_k (global features)");
+            s.d2h(dump.knn_idx, idx, T * K); s.d2h(dump.knn_dist, dist, T * K);
+        }
         for (int r = 0; r < R; ++r) {
             const VotingMaximum* m = r_max[r] >= 0 ? &out[r_obj[r]][r_max[r]] : nullptr;
             VotingMaximum::GlobalHypothesis g;
             g.classId = m ? m->classId : (unsigned)-1; g.instanceId = m ? m->instanceId : (unsigned)-1;      // the zero-weight hypothesis
-            if (live[r]) {
-                std::vector<unsigned> nc((size_t)K), ni((size_t)K);
-                for (int j = 0; j < K; ++j) { const int32_t w = dump.knn_idx[(size_t)r * K + j]; nc[j] = row_class[w]; ni[j] = row_inst[w]; }
-                g = classifyWithKNN(K, nc.data(), ni.data(), &dump.knn_dist[(size_t)r * K], g.classId, m_single_object_mode);
+            // the neighbours of the region's live rows, row after row (the loop of global_classifier.cpp:249-284 feeds one accumulator)
+            std::vector<unsigned> nc, ni; std::vector<float> nd;
+            for (size_t t = G.row_off[r]; t < G.row_off[r + 1]; ++t) {
+                if (!live[t]) continue;
+                for (int j = 0; j < K; ++j) {
+                    const int32_t w = dump.knn_idx[t * K + j];
+                    nc.push_back(row_class[w]); ni.push_back(row_inst[w]); nd.push_back(dump.knn_dist[t * K + j]);
+                }
             }
+            if (!nc.empty()) g = classifyWithKNN((int)nc.size(), nc.data(), ni.data(), nd.data(), g.classId, m_single_object_mode);
             hyp[r] = g;
             dump.hyp_id.push_back(g.classId); dump.hyp_id.push_back(g.instanceId); dump.hyp_w.push_back(g.classWeight); dump.hyp_w.push_back(g.instanceWeight);
         }
@@ -2371,22 +2427,27 @@ void ImplicitShapeModel::train() {                // :252-500
         append(hkx, f->kx, f->n); append(hky, f->ky, f->n); append(hkz, f->kz, f->n);
         // global features (:908-919, in training always): one whole-object region per cloud of the chunk, on the search surface the
         // local descriptors have just used
-        std::vector<uint32_t> g_nsel; std::vector<float> g_rad, g_lrf, g_desc;
+        std::vector<uint32_t> g_nsel, g_row_off; std::vector<float> g_rad, g_lrf, g_desc;
         const int GD = m_global_descriptor ? m_global_descriptor->getDescriptorLength() : 0;
         if (m_global_descriptor && !live.empty()) {
             std::vector<int32_t> r_obj(live.size()); std::iota(r_obj.begin(), r_obj.end(), 0);
             GlobalRegions G; G.set(r_obj, std::vector<float>(live.size() * 3, 0.f), std::vector<float>(live.size(), -1.f), GD);
             m_global_descriptor->describe(s, G);
-            s.d2h(g_nsel, G.n_sel, live.size()); s.d2h(g_rad, G.radius, live.size()); s.d2h(g_lrf, G.lrf, live.size() * 9); s.d2h(g_desc, G.desc, live.size() * GD);
+            g_row_off = G.row_off;
+            s.d2h(g_nsel, G.n_sel, live.size()); s.d2h(g_rad, G.radius, live.size());
+            if (G.rows() > 0) { s.d2h(g_lrf, G.lrf, G.rows() * 9); s.d2h(g_desc, G.desc, G.rows() * GD); }
         }
         for (size_t o = 0; m_global_descriptor && o < part.size(); ++o) {
             global_features[obj_class[b + o]].emplace_back();
             const int l = live_of[o];
-            if (l < 0 || std::isnan(g_desc[(size_t)l * GD])) continue;              // removeNaNFeatures: the rows are NaN as a whole
-            StoredGlobalFeature gf; gf.classId = obj_class[b + o]; gf.instanceId = obj_inst[b + o]; gf.radius = g_rad[l];
-            std::copy(g_lrf.begin() + (size_t)l * 9, g_lrf.begin() + (size_t)(l + 1) * 9, gf.rf);
-            gf.descriptor.assign(g_desc.begin() + (size_t)l * GD, g_desc.begin() + (size_t)(l + 1) * GD);
-            global_features[obj_class[b + o]].back().push_back(gf);
+            if (l < 0) continue;
+            for (size_t t = g_row_off[l]; t < g_row_off[l + 1]; ++t) {               // every row of the cloud (implicit_shape_model.cpp:402); one but for CVFH
+                if (std::isnan(g_desc[t * GD])) continue;                           // removeNaNFeatures: the rows are NaN as a whole
+                StoredGlobalFeature gf; gf.classId = obj_class[b + o]; gf.instanceId = obj_inst[b + o]; gf.radius = g_rad[l];
+                std::copy(g_lrf.begin() + t * 9, g_lrf.begin() + (t + 1) * 9, gf.rf);
+                gf.descriptor.assign(g_desc.begin() + t * GD, g_desc.begin() + (t + 1) * GD);
+                global_features[obj_class[b + o]].back().push_back(gf);
+            }
         }
         for (size_t o = 0; o < part.size(); ++o) {
             std::array<float, 3> center, bsize;

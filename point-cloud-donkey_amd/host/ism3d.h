@@ -174,7 +174,7 @@ public:
     virtual void describe(DeviceSession& s, GlobalRegions& r) const = 0;     // fills r's outputs for r's regions on s.cloud
     virtual bool needsColor() const { return false; }                        // the batch is uploaded with its colours
     virtual void checkInput(const PointCloud&) const {}                      // refuses a cloud the descriptor cannot describe, on the host
-    static const char* builtTypes() { return "SHORT_SHOT_GLOBAL, SHOT_GLOBAL, VFH, GASD"; }
+    static const char* builtTypes() { return "SHORT_SHOT_GLOBAL, SHOT_GLOBAL, VFH, GASD, CVFH"; }
     static GlobalFeatures* createIfBuilt(const Json& object);                // nullptr for a type that is not built (or no object)
 };
 class GlobalFeaturesShortShot : public GlobalFeatures {      // features_short_shot_global.cpp:21-30, 168-249
@@ -214,6 +214,19 @@ public:
     void describe(DeviceSession& s, GlobalRegions& r) const override;    // the stored rf of a row is zeros, as for VFH
 private:
     bool m_use_color;
+};
+// features_cvfh.cpp: pcl::CVFHEstimation, angle 10 degrees, viewpoint (0, 0, 0). The one type with SEVERAL rows per region, one per smooth
+// cluster (GlobalRegions::row_off). The reference has no parameters; the three here default to PCL's metre-scale values and are this
+// port's own (a reference configuration behaves as the reference does).
+class GlobalFeaturesCVFH : public GlobalFeatures {
+public:
+    GlobalFeaturesCVFH();
+    static std::string getTypeStatic() { return "CVFH"; }
+    std::string getType() const override { return getTypeStatic(); }
+    int getDescriptorLength() const override { return ISMHIP_VFH_DIM; }
+    void describe(DeviceSession& s, GlobalRegions& r) const override;    // compacts the rows: r.desc [r.row_off.back()][308]; rf zeros
+private:
+    double m_cluster_tolerance, m_normal_radius; int m_min_points;
 };
 // one stored training row (ISMFeature of voting.cpp:586-613, 660-701)
 struct StoredGlobalFeature { unsigned classId = 0, instanceId = 0; float rf[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; std::vector<float> descriptor; float radius = 0; };
@@ -751,6 +764,8 @@ public:
     struct GlobalDump { int k = 0, dim = 0; std::vector<int32_t> region_obj, region_max; std::vector<uint32_t> n_sel; std::vector<float> centroid, radius, desc;
                         std::vector<int32_t> knn_idx; std::vector<float> knn_dist, hyp_w; std::vector<uint32_t> hyp_id;      // hyp_w / hyp_id: 2 per region
                         std::vector<uint32_t> max_off; std::vector<int32_t> max_cls, max_inst; std::vector<float> max_w, max_iw, max_pos;
+                        // rows of region r: row_off[r] .. row_off[r + 1] (one each but for CVFH); desc, knn_idx and knn_dist are per ROW
+                        std::vector<uint32_t> row_off;
                         std::vector<float> box; };   // 10 per region: position, size, rotQuat of the box made for an object without maxima, NaN where none was
     const GlobalDump& lastGlobal() const { return m_last_global; }
     void clear();
