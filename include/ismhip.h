@@ -83,7 +83,12 @@ extern "C" {
 #define ISMHIP_VFH_DIM 308         /* ismhip_global_vfh: 4 shape blocks of 45 bins + 128 viewpoint bins */
 #define ISMHIP_GASD_DIM 984        /* ismhip_global_gasd with colour: 6^3 shape bins + 4^3 cells x 12 hue bins */
 #define ISMHIP_GASD_SHAPE_DIM 512  /* without colour: the 216 shape bins followed by 296 zeros (pcl::GASDSignature512) */
-#define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot: the longest row ismhip_knn takes */
+#define ISMHIP_SHORT_CSHOT_MAX_DIM 1344 /* r_bins * e_bins * a_bins + rc_bins * ec_bins * ac_bins * hist_size of ismhip_short_cshot; also the longest row of ismhip_knn_large_k above K = 16, ismhip_knn_threshold, ismhip_knn_binary and ismhip_rank_scores */
+#define ISMHIP_KNN_MAX_DIM 2048    /* the longest row of ismhip_codebook_create, ismhip_knn (K <= 16), _ratio, _rule, ismhip_train_activate and ismhip_kmeans */
+#define ISMHIP_USC_DIM 1960        /* ismhip_usc: 14 azimuth x 14 elevation x 10 radial bins */
+#define ISMHIP_USC_AZIMUTH_BINS 14
+#define ISMHIP_USC_ELEVATION_BINS 14
+#define ISMHIP_USC_RADIAL_BINS 10
 
 typedef struct ismhip_ctx      ismhip_ctx;
 typedef struct ismhip_cloud    ismhip_cloud;
@@ -325,6 +330,41 @@ int  ismhip_keypoint_normals(ismhip_ctx* ctx, const ismhip_cloud* cloud, const u
 int  ismhip_spin_image(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
                        const float* kpx, const float* kpy, const float* kpz, const float* ax, const float* ay, const float* az,
                        float radius, int image_width, float* desc_out, uint32_t* neighbour_count_out);
+/* ---- Unique Shape Context (Features type "USC", features/features_usc.cpp -> pcl::UniqueShapeContext). PCL is external: the arithmetic
+ *      below is THIS library's definition, written from knowledge of PCL 1.10's usc.hpp; parity with PCL is unpinned. */
+/* density_out[n_pts] (cloud order): for every finite cloud point the number of finite points of the SAME object with
+ * d2 < (float)((double)density_radius * density_radius), d2 = (dx*dx + dy*dy) + dz*dz in float -- the point itself included, so at
+ * least 1; 0 for a point that is not finite. Exact and order free: the same bits for any grid cell size. Refused with
+ * ISMHIP_ERR_INVALID ("point_density: bad argument"): a missing array, a radius that is not positive or not finite. Timer "point_density". */
+int  ismhip_point_density(ismhip_ctx* ctx, const ismhip_cloud* cloud, float density_radius, uint32_t* density_out);
+/* The tables of ismhip_usc for (radius, min_radius), computed on the host in double (libm):
+ *   edges11[j]  = (float)exp(ln r_min + (j / 10.0) * ln(R / r_min)), j = 0 .. 10  (R = (double)radius, r_min = (double)min_radius)
+ *   lut140[j * 14 + k] = 1 / cbrt( (cos th_k - cos th_{k+1}) * (e_{j+1}^3 - e_j^3) / 3 * (2 pi / 14) ),  th_k = k * pi / 14, e_j the
+ *   DOUBLE edge before its rounding to float, j the radial and k the elevation bin.
+ * Either output may be NULL. Refused (ISMHIP_ERR_INVALID): radius not positive or not finite, min_radius not in (0, radius). */
+int  ismhip_usc_tables(float radius, float min_radius, double* lut140_out, float* edges11_out);
+/* desc_out[nkp * 1960] (ISMHIP_USC_DIM). Grid: 14 azimuth bins of 360/14 degrees, 14 elevation bins of 180/14 degrees, 10 radial bins
+ * with the edges of ismhip_usc_tables; bin index l * 140 + k * 10 + j (l azimuth, k elevation, j radial).
+ *  - Frame: x = lrf9[0..2], y = lrf9[3..5], z = lrf9[6..8] of the keypoint (only x and z are read). A frame with a non-finite
+ *    component, a keypoint that is not finite or a ball without a point: the WHOLE row NaN, count 0.
+ *  - Ball: the finite cloud points of the keypoint's object with d2 < (float)((double)radius * radius), as ismhip_shot352;
+ *    neighbour_count_out[nkp] (may be NULL) counts them all, the skipped ones too.
+ *  - Per ball point p, v = p - keypoint (float), from here in double on the float inputs: |v|^2 = (v.x^2 + v.y^2) + v.z^2 <= FLT_EPSILON:
+ *    skipped. r = sqrt(|v|^2); c = (z.v) / r clamped to [-1, 1], theta = acos(c) in degrees; u = v - (z.v) z; u == 0 (all three
+ *    components): phi = 0 -- NAMED DEVIATION, PCL divides by zero there; else phi = atan2(|x cross u|, x.u) in degrees, replaced by
+ *    360 - phi when (x cross u).z < 0.
+ *    j = the first radial bin whose upper edge e_{j+1} (the float of the table, widened) is not below r; k = the first with
+ *    (k + 1) * (180.0 / 14) not below theta; l = the first with (l + 1) * (360.0 / 14) not below phi. So r < r_min falls in j = 0.
+ *    A value beyond the last edge takes the LAST bin -- NAMED DEVIATION, PCL's loop leaves it in bin 0.
+ *  - Deposit: the integer q_p = (2^32 + n_p / 2) / n_p (64-bit integer division), n_p = max(1, density[p]) the point's density from
+ *    ismhip_point_density; a bin holds Q = the sum of its q_p in 64 bits. q_out[nkp * 1960] (may be NULL) receives Q (0 for a NaN row).
+ *  - Row: desc[i] = (float)((double)Q_i * 2^-32 * lut140[j * 14 + k]). No float atomics, no normalisation (the reference applies none).
+ * The row depends on neither the order of the points nor the grid: two calls give the same bits. A row is NaN throughout or finite
+ * throughout, never infinite. Balls of any size are served. Refused (ISMHIP_ERR_INVALID, "usc: bad argument"): a missing array (density
+ * included), radius not positive or not finite, min_radius not in (0, radius). Timer "usc". */
+int  ismhip_usc(ismhip_ctx* ctx, const ismhip_cloud* cloud, const uint32_t* kp_offsets_h,
+                const float* kpx, const float* kpy, const float* kpz, const float* lrf9, float radius, float min_radius,
+                const uint32_t* density, float* desc_out, uint32_t* neighbour_count_out, unsigned long long* q_out);
 /* FeaturesRSD::iComputeDescriptors (features/features_rsd.cpp:29-103) -> PCL 1.10 RSDEstimation::computeFeature / computeRSD as :41-56
  * configure it (5 subdivisions, max_dist = the search radius, plane_radius = Radius), then, for the histogram, normalizeDescriptors
  * (features/features.cpp:282-297). desc_out[nkp * 25] (ISMHIP_RSD_DIM) when full_histogram is not 0, else desc_out[nkp * 2]
@@ -840,9 +880,9 @@ int  ismhip_compact_features(ismhip_ctx* ctx, int n_obj, const uint32_t* kp_offs
  * src_index_out, if given, is 0..nkp-1) and keep_offsets_h_out = kp_offsets_h. Otherwise exactly as ismhip_compact_features.
  * THE ROW CONTRACT it rests on: a row is finite throughout or NaN throughout (invalid frame, keypoint not finite, empty
  * neighbourhood, zero norm, a NaN input reaching the histogram) -- never a finite first element with a NaN behind it, and never an
- * infinity. It covers the rows of all twelve local Features entry points: ismhip_shot352 / ismhip_bshot352 / ismhip_cshot1344 /
+ * infinity. It covers the rows of all thirteen local Features entry points: ismhip_shot352 / ismhip_bshot352 / ismhip_cshot1344 /
  * ismhip_short_shot / ismhip_short_cshot / ismhip_fpfh33 / ismhip_cospair / ismhip_spin_image / ismhip_rsd / ismhip_rift /
- * ismhip_esf_local / ismhip_cgf_raw followed by ismhip_mlp_forward. Of these, FPFH rescales its three 11-bin blocks
+ * ismhip_esf_local / ismhip_usc / ismhip_cgf_raw followed by ismhip_mlp_forward. Of these, FPFH rescales its three 11-bin blocks
  * independently, and they are NaN together; BSHOT holds no NaN at all (a NaN SHOT row is 352 ones and stays); a NaN raw CGF row gives
  * a NaN output row of the embedding, and only that row. tests/test_gpu_feature_batch.py holds every one of them to the contract on a
  * ragged batch with every kind of special row, and holds this call to ismhip_compact_features on those rows. A descriptor matrix from

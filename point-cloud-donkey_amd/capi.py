@@ -40,6 +40,7 @@ EXPORTS = [
     "ismhip_cgfw_open", "ismhip_cgfw_close", "ismhip_cgfw_layers", "ismhip_cgfw_layer", "ismhip_mlp_from_cgfw", "ismhip_rgb2lab",
     "ismhip_esf_local", "ismhip_global_gasd", "ismhip_gasd_hue_bins", "ismhip_region_mvbb", "ismhip_global_cvfh",
     "ismhip_normal_curvature", "ismhip_voxel_downsample_xyzi", "ismhip_sift3d_scale_space", "ismhip_sift3d_extrema", "ismhip_sift3d_keypoints",
+    "ismhip_point_density", "ismhip_usc_tables", "ismhip_usc",
 ]
 SIFT3D_MIN_POINTS = 25             # ISMHIP_SIFT3D_MIN_POINTS: an octave below it ends the object; also the extrema's number of neighbours
 # KeypointsVoxelGridCulling: method and type strings as the reference compares them (lower-cased; CombineFilters is case-sensitive)
@@ -491,6 +492,48 @@ def esf_local(ctx, cloud, kp_offsets, kpx, kpy, kpz, radius, n_samples=ESF_SAMPL
     ctx.check(lib().ismhip_esf_local(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), C.c_float(radius), C.c_int(int(n_samples)),
                                      C.c_uint32(int(seed) & 0xffffffff), _p(out), _p(cnt), _p(bins), _p(scale)), "ismhip_esf_local")
     extra = [t for t in (cnt, bins, scale) if t is not None]
+    return (out, *extra) if extra else out
+
+
+KNN_MAX_DIM = 2048                 # ISMHIP_KNN_MAX_DIM: the longest row of Codebook, knn (K <= 16), knn_ratio, knn_rule, train_activate, kmeans
+USC_DIM = 1960                     # ISMHIP_USC_DIM: 14 azimuth x 14 elevation x 10 radial bins
+USC_POINT_DENSITY_RADIUS = 0.1     # as ism3d.h: the value pcl::UniqueShapeContext's constructor is recalled to set; the reference leaves it there
+
+
+def point_density(ctx, cloud, density_radius):
+    """ismhip_point_density -> int32 [n_pts] in cloud order: the object's finite points within density_radius of every point, itself
+    included (0 for a point that is not finite)"""
+    torch = _torch()
+    dev = cloud._keep[0].device
+    n = int(cloud.pt_offsets[-1])
+    out = torch.zeros((n,), dtype=torch.int32, device=dev)
+    ctx.check(lib().ismhip_point_density(ctx._h, cloud._h, C.c_float(density_radius), _p(out)), "ismhip_point_density")
+    return out
+
+
+def usc_tables(radius, min_radius):
+    """ismhip_usc_tables -> (lut float64 [10, 14] by (radial, elevation) bin, edges float32 [11]); ValueError for radii ismhip_usc refuses"""
+    import numpy as np
+    lut = np.empty(140, np.float64)
+    edges = np.empty(11, np.float32)
+    rc = lib().ismhip_usc_tables(C.c_float(radius), C.c_float(min_radius), C.c_void_p(lut.ctypes.data), C.c_void_p(edges.ctypes.data))
+    if rc != 0:
+        raise ValueError(f"ismhip_usc_tables: radius {radius}, min_radius {min_radius} refused ({rc})")
+    return lut.reshape(10, 14), edges
+
+
+def usc(ctx, cloud, kp_offsets, kpx, kpy, kpz, lrf, radius, min_radius, density, want_counts=False, want_q=False):
+    """ismhip_usc in the frames lrf [nkp, 9] with the densities of point_density -> [nkp, 1960]; then, for every want_* set and in this
+    order: the neighbours per keypoint [nkp] int32 and the integer bins Q [nkp, 1960] int64"""
+    torch = _torch()
+    ko = _u32(kp_offsets)
+    n = int(ko[-1])
+    out = torch.empty((n, USC_DIM), dtype=torch.float32, device=kpx.device)
+    cnt = torch.empty((n,), dtype=torch.int32, device=kpx.device) if want_counts else None
+    q = torch.empty((n, USC_DIM), dtype=torch.int64, device=kpx.device) if want_q else None
+    ctx.check(lib().ismhip_usc(ctx._h, cloud._h, _p(ko), _p(kpx), _p(kpy), _p(kpz), _p(lrf), C.c_float(radius), C.c_float(min_radius),
+                               _p(density), _p(out), _p(cnt), _p(q)), "ismhip_usc")
+    extra = [t for t in (cnt, q) if t is not None]
     return (out, *extra) if extra else out
 
 

@@ -129,6 +129,7 @@ int ismhip_codebook_create(ismhip_ctx* ctx, int n_words, int dim, const float* w
         !vote_instance_h || n_classes <= 0 || !class_sigma_h)
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "codebook_create: bad argument");
     *out = nullptr;
+    if (dim > ISMHIP_KNN_MAX_DIM) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "codebook_create: descriptor longer than 2048 not built");
     if (vote_offsets_h[0] != 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "codebook_create: vote offsets must start at 0");
     int maxv = 0;
     for (int c = 0; c < n_words; ++c) {
@@ -181,6 +182,8 @@ int ismhip_codebook_create(ismhip_ctx* ctx, int n_words, int dim, const float* w
             b &= 0x7fffffffu; amax = b > amax ? b : amax;
         }
         cb->words_nonneg = nonneg;
+        // rows longer than 1344 floats are searched by the exact scan of knn_wide.hip alone: no 16-bit, rotated or square-root image
+        if (cb->dim_pad > ISMHIP_SHORT_CSHOT_MAX_DIM) { *out = cb; return ISMHIP_OK; }
         int rc = ism_codebook_split_bf16(ctx, cb, amax);
         if (rc != ISMHIP_OK || hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(rc != ISMHIP_OK ? rc : ISMHIP_ERR_HIP, "codebook_create: bf16 split");
         if (!ctx->codebook_light) rc = ism_codebook_build_pca(ctx, cb);

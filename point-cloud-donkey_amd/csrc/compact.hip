@@ -21,8 +21,8 @@ __global__ __launch_bounds__(256) void k_keep(int nkp, int dim, const float* __r
 }
 
 // the same decision from ONE element per row -- the 1.3 GB descriptor matrix of a 908-object batch is not read again just to be tested.
-// The row contract (include/ismhip.h, ismhip_compact_descriptor_rows): every row that one of the twelve local Features entry points
-// writes (shot, bshot, cshot, short_shot, short_cshot, fpfh, cospair, spin_image, rsd, rift, cgf_raw + mlp, esf) is finite throughout or
+// The row contract (include/ismhip.h, ismhip_compact_descriptor_rows): every row that one of the thirteen local Features entry points
+// writes (shot, bshot, cshot, short_shot, short_cshot, fpfh, cospair, spin_image, rsd, rift, cgf_raw + mlp, esf, usc) is finite throughout or
 // NaN throughout -- an invalid frame, a keypoint that is not finite, an empty neighbourhood, a zero norm; FPFH's three independently
 // rescaled blocks are NaN together. tests/test_gpu_feature_batch.py asserts it on every type's own rows and that this kernel and k_keep
 // keep the same rows. Matrices from elsewhere go through ismhip_compact_features (k_keep), which reads every element.

@@ -22,10 +22,14 @@
 #include <vector>
 
 int ism_knn_only_codebook(ismhip_ctx* ctx, int n_words, int dim, const float* words_d, ismhip_codebook** out, bool light);   // train.hip
+// knn_wide.hip: k_km_closest_wide, the kernel below for rows of 1345 .. ISMHIP_KNN_MAX_DIM floats (both are km_closest.h; why two units: there)
+void km_closest_wide_launch(hipStream_t st, unsigned grid, int n, int dim, int metric, const float* desc, const uint32_t* chosen, int step, float* closest,
+                            unsigned long long* slot);
 
 namespace {
 
 #include "functor.h"
+#include "km_closest.h"
 
 __host__ __device__ inline unsigned long long km_splitmix64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -33,31 +37,13 @@ __host__ __device__ inline unsigned long long km_splitmix64(unsigned long long x
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
-#define KM_INVALID 0xffffffffu
 #define KM_POT_BITS 40
 
-// closest[i] = min(closest[i], d(point i, centre chosen[step - 1])): one wave per point, the functor's own summation order.
-// slot[step] collects max over i of (closest bits << 32 | ~i): the farthest point, lowest index on ties (GONZALES; step 1 also
-// gives dmax0 for the k-means++ integers).
 __global__ __launch_bounds__(256) void k_km_closest(int n, int dim, int metric, const float* __restrict__ desc, const uint32_t* __restrict__ chosen, int step,
                                                     float* __restrict__ closest, unsigned long long* __restrict__ slot) {
     __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
     __shared__ unsigned long long s_best[4];
-    const uint32_t c = chosen[step - 1];
-    if (c == KM_INVALID) return;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    unsigned long long best = 0ull;
-    for (int i = blockIdx.x * 4 + wv; i < n; i += gridDim.x * 4) {
-        const float d = wave_functor(metric, desc + (size_t)i * dim, desc + (size_t)c * dim, dim, lane, s_terms[wv]);
-        float cur = closest[i];
-        if (d < cur) { cur = d; if (lane == 0) closest[i] = d; }
-        if (cur == cur) {                                             // NaN distances never lead
-            const unsigned long long key = ((unsigned long long)__float_as_uint(cur) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
-            best = key > best ? key : best;
-        }
-    }
-    best = block_max_u64(best, s_best);
-    if (threadIdx.x == 0 && best) atomicMax(&slot[step], best);
+    km_closest(n, dim, metric, desc, chosen, step, closest, slot, s_terms[threadIdx.x >> 6], s_best);
 }
 __device__ __forceinline__ unsigned long long km_pot(float d, float dmax0) {
     if (!(d > 0.f) || !(dmax0 > 0.f)) return 0ull;
@@ -212,7 +198,7 @@ extern "C" int ismhip_kmeans(ismhip_ctx* ctx, int metric, int n, int dim, const 
         (metric != ISMHIP_METRIC_L2SQ && metric != ISMHIP_METRIC_CHI2) ||
         (centers_init != ISMHIP_CENTERS_RANDOM && centers_init != ISMHIP_CENTERS_GONZALES && centers_init != ISMHIP_CENTERS_KMEANSPP))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "kmeans: bad argument");
-    if (dim > 1344) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "kmeans: descriptor longer than 1344 not built");
+    if (dim > ISMHIP_KNN_MAX_DIM) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "kmeans: descriptor longer than 2048 not built");
     if (n_clusters > n) n_clusters = n;                               // clustering_kmeans.h:69-73
     hipStream_t st = ctx->stream;
     const int k = n_clusters;
@@ -253,7 +239,8 @@ extern "C" int ismhip_kmeans(ismhip_ctx* ctx, int metric, int n, int dim, const 
     }
     ISM_HIP(ctx, hipMemcpyAsync(chosen, &first, 4, hipMemcpyHostToDevice, st));
     for (int step = 1; step < k; ++step) {
-        hipLaunchKernelGGL(k_km_closest, dim3(std::min(2048, (n + 3) / 4)), dim3(256), 0, st, n, dim, metric, desc, chosen, step, closest, slot);
+        if (dim > 1344) km_closest_wide_launch(st, (unsigned)std::min(2048, (n + 3) / 4), n, dim, metric, desc, chosen, step, closest, slot);
+        else hipLaunchKernelGGL(k_km_closest, dim3(std::min(2048, (n + 3) / 4)), dim3(256), 0, st, n, dim, metric, desc, chosen, step, closest, slot);
         if (centers_init == ISMHIP_CENTERS_KMEANSPP) {
             hipLaunchKernelGGL(k_km_block_sums, dim3(nb), dim3(256), 0, st, n, closest, slot, chosen, step, bsum);
             hipLaunchKernelGGL(k_km_select, dim3(1), dim3(1024), 0, st, n, nb, bsum, closest, slot, seed, step, chosen);

@@ -471,6 +471,8 @@ int ismhip_knn(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, c
     if (k > KNN_MAX_K) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn: k > 16 not built");
     if (nq == 0) return ISMHIP_OK;
     TimerScope ts(ctx, "knn");
+    // rows of 1345 .. ISMHIP_KNN_MAX_DIM floats (USC): the exact scan of knn_wide.hip, which needs none of the images
+    if (cb->dim_pad / 16 > KNN_FB_MAXJ) return run_knn_wide(ctx, cb, metric, nq, q, k, idx_out, dist_out);
     // T = candidates kept per slot. The bf16x3 candidate scores carry a larger error bound, so more are kept (T = 4): the proof
     // then compares against the 5th best of every slot and almost never fails.
     // (short descriptors take the exact-f32 contraction, whose scores are as good as exact: two candidates per slot are plenty)

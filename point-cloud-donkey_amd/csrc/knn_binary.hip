@@ -223,6 +223,7 @@ extern "C" {
 int ismhip_codebook_make_binary(ismhip_ctx* ctx, ismhip_codebook* cb) {
     if (!ctx || !cb || !cb->words) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "codebook_make_binary: bad argument");
     if (cb->bin_words) return ISMHIP_OK;
+    if (cb->dim_pad > ISMHIP_SHORT_CSHOT_MAX_DIM) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "codebook_make_binary: descriptor longer than 1344 not built");
     int shift = 7;
     while (shift < 31 && (1ll << shift) < (long long)cb->n_words_pad) ++shift;
     if (((long long)(cb->dim + 2) << shift) > (1ll << 31))

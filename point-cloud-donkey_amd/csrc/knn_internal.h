@@ -303,6 +303,8 @@ KnnQueue knn_queue_carve(void* mem, size_t n_queries, size_t q_items);
 // exact scan of the queued slots' rows into the unproven queries' results: one scan and one merge launch for a queue, whichever
 // searches filled it (q, idx_out, dist_out are indexed by the queue's query numbers)
 int knn_scan_queue(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int k, const float* q, int ldq, const KnnQueue& Q, const int* qrange, int32_t* idx_out, float* dist_out);
+// ---- knn_wide.hip: rows longer than KNN_TERMS floats, up to ISMHIP_KNN_MAX_DIM -- an exact scan of its own (none of the stages above) ---------
+int run_knn_wide(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric, int nq, const float* q, int k, int32_t* idx_out, float* dist_out);
 // ---- knn_two_stage.hip: the two-stage drivers; chi-square: taken = false: not histogram data, the caller takes the VALU kernel ------------
 int run_knn_two_stage(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out);
 int run_knn_chi2_hellinger(ismhip_ctx* ctx, const ismhip_codebook* cb, int nq, const float* q, int k, int32_t* idx_out, float* dist_out, bool& taken);

@@ -206,6 +206,7 @@ int ismhip_knn_threshold(ismhip_ctx* ctx, const ismhip_codebook* cb, int metric,
         (metric != ISMHIP_METRIC_L2SQ && metric != ISMHIP_METRIC_CHI2))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "knn_threshold: bad argument");
     *n_act_h_out = 0;
+    if (cb->dim_pad / 16 > KNN_FB_MAXJ) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "knn_threshold: descriptor longer than 1344 not built");
     TimerScope ts(ctx, "knn_threshold");
     if (nq == 0 || !(threshold > 0.f)) {                                  // functor values are >= 0 (or NaN): nothing is below
         ISM_HIP(ctx, hipMemsetAsync(act_offsets_out, 0, ((size_t)nq + 1) * 4, ctx->stream));

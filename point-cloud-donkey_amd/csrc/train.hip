@@ -91,19 +91,30 @@ __global__ void k_tr_tail(const uint32_t* __restrict__ n_words_p, const uint32_t
 
 // sigma sample: pair p of class c = (feature sf[f0 + p / nw], codeword act[sw[w0 + p % nw]]) in the reference's loop order
 struct SigmaClass { uint32_t f0, nf, w0, nw, d0; };      // offsets into the sample lists and the distance buffer
-__global__ __launch_bounds__(256) void k_tr_sigma_dist(int n_classes, const SigmaClass* __restrict__ sc, const uint32_t* __restrict__ sf,
-                                                       const int32_t* __restrict__ sw, int metric, const float* __restrict__ feats,
-                                                       const float* __restrict__ words, int dim, float* __restrict__ dist) {
-    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+__device__ __forceinline__ void tr_sigma_dist(const SigmaClass* __restrict__ sc, const uint32_t* __restrict__ sf, const int32_t* __restrict__ sw, int metric,
+                                              const float* __restrict__ feats, const float* __restrict__ words, int dim, float* __restrict__ dist, float* sT) {
     const int c = blockIdx.y;
     const SigmaClass s = sc[c];
     const uint32_t np = s.nf * s.nw;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     for (uint32_t p = blockIdx.x * 4 + wv; p < np; p += gridDim.x * 4) {
         const uint32_t fi = sf[s.f0 + p / s.nw]; const int w = sw[s.w0 + p % s.nw];
-        const float d = wave_functor(metric, feats + (size_t)fi * dim, words + (size_t)w * dim, dim, lane, s_terms[wv]);
+        const float d = wave_functor(metric, feats + (size_t)fi * dim, words + (size_t)w * dim, dim, lane, sT);
         if (lane == 0) dist[s.d0 + p] = d;
     }
+}
+__global__ __launch_bounds__(256) void k_tr_sigma_dist(int n_classes, const SigmaClass* __restrict__ sc, const uint32_t* __restrict__ sf,
+                                                       const int32_t* __restrict__ sw, int metric, const float* __restrict__ feats,
+                                                       const float* __restrict__ words, int dim, float* __restrict__ dist) {
+    __shared__ __attribute__((aligned(16))) float s_terms[4][1344];
+    tr_sigma_dist(sc, sf, sw, metric, feats, words, dim, dist, s_terms[threadIdx.x >> 6]);
+}
+// the same for rows of 1345 .. ISMHIP_KNN_MAX_DIM floats (a kernel of its own: the one above keeps its LDS and its occupancy)
+__global__ __launch_bounds__(256) void k_tr_sigma_dist_wide(int n_classes, const SigmaClass* __restrict__ sc, const uint32_t* __restrict__ sf,
+                                                            const int32_t* __restrict__ sw, int metric, const float* __restrict__ feats,
+                                                            const float* __restrict__ words, int dim, float* __restrict__ dist) {
+    __shared__ __attribute__((aligned(16))) float s_terms[4][ISMHIP_KNN_MAX_DIM];
+    tr_sigma_dist(sc, sf, sw, metric, feats, words, dim, dist, s_terms[threadIdx.x >> 6]);
 }
 __global__ void k_tr_sigma(int n_classes, const SigmaClass* __restrict__ sc, const float* __restrict__ dist, float* __restrict__ sigma) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -385,7 +396,8 @@ static int train_from_activations(ismhip_ctx* ctx, int metric, int n, int dim, c
             }
         }
         if (d0) {
-            hipLaunchKernelGGL(k_tr_sigma_dist, dim3(1024, n_classes), dim3(256), 0, st, n_classes, d_sc, d_sf, d_sw, metric, desc, codewords, dim, d_dist);
+            const auto sigma_dist = dim > 1344 ? k_tr_sigma_dist_wide : k_tr_sigma_dist;
+            hipLaunchKernelGGL(sigma_dist, dim3(1024, n_classes), dim3(256), 0, st, n_classes, d_sc, d_sf, d_sw, metric, desc, codewords, dim, d_dist);
         }
         hipLaunchKernelGGL(k_tr_sigma, dim3((n_classes + 63) / 64), dim3(64), 0, st, n_classes, d_sc, d_dist, sigma);
     }
@@ -430,7 +442,7 @@ static int train_from_activations(ismhip_ctx* ctx, int metric, int n, int dim, c
 }
 
 // argument checks shared by both entry points; codewords == NULL -> the features themselves (clustering_none.cpp:25-35)
-static int train_check(ismhip_ctx* ctx, int metric, int n, int dim, const float* desc, const float* lrf9, const float* kpx, const float* kpy,
+static int train_check(ismhip_ctx* ctx, int max_dim, int metric, int n, int dim, const float* desc, const float* lrf9, const float* kpx, const float* kpy,
                        const float* kpz, const uint32_t* feat_class_h, const uint32_t* feat_model_h, const float* feat_center_h, int n_classes,
                        int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out, float* vote_xyz_out,
                        float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
@@ -438,7 +450,7 @@ static int train_check(ismhip_ctx* ctx, int metric, int n, int dim, const float*
         n_classes <= 0 || !n_words_out || !word_src_out || !vote_offsets_out || !vote_feature_out || !vote_xyz_out || !vote_weight_out ||
         !vote_class_weight_out || !class_sigma_out || (metric != ISMHIP_METRIC_L2SQ && metric != ISMHIP_METRIC_CHI2))
         return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
-    if (dim > 1344) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: descriptor longer than 1344 not built");
+    if (dim > max_dim) return ism_set_err(ctx, ISMHIP_ERR_UNSUPPORTED, "train_activate: descriptor longer than " + std::to_string(max_dim) + " not built");
     for (int i = 0; i < n; ++i) {
         if ((int)feat_class_h[i] >= n_classes) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: class id out of range");
         if (i && feat_class_h[i] < feat_class_h[i - 1]) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: features must be class-major (the reference iterates classes in ascending order)");
@@ -453,7 +465,7 @@ extern "C" int ismhip_train_activate(ismhip_ctx* ctx, int metric, int n, int dim
                                      int k, int clean_up, int n_classes,
                                      int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
                                      float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
-    int rc = train_check(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
+    int rc = train_check(ctx, ISMHIP_KNN_MAX_DIM, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
                          vote_offsets_out, vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
     if (rc != ISMHIP_OK) return rc;
     if (k <= 0) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate: bad argument");
@@ -491,7 +503,8 @@ extern "C" int ismhip_train_activate_lists(ismhip_ctx* ctx, int metric, int n, i
                                            const uint32_t* act_offsets, const int32_t* act_idx, int64_t n_act, int n_classes,
                                            int32_t* n_words_out, uint32_t* word_src_out, uint32_t* vote_offsets_out, uint32_t* vote_feature_out,
                                            float* vote_xyz_out, float* vote_weight_out, float* vote_class_weight_out, float* class_sigma_out) {
-    int rc = train_check(ctx, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
+    // (the lists come from ismhip_knn_threshold, which keeps the 1344 limit)
+    int rc = train_check(ctx, ISMHIP_SHORT_CSHOT_MAX_DIM, metric, n, dim, desc, lrf9, kpx, kpy, kpz, feat_class_h, feat_model_h, feat_center_h, n_classes, n_words_out, word_src_out,
                          vote_offsets_out, vote_feature_out, vote_xyz_out, vote_weight_out, vote_class_weight_out, class_sigma_out);
     if (rc != ISMHIP_OK) return rc;
     if (!act_offsets || n_act < 0 || (n_act > 0 && !act_idx)) return ism_set_err(ctx, ISMHIP_ERR_INVALID, "train_activate_lists: bad argument");

@@ -102,6 +102,7 @@ public:
     DevBuf raw_lrf, raw_desc, raw_cnt;
     DevBuf raw_axis;      // SpinImage: the keypoints' looked-up normals, three runs of nkp floats
     DevBuf raw_grad;      // RIFT: the intensity gradient of every point of the batch, three floats each
+    DevBuf raw_usc;       // USC: the point density of every point of the batch (uint32), then the rows' own frames, nine floats per keypoint
     DevBuf cgf_lrf, cgf_normal, cgf_rows;   // CGF: its own frames, the keypoints' PCA normals (three runs of nkp floats), a chunk of raw rows
     ismhip_mlp* cgf_mlp = nullptr;          // CGF: the embedding of cgf_mlp_file on this context
     std::string cgf_mlp_file;
@@ -589,6 +590,7 @@ FeaturesRSD::FeaturesRSD() {                     // features_rsd.cpp:19-23
 }
 FeaturesRIFT::FeaturesRIFT() { addParameter(m_radius, "Radius", 0.1f); }   // features_rift.cpp:20-23
 FeaturesESFLocal::FeaturesESFLocal() { addParameter(m_radius, "Radius", 0.1f); }   // features_esf_local.cpp:21
+FeaturesUSC::FeaturesUSC() { addParameter(m_radius, "Radius", 0.1f); }             // features_usc.cpp:20-23
 FeaturesCGF::FeaturesCGF() {                     // features_cgf.cpp:22-25
     addParameter(m_radius, "Radius", 0.1f);
     addParameter(m_model_file, "CgfModelFile", std::string("embed_model_910000.cgfw"));
@@ -670,6 +672,19 @@ void FeaturesRIFT::iComputeDescriptors(DeviceSession& s, const float*, float* de
 void FeaturesESFLocal::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
     s.check(ismhip_esf_local(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), m_radius, ISMHIP_ESF_SAMPLES,
                              ISMHIP_ESF_SEED, desc_out, counts_out, nullptr, nullptr), "ismhip_esf_local");
+}
+// features_usc.cpp:28-75: the density of the cloud's points once, PCL's own frames (SHOT frames at Radius - 0.1, :52-54; lrf9, the frames
+// of ReferenceFrameType, only decided which keypoints stay), then the rows with the minimal radius Radius / 10 (:50)
+void FeaturesUSC::iComputeDescriptors(DeviceSession& s, const float*, float* desc_out, uint32_t* counts_out) const {
+    const size_t n_pts = std::max<size_t>(s.pt_off.back(), 1), nkp = s.kp_off.back();
+    s.raw_usc.reserve(n_pts * 4 + nkp * 9 * 4);
+    uint32_t* density = s.raw_usc.as<uint32_t>();
+    float* frames = (float*)(density + n_pts);
+    s.check(ismhip_point_density(s.ctx, s.cloud, USC_POINT_DENSITY_RADIUS, density), "ismhip_point_density");
+    const float frame_radius = m_radius <= 0.1f ? 0.1f : m_radius - 0.1f;
+    s.check(ismhip_shot_lrf(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), frame_radius, frames), "ismhip_shot_lrf");
+    s.check(ismhip_usc(s.ctx, s.cloud, s.kp_off.data(), s.kx.as<float>(), s.ky.as<float>(), s.kz.as<float>(), frames, m_radius, m_radius / 10.0f, density,
+                       desc_out, counts_out, nullptr), "ismhip_usc");
 }
 
 // features_cgf.cpp:46-68 -> cgf.cpp:64-165 and embedding.py: the three lengths after their trip through std::to_string, CGF's own frames and
@@ -1827,7 +1842,8 @@ template <> Features* Factory<Features>::createByType(const std::string& type) {
     if (type == FeaturesRIFT::getTypeStatic()) return new FeaturesRIFT();
     if (type == FeaturesCGF::getTypeStatic()) return new FeaturesCGF();
     if (type == FeaturesESFLocal::getTypeStatic()) return new FeaturesESFLocal();
-    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR)");
+    if (type == FeaturesUSC::getTypeStatic()) return new FeaturesUSC();
+    throw RuntimeException("feature type \"" + type + "\" is outside the MI355X hot path (built: SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR) and USC");
 }
 template <> Keypoints* Factory<Keypoints>::createByType(const std::string& type) {
     if (type == KeypointsVoxelGrid::getTypeStatic()) return new KeypointsVoxelGrid();
@@ -2076,6 +2092,21 @@ bool ImplicitShapeModel::iChildConfigsFromJson(const Json& c) {   // :1085-1142
         }
     }
     if (m_voting) m_voting->setGlobalFeatureDescriptor(m_global_descriptor.get());
+    // rows longer than ISMHIP_SHORT_CSHOT_MAX_DIM (USC, 1960 floats) are served by ismhip_knn up to K = 16, ismhip_train_activate and
+    // ismhip_kmeans only (ISMHIP_KNN_MAX_DIM); the radius search, the large-K search and the ranking scores keep the shorter limit
+    if (m_feature_descriptor && m_feature_descriptor->getDescriptorLength() > ISMHIP_SHORT_CSHOT_MAX_DIM) {
+        const std::string ft_type = m_feature_descriptor->getType(), len = std::to_string(m_feature_descriptor->getDescriptorLength());
+        const ActivationStrategy* as = m_codebook ? m_codebook->getActivationStrategy() : nullptr;
+        if (as && as->getType() == ActivationStrategyThreshold::getTypeStatic())
+            throw RuntimeException("ActivationStrategy \"Threshold\" with Features type \"" + ft_type + "\" is not built (ismhip_knn_threshold takes rows up to " +
+                                   std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + " floats, " + ft_type + " has " + len + ")");
+        if (as && as->getK() > 16)
+            throw RuntimeException("ActivationStrategy K " + std::to_string(as->getK()) + " with Features type \"" + ft_type + "\" is not built (rows of " + len +
+                                   " floats are searched up to K = 16)");
+        if (m_feature_ranking && m_feature_ranking->ranks())
+            throw RuntimeException("FeatureWeighting \"" + m_feature_ranking->getType() + "\" with Features type \"" + ft_type + "\" is not built (ismhip_rank_scores takes rows up to " +
+                                   std::to_string(ISMHIP_SHORT_CSHOT_MAX_DIM) + " floats; built: Uniform)");
+    }
     if (m_use_smoothing || m_use_voxel_filtering) throw RuntimeException("point cloud pre-filters smoothing (UseSmoothing) and voxel filtering (UseVoxelFiltering) are not built");
     if (m_use_sor && (m_sor_mean_k < 1 || m_sor_mean_k > ISMHIP_SOR_MAX_MEAN_K))
         throw RuntimeException("OutlierRemovalMeanK " + std::to_string(m_sor_mean_k) + " is not built (built: 1 .. " + std::to_string(ISMHIP_SOR_MAX_MEAN_K) + ")");

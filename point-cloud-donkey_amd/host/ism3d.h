@@ -4,7 +4,7 @@
 // (paths relative to /root/reference/src/implicit_shape_model):
 //   JSONObject / JSONParameter / Factory<T>      utils/json_object.h:31-103, utils/factory.h:20-53
 //   Exception hierarchy                          utils/exception.h:21-88
-//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT/CGF/ESF_LOCAL   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp, features_cgf.cpp, features_esf_local.cpp
+//   Features + SHOT/CSHOT/FPFH/SHORT_SHOT/SHORT_CSHOT/CoSPAIR/BSHOT/SpinImage/RSD/RIFT/CGF/ESF_LOCAL/USC   features/features.h:31-112, features_shot.cpp, features_cshot.cpp, features_fpfh.cpp, features_short_shot.cpp, features_short_cshot.cpp, features_cospair.cpp, features_bshot.cpp, features_spin_image.cpp, features_rsd.cpp, features_rift.cpp, features_cgf.cpp, features_esf_local.cpp, features_usc.cpp
 //   Keypoints + VoxelGrid                        keypoints/keypoints.h:31-86, keypoints_voxel_grid.cpp:30-46
 //   ActivationStrategy(KNN), Codebook            activation_strategy/*.h, codebook/codebook.h:50
 //   FeatureRanking + KNNActivation/Incremental/Strangeness/NaiveBayes/Uniform   feature_ranking/feature_ranking.h, ranking_*.cpp, ranking_factory.h
@@ -380,6 +380,16 @@ ISM3D_FEATURE(FeaturesBSHOT, "BSHOT", ISMHIP_BSHOT_DIM, false)
 // the keypoint coincides with, 153 floats; a keypoint that is no cloud point gets the zero axis, as in the reference (DESIGN.md section
 // 4.15), so the type wants keypoints taken from the cloud (ISS3D). The frames only decide which keypoints stay; centerDist is not set.
 ISM3D_FEATURE(FeaturesSpinImage, "SpinImage", ISMHIP_SPIN_IMAGE_DIM, false)
+// features/features_usc.{h,cpp} -> pcl::UniqueShapeContext (ismhip_point_density, ismhip_usc): 14 x 14 x 10 bins of
+// the Radius ball in PCL's own frame, every point weighted by the bin's volume and the point's density, 1960 floats, not normalised.
+// Radius is the one parameter; the minimal radius is Radius / 10 and the frames of the rows are SHOT frames at Radius - 0.1 (0.1 when
+// Radius <= 0.1), computed apart from ReferenceFrameType / ReferenceFrameRadius (features_usc.cpp:46-54); the frames kept with the
+// features for voting stay the base class's. Rows of this length are searched by ismhip_knn's exact wide scan only: the Threshold
+// activation, KNN with K > 16 and a FeatureWeighting other than Uniform are refused when the configuration is read.
+ISM3D_FEATURE(FeaturesUSC, "USC", ISMHIP_USC_DIM, false)
+// The one value features_usc.cpp leaves to pcl::UniqueShapeContext's constructor: the radius of the point density. 0.1 AS RECALLED from
+// PCL 1.10's usc.h (PCL is not part of the reference tree, so the value is unpinned); change it here and in capi.py if PCL says otherwise.
+constexpr float USC_POINT_DENSITY_RADIUS = 0.1f;
 // features/features_short_shot.{h,cpp}: the generalised Short SHOT. Not an ISM3D_FEATURE: its length follows the spherical grid.
 class FeaturesSHORTSHOT : public Features {
 public:

@@ -105,7 +105,7 @@ class IsmConfig:
         if self.feature == "CGF":
             return capi.cgfw_read(self.cgf_model, capi.CGF_RAW_DIM)[-1][0].shape[1]      # D is the file's (32 or 40 in the reference's models)
         return {"SHOT": 352, "BSHOT": 352, "CSHOT": 1344, "FPFH": 33, "CoSPAIR": capi.COSPAIR_DIM, "SpinImage": capi.SPIN_IMAGE_DIM, "RIFT": capi.RIFT_DIM,
-                "ESF_LOCAL": capi.ESF_DIM}[self.feature]
+                "ESF_LOCAL": capi.ESF_DIM, "USC": capi.USC_DIM}[self.feature]
 
     @property
     def metric(self):
@@ -253,8 +253,14 @@ class Recognizer:
             # no normal, no colour and no frame enters the descriptor: point triples of the ball and their lines through its occupancy
             # grid (features_esf_local.cpp); the sample count and the seed are the library's constants, for train() and detect() alike
             desc, cnt = capi.esf_local(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, c.radius, want_counts=True)
+        elif c.feature == "USC":
+            # features_usc.cpp:46-54: min radius Radius / 10, frames of PCL's own (SHOT frames at Radius - 0.1, or 0.1 when Radius <= 0.1)
+            # whatever lrf_type says; the frames kept with the features for voting stay the base class's. The point density once per cloud.
+            usc_lrf = capi.shot_lrf(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, 0.1 if c.radius <= 0.1 else c.radius - 0.1)
+            density = capi.point_density(ctx, cloud, capi.USC_POINT_DENSITY_RADIUS)
+            desc, cnt = capi.usc(ctx, cloud, b.kp_off, b.kx, b.ky, b.kz, usc_lrf, c.radius, c.radius / 10.0, density, want_counts=True)
         else:
-            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR)")
+            raise capi.IsmHipError(f"feature {c.feature!r} is not built (SHOT, BSHOT, CSHOT, FPFH, SHORT_SHOT, SHORT_CSHOT, ESF_LOCAL, CGF, RIFT, SpinImage, RSD, CoSPAIR, USC)")
         keep, desc, lrf, kx, ky, kz, src = capi.compact_descriptor_rows(ctx, b.kp_off, desc, lrf, b.kx, b.ky, b.kz)
         out = dict(off=keep, desc=desc, lrf=lrf, kx=kx, ky=ky, kz=kz, src=src, cloud=cloud)
         if want_counts:
